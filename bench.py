@@ -1,10 +1,22 @@
 #!/usr/bin/env python3
 """bench.py -- particle-steps/s and achieved HBM GB/s of the photon time-step hot path on MI355X.
 
-    python bench.py                                        (N=1; 64 steps per block, 5 blocks, 32 warm-up steps)
+    python bench.py                                        (N=1; 32 warm-up steps, then ONE timed block of 64 steps)
     python bench.py --gpus N --steps K --warmup W          (N > 1: starts its own N ranks, one per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W          (same thing, ranks started by torchrun)
+    python bench.py --full ...                             (everything else the bench measures: see below)
+    python bench.py --dump-outputs DIR ...                 (also writes what the timed path computed: see below)
+
+A plain run does only what the headline needs: it fills the store, runs W warm-up steps, times ONE block of exactly K
+steps (`ms_per_step` = that block's time / K; --repeats R > 1 times R such blocks and reports the median one), writes its
+outputs if --dump-outputs is given, and prints the line.  --full adds, as before: five timed blocks by default (median
+reported), the single_step / tame / delete / iso_1e7 / mixed / api legs and the CPU baselines (N = 1).
+
+--dump-outputs DIR, after the timed steps: DIR/counters.npy = the last timed step's counter row [N, hits, xp, yp, zp]
+(summed over ranks, float64); DIR/r.npy, v.npy (n x 3), E.npy and id.npy (n) = rank 0's photons after that step, in the
+store's precision (ids as float64) -- all of them up to 2^19, else a fixed sample of 128 blocks of 4096 consecutive slots
+(offsets from a fixed seed).  Same arguments, same inputs: the photons are filled from --seed, Philox keyed by photon id.
 
 Workload (BASELINE.json configs[2], the config the metric is quoted on; weak-scaled = configs[3]):
 1e8 photons per GPU, r = 0, v = (c,0,0), E power-law between E(700 nm) and E(200 nm)
@@ -15,28 +27,31 @@ One "step" = one pass of the Simulation loop body (physicl/__init__.py:512-516):
 UpdateTimeStep -> NewtonianKinematicsStep -> ScatterIsotropicStep -> ScatterSignMeasureStep counters,
 then (N > 1) an RCCL all-reduce of the counter vector [N, hits, xp, yp, zp].
 
-Timing: W warm-up steps, then the block of exactly K steps is timed R times (--repeats, default 5), each block
-bracketed by barrier + device synchronise on both sides and reduced with MAX over ranks; `value` uses the MEDIAN
-block (every block's time is in `repeat_ms_per_step`).  The simulation simply keeps running from block to block.
+Timing: W warm-up steps, then the block of exactly K steps is timed R times (--repeats: 1 by default, 5 with --full),
+each block bracketed by barrier + device synchronise on both sides and reduced with MAX over ranks; `value` uses the
+MEDIAN block (every block's time is in `repeat_ms_per_step`).  The simulation simply keeps running from block to block.
+The hit fraction, and with it the time per step, falls over the first ~100 steps (0.57 -> 0.34 ms per step over five
+20-step blocks after 5 warm-up steps, flat at ~0.31 from there on): a plain run with a small K times those early steps,
+where --full's median block is a later one.
 
 Default mode "fused" with --steps-per-launch S > 1 runs S consecutive loop bodies per pass over the store
 (pcl_step_fused_multi: photons do not interact, so a photon is loaded once, stepped S times in registers and
 stored once -- bit-identical state and per-step counters, 128/S instead of 104 B of HBM traffic per
 particle-step, which turns the step from HBM-bound into VALU-bound).  The K timed steps are ceil(K/S) launches.
 --steps-per-launch 1 is the one-launch-per-step, HBM-bound path; with N=1 it is also measured in the same run
-and reported under "single_step", and the delete/compaction path (BASELINE configs[1](ii)) under "delete".
+and reported under "single_step" (--full), and the delete/compaction path (BASELINE configs[1](ii)) under "delete".
 
 Prints ONE JSON line on rank 0.  Every number in `roofline`, `single_step`, `delete`, `iso_1e7`, `mixed` and `api` is
 measured in THIS run (wall clock, and HIP event pairs recorded on the library's stream around every launch,
 pcl_prof_*); PMC-counter figures from committed rocprofv3 profiles appear only under `static_profile`, labelled with
-their source.  `roofline` refers to the MEDIAN block, the one `value` is taken from.  With N=1 the other BASELINE
+their source.  `roofline` refers to the MEDIAN block, the one `value` is taken from.  With N=1 and --full the other BASELINE
 configurations ride along: `delete` = configs[1](ii) at 1e7 and 1e8 (one call per loop body on the store's alive mask,
 and K bodies per launch), `iso_1e7` = configs[1](i), `mixed` = configs[4] in its 1-GPU form (fp64 and fp32, with the
 fp32-vs-fp64 error figures), `api` = configs[2]'s 500 passes through physicl_amd.Simulation with the constructor exactly
 as a script written against the reference calls it.  `--gpus N --dry-run` brings the ranks and the collective up and
 stops.
 `cpu_baseline` = the oracle's C/OpenMP port of the same step timed on this box's host cores on a
-bounded sample of the same photons (rank 0, N=1 only).
+bounded sample of the same photons (rank 0, N=1 and --full only).
 """
 import argparse
 import json
@@ -98,7 +113,13 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--warmup", type=int, default=32)
-    ap.add_argument("--repeats", type=int, default=5, help="how many times the block of --steps steps is timed (median reported)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="how many times the block of --steps steps is timed (median reported; default 1, 5 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: five timed blocks by default, the single_step, tame, delete, "
+                         "iso_1e7, mixed and api legs and the CPU baselines (N = 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy")
     ap.add_argument("--photons", type=float, default=1e8, help="photons PER GPU (weak scaling)")
     ap.add_argument("--profile", choices=sorted(PROFILES), default="example")
     ap.add_argument("--mode", choices=("fused", "fused-eager", "separate"), default="fused",
@@ -119,8 +140,8 @@ def parse_args(argv=None):
     ap.add_argument("--dry-run", action="store_true",
                     help="bring up the ranks, the collective backend and its start-up all-reduce, report every rank's "
                          "device and stop: nothing is allocated, nothing is timed")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the single_step, delete and api legs (N=1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the single_step, delete and api legs (N=1)")
     ap.add_argument("--cpu-photons", type=float, default=1e8)
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="target duration of the OpenMP CPU baseline")
     ap.add_argument("--delete-photons", type=str, default="1e7,1e8", help="sizes of the delete leg (comma separated)")
@@ -129,7 +150,10 @@ def parse_args(argv=None):
                          "else --steps)")
     ap.add_argument("--iso-photons", type=float, default=1e7, help="size of the iso_1e7 leg (BASELINE configs[1](i))")
     ap.add_argument("--mixed-photons", type=float, default=1e8, help="size of the mixed leg (BASELINE configs[4], 1-GPU form)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    return args
 
 
 def main():
@@ -291,6 +315,38 @@ class Bench:
             k += steps
         dev.prof_enable(False)
         return el, hits, kern, k
+
+
+DUMP_SAMPLE, DUMP_BLOCK, DUMP_SEED = 1 << 19, 4096, 20240611   # 2^19 photons x 8 float64 values = 32 MiB at most
+
+
+def dump_outputs(b, path):
+    """--dump-outputs: what the timed path computed in its last step, as ``path``/<name>.npy -- the counter row of that step
+    summed over ranks, and rank 0's photons (r, v, E, id) as the store holds them after it: all of them up to DUMP_SAMPLE,
+    else DUMP_SAMPLE / DUMP_BLOCK blocks of DUMP_BLOCK consecutive slots at offsets drawn from DUMP_SEED (the same blocks for
+    the same --photons).  Outside the timed region; the store is only read."""
+    if b.rank != 0:
+        return
+    dev, hip = b.dev, b.hip
+    n = dev.count
+    if n <= DUMP_SAMPLE:
+        starts, blk = [0], n
+    else:
+        rs = np.random.RandomState(DUMP_SEED)
+        starts = np.sort(rs.choice(n // DUMP_BLOCK, DUMP_SAMPLE // DUMP_BLOCK, replace=False)) * DUMP_BLOCK
+        blk = DUMP_BLOCK
+
+    def gather(fetch):
+        return np.concatenate([fetch(blk, int(s)) for s in starts])
+
+    out = {"counters": np.asarray(b.totals, dtype=np.float64),
+           "r": np.stack([gather(lambda m, s, f=f: dev.download(f, m, s)) for f in (hip.R0, hip.R1, hip.R2)], 1),
+           "v": np.stack([gather(lambda m, s, f=f: dev.download(f, m, s)) for f in (hip.V0, hip.V1, hip.V2)], 1),
+           "E": gather(lambda m, s: dev.download(hip.E, m, s)),
+           "id": gather(lambda m, s: dev.download_ids(m, s)).astype(np.float64)}
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
 
 
 def tame_leg(b, args, R):
@@ -553,6 +609,8 @@ def run_rank(args):
 
     R = max(1, args.repeats)
     el, hits, kern, k_next = b.timed_blocks(args.warmup, args.steps, R)
+    if args.dump_outputs:              # (before the legs below move the store on)
+        dump_outputs(b, args.dump_outputs)
     b.log_rows = False                 # (the legs below run other formulations / profiles on the same store)
     b.block_work_main = b.block_work
     totals_main = b.totals
@@ -569,7 +627,7 @@ def run_rank(args):
     steps_per_timed_launch = args.steps / max(1, kb["launches"]) if S > 1 else 1.0
 
     single = delete = api = None
-    extra = world == 1 and not args.no_extra
+    extra = args.full and world == 1 and not args.no_extra
     if extra and S > 1:
         # the one-launch-per-step path on the same store, same run: the HBM-bound kernel's own roofline line
         b.run_steps(k_next, k_next + 3, S=1)
@@ -666,7 +724,8 @@ def run_rank(args):
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
             "repeats": R, "repeat_ms_per_step": [round(e / args.steps * 1e3, 5) for e in el],
-            "repeat_hit_fraction": [round(h, 6) for h in h_blocks], "timing": "median of %d blocks of %d steps" % (R, args.steps),
+            "repeat_hit_fraction": [round(h, 6) for h in h_blocks],
+            "timing": "median of %d blocks of %d steps" % (R, args.steps) if R > 1 else "one block of %d steps" % args.steps,
             "config": {"workload": "BASELINE configs[2]%s: %.0e photons/GPU, variable-n + wavelength isotropic "
                                    "scatter (variable_n_scattering example); step = UpdateTime + Newton + "
                                    "ScatterIsotropic (Philox) + sign counters%s"
@@ -720,7 +779,7 @@ def run_rank(args):
             out["mixed"] = mixed
         if api is not None:
             out["api"] = api
-        if world == 1 and not args.no_cpu_baseline and not f32:
+        if args.full and world == 1 and not args.no_cpu_baseline and not f32:
             dev2 = hip.Device(b.dev_index)
             try:
                 out["cpu_baseline"] = cpu_baseline(dev2, args, prof, b.rows_log)

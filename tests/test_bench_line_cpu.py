@@ -6,6 +6,7 @@ import importlib.util
 import json
 import os
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -73,3 +74,63 @@ def test_detail_file_is_written_atomically_and_is_the_full_record(tmp_path, monk
     rel = b.write_detail(rec)
     assert json.load(open(tmp_path / "d.json")) == rec and rel.endswith("d.json")
     assert not [p for p in os.listdir(tmp_path) if ".tmp" in p]
+
+
+def test_a_plain_run_times_one_block_and_full_keeps_five():
+    b = bench_module()
+    a = b.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and a.repeats == 1 and not a.full and a.dump_outputs is None
+    assert b.parse_args(["--full"]).repeats == 5 and b.parse_args(["--full", "--repeats", "2"]).repeats == 2
+    assert b.parse_args(["--dump-outputs", "out"]).dump_outputs == "out"
+
+
+class _FakeStore:
+    """The four calls dump_outputs makes, on host arrays: field f of slot i holds f * 1e9 + i, ids are id_base + i."""
+
+    def __init__(self, n, id_base=0):
+        self.count, self.id_base = n, id_base
+
+    def download(self, field, n, offset):
+        assert 0 <= offset and offset + n <= self.count
+        return field * 1e9 + np.arange(offset, offset + n, dtype=np.float64)
+
+    def download_ids(self, n, offset):
+        assert 0 <= offset and offset + n <= self.count
+        return self.id_base + np.arange(offset, offset + n, dtype=np.int64)
+
+
+class _FakeBench:
+    def __init__(self, n, rank=0):
+        from types import SimpleNamespace
+        self.rank, self.dev, self.totals = rank, _FakeStore(n), np.array([n, 7, 1, 2, 3], dtype=np.int64)
+        self.hip = SimpleNamespace(R0=0, R1=1, R2=2, V0=3, V1=4, V2=5, E=12)
+
+
+def _dumped(path):
+    return {f[:-4]: np.load(os.path.join(path, f)) for f in sorted(os.listdir(path))}
+
+
+def test_dump_outputs_writes_every_photon_of_a_small_store(tmp_path):
+    b = bench_module()
+    b.dump_outputs(_FakeBench(1000), str(tmp_path / "d"))
+    d = _dumped(tmp_path / "d")
+    assert sorted(d) == ["E", "counters", "id", "r", "v"] and all(a.dtype == np.float64 for a in d.values())
+    assert list(d["counters"]) == [1000, 7, 1, 2, 3]
+    assert np.array_equal(d["id"], np.arange(1000)) and d["r"].shape == d["v"].shape == (1000, 3)
+    assert np.array_equal(d["v"][:, 1], 4e9 + np.arange(1000)) and np.array_equal(d["E"], 12e9 + np.arange(1000))
+
+
+def test_dump_outputs_samples_a_big_store_the_same_way_every_time(tmp_path):
+    """1e8 photons: a fixed sample of whole blocks, rows of the same slots in every array, at most 64 MB in all."""
+    b = bench_module()
+    b.dump_outputs(_FakeBench(100_000_000), str(tmp_path / "a"))
+    b.dump_outputs(_FakeBench(100_000_000), str(tmp_path / "b"))
+    b.dump_outputs(_FakeBench(100_000_000, rank=1), str(tmp_path / "c"))        # only rank 0 writes
+    a, again = _dumped(tmp_path / "a"), _dumped(tmp_path / "b")
+    assert not os.path.exists(tmp_path / "c")
+    assert all(np.array_equal(a[k], again[k]) for k in a)
+    ids = a["id"]
+    assert len(ids) == b.DUMP_SAMPLE and len(np.unique(ids)) == len(ids) and np.all(np.diff(ids) > 0)
+    assert np.all(ids[::b.DUMP_BLOCK] % b.DUMP_BLOCK == 0) and ids[-1] < 100_000_000
+    assert np.array_equal(a["r"][:, 2] - 2e9, ids) and np.array_equal(a["E"] - 12e9, ids)
+    assert sum(os.path.getsize(os.path.join(tmp_path, "a", f)) for f in os.listdir(tmp_path / "a")) <= 64 << 20

@@ -33,11 +33,11 @@ def check_line(stdout, only_line=True):
 
 
 def run_bench(*extra, photons="300000"):
-    """Runs bench.py, checks the stdout line as the driver would read it, and returns the run's FULL record (the detail
+    """Runs bench.py --full, checks the stdout line as the driver would read it, and returns the run's FULL record (the detail
     file bench.py writes beside the line) with the parsed line under "_line"."""
     with tempfile.TemporaryDirectory() as tmp:
         detail = os.path.join(tmp, "bench_detail.json")
-        out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--photons", photons, "--steps", "6",
+        out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--photons", photons, "--steps", "6",
                                        "--warmup", "3", "--repeats", "3", "--cpu-photons", "20000", "--cpu-seconds", "0.5",
                                        "--delete-photons", "30000", "--iso-photons", "30000",
                                        "--mixed-photons", "30000", *extra], cwd=ROOT, env=dict(os.environ, PCL_BENCH_DETAIL=detail),

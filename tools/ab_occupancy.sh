@@ -2,7 +2,7 @@
 #   tools/ab_occupancy.sh        -> gpurun_out/occ_<tag>_<rep>.json
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 O=gpurun_out
-run() { PCL_BENCH_DETAIL=$O/occ_$1.json timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-extra --no-cpu-baseline > $O/occ_$1.line 2> /dev/null; }
+run() { PCL_BENCH_DETAIL=$O/occ_$1.json timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-extra --no-cpu-baseline > $O/occ_$1.line 2> /dev/null; }
 for rep in 1 2; do
   run A_$rep &&
   PCL_RTC_DEFINE="-DPCL_MULTI2_ATTR=__attribute__((amdgpu_waves_per_eu(5,5)))" run B_$rep &&

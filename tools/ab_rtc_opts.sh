@@ -7,7 +7,7 @@ for rep in 1 2; do
   i=0
   for opts in "$@"; do
     i=$((i+1))
-    PCL_RTC_DEFINE="$opts" PCL_BENCH_DETAIL=$O/rtcopt_${i}_$rep.json timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-extra --no-cpu-baseline > $O/rtcopt_${i}_$rep.line 2> /dev/null || { echo "failed: $opts"; continue; }
+    PCL_RTC_DEFINE="$opts" PCL_BENCH_DETAIL=$O/rtcopt_${i}_$rep.json timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-extra --no-cpu-baseline > $O/rtcopt_${i}_$rep.line 2> /dev/null || { echo "failed: $opts"; continue; }
     python - "$opts" $O/rtcopt_${i}_$rep.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[2]))

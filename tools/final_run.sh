@@ -13,9 +13,9 @@ profiles)
   bash tools/prof_driver_cmd.sh r06_driver_cmd && bash tools/prof_driver_cmd.sh r06_default_cmd --gpus 1 && bash tools/prof_calib_ahead.sh > $O/r06_calib.log 2>&1
   ;;
 lines)
-  python bench.py --gpus 1 --steps 20 --warmup 5 > $O/r06_line_driver.json 2>/dev/null && cp bench_detail.json $O/r06_detail_driver.json &&
-  python bench.py > $O/r06_line_default.json 2>/dev/null && cp bench_detail.json $O/r06_detail_default.json &&
-  python bench.py --gpus 2 --backend gloo --device 0 --photons 5e7 --steps 20 --warmup 5 > $O/r06_line_2rank.json 2>/dev/null && cp bench_detail.json $O/r06_detail_2rank.json
+  python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/r06_line_driver.json 2>/dev/null && cp bench_detail.json $O/r06_detail_driver.json &&
+  python bench.py --full > $O/r06_line_default.json 2>/dev/null && cp bench_detail.json $O/r06_detail_default.json &&
+  python bench.py --full --gpus 2 --backend gloo --device 0 --photons 5e7 --steps 20 --warmup 5 > $O/r06_line_2rank.json 2>/dev/null && cp bench_detail.json $O/r06_detail_2rank.json
   rc=$?; wc -c $O/r06_line_*.json; exit $rc
   ;;
 *) echo "usage: tools/final_run.sh profiles|lines"; exit 2;;
