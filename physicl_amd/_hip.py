@@ -239,6 +239,55 @@ def _host(a, dtype):
     return a, a.ctypes.data_as(c_void_p)
 
 
+# ---------------------------------------------------------------- what every fused step takes and answers
+# A counter row, one per light step per pass: int64 [N, sign x 3, planes ..., hits | removed].  This is the one layout; the
+# host layer (physicl_amd/core.py) reads rows through _split_rows and knows no column numbers of its own.
+_EVENT = -1               # the last column; CNT_N .. CNT_PLANE0 above name the others
+_PHASES = {"iso": PHASE_ISOTROPIC, "delete": PHASE_DELETE}
+
+
+def _split_rows(rows):
+    """(N, sign x 3, planes, hits | removed) of one counter row or of a block of them: views of ``rows``."""
+    return rows[..., CNT_N], rows[..., CNT_XP:CNT_PLANE0], rows[..., CNT_PLANE0:_EVENT], rows[..., _EVENT]
+
+
+def _row_dict(row, event):
+    """A counter row in its dict form (arrays of its own); ``event`` names the last column ("hits" / "removed")."""
+    n, sign, planes, last = _split_rows(row)
+    return {"N": int(n), "sign": sign.copy(), "planes": planes.copy(), event: int(last)}
+
+
+def _planes(planes, off=False):
+    """Measure planes -> (the float64 array the caller keeps alive over the call, its address or None, n_planes).  A ready
+    array (C-contiguous, 2-D, float64: a loop hands the same one over every body) is taken as it is; no planes are a NULL
+    pointer; ``None`` means "counters off" (n_planes = -1) where the entry point has that (``off``)."""
+    if planes is None and off:
+        return None, None, -1
+    if type(planes) is np.ndarray and planes.dtype == np.float64 and planes.ndim == 2 and planes.flags.c_contiguous:
+        pl = planes
+    else:
+        pl = np.ascontiguousarray(np.asarray(planes, dtype=np.float64).reshape(-1, 3))
+    return pl, (pl.ctypes.data if len(pl) else None), len(pl)
+
+
+def _scatter(sc, required=False, lazy=False, empty_expr=b""):
+    """The scatter constants of a dict, in ABI order: A, n, flags, c, h, n_expr.  Missing keys are zeros, but A and n raise
+    KeyError where the entry point has no "no scatter" form (``required``).  ``empty_expr``: what an empty expression goes
+    over as (see DeviceGroup)."""
+    A, n = (sc["A"], sc["n"]) if required else (sc.get("A", 0.0), sc.get("n", 0.0))
+    expr = sc.get("n_expr")
+    return (float(A), float(n), int(sc.get("flags", 0)) | (FUSED_LAZY if lazy else 0), float(sc.get("c", 0.0)),
+            float(sc.get("h", 0.0)), None if expr is None else expr.encode() if expr else empty_expr)
+
+
+def _phase_kinds(phases):
+    return np.array([_PHASES[p] for p in phases], dtype=np.int32)
+
+
+def _rows_out(n_rows, n_planes):
+    return np.zeros((n_rows, 5 + max(n_planes, 0)), dtype=np.int64)
+
+
 class DeviceArray:
     """Raw device allocation for Level-1 callers (what cl_array.to_device / cl_array.empty gave)."""
 
@@ -616,23 +665,12 @@ class Device:
         seed, step), then counters if ``planes`` is not None (sequence of [x,y,z] rows, may be empty).
         Returns {'N','sign','planes','hits'} when counters are on and sync, else None."""
         sc = scatter or {}
-        if planes is None:
-            npl, pp, out, op = -1, None, None, None
-        else:
-            pl = np.ascontiguousarray(np.asarray(planes, dtype=np.float64).reshape(-1, 3))
-            npl = len(pl)
-            pp = pl.ctypes.data_as(c_void_p) if npl else None
-            out = np.zeros(5 + npl, dtype=np.int64) if sync else None
-            op = out.ctypes.data_as(c_void_p) if sync else None
-        expr = sc.get("n_expr")
+        pl, pp, npl = _planes(planes, off=True)
+        out = _rows_out(1, npl)[0] if sync and npl >= 0 else None
         check(self.lib.pcl_step_fused(
-            self.ctx, float(dt), 1 if scatter else 0, float(sc.get("A", 0.0)), float(sc.get("n", 0.0)),
-            int(sc.get("flags", 0)) | (FUSED_LAZY if lazy else 0), float(sc.get("c", 0.0)), float(sc.get("h", 0.0)),
-            expr.encode() if expr is not None else None, int(sc.get("rng_mode", RNG_PHILOX)), int(sc.get("seed", 0)),
-            int(sc.get("step", 0)) & 0xFFFFFFFF, pp, npl, op))
-        if out is None:
-            return None
-        return {"N": int(out[0]), "sign": out[1:4].copy(), "planes": out[4:4 + npl].copy(), "hits": int(out[4 + npl])}
+            self.ctx, float(dt), 1 if scatter else 0, *_scatter(sc, lazy=lazy), int(sc.get("rng_mode", RNG_PHILOX)),
+            int(sc.get("seed", 0)), int(sc.get("step", 0)) & 0xFFFFFFFF, pp, npl, None if out is None else out.ctypes.data))
+        return None if out is None else _row_dict(out, "hits")
 
     def is_uniform(self):
         """All photons with implicit ids: eligible for step_fused_multi."""
@@ -645,20 +683,14 @@ class Device:
         launch indices scatter['step'] .. +k_steps-1) in one pass over the store.  Returns a list of k_steps dicts like
         step_fused's (or None if not sync)."""
         sc = scatter
-        pl = np.ascontiguousarray(np.asarray(planes, dtype=np.float64).reshape(-1, 3))
-        npl = len(pl)
-        out = np.zeros((k_steps, 5 + npl), dtype=np.int64) if sync else None
-        expr = sc.get("n_expr")
+        pl, pp, npl = _planes(planes)
+        out = _rows_out(k_steps, npl) if sync else None
         check(self.lib.pcl_step_fused_multi(
-            self.ctx, float(dt), int(k_steps), float(sc["A"]), float(sc["n"]), int(sc.get("flags", 0)),
-            float(sc.get("c", 0.0)), float(sc.get("h", 0.0)), expr.encode() if expr is not None else None,
-            int(sc.get("seed", 0)), int(sc.get("step", 0)) & 0xFFFFFFFF, pl.ctypes.data_as(c_void_p) if npl else None, npl,
-            out.ctypes.data_as(c_void_p) if sync else None))
-        if out is None:
-            return None
-        if raw:                   # (k_steps, 5 + n_planes) int64: [N, sign x 3, planes ..., hits] per step
+            self.ctx, float(dt), int(k_steps), *_scatter(sc, required=True), int(sc.get("seed", 0)),
+            int(sc.get("step", 0)) & 0xFFFFFFFF, pp, npl, out.ctypes.data if sync else None))
+        if out is None or raw:    # raw: (k_steps, 5 + n_planes) int64, [N, sign x 3, planes ..., hits] per step
             return out
-        return [{"N": int(o[0]), "sign": o[1:4].copy(), "planes": o[4:4 + npl].copy(), "hits": int(o[4 + npl])} for o in out]
+        return [_row_dict(o, "hits") for o in out]
 
     def step_mixed_multi(self, dt, k_passes, phases, scatter=None, delete=None, planes=(), seed=0, step=0, raw=False):
         """``k_passes`` passes of a loop whose body holds the phases ``phases`` -- a sequence of "iso" / "delete", at
@@ -667,26 +699,17 @@ class Device:
         (kernel constants) of the isotropic phase; ``delete``: (A, n) of the delete phase.  Device RNG; phase j of
         pass p uses launch index ``step + p * len(phases) + j``.  Returns one dict per phase, in order:
         {'phase', 'N' (alive after it), 'sign', 'planes', 'hits' | 'removed'}."""
-        kinds = np.array([{"iso": PHASE_ISOTROPIC, "delete": PHASE_DELETE}[p] for p in phases], dtype=np.int32)
-        sc = scatter or {}
+        kinds = _phase_kinds(phases)
         A_d, n_d = delete if delete is not None else (0.0, 0.0)
-        pl = np.ascontiguousarray(np.asarray(planes, dtype=np.float64).reshape(-1, 3))
-        npl = len(pl)
-        out = np.zeros((k_passes * len(kinds), 5 + npl), dtype=np.int64)
-        expr = sc.get("n_expr")
+        pl, pp, npl = _planes(planes)
+        out = _rows_out(k_passes * len(kinds), npl)
         check(self.lib.pcl_step_mixed_multi(
-            self.ctx, float(dt), int(k_passes), len(kinds), kinds.ctypes.data_as(c_void_p), float(sc.get("A", 0.0)),
-            float(sc.get("n", 0.0)), int(sc.get("flags", 0)), float(sc.get("c", 0.0)), float(sc.get("h", 0.0)),
-            expr.encode() if expr is not None else None, float(A_d), float(n_d), int(seed), int(step) & 0xFFFFFFFF,
-            pl.ctypes.data_as(c_void_p) if npl else None, npl, out.ctypes.data_as(c_void_p)))
+            self.ctx, float(dt), int(k_passes), len(kinds), kinds.ctypes.data, *_scatter(scatter or {}), float(A_d), float(n_d),
+            int(seed), int(step) & 0xFFFFFFFF, pp, npl, out.ctypes.data))
         if raw:                   # (k_passes * len(phases), 5 + n_planes) int64: [N, sign x 3, planes ..., hits | removed]
             return out
-        rows = []
-        for k, o in enumerate(out):
-            ph = phases[k % len(kinds)]
-            rows.append({"phase": ph, "N": int(o[0]), "sign": o[1:4].copy(), "planes": o[4:4 + npl].copy(),
-                         ("hits" if ph == "iso" else "removed"): int(o[4 + npl])})
-        return rows
+        return [dict(phase=ph, **_row_dict(o, "hits" if ph == "iso" else "removed"))
+                for o, ph in zip(out, list(phases) * int(k_passes))]
 
     def trace_ahead(self, ids, dt, k_passes, phases, record_phase=0, scatter=None, delete=None, seed=0, step=0, defer=False):
         """Where the particles with the (ascending) ids ``ids`` will be when a trace step behind phase ``record_phase`` runs
@@ -697,16 +720,13 @@ class Device:
         ``defer=True``: the kernel is only enqueued and a function is returned that hands the rows out -- call it behind the
         K-pass launch (same stream, in order: the rows are there when the launch's own counter rows are, no extra wait)."""
         ids = np.ascontiguousarray(ids, dtype=np.int64)
-        kinds = np.array([{"iso": PHASE_ISOTROPIC, "delete": PHASE_DELETE}[p] for p in phases], dtype=np.int32)
-        sc = scatter or {}
+        kinds = _phase_kinds(phases)
         A_d, n_d = delete if delete is not None else (0.0, 0.0)
         out = np.empty((int(k_passes), len(ids), 4), dtype=np.float64)
-        expr = sc.get("n_expr")
         check(self.lib.pcl_store_trace_ahead(
-            self.ctx, ids.ctypes.data_as(c_void_p), len(ids), float(dt), int(k_passes), len(kinds), kinds.ctypes.data_as(c_void_p),
-            int(record_phase), float(sc.get("A", 0.0)), float(sc.get("n", 0.0)), int(sc.get("flags", 0)), float(sc.get("c", 0.0)),
-            float(sc.get("h", 0.0)), expr.encode() if expr is not None else None, float(A_d), float(n_d), int(seed),
-            int(step) & 0xFFFFFFFF, None if (defer and out.size) else out.ctypes.data_as(c_void_p)))
+            self.ctx, ids.ctypes.data_as(c_void_p), len(ids), float(dt), int(k_passes), len(kinds), kinds.ctypes.data,
+            int(record_phase), *_scatter(scatter or {}), float(A_d), float(n_d), int(seed), int(step) & 0xFFFFFFFF,
+            None if (defer and out.size) else out.ctypes.data_as(c_void_p)))
         if not defer:
             return out
 
@@ -718,10 +738,9 @@ class Device:
 
     def step_fused_read(self, n_planes=0):
         """Counters of the last ``step_fused(..., sync=False)``: same dict as the synchronous call."""
-        out = np.zeros(5 + n_planes, dtype=np.int64)
-        check(self.lib.pcl_step_fused_read(self.ctx, n_planes, out.ctypes.data_as(c_void_p)))
-        return {"N": int(out[0]), "sign": out[1:4].copy(), "planes": out[4:4 + n_planes].copy(),
-                "hits": int(out[4 + n_planes])}
+        out = _rows_out(1, n_planes)[0]
+        check(self.lib.pcl_step_fused_read(self.ctx, n_planes, out.ctypes.data))
+        return _row_dict(out, "hits")
 
     def last_scatter_hits(self):
         h = c_int64()
@@ -737,39 +756,27 @@ class Device:
     def step_fused_delete(self, dt, A, n, rng_mode=RNG_PHILOX, seed=0, step=0, planes=None, lazy=False):
         """Newton + ScatterDelete (+ counters on the survivors if ``planes`` is not None) as one pipeline.
         Returns {'N' (alive), 'removed', 'sign', 'planes'}."""
-        if planes is None:
-            npl, pp = -1, None
-        else:
-            # (a loop calls this once per body with the same planes: a ready float64 array is taken as it is)
-            pl = planes if (type(planes) is np.ndarray and planes.dtype == np.float64 and planes.ndim == 2 and
-                            planes.flags.c_contiguous) else np.ascontiguousarray(np.asarray(planes, dtype=np.float64).reshape(-1, 3))
-            npl = len(pl)
-            pp = pl.ctypes.data if npl else None
-        k = max(npl, 0)
-        out = np.zeros(5 + k, dtype=np.int64)
+        # (the host-latency path of the delete-until-empty run, one call per loop body: plain addresses instead of c_void_p
+        #  objects, no call of check() unless something failed, and views of ``out`` -- this call's own array -- not copies,
+        #  cut here: _row_dict's two calls and ``...`` indexing cost this call a tenth of its host time)
+        pl, pp, npl = _planes(planes, off=True)
+        out = np.zeros(5 + max(npl, 0), dtype=np.int64)
         rc = self.lib.pcl_step_fused_delete(self.ctx, float(dt), float(A), float(n), FUSED_LAZY if lazy else 0,
                                             int(rng_mode), int(seed), int(step) & 0xFFFFFFFF, pp, npl, out.ctypes.data)
         if rc != 0:
             check(rc)
-        # (``out`` is this call's own array: the slices need no copy)
-        return {"N": int(out[0]), "sign": out[1:4], "planes": out[4:4 + k], "removed": int(out[4 + k])}
+        return {"N": int(out[CNT_N]), "sign": out[CNT_XP:CNT_PLANE0], "planes": out[CNT_PLANE0:_EVENT], "removed": int(out[_EVENT])}
 
     def step_fused_delete_multi(self, dt, k_steps, A, n, seed=0, step=0, planes=None, raw=False):
         """``k_steps`` delete loop bodies (Newton + ScatterDelete + counters on the survivors) in one pass and one
         compaction.  Returns a list of k_steps dicts {'N','removed','sign','planes'}."""
-        if planes is None:
-            npl, pp = -1, None
-        else:
-            pl = np.ascontiguousarray(np.asarray(planes, dtype=np.float64).reshape(-1, 3))
-            npl = len(pl)
-            pp = pl.ctypes.data_as(c_void_p) if npl else None
-        k = max(npl, 0)
-        out = np.zeros((k_steps, 5 + k), dtype=np.int64)
+        pl, pp, npl = _planes(planes, off=True)
+        out = _rows_out(k_steps, npl)
         check(self.lib.pcl_step_fused_delete_multi(self.ctx, float(dt), int(k_steps), float(A), float(n), int(seed),
-                                                   int(step) & 0xFFFFFFFF, pp, npl, out.ctypes.data_as(c_void_p)))
+                                                   int(step) & 0xFFFFFFFF, pp, npl, out.ctypes.data))
         if raw:                   # (k_steps, 5 + n_planes) int64: [N, sign x 3, planes ..., removed] per body
             return out
-        return [{"N": int(o[0]), "sign": o[1:4].copy(), "planes": o[4:4 + k].copy(), "removed": int(o[4 + k])} for o in out]
+        return [_row_dict(o, "removed") for o in out]
 
     def last_delete_flags(self, n):
         out = np.empty(n, dtype=np.int32)
@@ -790,10 +797,9 @@ class Device:
         return out[:n.value].copy()
 
     def step_counters(self, planes=()):
-        planes = np.ascontiguousarray(np.asarray(planes, dtype=np.float64).reshape(-1, 3))
-        out = np.zeros(CNT_PLANE0 + len(planes), dtype=np.int64)
-        check(self.lib.pcl_step_counters(self.ctx, planes.ctypes.data_as(c_void_p) if len(planes) else None,
-                                         len(planes), out.ctypes.data_as(c_void_p)))
+        pl, pp, npl = _planes(planes)
+        out = np.zeros(CNT_PLANE0 + npl, dtype=np.int64)      # [N, sign x 3, planes ...]: no light step, no last column
+        check(self.lib.pcl_step_counters(self.ctx, pp, npl, out.ctypes.data))
         return out
 
 
@@ -847,39 +853,37 @@ class DeviceGroup:
     def sync(self):
         check(self.lib.pcl_group_sync(self.g))
 
+    # The step methods answer with the raw rows ([N, sign x 3, planes ..., hits | removed], summed over the contexts).
+    # One difference to Device is kept: an EMPTY n_expr goes over as NULL here, as "" there.  With SCATTER_VARIABLE_N set
+    # the library refuses both with PCL_ERR_EXPR but words the message differently ("is NULL" / "is empty or longer ...").
     def step_fused_multi(self, dt, k_steps, sc, planes=()):
-        pl = np.ascontiguousarray(np.asarray(planes, dtype=np.float64).reshape(-1, 3))
-        out = np.zeros((k_steps, 5 + len(pl)), dtype=np.int64)
-        expr = sc.get("n_expr")
-        check(self.lib.pcl_group_step_fused_multi(self.g, float(dt), int(k_steps), float(sc["A"]), float(sc["n"]), int(sc.get("flags", 0)),
-                                                  float(sc.get("c", 0.0)), float(sc.get("h", 0.0)), expr.encode() if expr else None,
-                                                  int(sc.get("seed", 0)), int(sc.get("step", 0)) & 0xFFFFFFFF,
-                                                  pl.ctypes.data if len(pl) else None, len(pl), out.ctypes.data))
+        pl, pp, npl = _planes(planes)
+        out = _rows_out(k_steps, npl)
+        check(self.lib.pcl_group_step_fused_multi(self.g, float(dt), int(k_steps), *_scatter(sc, required=True, empty_expr=None),
+                                                  int(sc.get("seed", 0)), int(sc.get("step", 0)) & 0xFFFFFFFF, pp, npl, out.ctypes.data))
         return out
 
     def step_fused_delete(self, dt, A, n, seed, step, planes=(), lazy=True):
-        pl = np.ascontiguousarray(np.asarray(planes, dtype=np.float64).reshape(-1, 3))
-        out = np.zeros(5 + len(pl), dtype=np.int64)
+        pl, pp, npl = _planes(planes)
+        out = np.zeros(5 + npl, dtype=np.int64)
         check(self.lib.pcl_group_step_fused_delete(self.g, float(dt), float(A), float(n), FUSED_LAZY if lazy else 0, RNG_PHILOX, int(seed),
-                                                   int(step) & 0xFFFFFFFF, pl.ctypes.data if len(pl) else None, len(pl), out.ctypes.data))
+                                                   int(step) & 0xFFFFFFFF, pp, npl, out.ctypes.data))
         return out
 
     def step_fused_delete_multi(self, dt, k_steps, A, n, seed, step, planes=()):
-        pl = np.ascontiguousarray(np.asarray(planes, dtype=np.float64).reshape(-1, 3))
-        out = np.zeros((k_steps, 5 + len(pl)), dtype=np.int64)
+        pl, pp, npl = _planes(planes)
+        out = _rows_out(k_steps, npl)
         check(self.lib.pcl_group_step_fused_delete_multi(self.g, float(dt), int(k_steps), float(A), float(n), int(seed), int(step) & 0xFFFFFFFF,
-                                                         pl.ctypes.data if len(pl) else None, len(pl), out.ctypes.data))
+                                                         pp, npl, out.ctypes.data))
         return out
 
     def step_mixed_multi(self, dt, k_passes, phases, sc, delete, seed, step, planes=()):
-        kinds = np.array([{"iso": PHASE_ISOTROPIC, "delete": PHASE_DELETE}[p] for p in phases], dtype=np.int32)
-        pl = np.ascontiguousarray(np.asarray(planes, dtype=np.float64).reshape(-1, 3))
-        out = np.zeros((k_passes * len(kinds), 5 + len(pl)), dtype=np.int64)
-        expr = sc.get("n_expr")
-        check(self.lib.pcl_group_step_mixed_multi(self.g, float(dt), int(k_passes), len(kinds), kinds.ctypes.data, float(sc.get("A", 0.0)),
-                                                  float(sc.get("n", 0.0)), int(sc.get("flags", 0)), float(sc.get("c", 0.0)), float(sc.get("h", 0.0)),
-                                                  expr.encode() if expr else None, float(delete[0]), float(delete[1]), int(seed),
-                                                  int(step) & 0xFFFFFFFF, pl.ctypes.data if len(pl) else None, len(pl), out.ctypes.data))
+        kinds = _phase_kinds(phases)
+        pl, pp, npl = _planes(planes)
+        out = _rows_out(k_passes * len(kinds), npl)
+        check(self.lib.pcl_group_step_mixed_multi(self.g, float(dt), int(k_passes), len(kinds), kinds.ctypes.data,
+                                                  *_scatter(sc, empty_expr=None), float(delete[0]), float(delete[1]), int(seed),
+                                                  int(step) & 0xFFFFFFFF, pp, npl, out.ctypes.data))
         return out
 
     def download(self, field, n=None, offset=0, dtype=None):

@@ -46,6 +46,20 @@ def _snap(x):
 _MAX_PLANES = 12        # == _hip.MAX_PLANES == PCL_MAX_PLANES (include/physicl_hip.h); tests/test_host_api.py checks it
 
 
+def _as_row(out, event):
+    """The dict answer of a one-launch step as the library's counter row [N, sign x 3, planes ..., hits | removed]."""
+    return np.concatenate([[out["N"]], out["sign"], out["planes"], [out[event]]]).astype(np.int64, copy=False)
+
+
+def _deal_planes(measures, crossed, at=0):
+    """The plane columns ``crossed`` of a group's counter rows (one row or a block), dealt to its counting measure steps
+    in order from column ``at``: yields (step, its columns)."""
+    for m in measures:
+        if m._fuse_role != "trace":                   # (a TracePathMeasureStep has no planes and files no counter row)
+            yield m, crossed[..., at:at + m._n_planes()]
+            at += m._n_planes()
+
+
 class Step:
     """Base class of every plugin (physicl/__init__.py:293-322)."""
     _device_native = False      # True: implements _device_run(sim) on the resident store
@@ -792,11 +806,10 @@ class Simulation(threading.Thread):
         k = len(times)
         if k == 0:
             return False                              # nothing could be planned ahead: this pass runs the plain way
-        planes, span = [], []
+        planes, first = [], []                        # all groups' planes, and where each group's begin among them
         for g in groups:
-            pl = [p for m in g[2:] for p in m._plane_rows()]
-            span.append((len(planes), len(pl)))
-            planes += pl
+            first.append(len(planes))
+            planes += [p for m in g[2:] for p in m._plane_rows()]
         sc = dl = None
         for s in lights:
             if s._fuse_role == "scatter_iso":
@@ -826,14 +839,7 @@ class Simulation(threading.Thread):
             raw = dev.step_mixed_multi(dt0, k, phases, sc, dl, planes, self.seed, step0, raw=True)
             self.schedule["mixed_multi"] += 1
         traced = [(m, read()) for m, read in traced]   # (the rows were written while the launch ran: nothing to wait for)
-        npl = len(planes)
-        have = raw.shape[1] - 5                       # plane columns the library returned (0 when no measure step asked)
-        flat = np.zeros((k * P, 5 + npl), dtype=np.int64)     # [N, event count, sign x 3, planes ...]: what is all-reduced
-        flat[:, 0] = raw[:, 0]
-        flat[:, 1] = raw[:, 4 + have]
-        flat[:, 2:5] = raw[:, 1:4]
-        flat[:, 5:5 + have] = raw[:, 4:4 + have]
-        glob = self._global(flat.reshape(-1)).reshape(k * P, 5 + npl) if self.comm is not None else flat
+        glob = self._global(raw.reshape(-1)).reshape(raw.shape) if self.comm is not None else raw   # the rows as they are
         ts = self.ts
         # How many of the k passes does the loop keep?  Without a delete step all of them (the exit tests were planned).  With
         # one, the planned tests were made for a store that is not empty (the functions ask for emptiness only:
@@ -850,20 +856,14 @@ class Simulation(threading.Thread):
                 return
             self.t, self.dt = times[upto - 1]
             for j, g in enumerate(groups):
-                last = glob[(upto - 1) * P + j]
+                n, sign, crossed, event = hip._split_rows(glob[lo * P + j:upto * P:P])    # group j's rows of these passes
                 if phases[j] == "iso":
-                    self.hits = int(last[1])
+                    self.hits = int(event[-1])
                     self._scattered = True
                 else:
-                    self._alive, lights[j].removed = int(last[0]), int(last[1])
-                at = 5 + span[j][0]
-                for m in g[2:]:
-                    if m._fuse_role == "trace":
-                        continue
-                    n_m = m._n_planes()
-                    m._record_rows(self, [times[i][0] for i in range(lo, upto)], glob[lo * P + j:upto * P:P, 0],
-                                   glob[lo * P + j:upto * P:P, 2:5], glob[lo * P + j:upto * P:P, at:at + n_m])
-                    at += n_m
+                    self._alive, lights[j].removed = int(n[-1]), int(event[-1])
+                for m, mine in _deal_planes(g[2:], crossed, first[j]):
+                    m._record_rows(self, [times[i][0] for i in range(lo, upto)], n, sign, mine)
             for m, rows in traced:
                 m._ahead_record(self, [times[i][0] for i in range(lo, upto)], rows[lo:upto])
             done[0] = upto
@@ -871,7 +871,7 @@ class Simulation(threading.Thread):
         keep = k
         if has_delete:
             jd = phases.index("delete")
-            for i in np.flatnonzero(glob[jd:(k - 1) * P:P, 0] == 0).tolist():
+            for i in np.flatnonzero(hip._split_rows(glob[jd:(k - 1) * P:P])[0] == 0).tolist():
                 flush(i + 1)
                 later = ts[n_ts + i + 1:]
                 del ts[n_ts + i + 1:]
@@ -900,6 +900,10 @@ class Simulation(threading.Thread):
                 ahead.append((m, None if ids is None else dev.trace_ahead(ids, self._dt_code(), 1, [phase], 0, sc_, dl_, self.seed, step)))
             return ahead
 
+        def file_row(n, sign, crossed):
+            for m, mine in _deal_planes(measures, crossed):
+                m._record(self, int(n), sign, mine)
+
         def trace_file(ahead):
             for m, rows in ahead:
                 if rows is not None:
@@ -921,13 +925,9 @@ class Simulation(threading.Thread):
             out = dev.step_fused_delete(self._dt_code(), A_k, n_k, mode, self.seed, step,
                                         planes if measures else None, lazy=True)
             self.schedule["fused_delete"] += 1
-            g = self._global(np.concatenate([[out["N"], out["removed"]], out["sign"], out["planes"]]))
-            self._alive, delete.removed = int(g[0]), int(g[1])
-            k = 5
-            for m in measures:
-                npl = m._n_planes()
-                m._record(self, int(g[0]), g[2:5], g[k:k + npl])
-                k += npl
+            n, sign, crossed, removed = hip._split_rows(self._global(_as_row(out, "removed")))
+            self._alive, delete.removed = int(n), int(removed)
+            file_row(n, sign, crossed)
             trace_file(ahead)
             return
         sc = None
@@ -945,14 +945,11 @@ class Simulation(threading.Thread):
         out = dev.step_fused(self._dt_code(), sc, planes if (measures or scatter) else None, sync=True, lazy=True)
         self.schedule["fused"] += 1
         if out is not None:
+            row = _as_row(out, "hits")
             if scatter is not None:
-                self.hits = int(self._global([out["hits"]])[0])
-            glob = self._global(np.concatenate([[out["N"]], out["sign"], out["planes"]]))
-            k = 4
-            for m in measures:
-                npl = m._n_planes()
-                m._record(self, int(glob[0]), glob[1:4], glob[k:k + npl])
-                k += npl
+                self.hits = int(self._global(row[hip._EVENT:])[0])
+            row[:hip._EVENT] = self._global(row[:hip._EVENT])   # (two reductions, hits and the rest: number and lengths are fixed)
+            file_row(*hip._split_rows(row)[:3])
         trace_file(ahead)
 
     def run(self):

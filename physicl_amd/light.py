@@ -244,11 +244,6 @@ class ScatterSphericalStep(ScatterIsotropicStep):
 
 
 # ---------------------------------------------------------------------------------------------- measure steps
-def _plane_axis(loc):
-    loc = np.asarray(loc, dtype=np.float64).reshape(3)
-    return loc
-
-
 class _CountingMeasure(DeviceStep, MeasureStep):
     """Measure steps whose rows are counters: one fused reduction on the device."""
     _fuse_role = "measure"

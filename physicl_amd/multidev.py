@@ -65,19 +65,18 @@ class MultiDevice:
             at += c
         return out
 
-    @staticmethod
-    def _sum_dicts(outs):
-        if outs[0] is None:
-            return None
-        tot = {}
-        for k, v in outs[0].items():
-            if isinstance(v, str):
-                tot[k] = v
-            elif isinstance(v, np.ndarray):
-                tot[k] = np.sum([o[k] for o in outs], axis=0)
-            else:
-                tot[k] = sum(o[k] for o in outs)
-        return tot
+    @classmethod
+    def _sum(cls, outs):
+        """The shards' answers to one step added up, whatever form the step answers in: None (no counters), raw rows,
+        a dict of counters (its "phase" label is kept) or a list of such dicts."""
+        first = outs[0]
+        if first is None or isinstance(first, str):
+            return first
+        if isinstance(first, dict):
+            return {k: cls._sum([o[k] for o in outs]) for k in first}
+        if isinstance(first, list):
+            return [cls._sum([o[k] for o in outs]) for k in range(len(first))]
+        return np.sum(outs, axis=0) if isinstance(first, np.ndarray) else sum(outs)
 
     # ---------------------------------------------------------------- lifecycle
     def close(self):
@@ -206,7 +205,7 @@ class MultiDevice:
             raise NotImplementedError("partial kind uploads on a multi-device store")
         self._each(lambda s, h: s.upload_kind(np.ascontiguousarray(h)), self._split(host))
 
-    def _concat(self, parts, dtype=None):
+    def _concat(self, parts):
         return np.concatenate(parts) if len(parts) > 1 else parts[0]
 
     def _window(self, n, offset):
@@ -267,25 +266,19 @@ class MultiDevice:
         return self._concat(self._each(lambda s: s.plane_energies(plane)))      # (a shard does not know its share of the hint)
 
     def step_fused(self, dt, scatter=None, planes=None, sync=True, lazy=False):
-        return self._sum_dicts(self._each(lambda s: s.step_fused(dt, scatter, planes, sync, lazy)))
+        return self._sum(self._each(lambda s: s.step_fused(dt, scatter, planes, sync, lazy)))
 
     def step_fused_read(self, n_planes=0):
-        return self._sum_dicts(self._each(lambda s: s.step_fused_read(n_planes)))
+        return self._sum(self._each(lambda s: s.step_fused_read(n_planes)))
 
     def last_scatter_hits(self):
         return sum(self._each(lambda s: s.last_scatter_hits()))
 
     def step_fused_delete(self, *a, **kw):
-        return self._sum_dicts(self._each(lambda s: s.step_fused_delete(*a, **kw)))
-
-    def _sum_rows(self, outs, raw):
-        if raw:
-            return np.sum(outs, axis=0)
-        return [self._sum_dicts([o[k] for o in outs]) for k in range(len(outs[0]))]
+        return self._sum(self._each(lambda s: s.step_fused_delete(*a, **kw)))
 
     def step_fused_multi(self, dt, k_steps, scatter, planes=(), sync=True, raw=False):
-        outs = self._each(lambda s: s.step_fused_multi(dt, k_steps, scatter, planes, sync, raw))
-        return None if outs[0] is None else self._sum_rows(outs, raw)
+        return self._sum(self._each(lambda s: s.step_fused_multi(dt, k_steps, scatter, planes, sync, raw)))
 
     def trace_ahead(self, ids, *a, defer=False, **kw):
         """Every context is asked for every tracked id and answers NaN rows for the particles it does not hold; a particle
@@ -302,7 +295,7 @@ class MultiDevice:
         return lambda: merge([read() for read in outs])
 
     def step_fused_delete_multi(self, dt, k_steps, A, n, seed=0, step=0, planes=None, raw=False):
-        return self._sum_rows(self._each(lambda s: s.step_fused_delete_multi(dt, k_steps, A, n, seed, step, planes, raw)), raw)
+        return self._sum(self._each(lambda s: s.step_fused_delete_multi(dt, k_steps, A, n, seed, step, planes, raw)))
 
     def step_mixed_multi(self, dt, k_passes, phases, scatter=None, delete=None, planes=(), seed=0, step=0, raw=False):
-        return self._sum_rows(self._each(lambda s: s.step_mixed_multi(dt, k_passes, phases, scatter, delete, planes, seed, step, raw)), raw)
+        return self._sum(self._each(lambda s: s.step_mixed_multi(dt, k_passes, phases, scatter, delete, planes, seed, step, raw)))
