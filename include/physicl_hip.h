@@ -493,6 +493,27 @@ int pcl_step_plane_energies(pcl_ctx *ctx, const double *plane_host, void *E_out_
  * defining the plane.  out_host: int64[PCL_CNT_PLANE0 + n_planes].  Synchronises. */
 int pcl_step_counters(pcl_ctx *ctx, const double *planes_host, int n_planes, int64_t *out_host);
 
+/* ScatterMeasureStep(measure_E=True) with bin edges: what the reference's scripts do with the energy lists of
+ * pcl_step_plane_energies is a histogram (examples/planck_distribution.ipynb: plt.hist(sim.steps[4].data[49][3], 50)), so
+ * this returns the histogram -- per plane the count of crossing photons per energy bin, for ALL planes of the call in one
+ * sweep of the store, as int64 rows that add across devices and ranks like every other counter.  planes_host: n_planes x 3
+ * doubles, NaN = coordinate not defining the plane (1 <= n_planes <= PCL_MAX_PLANES, each with a defining coordinate);
+ * edges_host: n_bins + 1 finite, strictly increasing doubles (1 <= n_bins <= PCL_SPECTRUM_MAX_BINS) in the unit E is
+ * stored in.  counts_out_host[p] = the plane counter of pcl_step_counters (every particle of the store);
+ * hist_out_host[p * n_bins + b] = crossing photons (plain Objects carry no energy) whose E lies in bin b as
+ * numpy.histogram(E, bins=edges) counts it: [e_b, e_b+1), the last bin closed, E outside [e_0, e_nbins] or NaN in no bin
+ * -- an fp32 store's E is widened to double (exact) for the comparison.  Crossing predicate and the store as
+ * pcl_step_plane_energies sees it (dense, dr real).  Host pointers; synchronises once.  An empty store answers zeros without
+ * a launch.  PCL_ERR_ARG / PCL_ERR_STATE (no store) are returned before anything is launched.
+ * pcl_last_error() is GENERIC for these two entry points: the thread's text belongs to the core source file and has no setter,
+ * so a refused argument leaves the core's "bad argument" (not which edge or plane), a failed launch of this unit leaves the
+ * text of the last call that set one, and a shard's text in the group form stays on that shard's thread.  Go by the code.
+ * Compiled from a source file of its own (physicl_amd/csrc/pcl_spectrum.hip) on top of the functions above; it reads E through
+ * pcl_store_field_ptr, so a wavelength-dependent scatter step that follows rebuilds its wavelength-term cache. */
+#define PCL_SPECTRUM_MAX_BINS 1024
+int pcl_step_plane_spectra(pcl_ctx *ctx, const double *planes_host, int n_planes, const double *edges_host, int n_bins,
+                           int64_t *counts_out_host, int64_t *hist_out_host);
+
 /* ---- Device groups: several GPUs from ONE process ---------------------------------------------------------------
  * The reference is a single process with one simulation thread (physicl/__init__.py:400-432, 501-524); this is how
  * a host written against this ABI uses a node's GPUs the same way, without one process per GPU.  A group owns one
@@ -539,6 +560,9 @@ int pcl_group_step_mixed_multi(pcl_group *group, double dt, int k_passes, int n_
 /* elements [offset, offset + n) of a field / of the ids in GLOBAL particle order (host pointers, store dtype / int64) */
 int pcl_group_download(pcl_group *group, int field, void *host, int64_t offset, int64_t n);
 int pcl_group_download_ids(pcl_group *group, int64_t *host, int64_t offset, int64_t n);
+/* pcl_step_plane_spectra on every shard (side by side), counts and histograms summed over the group's devices */
+int pcl_group_step_plane_spectra(pcl_group *group, const double *planes_host, int n_planes, const double *edges_host, int n_bins,
+                                 int64_t *counts_out_host, int64_t *hist_out_host);
 
 /* ---------------------------------------------------------------- the counters' collective (one process per GPU)
  * The path shards by global index with no data-path exchange; the only global quantities are the int64

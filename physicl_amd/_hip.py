@@ -139,6 +139,7 @@ _PROTOTYPES = {
     "pcl_step_fused_delete": [_vp, c_double, c_double, c_double, c_int, c_int, c_uint64, c_uint32, _vp, c_int, _vp],
     "pcl_store_last_delete_flags": [_vp, _vp, c_int64],
     "pcl_step_counters": [_vp, _vp, c_int, _vp],
+    "pcl_step_plane_spectra": [_vp, _vp, c_int, _vp, c_int, _vp, _vp],
     # device groups: several GPUs from one process (the C-level counterpart of physicl_amd.multidev.MultiDevice)
     "pcl_group_create": [c_int, POINTER(c_int), POINTER(_vp)],
     "pcl_group_destroy": [_vp],
@@ -161,6 +162,7 @@ _PROTOTYPES = {
                                    c_double, c_double, c_uint64, c_uint32, _vp, c_int, _vp],
     "pcl_group_download": [_vp, c_int, _vp, c_int64, c_int64],
     "pcl_group_download_ids": [_vp, _vp, c_int64, c_int64],
+    "pcl_group_step_plane_spectra": [_vp, _vp, c_int, _vp, c_int, _vp, _vp],
 }
 EXPORTS = sorted(list(_PROTOTYPES) + ["pcl_last_error"])
 
@@ -268,6 +270,16 @@ def _planes(planes, off=False):
     else:
         pl = np.ascontiguousarray(np.asarray(planes, dtype=np.float64).reshape(-1, 3))
     return pl, (pl.ctypes.data if len(pl) else None), len(pl)
+
+
+def _spectra(entry, handle, planes, edges):
+    """One call of pcl_step_plane_spectra / pcl_group_step_plane_spectra: (counts int64[P], hist int64[P, B])."""
+    pl, pp, npl = _planes(planes)
+    ed = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+    n_bins = len(ed) - 1
+    counts, hist = np.zeros(npl, dtype=np.int64), np.zeros((npl, max(n_bins, 0)), dtype=np.int64)
+    check(entry(handle, pp, npl, ed.ctypes.data, n_bins, counts.ctypes.data, hist.ctypes.data))
+    return counts, hist
 
 
 def _scatter(sc, required=False, lazy=False, empty_expr=b""):
@@ -802,6 +814,12 @@ class Device:
         check(self.lib.pcl_step_counters(self.ctx, pp, npl, out.ctypes.data))
         return out
 
+    def plane_spectra(self, planes, edges):
+        """Per plane the number of particles that crossed it in the last move and the histogram of the crossing photons'
+        energies over the bin ``edges`` (len(edges) - 1 bins, counted as ``numpy.histogram(E, bins=edges)`` does), for all
+        planes in one sweep of the store: (counts int64[P], hist int64[P, B]).  ScatterMeasureStep(measure_E=True, E_bins=...)."""
+        return _spectra(self.lib.pcl_step_plane_spectra, self.ctx, planes, edges)
+
 
 class DeviceGroup:
     """``pcl_group_*``: several contexts in one process, sharded by global index, behind the C ABI (the shim owns the
@@ -885,6 +903,10 @@ class DeviceGroup:
                                                   *_scatter(sc, empty_expr=None), float(delete[0]), float(delete[1]), int(seed),
                                                   int(step) & 0xFFFFFFFF, pp, npl, out.ctypes.data))
         return out
+
+    def plane_spectra(self, planes, edges):
+        """``Device.plane_spectra`` summed over the group's contexts (pcl_group_step_plane_spectra)."""
+        return _spectra(self.lib.pcl_group_step_plane_spectra, self.g, planes, edges)
 
     def download(self, field, n=None, offset=0, dtype=None):
         n = self.count - offset if n is None else n

@@ -281,14 +281,52 @@ class _CountingMeasure(DeviceStep, MeasureStep):
         raise NotImplementedError
 
 
+_MAX_E_BINS = 1024            # PCL_SPECTRUM_MAX_BINS: bins of a binned spectrum
+_ALLREDUCE_CHUNK = 2048      # values one pcl_comm_allreduce_sum_i64 call takes (physicl_amd.comm.NativeCounterComm)
+
+
+def _check_E_bins(E_bins):
+    """The bin edges of ScatterMeasureStep(E_bins=...) as a float64 array, or ValueError."""
+    try:
+        edges = np.array(E_bins, dtype=np.float64)            # a Measurement is taken by its stored value
+    except (TypeError, ValueError):
+        raise ValueError("E_bins must be a 1-D sequence of numbers (bin edges)") from None
+    if edges.ndim != 1 or len(edges) < 2:
+        raise ValueError("E_bins must be a 1-D sequence of at least two bin edges, got shape %r" % (edges.shape,))
+    if len(edges) - 1 > _MAX_E_BINS:
+        raise ValueError("E_bins describes %d bins, at most %d are supported" % (len(edges) - 1, _MAX_E_BINS))
+    if not np.all(np.isfinite(edges)) or not np.all(np.diff(edges) > 0):
+        raise ValueError("E_bins must be finite and strictly increasing")
+    return np.ascontiguousarray(edges)
+
+
+def _allreduce_chunked(sim, values):
+    """``sim._global`` of a payload of any length.  The library's own communicator takes 2048 values per call, so a longer
+    payload goes over in consecutive pieces of that size -- cut by position alone, so every rank cuts alike."""
+    values = np.ascontiguousarray(values, dtype=np.int64).reshape(-1)
+    if len(values) <= _ALLREDUCE_CHUNK:
+        return np.asarray(sim._global(values), dtype=np.int64)
+    return np.concatenate([np.asarray(sim._global(values[at:at + _ALLREDUCE_CHUNK]), dtype=np.int64)
+                           for at in range(0, len(values), _ALLREDUCE_CHUNK)])
+
+
 class ScatterMeasureStep(_CountingMeasure):
     """Row per step: ``[t, N, crossings of plane 0, ...]`` (physicl/light.py:361-404).  A plane is a
     3-vector with NaN in the coordinates that do not define it.  With ``measure_E`` each plane's count is followed
-    by the list of the crossing photons' energies (object order), gathered on the device."""
+    by the list of the crossing photons' energies (object order), gathered on the device.
 
-    def __init__(self, out_fn, measure_n=True, measure_locs=[], measure_E=False):
+    ``E_bins`` (not in the reference; needs ``measure_E``): bin edges, in the unit E is stored in.  Each plane's count is
+    then followed by the histogram of the crossing photons' energies over those bins -- an int64 array of
+    ``len(E_bins) - 1``, what ``numpy.histogram(list, bins=E_bins)[0]`` makes of the list form -- computed on the device
+    for all planes in one sweep.  Histograms add, so sharded runs all-reduce them with the counts (also on the library's own
+    communicator, which cannot carry the lists)."""
+
+    def __init__(self, out_fn, measure_n=True, measure_locs=[], measure_E=False, E_bins=None):
         MeasureStep.__init__(self, out_fn)
         self.measure_locs, self.measure_n, self.measure_E = measure_locs, measure_n, measure_E
+        if E_bins is not None and not measure_E:
+            raise ValueError("E_bins bins the energies measure_E=True records: pass measure_E=True with it")
+        self.E_bins = None if E_bins is None else _check_E_bins(E_bins)
         if measure_E:
             # rows carry variable-length energy lists: a separate gather per plane after the counters, outside the
             # fused kernels (this instance takes no part in step fusion / steps_per_launch)
@@ -297,6 +335,8 @@ class ScatterMeasureStep(_CountingMeasure):
     def _device_run(self, sim):
         if not self.measure_E:
             return _CountingMeasure._device_run(self, sim)
+        if self.E_bins is not None:
+            return self._device_run_binned(sim)
         dev = sim._dev
         cnt = dev.step_counters(self._plane_rows())
         glob = sim._global(cnt)                                              # counts over all shards
@@ -313,6 +353,66 @@ class ScatterMeasureStep(_CountingMeasure):
         out = np.empty(len(row), dtype=object)                               # ragged row, as the reference's np.array(out)
         out[:] = row
         self.data.append(out)
+
+    # -- E_bins: the spectra as histograms ---------------------------------------------------------------------------
+    def _device_run_binned(self, sim):
+        """One sweep of the store for every plane, then ONE collective for the whole step: [N, counts, histograms]
+        flattened (every rank issues it, also with an empty shard)."""
+        dev, planes = sim._dev, self._plane_rows()
+        n_bins = len(self.E_bins) - 1
+        if planes:
+            counts, hist = dev.plane_spectra(planes, self.E_bins)
+        else:
+            counts, hist = np.zeros(0, dtype=np.int64), np.zeros((0, n_bins), dtype=np.int64)
+        glob = _allreduce_chunked(sim, np.concatenate([[dev.count], counts, hist.reshape(-1)]))
+        P = len(planes)
+        self._record_binned(sim, int(glob[0]), glob[1:1 + P], glob[1 + P:].reshape(P, n_bins))
+
+    def _host_run_binned(self, sim):
+        """The same row from the Python objects (they hold the state: nothing to upload for a measurement): the list the
+        reference builds per plane (physicl/light.py:378-402), binned with numpy.histogram."""
+        objs = list(sim.objects)
+        counts, hists = [], []
+        for loc in self._plane_rows():
+            ax = 0 if not np.isnan(loc[0]) else (1 if not np.isnan(loc[1]) else 2)
+            L, nl, Es = loc[ax], 0, []
+            for obj in objs:
+                x = float(np.asarray(obj.r, dtype=np.float64)[ax])
+                prev = x - float(np.asarray(obj.dr, dtype=np.float64)[ax])
+                if (prev <= L and L <= x) or (prev >= L and L >= x):
+                    nl += 1
+                    if type(obj) is PhotonObject:
+                        Es.append(float(np.asarray(obj.E)))
+            counts.append(nl)
+            hists.append(np.histogram(np.array(Es, dtype=np.float64), bins=self.E_bins)[0].astype(np.int64))
+        self._record_binned(sim, len(objs), counts, hists)
+
+    def _record_binned(self, sim, n, counts, hists):
+        row = [sim.t]
+        if self.measure_n:
+            row.append(int(n))
+        for nl, hist in zip(counts, hists):
+            row.append(int(nl))
+            row.append(np.array(hist, dtype=np.int64))
+        out = np.empty(len(row), dtype=object)         # the measure_E row, each energy list replaced by its histogram
+        for k, x in enumerate(row):
+            out[k] = x
+        self.data.append(out)
+
+    def run(self, sim):
+        if self.E_bins is not None and getattr(sim, "_residency", None) == "host" and getattr(sim, "_batch", None) is None \
+                and (sim.comm is None or sim.comm.world == 1):
+            # called as a host plugin on host-resident objects.  float64 on both sides: a Simulation's store is fp64
+            # (core.py allocates no other), so the row does not depend on where the objects reside
+            return self._host_run_binned(sim)          # called as a host plugin on host-resident objects
+        return DeviceStep.run(self, sim)
+
+    def terminate(self, sim):
+        if self.E_bins is None or self.out_fn is None:
+            return MeasureStep.terminate(self, sim)
+        with open(self.out_fn, "w") as f:              # a histogram cell is written as the list cells are: a plain list of integers
+            for row in self.data:
+                f.write(", ".join(str(x.tolist() if isinstance(x, np.ndarray) else x) for x in list(row)) + "\n")
 
     def _n_planes(self):
         return len(self.measure_locs)

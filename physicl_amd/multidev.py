@@ -262,6 +262,9 @@ class MultiDevice:
     def step_counters(self, planes=()):
         return np.sum(self._each(lambda s: s.step_counters(planes)), axis=0)
 
+    def plane_spectra(self, planes, edges):
+        return tuple(self._sum(list(part)) for part in zip(*self._each(lambda s: s.plane_spectra(planes, edges))))
+
     def plane_energies(self, plane, n_hint=None):
         return self._concat(self._each(lambda s: s.plane_energies(plane)))      # (a shard does not know its share of the hint)
 
