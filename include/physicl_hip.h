@@ -315,6 +315,41 @@ int pcl_store_fill_photons(pcl_ctx *ctx, int64_t n, int64_t id_base, double c, d
 int pcl_store_fill_photons_table(pcl_ctx *ctx, int64_t n, int64_t id_base, double c, const double *cdf_host,
                                  const double *grid_host, int nbins, uint64_t seed);
 
+/* Photon sources: where the photons of a bulk fill start and where they go.  angular = the distribution of the direction
+ * about the axis d, spatial = the distribution of the position in the plane through origin perpendicular to d. */
+#define PCL_SRC_BEAM 0        /* angular: v = c * d */
+#define PCL_SRC_ISOTROPIC 1   /*          uniform on the sphere */
+#define PCL_SRC_CONE 2        /*          uniform in solid angle inside the half angle about d */
+#define PCL_SRC_LAMBERTIAN 3  /*          cosine-weighted hemisphere about d (emission from a surface) */
+#define PCL_SRC_POINT 0       /* spatial: r = origin */
+#define PCL_SRC_DISC 1        /*          uniform over a disc of the given radius */
+#define PCL_SRC_GAUSSIAN 2    /*          two-dimensional normal spot, radius = sigma */
+typedef struct pcl_source {
+    double origin[3];         /* code units */
+    double e1[3], e2[3], d[3];/* right-handed orthonormal frame, d = the source's axis; made by the host */
+    int angular, spatial;
+    double cos_half_angle;    /* PCL_SRC_CONE */
+    double radius;            /* PCL_SRC_DISC: radius; PCL_SRC_GAUSSIAN: sigma */
+} pcl_source;
+/* Gives the population that pcl_store_fill_photons[_table] has just created its positions and velocities.  The store must
+ * be uniform (pcl_store_is_uniform: ids = id_base + index, every particle a photon; PCL_ERR_STATE otherwise, also without a
+ * store); the rows R0..R2 and V0..V2 of photons [0, count) are overwritten in the store's dtype -- computed in fp64, unfused,
+ * rounded once --, E, dr, dv, ids and kinds are not touched, and rows that would not change are not written (point source at
+ * the origin: no r rows; beam along +x: nothing at all).  ``c`` = the speed of light in code units, ``seed`` = the fill's.
+ * The draws are Philox4x32-10 blocks keyed like the fill's energy draw -- key (seed_lo, seed_hi), counter (id_lo, id_hi,
+ * 0xFFFFFFFF, block), u53 = ((w_a >> 5) * 2^26 + (w_b >> 6)) / 2^53 -- so a photon is the same photon however the run is sharded:
+ *   block 4, direction: u_a = u53(w0, w1), u_b = u53(w2, w3); mu = cosine of the polar angle about d: beam: no draw;
+ *     isotropic mu = 1 - 2*u_a; cone mu = 1 - u_a*(1 - cos_half_angle); lambertian mu = sqrt(1 - u_a);
+ *     s = sqrt((1 - mu)*(1 + mu)), psi = (u_b*2)*pi, v_k = c * ((s*cos psi)*e1_k + (s*sin psi)*e2_k + mu*d_k);
+ *   block 5, position: u_c = u53(w0, w1), u_d = u53(w2, w3); disc rho = radius*sqrt(u_c); gaussian
+ *     rho = radius*sqrt(-2*log(1 - u_c)); phi = (u_d*2)*pi, r_k = origin_k + ((rho*cos phi)*e1_k + (rho*sin phi)*e2_k).
+ * PCL_ERR_ARG (NULL, unknown mode, non-finite origin / frame / c, cos_half_angle outside [-1, 1] for a cone, radius negative
+ * or not finite for a disc / gaussian) is returned before anything is written; an empty store is PCL_OK.  Asynchronous on the
+ * context's stream.  The group form checks every shard first and runs the shards side by side.  pcl_last_error() is generic
+ * for these two entry points, as for pcl_step_plane_spectra: they are compiled from a source file of their own
+ * (physicl_amd/csrc/pcl_source.hip) on top of the functions above. */
+int pcl_store_apply_source(pcl_ctx *ctx, const pcl_source *src, double c, uint64_t seed);
+
 /* NewtonianKinematicsStep.run (physicl/newton.py:10-16): dr = v*dt (rounded, stored); r = r + dr.
  * Applies to every particle of every kind. */
 int pcl_step_newton(pcl_ctx *ctx, double dt);
@@ -563,6 +598,8 @@ int pcl_group_download_ids(pcl_group *group, int64_t *host, int64_t offset, int6
 /* pcl_step_plane_spectra on every shard (side by side), counts and histograms summed over the group's devices */
 int pcl_group_step_plane_spectra(pcl_group *group, const double *planes_host, int n_planes, const double *edges_host, int n_bins,
                                  int64_t *counts_out_host, int64_t *hist_out_host);
+/* pcl_store_apply_source on every shard of a group filled with pcl_group_fill_photons (ids are global: the same photons) */
+int pcl_group_apply_source(pcl_group *group, const pcl_source *src, double c, uint64_t seed);
 
 /* ---------------------------------------------------------------- the counters' collective (one process per GPU)
  * The path shards by global index with no data-path exchange; the only global quantities are the int64

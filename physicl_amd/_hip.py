@@ -22,6 +22,8 @@ DTYPE_F64, DTYPE_F32 = 0, 1
 _NP_DTYPE = {DTYPE_F64: np.float64, DTYPE_F32: np.float32}
 CNT_N, CNT_XP, CNT_YP, CNT_ZP, CNT_PLANE0 = 0, 1, 2, 3, 4
 MAX_PLANES = 12
+SRC_ANGULAR = {"beam": 0, "isotropic": 1, "cone": 2, "lambertian": 3}       # PCL_SRC_BEAM ...
+SRC_SPATIAL = {"point": 0, "disc": 1, "gaussian": 2}                         # PCL_SRC_POINT ...
 PROF_NEWTON, PROF_SCATTER, PROF_DELETE_MASK, PROF_COMPACT, PROF_COUNTERS, PROF_FUSED, PROF_MULTI, PROF_ONEPASS, \
     PROF_DELETE_AHEAD = range(9)
 PROF_NAMES = {PROF_NEWTON: "k_newton", PROF_SCATTER: "k_scatter", PROF_DELETE_MASK: "k_delete_mask",
@@ -115,6 +117,7 @@ _PROTOTYPES = {
     "pcl_store_upload_rand3": [_vp, _vp, c_int64, c_int64],
     "pcl_store_fill_photons": [_vp, c_int64, c_int64, c_double, c_double, c_double, c_uint64],
     "pcl_store_fill_photons_table": [_vp, c_int64, c_int64, c_double, _vp, _vp, c_int, c_uint64],
+    "pcl_store_apply_source": [_vp, _vp, c_double, c_uint64],
     "pcl_step_newton": [_vp, c_double],
     "pcl_step_scatter_isotropic": [_vp, c_double, c_double, c_int, c_double, c_double, c_char_p, c_int, c_uint64,
                                    c_uint32, POINTER(c_int64)],
@@ -163,6 +166,7 @@ _PROTOTYPES = {
     "pcl_group_download": [_vp, c_int, _vp, c_int64, c_int64],
     "pcl_group_download_ids": [_vp, _vp, c_int64, c_int64],
     "pcl_group_step_plane_spectra": [_vp, _vp, c_int, _vp, c_int, _vp, _vp],
+    "pcl_group_apply_source": [_vp, _vp, c_double, c_uint64],
 }
 EXPORTS = sorted(list(_PROTOTYPES) + ["pcl_last_error"])
 
@@ -280,6 +284,22 @@ def _spectra(entry, handle, planes, edges):
     counts, hist = np.zeros(npl, dtype=np.int64), np.zeros((npl, max(n_bins, 0)), dtype=np.int64)
     check(entry(handle, pp, npl, ed.ctypes.data, n_bins, counts.ctypes.data, hist.ctypes.data))
     return counts, hist
+
+
+class SourceStruct(ctypes.Structure):
+    """``pcl_source`` of include/physicl_hip.h."""
+    _fields_ = [("origin", c_double * 3), ("e1", c_double * 3), ("e2", c_double * 3), ("d", c_double * 3),
+                ("angular", c_int), ("spatial", c_int), ("cos_half_angle", c_double), ("radius", c_double)]
+
+
+def _source(entry, handle, src, c, seed):
+    """One call of pcl_store_apply_source / pcl_group_apply_source.  ``src``: a light.PhotonSource, or anything with its
+    attributes (origin, e1, e2, d: three numbers each; angular, spatial: names or the header's numbers; cos_half_angle,
+    radius)."""
+    vec = lambda a: (c_double * 3)(*[float(x) for x in a])                                                     # noqa: E731
+    st = SourceStruct(vec(src.origin), vec(src.e1), vec(src.e2), vec(src.d), int(SRC_ANGULAR.get(src.angular, src.angular)),
+                      int(SRC_SPATIAL.get(src.spatial, src.spatial)), float(src.cos_half_angle), float(src.radius))
+    check(entry(handle, ctypes.addressof(st), float(c), int(seed)))
 
 
 def _scatter(sc, required=False, lazy=False, empty_expr=b""):
@@ -621,6 +641,11 @@ class Device:
         assert cdf.shape == grid.shape
         check(self.lib.pcl_store_fill_photons_table(self.ctx, int(n), int(id_base), c, cp, gp, len(cdf), int(seed)))
 
+    def apply_source(self, src, c, seed):
+        """Positions and velocities of a ``light.PhotonSource`` for the photons ``fill_photons`` / ``fill_photons_table`` has
+        just created (pcl_store_apply_source; ``seed`` = the fill's: the draws are keyed by it and the photon's id)."""
+        _source(self.lib.pcl_store_apply_source, self.ctx, src, c, seed)
+
     def upload_state(self, state):
         """state: dict with 'r','v','dr','dv' -> (n,3) or 3 arrays, 'E' -> (n,).  Sets count = n."""
         n = len(np.asarray(state["E"]))
@@ -861,6 +886,10 @@ class DeviceGroup:
 
     def fill_photons(self, n, id_base, c, e_min, e_max, seed):
         check(self.lib.pcl_group_fill_photons(self.g, int(n), int(id_base), c, e_min, e_max, int(seed)))
+
+    def apply_source(self, src, c, seed):
+        """``Device.apply_source`` on every context of the group (pcl_group_apply_source)."""
+        _source(self.lib.pcl_group_apply_source, self.g, src, c, seed)
 
     @property
     def count(self):

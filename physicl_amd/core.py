@@ -141,15 +141,16 @@ class Object:
 
 
 class PhotonBatch:
-    """``n`` photons described, not instantiated: r = 0, v = (c,0,0), E = min + (max-min) * U**(1/3)
+    """``n`` photons described, not instantiated: r = 0, v = (c,0,0) (or as ``source`` says), E = min + (max-min) * U**(1/3)
     -- what ``light.generate_photons(n, min=, max=)`` makes one Python object at a time
     (physicl/light.py:112-128).  ``Simulation.add_objs(batch)`` creates them directly in device
     memory (1e8 photons take milliseconds instead of hours and ~100 GB of Python objects)."""
 
-    def __init__(self, n, e_min, e_max, seed=0, table=None, fn_vec=None):
+    def __init__(self, n, e_min, e_max, seed=0, table=None, fn_vec=None, source=None):
         self.n, self.e_min, self.e_max, self.seed = int(n), float(np.asarray(e_min)), float(np.asarray(e_max)), int(seed)
         self.table = table        # (cdf, grid): tabulated energy distribution instead of the power law
         self.fn_vec = fn_vec      # fn_vec(size) -> size numbers: the user's own sampler, evaluated on the host in chunks
+        self.source = source      # light.PhotonSource: where the photons start and where they go (None: r = 0, v = (c,0,0))
 
     FN_CHUNK = 1 << 22
 
@@ -452,6 +453,8 @@ class Simulation(threading.Thread):
                 if b.fn_vec is not None:                  # the user's sampler: r, v, ids as filled, E from the host
                     for off, E in b.host_energies(lo, hi):
                         dev.upload(self._hip.E, E.astype(dev.np_dtype, copy=False), off)
+            if b.source is not None:                      # r and v of the photons just created (ids lo .. hi - 1), on the device
+                dev.apply_source(b.source, float(np.asarray(_c)), b.seed)
             self._all_photons = True
             self._alive = b.n
             self._residency = DEVICE

@@ -84,7 +84,75 @@ def generate_photons(n, fn=lambda: np.random.power(3), min=0, max=0, bins=-1, di
     return [PhotonObject(E=min + (max - min) * fn(), v=Measurement([c, 0, 0], "m**1 s**-1")) for _ in range(int(n))]
 
 
-def generate_photons_bulk(n, min=0, max=0, seed=0, T=None, bins=1000, fn_vec=None):
+class PhotonSource:
+    """Where the photons of ``generate_photons_bulk(..., source=)`` start and where they go -- the initial condition of a bulk
+    run (the default is what a PhotonBatch has always been: every photon at the origin, moving along +x).
+
+    ``origin``: the source's centre (numbers in code units, or a Measurement).  ``direction``: its axis, any non-zero vector.
+    ``angular``: "beam" (every photon along the axis), "isotropic" (uniform on the sphere: cos(polar angle) uniform in [-1, 1]
+    -- NOT the reference scatter kernel's angles, which are uniform in the polar angle and so crowd the poles), "cone"
+    (uniform in solid angle within ``half_angle`` radians of the axis, 0 < half_angle <= pi) or "lambertian" (cosine-weighted
+    hemisphere about the axis: emission from a surface).  ``spatial``: "point", "disc" (uniform over a disc of ``radius``) or
+    "gaussian" (a normal spot, sigma = ``radius``), in the plane through ``origin`` perpendicular to the axis.
+
+    The photons are drawn on the device, keyed by the batch's seed and the photon's number (include/physicl_hip.h:
+    pcl_store_apply_source), so a sharded run starts from the very same photons.  The frame the draws are laid out in is made
+    here in float64: d = direction/|direction|; a = the coordinate axis with the smallest |d_k| (the lowest index on a tie);
+    e1 = (a x d)/|a x d|; e2 = d x e1.  For an axis-aligned direction these are exact unit vectors: ``direction=(0, 0, -1)``
+    gives v = (0, 0, -c) bit for bit."""
+
+    def __init__(self, origin=(0, 0, 0), direction=(1, 0, 0), angular="beam", half_angle=None, spatial="point", radius=None):
+        def vec3(x, what):
+            try:
+                a = np.array(x, dtype=np.float64).reshape(-1)
+            except (TypeError, ValueError):
+                raise ValueError("PhotonSource: %s must be three numbers" % what)
+            if a.shape != (3,) or not np.all(np.isfinite(a)):
+                raise ValueError("PhotonSource: %s must be three finite numbers" % what)
+            return a
+        self.origin = vec3(origin, "origin") + 0.0
+        direction = vec3(direction, "direction")
+        norm = float(np.sqrt(np.sum(direction * direction)))
+        if not (norm > 0 and np.isfinite(norm)):
+            raise ValueError("PhotonSource: direction must be a non-zero vector")
+        if angular not in ("beam", "isotropic", "cone", "lambertian"):
+            raise ValueError("PhotonSource: angular must be 'beam', 'isotropic', 'cone' or 'lambertian'")
+        if spatial not in ("point", "disc", "gaussian"):
+            raise ValueError("PhotonSource: spatial must be 'point', 'disc' or 'gaussian'")
+        if (angular == "cone") != (half_angle is not None):
+            raise ValueError("PhotonSource: half_angle is required for, and only allowed with, angular='cone'")
+        if (spatial != "point") != (radius is not None):
+            raise ValueError("PhotonSource: radius is required for, and only allowed with, spatial='disc' / 'gaussian'")
+        self.angular, self.spatial = angular, spatial
+        self.half_angle = self.cos_half_angle = None
+        if half_angle is not None:
+            half_angle = float(np.asarray(half_angle))
+            if not 0.0 < half_angle <= np.pi:
+                raise ValueError("PhotonSource: half_angle must lie in (0, pi] radians")
+            self.half_angle, self.cos_half_angle = half_angle, float(np.cos(half_angle))
+        self.radius = None
+        if radius is not None:
+            radius = float(np.asarray(radius))
+            if not (radius > 0 and np.isfinite(radius)):
+                raise ValueError("PhotonSource: radius must be positive and finite")
+            self.radius = radius
+        d = direction / norm + 0.0                       # (+ 0.0: no negative zeros in the frame)
+        a = np.zeros(3)
+        a[int(np.argmin(np.abs(d)))] = 1.0               # argmin: the lowest index on a tie
+        e1 = np.cross(a, d)
+        e1 = e1 / np.sqrt(np.sum(e1 * e1)) + 0.0
+        self.d, self.e1, self.e2 = d, e1, np.cross(d, e1) + 0.0
+        if self.cos_half_angle is None:
+            self.cos_half_angle = 1.0                    # (unused over the ABI without a cone; radius likewise)
+        if self.radius is None:
+            self.radius = 0.0
+
+    def __repr__(self):
+        return "PhotonSource(origin=%s, direction=%s, angular=%r, half_angle=%r, spatial=%r, radius=%r)" % (
+            self.origin.tolist(), self.d.tolist(), self.angular, self.half_angle, self.spatial, self.radius if self.spatial != "point" else None)
+
+
+def generate_photons_bulk(n, min=0, max=0, seed=0, T=None, bins=1000, fn_vec=None, source=None):
     """``n`` photons created directly in device memory when the simulation first needs them (returns a
     PhotonBatch for ``sim.add_objs``).  Default: the distribution of ``generate_photons`` with its default
     sampler.  With a temperature ``T``: energies from the binned Planck distribution between ``min`` and
@@ -95,13 +163,17 @@ def generate_photons_bulk(n, min=0, max=0, seed=0, T=None, bins=1000, fn_vec=Non
     ``fn`` (physicl/light.py:112-128: ``E = min + (max - min) * fn()`` per photon): evaluated on the host in chunks of 4M
     photons, in photon order, and uploaded; ``fn_vec=lambda size: np.random.power(3, size)`` after ``np.random.seed(s)``
     gives photon i the energy ``generate_photons`` gives it after the same seed (numpy fills an array from the stream
-    its scalar calls walk).  No Python object per photon either way."""
+    its scalar calls walk).  No Python object per photon either way.
+    ``source``: a ``PhotonSource`` -- where the photons start and where they go (default: at the origin, along +x); it
+    combines with every form of the energies above."""
+    if source is not None and not isinstance(source, PhotonSource):
+        raise ValueError("generate_photons_bulk: source must be a PhotonSource")
     if fn_vec is not None:
         if T is not None:
             raise ValueError("generate_photons_bulk: give a temperature T or a sampler fn_vec, not both")
-        return PhotonBatch(n, min, max, seed, fn_vec=fn_vec)
+        return PhotonBatch(n, min, max, seed, fn_vec=fn_vec, source=source)
     if T is None:
-        return PhotonBatch(n, min, max, seed)
+        return PhotonBatch(n, min, max, seed, source=source)
     lo, hi, T_ = (float(np.asarray(v.__unscaled__() if isinstance(v, Measurement) else v)) for v in (min, max, T))
     grid = np.linspace(lo, hi, int(bins))
     xk = grid / (float(np.asarray(kB.__unscaled__())) * T_)
@@ -109,7 +181,7 @@ def generate_photons_bulk(n, min=0, max=0, seed=0, T=None, bins=1000, fn_vec=Non
     cdf = np.cumsum(mass / mass.sum())
     cdf[-1] = 1.0
     scale = float(np.asarray(Measurement(1, "J**1").scale))          # table energies in code units
-    return PhotonBatch(n, lo * scale, hi * scale, seed, table=(cdf, grid[:-1] * scale))
+    return PhotonBatch(n, lo * scale, hi * scale, seed, table=(cdf, grid[:-1] * scale), source=source)
 
 
 # ---------------------------------------------------------------------------------------------- helpers
@@ -758,11 +830,18 @@ def _snap_t(t):
 
 def _batch_photon(sim, i):
     """Photon ``i`` of a PhotonBatch as generate_photons would have made it (physicl/light.py:126-128), for id_info_fn."""
-    # (the energy is looked up while the store still holds every photon at its own index; afterwards it is not known here)
-    E = sim._dev.download(sim._hip.E, 1, int(i)) if (sim.comm is None and sim._dev.is_uniform() and i < sim._dev.count) else np.nan
+    # (the energy is looked up while the store still holds every photon at its own index; afterwards it is not known here;
+    #  a sourced batch's r and v are the store's at that moment -- behind the launch whose rows are being filed -- under the
+    #  same condition, NaN otherwise)
+    known = sim.comm is None and sim._dev.is_uniform() and i < sim._dev.count
+    E = sim._dev.download(sim._hip.E, 1, int(i)) if known else np.nan
     o = PhotonObject.__new__(PhotonObject)
     Object.__init__(o, E=np.double(np.asarray(E).reshape(-1)[0]), v=Measurement._from_code([float(np.asarray(c)), 0, 0], units="m**1 s**-1"),
                     uid=int(i))
+    if getattr(sim._batch, "source", None) is not None:      # a sourced batch: r and v are the store's, known when E is
+        get = lambda fids: [float(sim._dev.download(f, 1, int(i))[0]) if known else np.nan for f in fids]     # noqa: E731
+        o.r = Measurement._from_code(get(sim._hip.FIELD_GROUPS["r"]), units="m**1")
+        o.v = Measurement._from_code(get(sim._hip.FIELD_GROUPS["v"]), units="m**1 s**-1")
     return o
 
 

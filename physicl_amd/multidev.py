@@ -159,6 +159,9 @@ class MultiDevice:
         self._bounds = [shard_range(n, g, G) for g in range(G)]
         self._each(lambda s, b: s.fill_photons_table(b[1] - b[0], id_base + b[0], c, cdf, grid, seed), self._bounds)
 
+    def apply_source(self, src, c, seed):
+        self._each(lambda s: s.apply_source(src, c, seed))       # (ids are global: every shard draws its own photons' blocks)
+
     def upload_state(self, state):
         n, G = len(np.asarray(state["E"])), len(self.shards)
         self._bounds = [shard_range(n, g, G) for g in range(G)]
