@@ -2,12 +2,14 @@
 """A photon source on the Earth's surface under an exponential atmosphere -- the radial variable-n expression of the reference's
 examples (n(r) = 2.5e25 m^-3 * exp(-(|r| - 6371 km) / 8.6 km)) with photons that do NOT start at the origin along +x:
 
-    python examples/point_source_atmosphere.py [n_photons] [passes] [--cone | --beam-down | --default]
+    python examples/point_source_atmosphere.py [n_photons] [passes] [--cone | --beam-down | --default] [--profile]
 
 default: a point source at (6371 km, 0, 0) emitting isotropically; ``--cone``: a 0.3 rad cone pointing up (+x) from a 1 km disc;
 ``--beam-down``: a 10 km gaussian beam entering from 100 km above the surface along -x; ``--default``: the same step list from
 the batch's default source (origin, +x) for comparison.  The photons never exist as Python objects: they are created and given
-their positions and directions on the device, and stepped 32 passes per launch like every other bulk run.
+their positions and directions on the device, and stepped 32 passes per launch like every other bulk run.  ``--profile``
+records where they are every 32 passes -- altitude shells of 5 km up to 200 km (a radius axis about the Earth's centre) and a
+y-z image -- as integer grids made on the device (PositionGridMeasureStep), and prints the last profile.
 """
 import os
 import sys
@@ -43,6 +45,12 @@ signs = light.ScatterSignMeasureStep(None, True)
 sim.add_step(3, signs)
 shells = light.ScatterMeasureStep(None, True, [[R + 20e3, np.nan, np.nan], [np.nan, 0.0, np.nan]])   # 20 km up; the plane y = 0
 sim.add_step(4, shells)
+profile = image = None
+if "--profile" in sys.argv:                                    # behind the last light step: the 32-pass launches are kept
+    profile = light.PositionGridMeasureStep(None, ("r",), [R + np.linspace(0.0, 200e3, 41)], every=32)
+    image = light.PositionGridMeasureStep(None, ("y", "z"), [np.linspace(-300e3, 300e3, 129)] * 2, every=32, measure_n=False)
+    sim.add_step(5, profile)
+    sim.add_step(6, image)
 sim.add_objs(light.generate_photons_bulk(n, min=light.E_from_wavelength(700e-9), max=light.E_from_wavelength(200e-9), seed=1234, source=source))
 
 sim.prepare()                                                  # the photons are created now: run_time below is stepping only
@@ -59,3 +67,10 @@ for row in signs.data[-3:]:
 for row in shells.data[-3:]:
     print("[t, N, crossed x = R + 20 km, crossed y = 0]:", [float(x) for x in row])
 print("scattered in the last step:", sim.hits)
+if profile is not None and profile.data:
+    t, N, shells_now = profile.data[-1]
+    print("altitude profile at t = %g s (%d records, one every 32 passes): %d of %d photons between 0 and 200 km" % (float(t), len(profile.data), shells_now.sum(), N))
+    for k in range(0, 40, 4):
+        print("  %3d - %3d km: %d" % (5 * k, 5 * k + 20, shells_now[k:k + 4].sum()))
+    img = image.data[-1][1]
+    print("y-z image, 128 x 128 cells of 4.7 km: %d photons inside, %d cells hit, brightest cell %d" % (img.sum(), np.count_nonzero(img), img.max()))

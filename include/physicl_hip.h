@@ -549,6 +549,41 @@ int pcl_step_counters(pcl_ctx *ctx, const double *planes_host, int n_planes, int
 int pcl_step_plane_spectra(pcl_ctx *ctx, const double *planes_host, int n_planes, const double *edges_host, int n_bins,
                            int64_t *counts_out_host, int64_t *hist_out_host);
 
+/* Where the particles are: an integer histogram of the store's positions over one to three axes, made in one sweep of the
+ * resident store -- an altitude profile (one PCL_GRID_RADIUS axis about the planet's centre), an image (two Cartesian axes), a
+ * coarse volume density (three) -- as int64 cells that add across devices and ranks like every other counter row.  The other
+ * way to it is a download of r (24 B per particle over the host link) and numpy.histogramdd.
+ * coords_host[a]: the coordinate axis a bins (each at most once); n_bins_host[a]: its bins, 1..PCL_GRID_MAX_BINS, the product
+ * at most PCL_GRID_MAX_CELLS; edges_host: the axes' n_bins[a] + 1 edges one after another, finite and strictly increasing, in
+ * code units; center_host: 3 finite doubles, NULL = the origin.  grid_out_host: prod(n_bins) cells in C order, first axis slowest.
+ * EVERY particle of the store counts, plain Objects included (as N and the plane counters; no kind bytes are read).
+ * A Cartesian axis: the particle is in bin b iff e_b <= x < e_(b+1), the last bin closed -- exactly
+ * numpy.histogramdd(sample, bins=[edges...]); only comparisons are made, an fp32 store's value is widened to double first
+ * (exact).  A particle with any coordinate outside its axis's range, or NaN, is in no cell.
+ * PCL_GRID_RADIUS bins q = ((x-cx)*(x-cx) + (y-cy)*(y-cy)) + (z-cz)*(z-cz), evaluated in fp64, unfused, in that order, against
+ * the SQUARED edges e*e, which the entry point makes on the host: there is no square root anywhere, so numpy restates the
+ * result exactly -- and it is NOT histogram(sqrt(q)) for a particle within an ulp of an edge.  Radius edges must be >= 0,
+ * their squares finite and strictly increasing.
+ * PCL_ERR_ARG (a NULL pointer, n_axes outside 1..3, an unknown or repeated coordinate, a bin count outside 1..1024, too many
+ * cells, edges not finite or not strictly increasing, a non-finite centre) is returned before anything is launched or written;
+ * PCL_ERR_STATE without a store; an empty store answers zeros without a launch.  Host pointers; synchronises once, with the
+ * one copy of the grid.  The store is seen dense with r current (pcl_store_field_ptr(PCL_R0..R2): nothing is invalidated).
+ * Grids of up to 4096 cells are accumulated per workgroup in LDS, larger ones with 64-bit atomics on the device grid; the
+ * environment variable PCL_GRID_LDS_CELLS (read per call, 0..8192) moves that switch-over -- same cells either way.
+ * pcl_last_error() is generic for these two entry points, as for pcl_step_plane_spectra: they are compiled from a source file
+ * of their own (physicl_amd/csrc/pcl_grid.hip) on top of the functions above. */
+#define PCL_GRID_X 0
+#define PCL_GRID_Y 1
+#define PCL_GRID_Z 2
+#define PCL_GRID_RADIUS 3          /* distance from center_host */
+#define PCL_GRID_MAX_AXES 3
+#define PCL_GRID_MAX_BINS 1024     /* per axis */
+#define PCL_GRID_MAX_CELLS (1 << 20)
+int pcl_step_position_grid(pcl_ctx *ctx, int n_axes, const int *coords_host, const int *n_bins_host,
+                           const double *edges_host,   /* the axes' edges one after another: sum(n_bins[a] + 1) */
+                           const double *center_host,  /* 3 doubles, NULL = origin; used by PCL_GRID_RADIUS only */
+                           int64_t *grid_out_host);    /* prod(n_bins) cells, C order, first axis slowest */
+
 /* ---- Device groups: several GPUs from ONE process ---------------------------------------------------------------
  * The reference is a single process with one simulation thread (physicl/__init__.py:400-432, 501-524); this is how
  * a host written against this ABI uses a node's GPUs the same way, without one process per GPU.  A group owns one
@@ -600,6 +635,10 @@ int pcl_group_step_plane_spectra(pcl_group *group, const double *planes_host, in
                                  int64_t *counts_out_host, int64_t *hist_out_host);
 /* pcl_store_apply_source on every shard of a group filled with pcl_group_fill_photons (ids are global: the same photons) */
 int pcl_group_apply_source(pcl_group *group, const pcl_source *src, double c, uint64_t seed);
+/* pcl_step_position_grid on every shard (side by side), the grids summed over the group's devices; the arguments are checked
+ * once for the group, before any shard is asked */
+int pcl_group_step_position_grid(pcl_group *group, int n_axes, const int *coords_host, const int *n_bins_host,
+                                 const double *edges_host, const double *center_host, int64_t *grid_out_host);
 
 /* ---------------------------------------------------------------- the counters' collective (one process per GPU)
  * The path shards by global index with no data-path exchange; the only global quantities are the int64

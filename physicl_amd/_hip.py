@@ -24,6 +24,8 @@ CNT_N, CNT_XP, CNT_YP, CNT_ZP, CNT_PLANE0 = 0, 1, 2, 3, 4
 MAX_PLANES = 12
 SRC_ANGULAR = {"beam": 0, "isotropic": 1, "cone": 2, "lambertian": 3}       # PCL_SRC_BEAM ...
 SRC_SPATIAL = {"point": 0, "disc": 1, "gaussian": 2}                         # PCL_SRC_POINT ...
+GRID_COORDS = {"x": 0, "y": 1, "z": 2, "r": 3}                               # PCL_GRID_X ... PCL_GRID_RADIUS
+GRID_MAX_AXES, GRID_MAX_BINS, GRID_MAX_CELLS = 3, 1024, 1 << 20
 PROF_NEWTON, PROF_SCATTER, PROF_DELETE_MASK, PROF_COMPACT, PROF_COUNTERS, PROF_FUSED, PROF_MULTI, PROF_ONEPASS, \
     PROF_DELETE_AHEAD = range(9)
 PROF_NAMES = {PROF_NEWTON: "k_newton", PROF_SCATTER: "k_scatter", PROF_DELETE_MASK: "k_delete_mask",
@@ -143,6 +145,7 @@ _PROTOTYPES = {
     "pcl_store_last_delete_flags": [_vp, _vp, c_int64],
     "pcl_step_counters": [_vp, _vp, c_int, _vp],
     "pcl_step_plane_spectra": [_vp, _vp, c_int, _vp, c_int, _vp, _vp],
+    "pcl_step_position_grid": [_vp, c_int, _vp, _vp, _vp, _vp, _vp],
     # device groups: several GPUs from one process (the C-level counterpart of physicl_amd.multidev.MultiDevice)
     "pcl_group_create": [c_int, POINTER(c_int), POINTER(_vp)],
     "pcl_group_destroy": [_vp],
@@ -167,6 +170,7 @@ _PROTOTYPES = {
     "pcl_group_download_ids": [_vp, _vp, c_int64, c_int64],
     "pcl_group_step_plane_spectra": [_vp, _vp, c_int, _vp, c_int, _vp, _vp],
     "pcl_group_apply_source": [_vp, _vp, c_double, c_uint64],
+    "pcl_group_step_position_grid": [_vp, c_int, _vp, _vp, _vp, _vp, _vp],
 }
 EXPORTS = sorted(list(_PROTOTYPES) + ["pcl_last_error"])
 
@@ -284,6 +288,22 @@ def _spectra(entry, handle, planes, edges):
     counts, hist = np.zeros(npl, dtype=np.int64), np.zeros((npl, max(n_bins, 0)), dtype=np.int64)
     check(entry(handle, pp, npl, ed.ctypes.data, n_bins, counts.ctypes.data, hist.ctypes.data))
     return counts, hist
+
+
+def _grid(entry, handle, axes, edges, center=None):
+    """One call of pcl_step_position_grid / pcl_group_step_position_grid: the int64 grid of shape (bins of axis 0, ...).
+    ``axes``: "x", "y", "z", "r" (or the header's numbers), ``edges``: one sequence of edges per axis."""
+    coords = np.array([GRID_COORDS.get(a, a) for a in axes], dtype=np.int32)
+    per_axis = [np.ascontiguousarray(e, dtype=np.float64).reshape(-1) for e in edges]
+    if len(per_axis) != len(coords):
+        raise ValueError("one sequence of edges per axis: %d axes, %d sequences" % (len(coords), len(per_axis)))
+    n_bins = np.array([len(e) - 1 for e in per_axis], dtype=np.int32)
+    ed = np.ascontiguousarray(np.concatenate(per_axis)) if per_axis else np.zeros(0)
+    ce = None if center is None else np.ascontiguousarray(center, dtype=np.float64).reshape(3)
+    out = np.zeros([max(int(b), 0) for b in n_bins], dtype=np.int64)
+    check(entry(handle, len(coords), coords.ctypes.data, n_bins.ctypes.data, ed.ctypes.data, None if ce is None else ce.ctypes.data,
+                out.ctypes.data))
+    return out
 
 
 class SourceStruct(ctypes.Structure):
@@ -845,6 +865,13 @@ class Device:
         planes in one sweep of the store: (counts int64[P], hist int64[P, B]).  ScatterMeasureStep(measure_E=True, E_bins=...)."""
         return _spectra(self.lib.pcl_step_plane_spectra, self.ctx, planes, edges)
 
+    def position_grid(self, axes, edges, center=None):
+        """Where the particles of the store are: the int64 histogram of their positions over the ``axes`` ("x", "y", "z",
+        or "r", the distance from ``center``; one to three, each once), ``edges[a]`` the bin edges of axis a -- shape (bins of
+        axis 0, ...), counted as ``numpy.histogramdd`` counts (a radius axis compares the squared distance with the squared
+        edges), every particle of the store, in one sweep (pcl_step_position_grid).  PositionGridMeasureStep."""
+        return _grid(self.lib.pcl_step_position_grid, self.ctx, axes, edges, center)
+
 
 class DeviceGroup:
     """``pcl_group_*``: several contexts in one process, sharded by global index, behind the C ABI (the shim owns the
@@ -936,6 +963,10 @@ class DeviceGroup:
     def plane_spectra(self, planes, edges):
         """``Device.plane_spectra`` summed over the group's contexts (pcl_group_step_plane_spectra)."""
         return _spectra(self.lib.pcl_group_step_plane_spectra, self.g, planes, edges)
+
+    def position_grid(self, axes, edges, center=None):
+        """``Device.position_grid`` summed over the group's contexts (pcl_group_step_position_grid)."""
+        return _grid(self.lib.pcl_group_step_position_grid, self.g, axes, edges, center)
 
     def download(self, field, n=None, offset=0, dtype=None):
         n = self.count - offset if n is None else n

@@ -55,7 +55,7 @@ def _deal_planes(measures, crossed, at=0):
     """The plane columns ``crossed`` of a group's counter rows (one row or a block), dealt to its counting measure steps
     in order from column ``at``: yields (step, its columns)."""
     for m in measures:
-        if m._fuse_role != "trace":                   # (a TracePathMeasureStep has no planes and files no counter row)
+        if m._fuse_role not in ("trace", "snapshot"):  # (a TracePathMeasureStep / PositionGridMeasureStep has no planes and files no counter row)
             yield m, crossed[..., at:at + m._n_planes()]
             at += m._n_planes()
 
@@ -618,7 +618,7 @@ class Simulation(threading.Thread):
                     group.append(steps[j])
                     j += 1
                 n_planes = 0
-                while j < len(steps) and getattr(steps[j], "_fuse_role", None) in ("measure", "trace") and \
+                while j < len(steps) and getattr(steps[j], "_fuse_role", None) in ("measure", "trace", "snapshot") and \
                         n_planes + steps[j]._n_planes() <= _MAX_PLANES:
                     n_planes += steps[j]._n_planes()
                     group.append(steps[j])
@@ -681,12 +681,19 @@ class Simulation(threading.Thread):
                 return False
             roles = [s._fuse_role for s in group]
             if roles[0] != "newton" or len(roles) < 2 or roles[1] not in ("scatter_iso", "scatter_delete") or \
-                    any(r not in ("measure", "trace") for r in roles[2:]) or roles[1] in seen:
+                    any(r not in ("measure", "trace", "snapshot") for r in roles[2:]) or roles[1] in seen:
                 return False
             seen.append(roles[1])
         if sum(m._n_planes() for _, group in plan[1:] for m in group[2:]) > self._hip.MAX_PLANES:
             return False
         if self._rng_mode() != self._hip.RNG_PHILOX:
+            return False
+        # a snapshot step (PositionGridMeasureStep) looks at the store itself: a launch can only end on its pass if nothing
+        # moves the particles after it within the pass, i.e. if it rides at the end of the pass's LAST group.  (Only here, in a
+        # pass that could otherwise run K passes per launch, is the step the reason for one launch per light step.)
+        if any(m._fuse_role == "snapshot" for _, group in plan[1:-1] for m in group[2:]):
+            self.launch_note = "one launch per light step: a PositionGridMeasureStep sits before the pass's last light step " \
+                               "(it reads the store where it stands; only behind the last light step can a launch end on its pass)"
             return False
         # a TracePathMeasureStep in the loop: its tracked subset is worked out on the device ahead of every launch
         # (pcl_store_trace_ahead) -- or, if it cannot be (it asks for more particles than that takes), the loop runs one
@@ -805,6 +812,10 @@ class Simulation(threading.Thread):
         k_max = self._k_wanted()
         if self.steps_per_launch is None and phases == ["delete"]:
             k_max = 64                                # (automatic, delete-only loop: see above)
+        # PositionGridMeasureStep (last group only, _multi_eligible): the launch ends on the earliest pass one of them records
+        snaps = [m for m in groups[-1][2:] if m._fuse_role == "snapshot"]
+        if snaps:
+            k_max = min(k_max, min(m._passes_to_record() for m in snaps))
         times, dt0 = self._plan_passes(upd, max(1, min(k_max, 64 // P)), has_delete)
         k = len(times)
         if k == 0:
@@ -836,7 +847,8 @@ class Simulation(threading.Thread):
             raw = dev.step_fused_multi(dt0, k, sc, planes, raw=True)
             self.schedule["fused_multi"] += 1
         elif phases == ["delete"]:
-            raw = dev.step_fused_delete_multi(dt0, k, dl[0], dl[1], self.seed, step0, planes if groups[0][2:] else None, raw=True)
+            counted = any(m._fuse_role != "snapshot" for m in groups[0][2:])
+            raw = dev.step_fused_delete_multi(dt0, k, dl[0], dl[1], self.seed, step0, planes if counted else None, raw=True)
             self.schedule["fused_delete_multi"] += 1
         else:
             raw = dev.step_mixed_multi(dt0, k, phases, sc, dl, planes, self.seed, step0, raw=True)
@@ -883,6 +895,11 @@ class Simulation(threading.Thread):
                     break
                 ts.extend(later)
         flush(keep)
+        # the store now stands where pass ``keep`` left it (a delete loop cut short at keep < k was cut because the store was empty
+        # from that pass on), and sim.t is that pass's time: the snapshot steps whose recording run this is look at it
+        for m in snaps:
+            if m._advance(keep):
+                m._take(self)
         return True
 
     def _run_fused(self, group):
@@ -892,6 +909,7 @@ class Simulation(threading.Thread):
         delete = next((s for s in group if s._fuse_role == "scatter_delete"), None)
         measures = [s for s in group if s._fuse_role == "measure"]
         tracers = [s for s in group if s._fuse_role == "trace"]
+        snaps = [s for s in group if s._fuse_role == "snapshot"]    # run on the store behind the launch and its rows
         planes = [p for m in measures for p in m._plane_rows()]
 
         def trace_ahead(phase, sc_, dl_, step):
@@ -932,6 +950,8 @@ class Simulation(threading.Thread):
             self._alive, delete.removed = int(n), int(removed)
             file_row(n, sign, crossed)
             trace_file(ahead)
+            for m in snaps:
+                m._device_run(self)
             return
         sc = None
         ahead = []
@@ -954,6 +974,8 @@ class Simulation(threading.Thread):
             row[:hip._EVENT] = self._global(row[:hip._EVENT])   # (two reductions, hits and the rest: number and lengths are fixed)
             file_row(*hip._split_rows(row)[:3])
         trace_file(ahead)
+        for m in snaps:
+            m._device_run(self)
 
     def run(self):
         # HIP's current device is per thread and a thread's first HIP call sets its runtime state up (tenths of a millisecond):

@@ -1,0 +1,345 @@
+// pcl_grid.hip -- binned position grids (PositionGridMeasureStep): where the particles of the store are, as an integer
+// histogram over one to three axes (x, y, z, or the distance from a centre), made in one sweep of the resident store.
+//
+// A translation unit of its own, linked into libphysicl_hip.so behind pcl_spectrum.hip and pcl_source.hip: it does not see
+// struct pcl_ctx and works through the public C ABI (include/physicl_hip.h) like any other host of the library.  The tuned
+// kernels, their register budgets and the source hash the counter records are tied to (physicl_amd/build.py: csrc_sha) are
+// not touched by anything here.
+//
+//   k_position_grid<T, lds>   one grid-stride sweep of the tiled slab: per slot the r rows some axis needs (all three for a
+//                             radius axis), a binary search per axis in the edges (LDS), then one add to the slot's cell --
+//                             lds = true:  into a workgroup-private uint32 histogram in LDS, flushed at the end with 64-bit
+//                                          atomics on the non-zero cells (grids of up to PCL_GRID_LDS_CELLS cells);
+//                             lds = false: 64-bit atomics straight onto the device grid (up to PCL_GRID_MAX_CELLS cells).
+//                             A wave whose in-range lanes all hold the same cell -- the population every bulk run starts
+//                             from -- issues ONE add of their count instead of up to 64 adds to one address, and one add
+//                             for a whole run of such trips in the same cell.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+#include <system_error>
+#include <thread>
+#include <vector>
+
+#include "../../include/physicl_hip.h"
+
+namespace {
+
+constexpr int kBlock = 256;                 // 4 wave64 per workgroup, as the library's sweeps
+constexpr int kWorkgroupsPerCU = 8;         // grid cap of the sweep: resident workgroups, each takes the same number of trips
+constexpr int kLdsPerCU = 160 * 1024;       // gfx950
+// The LDS form's switch-over: grids of up to this many cells are accumulated per workgroup in LDS.  4096 cells are 16 KiB;
+// with the largest edge table (3 x 1025 doubles, 24 KiB) a workgroup then holds 40 KiB and three of them (12 waves) share
+// a CU, a 64 x 64 image with its 130 edges holds 17 KiB and all eight do ("Position grids").  PCL_GRID_LDS_CELLS
+// (environment, read per call) moves it, up to kLdsCellsMax: edges + histogram stay below the 64 KiB a launch may ask for.
+constexpr int kLdsCellsDefault = 4096;
+constexpr int kLdsCellsMax = 8192;
+// A workgroup-private cell is a uint32: a workgroup adds at most one per slot, and the entry point bounds a workgroup to
+// fewer than 2^32 slots (kMaxSlotsPerWorkgroup), so it cannot overflow.
+constexpr int64_t kMaxSlotsPerWorkgroup = ((int64_t)1 << 32) - kBlock;
+
+template <typename T>
+struct grid_args {
+    const T *r[3];               // rows some axis needs (NULL otherwise)
+    const double *edges;         // the axes' edges one after another (a radius axis: squared), device
+    unsigned long long *grid;    // [n_cells], device, zeroed by the entry point
+    int64_t N, ts;               // particles, tile stride of the slab (elements)
+    int tile_log;                // log2 of the tile length (pcl_store_layout: 2048 particles)
+    int n_axes, n_edges, n_cells;
+    int coord[PCL_GRID_MAX_AXES], n_bins[PCL_GRID_MAX_AXES], edge_at[PCL_GRID_MAX_AXES];
+    int rows;                    // bit k: row k is read
+    double c[3];                 // centre of a radius axis
+};
+
+template <typename T, bool kLds>
+__global__ void __launch_bounds__(kBlock) k_position_grid(grid_args<T> a) {
+    extern __shared__ double s_mem[];                                  // edges | histogram (LDS form)
+    double *s_edges = s_mem;
+    uint32_t *s_hist = reinterpret_cast<uint32_t *>(s_mem + a.n_edges);
+    for (int k = threadIdx.x; k < a.n_edges; k += kBlock) s_edges[k] = a.edges[k];
+    if (kLds)
+        for (int k = threadIdx.x; k < a.n_cells; k += kBlock) s_hist[k] = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    // whole waves run the same number of trips (the ballots below need every lane of the wave inside the loop)
+    const int64_t n_round = (a.N + 63) / 64 * 64;
+    // wave-uniform: the cell and the count of consecutive trips whose in-range lanes all sat in that one cell, not added yet
+    // (fewer than 2^32: kMaxSlotsPerWorkgroup).  Adds to ONE address serialise where they are carried out -- the untouched
+    // fill through the global form was 19 ms at 1e8 photons with an add per trip (CHANGELOG.md) --, so a run is added once.
+    int run_cell = 0;
+    uint32_t run_n = 0;
+    auto flush_run = [&]() {
+        if (lane == 0 && run_n) {
+            if (kLds) atomicAdd(&s_hist[run_cell], run_n);
+            else atomicAdd(&a.grid[run_cell], (unsigned long long)run_n);
+        }
+        run_n = 0;
+    };
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n_round; i += stride) {
+        bool ok = i < a.N;
+        const int64_t ti = (i >> a.tile_log) * a.ts + (i & (((int64_t)1 << a.tile_log) - 1));
+        double x[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            if (ok && ((a.rows >> k) & 1)) x[k] = (double)a.r[k][ti]; // fp32 widens exactly
+        int cell = 0;
+        for (int ax = 0; ax < a.n_axes; ++ax) {
+            const int co = a.coord[ax], nb = a.n_bins[ax];
+            const double *e = s_edges + a.edge_at[ax];
+            double v;
+            if (co == PCL_GRID_RADIUS) {       // q, unfused, in this order (the library is built with -ffp-contract=off)
+                const double dx = x[0] - a.c[0], dy = x[1] - a.c[1], dz = x[2] - a.c[2];
+                v = (dx * dx + dy * dy) + dz * dz;
+            } else {
+                v = co == 0 ? x[0] : (co == 1 ? x[1] : x[2]);
+            }
+            ok = ok && v >= e[0] && v <= e[nb];  // NaN and anything outside the axis's range are in no cell
+            int lo = 0, hi = nb;                 // invariant: e[lo] <= v, and v < e[hi] or hi == nb
+            while (hi - lo > 1) {
+                const int mid = (lo + hi) >> 1;
+                if (e[mid] <= v) lo = mid; else hi = mid;
+            }
+            // lo = the last edge <= v among e[0 .. nb - 1]: bins [e_b, e_b+1), the last one closed (numpy.histogramdd)
+            cell = cell * nb + lo;
+        }
+        const unsigned long long m = __ballot(ok);
+        if (m) {
+            const int first = __ffsll((long long)m) - 1;
+            const int c0 = __shfl(cell, first);
+            if (__ballot(ok && cell == c0) == m) { // every in-range lane of the wave in one cell: one add of their count,
+                if (c0 != run_cell) {              // put off while the next trips land in the same cell
+                    flush_run();
+                    run_cell = c0;
+                }
+                run_n += (uint32_t)__popcll(m);
+            } else if (ok) {
+                if (kLds) atomicAdd(&s_hist[cell], 1u);
+                else atomicAdd(&a.grid[cell], 1ull);
+            }
+        }
+    }
+    flush_run();
+    if (kLds) {
+        __syncthreads();
+        for (int k = threadIdx.x; k < a.n_cells; k += kBlock)
+            if (s_hist[k]) atomicAdd(&a.grid[k], (unsigned long long)s_hist[k]);
+    }
+}
+
+// The calling thread's message (pcl_last_error) lives in the core unit and has no setter in the ABI: a refused call leaves
+// the core's own generic "bad argument" there, as pcl_spectrum.hip does (include/physicl_hip.h says so).
+int bad_argument(pcl_ctx *ctx) {
+    void *none = nullptr;
+    if (ctx) (void)pcl_dev_alloc(ctx, -1, &none);
+    return PCL_ERR_ARG;
+}
+
+#define GRD_TRY(expr)                    \
+    do {                                 \
+        int rc__ = (expr);               \
+        if (rc__ != PCL_OK) return rc__; \
+    } while (0)
+
+struct dev_block { // one device allocation per call, handed back on every way out
+    pcl_ctx *ctx;
+    void *p = nullptr;
+    explicit dev_block(pcl_ctx *c) : ctx(c) {}
+    ~dev_block() { if (p) pcl_dev_free(ctx, p); }
+};
+
+struct grid_spec { // a call's arguments, checked; what the kernel compares against
+    int n_axes = 0, n_edges = 0, rows = 0;
+    int64_t cells = 1;
+    int coord[PCL_GRID_MAX_AXES], n_bins[PCL_GRID_MAX_AXES], edge_at[PCL_GRID_MAX_AXES];
+    double c[3] = {0.0, 0.0, 0.0};
+    std::vector<double> edges; // a radius axis: squared
+};
+
+// Everything PCL_ERR_ARG stands for except the NULL context; nothing is launched or written before this has passed.
+bool check_spec(int n_axes, const int *coords, const int *n_bins, const double *edges, const double *center, int64_t *grid_out,
+                grid_spec &s) {
+    if (!coords || !n_bins || !edges || !grid_out) return false;
+    if (n_axes < 1 || n_axes > PCL_GRID_MAX_AXES) return false;
+    int seen = 0;
+    for (int a = 0; a < n_axes; ++a) {
+        if (coords[a] < PCL_GRID_X || coords[a] > PCL_GRID_RADIUS || ((seen >> coords[a]) & 1)) return false;
+        seen |= 1 << coords[a];
+        if (n_bins[a] < 1 || n_bins[a] > PCL_GRID_MAX_BINS) return false;
+        s.cells *= n_bins[a];
+    }
+    if (s.cells > PCL_GRID_MAX_CELLS) return false;
+    if (center)
+        for (int k = 0; k < 3; ++k) {
+            if (!std::isfinite(center[k])) return false;
+            s.c[k] = center[k];
+        }
+    s.n_axes = n_axes;
+    for (int a = 0; a < n_axes; ++a) {
+        s.coord[a] = coords[a];
+        s.n_bins[a] = n_bins[a];
+        s.edge_at[a] = s.n_edges;
+        s.rows |= coords[a] == PCL_GRID_RADIUS ? 7 : 1 << coords[a];
+        const double *e = edges + s.n_edges;
+        for (int b = 0; b <= n_bins[a]; ++b) {
+            double v = e[b];
+            if (!std::isfinite(v)) return false;
+            if (coords[a] == PCL_GRID_RADIUS) { // q is compared against e*e: no square root anywhere
+                if (v < 0) return false;
+                v = v * v;
+                if (!std::isfinite(v)) return false;
+            }
+            if (b > 0 && !(v > s.edges.back())) return false;
+            s.edges.push_back(v);
+        }
+        s.n_edges += n_bins[a] + 1;
+    }
+    return true;
+}
+
+int lds_cells_now() { // the switch-over of this call
+    const char *t = getenv("PCL_GRID_LDS_CELLS");
+    if (!t || !*t) return kLdsCellsDefault;
+    char *end = nullptr;
+    const long v = strtol(t, &end, 10);
+    if (end == t) return kLdsCellsDefault;
+    return v < 0 ? 0 : (v > kLdsCellsMax ? kLdsCellsMax : (int)v);
+}
+
+template <typename T>
+int launch_grid(pcl_ctx *ctx, hipStream_t stream, const grid_spec &s, const double *edges_dev, unsigned long long *grid_dev, int64_t N,
+                int64_t ts, int tile_log, int n_cu) {
+    grid_args<T> a{};
+    for (int k = 0; k < 3; ++k) {
+        if (!((s.rows >> k) & 1)) continue;
+        void *r = nullptr;
+        GRD_TRY(pcl_store_field_ptr(ctx, PCL_R0 + k, &r));
+        a.r[k] = static_cast<const T *>(r);
+    }
+    a.edges = edges_dev; a.grid = grid_dev;
+    a.N = N; a.ts = ts; a.tile_log = tile_log;
+    a.n_axes = s.n_axes; a.n_edges = s.n_edges; a.n_cells = (int)s.cells; a.rows = s.rows;
+    for (int k = 0; k < s.n_axes; ++k) { a.coord[k] = s.coord[k]; a.n_bins[k] = s.n_bins[k]; a.edge_at[k] = s.edge_at[k]; }
+    for (int k = 0; k < 3; ++k) a.c[k] = s.c[k];
+    const bool lds_form = s.cells <= lds_cells_now();
+    const size_t lds = (size_t)s.n_edges * sizeof(double) + (lds_form ? (size_t)s.cells * sizeof(uint32_t) : 0);
+    // resident workgroups only: every workgroup of the LDS form flushes its own histogram
+    int per_cu = (int)(kLdsPerCU / (lds > 0 ? lds : 1));
+    per_cu = per_cu < 1 ? 1 : (per_cu > kWorkgroupsPerCU ? kWorkgroupsPerCU : per_cu);
+    const int64_t blocks = (N + kBlock - 1) / kBlock;
+    int64_t grid = blocks, cap = (int64_t)(n_cu > 0 ? n_cu : 256) * per_cu;
+    if (grid > cap) {
+        int64_t trips = (blocks + cap - 1) / cap;
+        while (trips * kBlock > kMaxSlotsPerWorkgroup) { cap *= 2; trips = (blocks + cap - 1) / cap; } // (never, below 2^43 slots)
+        grid = (blocks + trips - 1) / trips; // every workgroup takes the same number of trips
+    }
+    if (lds_form) hipLaunchKernelGGL((k_position_grid<T, true>), dim3((unsigned)grid), dim3(kBlock), lds, stream, a);
+    else hipLaunchKernelGGL((k_position_grid<T, false>), dim3((unsigned)grid), dim3(kBlock), lds, stream, a);
+    return hipGetLastError() == hipSuccess ? PCL_OK : PCL_ERR_HIP;
+}
+
+int position_grid(pcl_ctx *ctx, int n_axes, const int *coords_host, const int *n_bins_host, const double *edges_host,
+                  const double *center_host, int64_t *grid_out_host) {
+    grid_spec s;
+    if (!ctx || !check_spec(n_axes, coords_host, n_bins_host, edges_host, center_host, grid_out_host, s)) return bad_argument(ctx);
+    // the first look at the store: a store behind an alive mask becomes dense, r current (PCL_ERR_STATE without a store)
+    void *r_first = nullptr;
+    for (int k = 0; k < 3; ++k)
+        if ((s.rows >> k) & 1) { GRD_TRY(pcl_store_field_ptr(ctx, PCL_R0 + k, &r_first)); break; }
+    int64_t N = 0, tile = 0, ts = 0;
+    GRD_TRY(pcl_store_count(ctx, &N));
+    const size_t out_bytes = (size_t)s.cells * sizeof(uint64_t), edge_bytes = (size_t)s.n_edges * sizeof(double);
+    if (N <= 0) {
+        memset(grid_out_host, 0, out_bytes);
+        return PCL_OK;
+    }
+    int dtype = PCL_DTYPE_F64, n_cu = 0;
+    GRD_TRY(pcl_store_dtype(ctx, &dtype));
+    GRD_TRY(pcl_store_layout(ctx, &tile, &ts));
+    int tile_log = 0;
+    while (((int64_t)1 << tile_log) < tile) ++tile_log;
+    if (((int64_t)1 << tile_log) != tile) return PCL_ERR_STATE; // the slab's tiles are a power of two long
+    GRD_TRY(pcl_ctx_device_info(ctx, nullptr, 0, nullptr, &n_cu, nullptr));
+    void *stream_v = nullptr;
+    GRD_TRY(pcl_ctx_stream(ctx, &stream_v));
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+
+    dev_block blk(ctx);
+    GRD_TRY(pcl_dev_alloc(ctx, (int64_t)(out_bytes + edge_bytes), &blk.p));
+    char *base = static_cast<char *>(blk.p);
+    if (hipMemsetAsync(base, 0, out_bytes, stream) != hipSuccess) return PCL_ERR_HIP;
+    if (hipMemcpyAsync(base + out_bytes, s.edges.data(), edge_bytes, hipMemcpyHostToDevice, stream) != hipSuccess) return PCL_ERR_HIP;
+    const double *edges_dev = reinterpret_cast<const double *>(base + out_bytes);
+    unsigned long long *grid_dev = reinterpret_cast<unsigned long long *>(base);
+    GRD_TRY(dtype == PCL_DTYPE_F64 ? launch_grid<double>(ctx, stream, s, edges_dev, grid_dev, N, ts, tile_log, n_cu)
+                                   : launch_grid<float>(ctx, stream, s, edges_dev, grid_dev, N, ts, tile_log, n_cu));
+    return pcl_d2h(ctx, grid_out_host, base, (int64_t)out_bytes); // the call's one synchronisation (a count is below 2^63)
+}
+
+int group_position_grid(pcl_group *group, int n_axes, const int *coords_host, const int *n_bins_host, const double *edges_host,
+                        const double *center_host, int64_t *grid_out_host) {
+    int n = 0;
+    GRD_TRY(pcl_group_size(group, &n));
+    std::vector<pcl_ctx *> ctx((size_t)n);
+    for (int g = 0; g < n; ++g) GRD_TRY(pcl_group_ctx(group, g, &ctx[(size_t)g]));
+    grid_spec s;
+    if (n < 1 || !check_spec(n_axes, coords_host, n_bins_host, edges_host, center_host, grid_out_host, s))
+        return bad_argument(n > 0 ? ctx[0] : nullptr);
+    const size_t cells = (size_t)s.cells;
+    std::vector<std::vector<int64_t>> part((size_t)n, std::vector<int64_t>(cells, 0));
+    std::vector<int> rcs((size_t)n, PCL_OK);
+    auto one = [&](int g) {
+        rcs[(size_t)g] = pcl_step_position_grid(ctx[(size_t)g], n_axes, coords_host, n_bins_host, edges_host, center_host, part[(size_t)g].data());
+    };
+    // the shards' sweeps run side by side: a thread each per call (the group's own workers cannot be reached through the
+    // ABI), the calling thread takes shard 0.  A shard whose thread cannot be started is served by the calling thread.
+    std::vector<std::thread> th;
+    th.reserve((size_t)n);
+    for (int g = 1; g < n; ++g) {
+        try {
+            th.emplace_back(one, g);
+        } catch (const std::system_error &) {
+            one(g);
+        }
+    }
+    one(0);
+    for (auto &t : th) t.join();
+    for (int g = 0; g < n; ++g) GRD_TRY(rcs[(size_t)g]);
+    memset(grid_out_host, 0, cells * sizeof(int64_t));
+    for (int g = 0; g < n; ++g)
+        for (size_t k = 0; k < cells; ++k) grid_out_host[k] += part[(size_t)g][k];
+    return PCL_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+// Nothing may be thrown through the C boundary: host allocations of the bodies above (the edges, the per-shard grids) can fail.
+int pcl_step_position_grid(pcl_ctx *ctx, int n_axes, const int *coords_host, const int *n_bins_host, const double *edges_host,
+                           const double *center_host, int64_t *grid_out_host) {
+    try {
+        return position_grid(ctx, n_axes, coords_host, n_bins_host, edges_host, center_host, grid_out_host);
+    } catch (const std::bad_alloc &) {
+        return PCL_ERR_NOMEM;
+    } catch (...) {
+        return PCL_ERR_HIP;
+    }
+}
+
+int pcl_group_step_position_grid(pcl_group *group, int n_axes, const int *coords_host, const int *n_bins_host, const double *edges_host,
+                                 const double *center_host, int64_t *grid_out_host) {
+    try {
+        return group_position_grid(group, n_axes, coords_host, n_bins_host, edges_host, center_host, grid_out_host);
+    } catch (const std::bad_alloc &) {
+        return PCL_ERR_NOMEM;
+    } catch (...) {
+        return PCL_ERR_HIP;
+    }
+}
+
+} // extern "C"

@@ -521,6 +521,153 @@ class ScatterSignMeasureStep(_CountingMeasure):
         return ([n] if self.measure_n else []) + [sign[:, k] for k in range(3)]
 
 
+# ---------------------------------------------------------------------------------------------- position grids
+def _check_grid(axes, edges, center):
+    """(axes as a tuple of names, one float64 edge array per axis, the centre as 3 float64) of a PositionGridMeasureStep,
+    or ValueError for everything pcl_step_position_grid would refuse."""
+    from ._hip import GRID_COORDS, GRID_MAX_AXES, GRID_MAX_BINS, GRID_MAX_CELLS      # (the header's names and limits: one place)
+    try:
+        axes = tuple(axes)                              # ("yz" reads as ("y", "z"))
+    except TypeError:
+        raise ValueError("axes must be a sequence of names out of 'x', 'y', 'z', 'r'") from None
+    if not 1 <= len(axes) <= GRID_MAX_AXES:
+        raise ValueError("a position grid has one to three axes, got %d" % len(axes))
+    if any(not isinstance(a, str) or a not in GRID_COORDS for a in axes) or len(set(axes)) != len(axes):
+        raise ValueError("axes must be distinct names out of 'x', 'y', 'z', 'r', got %r" % (axes,))
+    try:
+        edges = [np.array(e, dtype=np.float64) for e in edges]        # a Measurement is taken by its stored value
+    except (TypeError, ValueError):
+        raise ValueError("edges must be one 1-D sequence of numbers (bin edges) per axis") from None
+    if len(edges) != len(axes):
+        raise ValueError("edges must hold one sequence of bin edges per axis: %d axes, %d sequences" % (len(axes), len(edges)))
+    cells = 1
+    for a, e in zip(axes, edges):
+        if e.ndim != 1 or len(e) < 2:
+            raise ValueError("axis %r: at least two bin edges in a 1-D sequence, got shape %r" % (a, e.shape))
+        if len(e) - 1 > GRID_MAX_BINS:
+            raise ValueError("axis %r: %d bins, at most %d are supported" % (a, len(e) - 1, GRID_MAX_BINS))
+        cmp = e
+        if a == "r":                                    # the device compares the squared distance with the squared edges
+            if not np.all(e >= 0):                      # (False for NaN as well)
+                raise ValueError("axis 'r': radius edges must not be negative")
+            with np.errstate(over="ignore"):
+                cmp = e * e
+        if not np.all(np.isfinite(cmp)) or not np.all(np.diff(cmp) > 0):
+            raise ValueError("axis %r: edges must be finite and strictly increasing%s" % (a, " (their squares, too)" if a == "r" else ""))
+        cells *= len(e) - 1
+    if cells > GRID_MAX_CELLS:
+        raise ValueError("the grid has %d cells, at most %d are supported" % (cells, GRID_MAX_CELLS))
+    try:
+        center = np.array(center, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("center must be three numbers") from None
+    if center.shape != (3,) or not np.all(np.isfinite(center)):
+        raise ValueError("center must be three finite numbers, got %r" % (center,))
+    return axes, [np.ascontiguousarray(e) for e in edges], np.ascontiguousarray(center)
+
+
+def _grid_of_positions(r, axes, edges, center):
+    """The grid of pcl_step_position_grid from an (n, 3) float64 array of positions, with numpy: per axis the bin with
+    e_b <= v < e_(b+1), the last bin closed (numpy.histogramdd); a radius axis bins the squared distance
+    ((x-cx)**2 + (y-cy)**2) + (z-cz)**2 against the squared edges."""
+    from ._hip import GRID_COORDS
+    r = np.asarray(r, dtype=np.float64).reshape(-1, 3)
+    ok, cell = np.ones(len(r), dtype=bool), np.zeros(len(r), dtype=np.int64)
+    for a, e in zip(axes, edges):
+        if a == "r":
+            d = r - center
+            v, e = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2], e * e
+        else:
+            v = r[:, GRID_COORDS[a]]
+        nb = len(e) - 1
+        with np.errstate(invalid="ignore"):
+            ok &= (v >= e[0]) & (v <= e[-1])
+        cell = cell * nb + np.clip(np.searchsorted(e, v, side="right") - 1, 0, nb - 1)
+    shape = [len(e) - 1 for e in edges]
+    return np.bincount(cell[ok], minlength=int(np.prod(shape))).astype(np.int64).reshape(shape)
+
+
+class PositionGridMeasureStep(DeviceStep, MeasureStep):
+    """Where the particles are (not in the reference): every ``every``-th run of the step records the row ``[t, N, grid]``
+    (``[t, grid]`` with ``measure_n=False``), ``grid`` an int64 array with one dimension per axis -- the histogram of the
+    positions of EVERY particle over the ``axes``: names out of ``"x"``, ``"y"``, ``"z"`` and ``"r"``, the distance from
+    ``center``; ``edges`` holds one sequence of bin edges per axis, in code units (at most 1024 bins per axis, 2**20 cells).
+    An altitude profile is ``axes=("r",)`` about the planet's centre, an image two Cartesian axes, a volume density three.
+    Counted as ``numpy.histogramdd`` counts: bins ``[e_b, e_b+1)``, the last one closed, a particle outside any axis's
+    range in no cell; a radius axis compares the squared distance with the squared edges (no square root is taken).
+
+    The grid is made on the device in one sweep of the resident store (pcl_step_position_grid); grids add, so sharded runs
+    all-reduce ``[N, cells]`` in one collective per recorded pass.  The step counts its own runs from 1 and records on run m
+    when ``m % every == 0``.  As the last step(s) of a pass it keeps the K-passes-per-launch schedule
+    (``Simulation.steps_per_launch``): a launch ends on the pass that is to be recorded."""
+    _fuse_role = "snapshot"
+
+    def __init__(self, out_fn, axes, edges, center=(0, 0, 0), every=1, measure_n=True):
+        MeasureStep.__init__(self, out_fn)
+        self.axes, self.edges, self.center = _check_grid(axes, edges, center)
+        if isinstance(every, bool) or not isinstance(every, (int, np.integer)) or every < 1:
+            raise ValueError("every must be a whole number of at least 1, got %r" % (every,))
+        self.every, self.measure_n = int(every), measure_n
+        self._runs = 0
+
+    # a snapshot step rides at the end of a fused group like a counting measure, with no planes and no counter row
+    def _n_planes(self):
+        return 0
+
+    def _plane_rows(self):
+        return []
+
+    def _passes_to_record(self):
+        """How many more runs until the one that records (1: the next one)."""
+        return self.every - self._runs % self.every
+
+    def _advance(self, runs=1):
+        """``runs`` more runs have happened; True if the last of them is one that records."""
+        self._runs += runs
+        return runs > 0 and self._runs % self.every == 0
+
+    def _take(self, sim):
+        """One sweep of the store, then ONE collective: [N, cells] (every rank issues it, also with an empty shard)."""
+        dev = sim._dev
+        grid = dev.position_grid(self.axes, self.edges, self.center)
+        glob = _allreduce_chunked(sim, np.concatenate([[dev.count], grid.reshape(-1)]))
+        self._record_grid(sim, int(glob[0]), glob[1:].reshape(grid.shape))
+
+    def _host_take(self, sim):
+        """The same row from the Python objects (they hold the state: nothing to upload for a measurement)."""
+        objs = list(sim.objects)
+        r = np.array([np.asarray(o.r, dtype=np.float64).reshape(3) for o in objs], dtype=np.float64).reshape(len(objs), 3)
+        self._record_grid(sim, len(objs), _grid_of_positions(r, self.axes, self.edges, self.center))
+
+    def _record_grid(self, sim, n, grid):
+        t = sim.t if isinstance(sim.t, (int, float, np.generic)) else copy.deepcopy(sim.t)   # (a clock with units advances in place)
+        row = [t] + ([int(n)] if self.measure_n else []) + [np.array(grid, dtype=np.int64)]
+        out = np.empty(len(row), dtype=object)
+        for k, x in enumerate(row):
+            out[k] = x
+        self.data.append(out)
+
+    def _device_run(self, sim):
+        if self._advance():
+            self._take(sim)
+
+    def run(self, sim):
+        if getattr(sim, "_residency", None) == "host" and getattr(sim, "_batch", None) is None \
+                and (sim.comm is None or sim.comm.world == 1):
+            # called as a host plugin on host-resident objects.  float64 on both sides: a Simulation's store is fp64
+            if self._advance():
+                self._host_take(sim)
+            return None
+        return DeviceStep.run(self, sim)
+
+    def terminate(self, sim):
+        if self.out_fn is None:
+            return
+        with open(self.out_fn, "w") as f:              # the grid is written as the binned spectrum is: a nested plain list
+            for row in self.data:
+                f.write(", ".join(str(x.tolist() if isinstance(x, np.ndarray) else x) for x in list(row)) + "\n")
+
+
 def _DEFAULT_ID_INFO(x):
     """The reference's default ``lambda x: str(type(x))`` (light.py:438), recognised by identity.  The label goes into the trace
     table's first column: this package's own classes read as the reference's (``<class 'physicl.light.PhotonObject'>``, what a

@@ -268,6 +268,9 @@ class MultiDevice:
     def plane_spectra(self, planes, edges):
         return tuple(self._sum(list(part)) for part in zip(*self._each(lambda s: s.plane_spectra(planes, edges))))
 
+    def position_grid(self, axes, edges, center=None):
+        return self._sum(self._each(lambda s: s.position_grid(axes, edges, center)))
+
     def plane_energies(self, plane, n_hint=None):
         return self._concat(self._each(lambda s: s.plane_energies(plane)))      # (a shard does not know its share of the hint)
 
