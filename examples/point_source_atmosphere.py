@@ -2,14 +2,17 @@
 """A photon source on the Earth's surface under an exponential atmosphere -- the radial variable-n expression of the reference's
 examples (n(r) = 2.5e25 m^-3 * exp(-(|r| - 6371 km) / 8.6 km)) with photons that do NOT start at the origin along +x:
 
-    python examples/point_source_atmosphere.py [n_photons] [passes] [--cone | --beam-down | --default] [--profile]
+    python examples/point_source_atmosphere.py [n_photons] [passes] [--cone | --beam-down | --default] [--profile] [--shells]
 
 default: a point source at (6371 km, 0, 0) emitting isotropically; ``--cone``: a 0.3 rad cone pointing up (+x) from a 1 km disc;
 ``--beam-down``: a 10 km gaussian beam entering from 100 km above the surface along -x; ``--default``: the same step list from
 the batch's default source (origin, +x) for comparison.  The photons never exist as Python objects: they are created and given
 their positions and directions on the device, and stepped 32 passes per launch like every other bulk run.  ``--profile``
 records where they are every 32 passes -- altitude shells of 5 km up to 200 km (a radius axis about the Earth's centre) and a
-y-z image -- as integer grids made on the device (PositionGridMeasureStep), and prints the last profile.
+y-z image -- as integer grids made on the device (PositionGridMeasureStep), and prints the last profile.  ``--shells``
+tallies what passes through the ground and through the spheres 10, 50 and 100 km above it on every pass -- outward and inward
+counts per shell and a histogram of the direction cosine against the local vertical (ShellCrossingMeasureStep), the top one
+printed.  A flux needs every pass, so with ``--shells`` the run drops to one launch per light step (sim.launch_note says so).
 """
 import os
 import sys
@@ -51,6 +54,10 @@ if "--profile" in sys.argv:                                    # behind the last
     image = light.PositionGridMeasureStep(None, ("y", "z"), [np.linspace(-300e3, 300e3, 129)] * 2, every=32, measure_n=False)
     sim.add_step(5, profile)
     sim.add_step(6, image)
+tally = None
+if "--shells" in sys.argv:                                     # the ground and three altitudes, about the Earth's centre
+    tally = light.ShellCrossingMeasureStep(None, R + np.array([0.0, 10e3, 50e3, 100e3]), mu_bins=np.linspace(-1.0, 1.0, 11))
+    sim.add_step(7, tally)
 sim.add_objs(light.generate_photons_bulk(n, min=light.E_from_wavelength(700e-9), max=light.E_from_wavelength(200e-9), seed=1234, source=source))
 
 sim.prepare()                                                  # the photons are created now: run_time below is stepping only
@@ -74,3 +81,9 @@ if profile is not None and profile.data:
         print("  %3d - %3d km: %d" % (5 * k, 5 * k + 20, shells_now[k:k + 4].sum()))
     img = image.data[-1][1]
     print("y-z image, 128 x 128 cells of 4.7 km: %d photons inside, %d cells hit, brightest cell %d" % (img.sum(), np.count_nonzero(img), img.max()))
+if tally is not None:
+    out, inn = (np.array([row[k] for row in tally.data]) for k in (2, 3))
+    print("crossings of the ground, 10, 50 and 100 km, summed over %d passes: outward %s, inward %s" % (len(tally.data), out.sum(axis=0).tolist(), inn.sum(axis=0).tolist()))
+    for row in tally.data[-3:]:
+        print("[t, N, out, in]:", float(row[0]), row[1], row[2].tolist(), row[3].tolist())
+    print("escapes through 100 km by direction cosine against the vertical, 10 bins over [-1, 1]:", np.sum([row[4][3] for row in tally.data], axis=0).tolist())

@@ -584,6 +584,51 @@ int pcl_step_position_grid(pcl_ctx *ctx, int n_axes, const int *coords_host, con
                            const double *center_host,  /* 3 doubles, NULL = origin; used by PCL_GRID_RADIUS only */
                            int64_t *grid_out_host);    /* prod(n_bins) cells, C order, first axis slowest */
 
+/* What passed through a sphere in the last move: the crossing measure of a radial problem (pcl_step_counters and
+ * pcl_step_plane_spectra know axis-aligned planes only).  For up to PCL_SHELL_MAX_SHELLS spheres of radii radii_host[s] > 0
+ * (finite, R*R finite, any order) about center_host (3 finite doubles, NULL = the origin), in ONE read-only sweep of the
+ * resident store: per shell the particles that went out and the ones that came in, and -- when asked for -- histograms of
+ * the crossing photons' energies and of the direction cosine of the move against the outward normal, as int64 cells that
+ * add across devices and ranks like every other counter row.  The other way to it is a download of r and dr (48 B per
+ * particle over the host link) and numpy, every pass.
+ * All arithmetic is fp64, unfused, in the order written; an fp32 store's values are widened first (exact).  Per particle,
+ * plain Objects included:  d = (x-cx, y-cy, z-cz);  p = d - dr, component by component (the position before the last move);
+ * q_now = (d0*d0 + d1*d1) + d2*d2, q_prev the same over p;  R2 = R*R, made once per shell on the host.
+ *   outward crossing of shell s  iff  q_prev <  R2_s and q_now >= R2_s
+ *   inward  crossing             iff  q_prev >= R2_s and q_now <  R2_s
+ * Half-open: a particle exactly on the sphere belongs to the outside, and every transition between q < R2 and q >= R2 is
+ * counted exactly once -- unlike the plane rule, which counts a stop exactly on a plane twice.  End points are tested, as
+ * the plane measure tests them: a chord that enters and leaves the sphere within one move is not counted.  NaN anywhere: no
+ * crossing.
+ * counts_out_host[dir * n_shells + s] (dir 0 = outward, 1 = inward): all particles.
+ * E_hist_out_host[(dir * n_shells + s) * n_E_bins + b]: crossing PHOTONS (plain Objects carry no energy) whose E lies in bin
+ * b as numpy.histogram(E, bins=E_edges) counts it: [e_b, e_b+1), the last bin closed, E outside the edges or NaN in no bin --
+ * what pcl_step_plane_spectra does.
+ * mu_hist_out_host[(dir * n_shells + s) * n_mu_bins + b]: all crossing particles by mu, the cosine between dr and the outward
+ * normal at the new position, binned without a square root or a division so that numpy restates it bit for bit:
+ *   s = (d0*dr0 + d1*dr1) + d2*dr2;  dd = (dr0*dr0 + dr1*dr1) + dr2*dr2;  W = s*|s|;  D = q_now*dd;  w_b = e_b*|e_b| (host);
+ *   bin b  iff  w_b*D <= W < w_(b+1)*D, the last bin closed (W <= w_B*D): mu = s / sqrt(D), both sides signed-squared.
+ * Rounded products are monotone in b: a binary search with one multiply per probe.  D == 0 (no move, or on the centre), or
+ * D or W not finite: counted as a crossing, in no mu bin.
+ * E_edges_host / mu_edges_host: n + 1 finite, strictly increasing doubles (1 <= n <= PCL_SHELL_MAX_BINS; the w_b finite and
+ * strictly increasing too), or 0 bins (the pointers are not looked at): no such histogram.  2 * n_shells * (n_E_bins +
+ * n_mu_bins) may not exceed PCL_SHELL_MAX_CELLS: a workgroup's uint32 histograms (32 KiB) and both edge tables stay below
+ * the 64 KiB of LDS a launch may ask for.
+ * PCL_ERR_ARG is returned before anything is launched or written; PCL_ERR_STATE without a store; an empty store answers zeros
+ * without a launch.  Host pointers; one device allocation per call, handed back on every way out; synchronises once, with
+ * the one copy of the results.  The store is seen dense with dr real (pcl_store_field_ptr); E is looked at only with energy
+ * bins (a wavelength-dependent scatter step that follows then rebuilds its wavelength-term cache, as after
+ * pcl_step_plane_spectra).  pcl_last_error() is generic for these two entry points, as for pcl_step_plane_spectra: they are
+ * compiled from a source file of their own (physicl_amd/csrc/pcl_shell.hip) on top of the functions above. */
+#define PCL_SHELL_MAX_SHELLS 16
+#define PCL_SHELL_MAX_BINS 1024    /* per histogram */
+#define PCL_SHELL_MAX_CELLS 8192   /* 2 * n_shells * (n_E_bins + n_mu_bins) */
+int pcl_step_shell_crossings(pcl_ctx *ctx, int n_shells, const double *radii_host, const double *center_host,
+                             const double *E_edges_host, int n_E_bins,      /* NULL, 0: no energy histograms */
+                             const double *mu_edges_host, int n_mu_bins,    /* NULL, 0: no direction histograms */
+                             int64_t *counts_out_host,                      /* [2][n_shells]: outward, inward */
+                             int64_t *E_hist_out_host, int64_t *mu_hist_out_host);   /* may be NULL with 0 bins */
+
 /* ---- Device groups: several GPUs from ONE process ---------------------------------------------------------------
  * The reference is a single process with one simulation thread (physicl/__init__.py:400-432, 501-524); this is how
  * a host written against this ABI uses a node's GPUs the same way, without one process per GPU.  A group owns one
@@ -639,6 +684,11 @@ int pcl_group_apply_source(pcl_group *group, const pcl_source *src, double c, ui
  * once for the group, before any shard is asked */
 int pcl_group_step_position_grid(pcl_group *group, int n_axes, const int *coords_host, const int *n_bins_host,
                                  const double *edges_host, const double *center_host, int64_t *grid_out_host);
+/* pcl_step_shell_crossings on every shard (side by side), counts and histograms summed over the group's devices; the
+ * arguments are checked once for the group, before any shard is asked */
+int pcl_group_step_shell_crossings(pcl_group *group, int n_shells, const double *radii_host, const double *center_host,
+                                   const double *E_edges_host, int n_E_bins, const double *mu_edges_host, int n_mu_bins,
+                                   int64_t *counts_out_host, int64_t *E_hist_out_host, int64_t *mu_hist_out_host);
 
 /* ---------------------------------------------------------------- the counters' collective (one process per GPU)
  * The path shards by global index with no data-path exchange; the only global quantities are the int64

@@ -26,6 +26,7 @@ SRC_ANGULAR = {"beam": 0, "isotropic": 1, "cone": 2, "lambertian": 3}       # PC
 SRC_SPATIAL = {"point": 0, "disc": 1, "gaussian": 2}                         # PCL_SRC_POINT ...
 GRID_COORDS = {"x": 0, "y": 1, "z": 2, "r": 3}                               # PCL_GRID_X ... PCL_GRID_RADIUS
 GRID_MAX_AXES, GRID_MAX_BINS, GRID_MAX_CELLS = 3, 1024, 1 << 20
+SHELL_MAX_SHELLS, SHELL_MAX_BINS, SHELL_MAX_CELLS = 16, 1024, 8192              # PCL_SHELL_MAX_SHELLS ...
 PROF_NEWTON, PROF_SCATTER, PROF_DELETE_MASK, PROF_COMPACT, PROF_COUNTERS, PROF_FUSED, PROF_MULTI, PROF_ONEPASS, \
     PROF_DELETE_AHEAD = range(9)
 PROF_NAMES = {PROF_NEWTON: "k_newton", PROF_SCATTER: "k_scatter", PROF_DELETE_MASK: "k_delete_mask",
@@ -146,6 +147,7 @@ _PROTOTYPES = {
     "pcl_step_counters": [_vp, _vp, c_int, _vp],
     "pcl_step_plane_spectra": [_vp, _vp, c_int, _vp, c_int, _vp, _vp],
     "pcl_step_position_grid": [_vp, c_int, _vp, _vp, _vp, _vp, _vp],
+    "pcl_step_shell_crossings": [_vp, c_int, _vp, _vp, _vp, c_int, _vp, c_int, _vp, _vp, _vp],
     # device groups: several GPUs from one process (the C-level counterpart of physicl_amd.multidev.MultiDevice)
     "pcl_group_create": [c_int, POINTER(c_int), POINTER(_vp)],
     "pcl_group_destroy": [_vp],
@@ -171,6 +173,7 @@ _PROTOTYPES = {
     "pcl_group_step_plane_spectra": [_vp, _vp, c_int, _vp, c_int, _vp, _vp],
     "pcl_group_apply_source": [_vp, _vp, c_double, c_uint64],
     "pcl_group_step_position_grid": [_vp, c_int, _vp, _vp, _vp, _vp, _vp],
+    "pcl_group_step_shell_crossings": [_vp, c_int, _vp, _vp, _vp, c_int, _vp, c_int, _vp, _vp, _vp],
 }
 EXPORTS = sorted(list(_PROTOTYPES) + ["pcl_last_error"])
 
@@ -304,6 +307,26 @@ def _grid(entry, handle, axes, edges, center=None):
     check(entry(handle, len(coords), coords.ctypes.data, n_bins.ctypes.data, ed.ctypes.data, None if ce is None else ce.ctypes.data,
                 out.ctypes.data))
     return out
+
+
+def _shells(entry, handle, radii, center=None, E_edges=None, mu_edges=None):
+    """One call of pcl_step_shell_crossings / pcl_group_step_shell_crossings: (counts int64[2, S], E_hist int64[2, S, B_E] or
+    None, mu_hist int64[2, S, B_mu] or None) -- [0]: outward, [1]: inward.  The edges go over as given: the library makes
+    R*R and the signed squares of the direction edges."""
+    ra = np.ascontiguousarray(radii, dtype=np.float64).reshape(-1)
+    ce = None if center is None else np.ascontiguousarray(center, dtype=np.float64).reshape(3)
+    S = len(ra)
+    counts = np.zeros((2, S), dtype=np.int64)
+    edges, hists = [], []
+    for e in (E_edges, mu_edges):
+        ed = None if e is None else np.ascontiguousarray(e, dtype=np.float64).reshape(-1)
+        edges.append(ed)
+        hists.append(None if ed is None else np.zeros((2, S, max(len(ed) - 1, 0)), dtype=np.int64))
+    ptr = lambda a: None if a is None else a.ctypes.data                                                       # noqa: E731
+    nb = lambda e: 0 if e is None else len(e) - 1                                                              # noqa: E731
+    check(entry(handle, S, ra.ctypes.data, ptr(ce), ptr(edges[0]), nb(edges[0]), ptr(edges[1]), nb(edges[1]), counts.ctypes.data,
+                ptr(hists[0]), ptr(hists[1])))
+    return counts, hists[0], hists[1]
 
 
 class SourceStruct(ctypes.Structure):
@@ -872,6 +895,13 @@ class Device:
         edges), every particle of the store, in one sweep (pcl_step_position_grid).  PositionGridMeasureStep."""
         return _grid(self.lib.pcl_step_position_grid, self.ctx, axes, edges, center)
 
+    def shell_crossings(self, radii, center=None, E_edges=None, mu_edges=None):
+        """What crossed the spheres of ``radii`` about ``center`` (None: the origin) in the last move, every particle of the
+        store, in one sweep (pcl_step_shell_crossings): ``(counts int64[2, S], E_hist int64[2, S, B_E] | None, mu_hist
+        int64[2, S, B_mu] | None)``, index 0 outward, 1 inward.  ``E_edges``: bin edges of the crossing photons' energies;
+        ``mu_edges``: of the cosine between the move and the outward normal.  ShellCrossingMeasureStep."""
+        return _shells(self.lib.pcl_step_shell_crossings, self.ctx, radii, center, E_edges, mu_edges)
+
 
 class DeviceGroup:
     """``pcl_group_*``: several contexts in one process, sharded by global index, behind the C ABI (the shim owns the
@@ -967,6 +997,10 @@ class DeviceGroup:
     def position_grid(self, axes, edges, center=None):
         """``Device.position_grid`` summed over the group's contexts (pcl_group_step_position_grid)."""
         return _grid(self.lib.pcl_group_step_position_grid, self.g, axes, edges, center)
+
+    def shell_crossings(self, radii, center=None, E_edges=None, mu_edges=None):
+        """``Device.shell_crossings`` summed over the group's contexts (pcl_group_step_shell_crossings)."""
+        return _shells(self.lib.pcl_group_step_shell_crossings, self.g, radii, center, E_edges, mu_edges)
 
     def download(self, field, n=None, offset=0, dtype=None):
         n = self.count - offset if n is None else n

@@ -668,6 +668,173 @@ class PositionGridMeasureStep(DeviceStep, MeasureStep):
                 f.write(", ".join(str(x.tolist() if isinstance(x, np.ndarray) else x) for x in list(row)) + "\n")
 
 
+# ---------------------------------------------------------------------------------------------- shell crossings
+def _check_bins(name, bins, signed_square=False):
+    """The bin edges ``name=`` of a ShellCrossingMeasureStep as a float64 array, or ValueError."""
+    from ._hip import SHELL_MAX_BINS
+    try:
+        edges = np.array(bins, dtype=np.float64)              # a Measurement is taken by its stored value
+    except (TypeError, ValueError):
+        raise ValueError("%s must be a 1-D sequence of numbers (bin edges)" % name) from None
+    if edges.ndim != 1 or len(edges) < 2:
+        raise ValueError("%s must be a 1-D sequence of at least two bin edges, got shape %r" % (name, edges.shape))
+    if len(edges) - 1 > SHELL_MAX_BINS:
+        raise ValueError("%s describes %d bins, at most %d are supported" % (name, len(edges) - 1, SHELL_MAX_BINS))
+    if not np.all(np.isfinite(edges)) or not np.all(np.diff(edges) > 0):
+        raise ValueError("%s must be finite and strictly increasing" % name)
+    if signed_square:                                         # the device compares s*|s| with e*|e| times q*dr.dr
+        with np.errstate(over="ignore"):
+            w = edges * np.abs(edges)
+        if not np.all(np.isfinite(w)) or not np.all(np.diff(w) > 0):
+            raise ValueError("%s: the signed squares e*|e| of the edges must be finite and strictly increasing, too" % name)
+    return np.ascontiguousarray(edges)
+
+
+def _check_shells(radii, center, E_bins, mu_bins):
+    """(radii, centre, energy edges or None, direction edges or None) of a ShellCrossingMeasureStep as float64 arrays, or
+    ValueError for everything pcl_step_shell_crossings would refuse."""
+    from ._hip import SHELL_MAX_CELLS, SHELL_MAX_SHELLS       # (the header's limits: one place)
+    try:
+        radii = np.array(radii, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("radii must be a 1-D sequence of numbers (shell radii)") from None
+    if radii.ndim != 1 or not 1 <= len(radii) <= SHELL_MAX_SHELLS:
+        raise ValueError("radii must be a 1-D sequence of 1 to %d shell radii, got shape %r" % (SHELL_MAX_SHELLS, radii.shape))
+    with np.errstate(over="ignore"):
+        if not np.all(np.isfinite(radii)) or not np.all(radii > 0) or not np.all(np.isfinite(radii * radii)):
+            raise ValueError("radii must be finite and positive (their squares finite, too)")
+    try:
+        center = np.array(center, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("center must be three numbers") from None
+    if center.shape != (3,) or not np.all(np.isfinite(center)):
+        raise ValueError("center must be three finite numbers, got %r" % (center,))
+    E_bins = None if E_bins is None else _check_bins("E_bins", E_bins)
+    mu_bins = None if mu_bins is None else _check_bins("mu_bins", mu_bins, signed_square=True)
+    cells = 2 * len(radii) * (sum(len(e) - 1 for e in (E_bins, mu_bins) if e is not None))
+    if cells > SHELL_MAX_CELLS:
+        raise ValueError("2 x %d shells x (E_bins + mu_bins) bins are %d histogram cells, at most %d are supported"
+                         % (len(radii), cells, SHELL_MAX_CELLS))
+    return np.ascontiguousarray(radii), np.ascontiguousarray(center), E_bins, mu_bins
+
+
+def _shell_tallies(r, dr, E, photon, radii, center, E_edges=None, mu_edges=None):
+    """What pcl_step_shell_crossings answers, from (n, 3) float64 positions and last moves, the energies and who is a photon,
+    with numpy -- every operation the device's operation, one rounding each (include/physicl_hip.h):
+    (counts int64[2, S], E_hist int64[2, S, B_E] or None, mu_hist int64[2, S, B_mu] or None), [0] outward, [1] inward."""
+    r, dr = np.asarray(r, dtype=np.float64).reshape(-1, 3), np.asarray(dr, dtype=np.float64).reshape(-1, 3)
+    R2 = np.asarray(radii, dtype=np.float64) * np.asarray(radii, dtype=np.float64)
+    S = len(R2)
+    with np.errstate(invalid="ignore", over="ignore"):
+        d = r - np.asarray(center, dtype=np.float64)
+        p = d - dr
+        q_now = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+        q_prev = (p[:, 0] * p[:, 0] + p[:, 1] * p[:, 1]) + p[:, 2] * p[:, 2]
+        cross = np.stack([(q_prev < R2[:, None]) & (q_now >= R2[:, None]),          # outward: on the sphere is outside
+                          (q_prev >= R2[:, None]) & (q_now < R2[:, None])])         # inward; NaN: neither
+    counts = cross.sum(axis=2).astype(np.int64)
+    hit = np.flatnonzero(cross.any(axis=(0, 1)))                                    # the histograms look at these only
+    cross = cross[:, :, hit]
+
+    def hist(bins, ok, n_bins):
+        return np.stack([[np.bincount(bins[c & ok], minlength=n_bins)[:n_bins] for c in side] for side in cross]).astype(np.int64)
+
+    E_hist = mu_hist = None
+    if E_edges is not None:                                   # numpy.histogram's bins: [e_b, e_b+1), the last one closed
+        e, v = np.asarray(E_edges, dtype=np.float64), np.asarray(E, dtype=np.float64).reshape(-1)[hit]
+        with np.errstate(invalid="ignore"):
+            ok = (v >= e[0]) & (v <= e[-1]) & np.asarray(photon, dtype=bool).reshape(-1)[hit]
+        E_hist = hist(np.clip(np.searchsorted(e, v, side="right") - 1, 0, len(e) - 2), ok, len(e) - 1)
+    if mu_edges is not None:                                  # w_b*D <= W < w_(b+1)*D, the last bin closed
+        e = np.asarray(mu_edges, dtype=np.float64)
+        w, d, m = e * np.abs(e), d[hit], dr[hit]
+        with np.errstate(invalid="ignore", over="ignore"):
+            s = (d[:, 0] * m[:, 0] + d[:, 1] * m[:, 1]) + d[:, 2] * m[:, 2]
+            dd = (m[:, 0] * m[:, 0] + m[:, 1] * m[:, 1]) + m[:, 2] * m[:, 2]
+            W, D = s * np.abs(s), q_now[hit] * dd
+            prod = w[None, :] * D[:, None]
+            ok = (D > 0) & np.isfinite(D) & np.isfinite(W) & (W >= prod[:, 0]) & (W <= prod[:, -1])
+            bins = np.clip((prod[:, :-1] <= W[:, None]).sum(axis=1) - 1, 0, len(e) - 2)   # (the rounded products are monotone in b)
+        mu_hist = hist(bins, ok, len(e) - 1)
+    return counts, E_hist, mu_hist
+
+
+class ShellCrossingMeasureStep(DeviceStep, MeasureStep):
+    """What passed through a sphere (not in the reference; ScatterMeasureStep knows axis-aligned planes only): every run
+    records the row ``[t, N, out, in]`` (no ``N`` with ``measure_n=False``) -- ``out[s]`` / ``in[s]`` the particles whose
+    last move took them out of / into the sphere of radius ``radii[s]`` about ``center`` (code units, at most 16 shells),
+    int64 arrays of ``len(radii)``.  With ``E_bins`` (bin edges, in the unit E is stored in) the row goes on with
+    ``E_out, E_in``, int64 ``[S, B_E]``: the crossing photons' energies binned as ``numpy.histogram`` bins them; with
+    ``mu_bins`` (edges over ``[-1, 1]``) with ``mu_out, mu_in``, int64 ``[S, B_mu]``: the cosine between the move and the
+    outward normal where the particle now is.  At most 1024 bins each, ``2 * S * (B_E + B_mu) <= 8192``.
+
+    A crossing is a change of side between the end points of the move, a particle exactly on the sphere being outside:
+    outward iff ``q_prev < R*R <= q_now``, inward iff ``q_now < R*R <= q_prev``, ``q`` the squared distance from the centre
+    in float64.  Every change of side is counted exactly once, so ``cumsum(out - in)`` is the change of the number of
+    particles outside; a chord through the sphere within one move is not seen.  No square root and no division is taken
+    anywhere (``mu`` is compared as ``s*|s|`` against ``e*|e| * q * dr.dr``), so numpy restates every cell exactly.
+
+    The tallies are made on the device in one sweep of the resident store (pcl_step_shell_crossings) and add, so sharded
+    runs all-reduce ``[N, counts, histograms]`` in one collective per pass.  A flux needs every pass, which the
+    K-passes-per-launch kernels cannot carry: a loop with this step runs one launch per light step, as with
+    ``ScatterMeasureStep(measure_E=True)``, and ``sim.launch_note`` says so."""
+    _fuse_role = None
+    _NOTE = "one launch per light step: a ShellCrossingMeasureStep tallies the last move of every pass, which the " \
+            "K-passes-per-launch kernels cannot carry"
+
+    def __init__(self, out_fn, radii, center=(0, 0, 0), E_bins=None, mu_bins=None, measure_n=True):
+        MeasureStep.__init__(self, out_fn)
+        self.radii, self.center, self.E_bins, self.mu_bins = _check_shells(radii, center, E_bins, mu_bins)
+        self.measure_n = measure_n
+
+    def _device_run(self, sim):
+        """One sweep of the store, then ONE collective: [N, counts, histograms] (every rank issues it, also with an empty shard)."""
+        if getattr(sim, "launch_note", self._NOTE) is None and sim._k_wanted() > 1:
+            sim.launch_note = self._NOTE
+        dev = sim._dev
+        parts = dev.shell_crossings(self.radii, self.center, self.E_bins, self.mu_bins)
+        glob = _allreduce_chunked(sim, np.concatenate([[dev.count]] + [x.reshape(-1) for x in parts if x is not None]))
+        out, at = [], 1
+        for x in parts:
+            out.append(None if x is None else glob[at:at + x.size].reshape(x.shape))
+            at += 0 if x is None else x.size
+        self._record_tallies(sim, int(glob[0]), *out)
+
+    def _host_run(self, sim):
+        """The same row from the Python objects (they hold the state: nothing to upload for a measurement)."""
+        objs = list(sim.objects)
+        vec = lambda get: np.array([np.asarray(get(o), dtype=np.float64).reshape(3) for o in objs], dtype=np.float64).reshape(len(objs), 3)  # noqa: E731
+        photon = np.array([type(o) is PhotonObject for o in objs], dtype=bool)
+        E = np.array([float(np.asarray(o.E)) if ph else np.nan for o, ph in zip(objs, photon)], dtype=np.float64)
+        self._record_tallies(sim, len(objs), *_shell_tallies(vec(lambda o: o.r), vec(lambda o: o.dr), E, photon, self.radii, self.center,
+                                                             self.E_bins, self.mu_bins))
+
+    def _record_tallies(self, sim, n, counts, E_hist, mu_hist):
+        t = sim.t if isinstance(sim.t, (int, float, np.generic)) else copy.deepcopy(sim.t)   # (a clock with units advances in place)
+        row = [t] + ([int(n)] if self.measure_n else [])
+        for x in (counts, E_hist, mu_hist):
+            if x is not None:
+                row += [np.array(x[0], dtype=np.int64), np.array(x[1], dtype=np.int64)]      # outward, inward
+        out = np.empty(len(row), dtype=object)
+        for k, x in enumerate(row):
+            out[k] = x
+        self.data.append(out)
+
+    def run(self, sim):
+        if getattr(sim, "_residency", None) == "host" and getattr(sim, "_batch", None) is None \
+                and (sim.comm is None or sim.comm.world == 1):
+            # called as a host plugin on host-resident objects.  float64 on both sides: a Simulation's store is fp64
+            return self._host_run(sim)
+        return DeviceStep.run(self, sim)
+
+    def terminate(self, sim):
+        if self.out_fn is None:
+            return
+        with open(self.out_fn, "w") as f:              # a tally is written as the binned spectrum is: a (nested) plain list
+            for row in self.data:
+                f.write(", ".join(str(x.tolist() if isinstance(x, np.ndarray) else x) for x in list(row)) + "\n")
+
+
 def _DEFAULT_ID_INFO(x):
     """The reference's default ``lambda x: str(type(x))`` (light.py:438), recognised by identity.  The label goes into the trace
     table's first column: this package's own classes read as the reference's (``<class 'physicl.light.PhotonObject'>``, what a

@@ -271,6 +271,10 @@ class MultiDevice:
     def position_grid(self, axes, edges, center=None):
         return self._sum(self._each(lambda s: s.position_grid(axes, edges, center)))
 
+    def shell_crossings(self, radii, center=None, E_edges=None, mu_edges=None):
+        parts = self._each(lambda s: s.shell_crossings(radii, center, E_edges, mu_edges))
+        return tuple(None if part[0] is None else self._sum(list(part)) for part in zip(*parts))
+
     def plane_energies(self, plane, n_hint=None):
         return self._concat(self._each(lambda s: s.plane_energies(plane)))      # (a shard does not know its share of the hint)
 
