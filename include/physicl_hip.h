@@ -541,8 +541,11 @@ int pcl_step_counters(pcl_ctx *ctx, const double *planes_host, int n_planes, int
  * pcl_step_plane_energies sees it (dense, dr real).  Host pointers; synchronises once.  An empty store answers zeros without
  * a launch.  PCL_ERR_ARG / PCL_ERR_STATE (no store) are returned before anything is launched.
  * pcl_last_error() is GENERIC for these two entry points: the thread's text belongs to the core source file and has no setter,
- * so a refused argument leaves the core's "bad argument" (not which edge or plane), a failed launch of this unit leaves the
- * text of the last call that set one, and a shard's text in the group form stays on that shard's thread.  Go by the code.
+ * so a refused argument leaves the core's "bad argument" (not which edge or plane; "ctx is NULL" after a NULL context), a
+ * failed launch of this unit leaves the text of the last call that set one, and a shard's text in the group form stays on that
+ * shard's thread.  Go by the code.  The same holds for every entry point compiled from a unit of its own on top of the
+ * functions above (pcl_store_apply_source, pcl_step_position_grid, pcl_step_shell_crossings and their group forms): they
+ * share that behaviour through physicl_amd/csrc/pcl_sweep.h.
  * Compiled from a source file of its own (physicl_amd/csrc/pcl_spectrum.hip) on top of the functions above; it reads E through
  * pcl_store_field_ptr, so a wavelength-dependent scatter step that follows rebuilds its wavelength-term cache. */
 #define PCL_SPECTRUM_MAX_BINS 1024

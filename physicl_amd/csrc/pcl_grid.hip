@@ -4,7 +4,7 @@
 // A translation unit of its own, linked into libphysicl_hip.so behind pcl_spectrum.hip and pcl_source.hip: it does not see
 // struct pcl_ctx and works through the public C ABI (include/physicl_hip.h) like any other host of the library.  The tuned
 // kernels, their register budgets and the source hash the counter records are tied to (physicl_amd/build.py: csrc_sha) are
-// not touched by anything here.
+// not touched by anything here.  The scaffold it shares with the other units of its kind is pcl_sweep.h.
 //
 //   k_position_grid<T, lds>   one grid-stride sweep of the tiled slab: per slot the r rows some axis needs (all three for a
 //                             radius axis), a binary search per axis in the edges (LDS), then one add to the slot's cell --
@@ -14,33 +14,20 @@
 //                             A wave whose in-range lanes all hold the same cell -- the population every bulk run starts
 //                             from -- issues ONE add of their count instead of up to 64 adds to one address, and one add
 //                             for a whole run of such trips in the same cell.
-#include <hip/hip_runtime.h>
-
-#include <cmath>
-#include <cstdint>
 #include <cstdlib>
-#include <cstring>
-#include <new>
-#include <system_error>
-#include <thread>
-#include <vector>
 
-#include "../../include/physicl_hip.h"
+#include "pcl_sweep.h"
 
 namespace {
 
-constexpr int kBlock = 256;                 // 4 wave64 per workgroup, as the library's sweeps
-constexpr int kWorkgroupsPerCU = 8;         // grid cap of the sweep: resident workgroups, each takes the same number of trips
-constexpr int kLdsPerCU = 160 * 1024;       // gfx950
+using namespace pcl_sweep;
+
 // The LDS form's switch-over: grids of up to this many cells are accumulated per workgroup in LDS.  4096 cells are 16 KiB;
 // with the largest edge table (3 x 1025 doubles, 24 KiB) a workgroup then holds 40 KiB and three of them (12 waves) share
 // a CU, a 64 x 64 image with its 130 edges holds 17 KiB and all eight do ("Position grids").  PCL_GRID_LDS_CELLS
 // (environment, read per call) moves it, up to kLdsCellsMax: edges + histogram stay below the 64 KiB a launch may ask for.
 constexpr int kLdsCellsDefault = 4096;
 constexpr int kLdsCellsMax = 8192;
-// A workgroup-private cell is a uint32: a workgroup adds at most one per slot, and the entry point bounds a workgroup to
-// fewer than 2^32 slots (kMaxSlotsPerWorkgroup), so it cannot overflow.
-constexpr int64_t kMaxSlotsPerWorkgroup = ((int64_t)1 << 32) - kBlock;
 
 template <typename T>
 struct grid_args {
@@ -82,7 +69,7 @@ __global__ void __launch_bounds__(kBlock) k_position_grid(grid_args<T> a) {
     };
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n_round; i += stride) {
         bool ok = i < a.N;
-        const int64_t ti = (i >> a.tile_log) * a.ts + (i & (((int64_t)1 << a.tile_log) - 1));
+        const int64_t ti = tile_index(i, a.tile_log, a.ts);
         double x[3] = {0.0, 0.0, 0.0};
 #pragma unroll
         for (int k = 0; k < 3; ++k)
@@ -99,13 +86,7 @@ __global__ void __launch_bounds__(kBlock) k_position_grid(grid_args<T> a) {
                 v = co == 0 ? x[0] : (co == 1 ? x[1] : x[2]);
             }
             ok = ok && v >= e[0] && v <= e[nb];  // NaN and anything outside the axis's range are in no cell
-            int lo = 0, hi = nb;                 // invariant: e[lo] <= v, and v < e[hi] or hi == nb
-            while (hi - lo > 1) {
-                const int mid = (lo + hi) >> 1;
-                if (e[mid] <= v) lo = mid; else hi = mid;
-            }
-            // lo = the last edge <= v among e[0 .. nb - 1]: bins [e_b, e_b+1), the last one closed (numpy.histogramdd)
-            cell = cell * nb + lo;
+            cell = cell * nb + bin_of(e, nb, v); // (numpy.histogramdd)
         }
         const unsigned long long m = __ballot(ok);
         if (m) {
@@ -126,31 +107,9 @@ __global__ void __launch_bounds__(kBlock) k_position_grid(grid_args<T> a) {
     flush_run();
     if (kLds) {
         __syncthreads();
-        for (int k = threadIdx.x; k < a.n_cells; k += kBlock)
-            if (s_hist[k]) atomicAdd(&a.grid[k], (unsigned long long)s_hist[k]);
+        flush_cells(s_hist, a.grid, a.n_cells);
     }
 }
-
-// The calling thread's message (pcl_last_error) lives in the core unit and has no setter in the ABI: a refused call leaves
-// the core's own generic "bad argument" there, as pcl_spectrum.hip does (include/physicl_hip.h says so).
-int bad_argument(pcl_ctx *ctx) {
-    void *none = nullptr;
-    if (ctx) (void)pcl_dev_alloc(ctx, -1, &none);
-    return PCL_ERR_ARG;
-}
-
-#define GRD_TRY(expr)                    \
-    do {                                 \
-        int rc__ = (expr);               \
-        if (rc__ != PCL_OK) return rc__; \
-    } while (0)
-
-struct dev_block { // one device allocation per call, handed back on every way out
-    pcl_ctx *ctx;
-    void *p = nullptr;
-    explicit dev_block(pcl_ctx *c) : ctx(c) {}
-    ~dev_block() { if (p) pcl_dev_free(ctx, p); }
-};
 
 struct grid_spec { // a call's arguments, checked; what the kernel compares against
     int n_axes = 0, n_edges = 0, rows = 0;
@@ -184,18 +143,8 @@ bool check_spec(int n_axes, const int *coords, const int *n_bins, const double *
         s.n_bins[a] = n_bins[a];
         s.edge_at[a] = s.n_edges;
         s.rows |= coords[a] == PCL_GRID_RADIUS ? 7 : 1 << coords[a];
-        const double *e = edges + s.n_edges;
-        for (int b = 0; b <= n_bins[a]; ++b) {
-            double v = e[b];
-            if (!std::isfinite(v)) return false;
-            if (coords[a] == PCL_GRID_RADIUS) { // q is compared against e*e: no square root anywhere
-                if (v < 0) return false;
-                v = v * v;
-                if (!std::isfinite(v)) return false;
-            }
-            if (b > 0 && !(v > s.edges.back())) return false;
-            s.edges.push_back(v);
-        }
+        // q of a radius axis is compared against e*e: no square root anywhere
+        if (!check_edges(edges + s.n_edges, n_bins[a], coords[a] == PCL_GRID_RADIUS ? kEdgeSquare : kEdgePlain, &s.edges)) return false;
         s.n_edges += n_bins[a] + 1;
     }
     return true;
@@ -211,34 +160,24 @@ int lds_cells_now() { // the switch-over of this call
 }
 
 template <typename T>
-int launch_grid(pcl_ctx *ctx, hipStream_t stream, const grid_spec &s, const double *edges_dev, unsigned long long *grid_dev, int64_t N,
-                int64_t ts, int tile_log, int n_cu) {
+int launch_grid(pcl_ctx *ctx, const store_view &v, const grid_spec &s, const double *edges_dev, unsigned long long *grid_dev) {
     grid_args<T> a{};
     for (int k = 0; k < 3; ++k) {
         if (!((s.rows >> k) & 1)) continue;
         void *r = nullptr;
-        GRD_TRY(pcl_store_field_ptr(ctx, PCL_R0 + k, &r));
+        PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_R0 + k, &r));
         a.r[k] = static_cast<const T *>(r);
     }
     a.edges = edges_dev; a.grid = grid_dev;
-    a.N = N; a.ts = ts; a.tile_log = tile_log;
+    a.N = v.N; a.ts = v.ts; a.tile_log = v.tile_log;
     a.n_axes = s.n_axes; a.n_edges = s.n_edges; a.n_cells = (int)s.cells; a.rows = s.rows;
     for (int k = 0; k < s.n_axes; ++k) { a.coord[k] = s.coord[k]; a.n_bins[k] = s.n_bins[k]; a.edge_at[k] = s.edge_at[k]; }
     for (int k = 0; k < 3; ++k) a.c[k] = s.c[k];
     const bool lds_form = s.cells <= lds_cells_now();
     const size_t lds = (size_t)s.n_edges * sizeof(double) + (lds_form ? (size_t)s.cells * sizeof(uint32_t) : 0);
-    // resident workgroups only: every workgroup of the LDS form flushes its own histogram
-    int per_cu = (int)(kLdsPerCU / (lds > 0 ? lds : 1));
-    per_cu = per_cu < 1 ? 1 : (per_cu > kWorkgroupsPerCU ? kWorkgroupsPerCU : per_cu);
-    const int64_t blocks = (N + kBlock - 1) / kBlock;
-    int64_t grid = blocks, cap = (int64_t)(n_cu > 0 ? n_cu : 256) * per_cu;
-    if (grid > cap) {
-        int64_t trips = (blocks + cap - 1) / cap;
-        while (trips * kBlock > kMaxSlotsPerWorkgroup) { cap *= 2; trips = (blocks + cap - 1) / cap; } // (never, below 2^43 slots)
-        grid = (blocks + trips - 1) / trips; // every workgroup takes the same number of trips
-    }
-    if (lds_form) hipLaunchKernelGGL((k_position_grid<T, true>), dim3((unsigned)grid), dim3(kBlock), lds, stream, a);
-    else hipLaunchKernelGGL((k_position_grid<T, false>), dim3((unsigned)grid), dim3(kBlock), lds, stream, a);
+    const int64_t grid = balanced_grid(v.N, v.n_cu, resident_per_cu(lds));
+    if (lds_form) hipLaunchKernelGGL((k_position_grid<T, true>), dim3((unsigned)grid), dim3(kBlock), lds, v.stream, a);
+    else hipLaunchKernelGGL((k_position_grid<T, false>), dim3((unsigned)grid), dim3(kBlock), lds, v.stream, a);
     return hipGetLastError() == hipSuccess ? PCL_OK : PCL_ERR_HIP;
 }
 
@@ -246,69 +185,35 @@ int position_grid(pcl_ctx *ctx, int n_axes, const int *coords_host, const int *n
                   const double *center_host, int64_t *grid_out_host) {
     grid_spec s;
     if (!ctx || !check_spec(n_axes, coords_host, n_bins_host, edges_host, center_host, grid_out_host, s)) return bad_argument(ctx);
-    // the first look at the store: a store behind an alive mask becomes dense, r current (PCL_ERR_STATE without a store)
-    void *r_first = nullptr;
-    for (int k = 0; k < 3; ++k)
-        if ((s.rows >> k) & 1) { GRD_TRY(pcl_store_field_ptr(ctx, PCL_R0 + k, &r_first)); break; }
-    int64_t N = 0, tile = 0, ts = 0;
-    GRD_TRY(pcl_store_count(ctx, &N));
+    store_view v;
+    PCL_SWEEP_TRY(open_store(ctx, PCL_R0 + (s.rows & 1 ? 0 : (s.rows & 2 ? 1 : 2)), &v)); // the first row some axis needs
     const size_t out_bytes = (size_t)s.cells * sizeof(uint64_t), edge_bytes = (size_t)s.n_edges * sizeof(double);
-    if (N <= 0) {
+    if (v.N <= 0) {
         memset(grid_out_host, 0, out_bytes);
         return PCL_OK;
     }
-    int dtype = PCL_DTYPE_F64, n_cu = 0;
-    GRD_TRY(pcl_store_dtype(ctx, &dtype));
-    GRD_TRY(pcl_store_layout(ctx, &tile, &ts));
-    int tile_log = 0;
-    while (((int64_t)1 << tile_log) < tile) ++tile_log;
-    if (((int64_t)1 << tile_log) != tile) return PCL_ERR_STATE; // the slab's tiles are a power of two long
-    GRD_TRY(pcl_ctx_device_info(ctx, nullptr, 0, nullptr, &n_cu, nullptr));
-    void *stream_v = nullptr;
-    GRD_TRY(pcl_ctx_stream(ctx, &stream_v));
-    hipStream_t stream = static_cast<hipStream_t>(stream_v);
-
     dev_block blk(ctx);
-    GRD_TRY(pcl_dev_alloc(ctx, (int64_t)(out_bytes + edge_bytes), &blk.p));
+    PCL_SWEEP_TRY(stage(blk, v.stream, out_bytes, s.edges.data(), edge_bytes));
     char *base = static_cast<char *>(blk.p);
-    if (hipMemsetAsync(base, 0, out_bytes, stream) != hipSuccess) return PCL_ERR_HIP;
-    if (hipMemcpyAsync(base + out_bytes, s.edges.data(), edge_bytes, hipMemcpyHostToDevice, stream) != hipSuccess) return PCL_ERR_HIP;
     const double *edges_dev = reinterpret_cast<const double *>(base + out_bytes);
     unsigned long long *grid_dev = reinterpret_cast<unsigned long long *>(base);
-    GRD_TRY(dtype == PCL_DTYPE_F64 ? launch_grid<double>(ctx, stream, s, edges_dev, grid_dev, N, ts, tile_log, n_cu)
-                                   : launch_grid<float>(ctx, stream, s, edges_dev, grid_dev, N, ts, tile_log, n_cu));
+    PCL_SWEEP_TRY(v.dtype == PCL_DTYPE_F64 ? launch_grid<double>(ctx, v, s, edges_dev, grid_dev) : launch_grid<float>(ctx, v, s, edges_dev, grid_dev));
     return pcl_d2h(ctx, grid_out_host, base, (int64_t)out_bytes); // the call's one synchronisation (a count is below 2^63)
 }
 
 int group_position_grid(pcl_group *group, int n_axes, const int *coords_host, const int *n_bins_host, const double *edges_host,
                         const double *center_host, int64_t *grid_out_host) {
-    int n = 0;
-    GRD_TRY(pcl_group_size(group, &n));
-    std::vector<pcl_ctx *> ctx((size_t)n);
-    for (int g = 0; g < n; ++g) GRD_TRY(pcl_group_ctx(group, g, &ctx[(size_t)g]));
+    std::vector<pcl_ctx *> ctx;
+    PCL_SWEEP_TRY(shards_of(group, ctx));
+    const int n = (int)ctx.size();
     grid_spec s;
     if (n < 1 || !check_spec(n_axes, coords_host, n_bins_host, edges_host, center_host, grid_out_host, s))
         return bad_argument(n > 0 ? ctx[0] : nullptr);
     const size_t cells = (size_t)s.cells;
     std::vector<std::vector<int64_t>> part((size_t)n, std::vector<int64_t>(cells, 0));
-    std::vector<int> rcs((size_t)n, PCL_OK);
-    auto one = [&](int g) {
-        rcs[(size_t)g] = pcl_step_position_grid(ctx[(size_t)g], n_axes, coords_host, n_bins_host, edges_host, center_host, part[(size_t)g].data());
-    };
-    // the shards' sweeps run side by side: a thread each per call (the group's own workers cannot be reached through the
-    // ABI), the calling thread takes shard 0.  A shard whose thread cannot be started is served by the calling thread.
-    std::vector<std::thread> th;
-    th.reserve((size_t)n);
-    for (int g = 1; g < n; ++g) {
-        try {
-            th.emplace_back(one, g);
-        } catch (const std::system_error &) {
-            one(g);
-        }
-    }
-    one(0);
-    for (auto &t : th) t.join();
-    for (int g = 0; g < n; ++g) GRD_TRY(rcs[(size_t)g]);
+    PCL_SWEEP_TRY(for_each_shard(ctx, [&](int g, pcl_ctx *c) {
+        return pcl_step_position_grid(c, n_axes, coords_host, n_bins_host, edges_host, center_host, part[(size_t)g].data());
+    }));
     memset(grid_out_host, 0, cells * sizeof(int64_t));
     for (int g = 0; g < n; ++g)
         for (size_t k = 0; k < cells; ++k) grid_out_host[k] += part[(size_t)g][k];
@@ -319,27 +224,14 @@ int group_position_grid(pcl_group *group, int n_axes, const int *coords_host, co
 
 extern "C" {
 
-// Nothing may be thrown through the C boundary: host allocations of the bodies above (the edges, the per-shard grids) can fail.
 int pcl_step_position_grid(pcl_ctx *ctx, int n_axes, const int *coords_host, const int *n_bins_host, const double *edges_host,
                            const double *center_host, int64_t *grid_out_host) {
-    try {
-        return position_grid(ctx, n_axes, coords_host, n_bins_host, edges_host, center_host, grid_out_host);
-    } catch (const std::bad_alloc &) {
-        return PCL_ERR_NOMEM;
-    } catch (...) {
-        return PCL_ERR_HIP;
-    }
+    return guarded([&] { return position_grid(ctx, n_axes, coords_host, n_bins_host, edges_host, center_host, grid_out_host); });
 }
 
 int pcl_group_step_position_grid(pcl_group *group, int n_axes, const int *coords_host, const int *n_bins_host, const double *edges_host,
                                  const double *center_host, int64_t *grid_out_host) {
-    try {
-        return group_position_grid(group, n_axes, coords_host, n_bins_host, edges_host, center_host, grid_out_host);
-    } catch (const std::bad_alloc &) {
-        return PCL_ERR_NOMEM;
-    } catch (...) {
-        return PCL_ERR_HIP;
-    }
+    return guarded([&] { return group_position_grid(group, n_axes, coords_host, n_bins_host, edges_host, center_host, grid_out_host); });
 }
 
 } // extern "C"

@@ -7,28 +7,21 @@
 // A translation unit of its own, linked into libphysicl_hip.so behind pcl_spectrum.hip: it does not see struct pcl_ctx and
 // works through the public C ABI (include/physicl_hip.h) like any other host of the library; pcl_device.h is included for
 // the Philox block, the 53-bit uniform and the project's sincos only.  The tuned kernels, their register budgets and the
-// source hash the counter records are tied to (physicl_amd/build.py: csrc_sha) are not touched by anything here.
+// source hash the counter records are tied to (physicl_amd/build.py: csrc_sha) are not touched by anything here.  The
+// scaffold it shares with the other units of its kind is pcl_sweep.h; the launch geometry is its own (there is nothing
+// to flush, so every block's workgroup may as well exist: min(blocks, cap)).
 //
 //   k_apply_source<T>   one grid-stride sweep of photons [0, n): Philox block 4 of the photon's id for the direction, block 5
 //                       for the position (blocks 2 and 3 are the energy draws of k_fill_photons / k_fill_table), so a photon
 //                       is the same photon however the run is sharded.  Everything is computed in fp64, unfused, and rounded
 //                       once to the store's precision.  Rows that would not change are not written.
-#include <hip/hip_runtime.h>
+#include "pcl_sweep.h"
 
-#include <cmath>
-#include <cstdint>
-#include <new>
-#include <system_error>
-#include <thread>
-#include <vector>
-
-#include "../../include/physicl_hip.h"
-#include "pcl_device.h"
+#include "pcl_device.h" // (after the HIP runtime and the ABI's header, which pcl_sweep.h brings)
 
 namespace {
 
-constexpr int kBlock = 256;         // 4 wave64 per workgroup, as the library's sweeps
-constexpr int kWorkgroupsPerCU = 8; // grid cap of the sweep
+using namespace pcl_sweep;
 
 template <typename T>
 struct source_args {
@@ -47,7 +40,7 @@ __global__ void __launch_bounds__(kBlock) k_apply_source(source_args<T> a) {
     const pcl_u32 k0 = (pcl_u32)a.seed, k1 = (pcl_u32)(a.seed >> 32);
     const bool write_v = a.v[0] != nullptr, write_r = a.r[0] != nullptr;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < a.n; i += stride) {
-        const int64_t ti = (i >> a.tile_log) * a.ts + (i & (((int64_t)1 << a.tile_log) - 1));
+        const int64_t ti = tile_index(i, a.tile_log, a.ts);
         const uint64_t id = (uint64_t)(a.id_base + i);
         if (write_v) {
             if (a.angular == PCL_SRC_BEAM) { // a constant: no draw
@@ -97,20 +90,6 @@ __global__ void __launch_bounds__(kBlock) k_apply_source(source_args<T> a) {
     }
 }
 
-// The calling thread's message (pcl_last_error) lives in the core unit and has no setter in the ABI: a refused call leaves
-// the core's own generic "bad argument" there (pcl_dev_alloc refuses a negative size), as pcl_spectrum.hip does.
-int bad_argument(pcl_ctx *ctx) {
-    void *none = nullptr;
-    (void)pcl_dev_alloc(ctx, -1, &none);
-    return PCL_ERR_ARG;
-}
-
-#define SRC_TRY(expr)                    \
-    do {                                 \
-        int rc__ = (expr);               \
-        if (rc__ != PCL_OK) return rc__; \
-    } while (0)
-
 bool finite3(const double *x) { return std::isfinite(x[0]) && std::isfinite(x[1]) && std::isfinite(x[2]); }
 
 bool source_ok(const pcl_source *s, double c) {
@@ -123,106 +102,64 @@ bool source_ok(const pcl_source *s, double c) {
 }
 
 template <typename T>
-int launch_source(pcl_ctx *ctx, const pcl_source *s, bool write_r, bool write_v, source_args<T> &a, int n_cu) {
+int launch_source(pcl_ctx *ctx, const store_view &v, const pcl_source *s, double c, uint64_t seed, int64_t id_base, bool write_r,
+                  bool write_v) {
+    source_args<T> a{};
+    a.n = v.N; a.id_base = id_base; a.ts = v.ts; a.tile_log = v.tile_log; a.angular = s->angular; a.spatial = s->spatial;
+    a.c = c; a.cos_half_angle = s->cos_half_angle; a.radius = s->radius; a.seed = seed;
     for (int k = 0; k < 3; ++k) {
-        void *r = nullptr, *v = nullptr;
-        if (write_r) SRC_TRY(pcl_store_field_ptr(ctx, PCL_R0 + k, &r));
-        if (write_v) SRC_TRY(pcl_store_field_ptr(ctx, PCL_V0 + k, &v));
+        void *r = nullptr, *vel = nullptr;
+        if (write_r) PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_R0 + k, &r));
+        if (write_v) PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_V0 + k, &vel));
         a.r[k] = static_cast<T *>(r);
-        a.v[k] = static_cast<T *>(v);
+        a.v[k] = static_cast<T *>(vel);
         a.origin[k] = s->origin[k]; a.e1[k] = s->e1[k]; a.e2[k] = s->e2[k]; a.d[k] = s->d[k];
     }
-    void *stream_v = nullptr;
-    SRC_TRY(pcl_ctx_stream(ctx, &stream_v));
-    const int64_t blocks = (a.n + kBlock - 1) / kBlock, cap = (int64_t)(n_cu > 0 ? n_cu : 256) * kWorkgroupsPerCU;
-    hipLaunchKernelGGL(k_apply_source<T>, dim3((unsigned)(blocks < cap ? blocks : cap)), dim3(kBlock), 0, static_cast<hipStream_t>(stream_v), a);
+    const int64_t blocks = (a.n + kBlock - 1) / kBlock, cap = (int64_t)(v.n_cu > 0 ? v.n_cu : 256) * kWorkgroupsPerCU;
+    hipLaunchKernelGGL(k_apply_source<T>, dim3((unsigned)(blocks < cap ? blocks : cap)), dim3(kBlock), 0, v.stream, a);
     return hipGetLastError() == hipSuccess ? PCL_OK : PCL_ERR_HIP;
 }
 
 int apply_source(pcl_ctx *ctx, const pcl_source *s, double c, uint64_t seed) {
     if (!ctx || !s || !source_ok(s, c)) return bad_argument(ctx);
     int uniform = 0;
-    SRC_TRY(pcl_store_is_uniform(ctx, &uniform)); // (PCL_ERR_STATE without a store)
-    if (!uniform) return PCL_ERR_STATE;           // ids must be id_base + index: a freshly filled population
-    int64_t n = 0, id_base = 0, tile = 0, ts = 0;
-    SRC_TRY(pcl_store_count(ctx, &n));
-    if (n <= 0) return PCL_OK;
+    PCL_SWEEP_TRY(pcl_store_is_uniform(ctx, &uniform)); // (PCL_ERR_STATE without a store)
+    if (!uniform) return PCL_ERR_STATE;                 // ids must be id_base + index: a freshly filled population
     // rows that would not change are not written: the fill left r = 0 and v = (c, 0, 0)
     const bool write_r = s->spatial != PCL_SRC_POINT || s->origin[0] != 0.0 || s->origin[1] != 0.0 || s->origin[2] != 0.0;
     const bool write_v = s->angular != PCL_SRC_BEAM || !(s->d[0] == 1.0 && s->d[1] == 0.0 && s->d[2] == 0.0);
     if (!write_r && !write_v) return PCL_OK;
-    SRC_TRY(pcl_store_download_ids(ctx, &id_base, 0, 1)); // (a uniform store keeps no id array: answered on the host)
-    int dtype = PCL_DTYPE_F64, n_cu = 0, tile_log = 0;
-    SRC_TRY(pcl_store_dtype(ctx, &dtype));
-    SRC_TRY(pcl_store_layout(ctx, &tile, &ts));
-    while (((int64_t)1 << tile_log) < tile) ++tile_log;
-    if (((int64_t)1 << tile_log) != tile) return PCL_ERR_STATE; // the slab's tiles are a power of two long
-    SRC_TRY(pcl_ctx_device_info(ctx, nullptr, 0, nullptr, &n_cu, nullptr));
-    if (dtype == PCL_DTYPE_F64) {
-        source_args<double> a{};
-        a.n = n; a.id_base = id_base; a.ts = ts; a.tile_log = tile_log; a.angular = s->angular; a.spatial = s->spatial;
-        a.c = c; a.cos_half_angle = s->cos_half_angle; a.radius = s->radius; a.seed = seed;
-        return launch_source<double>(ctx, s, write_r, write_v, a, n_cu);
-    }
-    source_args<float> a{};
-    a.n = n; a.id_base = id_base; a.ts = ts; a.tile_log = tile_log; a.angular = s->angular; a.spatial = s->spatial;
-    a.c = c; a.cos_half_angle = s->cos_half_angle; a.radius = s->radius; a.seed = seed;
-    return launch_source<float>(ctx, s, write_r, write_v, a, n_cu);
+    store_view v;
+    PCL_SWEEP_TRY(read_store(ctx, &v)); // (no field is looked at first: a uniform store is dense)
+    if (v.N <= 0) return PCL_OK;
+    int64_t id_base = 0;
+    PCL_SWEEP_TRY(pcl_store_download_ids(ctx, &id_base, 0, 1)); // (a uniform store keeps no id array: answered on the host)
+    return v.dtype == PCL_DTYPE_F64 ? launch_source<double>(ctx, v, s, c, seed, id_base, write_r, write_v)
+                                    : launch_source<float>(ctx, v, s, c, seed, id_base, write_r, write_v);
 }
 
 int group_apply_source(pcl_group *group, const pcl_source *s, double c, uint64_t seed) {
-    int n = 0;
-    SRC_TRY(pcl_group_size(group, &n));
-    std::vector<pcl_ctx *> ctx((size_t)n);
-    for (int g = 0; g < n; ++g) SRC_TRY(pcl_group_ctx(group, g, &ctx[(size_t)g]));
-    if (!s || !source_ok(s, c)) return bad_argument(n > 0 ? ctx[0] : nullptr); // before any shard is written
-    for (int g = 0; g < n; ++g) {
+    std::vector<pcl_ctx *> ctx;
+    PCL_SWEEP_TRY(shards_of(group, ctx));
+    if (!s || !source_ok(s, c)) return bad_argument(ctx.empty() ? nullptr : ctx[0]); // before any shard is written
+    for (pcl_ctx *one : ctx) {
         int uniform = 0;
-        SRC_TRY(pcl_store_is_uniform(ctx[(size_t)g], &uniform));
+        PCL_SWEEP_TRY(pcl_store_is_uniform(one, &uniform));
         if (!uniform) return PCL_ERR_STATE;
     }
-    std::vector<int> rcs((size_t)n, PCL_OK);
-    auto one = [&](int g) { rcs[(size_t)g] = pcl_store_apply_source(ctx[(size_t)g], s, c, seed); };
-    // the shards side by side: a thread each per call (the group's own workers cannot be reached through the ABI), the
-    // calling thread takes shard 0.  A shard whose thread cannot be started is served by the calling thread.
-    std::vector<std::thread> th;
-    th.reserve((size_t)n);
-    for (int g = 1; g < n; ++g) {
-        try {
-            th.emplace_back(one, g);
-        } catch (const std::system_error &) {
-            one(g);
-        }
-    }
-    if (n > 0) one(0);
-    for (auto &t : th) t.join();
-    for (int g = 0; g < n; ++g) SRC_TRY(rcs[(size_t)g]);
-    return PCL_OK;
+    return for_each_shard(ctx, [&](int, pcl_ctx *one) { return pcl_store_apply_source(one, s, c, seed); });
 }
 
 } // namespace
 
 extern "C" {
 
-// Nothing may be thrown through the C boundary (the group form allocates on the host).
 int pcl_store_apply_source(pcl_ctx *ctx, const pcl_source *src, double c, uint64_t seed) {
-    try {
-        return apply_source(ctx, src, c, seed);
-    } catch (const std::bad_alloc &) {
-        return PCL_ERR_NOMEM;
-    } catch (...) {
-        return PCL_ERR_HIP;
-    }
+    return guarded([&] { return apply_source(ctx, src, c, seed); });
 }
 
 int pcl_group_apply_source(pcl_group *group, const pcl_source *src, double c, uint64_t seed) {
-    try {
-        return group_apply_source(group, src, c, seed);
-    } catch (const std::bad_alloc &) {
-        return PCL_ERR_NOMEM;
-    } catch (...) {
-        return PCL_ERR_HIP;
-    }
+    return guarded([&] { return group_apply_source(group, src, c, seed); });
 }
 
 } // extern "C"

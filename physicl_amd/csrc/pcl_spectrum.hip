@@ -2,31 +2,19 @@
 //
 // A translation unit of its own, linked into libphysicl_hip.so: it does not see struct pcl_ctx and works through the
 // public C ABI (include/physicl_hip.h) like any other host of the library.  The tuned kernels, their register budgets and
-// the source hash the counter records are tied to (physicl_amd/build.py: csrc_sha) are not touched by anything here.
+// the source hash the counter records are tied to (physicl_amd/build.py: csrc_sha) are not touched by anything here.  What
+// it shares with the other units of its kind -- opening the store, the balanced grid, the group fan-out, the device
+// helpers -- is pcl_sweep.h.
 //
 //   k_plane_spectra<T>   one grid-stride sweep of the tiled slab for ALL planes of a call: per slot r[ax] and dr[ax] of
 //                        every axis some plane uses, E only where a plane was crossed; crossing lanes look their bin up
 //                        in the edges (LDS, binary search) and add to a workgroup-private histogram in LDS; a workgroup
 //                        flushes its non-zero bins with 64-bit atomics at the end.
-#include <hip/hip_runtime.h>
-
-#include <cmath>
-#include <cstdint>
-#include <cstring>
-#include <new>
-#include <system_error>
-#include <thread>
-#include <vector>
-
-#include "../../include/physicl_hip.h"
+#include "pcl_sweep.h"
 
 namespace {
 
-constexpr int kBlock = 256;                 // 4 wave64 per workgroup, as the library's sweeps
-constexpr int kWorkgroupsPerCU = 8;         // grid cap of the sweep: resident workgroups, each takes the same number of trips
-// A workgroup-private bin is a uint32: a workgroup adds at most one per slot and plane bin, and the entry point bounds a
-// workgroup to fewer than 2^32 slots (kMaxSlotsPerWorkgroup), so it cannot overflow.
-constexpr int64_t kMaxSlotsPerWorkgroup = ((int64_t)1 << 32) - kBlock;
+using namespace pcl_sweep;
 
 template <typename T>
 struct spectrum_args {
@@ -60,7 +48,7 @@ __global__ void __launch_bounds__(kBlock) k_plane_spectra(spectrum_args<T> a) {
     const int64_t n_round = (a.N + 63) / 64 * 64;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n_round; i += stride) {
         const bool in = i < a.N;
-        const int64_t ti = (i >> a.tile_log) * a.ts + (i & (((int64_t)1 << a.tile_log) - 1));
+        const int64_t ti = tile_index(i, a.tile_log, a.ts);
         T x[3] = {(T)0, (T)0, (T)0}, prev[3] = {(T)0, (T)0, (T)0};
 #pragma unroll
         for (int k = 0; k < 3; ++k)
@@ -80,65 +68,38 @@ __global__ void __launch_bounds__(kBlock) k_plane_spectra(spectrum_args<T> a) {
         if (crossed && (a.kind ? a.kind[i] != 0 : true)) {
             const double e = (double)a.E[ti]; // fp32 widens exactly
             if (e >= e_lo && e <= e_hi) {     // NaN and under/overflow are counted in no bin
-                int lo = 0, hi = a.n_bins;    // invariant: edges[lo] <= e, and e < edges[hi] or hi == n_bins
-                while (hi - lo > 1) {
-                    const int mid = (lo + hi) >> 1;
-                    if (s_edges[mid] <= e) lo = mid; else hi = mid;
-                }
-                // lo = the last edge <= e among edges[0 .. n_bins - 1]: bins [e_b, e_b+1), the last one closed (numpy.histogram)
+                const int lo = bin_of(s_edges, a.n_bins, e);
                 for (uint32_t m = crossed; m; m &= m - 1) atomicAdd(&s_hist[(__ffs(m) - 1) * a.n_bins + lo], 1u);
             }
         }
     }
     __syncthreads();
-    for (int k = threadIdx.x; k < n_cells; k += kBlock)
-        if (s_hist[k]) atomicAdd(&a.hist[k], (unsigned long long)s_hist[k]);
+    flush_cells(s_hist, a.hist, n_cells);
     if ((int)threadIdx.x < a.n_planes && s_cnt[threadIdx.x]) atomicAdd(&a.counts[threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
 }
 
-// The calling thread's message (pcl_last_error) lives in the core unit and has no setter in the ABI.  A refused call
-// leaves the core's own generic "bad argument" there (pcl_dev_alloc refuses a negative size) rather than the text of some
-// earlier failure; the text does not say which edge or plane, and a failed launch of this unit leaves whatever was there
-// (include/physicl_hip.h says so).
-int bad_argument(pcl_ctx *ctx) {
-    void *none = nullptr;
-    (void)pcl_dev_alloc(ctx, -1, &none);
-    return PCL_ERR_ARG;
-}
-
-#define SPC_TRY(expr)                    \
-    do {                                 \
-        int rc__ = (expr);               \
-        if (rc__ != PCL_OK) return rc__; \
-    } while (0)
-
-struct dev_block { // one device allocation per call, handed back on every way out
-    pcl_ctx *ctx;
-    void *p = nullptr;
-    explicit dev_block(pcl_ctx *c) : ctx(c) {}
-    ~dev_block() { if (p) pcl_dev_free(ctx, p); }
-};
-
 template <typename T>
-int launch_spectra(pcl_ctx *ctx, hipStream_t stream, spectrum_args<T> &a, const double *planes_host, int n_cu) {
-    for (int p = 0; p < a.n_planes; ++p) a.L[p] = (T)planes_host[3 * p + a.ax[p]];
+int launch_spectra(pcl_ctx *ctx, const store_view &v, const void *E, const unsigned char *kind, const double *edges_dev,
+                   unsigned long long *hist_dev, const double *planes_host, const int *ax, int ax_used, int n_planes, int n_bins) {
+    spectrum_args<T> a{};
+    a.E = static_cast<const T *>(E); a.kind = kind; a.edges = edges_dev;
+    a.hist = hist_dev; a.counts = hist_dev + (size_t)n_planes * n_bins;
+    a.N = v.N; a.ts = v.ts; a.tile_log = v.tile_log; a.n_planes = n_planes; a.n_bins = n_bins; a.ax_used = ax_used;
+    for (int p = 0; p < n_planes; ++p) {
+        a.ax[p] = ax[p];
+        a.L[p] = (T)planes_host[3 * p + ax[p]];
+    }
     for (int k = 0; k < 3; ++k) {
-        if (!((a.ax_used >> k) & 1)) continue;
+        if (!((ax_used >> k) & 1)) continue;
         void *r = nullptr, *dr = nullptr;
-        SPC_TRY(pcl_store_field_ptr(ctx, PCL_R0 + k, &r));
-        SPC_TRY(pcl_store_field_ptr(ctx, PCL_DR0 + k, &dr));
+        PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_R0 + k, &r));
+        PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_DR0 + k, &dr));
         a.r[k] = static_cast<const T *>(r);
         a.dr[k] = static_cast<const T *>(dr);
     }
-    const int64_t blocks = (a.N + kBlock - 1) / kBlock;
-    int64_t grid = blocks, cap = (int64_t)(n_cu > 0 ? n_cu : 256) * kWorkgroupsPerCU;
-    if (grid > cap) {
-        int64_t trips = (blocks + cap - 1) / cap;
-        while (trips * kBlock > kMaxSlotsPerWorkgroup) { cap *= 2; trips = (blocks + cap - 1) / cap; } // (never, below 2^43 slots)
-        grid = (blocks + trips - 1) / trips; // every workgroup takes the same number of trips
-    }
-    const size_t lds = (size_t)(a.n_bins + 1) * sizeof(double) + ((size_t)a.n_planes * a.n_bins + a.n_planes) * sizeof(uint32_t);
-    hipLaunchKernelGGL(k_plane_spectra<T>, dim3((unsigned)grid), dim3(kBlock), lds, stream, a);
+    const size_t lds = (size_t)(n_bins + 1) * sizeof(double) + ((size_t)n_planes * n_bins + n_planes) * sizeof(uint32_t);
+    const int64_t grid = balanced_grid(v.N, v.n_cu, kWorkgroupsPerCU);
+    hipLaunchKernelGGL(k_plane_spectra<T>, dim3((unsigned)grid), dim3(kBlock), lds, v.stream, a);
     return hipGetLastError() == hipSuccess ? PCL_OK : PCL_ERR_HIP;
 }
 
@@ -146,8 +107,7 @@ int plane_spectra(pcl_ctx *ctx, const double *planes_host, int n_planes, const d
                   int64_t *counts_out_host, int64_t *hist_out_host) {
     if (!ctx || !planes_host || !edges_host || !counts_out_host || !hist_out_host) return bad_argument(ctx);
     if (n_planes < 1 || n_planes > PCL_MAX_PLANES || n_bins < 1 || n_bins > PCL_SPECTRUM_MAX_BINS) return bad_argument(ctx);
-    for (int b = 0; b <= n_bins; ++b)
-        if (!std::isfinite(edges_host[b]) || (b > 0 && !(edges_host[b] > edges_host[b - 1]))) return bad_argument(ctx);
+    if (!check_edges(edges_host, n_bins, kEdgePlain)) return bad_argument(ctx);
     int ax[PCL_MAX_PLANES], ax_used = 0;
     for (int p = 0; p < n_planes; ++p) {
         const double *loc = planes_host + 3 * p;
@@ -155,66 +115,28 @@ int plane_spectra(pcl_ctx *ctx, const double *planes_host, int n_planes, const d
         if (std::isnan(loc[ax[p]])) return bad_argument(ctx);
         ax_used |= 1 << ax[p];
     }
-    // the first look at the store: a store behind an alive mask becomes dense, an implicit dr real (PCL_ERR_STATE without a store)
     void *E = nullptr;
-    SPC_TRY(pcl_store_field_ptr(ctx, PCL_E, &E));
+    store_view v;
+    PCL_SWEEP_TRY(open_store(ctx, PCL_E, &v, &E));
     for (int p = 0; p < n_planes; ++p) counts_out_host[p] = 0;
     memset(hist_out_host, 0, (size_t)n_planes * n_bins * sizeof(int64_t));
-    int64_t N = 0, tile = 0, ts = 0;
-    SPC_TRY(pcl_store_count(ctx, &N));
-    if (N <= 0) return PCL_OK;
-    int dtype = PCL_DTYPE_F64, uniform = 0, n_cu = 0;
-    SPC_TRY(pcl_store_dtype(ctx, &dtype));
-    SPC_TRY(pcl_store_layout(ctx, &tile, &ts));
-    int tile_log = 0;
-    while (((int64_t)1 << tile_log) < tile) ++tile_log;
-    if (((int64_t)1 << tile_log) != tile) return PCL_ERR_STATE; // the slab's tiles are a power of two long
-    SPC_TRY(pcl_store_is_uniform(ctx, &uniform));
-    SPC_TRY(pcl_ctx_device_info(ctx, nullptr, 0, nullptr, &n_cu, nullptr));
-    void *stream_v = nullptr;
-    SPC_TRY(pcl_ctx_stream(ctx, &stream_v));
-    hipStream_t stream = static_cast<hipStream_t>(stream_v);
-
-    // plain Objects carry no energy: their kind bytes go along when the store holds any (the ABI hands them out on the host only)
+    if (v.N <= 0) return PCL_OK;
     std::vector<uint8_t> kind_host;
     bool mixed = false;
-    if (!uniform) {
-        kind_host.resize((size_t)N);
-        SPC_TRY(pcl_store_download_kind(ctx, kind_host.data(), 0, N));
-        mixed = memchr(kind_host.data(), PCL_KIND_OBJECT, (size_t)N) != nullptr;
-    }
+    PCL_SWEEP_TRY(kind_bytes(ctx, v.N, kind_host, &mixed));
     const size_t cells = (size_t)n_planes * n_bins;
     const size_t out_bytes = (cells + n_planes) * sizeof(uint64_t), edge_bytes = (size_t)(n_bins + 1) * sizeof(double);
     dev_block blk(ctx);
-    SPC_TRY(pcl_dev_alloc(ctx, (int64_t)(out_bytes + edge_bytes + (mixed ? (size_t)N : 0)), &blk.p));
+    PCL_SWEEP_TRY(stage(blk, v.stream, out_bytes, edges_host, edge_bytes, kind_host));
     char *base = static_cast<char *>(blk.p);
-    if (hipMemsetAsync(base, 0, out_bytes, stream) != hipSuccess) return PCL_ERR_HIP;
-    if (hipMemcpyAsync(base + out_bytes, edges_host, edge_bytes, hipMemcpyHostToDevice, stream) != hipSuccess) return PCL_ERR_HIP;
-    if (mixed && hipMemcpyAsync(base + out_bytes + edge_bytes, kind_host.data(), (size_t)N, hipMemcpyHostToDevice, stream) != hipSuccess)
-        return PCL_ERR_HIP;
+    const double *edges_dev = reinterpret_cast<const double *>(base + out_bytes);
     const unsigned char *kind = mixed ? reinterpret_cast<const unsigned char *>(base + out_bytes + edge_bytes) : nullptr;
-
-    int rc;
-    if (dtype == PCL_DTYPE_F64) {
-        spectrum_args<double> a{};
-        a.E = static_cast<const double *>(E);
-        a.kind = kind; a.edges = reinterpret_cast<const double *>(base + out_bytes);
-        a.hist = reinterpret_cast<unsigned long long *>(base); a.counts = a.hist + cells;
-        a.N = N; a.ts = ts; a.tile_log = tile_log; a.n_planes = n_planes; a.n_bins = n_bins; a.ax_used = ax_used;
-        for (int p = 0; p < n_planes; ++p) a.ax[p] = ax[p];
-        rc = launch_spectra<double>(ctx, stream, a, planes_host, n_cu);
-    } else {
-        spectrum_args<float> a{};
-        a.E = static_cast<const float *>(E);
-        a.kind = kind; a.edges = reinterpret_cast<const double *>(base + out_bytes);
-        a.hist = reinterpret_cast<unsigned long long *>(base); a.counts = a.hist + cells;
-        a.N = N; a.ts = ts; a.tile_log = tile_log; a.n_planes = n_planes; a.n_bins = n_bins; a.ax_used = ax_used;
-        for (int p = 0; p < n_planes; ++p) a.ax[p] = ax[p];
-        rc = launch_spectra<float>(ctx, stream, a, planes_host, n_cu);
-    }
-    SPC_TRY(rc);
+    unsigned long long *hist_dev = reinterpret_cast<unsigned long long *>(base);
+    PCL_SWEEP_TRY(v.dtype == PCL_DTYPE_F64
+                      ? launch_spectra<double>(ctx, v, E, kind, edges_dev, hist_dev, planes_host, ax, ax_used, n_planes, n_bins)
+                      : launch_spectra<float>(ctx, v, E, kind, edges_dev, hist_dev, planes_host, ax, ax_used, n_planes, n_bins));
     std::vector<uint64_t> out(cells + n_planes);
-    SPC_TRY(pcl_d2h(ctx, out.data(), base, (int64_t)out_bytes)); // the call's one synchronisation
+    PCL_SWEEP_TRY(pcl_d2h(ctx, out.data(), base, (int64_t)out_bytes)); // the call's one synchronisation
     for (size_t k = 0; k < cells; ++k) hist_out_host[k] = (int64_t)out[k];
     for (int p = 0; p < n_planes; ++p) counts_out_host[p] = (int64_t)out[cells + p];
     return PCL_OK;
@@ -222,36 +144,16 @@ int plane_spectra(pcl_ctx *ctx, const double *planes_host, int n_planes, const d
 
 int group_plane_spectra(pcl_group *group, const double *planes_host, int n_planes, const double *edges_host, int n_bins,
                         int64_t *counts_out_host, int64_t *hist_out_host) {
-    int n = 0;
-    SPC_TRY(pcl_group_size(group, &n));
-    if (!counts_out_host || !hist_out_host || n_planes < 1 || n_planes > PCL_MAX_PLANES || n_bins < 1 || n_bins > PCL_SPECTRUM_MAX_BINS) {
-        pcl_ctx *first = nullptr;
-        SPC_TRY(pcl_group_ctx(group, 0, &first));
-        return bad_argument(first);
-    }
+    std::vector<pcl_ctx *> ctx;
+    PCL_SWEEP_TRY(shards_of(group, ctx));
+    const int n = (int)ctx.size();
+    if (n < 1 || !counts_out_host || !hist_out_host || n_planes < 1 || n_planes > PCL_MAX_PLANES || n_bins < 1 || n_bins > PCL_SPECTRUM_MAX_BINS)
+        return bad_argument(n > 0 ? ctx[0] : nullptr);
     const size_t cells = (size_t)n_planes * n_bins;
-    std::vector<pcl_ctx *> ctx((size_t)n);
-    for (int g = 0; g < n; ++g) SPC_TRY(pcl_group_ctx(group, g, &ctx[(size_t)g]));
     std::vector<std::vector<int64_t>> part((size_t)n, std::vector<int64_t>(cells + n_planes, 0));
-    std::vector<int> rcs((size_t)n, PCL_OK);
-    auto one = [&](int g) {
-        rcs[(size_t)g] = pcl_step_plane_spectra(ctx[(size_t)g], planes_host, n_planes, edges_host, n_bins, part[(size_t)g].data() + cells,
-                                                part[(size_t)g].data());
-    };
-    // the shards' sweeps run side by side: a thread each per call (the group's own workers cannot be reached through the
-    // ABI), the calling thread takes shard 0.  A shard whose thread cannot be started is served by the calling thread.
-    std::vector<std::thread> th;
-    th.reserve((size_t)n);
-    for (int g = 1; g < n; ++g) {
-        try {
-            th.emplace_back(one, g);
-        } catch (const std::system_error &) {
-            one(g);
-        }
-    }
-    one(0);
-    for (auto &t : th) t.join();
-    for (int g = 0; g < n; ++g) SPC_TRY(rcs[(size_t)g]);
+    PCL_SWEEP_TRY(for_each_shard(ctx, [&](int g, pcl_ctx *c) {
+        return pcl_step_plane_spectra(c, planes_host, n_planes, edges_host, n_bins, part[(size_t)g].data() + cells, part[(size_t)g].data());
+    }));
     for (int p = 0; p < n_planes; ++p) counts_out_host[p] = 0;
     memset(hist_out_host, 0, cells * sizeof(int64_t));
     for (int g = 0; g < n; ++g) {
@@ -265,28 +167,14 @@ int group_plane_spectra(pcl_group *group, const double *planes_host, int n_plane
 
 extern "C" {
 
-// Nothing may be thrown through the C boundary: host allocations of the bodies above (the kind bytes of a big store, the
-// per-shard rows) can fail.
 int pcl_step_plane_spectra(pcl_ctx *ctx, const double *planes_host, int n_planes, const double *edges_host, int n_bins,
                            int64_t *counts_out_host, int64_t *hist_out_host) {
-    try {
-        return plane_spectra(ctx, planes_host, n_planes, edges_host, n_bins, counts_out_host, hist_out_host);
-    } catch (const std::bad_alloc &) {
-        return PCL_ERR_NOMEM;
-    } catch (...) {
-        return PCL_ERR_HIP;
-    }
+    return guarded([&] { return plane_spectra(ctx, planes_host, n_planes, edges_host, n_bins, counts_out_host, hist_out_host); });
 }
 
 int pcl_group_step_plane_spectra(pcl_group *group, const double *planes_host, int n_planes, const double *edges_host, int n_bins,
                                  int64_t *counts_out_host, int64_t *hist_out_host) {
-    try {
-        return group_plane_spectra(group, planes_host, n_planes, edges_host, n_bins, counts_out_host, hist_out_host);
-    } catch (const std::bad_alloc &) {
-        return PCL_ERR_NOMEM;
-    } catch (...) {
-        return PCL_ERR_HIP;
-    }
+    return guarded([&] { return group_plane_spectra(group, planes_host, n_planes, edges_host, n_bins, counts_out_host, hist_out_host); });
 }
 
 } // extern "C"

@@ -246,7 +246,7 @@ def test_needs_build_sees_the_shell_unit(tmp_path, monkeypatch):
     lib = tmp_path / "lib.so"
     lib.write_bytes(b"")
     monkeypatch.setattr(build, "LIB", str(lib))
-    newest = max(os.path.getmtime(s) for s in build.SOURCES + build.LATER_UNITS + [build.__file__])
+    newest = max(os.path.getmtime(s) for s in build.SOURCES + build.LATER_UNITS + build.LATER_HEADERS + [build.__file__])
     os.utime(str(lib), (newest + 10, newest + 10))
     assert not build.needs_build()
     unit = shell_unit()
