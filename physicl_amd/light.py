@@ -7,6 +7,7 @@ import copy
 import numpy as np
 import numpy.linalg as np_lin
 
+from . import tally
 from .core import DeviceStep, MeasureStep, Object, PhotonBatch, Step
 from .units import Measurement
 
@@ -354,35 +355,25 @@ class _CountingMeasure(DeviceStep, MeasureStep):
 
 
 _MAX_E_BINS = 1024            # PCL_SPECTRUM_MAX_BINS: bins of a binned spectrum
-_ALLREDUCE_CHUNK = 2048      # values one pcl_comm_allreduce_sum_i64 call takes (physicl_amd.comm.NativeCounterComm)
 
 
-def _check_E_bins(E_bins):
-    """The bin edges of ScatterMeasureStep(E_bins=...) as a float64 array, or ValueError."""
-    try:
-        edges = np.array(E_bins, dtype=np.float64)            # a Measurement is taken by its stored value
-    except (TypeError, ValueError):
-        raise ValueError("E_bins must be a 1-D sequence of numbers (bin edges)") from None
-    if edges.ndim != 1 or len(edges) < 2:
-        raise ValueError("E_bins must be a 1-D sequence of at least two bin edges, got shape %r" % (edges.shape,))
-    if len(edges) - 1 > _MAX_E_BINS:
-        raise ValueError("E_bins describes %d bins, at most %d are supported" % (len(edges) - 1, _MAX_E_BINS))
-    if not np.all(np.isfinite(edges)) or not np.all(np.diff(edges) > 0):
-        raise ValueError("E_bins must be finite and strictly increasing")
-    return np.ascontiguousarray(edges)
+def _plane_spectra(r, dr, E, photon, planes, edges):
+    """What Device.plane_spectra answers, from (n, 3) float64 positions and last moves: per plane the particles with
+    ``r - dr <= loc <= r`` or the other way round, both ends included (physicl/light.py:378-402), and numpy.histogram of the
+    crossing photons' energies: (counts, histograms)."""
+    counts, hists = [], []
+    for loc in planes:
+        ax = 0 if not np.isnan(loc[0]) else (1 if not np.isnan(loc[1]) else 2)
+        L, x = loc[ax], r[:, ax]
+        with np.errstate(invalid="ignore"):
+            prev = x - dr[:, ax]
+            cross = ((prev <= L) & (L <= x)) | ((prev >= L) & (L >= x))
+        counts.append(int(np.count_nonzero(cross)))
+        hists.append(np.histogram(E[cross & photon], bins=edges)[0].astype(np.int64))
+    return counts, hists
 
 
-def _allreduce_chunked(sim, values):
-    """``sim._global`` of a payload of any length.  The library's own communicator takes 2048 values per call, so a longer
-    payload goes over in consecutive pieces of that size -- cut by position alone, so every rank cuts alike."""
-    values = np.ascontiguousarray(values, dtype=np.int64).reshape(-1)
-    if len(values) <= _ALLREDUCE_CHUNK:
-        return np.asarray(sim._global(values), dtype=np.int64)
-    return np.concatenate([np.asarray(sim._global(values[at:at + _ALLREDUCE_CHUNK]), dtype=np.int64)
-                           for at in range(0, len(values), _ALLREDUCE_CHUNK)])
-
-
-class ScatterMeasureStep(_CountingMeasure):
+class ScatterMeasureStep(tally.TallyStep, _CountingMeasure):
     """Row per step: ``[t, N, crossings of plane 0, ...]`` (physicl/light.py:361-404).  A plane is a
     3-vector with NaN in the coordinates that do not define it.  With ``measure_E`` each plane's count is followed
     by the list of the crossing photons' energies (object order), gathered on the device.
@@ -391,14 +382,16 @@ class ScatterMeasureStep(_CountingMeasure):
     then followed by the histogram of the crossing photons' energies over those bins -- an int64 array of
     ``len(E_bins) - 1``, what ``numpy.histogram(list, bins=E_bins)[0]`` makes of the list form -- computed on the device
     for all planes in one sweep.  Histograms add, so sharded runs all-reduce them with the counts (also on the library's own
-    communicator, which cannot carry the lists)."""
+    communicator, which cannot carry the lists).
+
+    The plain and the list form are the reference's and a _CountingMeasure's; only the ``E_bins`` form is a TallyStep."""
 
     def __init__(self, out_fn, measure_n=True, measure_locs=[], measure_E=False, E_bins=None):
         MeasureStep.__init__(self, out_fn)
         self.measure_locs, self.measure_n, self.measure_E = measure_locs, measure_n, measure_E
         if E_bins is not None and not measure_E:
             raise ValueError("E_bins bins the energies measure_E=True records: pass measure_E=True with it")
-        self.E_bins = None if E_bins is None else _check_E_bins(E_bins)
+        self.E_bins = None if E_bins is None else tally.check_edges("E_bins", E_bins, _MAX_E_BINS)
         if measure_E:
             # rows carry variable-length energy lists: a separate gather per plane after the counters, outside the
             # fused kernels (this instance takes no part in step fusion / steps_per_launch)
@@ -408,7 +401,7 @@ class ScatterMeasureStep(_CountingMeasure):
         if not self.measure_E:
             return _CountingMeasure._device_run(self, sim)
         if self.E_bins is not None:
-            return self._device_run_binned(sim)
+            return tally.TallyStep._device_run(self, sim)
         dev = sim._dev
         cnt = dev.step_counters(self._plane_rows())
         glob = sim._global(cnt)                                              # counts over all shards
@@ -422,69 +415,31 @@ class ScatterMeasureStep(_CountingMeasure):
             if sim.comm is not None:
                 Es = sim.comm.allgather_concat(Es)                           # rank order == particle order
             row.append(Es.tolist())                                          # crossing photons' E, object order
-        out = np.empty(len(row), dtype=object)                               # ragged row, as the reference's np.array(out)
-        out[:] = row
-        self.data.append(out)
+        self.data.append(tally.object_row(row))                              # ragged row, as the reference's np.array(out)
 
-    # -- E_bins: the spectra as histograms ---------------------------------------------------------------------------
-    def _device_run_binned(self, sim):
-        """One sweep of the store for every plane, then ONE collective for the whole step: [N, counts, histograms]
-        flattened (every rank issues it, also with an empty shard)."""
-        dev, planes = sim._dev, self._plane_rows()
-        n_bins = len(self.E_bins) - 1
+    # -- E_bins: the spectra as histograms, [N, counts, histograms] in one collective ----------------------------------
+    def _sweep(self, dev):
+        planes, n_bins = self._plane_rows(), len(self.E_bins) - 1
         if planes:
-            counts, hist = dev.plane_spectra(planes, self.E_bins)
-        else:
-            counts, hist = np.zeros(0, dtype=np.int64), np.zeros((0, n_bins), dtype=np.int64)
-        glob = _allreduce_chunked(sim, np.concatenate([[dev.count], counts, hist.reshape(-1)]))
-        P = len(planes)
-        self._record_binned(sim, int(glob[0]), glob[1:1 + P], glob[1 + P:].reshape(P, n_bins))
+            return dev.plane_spectra(planes, self.E_bins)
+        return np.zeros(0, dtype=np.int64), np.zeros((0, n_bins), dtype=np.int64)
 
-    def _host_run_binned(self, sim):
-        """The same row from the Python objects (they hold the state: nothing to upload for a measurement): the list the
-        reference builds per plane (physicl/light.py:378-402), binned with numpy.histogram."""
-        objs = list(sim.objects)
-        counts, hists = [], []
-        for loc in self._plane_rows():
-            ax = 0 if not np.isnan(loc[0]) else (1 if not np.isnan(loc[1]) else 2)
-            L, nl, Es = loc[ax], 0, []
-            for obj in objs:
-                x = float(np.asarray(obj.r, dtype=np.float64)[ax])
-                prev = x - float(np.asarray(obj.dr, dtype=np.float64)[ax])
-                if (prev <= L and L <= x) or (prev >= L and L >= x):
-                    nl += 1
-                    if type(obj) is PhotonObject:
-                        Es.append(float(np.asarray(obj.E)))
-            counts.append(nl)
-            hists.append(np.histogram(np.array(Es, dtype=np.float64), bins=self.E_bins)[0].astype(np.int64))
-        self._record_binned(sim, len(objs), counts, hists)
+    def _host_parts(self, objs):
+        """The list the reference builds per plane (physicl/light.py:378-402), binned with numpy.histogram."""
+        return _plane_spectra(tally.vec3(objs, "r"), tally.vec3(objs, "dr"), *tally.photon_energies(objs, PhotonObject),
+                                    self._plane_rows(), self.E_bins)
 
-    def _record_binned(self, sim, n, counts, hists):
-        row = [sim.t]
-        if self.measure_n:
-            row.append(int(n))
-        for nl, hist in zip(counts, hists):
-            row.append(int(nl))
-            row.append(np.array(hist, dtype=np.int64))
-        out = np.empty(len(row), dtype=object)         # the measure_E row, each energy list replaced by its histogram
-        for k, x in enumerate(row):
-            out[k] = x
-        self.data.append(out)
+    def _cells(self, parts):                           # the measure_E row, each energy list replaced by its histogram
+        return [x for nl, hist in zip(*parts) for x in (int(nl), np.array(hist, dtype=np.int64))]
+
+    def _clock(self, sim):
+        return sim.t                                   # as every ScatterMeasureStep row carries it (no copy: the reference's row)
 
     def run(self, sim):
-        if self.E_bins is not None and getattr(sim, "_residency", None) == "host" and getattr(sim, "_batch", None) is None \
-                and (sim.comm is None or sim.comm.world == 1):
-            # called as a host plugin on host-resident objects.  float64 on both sides: a Simulation's store is fp64
-            # (core.py allocates no other), so the row does not depend on where the objects reside
-            return self._host_run_binned(sim)          # called as a host plugin on host-resident objects
-        return DeviceStep.run(self, sim)
+        return (DeviceStep if self.E_bins is None else tally.TallyStep).run(self, sim)
 
     def terminate(self, sim):
-        if self.E_bins is None or self.out_fn is None:
-            return MeasureStep.terminate(self, sim)
-        with open(self.out_fn, "w") as f:              # a histogram cell is written as the list cells are: a plain list of integers
-            for row in self.data:
-                f.write(", ".join(str(x.tolist() if isinstance(x, np.ndarray) else x) for x in list(row)) + "\n")
+        return (MeasureStep if self.E_bins is None else tally.TallyStep).terminate(self, sim)
 
     def _n_planes(self):
         return len(self.measure_locs)
@@ -535,35 +490,17 @@ def _check_grid(axes, edges, center):
     if any(not isinstance(a, str) or a not in GRID_COORDS for a in axes) or len(set(axes)) != len(axes):
         raise ValueError("axes must be distinct names out of 'x', 'y', 'z', 'r', got %r" % (axes,))
     try:
-        edges = [np.array(e, dtype=np.float64) for e in edges]        # a Measurement is taken by its stored value
-    except (TypeError, ValueError):
+        edges = list(edges)
+    except TypeError:
         raise ValueError("edges must be one 1-D sequence of numbers (bin edges) per axis") from None
     if len(edges) != len(axes):
         raise ValueError("edges must hold one sequence of bin edges per axis: %d axes, %d sequences" % (len(axes), len(edges)))
-    cells = 1
-    for a, e in zip(axes, edges):
-        if e.ndim != 1 or len(e) < 2:
-            raise ValueError("axis %r: at least two bin edges in a 1-D sequence, got shape %r" % (a, e.shape))
-        if len(e) - 1 > GRID_MAX_BINS:
-            raise ValueError("axis %r: %d bins, at most %d are supported" % (a, len(e) - 1, GRID_MAX_BINS))
-        cmp = e
-        if a == "r":                                    # the device compares the squared distance with the squared edges
-            if not np.all(e >= 0):                      # (False for NaN as well)
-                raise ValueError("axis 'r': radius edges must not be negative")
-            with np.errstate(over="ignore"):
-                cmp = e * e
-        if not np.all(np.isfinite(cmp)) or not np.all(np.diff(cmp) > 0):
-            raise ValueError("axis %r: edges must be finite and strictly increasing%s" % (a, " (their squares, too)" if a == "r" else ""))
-        cells *= len(e) - 1
+    # (a radius axis: the device compares the squared distance with the squared edges)
+    edges = [tally.check_edges("axis %r" % a, e, GRID_MAX_BINS, "square" if a == "r" else None) for a, e in zip(axes, edges)]
+    cells = int(np.prod([len(e) - 1 for e in edges]))
     if cells > GRID_MAX_CELLS:
         raise ValueError("the grid has %d cells, at most %d are supported" % (cells, GRID_MAX_CELLS))
-    try:
-        center = np.array(center, dtype=np.float64)
-    except (TypeError, ValueError):
-        raise ValueError("center must be three numbers") from None
-    if center.shape != (3,) or not np.all(np.isfinite(center)):
-        raise ValueError("center must be three finite numbers, got %r" % (center,))
-    return axes, [np.ascontiguousarray(e) for e in edges], np.ascontiguousarray(center)
+    return axes, edges, tally.check_center(center)
 
 
 def _grid_of_positions(r, axes, edges, center):
@@ -587,7 +524,7 @@ def _grid_of_positions(r, axes, edges, center):
     return np.bincount(cell[ok], minlength=int(np.prod(shape))).astype(np.int64).reshape(shape)
 
 
-class PositionGridMeasureStep(DeviceStep, MeasureStep):
+class PositionGridMeasureStep(tally.TallyStep):
     """Where the particles are (not in the reference): every ``every``-th run of the step records the row ``[t, N, grid]``
     (``[t, grid]`` with ``measure_n=False``), ``grid`` an int64 array with one dimension per axis -- the histogram of the
     positions of EVERY particle over the ``axes``: names out of ``"x"``, ``"y"``, ``"z"`` and ``"r"``, the distance from
@@ -626,74 +563,24 @@ class PositionGridMeasureStep(DeviceStep, MeasureStep):
         self._runs += runs
         return runs > 0 and self._runs % self.every == 0
 
-    def _take(self, sim):
-        """One sweep of the store, then ONE collective: [N, cells] (every rank issues it, also with an empty shard)."""
-        dev = sim._dev
-        grid = dev.position_grid(self.axes, self.edges, self.center)
-        glob = _allreduce_chunked(sim, np.concatenate([[dev.count], grid.reshape(-1)]))
-        self._record_grid(sim, int(glob[0]), glob[1:].reshape(grid.shape))
+    def _due(self):
+        return self._advance()
 
-    def _host_take(self, sim):
-        """The same row from the Python objects (they hold the state: nothing to upload for a measurement)."""
-        objs = list(sim.objects)
-        r = np.array([np.asarray(o.r, dtype=np.float64).reshape(3) for o in objs], dtype=np.float64).reshape(len(objs), 3)
-        self._record_grid(sim, len(objs), _grid_of_positions(r, self.axes, self.edges, self.center))
+    def _sweep(self, dev):
+        return [dev.position_grid(self.axes, self.edges, self.center)]
 
-    def _record_grid(self, sim, n, grid):
-        t = sim.t if isinstance(sim.t, (int, float, np.generic)) else copy.deepcopy(sim.t)   # (a clock with units advances in place)
-        row = [t] + ([int(n)] if self.measure_n else []) + [np.array(grid, dtype=np.int64)]
-        out = np.empty(len(row), dtype=object)
-        for k, x in enumerate(row):
-            out[k] = x
-        self.data.append(out)
+    def _host_parts(self, objs):
+        return [_grid_of_positions(tally.vec3(objs, "r"), self.axes, self.edges, self.center)]
 
-    def _device_run(self, sim):
-        if self._advance():
-            self._take(sim)
-
-    def run(self, sim):
-        if getattr(sim, "_residency", None) == "host" and getattr(sim, "_batch", None) is None \
-                and (sim.comm is None or sim.comm.world == 1):
-            # called as a host plugin on host-resident objects.  float64 on both sides: a Simulation's store is fp64
-            if self._advance():
-                self._host_take(sim)
-            return None
-        return DeviceStep.run(self, sim)
-
-    def terminate(self, sim):
-        if self.out_fn is None:
-            return
-        with open(self.out_fn, "w") as f:              # the grid is written as the binned spectrum is: a nested plain list
-            for row in self.data:
-                f.write(", ".join(str(x.tolist() if isinstance(x, np.ndarray) else x) for x in list(row)) + "\n")
+    def _cells(self, parts):
+        return [np.array(parts[0], dtype=np.int64)]
 
 
 # ---------------------------------------------------------------------------------------------- shell crossings
-def _check_bins(name, bins, signed_square=False):
-    """The bin edges ``name=`` of a ShellCrossingMeasureStep as a float64 array, or ValueError."""
-    from ._hip import SHELL_MAX_BINS
-    try:
-        edges = np.array(bins, dtype=np.float64)              # a Measurement is taken by its stored value
-    except (TypeError, ValueError):
-        raise ValueError("%s must be a 1-D sequence of numbers (bin edges)" % name) from None
-    if edges.ndim != 1 or len(edges) < 2:
-        raise ValueError("%s must be a 1-D sequence of at least two bin edges, got shape %r" % (name, edges.shape))
-    if len(edges) - 1 > SHELL_MAX_BINS:
-        raise ValueError("%s describes %d bins, at most %d are supported" % (name, len(edges) - 1, SHELL_MAX_BINS))
-    if not np.all(np.isfinite(edges)) or not np.all(np.diff(edges) > 0):
-        raise ValueError("%s must be finite and strictly increasing" % name)
-    if signed_square:                                         # the device compares s*|s| with e*|e| times q*dr.dr
-        with np.errstate(over="ignore"):
-            w = edges * np.abs(edges)
-        if not np.all(np.isfinite(w)) or not np.all(np.diff(w) > 0):
-            raise ValueError("%s: the signed squares e*|e| of the edges must be finite and strictly increasing, too" % name)
-    return np.ascontiguousarray(edges)
-
-
 def _check_shells(radii, center, E_bins, mu_bins):
     """(radii, centre, energy edges or None, direction edges or None) of a ShellCrossingMeasureStep as float64 arrays, or
     ValueError for everything pcl_step_shell_crossings would refuse."""
-    from ._hip import SHELL_MAX_CELLS, SHELL_MAX_SHELLS       # (the header's limits: one place)
+    from ._hip import SHELL_MAX_BINS, SHELL_MAX_CELLS, SHELL_MAX_SHELLS       # (the header's limits: one place)
     try:
         radii = np.array(radii, dtype=np.float64)
     except (TypeError, ValueError):
@@ -703,19 +590,15 @@ def _check_shells(radii, center, E_bins, mu_bins):
     with np.errstate(over="ignore"):
         if not np.all(np.isfinite(radii)) or not np.all(radii > 0) or not np.all(np.isfinite(radii * radii)):
             raise ValueError("radii must be finite and positive (their squares finite, too)")
-    try:
-        center = np.array(center, dtype=np.float64)
-    except (TypeError, ValueError):
-        raise ValueError("center must be three numbers") from None
-    if center.shape != (3,) or not np.all(np.isfinite(center)):
-        raise ValueError("center must be three finite numbers, got %r" % (center,))
-    E_bins = None if E_bins is None else _check_bins("E_bins", E_bins)
-    mu_bins = None if mu_bins is None else _check_bins("mu_bins", mu_bins, signed_square=True)
+    center = tally.check_center(center)
+    E_bins = None if E_bins is None else tally.check_edges("E_bins", E_bins, SHELL_MAX_BINS)
+    # (the device compares s*|s| with e*|e| times q*dr.dr)
+    mu_bins = None if mu_bins is None else tally.check_edges("mu_bins", mu_bins, SHELL_MAX_BINS, "signed_square")
     cells = 2 * len(radii) * (sum(len(e) - 1 for e in (E_bins, mu_bins) if e is not None))
     if cells > SHELL_MAX_CELLS:
         raise ValueError("2 x %d shells x (E_bins + mu_bins) bins are %d histogram cells, at most %d are supported"
                          % (len(radii), cells, SHELL_MAX_CELLS))
-    return np.ascontiguousarray(radii), np.ascontiguousarray(center), E_bins, mu_bins
+    return np.ascontiguousarray(radii), center, E_bins, mu_bins
 
 
 def _shell_tallies(r, dr, E, photon, radii, center, E_edges=None, mu_edges=None):
@@ -724,7 +607,6 @@ def _shell_tallies(r, dr, E, photon, radii, center, E_edges=None, mu_edges=None)
     (counts int64[2, S], E_hist int64[2, S, B_E] or None, mu_hist int64[2, S, B_mu] or None), [0] outward, [1] inward."""
     r, dr = np.asarray(r, dtype=np.float64).reshape(-1, 3), np.asarray(dr, dtype=np.float64).reshape(-1, 3)
     R2 = np.asarray(radii, dtype=np.float64) * np.asarray(radii, dtype=np.float64)
-    S = len(R2)
     with np.errstate(invalid="ignore", over="ignore"):
         d = r - np.asarray(center, dtype=np.float64)
         p = d - dr
@@ -759,7 +641,7 @@ def _shell_tallies(r, dr, E, photon, radii, center, E_edges=None, mu_edges=None)
     return counts, E_hist, mu_hist
 
 
-class ShellCrossingMeasureStep(DeviceStep, MeasureStep):
+class ShellCrossingMeasureStep(tally.TallyStep):
     """What passed through a sphere (not in the reference; ScatterMeasureStep knows axis-aligned planes only): every run
     records the row ``[t, N, out, in]`` (no ``N`` with ``measure_n=False``) -- ``out[s]`` / ``in[s]`` the particles whose
     last move took them out of / into the sphere of radius ``radii[s]`` about ``center`` (code units, at most 16 shells),
@@ -788,51 +670,19 @@ class ShellCrossingMeasureStep(DeviceStep, MeasureStep):
         self.measure_n = measure_n
 
     def _device_run(self, sim):
-        """One sweep of the store, then ONE collective: [N, counts, histograms] (every rank issues it, also with an empty shard)."""
-        if getattr(sim, "launch_note", self._NOTE) is None and sim._k_wanted() > 1:
+        if getattr(sim, "launch_note", self._NOTE) is None and sim._k_wanted() > 1:      # (a device run only: the host path says nothing)
             sim.launch_note = self._NOTE
-        dev = sim._dev
-        parts = dev.shell_crossings(self.radii, self.center, self.E_bins, self.mu_bins)
-        glob = _allreduce_chunked(sim, np.concatenate([[dev.count]] + [x.reshape(-1) for x in parts if x is not None]))
-        out, at = [], 1
-        for x in parts:
-            out.append(None if x is None else glob[at:at + x.size].reshape(x.shape))
-            at += 0 if x is None else x.size
-        self._record_tallies(sim, int(glob[0]), *out)
+        tally.TallyStep._device_run(self, sim)
 
-    def _host_run(self, sim):
-        """The same row from the Python objects (they hold the state: nothing to upload for a measurement)."""
-        objs = list(sim.objects)
-        vec = lambda get: np.array([np.asarray(get(o), dtype=np.float64).reshape(3) for o in objs], dtype=np.float64).reshape(len(objs), 3)  # noqa: E731
-        photon = np.array([type(o) is PhotonObject for o in objs], dtype=bool)
-        E = np.array([float(np.asarray(o.E)) if ph else np.nan for o, ph in zip(objs, photon)], dtype=np.float64)
-        self._record_tallies(sim, len(objs), *_shell_tallies(vec(lambda o: o.r), vec(lambda o: o.dr), E, photon, self.radii, self.center,
-                                                             self.E_bins, self.mu_bins))
+    def _sweep(self, dev):
+        return dev.shell_crossings(self.radii, self.center, self.E_bins, self.mu_bins)
 
-    def _record_tallies(self, sim, n, counts, E_hist, mu_hist):
-        t = sim.t if isinstance(sim.t, (int, float, np.generic)) else copy.deepcopy(sim.t)   # (a clock with units advances in place)
-        row = [t] + ([int(n)] if self.measure_n else [])
-        for x in (counts, E_hist, mu_hist):
-            if x is not None:
-                row += [np.array(x[0], dtype=np.int64), np.array(x[1], dtype=np.int64)]      # outward, inward
-        out = np.empty(len(row), dtype=object)
-        for k, x in enumerate(row):
-            out[k] = x
-        self.data.append(out)
+    def _host_parts(self, objs):
+        return _shell_tallies(tally.vec3(objs, "r"), tally.vec3(objs, "dr"), *tally.photon_energies(objs, PhotonObject),
+                                    self.radii, self.center, self.E_bins, self.mu_bins)
 
-    def run(self, sim):
-        if getattr(sim, "_residency", None) == "host" and getattr(sim, "_batch", None) is None \
-                and (sim.comm is None or sim.comm.world == 1):
-            # called as a host plugin on host-resident objects.  float64 on both sides: a Simulation's store is fp64
-            return self._host_run(sim)
-        return DeviceStep.run(self, sim)
-
-    def terminate(self, sim):
-        if self.out_fn is None:
-            return
-        with open(self.out_fn, "w") as f:              # a tally is written as the binned spectrum is: a (nested) plain list
-            for row in self.data:
-                f.write(", ".join(str(x.tolist() if isinstance(x, np.ndarray) else x) for x in list(row)) + "\n")
+    def _cells(self, parts):                           # counts, E_hist, mu_hist: each outward, then inward
+        return [np.array(side, dtype=np.int64) for x in parts if x is not None for side in (x[0], x[1])]
 
 
 def _DEFAULT_ID_INFO(x):

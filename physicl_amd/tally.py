@@ -1,0 +1,142 @@
+"""The host side of a tally measure step, once -- the counterpart of csrc/pcl_sweep.h: the bin-edge and centre checks, the
+state of host-resident Python objects as arrays, the one collective of a pass, and ``TallyStep``, the base class that turns
+"one sweep of the store -> one collective -> one object row" into three hooks.  The steps themselves, and the numpy
+restatements of their sweeps that the host-plugin path answers with, are in light.py.  NumPy only."""
+import numpy as np
+
+from .core import DeviceStep, MeasureStep, _snap
+
+ALLREDUCE_CHUNK = 2048       # values one pcl_comm_allreduce_sum_i64 call takes (physicl_amd.comm.NativeCounterComm)
+
+
+# ---------------------------------------------------------------------------------------------- checks
+def check_edges(name, edges, max_bins, transform=None):
+    """The bin edges ``name`` as a contiguous float64 array, or ValueError -- the rule of pcl_sweep::check_edges: a 1-D
+    sequence of 2 to ``max_bins + 1`` finite, strictly increasing numbers.  ``transform`` is what the device compares with:
+    None (the edges), "square" (e*e: a radius, which must not be negative) or "signed_square" (e*|e|: a cosine); the
+    transformed edges must be finite and strictly increasing as well (1e200 squares to inf, +-1e-200 to +-0: a tie)."""
+    try:
+        e = np.array(edges, dtype=np.float64)                 # a Measurement is taken by its stored value
+    except (TypeError, ValueError):
+        raise ValueError("%s must be a 1-D sequence of numbers (bin edges)" % name) from None
+    if e.ndim != 1 or len(e) < 2:
+        raise ValueError("%s must be a 1-D sequence of at least two bin edges, got shape %r" % (name, e.shape))
+    if len(e) - 1 > max_bins:
+        raise ValueError("%s describes %d bins, at most %d are supported" % (name, len(e) - 1, max_bins))
+    if transform == "square" and not np.all(e >= 0):          # (False for NaN as well)
+        raise ValueError("%s: radius edges must not be negative" % name)
+    with np.errstate(over="ignore"):
+        w = e if transform is None else e * (e if transform == "square" else np.abs(e))
+    for x, what in ((e, ""), (w, " (also as the device compares them: %s)" % transform)):
+        if not np.all(np.isfinite(x)) or not np.all(np.diff(x) > 0):
+            raise ValueError("%s must be finite and strictly increasing%s" % (name, what))
+    return np.ascontiguousarray(e)
+
+
+def check_center(center):
+    """``center`` as three finite float64, or ValueError."""
+    try:
+        center = np.array(center, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("center must be three numbers") from None
+    if center.shape != (3,) or not np.all(np.isfinite(center)):
+        raise ValueError("center must be three finite numbers, got %r" % (center,))
+    return np.ascontiguousarray(center)
+
+
+# ---------------------------------------------------------------------------------------------- host-resident objects
+def vec3(objs, attr):
+    """``obj.<attr>`` of every object as an (n, 3) float64 array."""
+    return np.array([np.asarray(getattr(o, attr), dtype=np.float64).reshape(3) for o in objs], dtype=np.float64).reshape(len(objs), 3)
+
+
+def photon_energies(objs, photon_type):
+    """(E as float64, NaN for what is no photon; who is a photon) -- exactly ``photon_type``, as the light steps decide it."""
+    photon = np.array([type(o) is photon_type for o in objs], dtype=bool)
+    return np.array([float(np.asarray(o.E)) if ph else np.nan for o, ph in zip(objs, photon)], dtype=np.float64), photon
+
+
+# ---------------------------------------------------------------------------------------------- the collective
+def reduce_parts(sim, parts):
+    """(N, parts) summed over all shards in ONE payload: ``[sim._dev.count] + parts`` flattened in this order (``parts``: int64
+    arrays, None where a tally was not asked for; the answer has the same shapes).  The library's own communicator takes 2048
+    values per call, so a longer payload goes through ``sim._global`` in consecutive pieces of that size -- cut by position
+    alone, so every rank cuts alike.  Every rank must call this, also with an empty shard."""
+    flat = np.concatenate([[sim._dev.count]] + [x.reshape(-1) for x in parts if x is not None]).astype(np.int64, copy=False)
+    if len(flat) <= ALLREDUCE_CHUNK:
+        glob = np.asarray(sim._global(flat), dtype=np.int64)
+    else:
+        glob = np.concatenate([np.asarray(sim._global(flat[at:at + ALLREDUCE_CHUNK]), dtype=np.int64)
+                               for at in range(0, len(flat), ALLREDUCE_CHUNK)])
+    out, at = [], 1
+    for x in parts:
+        out.append(None if x is None else glob[at:at + x.size].reshape(x.shape))
+        at += 0 if x is None else x.size
+    return int(glob[0]), out
+
+
+# ---------------------------------------------------------------------------------------------- rows
+def object_row(cells):
+    """The cells as one object-dtype row (cell by cell: numpy must not look into the arrays and lists among them)."""
+    out = np.empty(len(cells), dtype=object)
+    for k, x in enumerate(cells):
+        out[k] = x
+    return out
+
+
+class TallyStep(DeviceStep, MeasureStep):
+    """A measure step whose row is ``[t, N, cells...]``, the cells made of integer tallies that add over shards.  A subclass
+    sets ``measure_n`` and supplies three things:
+
+    * ``_sweep(dev)``: the tallies of the resident store, one device sweep -- a sequence of int64 arrays (None: not asked for);
+    * ``_host_parts(objs)``: the same sequence from the Python objects, with numpy;
+    * ``_cells(parts)``: the row's cells behind ``[t, N]``.
+
+    ``_device_run(sim)`` asks the simulation for ``t``, ``_dev`` and ``_global`` and nothing else (the CPU tests drive it
+    with stand-ins that have no more).  ``_take`` is the name core.py calls behind a launch on a "snapshot" step."""
+
+    def _sweep(self, dev):
+        raise NotImplementedError
+
+    def _host_parts(self, objs):
+        raise NotImplementedError
+
+    def _cells(self, parts):
+        raise NotImplementedError
+
+    def _due(self):
+        """Whether this run of the step records (a step that records every n-th run counts here)."""
+        return True
+
+    def _clock(self, sim):
+        return _snap(sim.t)                            # (a clock with units advances in place: the row keeps its own copy)
+
+    def _record_tally(self, sim, n, parts):
+        self.data.append(object_row([self._clock(sim)] + ([int(n)] if self.measure_n else []) + self._cells(parts)))
+
+    def _take(self, sim):
+        """One sweep of the store, then ONE collective for the whole row (every rank issues it, also with an empty shard)."""
+        self._record_tally(sim, *reduce_parts(sim, self._sweep(sim._dev)))
+
+    def _device_run(self, sim):
+        if self._due():
+            self._take(sim)
+
+    def run(self, sim):
+        if getattr(sim, "_residency", None) == "host" and getattr(sim, "_batch", None) is None \
+                and (sim.comm is None or sim.comm.world == 1):
+            # called as a host plugin on host-resident objects: they hold the state, so nothing is uploaded for a
+            # measurement.  float64 on both sides (core.py allocates no other store), so the row does not depend on where
+            # the objects reside
+            if self._due():
+                objs = list(sim.objects)
+                self._record_tally(sim, len(objs), self._host_parts(objs))
+            return None
+        return DeviceStep.run(self, sim)
+
+    def terminate(self, sim):
+        if self.out_fn is None:
+            return
+        with open(self.out_fn, "w") as f:              # an array cell is written as a list cell is: a (nested) plain list of integers
+            for row in self.data:
+                f.write(", ".join(str(x.tolist() if isinstance(x, np.ndarray) else x) for x in list(row)) + "\n")

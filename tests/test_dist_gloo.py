@@ -2,14 +2,11 @@
 same global counters and the same per-photon results as one unsharded run.  Per-shard compute in
 this CPU test is done by the oracle (test infrastructure); on GPUs it is the HIP step (the same
 property is tested on one GPU in test_gpu_parity.py::test_results_do_not_depend_on_sharding)."""
-import json
 import os
-import socket
-import subprocess
-import sys
 
 import numpy as np
 
+import rank_world
 from physicl_amd.dist import CounterComm, shard_range
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -47,28 +44,8 @@ comm.close()
 """
 
 
-def free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def run_world(world):
-    port = free_port()
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), OMP_NUM_THREADS="1")
-        procs.append(subprocess.Popen([sys.executable, "-c", WORKER % {"root": ROOT}], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
-    outs = []
-    for p in procs:
-        o, e = p.communicate(timeout=300)
-        assert p.returncode == 0, e[-2000:]
-        outs.append(json.loads(o.strip().splitlines()[-1]))
-    return sorted(outs, key=lambda d: d["rank"])
+    return rank_world.run_world(WORKER % {"root": ROOT}, world, timeout=300)
 
 
 def test_shard_ranges_partition_the_ids():

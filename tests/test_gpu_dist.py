@@ -5,11 +5,12 @@ N > 1 path -- sharding, id bases, the reduce of the counter vector, exit on the 
 runs here on real kernels.)"""
 import json
 import os
-import socket
 import subprocess
 import sys
 
 import pytest
+
+import rank_world
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -64,28 +65,8 @@ comm.close()
 """
 
 
-def free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def run_world(world, kind, spl=1):
-    port = free_port()
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
-        procs.append(subprocess.Popen([sys.executable, "-c", WORKER % {"root": ROOT, "kind": kind, "spl": spl}], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
-    outs = []
-    for p in procs:
-        o, e = p.communicate(timeout=600)
-        assert p.returncode == 0, e[-3000:]
-        outs.append(json.loads(o.strip().splitlines()[-1]))
-    return sorted(outs, key=lambda d: d["rank"])
+    return rank_world.run_world(WORKER % {"root": ROOT, "kind": kind, "spl": spl}, world)
 
 
 @pytest.mark.parametrize("kind", ["batch", "objects", "delete"])

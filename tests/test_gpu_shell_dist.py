@@ -4,13 +4,11 @@
 Simulation -- [N, counts, histograms] all-reduced in one collective per pass, 1 + 2 x 4 x (1 + 256 + 64) = 2569 values, i.e. two
 pieces of at most 2048 -- are the rows of the single-process run, on every rank; also when one rank's shard is empty.
 """
-import json
 import os
-import socket
-import subprocess
-import sys
 
 import pytest
+
+import rank_world
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -40,28 +38,8 @@ comm.close()
 """
 
 
-def free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def run_world(world, N):
-    port = free_port()
-    procs = []
-    for r in range(world):                                   # at most 2 processes with the GPU open
-        env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
-        procs.append(subprocess.Popen([sys.executable, "-c", WORKER % {"root": ROOT, "N": N}], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
-    outs = []
-    for p in procs:
-        o, e = p.communicate(timeout=600)
-        assert p.returncode == 0, e[-3000:]
-        outs.append(json.loads(o.strip().splitlines()[-1]))
-    return sorted(outs, key=lambda d: d["rank"])
+    return rank_world.run_world(WORKER % {"root": ROOT, "N": N}, world)
 
 
 @pytest.mark.parametrize("N", [150001, 1], ids=["payload_2569", "empty_shard"])

@@ -3,14 +3,12 @@ tests/test_gpu_spectrum_dist.py).  Each rank fills its block ``[lo, hi)`` with `
 initial positions and velocities of the two ranks, put one behind the other, are the single process's bit for bit, and so are the
 counter rows of the run (sign counts and plane crossings, all-reduced) on every rank.
 """
-import json
 import os
-import socket
-import subprocess
-import sys
 
 import numpy as np
 import pytest
+
+import rank_world
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -46,28 +44,8 @@ comm.close()
 """
 
 
-def free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def run_world(world, N, angular, spatial):
-    port = free_port()
-    procs = []
-    for r in range(world):                                   # at most 2 processes with the GPU open
-        env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
-        procs.append(subprocess.Popen([sys.executable, "-c", WORKER % {"root": ROOT, "N": N, "angular": angular, "spatial": spatial}], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
-    outs = []
-    for p in procs:
-        o, e = p.communicate(timeout=600)
-        assert p.returncode == 0, e[-3000:]
-        outs.append(json.loads(o.strip().splitlines()[-1]))
-    return sorted(outs, key=lambda d: d["rank"])
+    return rank_world.run_world(WORKER % {"root": ROOT, "N": N, "angular": angular, "spatial": spatial}, world)
 
 
 @pytest.mark.parametrize("N,angular,spatial", [(3 * 2048 + 77, "lambertian", "gaussian"), (3 * 2048 + 77, "cone", "disc"), (1, "isotropic", "point")],

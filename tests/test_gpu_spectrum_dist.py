@@ -7,14 +7,12 @@
   on one device are refused by RCCL, tests/test_gpu_comm.py): the same payload goes through the real
   pcl_comm_allreduce_sum_i64, which takes 2048 values per call, and gives the plain rows; the list form raises there.
 """
-import json
 import os
-import socket
-import subprocess
-import sys
 
 import numpy as np
 import pytest
+
+import rank_world
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -44,28 +42,8 @@ comm.close()
 """
 
 
-def free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def run_world(world, N, n_bins):
-    port = free_port()
-    procs = []
-    for r in range(world):                                   # at most 2 processes with the GPU open
-        env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
-        procs.append(subprocess.Popen([sys.executable, "-c", WORKER % {"root": ROOT, "N": N, "n_bins": n_bins}], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
-    outs = []
-    for p in procs:
-        o, e = p.communicate(timeout=600)
-        assert p.returncode == 0, e[-3000:]
-        outs.append(json.loads(o.strip().splitlines()[-1]))
-    return sorted(outs, key=lambda d: d["rank"])
+    return rank_world.run_world(WORKER % {"root": ROOT, "N": N, "n_bins": n_bins}, world)
 
 
 @pytest.mark.parametrize("N,n_bins", [(150001, 1024), (150001, 50), (1, 1024)], ids=["payload_4101", "payload_205", "empty_shard"])

@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 import physicl_amd as phys
+import rank_world
 from physicl_amd import _hip, build, light
 from grid_reference import position_grid
 
@@ -328,26 +329,7 @@ comm.close()
 
 
 def run_gloo_world(world):
-    import json
-    import socket
-    import sys
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), OMP_NUM_THREADS="1")
-        procs.append(subprocess.Popen([sys.executable, "-c", GLOO_WORKER % {"root": root}], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
-    outs = []
-    for p in procs:
-        o, e = p.communicate(timeout=300)
-        assert p.returncode == 0, e[-2000:]
-        outs.append(json.loads(o.strip().splitlines()[-1]))
-    return sorted(outs, key=lambda d: d["rank"])
+    return rank_world.run_world(GLOO_WORKER % {"root": os.path.dirname(os.path.dirname(os.path.abspath(__file__)))}, world, timeout=300)
 
 
 def test_world2_gloo_grids_equal_the_unsharded_grid():
