@@ -632,6 +632,47 @@ int pcl_step_shell_crossings(pcl_ctx *ctx, int n_shells, const double *radii_hos
                              int64_t *counts_out_host,                      /* [2][n_shells]: outward, inward */
                              int64_t *E_hist_out_host, int64_t *mu_hist_out_host);   /* may be NULL with 0 bins */
 
+/* A reflecting sphere: the ground of a radial problem (SurfaceReflectStep).  Photons whose last move took them into the sphere
+ * of ``radius`` > 0 (finite, R2 = radius*radius finite, made on the host) about center_host (3 finite doubles, NULL = the
+ * origin) are put back in ONE sweep of the resident store: reflected where the move met the sphere, or -- with albedo < 1 --
+ * absorbed there and left in the store at rest.  Nothing is removed, the count does not change, E, ids and kinds are not touched
+ * and E is not even asked for (a wavelength-dependent scatter step keeps its term cache).  Meant to be the last call of a pass.
+ * All arithmetic is fp64, every operation rounded once, in the order written (x.y of two vectors is (x0*y0 + x1*y1) + x2*y2
+ * everywhere); an fp32 store's values are widened first (exact) and what is written is rounded once to the store's dtype.
+ *   d = r - center;  m = dr;  p = d - m (the position before the last move);  q_now = d.d;  q_prev = p.p
+ *   hit  iff  q_now < R2 and R2 <= q_prev and q_prev < inf, and the particle is a photon
+ * -- the inward crossing of pcl_step_shell_crossings for one shell, so that tally (made BEFORE this call) counts exactly the
+ * photons hit, except for a move whose q_prev is not finite (it has no hit point: counted there, left alone here).  NaN
+ * anywhere: not hit.  Plain Objects (kind 0) are never hit.  A particle that is not hit is not written at all.
+ *   a = m.m;  b = p.m;  cq = q_prev - R2;  disc = max(b*b - a*cq, 0);  t = cq / (sqrt(disc) - b)        (0 <= t <= 1; b < 0 on a hit)
+ *   x = p + t*m (the hit point, about the centre);  nrm = x / sqrt(x.x) (the outward normal);  sa = sqrt(a);  w = (1 - t)*sa
+ * Outcome: reflected iff albedo == 1 or u_0 < albedo (albedo 0: every hit is absorbed, no matter what is drawn).
+ *   absorbed:    r = center + x;  v = 0;  dr = x - p;  dv = 0 - v_old
+ *   PCL_SURFACE_SPECULAR:    mh = m / sa;  dn = mh.nrm;  dir = mh - (2*dn)*nrm                               (no draw)
+ *   PCL_SURFACE_LAMBERTIAN:  mu = sqrt(1 - u_a);  s = sqrt((1 - mu)*(1 + mu));  psi = (u_b*2)*pi;  sc = s*cos psi;  ss = s*sin psi;
+ *     the frame of Duff et al. (2017), branch-free:  sg = copysign(1, nrm2);  aa = -1/(sg + nrm2);  bb = (nrm0*nrm1)*aa;
+ *     sn0 = sg*nrm0;  e1 = (1 + (sn0*nrm0)*aa, sg*bb, -sn0);  e2 = (bb, sg + (nrm1*nrm1)*aa, -nrm1);
+ *     dir = (sc*e1 + ss*e2) + mu*nrm   -- cosine-weighted about nrm, mu > 0 always; sin / cos are the scatter step's own
+ *   reflected:   v = c*dir;  dv = v - v_old;  dr = w*dir;  r = center + (x + dr)    (the rest of the move, flown along dir)
+ * ``c`` = the speed of light in code units (what the scatter step is handed).  The draws are Philox4x32-10 blocks with the key
+ * (seed_lo, seed_hi) and u53 of pcl_store_apply_source: counter (id_lo, id_hi, pass, 8): u_a = u53(w0, w1), u_b = u53(w2, w3);
+ * counter (id_lo, id_hi, pass, 9): u_0 = u53(w0, w1), drawn only with albedo < 1.  ``pass`` is the caller's own counter; the
+ * scatter kernels use the counter words (step >> 1, 0) and (step, 1), fill and source (0xFFFFFFFF, 2..5): no block is shared,
+ * and a photon draws the same numbers however the run is sharded.
+ * counts_out_host[0] = photons reflected, [1] = absorbed, by this call.
+ * A uniform store (pcl_store_is_uniform) runs from the device alone.  Any other store costs host traffic, every call: its ids
+ * are downloaded (8 B per particle) and, unless they turn out to be id[0] + index, uploaded again behind the counters (8 B);
+ * its kinds are downloaded (1 B) and uploaded (1 B) if a plain Object is among them.
+ * PCL_ERR_ARG (NULL counts, unknown mode, radius not positive / not finite / its square not finite, centre or c not finite,
+ * albedo outside [0, 1]) is returned before anything is launched or written; PCL_ERR_STATE without a store; an empty store
+ * answers zeros without a launch.  Host pointers; one device allocation per call, handed back on every way out; synchronises
+ * once, with the copy of the two counts.  pcl_last_error() is generic for these two entry points, as for
+ * pcl_step_plane_spectra: they are compiled from a source file of their own (physicl_amd/csrc/pcl_surface.hip). */
+#define PCL_SURFACE_LAMBERTIAN 0
+#define PCL_SURFACE_SPECULAR 1
+int pcl_step_surface_reflect(pcl_ctx *ctx, double radius, const double *center_host, double albedo, int mode, double c,
+                             uint64_t seed, uint32_t pass, int64_t *counts_out_host /* [2]: reflected, absorbed */);
+
 /* ---- Device groups: several GPUs from ONE process ---------------------------------------------------------------
  * The reference is a single process with one simulation thread (physicl/__init__.py:400-432, 501-524); this is how
  * a host written against this ABI uses a node's GPUs the same way, without one process per GPU.  A group owns one
@@ -692,6 +733,10 @@ int pcl_group_step_position_grid(pcl_group *group, int n_axes, const int *coords
 int pcl_group_step_shell_crossings(pcl_group *group, int n_shells, const double *radii_host, const double *center_host,
                                    const double *E_edges_host, int n_E_bins, const double *mu_edges_host, int n_mu_bins,
                                    int64_t *counts_out_host, int64_t *E_hist_out_host, int64_t *mu_hist_out_host);
+/* pcl_step_surface_reflect on every shard (side by side), the two counts summed over the group's devices; the arguments
+ * are checked once for the group, before any shard is written */
+int pcl_group_step_surface_reflect(pcl_group *group, double radius, const double *center_host, double albedo, int mode, double c,
+                                   uint64_t seed, uint32_t pass, int64_t *counts_out_host);
 
 /* ---------------------------------------------------------------- the counters' collective (one process per GPU)
  * The path shards by global index with no data-path exchange; the only global quantities are the int64

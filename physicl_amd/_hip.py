@@ -27,6 +27,7 @@ SRC_SPATIAL = {"point": 0, "disc": 1, "gaussian": 2}                         # P
 GRID_COORDS = {"x": 0, "y": 1, "z": 2, "r": 3}                               # PCL_GRID_X ... PCL_GRID_RADIUS
 GRID_MAX_AXES, GRID_MAX_BINS, GRID_MAX_CELLS = 3, 1024, 1 << 20
 SHELL_MAX_SHELLS, SHELL_MAX_BINS, SHELL_MAX_CELLS = 16, 1024, 8192              # PCL_SHELL_MAX_SHELLS ...
+SURFACE_MODES = {"lambertian": 0, "specular": 1}                             # PCL_SURFACE_LAMBERTIAN, PCL_SURFACE_SPECULAR
 PROF_NEWTON, PROF_SCATTER, PROF_DELETE_MASK, PROF_COMPACT, PROF_COUNTERS, PROF_FUSED, PROF_MULTI, PROF_ONEPASS, \
     PROF_DELETE_AHEAD = range(9)
 PROF_NAMES = {PROF_NEWTON: "k_newton", PROF_SCATTER: "k_scatter", PROF_DELETE_MASK: "k_delete_mask",
@@ -148,6 +149,7 @@ _PROTOTYPES = {
     "pcl_step_plane_spectra": [_vp, _vp, c_int, _vp, c_int, _vp, _vp],
     "pcl_step_position_grid": [_vp, c_int, _vp, _vp, _vp, _vp, _vp],
     "pcl_step_shell_crossings": [_vp, c_int, _vp, _vp, _vp, c_int, _vp, c_int, _vp, _vp, _vp],
+    "pcl_step_surface_reflect": [_vp, c_double, _vp, c_double, c_int, c_double, c_uint64, c_uint32, _vp],
     # device groups: several GPUs from one process (the C-level counterpart of physicl_amd.multidev.MultiDevice)
     "pcl_group_create": [c_int, POINTER(c_int), POINTER(_vp)],
     "pcl_group_destroy": [_vp],
@@ -174,6 +176,7 @@ _PROTOTYPES = {
     "pcl_group_apply_source": [_vp, _vp, c_double, c_uint64],
     "pcl_group_step_position_grid": [_vp, c_int, _vp, _vp, _vp, _vp, _vp],
     "pcl_group_step_shell_crossings": [_vp, c_int, _vp, _vp, _vp, c_int, _vp, c_int, _vp, _vp, _vp],
+    "pcl_group_step_surface_reflect": [_vp, c_double, _vp, c_double, c_int, c_double, c_uint64, c_uint32, _vp],
 }
 EXPORTS = sorted(list(_PROTOTYPES) + ["pcl_last_error"])
 
@@ -327,6 +330,16 @@ def _shells(entry, handle, radii, center=None, E_edges=None, mu_edges=None):
     check(entry(handle, S, ra.ctypes.data, ptr(ce), ptr(edges[0]), nb(edges[0]), ptr(edges[1]), nb(edges[1]), counts.ctypes.data,
                 ptr(hists[0]), ptr(hists[1])))
     return counts, hists[0], hists[1]
+
+
+def _surface(entry, handle, radius, center, albedo, mode, c, seed, n_pass):
+    """One call of pcl_step_surface_reflect / pcl_group_step_surface_reflect: (reflected, absorbed) of this call.  ``mode``:
+    "lambertian", "specular" or the header's numbers; ``n_pass``: the caller's own pass counter (a Philox counter word)."""
+    ce = None if center is None else np.ascontiguousarray(center, dtype=np.float64).reshape(3)
+    counts = np.zeros(2, dtype=np.int64)
+    check(entry(handle, float(radius), None if ce is None else ce.ctypes.data, float(albedo), int(SURFACE_MODES.get(mode, mode)),
+                float(c), int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_pass) & 0xFFFFFFFF, counts.ctypes.data))
+    return int(counts[0]), int(counts[1])
 
 
 class SourceStruct(ctypes.Structure):
@@ -902,6 +915,12 @@ class Device:
         ``mu_edges``: of the cosine between the move and the outward normal.  ShellCrossingMeasureStep."""
         return _shells(self.lib.pcl_step_shell_crossings, self.ctx, radii, center, E_edges, mu_edges)
 
+    def surface_reflect(self, radius, center=None, albedo=1.0, mode="lambertian", c=0.0, seed=0, n_pass=0):
+        """The photons whose last move took them into the sphere of ``radius`` about ``center`` (None: the origin) are put
+        back, in one sweep (pcl_step_surface_reflect): reflected at the hit point (``mode``: "lambertian" or "specular") with
+        speed ``c``, or -- with probability 1 - ``albedo`` -- left there at rest.  ``(reflected, absorbed)``.  SurfaceReflectStep."""
+        return _surface(self.lib.pcl_step_surface_reflect, self.ctx, radius, center, albedo, mode, c, seed, n_pass)
+
 
 class DeviceGroup:
     """``pcl_group_*``: several contexts in one process, sharded by global index, behind the C ABI (the shim owns the
@@ -1001,6 +1020,10 @@ class DeviceGroup:
     def shell_crossings(self, radii, center=None, E_edges=None, mu_edges=None):
         """``Device.shell_crossings`` summed over the group's contexts (pcl_group_step_shell_crossings)."""
         return _shells(self.lib.pcl_group_step_shell_crossings, self.g, radii, center, E_edges, mu_edges)
+
+    def surface_reflect(self, radius, center=None, albedo=1.0, mode="lambertian", c=0.0, seed=0, n_pass=0):
+        """``Device.surface_reflect`` on every context of the group, the counts summed (pcl_group_step_surface_reflect)."""
+        return _surface(self.lib.pcl_group_step_surface_reflect, self.g, radius, center, albedo, mode, c, seed, n_pass)
 
     def download(self, field, n=None, offset=0, dtype=None):
         n = self.count - offset if n is None else n

@@ -1,5 +1,5 @@
 // pcl_sweep.h -- what the units built on the public C ABI beside the tuned core (pcl_spectrum / pcl_source / pcl_shell /
-// pcl_grid .hip) share: one sweep of the resident store per call, tallied into workgroup-private cells.  Only those units
+// pcl_grid / pcl_surface .hip) share: one sweep of the resident store per call, tallied into workgroup-private cells.  Only those units
 // include it; it knows nothing of physicl_hip.hip, pcl_device.h or pcl_sincos.h, and they nothing of it (build.py: csrc_sha).
 //
 // Two layers: plain host arithmetic that any C++ program can include (tests/native/sweep_host.cpp does), and under
@@ -141,14 +141,39 @@ inline int kind_bytes(pcl_ctx *ctx, int64_t N, std::vector<uint8_t> &kind, bool 
     return PCL_OK;
 }
 
-// A call's one device block, on the store's stream: out_bytes of zeroed tallies | the tables | the kind bytes (if any)
+// Ids for a unit whose draws are keyed by the particle's id.  A uniform store keeps no id array: its one id is answered on
+// the host, *id_base = the id of slot 0 and ``ids`` stays empty.  Any other store's N ids are downloaded (the ABI hands them out
+// on the host only: 8 B per particle over the host link, every call); if they turn out to be id[0] + index they are dropped
+// again, otherwise they stay in ``ids`` for stage() to put behind the tables (another 8 B per particle).
+inline int id_words(pcl_ctx *ctx, int64_t N, std::vector<int64_t> &ids, int64_t *id_base) {
+    int uniform = 0;
+    *id_base = 0;
+    ids.clear();
+    if (N <= 0) return PCL_OK;
+    PCL_SWEEP_TRY(pcl_store_is_uniform(ctx, &uniform));
+    if (uniform) return pcl_store_download_ids(ctx, id_base, 0, 1);
+    ids.resize((size_t)N);
+    PCL_SWEEP_TRY(pcl_store_download_ids(ctx, ids.data(), 0, N));
+    *id_base = ids[0];
+    for (int64_t i = 0; i < N; ++i)
+        if (ids[(size_t)i] != *id_base + i) return PCL_OK;
+    ids.clear();
+    return PCL_OK;
+}
+
+// A call's one device block, on the store's stream: out_bytes of zeroed tallies | the tables (if any) | the ids (if any; out_bytes
+// and tab_bytes are multiples of 8) | the kind bytes (if any)
 inline int stage(dev_block &blk, hipStream_t stream, size_t out_bytes, const double *tables, size_t tab_bytes,
-                 const std::vector<uint8_t> &kind = {}) {
-    PCL_SWEEP_TRY(pcl_dev_alloc(blk.ctx, (int64_t)(out_bytes + tab_bytes + kind.size()), &blk.p));
+                 const std::vector<uint8_t> &kind = {}, const std::vector<int64_t> &ids = {}) {
+    const size_t id_bytes = ids.size() * sizeof(int64_t);
+    PCL_SWEEP_TRY(pcl_dev_alloc(blk.ctx, (int64_t)(out_bytes + tab_bytes + id_bytes + kind.size()), &blk.p));
     char *base = static_cast<char *>(blk.p);
     if (hipMemsetAsync(base, 0, out_bytes, stream) != hipSuccess) return PCL_ERR_HIP;
-    if (hipMemcpyAsync(base + out_bytes, tables, tab_bytes, hipMemcpyHostToDevice, stream) != hipSuccess) return PCL_ERR_HIP;
-    if (!kind.empty() && hipMemcpyAsync(base + out_bytes + tab_bytes, kind.data(), kind.size(), hipMemcpyHostToDevice, stream) != hipSuccess)
+    if (tab_bytes && hipMemcpyAsync(base + out_bytes, tables, tab_bytes, hipMemcpyHostToDevice, stream) != hipSuccess) return PCL_ERR_HIP;
+    if (id_bytes && hipMemcpyAsync(base + out_bytes + tab_bytes, ids.data(), id_bytes, hipMemcpyHostToDevice, stream) != hipSuccess)
+        return PCL_ERR_HIP;
+    if (!kind.empty() &&
+        hipMemcpyAsync(base + out_bytes + tab_bytes + id_bytes, kind.data(), kind.size(), hipMemcpyHostToDevice, stream) != hipSuccess)
         return PCL_ERR_HIP;
     return PCL_OK;
 }

@@ -685,6 +685,187 @@ class ShellCrossingMeasureStep(tally.TallyStep):
         return [np.array(side, dtype=np.int64) for x in parts if x is not None for side in (x[0], x[1])]
 
 
+# ---------------------------------------------------------------------------------------------- surface reflection
+_U32 = np.uint64(0xFFFFFFFF)
+
+
+def _philox_block(ids, seed, word2, word3):
+    """(u53(w0, w1), u53(w2, w3)) of the Philox4x32-10 block with counter (id_lo, id_hi, word2, word3) and key (seed_lo,
+    seed_hi) per id, with numpy -- the block and the 53-bit uniform of include/physicl_hip.h (pcl_store_apply_source)."""
+    ids = np.asarray(ids).astype(np.uint64)
+    cnt = [ids & _U32, ids >> np.uint64(32), np.full(ids.shape, int(word2) & 0xFFFFFFFF, dtype=np.uint64),
+           np.full(ids.shape, int(word3) & 0xFFFFFFFF, dtype=np.uint64)]
+    key = [int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF]
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * cnt[0], np.uint64(0xCD9E8D57) * cnt[2]          # 32 x 32 -> 64 bits: no overflow
+        cnt = [(p1 >> np.uint64(32)) ^ cnt[1] ^ np.uint64(key[0]), p1 & _U32, (p0 >> np.uint64(32)) ^ cnt[3] ^ np.uint64(key[1]), p0 & _U32]
+        key = [(key[0] + 0x9E3779B9) & 0xFFFFFFFF, (key[1] + 0xBB67AE85) & 0xFFFFFFFF]
+    u53 = lambda a, b: ((a >> np.uint64(5)) * np.uint64(1 << 26) + (b >> np.uint64(6))).astype(np.float64) * (1.0 / 9007199254740992.0)   # noqa: E731
+    return u53(cnt[0], cnt[1]), u53(cnt[2], cnt[3])
+
+
+def _dot3(x, y):
+    return (x[:, 0] * y[:, 0] + x[:, 1] * y[:, 1]) + x[:, 2] * y[:, 2]
+
+
+def _check_surface(radius, center, albedo, mode):
+    """(radius, centre as 3 float64, albedo, mode) of a SurfaceReflectStep, or ValueError for everything
+    pcl_step_surface_reflect would refuse."""
+    from ._hip import SURFACE_MODES
+    try:
+        radius = float(np.asarray(radius, dtype=np.float64).reshape(()))
+    except (TypeError, ValueError):
+        raise ValueError("radius must be a number") from None
+    if not (np.isfinite(radius) and radius > 0 and np.isfinite(radius * radius)):
+        raise ValueError("radius must be finite and positive (its square finite, too), got %r" % (radius,))
+    center = tally.check_center(center)
+    try:
+        albedo = float(np.asarray(albedo, dtype=np.float64).reshape(()))
+    except (TypeError, ValueError):
+        raise ValueError("albedo must be a number") from None
+    if not 0.0 <= albedo <= 1.0:                          # (False for NaN as well)
+        raise ValueError("albedo must lie in [0, 1], got %r" % (albedo,))
+    if not isinstance(mode, str) or mode not in SURFACE_MODES:
+        raise ValueError("mode must be 'lambertian' or 'specular', got %r" % (mode,))
+    return radius, center, albedo, mode
+
+
+def _surface_bounce(r, dr, v, photon, ids, radius, center, albedo, mode, c, seed, n_pass, dtype=np.float64):
+    """What pcl_step_surface_reflect makes of (n, 3) float64 positions, last moves and velocities, who is a photon and the
+    particles' ids, with numpy -- every operation the device's operation in the device's order, one rounding each
+    (include/physicl_hip.h), and what is written rounded once to ``dtype``.  Everything but sin / cos of the lambertian angle
+    (libm here, the library's own on the device) is the device's bit for bit.  A dict: ``r, v, dr, dv`` the new state (float64
+    arrays; rows of particles that are not hit are the arguments', zeros in ``dv``), ``hit, reflected, absorbed`` boolean masks, and of the hit
+    particles (NaN elsewhere) ``t``, ``x`` (the hit point about the centre), ``nrm`` and -- lambertian -- ``mu``."""
+    r, dr, v = (np.array(a, dtype=np.float64).reshape(-1, 3) for a in (r, dr, v))
+    n = len(r)
+    center, c, R2 = np.asarray(center, dtype=np.float64), np.float64(c), np.float64(radius) * np.float64(radius)
+    with np.errstate(invalid="ignore", over="ignore"):
+        d = r - center
+        p = d - dr
+        q_now, q_prev = _dot3(d, d), _dot3(p, p)
+        hit = (q_now < R2) & (q_prev >= R2) & (q_prev < np.inf) & np.asarray(photon, dtype=bool).reshape(-1)
+    at = np.flatnonzero(hit)
+    ids = np.asarray(ids).reshape(-1)[at]
+    refl = np.ones(len(at), dtype=bool)
+    if albedo < 1.0:
+        refl = _philox_block(ids, seed, n_pass, 9)[0] < albedo
+    out = {"hit": hit, "reflected": np.zeros(n, dtype=bool), "absorbed": np.zeros(n, dtype=bool),
+           "t": np.full(n, np.nan), "x": np.full((n, 3), np.nan), "nrm": np.full((n, 3), np.nan), "mu": np.full(n, np.nan)}
+    out["reflected"][at[refl]], out["absorbed"][at[~refl]] = True, True
+    m, p, vo = dr[at], p[at], v[at]
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        a, b, cq = _dot3(m, m), _dot3(p, m), q_prev[at] - R2
+        disc = np.fmax(b * b - a * cq, 0.0)
+        t = cq / (np.sqrt(disc) - b)
+        x = p + t[:, None] * m
+        nrm = x / np.sqrt(_dot3(x, x))[:, None]
+        sa = np.sqrt(a)
+        if mode == "specular":
+            mh = m / sa[:, None]
+            direction = mh - (2.0 * _dot3(mh, nrm))[:, None] * nrm
+        else:
+            u_a, u_b = _philox_block(ids, seed, n_pass, 8)
+            mu = np.sqrt(1.0 - u_a)
+            sn = np.sqrt((1.0 - mu) * (1.0 + mu))
+            psi = (u_b * 2.0) * np.pi
+            sc, ss = sn * np.cos(psi), sn * np.sin(psi)
+            n0, n1, n2 = nrm[:, 0], nrm[:, 1], nrm[:, 2]
+            sg = np.copysign(1.0, n2)
+            aa = -1.0 / (sg + n2)
+            bb, sn0 = (n0 * n1) * aa, sg * n0
+            e1 = np.stack([1.0 + (sn0 * n0) * aa, sg * bb, -sn0], axis=1)
+            e2 = np.stack([bb, sg + (n1 * n1) * aa, -n1], axis=1)
+            direction = (sc[:, None] * e1 + ss[:, None] * e2) + mu[:, None] * nrm
+            out["mu"][at] = mu
+        w = (1.0 - t) * sa
+        v_new = c * direction
+        dr_new = w[:, None] * direction
+        r_new = center + (x + dr_new)
+        dv_new = v_new - vo
+        gone = ~refl                                       # absorbed: parked on the sphere, at rest
+        r_new[gone], v_new[gone], dr_new[gone], dv_new[gone] = (center + x)[gone], 0.0, (x - p)[gone], (0.0 - vo)[gone]
+        for name, new in (("r", r_new), ("v", v_new), ("dr", dr_new), ("dv", dv_new)):
+            full = {"r": r, "v": v, "dr": dr}.get(name)
+            full = np.zeros((n, 3)) if full is None else full
+            full[at] = new.astype(dtype).astype(np.float64)
+            out[name] = full
+    out["t"][at], out["x"][at], out["nrm"][at] = t, x, nrm
+    return out
+
+
+class SurfaceReflectStep(DeviceStep, MeasureStep):
+    """A reflecting sphere: the ground of a radial problem (not in the reference).  Every photon whose last move took it into
+    the sphere of ``radius`` about ``center`` (code units) is put back: reflected at the point where the move met the sphere
+    -- ``mode="lambertian"``: cosine-weighted about the outward normal, ``"specular"``: mirrored -- with the rest of the move
+    flown along the new direction, or, with probability ``1 - albedo``, absorbed: left in the store AT REST on the sphere
+    (``v = 0``, ``dr`` the move up to the hit point, ``dv = -v_old``).  Nothing is removed, ``len(sim.objects)`` does not change.
+    After each run ``self.reflected`` and ``self.absorbed`` hold the pass's counts (global over shards and ranks) and
+    ``self.data`` gains the row ``[t, reflected, absorbed]``; ``out_fn`` takes the rows at the end of the run.
+
+    Put the step LAST in a pass: behind the Newton step, the scatter step and any measures.  Tally the ground with a
+    ``ShellCrossingMeasureStep`` of the same radius and centre placed BEFORE it: that tally sees the incoming move, and its
+    ``in`` count is this step's ``reflected + absorbed`` (a photon is hit iff ``q_now < R*R <= q_prev``, the shell's own rule in
+    float64; a move from infinitely far is counted there and left alone here).  A shell of the same radius BEHIND the step sees
+    the outgoing segment, which starts on the sphere: its side there is decided by rounding.  Plain ``Object``s and particles with
+    a NaN in ``r`` or ``dr`` are never hit.  The arithmetic is written out in include/physicl_hip.h
+    (pcl_step_surface_reflect); ``_surface_bounce`` restates it with numpy.
+
+    Absorbed photons no longer move (Newton: ``dr = v*dt = 0``) and cross nothing, so a ``PositionGridMeasureStep`` shows where
+    the light landed.  They are still looked at by the scatter steps: the kernels' hit test is ``pcoll >= rand`` with
+    ``pcoll = A*n*|dr| = 0`` for a photon at rest, true only for a draw of exactly 0 -- once in 2**53 draws (and never
+    otherwise, unless ``n`` is infinite there: 0*inf is NaN, which compares false).  A ScatterIsotropicStep that does hit
+    re-directs the photon with speed c, a ScatterDeleteStep removes it: absorbed photons are recognised by ``v == 0`` only until
+    then.  The scatter kernels are left as they are.
+
+    The draws are Philox blocks keyed by ``sim.seed``, the photon's id and a pass counter of the step's own, in counter words no
+    other kernel uses -- so the scatter steps of a simulation draw what they draw without this step, and a photon draws the same
+    numbers however the run is sharded.  They are made on the device with EVERY ``rng=`` setting: the step is not in the
+    reference, so there is no host stream to reproduce.
+
+    One launch per light step: the K-passes-per-launch kernels cannot bounce a photon between two of their passes, and
+    ``sim.launch_note`` says so.  On host-resident objects (``step.run(sim)`` outside a device loop) the same state is made with
+    numpy, the ids being the places in the object list -- what an upload would give them."""
+    _fuse_role = None
+    _NOTE = "one launch per light step: a SurfaceReflectStep bounces photons off its sphere behind every pass, which the " \
+            "K-passes-per-launch kernels cannot carry"
+
+    def __init__(self, radius, center=(0, 0, 0), albedo=1.0, mode="lambertian", out_fn=None):
+        MeasureStep.__init__(self, out_fn)
+        self.radius, self.center, self.albedo, self.mode = _check_surface(radius, center, albedo, mode)
+        self.reflected = self.absorbed = 0
+        self._pass = 0                                   # the step's own Philox counter word: one per run
+
+    def _record_pass(self, sim, reflected, absorbed):
+        self.reflected, self.absorbed = int(reflected), int(absorbed)
+        self.data.append(tally.object_row([tally._snap(sim.t), self.reflected, self.absorbed]))
+
+    def _device_run(self, sim):
+        if getattr(sim, "launch_note", self._NOTE) is None and sim._k_wanted() > 1:      # (a device run only: the host path says nothing)
+            sim.launch_note = self._NOTE
+        self._pass += 1
+        counts = sim._dev.surface_reflect(self.radius, self.center, self.albedo, self.mode, _c_h_literals()[0], sim.seed, self._pass)
+        sim._scattered = True                            # velocities were replaced on the device
+        self._record_pass(sim, *sim._global(list(counts)))   # (every rank issues it, also with an empty shard)
+
+    def run(self, sim):
+        if getattr(sim, "_residency", None) == "host" and getattr(sim, "_batch", None) is None \
+                and (sim.comm is None or sim.comm.world == 1):
+            objs = list(sim.objects)
+            self._pass += 1
+            photon = np.array([type(o) is PhotonObject for o in objs], dtype=bool)
+            new = _surface_bounce(tally.vec3(objs, "r"), tally.vec3(objs, "dr"), tally.vec3(objs, "v"), photon, np.arange(len(objs)),
+                                  self.radius, self.center, self.albedo, self.mode, _c_h_literals()[0], getattr(sim, "seed", 0), self._pass)
+            for k in np.flatnonzero(new["hit"]).tolist():
+                o = objs[k]
+                o.r = Measurement._from_code(new["r"][k], like=o.r, units="m**1")
+                o.dr = Measurement._from_code(new["dr"][k], units="m**1")
+                o.v, o.dv = np.array(new["v"][k], dtype=np.double), np.array(new["dv"][k], dtype=np.double)   # plain arrays, as a scatter leaves them
+            self._record_pass(sim, new["reflected"].sum(), new["absorbed"].sum())
+            return None
+        return DeviceStep.run(self, sim)
+
+
 def _DEFAULT_ID_INFO(x):
     """The reference's default ``lambda x: str(type(x))`` (light.py:438), recognised by identity.  The label goes into the trace
     table's first column: this package's own classes read as the reference's (``<class 'physicl.light.PhotonObject'>``, what a

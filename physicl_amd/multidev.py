@@ -275,6 +275,10 @@ class MultiDevice:
         parts = self._each(lambda s: s.shell_crossings(radii, center, E_edges, mu_edges))
         return tuple(None if part[0] is None else self._sum(list(part)) for part in zip(*parts))
 
+    def surface_reflect(self, *a, **kw):
+        outs = self._each(lambda s: s.surface_reflect(*a, **kw))
+        return sum(o[0] for o in outs), sum(o[1] for o in outs)
+
     def plane_energies(self, plane, n_hint=None):
         return self._concat(self._each(lambda s: s.plane_energies(plane)))      # (a shard does not know its share of the hint)
 
