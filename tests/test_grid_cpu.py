@@ -5,14 +5,12 @@
 * the constructor's checks;
 * what ``Device.position_grid`` / ``DeviceGroup.position_grid`` put over the C ABI and hand back, on a stand-in for the
   library in the manner of tests/test_binding_marshal_cpu.py;
-* the build lists, the library's exports and the unit's device assembly (no scratch, no spills, both dtypes, both forms);
+* (the unit's build is held in tests/test_build_cpu.py);
 * the host path -- the step called on host-resident Python objects -- and the ``every=`` run counter;
 * two gloo ranks on the host side of the collective all-reduce to the unsharded grid.
 """
-import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -167,49 +165,6 @@ def test_prototypes_constants_and_multidevice_sum():
     got = md.position_grid(("x", "y"), [E2, [0, 1, 2, 3]])
     md._pool.shutdown()
     assert got.dtype == np.int64 and got.tolist() == [[111] * 3] * 2
-
-
-# ------------------------------------------------------------------------------------------------ build
-def test_build_lists():
-    assert build.csrc_sha() == "b54e0443ee3f400f"                      # the priced kernels' three files are byte-identical
-    assert os.path.basename(build.LATER_UNITS[0]) == "pcl_source.hip"
-    assert os.path.basename(build.LATER_UNITS[-1]) == "pcl_grid.hip" and os.path.exists(build.LATER_UNITS[-1])
-    assert [os.path.basename(s) for s in build.SOURCES] == ["physicl_hip.hip", "pcl_device.h", "pcl_sincos.h", "physicl_hip.h", "pcl_spectrum.hip"]
-    assert [os.path.basename(s) for s in build.UNITS] == ["physicl_hip.hip", "pcl_spectrum.hip"]
-
-
-def test_needs_build_sees_the_grid_unit(tmp_path, monkeypatch):
-    lib = tmp_path / "lib.so"
-    lib.write_bytes(b"")
-    monkeypatch.setattr(build, "LIB", str(lib))
-    newest = max(os.path.getmtime(s) for s in build.SOURCES + build.LATER_UNITS + build.LATER_HEADERS + [build.__file__])
-    os.utime(str(lib), (newest + 10, newest + 10))
-    assert not build.needs_build()
-    unit = build.LATER_UNITS[-1]
-    assert os.path.basename(unit) == "pcl_grid.hip"
-    monkeypatch.setattr(os.path, "getmtime", lambda p, real=os.path.getmtime: real(p) + (1e6 if p == unit else 0))
-    assert build.needs_build()
-
-
-def test_library_builds_with_the_new_unit_and_exports_both_entry_points():
-    build.build_lib()
-    lib = ctypes.CDLL(_hip.LIB_PATH)
-    assert hasattr(lib, "pcl_step_position_grid") and hasattr(lib, "pcl_group_step_position_grid")
-
-
-def test_grid_kernels_use_no_scratch(tmp_path):
-    """From the unit's assembly, compiled with the library's own options: both dtypes, both forms, nothing in scratch, no spills."""
-    out = str(tmp_path / "pcl_grid.s")
-    subprocess.check_call([build.HIPCC] + [f for f in build.FLAGS if f not in ("-shared", "-fPIC")] +
-                          ["--cuda-device-only", "-S", "-o", out, build.LATER_UNITS[-1]], stderr=subprocess.DEVNULL)
-    text = open(out).read()
-    kernels = re.findall(r"\.name:\s+(_Z\w*k_position_grid\w*)\n(.*?)\.wavefront_size", text, re.S)
-    assert len(kernels) == 4, [k for k, _ in kernels]                  # <double | float> x <LDS form | global form>
-    for name, blk in kernels:
-        get = lambda k: int(re.search(r"\.%s:\s+(\d+)" % k, blk).group(1))                                  # noqa: E731
-        assert get("private_segment_fixed_size") == 0 and get("vgpr_spill_count") == 0 and get("sgpr_spill_count") == 0, name
-    assert "global_atomic_add_x2" in text and "ds_add_u32" in text     # 64-bit adds on the device grid, 32-bit ones in LDS
-    assert "v_fma_f64" not in text and "v_sqrt" not in text            # q is unfused, and no square root anywhere
 
 
 # ------------------------------------------------------------------------------------------------ host path

@@ -78,7 +78,7 @@ def aot_meta():
     if not os.path.exists(path):
         tmp = path + ".tmp%d" % os.getpid()
         subprocess.check_call([build.HIPCC] + [f for f in build.FLAGS if f not in ("-shared", "-fPIC")] +
-                              ["--cuda-device-only", "-S", "-o", tmp, build.SOURCES[0]], stderr=subprocess.DEVNULL)
+                              ["--cuda-device-only", "-S", "-o", tmp, build.CORE["src"]], stderr=subprocess.DEVNULL)
         os.replace(tmp, path)
     text = open(path).read()
     meta = {}

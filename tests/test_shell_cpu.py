@@ -3,15 +3,12 @@
 * the numpy restatement (tests/shell_reference.py) agrees with a per-particle Python loop written from the header's text, on
   drawn points and on hand-made edge cases; the package's own host-path statement agrees with both;
 * the step called on host-resident Python objects (plain Objects among the photons) files the restatement's row;
-* the constructor's checks; header constants against ``_hip``; the build list, the library's exports and the unit's device
-  metadata (no scratch, no spills, both dtypes);
+* the constructor's checks; header constants against ``_hip`` (the unit's build is held in tests/test_build_cpu.py);
 * ``MultiDevice.shell_crossings`` sums stand-in shards; what ``Device.shell_crossings`` / ``DeviceGroup.shell_crossings`` put
   over the C ABI and hand back, on a stand-in for the library in the manner of tests/test_binding_marshal_cpu.py.
 """
-import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -228,47 +225,3 @@ def test_prototypes_constants_and_multidevice_sum():
     md._pool.shutdown()
     assert counts.dtype == np.int64 and counts.tolist() == [[111] * 3] * 2 and E_hist is None and mu_hist.tolist() == [[[333] * 2] * 3] * 2
     assert both[1].shape == (2, 3, 4) and np.all(both[1] == 222)
-
-
-# ------------------------------------------------------------------------------------------------ build
-def shell_unit():
-    (unit,) = [u for u in build.LATER_UNITS if os.path.basename(u) == "pcl_shell.hip"]
-    return unit
-
-
-def test_build_lists():
-    assert build.csrc_sha() == "b54e0443ee3f400f"                      # the priced kernels' three files are byte-identical
-    assert [os.path.basename(u) for u in build.LATER_UNITS] == ["pcl_source.hip", "pcl_shell.hip", "pcl_grid.hip"]
-    assert os.path.exists(shell_unit()) and shell_unit() not in build.SOURCES
-
-
-def test_needs_build_sees_the_shell_unit(tmp_path, monkeypatch):
-    lib = tmp_path / "lib.so"
-    lib.write_bytes(b"")
-    monkeypatch.setattr(build, "LIB", str(lib))
-    newest = max(os.path.getmtime(s) for s in build.SOURCES + build.LATER_UNITS + build.LATER_HEADERS + [build.__file__])
-    os.utime(str(lib), (newest + 10, newest + 10))
-    assert not build.needs_build()
-    unit = shell_unit()
-    monkeypatch.setattr(os.path, "getmtime", lambda p, real=os.path.getmtime: real(p) + (1e6 if p == unit else 0))
-    assert build.needs_build()
-
-
-def test_library_builds_with_the_new_unit_and_exports_both_entry_points():
-    build.build_lib()
-    lib = ctypes.CDLL(_hip.LIB_PATH)
-    assert hasattr(lib, "pcl_step_shell_crossings") and hasattr(lib, "pcl_group_step_shell_crossings")
-
-
-def test_shell_kernels_use_no_scratch(tmp_path):
-    """From the unit's device metadata, compiled with the library's own options: both dtypes, nothing in scratch, no spills."""
-    out = str(tmp_path / "pcl_shell.s")
-    subprocess.check_call([build.HIPCC] + [f for f in build.FLAGS if f not in ("-shared", "-fPIC")] +
-                          ["--cuda-device-only", "-S", "-o", out, shell_unit()], stderr=subprocess.DEVNULL)
-    text = open(out).read()
-    kernels = re.findall(r"\.name:\s+(_Z\w*k_shell_crossings\w*)\n(.*?)\.wavefront_size", text, re.S)
-    assert len(kernels) == 2, [k for k, _ in kernels]                  # <double | float>
-    for name, blk in kernels:
-        get = lambda k: int(re.search(r"\.%s:\s+(\d+)" % k, blk).group(1))                                  # noqa: E731
-        assert get("private_segment_fixed_size") == 0 and get("vgpr_spill_count") == 0 and get("sgpr_spill_count") == 0, name
-        assert get("vgpr_count") <= 64, name                           # eight waves per SIMD: occupancy is left to LDS

@@ -5,16 +5,15 @@
 * what ``Device.apply_source`` / ``DeviceGroup.apply_source`` put over the C ABI, on a stand-in for the library in the manner of
   tests/test_spectrum_cpu.py; ``Simulation._upload_locked`` on a stand-in device fills, then applies the source once -- and makes no
   such call without a source;
-* the library cross-compiles with the new unit, exports both entry points, the priced kernels' source hash has not moved, and
-  the new kernels use no scratch;
 * the numpy restatement of the draws (tests/source_reference.py) meets the distributions' own 5-sigma conditions at n = 2^20:
   what the GPU tests compare the device against is itself a sampler of the right distributions.
+
+The unit's build is held in tests/test_build_cpu.py.
 """
 import ctypes
 import inspect
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -200,42 +199,6 @@ def test_multidevice_applies_the_source_on_every_shard():
     md.apply_source(src, C, 4)
     md._pool.shutdown()
     assert [s.calls for s in md.shards] == [[("apply_source", src, C, 4)]] * 2
-
-
-# ------------------------------------------------------------------------------------------------ build
-def test_library_builds_with_the_new_unit_and_exports_both_entry_points():
-    assert build.csrc_sha() == "b54e0443ee3f400f"                      # the priced kernels' three files are byte-identical
-    unit = [u for u in build.LATER_UNITS if u.endswith("pcl_source.hip")]
-    assert len(unit) == 1 and os.path.exists(unit[0]) and unit[0] not in build.SOURCES[:3]
-    build.build_lib()
-    lib = ctypes.CDLL(_hip.LIB_PATH)
-    assert hasattr(lib, "pcl_store_apply_source") and hasattr(lib, "pcl_group_apply_source")
-
-
-def test_needs_build_sees_the_source_unit(tmp_path, monkeypatch):
-    lib = tmp_path / "lib.so"
-    lib.write_bytes(b"")
-    monkeypatch.setattr(build, "LIB", str(lib))
-    newest = max(os.path.getmtime(s) for s in build.SOURCES + build.LATER_UNITS + build.LATER_HEADERS + [build.__file__])
-    os.utime(str(lib), (newest + 10, newest + 10))
-    assert not build.needs_build()
-    unit = build.LATER_UNITS[0]
-    monkeypatch.setattr(os.path, "getmtime", lambda p, real=os.path.getmtime: real(p) + (1e6 if p == unit else 0))
-    assert build.needs_build()
-
-
-def test_source_kernels_use_no_scratch(tmp_path):
-    """From the unit's assembly, compiled with the library's own options: both instantiations, nothing in scratch, no spills."""
-    out = str(tmp_path / "pcl_source.s")
-    subprocess.check_call([build.HIPCC] + [f for f in build.FLAGS if f not in ("-shared", "-fPIC")] +
-                          ["--cuda-device-only", "-S", "-o", out, build.LATER_UNITS[0]], stderr=subprocess.DEVNULL)
-    text = open(out).read()
-    kernels = re.findall(r"\.name:\s+(_Z\w*k_apply_source\w*)\n(.*?)\.wavefront_size", text, re.S)
-    assert len(kernels) == 2, [k for k, _ in kernels]
-    for name, blk in kernels:
-        get = lambda k: int(re.search(r"\.%s:\s+(\d+)" % k, blk).group(1))                                  # noqa: E731
-        assert get("private_segment_fixed_size") == 0 and get("vgpr_spill_count") == 0 and get("sgpr_spill_count") == 0, name
-    assert "v_fma_f64" in text                                           # (the sincos' explicit FMAs; everything else is unfused)
 
 
 # ------------------------------------------------------------------------------------------------ the restatement itself

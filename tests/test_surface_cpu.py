@@ -1,10 +1,8 @@
 """CPU: SurfaceReflectStep -- the constructor's refusals, the numpy restatement of the sweep (light._surface_bounce) on seeded
-clouds, degenerate inputs, the host-resident path, the plan the step makes, and the build (the unit is compiled, linked and
-exports both entry points; the kernels use no scratch)."""
-import ctypes
+clouds, degenerate inputs, the host-resident path, the plan the step makes, the header's mode constants and the refusals that
+need no device (the unit's build is held in tests/test_build_cpu.py)."""
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -288,38 +286,10 @@ def test_multi_device_sums_the_shards_counts():
     assert got == (111, 222)
 
 
-# ------------------------------------------------------------------------------------------------ build
-def surface_unit():
-    (unit,) = [u for u in build.STEP_UNITS if os.path.basename(u) == "pcl_surface.hip"]
-    return unit
-
-
-def test_build_lists():
-    assert build.csrc_sha() == "b54e0443ee3f400f"                      # the priced kernels' three files are byte-identical
-    assert os.path.exists(surface_unit()) and surface_unit() not in build.SOURCES + build.LATER_UNITS
-
-
-def test_needs_build_sees_the_surface_unit(tmp_path, monkeypatch):
-    lib = tmp_path / "lib.so"
-    lib.write_bytes(b"")
-    monkeypatch.setattr(build, "LIB", str(lib))
-    newest = max(os.path.getmtime(s) for s in build.SOURCES + build.LATER_UNITS + build.STEP_UNITS + build.LATER_HEADERS + [build.__file__])
-    os.utime(str(lib), (newest + 10, newest + 10))
-    assert not build.needs_build()
-    unit = surface_unit()
-    monkeypatch.setattr(os.path, "getmtime", lambda p, real=os.path.getmtime: real(p) + (1e6 if p == unit else 0))
-    assert build.needs_build()
-
-
-def test_library_exports_both_entry_points_and_the_header_declares_them():
-    build.build_lib()
-    lib = ctypes.CDLL(_hip.LIB_PATH)
-    assert hasattr(lib, "pcl_step_surface_reflect") and hasattr(lib, "pcl_group_step_surface_reflect")
-    assert lib.pcl_abi_version() == 1
+# ------------------------------------------------------------------------------------------------ the library
+def test_header_defines_the_modes():
     text = open(os.path.join(ROOT, "include", "physicl_hip.h")).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    for name in ("pcl_step_surface_reflect", "pcl_group_step_surface_reflect"):
-        assert re.search(r"\b%s\s*\(" % name, text) and name in _hip.EXPORTS
     assert re.search(r"#define\s+PCL_SURFACE_LAMBERTIAN\s+0\b", text) and re.search(r"#define\s+PCL_SURFACE_SPECULAR\s+1\b", text)
     assert re.search(r"#define\s+PCL_ABI_VERSION\s+1\b", text) or "pcl_abi_version" in text
 
@@ -332,17 +302,3 @@ def test_refused_calls_need_no_device():
     assert lib.pcl_step_surface_reflect(None, 1.0, None, 1.0, 0, C, 1, 1, counts.ctypes.data) == -2
     assert lib.pcl_group_step_surface_reflect(None, 1.0, None, 1.0, 0, C, 1, 1, counts.ctypes.data) != 0
     assert counts.tolist() == [-7, -7]
-
-
-def test_surface_kernels_use_no_scratch(tmp_path):
-    """From the unit's device metadata, compiled with the library's own options: both dtypes, nothing in scratch, no VGPR spill."""
-    out = str(tmp_path / "pcl_surface.s")
-    subprocess.check_call([build.HIPCC] + [f for f in build.FLAGS if f not in ("-shared", "-fPIC")] +
-                          ["--cuda-device-only", "-S", "-o", out, surface_unit()], stderr=subprocess.DEVNULL)
-    text = open(out).read()
-    kernels = re.findall(r"\.name:\s+(_Z\w*k_surface_reflect\w*)\n(.*?)\.wavefront_size", text, re.S)
-    assert len(kernels) == 2, [k for k, _ in kernels]                  # <double | float>
-    for name, blk in kernels:
-        get = lambda k: int(re.search(r"\.%s:\s+(\d+)" % k, blk).group(1))                                  # noqa: E731
-        assert get("private_segment_fixed_size") == 0 and get("vgpr_spill_count") == 0, name
-        assert get("vgpr_count") <= 80, name                           # six waves per SIMD or more

@@ -12,8 +12,6 @@ import subprocess
 
 import pytest
 
-from physicl_amd import build
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAN, INF = float("nan"), float("inf")
 K_BLOCK, MAX_SLOTS = 256, 2 ** 32 - 256
@@ -156,21 +154,7 @@ def test_edge_check(ask):
             assert [float.fromhex(x).hex() for x in tok[1:]] == [float(x).hex() for x in want], (e, t, line)
 
 
-# ------------------------------------------------------------------------------------------------ build
-def test_needs_build_sees_the_shared_header(tmp_path, monkeypatch):
-    (header,) = build.LATER_HEADERS
-    assert os.path.basename(header) == "pcl_sweep.h" and os.path.exists(header)
-    assert header not in build.SOURCES + build.LATER_UNITS          # csrc_sha() and the compile line do not see it
-    lib = tmp_path / "lib.so"
-    lib.write_bytes(b"")
-    monkeypatch.setattr(build, "LIB", str(lib))
-    newest = max(os.path.getmtime(s) for s in build.SOURCES + build.LATER_UNITS + build.LATER_HEADERS + [build.__file__])
-    os.utime(str(lib), (newest + 10, newest + 10))
-    assert not build.needs_build()
-    monkeypatch.setattr(os.path, "getmtime", lambda p, real=os.path.getmtime: real(p) + (1e6 if p == header else 0))
-    assert build.needs_build()                                     # the header alone newer than the library
-
-
+# ------------------------------------------------------------------------------------------------ the core
 def test_the_core_does_not_know_the_header():
     csrc = os.path.join(ROOT, "physicl_amd", "csrc")
     for name in ("physicl_hip.hip", "pcl_device.h", "pcl_sincos.h"):

@@ -35,7 +35,7 @@ def main():
         build._generate_rtc_source()
         asm_path = os.path.join(tempfile.mkdtemp(), "aot.s")
         subprocess.check_call([build.HIPCC] + [f for f in build.FLAGS if f not in ("-shared", "-fPIC")] +
-                              ["--cuda-device-only", "-S", "-o", asm_path, build.SOURCES[0]], stderr=subprocess.DEVNULL)
+                              ["--cuda-device-only", "-S", "-o", asm_path, build.CORE["src"]], stderr=subprocess.DEVNULL)
     lines = open(asm_path).read().split("\n")
     starts = [(i, m.group(1)) for i, ln in enumerate(lines) for m in [re.match(r"(_Z\w+):", ln)] if m]
     meta = {}

@@ -10,7 +10,7 @@ cd $W && python3 - <<'PY'
 import importlib.util, os, subprocess
 spec = importlib.util.spec_from_file_location("b", "physicl_amd/build.py"); b = importlib.util.module_from_spec(spec); spec.loader.exec_module(b)
 b._generate_rtc_source()
-subprocess.check_call([b.HIPCC] + b.FLAGS + [b.SOURCES[0], "-o", "old.so", "-ldl"])
+subprocess.check_call([b.HIPCC] + b.FLAGS + [os.path.join(b.CSRC, "physicl_hip.hip"), "-o", "old.so", "-ldl"])
 PY
 cd - > /dev/null
 cp $W/old.so physicl_amd/_lib/libphysicl_hip_old.so

@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
-"""Is the device code of the add-on units (pcl_spectrum / pcl_source / pcl_shell / pcl_grid .hip) in two source trees the
-same code?  For a refactor of their host side or of pcl_sweep.h, in place of a speed measurement:
+"""Is the device code of the add-on units (physicl_amd/build.py: ADDONS) in two source trees the same code?
+For a refactor of their host side, of pcl_sweep.h or of the build, in place of a speed measurement:
 
     python tools/compare_unit_asm.py <old tree> <new tree> [--md]
 
 Each unit of each tree is compiled to gfx950 assembly with the library's own options (physicl_amd/build.py: FLAGS without
--shared / -fPIC, plus --cuda-device-only -S, as the tests' *_kernels_use_no_scratch do).  Per kernel the register and
+-shared / -fPIC, plus --cuda-device-only -S, as tests/test_build_cpu.py does).  Per kernel the register and
 segment metadata must be equal and the instruction lines must be the same multiset (the scheduler may swap neighbours when
 a helper moves into a header, so not the same sequence).  Exit status 1 if any kernel differs.
 """
@@ -22,7 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from physicl_amd import build  # noqa: E402
 
-UNITS = ["pcl_spectrum.hip", "pcl_source.hip", "pcl_shell.hip", "pcl_grid.hip"]
+UNITS = [os.path.basename(u["src"]) for u in build.ADDONS]
 META = ["vgpr_count", "sgpr_count", "group_segment_fixed_size", "private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count"]
 
 

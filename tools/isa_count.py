@@ -245,9 +245,9 @@ def aot_kernels(names, workdir):
     from physicl_amd import build
     build._generate_rtc_source()
     asm_path = os.path.join(workdir, "aot.s")
-    if not (os.path.exists(asm_path) and all(os.path.getmtime(asm_path) > os.path.getmtime(f) for f in build.SOURCES)):
+    if not (os.path.exists(asm_path) and all(os.path.getmtime(asm_path) > os.path.getmtime(f) for f in [build.CORE["src"]] + build.CORE["deps"])):
         subprocess.check_call([build.HIPCC] + [f for f in build.FLAGS if f not in ("-shared", "-fPIC")] +
-                              ["--cuda-device-only", "-S", "-o", asm_path, build.SOURCES[0]], stderr=subprocess.DEVNULL)
+                              ["--cuda-device-only", "-S", "-o", asm_path, build.CORE["src"]], stderr=subprocess.DEVNULL)
     asm = open(asm_path).read()
     labels = re.findall(r"^(_Z[\w$.]+):", asm, re.M)
     dem = subprocess.check_output(["c++filt"], input="\n".join(labels).encode()).decode().splitlines()
