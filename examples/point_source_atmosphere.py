@@ -3,7 +3,7 @@
 examples (n(r) = 2.5e25 m^-3 * exp(-(|r| - 6371 km) / 8.6 km)) with photons that do NOT start at the origin along +x:
 
     python examples/point_source_atmosphere.py [n_photons] [passes] [--cone | --beam-down | --default] [--profile] [--shells]
-                                               [--ground [ALBEDO]]
+                                               [--ground [ALBEDO]] [--phase rayleigh | hg:G | isotropic]
 
 default: a point source at (6371 km, 0, 0) emitting isotropically; ``--cone``: a 0.3 rad cone pointing up (+x) from a 1 km disc;
 ``--beam-down``: a 10 km gaussian beam entering from 100 km above the surface along -x; ``--default``: the same step list from
@@ -18,6 +18,10 @@ printed.  A flux needs every pass, so with ``--shells`` the run drops to one lau
 to 0.3, the rest is absorbed and stays on the ground at rest) instead of letting the photons through the planet; the reflected
 and absorbed totals are printed, and with ``--shells`` the run is made a second time without the ground and the outward counts
 through the top shell (100 km) of the two runs are printed side by side.
+``--phase rayleigh``, ``--phase hg:0.85`` or ``--phase isotropic`` puts a PhaseFunctionStep directly behind the scatter step: the
+photons it hits leave with an angle drawn from that phase function about the direction they came from (without it they leave
+with the reference's own angles, which do not depend on it).  One launch per light step, as with ``--shells``; the number of
+photons re-directed is printed.
 """
 import os
 import sys
@@ -36,6 +40,11 @@ if "--ground" in argv:
     albedo = 0.3
     if at + 1 < len(argv) and not argv[at + 1].startswith("--"):
         albedo = float(argv.pop(at + 1))
+phase = None
+if "--phase" in argv:
+    at = argv.index("--phase")
+    name, _, g_text = (argv.pop(at + 1) if at + 1 < len(argv) else "").partition(":")
+    phase = (name, float(g_text) if g_text else 0.0)
 args = [a for a in argv if not a.startswith("--")]
 n = int(float(args[0])) if len(args) > 0 else 100_000_000
 passes = int(args[1]) if len(args) > 1 else 200
@@ -60,6 +69,9 @@ def run(ground):
     sim.add_step(1, newton.NewtonianKinematicsStep())
     # (the reference hands the kernel A := n, n := A: with variable_n the user's n scales the expression -- a cross-section of 4e-30 m^2)
     sim.add_step(2, light.ScatterIsotropicStep(n=4e-30, A=1.0, variable_n=True, variable_n_fn=cl_n))
+    angles = light.PhaseFunctionStep(*phase) if phase is not None else None
+    if angles is not None:                                     # directly behind the scatter step (steps run in the order they were added)
+        sim.add_step("phase", angles)
     signs = light.ScatterSignMeasureStep(None, True)
     sim.add_step(3, signs)
     shells = light.ScatterMeasureStep(None, True, [[R + 20e3, np.nan, np.nan], [np.nan, 0.0, np.nan]])   # 20 km up; the plane y = 0
@@ -82,7 +94,7 @@ def run(ground):
     sim.join()
     if sim.error is not None:
         raise sim.error
-    return sim, signs, shells, profile, image, tally, floor
+    return sim, signs, shells, profile, image, tally, floor, angles
 
 
 bare_top = None
@@ -92,7 +104,7 @@ if albedo is not None and "--shells" in sys.argv:              # the same run wi
     print("without the ground: %d photons x %d steps in %.2f s" % (n, len(bare[0].ts), bare[0].run_time))
     bare[0].close(download=False)
     del bare
-sim, signs, shells, profile, image, tally, floor = run(albedo)
+sim, signs, shells, profile, image, tally, floor, angles = run(albedo)
 steps = len(sim.ts)
 print("source:", source)
 print("%d photons x %d steps in %.2f s  ->  %.3g particle-steps/s" % (n, steps, sim.run_time, n * steps / sim.run_time))
@@ -102,6 +114,8 @@ for row in signs.data[-3:]:
 for row in shells.data[-3:]:
     print("[t, N, crossed x = R + 20 km, crossed y = 0]:", [float(x) for x in row])
 print("scattered in the last step:", sim.hits)
+if angles is not None:
+    print("phase function %s (g = %g): %d photons re-directed over %d passes" % (angles.phase, angles.g, sum(int(row[1]) for row in angles.data), len(angles.data)))
 if profile is not None and profile.data:
     t, N, shells_now = profile.data[-1]
     print("altitude profile at t = %g s (%d records, one every 32 passes): %d of %d photons between 0 and 200 km" % (float(t), len(profile.data), shells_now.sum(), N))

@@ -673,6 +673,45 @@ int pcl_step_shell_crossings(pcl_ctx *ctx, int n_shells, const double *radii_hos
 int pcl_step_surface_reflect(pcl_ctx *ctx, double radius, const double *center_host, double albedo, int mode, double c,
                              uint64_t seed, uint32_t pass, int64_t *counts_out_host /* [2]: reflected, absorbed */);
 
+/* A phase function for the scatter step (PhaseFunctionStep).  Called directly behind the scatter step of a pass, it REPLACES the
+ * direction that step gave a scattered photon by one drawn from a phase function about the photon's direction BEFORE the
+ * scatter, in ONE sweep of the resident store.  pcl_step_scatter_isotropic keeps deciding who scatters; its own new direction
+ * (polar angle uniform about the x axis: not isotropic, and independent of where the photon came from) is overwritten.
+ * "Scattered in this pass" is read off the store: the scatter step leaves dv = v' - v_old on a hit and dv = 0 on a miss (not with
+ * PCL_SCATTER_PY_DV, where a hit leaves dv = v_old: do not call this behind such a step).  Nothing is removed; r, dr, E, ids and
+ * kinds are not touched and E is not even asked for.  All arithmetic is fp64, every operation rounded once, in the order written
+ * (x.y is (x0*y0 + x1*y1) + x2*y2); an fp32 store's values are widened first and what is written is rounded once to its dtype.
+ *   scattered  iff  the particle is a photon and (dv0 != 0 or dv1 != 0 or dv2 != 0)                     (NaN != 0 is true)
+ *   o = v - dv (the velocity before the scatter);  oo = o.o;  re-directed iff scattered and 0 < oo < inf  (else: not written,
+ *   not counted);  on = sqrt(oo);  w = o / on
+ *   block A: u_a = u53(w0, w1), u_b = u53(w2, w3);  mu, the cosine of the scattering angle:
+ *   PCL_PHASE_ISOTROPIC:  mu = 1 - 2*u_a                        (uniform on the sphere: the law of PCL_SRC_ISOTROPIC)
+ *   PCL_PHASE_HG:         Henyey-Greenstein, |g| < 1 its mean cosine;  g == 0: the isotropic line, bit for bit;  otherwise
+ *                         q = (1 - g*g) / ((1 - g) + (2*g)*u_a);  mu = min(max(((1 + g*g) - q*q) / (2*g), -1), 1)
+ *                         (for tiny |g| the numerator is a difference of the order g: mu is good to about ulp(1)/|g|; harmless)
+ *   PCL_PHASE_RAYLEIGH:   3/8 (1 + mu*mu) as the mixture of 3/4 uniform and 1/4 of the density 3/2 mu*mu:
+ *                         s4 = u_a*4;  j = floor(s4);  f = s4 - j (both exact);  gq = 2*f - 1;   j < 3: mu = gq;
+ *                         j == 3: block B: u_c = u53(w0, w1), u_d = u53(w2, w3);  mu = copysign(max(max(|gq|, u_c), u_d), gq)
+ *                         (the largest of three uniforms has the density 3 x*x; the sign of gq is independent of its size)
+ *   s = sqrt((1 - mu)*(1 + mu));  psi = (u_b*2)*pi;  sc = s*cos psi;  ss = s*sin psi;  the frame e1, e2 about w exactly as
+ *   pcl_step_surface_reflect builds it about nrm;  dir = (sc*e1 + ss*e2) + mu*w;  v = c*dir;  dv = v - o
+ * Add, subtract, multiply, divide, square root, min / max, copysign and floor only: everything but sin / cos (the scatter step's
+ * own) can be restated bit for bit.  Philox4x32-10 blocks, key (seed_lo, seed_hi), u53 of pcl_store_apply_source: block A has the
+ * counter (id_lo, id_hi, pass, 10), block B (id_lo, id_hi, pass, 11), drawn only by the lanes that need it; ``pass`` is the
+ * caller's own counter.  The words 10 and 11 are used by nothing else (pcl_step_surface_reflect: 8 and 9), so every other step
+ * draws what it drew, and a photon draws the same numbers however the run is sharded.  ``c`` = the speed of light in code units.
+ * count_out_host[0] = photons re-directed by this call.  A store that is not uniform costs the host traffic it costs
+ * pcl_step_surface_reflect.  PCL_ERR_ARG (NULL count, unknown phase, g not finite or |g| >= 1 with PCL_PHASE_HG -- g is ignored
+ * otherwise --, c not finite) is returned before anything is launched or written; PCL_ERR_STATE without a store; an empty store
+ * answers zero without a launch.  Host pointer; one device allocation per call, handed back on every way out; synchronises once,
+ * with the copy of the count.  pcl_last_error() is generic, as for pcl_step_surface_reflect, whose source file these two entry
+ * points share (physicl_amd/csrc/pcl_surface.hip).  PCL_PHASE_ISOTROPIC (0) is the define above pcl_step_mixed_multi: a loop's
+ * phase kind and a phase function share that name and value, and nothing else. */
+#define PCL_PHASE_HG 1
+#define PCL_PHASE_RAYLEIGH 2
+int pcl_step_phase_redirect(pcl_ctx *ctx, int phase, double g, double c, uint64_t seed, uint32_t pass,
+                            int64_t *count_out_host /* [1]: re-directed */);
+
 /* ---- Device groups: several GPUs from ONE process ---------------------------------------------------------------
  * The reference is a single process with one simulation thread (physicl/__init__.py:400-432, 501-524); this is how
  * a host written against this ABI uses a node's GPUs the same way, without one process per GPU.  A group owns one
@@ -737,6 +776,10 @@ int pcl_group_step_shell_crossings(pcl_group *group, int n_shells, const double 
  * are checked once for the group, before any shard is written */
 int pcl_group_step_surface_reflect(pcl_group *group, double radius, const double *center_host, double albedo, int mode, double c,
                                    uint64_t seed, uint32_t pass, int64_t *counts_out_host);
+/* pcl_step_phase_redirect on every shard (side by side), the count summed over the group's devices; the arguments are checked
+ * once for the group, before any shard is written */
+int pcl_group_step_phase_redirect(pcl_group *group, int phase, double g, double c, uint64_t seed, uint32_t pass,
+                                  int64_t *count_out_host);
 
 /* ---------------------------------------------------------------- the counters' collective (one process per GPU)
  * The path shards by global index with no data-path exchange; the only global quantities are the int64

@@ -28,6 +28,7 @@ GRID_COORDS = {"x": 0, "y": 1, "z": 2, "r": 3}                               # P
 GRID_MAX_AXES, GRID_MAX_BINS, GRID_MAX_CELLS = 3, 1024, 1 << 20
 SHELL_MAX_SHELLS, SHELL_MAX_BINS, SHELL_MAX_CELLS = 16, 1024, 8192              # PCL_SHELL_MAX_SHELLS ...
 SURFACE_MODES = {"lambertian": 0, "specular": 1}                             # PCL_SURFACE_LAMBERTIAN, PCL_SURFACE_SPECULAR
+PHASE_FUNCTIONS = {"isotropic": 0, "hg": 1, "rayleigh": 2}                   # PCL_PHASE_ISOTROPIC, PCL_PHASE_HG, PCL_PHASE_RAYLEIGH
 PROF_NEWTON, PROF_SCATTER, PROF_DELETE_MASK, PROF_COMPACT, PROF_COUNTERS, PROF_FUSED, PROF_MULTI, PROF_ONEPASS, \
     PROF_DELETE_AHEAD = range(9)
 PROF_NAMES = {PROF_NEWTON: "k_newton", PROF_SCATTER: "k_scatter", PROF_DELETE_MASK: "k_delete_mask",
@@ -150,6 +151,7 @@ _PROTOTYPES = {
     "pcl_step_position_grid": [_vp, c_int, _vp, _vp, _vp, _vp, _vp],
     "pcl_step_shell_crossings": [_vp, c_int, _vp, _vp, _vp, c_int, _vp, c_int, _vp, _vp, _vp],
     "pcl_step_surface_reflect": [_vp, c_double, _vp, c_double, c_int, c_double, c_uint64, c_uint32, _vp],
+    "pcl_step_phase_redirect": [_vp, c_int, c_double, c_double, c_uint64, c_uint32, _vp],
     # device groups: several GPUs from one process (the C-level counterpart of physicl_amd.multidev.MultiDevice)
     "pcl_group_create": [c_int, POINTER(c_int), POINTER(_vp)],
     "pcl_group_destroy": [_vp],
@@ -177,6 +179,7 @@ _PROTOTYPES = {
     "pcl_group_step_position_grid": [_vp, c_int, _vp, _vp, _vp, _vp, _vp],
     "pcl_group_step_shell_crossings": [_vp, c_int, _vp, _vp, _vp, c_int, _vp, c_int, _vp, _vp, _vp],
     "pcl_group_step_surface_reflect": [_vp, c_double, _vp, c_double, c_int, c_double, c_uint64, c_uint32, _vp],
+    "pcl_group_step_phase_redirect": [_vp, c_int, c_double, c_double, c_uint64, c_uint32, _vp],
 }
 EXPORTS = sorted(list(_PROTOTYPES) + ["pcl_last_error"])
 
@@ -340,6 +343,15 @@ def _surface(entry, handle, radius, center, albedo, mode, c, seed, n_pass):
     check(entry(handle, float(radius), None if ce is None else ce.ctypes.data, float(albedo), int(SURFACE_MODES.get(mode, mode)),
                 float(c), int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_pass) & 0xFFFFFFFF, counts.ctypes.data))
     return int(counts[0]), int(counts[1])
+
+
+def _phase(entry, handle, phase, g, c, seed, n_pass):
+    """One call of pcl_step_phase_redirect / pcl_group_step_phase_redirect: the photons re-directed by this call.  ``phase``:
+    "isotropic", "hg", "rayleigh" or the header's numbers; ``n_pass``: the caller's own pass counter (a Philox counter word)."""
+    count = np.zeros(1, dtype=np.int64)
+    check(entry(handle, int(PHASE_FUNCTIONS.get(phase, phase)), float(g), float(c), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                int(n_pass) & 0xFFFFFFFF, count.ctypes.data))
+    return int(count[0])
 
 
 class SourceStruct(ctypes.Structure):
@@ -921,6 +933,12 @@ class Device:
         speed ``c``, or -- with probability 1 - ``albedo`` -- left there at rest.  ``(reflected, absorbed)``.  SurfaceReflectStep."""
         return _surface(self.lib.pcl_step_surface_reflect, self.ctx, radius, center, albedo, mode, c, seed, n_pass)
 
+    def phase_redirect(self, phase, g=0.0, c=0.0, seed=0, n_pass=0):
+        """The photons the scatter step of this pass has hit (``dv != 0``) get a direction drawn from the phase function
+        ``phase`` ("isotropic", "hg" with the mean cosine ``g``, "rayleigh") about the direction they had before the scatter, with
+        speed ``c``, in one sweep (pcl_step_phase_redirect).  The number re-directed.  PhaseFunctionStep."""
+        return _phase(self.lib.pcl_step_phase_redirect, self.ctx, phase, g, c, seed, n_pass)
+
 
 class DeviceGroup:
     """``pcl_group_*``: several contexts in one process, sharded by global index, behind the C ABI (the shim owns the
@@ -1024,6 +1042,10 @@ class DeviceGroup:
     def surface_reflect(self, radius, center=None, albedo=1.0, mode="lambertian", c=0.0, seed=0, n_pass=0):
         """``Device.surface_reflect`` on every context of the group, the counts summed (pcl_group_step_surface_reflect)."""
         return _surface(self.lib.pcl_group_step_surface_reflect, self.g, radius, center, albedo, mode, c, seed, n_pass)
+
+    def phase_redirect(self, phase, g=0.0, c=0.0, seed=0, n_pass=0):
+        """``Device.phase_redirect`` on every context of the group, the counts summed (pcl_group_step_phase_redirect)."""
+        return _phase(self.lib.pcl_group_step_phase_redirect, self.g, phase, g, c, seed, n_pass)
 
     def download(self, field, n=None, offset=0, dtype=None):
         n = self.count - offset if n is None else n

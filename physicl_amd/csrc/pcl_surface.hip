@@ -1,4 +1,6 @@
-// pcl_surface.hip -- a reflecting sphere (SurfaceReflectStep): the ground of a radial problem.  Photons whose last move took
+// pcl_surface.hip -- the two sweeps that re-direct photons.
+//
+// A reflecting sphere (SurfaceReflectStep): the ground of a radial problem.  Photons whose last move took
 // them into the sphere are put back: reflected at the point where the move met the sphere (specular, or cosine-weighted about
 // the outward normal), or -- with an albedo below 1 -- absorbed there and left in the store at rest.  Nothing is removed.
 //
@@ -26,6 +28,30 @@
 //                e1 = (1 + (sn0*n0)*aa, sg*bb, -sn0);  e2 = (bb, sg + (n1*n1)*aa, -n1)        (Duff et al. 2017, branch-free)
 //                dir_k = (sc*e1_k + ss*e2_k) + mu*nrm_k
 //   reflected:   v_k = c*dir_k;  dv_k = v_k - v_old_k;  dr_k = w*dir_k;  r_k = center_k + (x_k + dr_k)
+//
+// A phase function (PhaseFunctionStep): the photons the scatter step of this pass has hit (dv != 0) get a direction drawn about
+// the direction they had BEFORE the scatter -- uniform on the sphere, Henyey-Greenstein or Rayleigh.  It joined this unit rather
+// than a new one: the unit already includes pcl_device.h for the draws and holds the frame that turns (mu, psi) about an axis into
+// a direction ("Adding a unit on the public ABI").  The frame is written out a second time below; k_surface_reflect
+// is the code it was.
+//
+//   k_phase_redirect<T>    one grid-stride sweep: per slot the three dv rows (24 B in fp64), widened to double; lanes with a
+//                          non-zero dv load v, and those whose old velocity o = v - dv has a length that can be worked with are
+//                          counted (one ballot + popcount per wave, one LDS cell) and go on: they load their id, draw, and write
+//                          v and dv.  r, dr and E are never looked at.
+//
+// Operation order (what light._phase_redirect restates with numpy):
+//   scattered iff a photon and (dv0 != 0 or dv1 != 0 or dv2 != 0);  o_k = v_k - dv_k;  oo = o.o;  go on iff 0 < oo < inf
+//   on = sqrt(oo);  w_k = o_k / on;  block A = counter (id_lo, id_hi, pass, 10): u_a, u_b
+//   isotropic:  mu = 1 - 2*u_a
+//   hg:         g == 0: the isotropic line;  q = (1 - g*g) / ((1 - g) + (2*g)*u_a);  mu = min(max(((1 + g*g) - q*q) / (2*g), -1), 1)
+//               (for tiny |g| the difference (1 + g*g) - q*q is of the order g: mu is good to about ulp(1)/|g| -- harmless, the law
+//               is flat to first order in g there)
+//   rayleigh:   3/8 (1 + mu^2) = 3/4 uniform + 1/4 (3/2 mu^2):  s4 = u_a*4;  j = floor(s4);  f = s4 - j (both exact);  gq = 2*f - 1
+//               j < 3: mu = gq;  j == 3: block B = counter (id_lo, id_hi, pass, 11): u_c, u_d;
+//               mu = copysign(max(max(|gq|, u_c), u_d), gq)      (the largest of three uniforms has density 3 x^2)
+//   s = sqrt((1 - mu)*(1 + mu));  psi = (u_b*2)*pi;  sc = s*cos psi;  ss = s*sin psi;  the frame e1, e2 about w as above about nrm
+//   dir_k = (sc*e1_k + ss*e2_k) + mu*w_k;  v_k = c*dir_k;  dv_k = v_k - o_k
 #include "pcl_sweep.h"
 
 #include "pcl_device.h" // (after the HIP runtime and the ABI's header, which pcl_sweep.h brings)
@@ -149,6 +175,89 @@ __global__ void __launch_bounds__(kBlock) k_surface_reflect(surface_args<T> a) {
     flush_cells(s_cnt, a.out, 2);
 }
 
+template <typename T>
+struct phase_args {
+    T *v[3], *dv[3];
+    const unsigned char *kind;   // NULL: every particle is a photon
+    const int64_t *ids;          // NULL: the id of slot i is id_base + i
+    unsigned long long *out;     // [1]: re-directed; device, zeroed by the entry point
+    int64_t N, ts, id_base;      // particles, tile stride of the slab (elements), id of slot 0
+    int tile_log;                // log2 of the tile length
+    int phase;
+    double g, speed;
+    uint32_t k0, k1, pass;       // Philox key (seed_lo, seed_hi), the step's own pass counter
+};
+
+template <typename T>
+__global__ void __launch_bounds__(kBlock) k_phase_redirect(phase_args<T> a) {
+    __shared__ uint32_t s_cnt[1];                                       // re-directed
+    if (threadIdx.x == 0) s_cnt[0] = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    // whole waves run the same number of trips (the ballot below needs every lane of the wave inside the loop)
+    const int64_t n_round = (a.N + 63) / 64 * 64;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n_round; i += stride) {
+        const bool in = i < a.N;
+        const int64_t ti = tile_index(i, a.tile_log, a.ts);
+        double d[3] = {0.0, 0.0, 0.0}, o[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            if (in) d[k] = (double)a.dv[k][ti];                         // fp32 widens exactly
+        // scattered in this pass: the scatter step left dv = v' - v_old on a hit, 0 on a miss (NaN != 0 is true)
+        bool go = in && (d[0] != 0.0 || d[1] != 0.0 || d[2] != 0.0);
+        if (go && a.kind) go = a.kind[i] != 0;
+        if (go) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) o[k] = __dsub_rn((double)a.v[k][ti], d[k]);      // the velocity before the scatter
+        }
+        const double oo = dot3(o, o);
+        go = go && oo > 0.0 && oo < INFINITY;                            // an old direction that can be worked with (NaN: false)
+        const uint32_t n_go = (uint32_t)__popcll(__ballot(go));
+        if (lane == 0 && n_go) atomicAdd(&s_cnt[0], n_go);
+        if (!go) continue;      // lanes that are left alone wait at the loop's head: no ballot below this line
+        const uint64_t id = (uint64_t)(a.ids ? a.ids[i] : a.id_base + i);
+        const double on = __dsqrt_rn(oo);
+        double w[3], dir[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) w[k] = __ddiv_rn(o[k], on);
+        const pcl_u32x4 wa = pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, 10u, a.k0, a.k1);
+        const double u_a = pcl_u53(wa.x, wa.y), u_b = pcl_u53(wa.z, wa.w);
+        double mu = __dsub_rn(1.0, __dmul_rn(2.0, u_a));                                             // uniform on the sphere
+        if (a.phase == PCL_PHASE_HG && a.g != 0.0) {
+            const double gg = __dmul_rn(a.g, a.g), g2 = __dmul_rn(2.0, a.g);
+            const double q = __ddiv_rn(__dsub_rn(1.0, gg), __dadd_rn(__dsub_rn(1.0, a.g), __dmul_rn(g2, u_a)));
+            mu = fmin(fmax(__ddiv_rn(__dsub_rn(__dadd_rn(1.0, gg), __dmul_rn(q, q)), g2), -1.0), 1.0);
+        } else if (a.phase == PCL_PHASE_RAYLEIGH) {
+            const double s4 = __dmul_rn(u_a, 4.0), j = floor(s4);
+            const double gq = __dsub_rn(__dmul_rn(2.0, __dsub_rn(s4, j)), 1.0);
+            mu = gq;
+            if (j == 3.0) {                                             // one lane in four: the 3/2 mu^2 part
+                const pcl_u32x4 wb = pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, 11u, a.k0, a.k1);
+                mu = copysign(fmax(fmax(fabs(gq), pcl_u53(wb.x, wb.y)), pcl_u53(wb.z, wb.w)), gq);
+            }
+        }
+        const double s = __dsqrt_rn(__dmul_rn(__dsub_rn(1.0, mu), __dadd_rn(1.0, mu)));
+        double sn, cs;
+        pcl_sincos_2pi(__dmul_rn(__dmul_rn(u_b, 2.0), PCL_PI), &sn, &cs);                            // the scatter step's angle
+        const double sc = __dmul_rn(s, cs), ss = __dmul_rn(s, sn);
+        const double sg = copysign(1.0, w[2]);                                                       // the frame of k_surface_reflect
+        const double aa = __ddiv_rn(-1.0, __dadd_rn(sg, w[2]));
+        const double bb = __dmul_rn(__dmul_rn(w[0], w[1]), aa), sw0 = __dmul_rn(sg, w[0]);
+        const double e1[3] = {__dadd_rn(1.0, __dmul_rn(__dmul_rn(sw0, w[0]), aa)), __dmul_rn(sg, bb), -sw0};
+        const double e2[3] = {bb, __dadd_rn(sg, __dmul_rn(__dmul_rn(w[1], w[1]), aa)), -w[1]};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            dir[k] = __dadd_rn(__dadd_rn(__dmul_rn(sc, e1[k]), __dmul_rn(ss, e2[k])), __dmul_rn(mu, w[k]));
+            const double vk = __dmul_rn(a.speed, dir[k]);
+            a.v[k][ti] = (T)vk;
+            a.dv[k][ti] = (T)__dsub_rn(vk, o[k]);
+        }
+    }
+    __syncthreads();
+    flush_cells(s_cnt, a.out, 1);
+}
+
 struct surface_spec { // a call's arguments, checked
     double c[3] = {0.0, 0.0, 0.0};
     double R2 = 0.0, albedo = 1.0, speed = 0.0;
@@ -241,6 +350,70 @@ int group_surface_reflect(pcl_group *group, double radius, const double *center_
     return PCL_OK;
 }
 
+// Everything PCL_ERR_ARG stands for except the NULL context (g is looked at for Henyey-Greenstein only)
+bool check_phase(int phase, double g, double c, const int64_t *count_out) {
+    if (!count_out || (phase != PCL_PHASE_ISOTROPIC && phase != PCL_PHASE_HG && phase != PCL_PHASE_RAYLEIGH)) return false;
+    if (phase == PCL_PHASE_HG && !(std::isfinite(g) && std::fabs(g) < 1.0)) return false;
+    return std::isfinite(c);
+}
+
+template <typename T>
+int launch_phase(pcl_ctx *ctx, const store_view &v, int phase, double g, double c, uint64_t seed, uint32_t pass, int64_t id_base,
+                 const int64_t *ids, const unsigned char *kind, unsigned long long *out_dev) {
+    phase_args<T> a{};
+    for (int k = 0; k < 3; ++k) {
+        void *vel = nullptr, *dv = nullptr;
+        PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_V0 + k, &vel));
+        PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_DV0 + k, &dv));     // (what makes a lazy dv real)
+        a.v[k] = static_cast<T *>(vel); a.dv[k] = static_cast<T *>(dv);
+    }
+    a.kind = kind; a.ids = ids; a.out = out_dev;
+    a.N = v.N; a.ts = v.ts; a.id_base = id_base; a.tile_log = v.tile_log; a.phase = phase;
+    a.g = g; a.speed = c;
+    a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32); a.pass = pass;
+    const int64_t grid = balanced_grid(v.N, v.n_cu, resident_per_cu(sizeof(uint32_t)));
+    hipLaunchKernelGGL(k_phase_redirect<T>, dim3((unsigned)grid), dim3(kBlock), 0, v.stream, a);
+    return hipGetLastError() == hipSuccess ? PCL_OK : PCL_ERR_HIP;
+}
+
+int phase_redirect(pcl_ctx *ctx, int phase, double g, double c, uint64_t seed, uint32_t pass, int64_t *count_out_host) {
+    if (!ctx || !check_phase(phase, g, c, count_out_host)) return bad_argument(ctx);
+    store_view v;                                                       // E is never asked for, as above
+    PCL_SWEEP_TRY(open_store(ctx, PCL_DV0, &v));
+    count_out_host[0] = 0;
+    if (v.N <= 0) return PCL_OK;
+    std::vector<uint8_t> kind_host;                                     // a store that is not uniform: as surface_reflect
+    std::vector<int64_t> ids_host;
+    bool mixed = false;
+    int64_t id_base = 0;
+    PCL_SWEEP_TRY(kind_bytes(ctx, v.N, kind_host, &mixed));
+    PCL_SWEEP_TRY(id_words(ctx, v.N, ids_host, &id_base));
+    const size_t out_bytes = sizeof(uint64_t), id_bytes = ids_host.size() * sizeof(int64_t);
+    dev_block blk(ctx);
+    PCL_SWEEP_TRY(stage(blk, v.stream, out_bytes, nullptr, 0, kind_host, ids_host));
+    char *base = static_cast<char *>(blk.p);
+    const int64_t *ids = id_bytes ? reinterpret_cast<const int64_t *>(base + out_bytes) : nullptr;
+    const unsigned char *kind = mixed ? reinterpret_cast<const unsigned char *>(base + out_bytes + id_bytes) : nullptr;
+    unsigned long long *out_dev = reinterpret_cast<unsigned long long *>(base);
+    PCL_SWEEP_TRY(v.dtype == PCL_DTYPE_F64 ? launch_phase<double>(ctx, v, phase, g, c, seed, pass, id_base, ids, kind, out_dev)
+                                           : launch_phase<float>(ctx, v, phase, g, c, seed, pass, id_base, ids, kind, out_dev));
+    return pcl_d2h(ctx, count_out_host, base, (int64_t)out_bytes);     // the call's one synchronisation
+}
+
+int group_phase_redirect(pcl_group *group, int phase, double g, double c, uint64_t seed, uint32_t pass, int64_t *count_out_host) {
+    std::vector<pcl_ctx *> ctx;
+    PCL_SWEEP_TRY(shards_of(group, ctx));
+    const int n = (int)ctx.size();
+    if (n < 1 || !check_phase(phase, g, c, count_out_host)) return bad_argument(n > 0 ? ctx[0] : nullptr);
+    std::vector<int64_t> part((size_t)n, 0);
+    PCL_SWEEP_TRY(for_each_shard(ctx, [&](int s, pcl_ctx *one) {
+        return pcl_step_phase_redirect(one, phase, g, c, seed, pass, &part[(size_t)s]);
+    }));
+    count_out_host[0] = 0;
+    for (int s = 0; s < n; ++s) count_out_host[0] += part[(size_t)s];
+    return PCL_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -253,6 +426,15 @@ int pcl_step_surface_reflect(pcl_ctx *ctx, double radius, const double *center_h
 int pcl_group_step_surface_reflect(pcl_group *group, double radius, const double *center_host, double albedo, int mode, double c,
                                    uint64_t seed, uint32_t pass, int64_t *counts_out_host) {
     return guarded([&] { return group_surface_reflect(group, radius, center_host, albedo, mode, c, seed, pass, counts_out_host); });
+}
+
+int pcl_step_phase_redirect(pcl_ctx *ctx, int phase, double g, double c, uint64_t seed, uint32_t pass, int64_t *count_out_host) {
+    return guarded([&] { return phase_redirect(ctx, phase, g, c, seed, pass, count_out_host); });
+}
+
+int pcl_group_step_phase_redirect(pcl_group *group, int phase, double g, double c, uint64_t seed, uint32_t pass,
+                                  int64_t *count_out_host) {
+    return guarded([&] { return group_phase_redirect(group, phase, g, c, seed, pass, count_out_host); });
 }
 
 } // extern "C"

@@ -866,6 +866,149 @@ class SurfaceReflectStep(DeviceStep, MeasureStep):
         return DeviceStep.run(self, sim)
 
 
+# ---------------------------------------------------------------------------------------------- phase functions
+def _check_phase(phase, g):
+    """(phase, g as a float) of a PhaseFunctionStep, or ValueError for everything pcl_step_phase_redirect would refuse
+    (``g`` is checked for every phase here: a step is built once, and a bad number is a mistake whatever the phase)."""
+    from ._hip import PHASE_FUNCTIONS
+    if not isinstance(phase, str) or phase not in PHASE_FUNCTIONS:
+        raise ValueError("phase must be one of %s, got %r" % (", ".join(repr(k) for k in PHASE_FUNCTIONS), phase))
+    try:
+        g = float(np.asarray(g, dtype=np.float64).reshape(()))
+    except (TypeError, ValueError):
+        raise ValueError("g must be a number") from None
+    if not (np.isfinite(g) and abs(g) < 1.0):
+        raise ValueError("g must be finite with |g| < 1, got %r" % (g,))
+    return phase, g
+
+
+def _phase_redirect(v, dv, photon, ids, phase, g, c, seed, n_pass, dtype=np.float64):
+    """What pcl_step_phase_redirect makes of (n, 3) float64 velocities and last velocity changes, who is a photon and the
+    particles' ids, with numpy -- every operation the device's operation in the device's order, one rounding each
+    (include/physicl_hip.h), and what is written rounded once to ``dtype``.  Everything but sin / cos of the azimuth (libm here,
+    the library's own on the device) is the device's bit for bit.  A dict: ``v, dv`` the new state (float64 arrays; rows that are
+    not re-directed are the arguments'), ``scattered`` (a photon with a non-zero dv) and ``redirected`` (those of them whose old
+    velocity has a length that can be worked with) boolean masks, and of the re-directed rows (NaN elsewhere) ``mu``, the cosine
+    of the scattering angle, and ``w``, the unit vector of the old direction."""
+    v, dv = (np.array(a, dtype=np.float64).reshape(-1, 3) for a in (v, dv))
+    n = len(v)
+    phase, g = _check_phase(phase, g)
+    c, g = np.float64(c), np.float64(g)
+    with np.errstate(invalid="ignore", over="ignore"):
+        scattered = ((dv[:, 0] != 0) | (dv[:, 1] != 0) | (dv[:, 2] != 0)) & np.asarray(photon, dtype=bool).reshape(-1)
+        o_all = v - dv
+        oo = _dot3(o_all, o_all)
+        go = scattered & (oo > 0) & (oo < np.inf)
+    at = np.flatnonzero(go)
+    ids = np.asarray(ids).reshape(-1)[at]
+    out = {"scattered": scattered, "redirected": go, "mu": np.full(n, np.nan), "w": np.full((n, 3), np.nan)}
+    o = o_all[at]
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        w = o / np.sqrt(oo[at])[:, None]
+        u_a, u_b = _philox_block(ids, seed, n_pass, 10)
+        mu = 1.0 - 2.0 * u_a                               # uniform on the sphere
+        if phase == "hg" and g != 0.0:
+            gg, g2 = g * g, 2.0 * g
+            q = (1.0 - gg) / ((1.0 - g) + g2 * u_a)
+            mu = np.fmin(np.fmax(((1.0 + gg) - q * q) / g2, -1.0), 1.0)
+        elif phase == "rayleigh":
+            s4 = u_a * 4.0
+            j = np.floor(s4)
+            gq = 2.0 * (s4 - j) - 1.0
+            mu = gq.copy()
+            part = j == 3.0                                # one in four: the 3/2 mu^2 part of 3/8 (1 + mu^2)
+            u_c, u_d = _philox_block(ids[part], seed, n_pass, 11)
+            mu[part] = np.copysign(np.fmax(np.fmax(np.abs(gq[part]), u_c), u_d), gq[part])
+        sn = np.sqrt((1.0 - mu) * (1.0 + mu))
+        psi = (u_b * 2.0) * np.pi
+        sc, ss = sn * np.cos(psi), sn * np.sin(psi)
+        w0, w1, w2 = w[:, 0], w[:, 1], w[:, 2]
+        sg = np.copysign(1.0, w2)                          # the frame of _surface_bounce, about w
+        aa = -1.0 / (sg + w2)
+        bb, sw0 = (w0 * w1) * aa, sg * w0
+        e1 = np.stack([1.0 + (sw0 * w0) * aa, sg * bb, -sw0], axis=1)
+        e2 = np.stack([bb, sg + (w1 * w1) * aa, -w1], axis=1)
+        direction = (sc[:, None] * e1 + ss[:, None] * e2) + mu[:, None] * w
+        v_new = c * direction
+        dv_new = v_new - o
+    v[at], dv[at] = v_new.astype(dtype).astype(np.float64), dv_new.astype(dtype).astype(np.float64)
+    out["v"], out["dv"] = v, dv
+    out["mu"][at], out["w"][at] = mu, w
+    return out
+
+
+class PhaseFunctionStep(DeviceStep, MeasureStep):
+    """The scattering angle of a pass (not in the reference).  ``ScatterIsotropicStep`` decides who scatters and gives a hit
+    photon a direction whose polar angle is uniform about the x axis -- which bunches directions at the poles of x and does not
+    depend on where the photon came from.  This step, placed directly BEHIND the scatter step (measures may stand between),
+    replaces that direction by one drawn from a phase function about the photon's direction BEFORE the scatter:
+
+    * ``phase="isotropic"``: uniform on the sphere, ``mu = 1 - 2u`` -- what "isotropic" means (the law of
+      ``PhotonSource(angular="isotropic")``); ``ScatterIsotropicStep``'s own angles are not;
+    * ``phase="hg"``: Henyey-Greenstein with the mean cosine ``g``, ``|g| < 1`` (aerosols and clouds: about 0.85); ``g = 0`` is
+      the isotropic law bit for bit;
+    * ``phase="rayleigh"``: ``3/8 (1 + mu^2)``, a molecular atmosphere.
+
+    "Scattered in this pass" is read off the store: the scatter step leaves ``dv = v' - v_old`` on a hit and ``dv = 0`` on a miss,
+    so ``v - dv`` is the old velocity.  A photon whose old velocity is zero or not finite is left alone (and not counted); plain
+    ``Object``s are never touched.  After each run ``self.redirected`` holds the pass's count (global over shards and ranks) --
+    the scatter step's hit count -- and ``self.data`` gains the row ``[t, redirected]``; ``out_fn`` takes the rows at the end.
+    The arithmetic is written out in include/physicl_hip.h (pcl_step_phase_redirect); ``_phase_redirect`` restates it with numpy.
+
+    The draws are Philox blocks keyed by ``sim.seed``, the photon's id and a pass counter of the step's own, in counter words no
+    other kernel uses: the scatter step draws what it draws without this step, and a photon draws the same numbers however the
+    run is sharded.  They are made on the device with every ``rng=`` setting.  Under the reference's Python semantics
+    (``cl_on=False``) a hit leaves ``dv = v_old``, the rule above does not hold, and the step raises ``ValueError``.
+
+    One launch per light step: the K-passes-per-launch kernels cannot re-direct a photon between two of their passes, and
+    ``sim.launch_note`` says so.  On host-resident objects (``step.run(sim)`` outside a device loop) the same state is made with
+    numpy, the ids being the places in the object list."""
+    _fuse_role = None
+    _NOTE = "one launch per light step: a PhaseFunctionStep re-directs the scattered photons behind every pass, which the " \
+            "K-passes-per-launch kernels cannot carry"
+
+    def __init__(self, phase="hg", g=0.0, out_fn=None):
+        MeasureStep.__init__(self, out_fn)
+        self.phase, self.g = _check_phase(phase, g)
+        self.redirected = 0
+        self._pass = 0                                   # the step's own Philox counter word: one per run
+
+    def _record_pass(self, sim, redirected):
+        self.redirected = int(redirected)
+        self.data.append(tally.object_row([tally._snap(sim.t), self.redirected]))
+
+    @staticmethod
+    def _refuse_py_semantics(sim):
+        if getattr(sim, "_py_semantics", None) is not None and sim._py_semantics():
+            raise ValueError("PhaseFunctionStep needs cl_on=True: under the reference's Python semantics a scattered photon is left "
+                             "with dv = v_old, not v' - v_old, so its direction before the scatter cannot be read off the store")
+
+    def _device_run(self, sim):
+        self._refuse_py_semantics(sim)
+        if getattr(sim, "launch_note", self._NOTE) is None and sim._k_wanted() > 1:      # (a device run only: the host path says nothing)
+            sim.launch_note = self._NOTE
+        self._pass += 1
+        count = sim._dev.phase_redirect(self.phase, self.g, _c_h_literals()[0], sim.seed, self._pass)
+        sim._scattered = True                            # velocities were replaced on the device
+        self._record_pass(sim, sim._global([count])[0])  # (every rank issues it, also with an empty shard)
+
+    def run(self, sim):
+        self._refuse_py_semantics(sim)
+        if getattr(sim, "_residency", None) == "host" and getattr(sim, "_batch", None) is None \
+                and (sim.comm is None or sim.comm.world == 1):
+            objs = list(sim.objects)
+            self._pass += 1
+            photon = np.array([type(o) is PhotonObject for o in objs], dtype=bool)
+            new = _phase_redirect(tally.vec3(objs, "v"), tally.vec3(objs, "dv"), photon, np.arange(len(objs)), self.phase, self.g,
+                                  _c_h_literals()[0], getattr(sim, "seed", 0), self._pass)
+            for k in np.flatnonzero(new["redirected"]).tolist():
+                o = objs[k]
+                o.v, o.dv = np.array(new["v"][k], dtype=np.double), np.array(new["dv"][k], dtype=np.double)   # plain arrays, as a scatter leaves them
+            self._record_pass(sim, new["redirected"].sum())
+            return None
+        return DeviceStep.run(self, sim)
+
+
 def _DEFAULT_ID_INFO(x):
     """The reference's default ``lambda x: str(type(x))`` (light.py:438), recognised by identity.  The label goes into the trace
     table's first column: this package's own classes read as the reference's (``<class 'physicl.light.PhotonObject'>``, what a

@@ -279,6 +279,9 @@ class MultiDevice:
         outs = self._each(lambda s: s.surface_reflect(*a, **kw))
         return sum(o[0] for o in outs), sum(o[1] for o in outs)
 
+    def phase_redirect(self, *a, **kw):
+        return sum(self._each(lambda s: s.phase_redirect(*a, **kw)))
+
     def plane_energies(self, plane, n_hint=None):
         return self._concat(self._each(lambda s: s.plane_energies(plane)))      # (a shard does not know its share of the hint)
 
