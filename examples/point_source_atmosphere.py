@@ -3,7 +3,7 @@
 examples (n(r) = 2.5e25 m^-3 * exp(-(|r| - 6371 km) / 8.6 km)) with photons that do NOT start at the origin along +x:
 
     python examples/point_source_atmosphere.py [n_photons] [passes] [--cone | --beam-down | --default] [--profile] [--shells]
-                                               [--ground [ALBEDO]] [--phase rayleigh | hg:G | isotropic]
+                                               [--ground [ALBEDO]] [--phase rayleigh | hg:G | isotropic] [--omega0 W | W1,W2,...]
 
 default: a point source at (6371 km, 0, 0) emitting isotropically; ``--cone``: a 0.3 rad cone pointing up (+x) from a 1 km disc;
 ``--beam-down``: a 10 km gaussian beam entering from 100 km above the surface along -x; ``--default``: the same step list from
@@ -22,6 +22,11 @@ through the top shell (100 km) of the two runs are printed side by side.
 photons it hits leave with an angle drawn from that phase function about the direction they came from (without it they leave
 with the reference's own angles, which do not depend on it).  One launch per light step, as with ``--shells``; the number of
 photons re-directed is printed.
+``--omega0 W`` makes the medium absorb: an AbsorptionStep behind the scatter step (and before the phase function) absorbs each
+interacting photon with probability 1 - W and leaves it at rest where it was absorbed.  ``--omega0 W1,W2,...`` gives one
+single-scattering albedo per altitude shell: the three shells between the ``--shells`` radii (ground, 10, 50, 100 km) with
+three values, the forty 5 km shells of ``--profile`` with forty.  One launch per light step; the photons absorbed per layer are
+printed beside the top-of-atmosphere and ground counts.
 """
 import os
 import sys
@@ -45,6 +50,10 @@ if "--phase" in argv:
     at = argv.index("--phase")
     name, _, g_text = (argv.pop(at + 1) if at + 1 < len(argv) else "").partition(":")
     phase = (name, float(g_text) if g_text else 0.0)
+omega0 = None
+if "--omega0" in argv:
+    at = argv.index("--omega0")
+    omega0 = [float(x) for x in (argv.pop(at + 1) if at + 1 < len(argv) else "").split(",")]
 args = [a for a in argv if not a.startswith("--")]
 n = int(float(args[0])) if len(args) > 0 else 100_000_000
 passes = int(args[1]) if len(args) > 1 else 200
@@ -59,7 +68,14 @@ else:
     source = light.PhotonSource(origin=(R, 0, 0), angular="isotropic")
 cl_n = "2.5E+25 * exp(-1 * (sqrt(pow(r0[gid], 2) + pow(r1[gid], 2) + pow(r2[gid], 2)) - 6371000.0)/(8600.0))"
 dt = 1e-5                                                      # 3 km per pass
-
+SHELL_RADII = R + np.array([0.0, 10e3, 50e3, 100e3])
+PROFILE_RADII = R + np.linspace(0.0, 200e3, 41)
+layer_edges = None
+if omega0 is not None and len(omega0) > 1:                     # one value per altitude shell of --shells / --profile
+    fits = [e for flag, e in (("--shells", SHELL_RADII), ("--profile", PROFILE_RADII)) if flag in sys.argv and len(e) - 1 == len(omega0)]
+    if not fits:
+        sys.exit("--omega0 with %d values needs --shells (3 values: ground, 10, 50, 100 km) or --profile (40 values: 5 km shells)" % len(omega0))
+    layer_edges = fits[0]
 
 
 def run(ground):
@@ -69,6 +85,10 @@ def run(ground):
     sim.add_step(1, newton.NewtonianKinematicsStep())
     # (the reference hands the kernel A := n, n := A: with variable_n the user's n scales the expression -- a cross-section of 4e-30 m^2)
     sim.add_step(2, light.ScatterIsotropicStep(n=4e-30, A=1.0, variable_n=True, variable_n_fn=cl_n))
+    medium = None
+    if omega0 is not None:                                     # behind the scatter step, before the phase function
+        medium = light.AbsorptionStep(omega0[0] if layer_edges is None else omega0, edges=layer_edges)
+        sim.add_step("absorb", medium)
     angles = light.PhaseFunctionStep(*phase) if phase is not None else None
     if angles is not None:                                     # directly behind the scatter step (steps run in the order they were added)
         sim.add_step("phase", angles)
@@ -78,12 +98,12 @@ def run(ground):
     sim.add_step(4, shells)
     profile = image = tally = floor = None
     if "--profile" in sys.argv:                                # behind the last light step: the 32-pass launches are kept
-        profile = light.PositionGridMeasureStep(None, ("r",), [R + np.linspace(0.0, 200e3, 41)], every=32)
+        profile = light.PositionGridMeasureStep(None, ("r",), [PROFILE_RADII], every=32)
         image = light.PositionGridMeasureStep(None, ("y", "z"), [np.linspace(-300e3, 300e3, 129)] * 2, every=32, measure_n=False)
         sim.add_step(5, profile)
         sim.add_step(6, image)
     if "--shells" in sys.argv:                                 # the ground and three altitudes, about the Earth's centre
-        tally = light.ShellCrossingMeasureStep(None, R + np.array([0.0, 10e3, 50e3, 100e3]), mu_bins=np.linspace(-1.0, 1.0, 11))
+        tally = light.ShellCrossingMeasureStep(None, SHELL_RADII, mu_bins=np.linspace(-1.0, 1.0, 11))
         sim.add_step(7, tally)
     if ground is not None:                                     # last in the pass: the tally before it sees the incoming move
         floor = light.SurfaceReflectStep(R, albedo=ground)
@@ -94,7 +114,7 @@ def run(ground):
     sim.join()
     if sim.error is not None:
         raise sim.error
-    return sim, signs, shells, profile, image, tally, floor, angles
+    return sim, signs, shells, profile, image, tally, floor, angles, medium
 
 
 bare_top = None
@@ -104,7 +124,7 @@ if albedo is not None and "--shells" in sys.argv:              # the same run wi
     print("without the ground: %d photons x %d steps in %.2f s" % (n, len(bare[0].ts), bare[0].run_time))
     bare[0].close(download=False)
     del bare
-sim, signs, shells, profile, image, tally, floor, angles = run(albedo)
+sim, signs, shells, profile, image, tally, floor, angles, medium = run(albedo)
 steps = len(sim.ts)
 print("source:", source)
 print("%d photons x %d steps in %.2f s  ->  %.3g particle-steps/s" % (n, steps, sim.run_time, n * steps / sim.run_time))
@@ -133,3 +153,15 @@ if floor is not None:
     print("the ground (albedo %g, lambertian): %d reflected, %d absorbed over %d passes" % (albedo, sum(int(row[1]) for row in floor.data), sum(int(row[2]) for row in floor.data), len(floor.data)))
     if tally is not None:
         print("outward through the top of the atmosphere (100 km): %d with the ground, %d without" % (int(sum(row[2][3] for row in tally.data)), bare_top))
+if medium is not None:
+    by_layer = np.sum([row[3] for row in medium.data], axis=0)
+    print("the medium (omega0 %s): %d interactions, %d absorbed over %d passes" % (
+        ",".join("%g" % w for w in omega0), sum(int(row[1]) for row in medium.data), sum(int(row[2]) for row in medium.data), len(medium.data)))
+    if layer_edges is None:
+        print("  absorbed anywhere: %d" % by_layer[0])
+    else:
+        for b in range(len(by_layer)):
+            print("  %5.1f - %5.1f km: %d absorbed" % ((layer_edges[b] - R) / 1e3, (layer_edges[b + 1] - R) / 1e3, by_layer[b]))
+    if tally is not None:
+        print("  beside it: %d left through the top of the atmosphere (100 km)%s" % (
+            int(sum(row[2][3] for row in tally.data)), "" if floor is None else ", %d absorbed by the ground" % sum(int(row[2]) for row in floor.data)))

@@ -712,6 +712,53 @@ int pcl_step_surface_reflect(pcl_ctx *ctx, double radius, const double *center_h
 int pcl_step_phase_redirect(pcl_ctx *ctx, int phase, double g, double c, uint64_t seed, uint32_t pass,
                             int64_t *count_out_host /* [1]: re-directed */);
 
+/* An absorbing medium (AbsorptionStep): the single-scattering albedo, by layer.  Called anywhere behind the scatter step of a pass
+ * and before the next Newton step (before or behind pcl_step_phase_redirect), it lets each photon that step made interact be
+ * ABSORBED instead, with probability 1 - omega0 of the layer it stands in, in ONE sweep of the resident store.  Analog: an absorbed
+ * photon is left in the store at rest where it is; E is no statistical weight and is never scaled (the wavelength-dependent scatter
+ * step reads it as the photon's colour).  Nothing is removed; r, dr, E, ids and kinds are not written, and E is asked for only
+ * with energy bins.  "Interacted in this pass" is read off the store by pcl_step_phase_redirect's rule (not behind a
+ * PCL_SCATTER_PY_DV step).  All arithmetic is fp64, every operation rounded once, in the order written; an fp32 store's values are
+ * widened first (exact); what is written is zero.
+ *   interacted  iff  the particle is a photon and (dv0 != 0 or dv1 != 0 or dv2 != 0)                    (NaN != 0 is true)
+ *   n_layers == 0:  b = 0 for everybody: omega0_host[0] holds everywhere; edges_host and center_host are ignored
+ *   n_layers = L >= 1:  d = r - center;  q = (d0*d0 + d1*d1) + d2*d2;  e2_k = e_k*e_k (made on the host);
+ *                   inside iff e2_0 <= q and q <= e2_L (NaN: not inside);  b = the layer with e2_b <= q < e2_(b+1), the last one
+ *                   closed (numpy.histogram); no square root is taken.  A photon that is not inside is counted as interacting and
+ *                   left alone.
+ *   inside and omega0_host[b] < 1:  u = u53(w0, w1) of the block below;  absorbed iff not (u < omega0_host[b])
+ *                   (omega0 0: every interacting photon inside is absorbed; omega0 1: nothing is drawn)
+ *   absorbed:       v = 0;  dv = 0
+ * dv = 0 and not pcl_step_surface_reflect's dv = 0 - v_old: that call ends a pass, this one stands in the middle of one, and a
+ * pcl_step_phase_redirect or a second call of this entry point later in the pass must see a photon that did not scatter and leave
+ * it at rest (with dv = -v_old the phase function would give it the speed c again).  From then on the photon is what the ground
+ * leaves behind: pcl_step_newton does not move it, the scatter steps hit it on a draw of exactly 0 only.
+ * Compare, subtract, multiply and add only: everything can be restated bit for bit.  The draw is the Philox4x32-10 block with the
+ * key (seed_lo, seed_hi) and the counter (id_lo, id_hi, pass, 12), u53 of pcl_store_apply_source; ``pass`` is the caller's own
+ * counter.  The word 12 is used by nothing else (scatter kernels 0 and 1, fill and source 2..5, pcl_step_surface_reflect 8 and 9,
+ * pcl_step_phase_redirect 10 and 11), so every other step draws what it drew, and a photon draws the same number however the run is
+ * sharded.
+ * omega0_host: L' = max(L, 1) doubles in [0, 1].  edges_host: L + 1 finite, non-negative, strictly increasing radii about
+ * center_host (3 finite doubles, NULL = the origin) whose squares are finite and strictly increasing, 1 <= L <=
+ * PCL_ABSORB_MAX_LAYERS.  E_edges_host: n_E_bins + 1 finite, strictly increasing doubles, 1 <= n_E_bins <= PCL_ABSORB_MAX_BINS, or
+ * n_E_bins == 0 and no histogram.  2 + L' + L' * n_E_bins may not exceed PCL_ABSORB_MAX_CELLS: a workgroup's uint32 cells (48 KiB)
+ * and the three tables stay below 64 KiB of LDS.
+ * counts_out_host[0] = photons that interacted, [1] = absorbed, [2 + b] = absorbed in layer b, by this call;
+ * E_hist_out_host[b * n_E_bins + k] = absorbed in layer b with E in bin k ([e_k, e_(k+1)), the last bin closed; NaN and energies
+ * outside the edges in no bin).
+ * A store that is not uniform costs the host traffic it costs pcl_step_surface_reflect; the ids go along only if some omega0 < 1.
+ * PCL_ERR_ARG (NULL omega0 or counts, L outside 0 .. PCL_ABSORB_MAX_LAYERS, an omega0 outside [0, 1] or NaN, bad edges or centre,
+ * bad n_E_bins or E edges, NULL histogram with bins, too many cells) is returned before anything is launched or written;
+ * PCL_ERR_STATE without a store; an empty store answers zeros without a launch.  Host pointers; one device allocation per call,
+ * handed back on every way out; synchronises once, with the copy of the tallies.  pcl_last_error() is generic, as for
+ * pcl_step_surface_reflect, whose source file these two entry points share (physicl_amd/csrc/pcl_surface.hip). */
+#define PCL_ABSORB_MAX_LAYERS 64
+#define PCL_ABSORB_MAX_BINS 1024   /* per layer */
+#define PCL_ABSORB_MAX_CELLS 12288 /* 2 + L' + L' * n_E_bins */
+int pcl_step_absorb_scattered(pcl_ctx *ctx, int n_layers, const double *omega0_host, const double *edges_host,
+                              const double *center_host, int n_E_bins, const double *E_edges_host, uint64_t seed, uint32_t pass,
+                              int64_t *counts_out_host /* [2 + L'] */, int64_t *E_hist_out_host /* [L' * n_E_bins] or NULL */);
+
 /* ---- Device groups: several GPUs from ONE process ---------------------------------------------------------------
  * The reference is a single process with one simulation thread (physicl/__init__.py:400-432, 501-524); this is how
  * a host written against this ABI uses a node's GPUs the same way, without one process per GPU.  A group owns one
@@ -780,6 +827,11 @@ int pcl_group_step_surface_reflect(pcl_group *group, double radius, const double
  * once for the group, before any shard is written */
 int pcl_group_step_phase_redirect(pcl_group *group, int phase, double g, double c, uint64_t seed, uint32_t pass,
                                   int64_t *count_out_host);
+/* pcl_step_absorb_scattered on every shard (side by side), the tallies summed over the group's devices; the arguments are checked
+ * once for the group, before any shard is written */
+int pcl_group_step_absorb_scattered(pcl_group *group, int n_layers, const double *omega0_host, const double *edges_host,
+                                    const double *center_host, int n_E_bins, const double *E_edges_host, uint64_t seed, uint32_t pass,
+                                    int64_t *counts_out_host, int64_t *E_hist_out_host);
 
 /* ---------------------------------------------------------------- the counters' collective (one process per GPU)
  * The path shards by global index with no data-path exchange; the only global quantities are the int64

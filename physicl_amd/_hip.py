@@ -28,6 +28,7 @@ GRID_COORDS = {"x": 0, "y": 1, "z": 2, "r": 3}                               # P
 GRID_MAX_AXES, GRID_MAX_BINS, GRID_MAX_CELLS = 3, 1024, 1 << 20
 SHELL_MAX_SHELLS, SHELL_MAX_BINS, SHELL_MAX_CELLS = 16, 1024, 8192              # PCL_SHELL_MAX_SHELLS ...
 SURFACE_MODES = {"lambertian": 0, "specular": 1}                             # PCL_SURFACE_LAMBERTIAN, PCL_SURFACE_SPECULAR
+ABSORB_MAX_LAYERS, ABSORB_MAX_BINS, ABSORB_MAX_CELLS = 64, 1024, 12288           # PCL_ABSORB_MAX_LAYERS ...
 PHASE_FUNCTIONS = {"isotropic": 0, "hg": 1, "rayleigh": 2}                   # PCL_PHASE_ISOTROPIC, PCL_PHASE_HG, PCL_PHASE_RAYLEIGH
 PROF_NEWTON, PROF_SCATTER, PROF_DELETE_MASK, PROF_COMPACT, PROF_COUNTERS, PROF_FUSED, PROF_MULTI, PROF_ONEPASS, \
     PROF_DELETE_AHEAD = range(9)
@@ -152,6 +153,7 @@ _PROTOTYPES = {
     "pcl_step_shell_crossings": [_vp, c_int, _vp, _vp, _vp, c_int, _vp, c_int, _vp, _vp, _vp],
     "pcl_step_surface_reflect": [_vp, c_double, _vp, c_double, c_int, c_double, c_uint64, c_uint32, _vp],
     "pcl_step_phase_redirect": [_vp, c_int, c_double, c_double, c_uint64, c_uint32, _vp],
+    "pcl_step_absorb_scattered": [_vp, c_int, _vp, _vp, _vp, c_int, _vp, c_uint64, c_uint32, _vp, _vp],
     # device groups: several GPUs from one process (the C-level counterpart of physicl_amd.multidev.MultiDevice)
     "pcl_group_create": [c_int, POINTER(c_int), POINTER(_vp)],
     "pcl_group_destroy": [_vp],
@@ -180,6 +182,7 @@ _PROTOTYPES = {
     "pcl_group_step_shell_crossings": [_vp, c_int, _vp, _vp, _vp, c_int, _vp, c_int, _vp, _vp, _vp],
     "pcl_group_step_surface_reflect": [_vp, c_double, _vp, c_double, c_int, c_double, c_uint64, c_uint32, _vp],
     "pcl_group_step_phase_redirect": [_vp, c_int, c_double, c_double, c_uint64, c_uint32, _vp],
+    "pcl_group_step_absorb_scattered": [_vp, c_int, _vp, _vp, _vp, c_int, _vp, c_uint64, c_uint32, _vp, _vp],
 }
 EXPORTS = sorted(list(_PROTOTYPES) + ["pcl_last_error"])
 
@@ -352,6 +355,27 @@ def _phase(entry, handle, phase, g, c, seed, n_pass):
     check(entry(handle, int(PHASE_FUNCTIONS.get(phase, phase)), float(g), float(c), int(seed) & 0xFFFFFFFFFFFFFFFF,
                 int(n_pass) & 0xFFFFFFFF, count.ctypes.data))
     return int(count[0])
+
+
+def _absorb(entry, handle, omega0, edges, center, E_edges, seed, n_pass):
+    """One call of pcl_step_absorb_scattered / pcl_group_step_absorb_scattered: (interacted, absorbed, absorbed_by_layer int64[L'],
+    E_hist int64[L', B_E] or None).  ``omega0``: one number with ``edges=None``, else one per layer; the edges go over as given
+    (the library squares them); ``n_pass``: the caller's own pass counter (a Philox counter word)."""
+    om = np.ascontiguousarray(omega0, dtype=np.float64).reshape(-1)
+    ed = None if edges is None else np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+    L = 0 if ed is None else len(ed) - 1
+    rows = max(L, 1)
+    if len(om) != rows:
+        raise ValueError("omega0 holds %d values for %d layers" % (len(om), rows))
+    ce = None if center is None else np.ascontiguousarray(center, dtype=np.float64).reshape(3)
+    Ee = None if E_edges is None else np.ascontiguousarray(E_edges, dtype=np.float64).reshape(-1)
+    nE = 0 if Ee is None else len(Ee) - 1
+    counts = np.zeros(2 + rows, dtype=np.int64)
+    hist = None if Ee is None else np.zeros((rows, max(nE, 0)), dtype=np.int64)
+    ptr = lambda a: None if a is None else a.ctypes.data                                                       # noqa: E731
+    check(entry(handle, L, om.ctypes.data, ptr(ed), ptr(ce), nE, ptr(Ee), int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_pass) & 0xFFFFFFFF,
+                counts.ctypes.data, ptr(hist)))
+    return int(counts[0]), int(counts[1]), counts[2:].copy(), hist
 
 
 class SourceStruct(ctypes.Structure):
@@ -939,6 +963,12 @@ class Device:
         speed ``c``, in one sweep (pcl_step_phase_redirect).  The number re-directed.  PhaseFunctionStep."""
         return _phase(self.lib.pcl_step_phase_redirect, self.ctx, phase, g, c, seed, n_pass)
 
+    def absorb_scattered(self, omega0, edges=None, center=None, E_edges=None, seed=0, n_pass=0):
+        """Absorb, with probability ``1 - omega0`` of the layer it stands in, each photon the scatter step of this pass has hit
+        (dv != 0): it is left at rest where it is (v = 0, dv = 0), in one sweep (pcl_step_absorb_scattered).  ``(interacted,
+        absorbed, absorbed_by_layer int64[L'], E_hist int64[L', B_E] | None)``.  AbsorptionStep."""
+        return _absorb(self.lib.pcl_step_absorb_scattered, self.ctx, omega0, edges, center, E_edges, seed, n_pass)
+
 
 class DeviceGroup:
     """``pcl_group_*``: several contexts in one process, sharded by global index, behind the C ABI (the shim owns the
@@ -1046,6 +1076,10 @@ class DeviceGroup:
     def phase_redirect(self, phase, g=0.0, c=0.0, seed=0, n_pass=0):
         """``Device.phase_redirect`` on every context of the group, the counts summed (pcl_group_step_phase_redirect)."""
         return _phase(self.lib.pcl_group_step_phase_redirect, self.g, phase, g, c, seed, n_pass)
+
+    def absorb_scattered(self, omega0, edges=None, center=None, E_edges=None, seed=0, n_pass=0):
+        """``Device.absorb_scattered`` on every context of the group, the tallies summed (pcl_group_step_absorb_scattered)."""
+        return _absorb(self.lib.pcl_group_step_absorb_scattered, self.g, omega0, edges, center, E_edges, seed, n_pass)
 
     def download(self, field, n=None, offset=0, dtype=None):
         n = self.count - offset if n is None else n

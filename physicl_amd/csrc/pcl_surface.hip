@@ -1,4 +1,4 @@
-// pcl_surface.hip -- the two sweeps that re-direct photons.
+// pcl_surface.hip -- the sweeps that rewrite photons: two that re-direct them, one that absorbs them.
 //
 // A reflecting sphere (SurfaceReflectStep): the ground of a radial problem.  Photons whose last move took
 // them into the sphere are put back: reflected at the point where the move met the sphere (specular, or cosine-weighted about
@@ -52,6 +52,23 @@
 //               mu = copysign(max(max(|gq|, u_c), u_d), gq)      (the largest of three uniforms has density 3 x^2)
 //   s = sqrt((1 - mu)*(1 + mu));  psi = (u_b*2)*pi;  sc = s*cos psi;  ss = s*sin psi;  the frame e1, e2 about w as above about nrm
 //   dir_k = (sc*e1_k + ss*e2_k) + mu*w_k;  v_k = c*dir_k;  dv_k = v_k - o_k
+//
+// An absorbing medium (AbsorptionStep): of the photons the scatter step of this pass has hit (dv != 0), those whose draw falls
+// above the single-scattering albedo omega0 of the layer they stand in are absorbed: left in the store at rest where they are.
+// It joined this unit as the phase function did: the unit holds the sweeps that rewrite photons and has the Philox block.
+//
+//   k_absorb_scattered<T>  one grid-stride sweep: per slot the three dv rows (24 B in fp64), widened to double; lanes with a
+//                          non-zero dv are counted (one ballot + popcount per wave) and, with layers, load r and look q up in
+//                          the squared edges (LDS, a binary search, no square root); lanes whose layer has omega0 < 1 load their
+//                          id and draw; absorbed lanes are counted (a second ballot), write zeros to v and dv, add to their
+//                          layer's cell and -- with energy bins -- load E and add to their layer's histogram.  Tallies are
+//                          workgroup-private uint32 cells in LDS, flushed with 64-bit atomics.  dr and E are never written.
+//
+// Operation order (what light._absorb_scattered restates with numpy):
+//   interacted iff a photon and (dv0 != 0 or dv1 != 0 or dv2 != 0);  no layers: b = 0;  layers: d = r - center;  q = d.d;
+//   inside iff e2_0 <= q <= e2_L (NaN: false);  b = the bin of q in e2 = e*e: [e2_b, e2_(b+1)), the last one closed
+//   inside and omega0_b < 1:  u = u53(w0, w1) of counter (id_lo, id_hi, pass, 12);  absorbed iff not (u < omega0_b)
+//   absorbed:  v_k = 0;  dv_k = 0       (NOT the ground's dv = -v_old: a later sweep of this pass must see "did not scatter")
 #include "pcl_sweep.h"
 
 #include "pcl_device.h" // (after the HIP runtime and the ABI's header, which pcl_sweep.h brings)
@@ -258,6 +275,91 @@ __global__ void __launch_bounds__(kBlock) k_phase_redirect(phase_args<T> a) {
     flush_cells(s_cnt, a.out, 1);
 }
 
+template <typename T>
+struct absorb_args {
+    const T *r[3];
+    T *v[3], *dv[3];
+    const T *E;                  // NULL without energy bins
+    const unsigned char *kind;   // NULL: every particle is a photon
+    const int64_t *ids;          // NULL: the id of slot i is id_base + i
+    const double *tables;        // omega0 (L') | e*e of the layer edges (L + 1, if L) | E edges (n_E + 1, if any), device
+    unsigned long long *out;     // interacted, absorbed | absorbed by layer [L'] | E_hist [L'][n_E]; device, zeroed by the entry point
+    int64_t N, ts, id_base;      // particles, tile stride of the slab (elements), id of slot 0
+    int tile_log;                // log2 of the tile length
+    int n_layers, n_E;           // L (0: one omega0 everywhere, L' = 1), energy bins
+    double c[3];
+    uint32_t k0, k1, pass;       // Philox key (seed_lo, seed_hi), the step's own pass counter
+};
+
+template <typename T>
+__global__ void __launch_bounds__(kBlock) k_absorb_scattered(absorb_args<T> a) {
+    extern __shared__ double s_mem[];                                  // tables | interacted, absorbed | by layer | E histogram
+    const int L = a.n_layers, Lp = L > 0 ? L : 1, nE = a.n_E;
+    const int n_tab = Lp + (L ? L + 1 : 0) + (nE ? nE + 1 : 0);
+    const int n_cells = 2 + Lp * (1 + nE);
+    const double *s_om = s_mem;
+    const double *s_e2 = s_om + Lp;
+    const double *s_E = s_e2 + (L ? L + 1 : 0);
+    uint32_t *s_cnt = reinterpret_cast<uint32_t *>(s_mem + n_tab);
+    uint32_t *s_lay = s_cnt + 2;
+    uint32_t *s_Eh = s_lay + Lp;
+    for (int k = threadIdx.x; k < n_tab; k += kBlock) s_mem[k] = a.tables[k];
+    for (int k = threadIdx.x; k < n_cells; k += kBlock) s_cnt[k] = 0;  // (the layers and the histograms follow the two counts)
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    // whole waves run the same number of trips (the ballots below need every lane of the wave inside the loop)
+    const int64_t n_round = (a.N + 63) / 64 * 64;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n_round; i += stride) {
+        const bool in = i < a.N;
+        const int64_t ti = tile_index(i, a.tile_log, a.ts);
+        double d[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            if (in) d[k] = (double)a.dv[k][ti];                         // fp32 widens exactly
+        // interacted in this pass: the rule of k_phase_redirect (NaN != 0 is true)
+        bool go = in && (d[0] != 0.0 || d[1] != 0.0 || d[2] != 0.0);
+        if (go && a.kind) go = a.kind[i] != 0;
+        int b = go && L == 0 ? 0 : -1;                                  // the layer; -1: outside every layer, never absorbed
+        if (go && L > 0) {
+            double x[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) x[k] = __dsub_rn((double)a.r[k][ti], a.c[k]);
+            const double q = dot3(x, x);
+            if (q >= s_e2[0] && q <= s_e2[L]) b = bin_of(s_e2, L, q);   // NaN: in no layer
+        }
+        bool gone = false;
+        if (b >= 0) {
+            const double om = s_om[b];
+            if (om < 1.0) {                                             // a conservative layer draws nothing
+                const uint64_t id = (uint64_t)(a.ids ? a.ids[i] : a.id_base + i);
+                const pcl_u32x4 w = pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, 12u, a.k0, a.k1);
+                gone = !(pcl_u53(w.x, w.y) < om);                       // the sense of the ground's albedo draw
+            }
+        }
+        const uint32_t n_go = (uint32_t)__popcll(__ballot(go)), n_gone = (uint32_t)__popcll(__ballot(gone));
+        if (lane == 0 && n_go) atomicAdd(&s_cnt[0], n_go);
+        if (lane == 0 && n_gone) atomicAdd(&s_cnt[1], n_gone);
+        if (!gone) continue;    // lanes that are left alone wait at the loop's head: no ballot below this line
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {                                   // parked where it is, at rest; "did not scatter"
+            a.v[k][ti] = (T)0.0;
+            a.dv[k][ti] = (T)0.0;
+        }
+        atomicAdd(&s_lay[b], 1u);
+        if (nE) {
+            const double e = (double)a.E[ti];
+            if (e >= s_E[0] && e <= s_E[nE]) atomicAdd(&s_Eh[b * nE + bin_of(s_E, nE, e)], 1u);   // NaN and under/overflow: in no bin
+        }
+    }
+    __syncthreads();
+    // pcl_sweep::flush_cells, written out: its other two callers in this unit hand it a literal 1 or 2 cells, which the compiler
+    // folds into the helper before it inlines it; a third caller with a count that is not a literal takes that away and changes
+    // the epilogue of k_phase_redirect (tools/compare_unit_asm.py shows it).  In place, the two kernels stay the code they were.
+    for (int k = threadIdx.x; k < n_cells; k += kBlock)
+        if (s_cnt[k]) atomicAdd(&a.out[k], (unsigned long long)s_cnt[k]);
+}
+
 struct surface_spec { // a call's arguments, checked
     double c[3] = {0.0, 0.0, 0.0};
     double R2 = 0.0, albedo = 1.0, speed = 0.0;
@@ -414,6 +516,128 @@ int group_phase_redirect(pcl_group *group, int phase, double g, double c, uint64
     return PCL_OK;
 }
 
+struct absorb_spec { // a call's arguments, checked; what the kernel compares against
+    int n_layers = 0, n_E = 0;
+    double c[3] = {0.0, 0.0, 0.0};
+    bool draws = false;         // some layer has omega0 < 1: the ids are needed
+    std::vector<double> tables; // omega0 | e*e | E edges
+    int rows() const { return n_layers > 0 ? n_layers : 1; }
+    size_t cells() const { return (size_t)2 + (size_t)rows() * (1 + (size_t)n_E); }
+};
+
+// Everything PCL_ERR_ARG stands for except the NULL context; nothing is launched or written before this has passed.
+bool check_absorb(int n_layers, const double *omega0, const double *edges, const double *center, int n_E, const double *E_edges,
+                  const int64_t *counts_out, const int64_t *E_hist_out, absorb_spec &s) {
+    if (!omega0 || !counts_out || n_layers < 0 || n_layers > PCL_ABSORB_MAX_LAYERS) return false;
+    if (n_E < 0 || n_E > PCL_ABSORB_MAX_BINS || (n_E > 0 && (!E_edges || !E_hist_out))) return false;
+    s.n_layers = n_layers; s.n_E = n_E;
+    if (s.cells() > PCL_ABSORB_MAX_CELLS) return false;                 // the workgroup's cells and tables stay below 64 KiB of LDS
+    for (int b = 0; b < s.rows(); ++b) {
+        if (!(omega0[b] >= 0.0 && omega0[b] <= 1.0)) return false;      // (NaN as well)
+        s.draws = s.draws || omega0[b] < 1.0;
+        s.tables.push_back(omega0[b]);
+    }
+    if (n_layers > 0 && (!edges || !check_edges(edges, n_layers, kEdgeSquare, &s.tables))) return false;
+    if (n_E > 0 && !check_edges(E_edges, n_E, kEdgePlain, &s.tables)) return false;
+    if (center)
+        for (int k = 0; k < 3; ++k) {
+            if (!std::isfinite(center[k])) return false;
+            s.c[k] = center[k];
+        }
+    return true;
+}
+
+void zero_absorb(const absorb_spec &s, int64_t *counts, int64_t *E_hist) {
+    memset(counts, 0, (size_t)(2 + s.rows()) * sizeof(int64_t));
+    if (s.n_E) memset(E_hist, 0, (size_t)s.rows() * s.n_E * sizeof(int64_t));
+}
+
+template <typename T>
+int launch_absorb(pcl_ctx *ctx, const store_view &v, const absorb_spec &s, const void *E, uint64_t seed, uint32_t pass, int64_t id_base,
+                  const int64_t *ids, const unsigned char *kind, const double *tables_dev, unsigned long long *out_dev) {
+    absorb_args<T> a{};
+    for (int k = 0; k < 3; ++k) {
+        void *r = nullptr, *vel = nullptr, *dv = nullptr;
+        PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_R0 + k, &r));
+        PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_V0 + k, &vel));
+        PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_DV0 + k, &dv));
+        a.r[k] = static_cast<const T *>(r); a.v[k] = static_cast<T *>(vel); a.dv[k] = static_cast<T *>(dv);
+        a.c[k] = s.c[k];
+    }
+    a.E = static_cast<const T *>(E); a.kind = kind; a.ids = ids; a.tables = tables_dev; a.out = out_dev;
+    a.N = v.N; a.ts = v.ts; a.id_base = id_base; a.tile_log = v.tile_log;
+    a.n_layers = s.n_layers; a.n_E = s.n_E;
+    a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32); a.pass = pass;
+    const size_t lds = s.tables.size() * sizeof(double) + s.cells() * sizeof(uint32_t);
+    const int64_t grid = balanced_grid(v.N, v.n_cu, resident_per_cu(lds));
+    hipLaunchKernelGGL(k_absorb_scattered<T>, dim3((unsigned)grid), dim3(kBlock), lds, v.stream, a);
+    return hipGetLastError() == hipSuccess ? PCL_OK : PCL_ERR_HIP;
+}
+
+int absorb_scattered(pcl_ctx *ctx, int n_layers, const double *omega0_host, const double *edges_host, const double *center_host,
+                     int n_E_bins, const double *E_edges_host, uint64_t seed, uint32_t pass, int64_t *counts_out_host,
+                     int64_t *E_hist_out_host) {
+    absorb_spec s;
+    if (!ctx || !check_absorb(n_layers, omega0_host, edges_host, center_host, n_E_bins, E_edges_host, counts_out_host, E_hist_out_host, s))
+        return bad_argument(ctx);
+    store_view v;
+    PCL_SWEEP_TRY(open_store(ctx, PCL_DV0, &v));
+    zero_absorb(s, counts_out_host, E_hist_out_host);
+    if (v.N <= 0) return PCL_OK;
+    // E is asked for only with energy bins: the pointer costs a wavelength-dependent scatter step its term cache (pcl_shell.hip).
+    void *E = nullptr;
+    if (s.n_E) PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_E, &E));
+    std::vector<uint8_t> kind_host;                                     // a store that is not uniform: as surface_reflect;
+    std::vector<int64_t> ids_host;                                      // the ids only if somebody may draw
+    bool mixed = false;
+    int64_t id_base = 0;
+    PCL_SWEEP_TRY(kind_bytes(ctx, v.N, kind_host, &mixed));
+    if (s.draws) PCL_SWEEP_TRY(id_words(ctx, v.N, ids_host, &id_base));
+    const size_t cells = s.cells();
+    const size_t out_bytes = cells * sizeof(uint64_t), tab_bytes = s.tables.size() * sizeof(double);
+    const size_t id_bytes = ids_host.size() * sizeof(int64_t);
+    dev_block blk(ctx);
+    PCL_SWEEP_TRY(stage(blk, v.stream, out_bytes, s.tables.data(), tab_bytes, kind_host, ids_host));
+    char *base = static_cast<char *>(blk.p);
+    const double *tables_dev = reinterpret_cast<const double *>(base + out_bytes);
+    const int64_t *ids = id_bytes ? reinterpret_cast<const int64_t *>(base + out_bytes + tab_bytes) : nullptr;
+    const unsigned char *kind = mixed ? reinterpret_cast<const unsigned char *>(base + out_bytes + tab_bytes + id_bytes) : nullptr;
+    unsigned long long *out_dev = reinterpret_cast<unsigned long long *>(base);
+    PCL_SWEEP_TRY(v.dtype == PCL_DTYPE_F64 ? launch_absorb<double>(ctx, v, s, E, seed, pass, id_base, ids, kind, tables_dev, out_dev)
+                                           : launch_absorb<float>(ctx, v, s, E, seed, pass, id_base, ids, kind, tables_dev, out_dev));
+    std::vector<int64_t> out(cells);
+    PCL_SWEEP_TRY(pcl_d2h(ctx, out.data(), base, (int64_t)out_bytes)); // the call's one synchronisation (a count is below 2^63)
+    const size_t n_cnt = (size_t)2 + s.rows();
+    memcpy(counts_out_host, out.data(), n_cnt * sizeof(int64_t));
+    if (s.n_E) memcpy(E_hist_out_host, out.data() + n_cnt, (cells - n_cnt) * sizeof(int64_t));
+    return PCL_OK;
+}
+
+int group_absorb_scattered(pcl_group *group, int n_layers, const double *omega0_host, const double *edges_host, const double *center_host,
+                           int n_E_bins, const double *E_edges_host, uint64_t seed, uint32_t pass, int64_t *counts_out_host,
+                           int64_t *E_hist_out_host) {
+    std::vector<pcl_ctx *> ctx;
+    PCL_SWEEP_TRY(shards_of(group, ctx));
+    const int n = (int)ctx.size();
+    absorb_spec s;
+    if (n < 1 || !check_absorb(n_layers, omega0_host, edges_host, center_host, n_E_bins, E_edges_host, counts_out_host, E_hist_out_host, s))
+        return bad_argument(n > 0 ? ctx[0] : nullptr);
+    const size_t n_cnt = (size_t)2 + s.rows(), cells = s.cells();
+    std::vector<std::vector<int64_t>> part((size_t)n, std::vector<int64_t>(cells, 0));
+    PCL_SWEEP_TRY(for_each_shard(ctx, [&](int g, pcl_ctx *one) {
+        int64_t *p = part[(size_t)g].data();
+        return pcl_step_absorb_scattered(one, n_layers, omega0_host, edges_host, center_host, n_E_bins, E_edges_host, seed, pass, p,
+                                         n_E_bins ? p + n_cnt : nullptr);
+    }));
+    zero_absorb(s, counts_out_host, E_hist_out_host);
+    for (int g = 0; g < n; ++g) {
+        const int64_t *p = part[(size_t)g].data();
+        for (size_t k = 0; k < n_cnt; ++k) counts_out_host[k] += p[k];
+        for (size_t k = n_cnt; k < cells; ++k) E_hist_out_host[k - n_cnt] += p[k];
+    }
+    return PCL_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -435,6 +659,24 @@ int pcl_step_phase_redirect(pcl_ctx *ctx, int phase, double g, double c, uint64_
 int pcl_group_step_phase_redirect(pcl_group *group, int phase, double g, double c, uint64_t seed, uint32_t pass,
                                   int64_t *count_out_host) {
     return guarded([&] { return group_phase_redirect(group, phase, g, c, seed, pass, count_out_host); });
+}
+
+int pcl_step_absorb_scattered(pcl_ctx *ctx, int n_layers, const double *omega0_host, const double *edges_host, const double *center_host,
+                              int n_E_bins, const double *E_edges_host, uint64_t seed, uint32_t pass, int64_t *counts_out_host,
+                              int64_t *E_hist_out_host) {
+    return guarded([&] {
+        return absorb_scattered(ctx, n_layers, omega0_host, edges_host, center_host, n_E_bins, E_edges_host, seed, pass, counts_out_host,
+                                E_hist_out_host);
+    });
+}
+
+int pcl_group_step_absorb_scattered(pcl_group *group, int n_layers, const double *omega0_host, const double *edges_host,
+                                    const double *center_host, int n_E_bins, const double *E_edges_host, uint64_t seed, uint32_t pass,
+                                    int64_t *counts_out_host, int64_t *E_hist_out_host) {
+    return guarded([&] {
+        return group_absorb_scattered(group, n_layers, omega0_host, edges_host, center_host, n_E_bins, E_edges_host, seed, pass,
+                                      counts_out_host, E_hist_out_host);
+    });
 }
 
 } // extern "C"

@@ -1009,6 +1009,174 @@ class PhaseFunctionStep(DeviceStep, MeasureStep):
         return DeviceStep.run(self, sim)
 
 
+# ---------------------------------------------------------------------------------------------- absorbing media
+def _check_absorb(omega0, edges, center, E_bins):
+    """(omega0 -- a float without ``edges``, else a float64 array of one value per layer --, edges or None, centre, energy edges or
+    None) of an AbsorptionStep, or ValueError for everything pcl_step_absorb_scattered would refuse."""
+    from ._hip import ABSORB_MAX_BINS, ABSORB_MAX_CELLS, ABSORB_MAX_LAYERS      # (the header's limits: one place)
+    try:
+        om = np.array(omega0, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("omega0 must be a number, or with edges one number per layer") from None
+    if edges is None:
+        if om.shape != ():
+            raise ValueError("omega0 must be one number without edges (edges= gives it one value per layer), got shape %r" % (om.shape,))
+    else:
+        edges = tally.check_edges("edges", edges, ABSORB_MAX_LAYERS, "square")      # (the device compares q with e*e)
+        if om.ndim != 1 or len(om) != len(edges) - 1:
+            raise ValueError("omega0 must hold one value per layer: edges describe %d layers, omega0 has shape %r" % (len(edges) - 1, om.shape))
+    if not np.all((om >= 0.0) & (om <= 1.0)):                 # (False for NaN as well)
+        raise ValueError("omega0 must lie in [0, 1], got %r" % (omega0,))
+    center = tally.check_center(center)
+    rows = 1 if edges is None else len(edges) - 1
+    if E_bins is not None:
+        E_bins = tally.check_edges("E_bins", E_bins, ABSORB_MAX_BINS)
+        cells = 2 + rows * len(E_bins)
+        if cells > ABSORB_MAX_CELLS:
+            raise ValueError("%d layers x %d E_bins bins are %d tally cells, at most %d are supported" % (rows, len(E_bins) - 1, cells, ABSORB_MAX_CELLS))
+    return (float(om) if edges is None else np.ascontiguousarray(om)), edges, center, E_bins
+
+
+def _absorb_scattered(r, v, dv, E, photon, ids, omega0, edges, center, E_bins, seed, n_pass, dtype=np.float64):
+    """What pcl_step_absorb_scattered makes of (n, 3) float64 positions, velocities and last velocity changes, the energies, who is
+    a photon and the particles' ids, with numpy -- every operation the device's operation in the device's order, one rounding each
+    (include/physicl_hip.h): no transcendental function and no division, so everything is the device's bit for bit.  What is
+    written is zero, in any ``dtype``.  A dict: ``v, dv`` the new state (float64 arrays; rows that are not absorbed are the
+    arguments'), ``interacted`` (a photon with a non-zero dv) and ``absorbed`` boolean masks, ``layer`` (int64: the layer of every
+    interacting row, -1 for a row outside every layer or not interacting) and the tallies ``absorbed_by_layer`` (int64 [L'])
+    and ``E_hist`` (int64 [L', bins], None without ``E_bins``)."""
+    r, v, dv = (np.array(a, dtype=np.float64).reshape(-1, 3) for a in (r, v, dv))
+    n = len(v)
+    om = np.asarray(omega0, dtype=np.float64).reshape(-1)
+    rows = 1 if edges is None else len(edges) - 1
+    with np.errstate(invalid="ignore", over="ignore"):
+        interacted = ((dv[:, 0] != 0) | (dv[:, 1] != 0) | (dv[:, 2] != 0)) & np.asarray(photon, dtype=bool).reshape(-1)
+        at = np.flatnonzero(interacted)
+        layer = np.full(n, -1, dtype=np.int64)
+        if edges is None:
+            layer[at] = 0
+        else:
+            e = np.asarray(edges, dtype=np.float64)
+            e2 = e * e
+            d = r[at] - np.asarray(center, dtype=np.float64)
+            q = _dot3(d, d)
+            inside = (q >= e2[0]) & (q <= e2[-1])                                   # NaN: in no layer
+            layer[at[inside]] = np.clip(np.searchsorted(e2, q[inside], side="right") - 1, 0, rows - 1)   # the last layer is closed
+    draws = np.flatnonzero(layer >= 0)
+    draws = draws[om[layer[draws]] < 1.0]                      # a conservative layer draws nothing
+    u = _philox_block(np.asarray(ids).reshape(-1)[draws], seed, n_pass, 12)[0]
+    gone = draws[~(u < om[layer[draws]])]                      # the sense of the ground's albedo draw
+    absorbed = np.zeros(n, dtype=bool)
+    absorbed[gone] = True
+    v[gone], dv[gone] = np.zeros(3, dtype=dtype), np.zeros(3, dtype=dtype)
+    out = {"v": v, "dv": dv, "interacted": interacted, "absorbed": absorbed, "layer": layer,
+           "absorbed_by_layer": np.bincount(layer[gone], minlength=rows).astype(np.int64), "E_hist": None}
+    if E_bins is not None:                                     # numpy.histogram's bins: [e_b, e_b+1), the last one closed
+        eb, val = np.asarray(E_bins, dtype=np.float64), np.asarray(E, dtype=np.float64).reshape(-1)[gone]
+        nb = len(eb) - 1
+        with np.errstate(invalid="ignore"):
+            ok = (val >= eb[0]) & (val <= eb[-1])
+        cell = layer[gone][ok] * nb + np.clip(np.searchsorted(eb, val[ok], side="right") - 1, 0, nb - 1)
+        out["E_hist"] = np.bincount(cell, minlength=rows * nb).astype(np.int64).reshape(rows, nb)
+    return out
+
+
+class AbsorptionStep(DeviceStep, MeasureStep):
+    """An absorbing medium (not in the reference): the single-scattering albedo ``omega0``, the chance that an interaction is a
+    scatter and not an absorption.  ``ScatterIsotropicStep`` decides who interacts; this step, placed anywhere BEHIND the scatter
+    step of a pass and before the next Newton step (before or behind a ``PhaseFunctionStep``; measures may stand between), lets
+    each interacting photon be absorbed with probability ``1 - omega0``.
+
+    * ``edges=None``: ``omega0`` is one number in [0, 1] and holds everywhere;
+    * ``edges``: ``L + 1`` finite, non-negative, strictly increasing radii about ``center`` (code units, at most 64 layers);
+      ``omega0`` is then a sequence of ``L`` numbers in [0, 1].  Layer ``b`` holds a photon iff ``e_b**2 <= q < e_(b+1)**2``, the
+      last layer closed as in ``numpy.histogram``, ``q = (d0*d0 + d1*d1) + d2*d2`` the squared distance from ``center`` in
+      float64 -- no square root is taken.  A photon outside every layer (or with a NaN in ``q``) is never absorbed: it is counted
+      as interacting and left alone.
+
+    "Interacted in this pass" is read off the store by ``PhaseFunctionStep``'s rule: a photon with a non-zero ``dv``.  Plain
+    ``Object``s are never touched.  The step is ANALOG: an absorbed photon is parked at rest where it was absorbed, ``v = 0`` and
+    ``dv = 0``; ``r``, ``dr``, ``E``, ids and kinds are left alone.  ``E`` is not scaled as a statistical weight -- it is the photon's
+    energy, which the wavelength-dependent scatter step reads for its lambda**-4 term: a weight kept there would change the
+    photon's colour.  ``dv = 0`` is deliberate and differs from the ground's ``dv = -v_old`` (``SurfaceReflectStep``): the ground
+    ends a pass, this step stands in the middle of one, and a ``PhaseFunctionStep`` or a second ``AbsorptionStep`` later in the pass
+    must see a photon that did not scatter and leave it at rest -- with ``dv = -v_old`` the phase function would send it off again
+    at speed c.  From then on the photon behaves like one the ground absorbed: Newton does not move it, the scatter steps hit it
+    only on a draw of exactly 0, and a ``PositionGridMeasureStep`` shows where the energy was left.
+
+    After each run ``self.interacted`` and ``self.absorbed`` hold the pass's counts, ``self.absorbed_by_layer`` an int64 array
+    ``[L]`` (``[1]`` without ``edges``) and -- with ``E_bins``, bin edges in the unit E is stored in -- ``self.E_hist`` an int64 array
+    ``[max(L, 1), bins]``: the absorbed photons' energies per layer as ``numpy.histogram`` bins them (energies outside the edges are
+    not counted).  All of them are global over shards and ranks.  ``self.data`` gains the row ``[t, interacted, absorbed,
+    absorbed_by_layer (, E_hist)]``; ``out_fn`` takes the rows at the end.  The arithmetic is written out in include/physicl_hip.h
+    (pcl_step_absorb_scattered); ``_absorb_scattered`` restates every bit of it with numpy.
+
+    The draw is a Philox block keyed by ``sim.seed``, the photon's id and a pass counter of the step's own, in a counter word no
+    other kernel uses: every other step draws what it draws without this one, and a photon draws the same number however the run
+    is sharded.  A layer with ``omega0 == 1`` draws nothing.  The draws are made on the device with every ``rng=`` setting.  Under
+    the reference's Python semantics (``cl_on=False``) a hit leaves ``dv = v_old``, the rule above does not hold, and the step
+    raises ``ValueError``.
+
+    One launch per light step: the K-passes-per-launch kernels cannot absorb a photon between two of their passes, and
+    ``sim.launch_note`` says so.  On host-resident objects (``step.run(sim)`` outside a device loop) the same state is made with
+    numpy, the ids being the places in the object list."""
+    _fuse_role = None
+    _NOTE = "one launch per light step: an AbsorptionStep absorbs interacting photons behind every pass, which the " \
+            "K-passes-per-launch kernels cannot carry"
+
+    def __init__(self, omega0=1.0, edges=None, center=(0, 0, 0), E_bins=None, out_fn=None):
+        MeasureStep.__init__(self, out_fn)
+        self.omega0, self.edges, self.center, self.E_bins = _check_absorb(omega0, edges, center, E_bins)
+        rows = 1 if self.edges is None else len(self.edges) - 1
+        self.interacted = self.absorbed = 0
+        self.absorbed_by_layer = np.zeros(rows, dtype=np.int64)
+        self.E_hist = None if self.E_bins is None else np.zeros((rows, len(self.E_bins) - 1), dtype=np.int64)
+        self._pass = 0                                   # the step's own Philox counter word: one per run
+
+    def _record_pass(self, sim, interacted, absorbed, by_layer, E_hist):
+        self.interacted, self.absorbed = int(interacted), int(absorbed)
+        self.absorbed_by_layer = np.array(by_layer, dtype=np.int64)
+        self.E_hist = None if E_hist is None else np.array(E_hist, dtype=np.int64)
+        cells = [self.absorbed_by_layer.copy()] + ([] if self.E_hist is None else [self.E_hist.copy()])
+        self.data.append(tally.object_row([tally._snap(sim.t), self.interacted, self.absorbed] + cells))
+
+    @staticmethod
+    def _refuse_py_semantics(sim):
+        if getattr(sim, "_py_semantics", None) is not None and sim._py_semantics():
+            raise ValueError("AbsorptionStep needs cl_on=True: under the reference's Python semantics a scattered photon is left "
+                             "with dv = v_old, not v' - v_old, so who interacted in this pass cannot be read off the store")
+
+    def _device_run(self, sim):
+        self._refuse_py_semantics(sim)
+        if getattr(sim, "launch_note", self._NOTE) is None and sim._k_wanted() > 1:      # (a device run only: the host path says nothing)
+            sim.launch_note = self._NOTE
+        self._pass += 1
+        interacted, absorbed, by_layer, E_hist = sim._dev.absorb_scattered(self.omega0, self.edges, self.center, self.E_bins, sim.seed, self._pass)
+        sim._scattered = True                            # velocities were replaced on the device
+        # one payload, cut like the shell step's row where it is longer than one call of the library's own communicator carries
+        # (every rank issues it, also with an empty shard)
+        _, (both, by_layer, E_hist) = tally.reduce_parts(sim, [np.array([interacted, absorbed], dtype=np.int64), np.asarray(by_layer), E_hist])
+        self._record_pass(sim, both[0], both[1], by_layer, E_hist)
+
+    def run(self, sim):
+        self._refuse_py_semantics(sim)
+        if getattr(sim, "_residency", None) == "host" and getattr(sim, "_batch", None) is None \
+                and (sim.comm is None or sim.comm.world == 1):
+            objs = list(sim.objects)
+            self._pass += 1
+            E, photon = tally.photon_energies(objs, PhotonObject)
+            new = _absorb_scattered(tally.vec3(objs, "r"), tally.vec3(objs, "v"), tally.vec3(objs, "dv"), E, photon, np.arange(len(objs)),
+                                    self.omega0, self.edges, self.center, self.E_bins, getattr(sim, "seed", 0), self._pass)
+            for k in np.flatnonzero(new["absorbed"]).tolist():
+                o = objs[k]
+                o.v, o.dv = np.array(new["v"][k], dtype=np.double), np.array(new["dv"][k], dtype=np.double)   # plain arrays, as a scatter leaves them
+            self._record_pass(sim, new["interacted"].sum(), new["absorbed"].sum(), new["absorbed_by_layer"], new["E_hist"])
+            return None
+        return DeviceStep.run(self, sim)
+
+    terminate = tally.TallyStep.terminate                # (a row holds arrays: written as the tally steps write theirs, as plain lists)
+
+
 def _DEFAULT_ID_INFO(x):
     """The reference's default ``lambda x: str(type(x))`` (light.py:438), recognised by identity.  The label goes into the trace
     table's first column: this package's own classes read as the reference's (``<class 'physicl.light.PhotonObject'>``, what a

@@ -282,6 +282,12 @@ class MultiDevice:
     def phase_redirect(self, *a, **kw):
         return sum(self._each(lambda s: s.phase_redirect(*a, **kw)))
 
+    def absorb_scattered(self, *a, **kw):
+        outs = self._each(lambda s: s.absorb_scattered(*a, **kw))
+        hists = [o[3] for o in outs]
+        return (sum(o[0] for o in outs), sum(o[1] for o in outs), self._sum([o[2] for o in outs]),
+                None if hists[0] is None else self._sum(hists))
+
     def plane_energies(self, plane, n_hint=None):
         return self._concat(self._each(lambda s: s.plane_energies(plane)))      # (a shard does not know its share of the hint)
 

@@ -7,7 +7,9 @@ For a refactor of their host side, of pcl_sweep.h or of the build, in place of a
 Each unit of each tree is compiled to gfx950 assembly with the library's own options (physicl_amd/build.py: FLAGS without
 -shared / -fPIC, plus --cuda-device-only -S, as tests/test_build_cpu.py does).  Per kernel the register and
 segment metadata must be equal and the instruction lines must be the same multiset (the scheduler may swap neighbours when
-a helper moves into a header, so not the same sequence).  Exit status 1 if any kernel differs.
+a helper moves into a header, so not the same sequence).  A kernel that only the new tree has is listed as new with its
+metadata (a unit that gained a sweep: the kernels it had must still be the code they were); one that only the old tree has
+counts as a difference.  Exit status 1 if any kernel differs.
 """
 import argparse
 import collections
@@ -66,11 +68,18 @@ def main():
         print("|---|---|---|---|---|---|---|---|---|---|")
     for u in UNITS:
         old, new = asm[("old", u)], asm[("new", u)]
-        if sorted(old) != sorted(new):
+        if set(old) - set(new):
             bad += 1
-            print("%s: kernel names differ: %s | %s" % (u, sorted(old), sorted(new)))
-            continue
-        for name in sorted(old):
+            print("%s: kernels of the old tree are missing: %s" % (u, sorted(set(old) - set(new))))
+        for name in sorted(set(new) - set(old)):
+            m1, i1 = new[name]
+            if a.md:
+                print("| %s | `%s` | %d | %d | %d | %d | %d/%d | new: %d | new | new |" % (
+                    u, dem_short(name), m1["vgpr_count"], m1["sgpr_count"], m1["group_segment_fixed_size"], m1["private_segment_fixed_size"],
+                    m1["vgpr_spill_count"], m1["sgpr_spill_count"], sum(i1.values())))
+            else:
+                print("%-18s %-44s %5d instructions  new: %s" % (u, dem_short(name), sum(i1.values()), m1))
+        for name in sorted(set(old) & set(new)):
             (m0, i0), (m1, i1) = old[name], new[name]
             same_m, same_i = m0 == m1, i0 == i1
             bad += not (same_m and same_i)
