@@ -24,11 +24,11 @@ import physicl.light
 import physicl.newton
 from physicl_amd import light
 from phase_reference import C, SEED, cloud, ulp
+from writer_reference import DIR_OPS, DIR_ULP      # the derivation above, kept in one place
 
 pytestmark = pytest.mark.gpu
 
-DIR_OPS = 8
-DIR_ULP = 4 + DIR_OPS / 2
+assert (DIR_OPS, DIR_ULP) == (8, 8.0)
 SIZES = [1, 63, 64, 65, 255, 256, 257, 2047, 2048, 2049, 4097]
 LAWS = [("isotropic", 0.0), ("hg", 0.85), ("hg", -0.5), ("rayleigh", 0.0)]
 FIELDS = ("r", "v", "dr", "dv")

@@ -29,14 +29,15 @@ import physicl.light
 import physicl.newton
 from physicl_amd import light
 from surface_reference import C, CENTER, RADIUS, SEED, cloud, ulp
+from writer_reference import DIR_OPS, DIR_ULP, POS_OPS, lambertian_position_bound      # the derivation above, kept in one place
 
 pytestmark = pytest.mark.gpu
 
-DIR_OPS, POS_OPS = 8, 3
-DIR_ULP = 4 + DIR_OPS / 2
+assert (DIR_OPS, POS_OPS, DIR_ULP) == (8, 3, 8.0)
 W_MAX = 2.8 * RADIUS                   # the longest move of surface_reference.cloud
 MAG = float(np.max(np.abs(CENTER))) + RADIUS + W_MAX
-POS_BOUND = W_MAX / C * (DIR_ULP - 0.5) * ulp(C) + POS_OPS / 2 * ulp(MAG)
+POS_BOUND = lambertian_position_bound(W_MAX, MAG, C)
+assert POS_BOUND == W_MAX / C * (DIR_ULP - 0.5) * ulp(C) + POS_OPS / 2 * ulp(MAG)
 SIZES = [1, 63, 64, 65, 255, 256, 257, 2047, 2048, 2049, 4097]
 FIELDS = ("r", "v", "dr", "dv")
 ID_BASE = 7_000_000_001
