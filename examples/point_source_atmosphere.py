@@ -4,6 +4,7 @@ examples (n(r) = 2.5e25 m^-3 * exp(-(|r| - 6371 km) / 8.6 km)) with photons that
 
     python examples/point_source_atmosphere.py [n_photons] [passes] [--cone | --beam-down | --default] [--profile] [--shells]
                                                [--ground [ALBEDO]] [--phase rayleigh | hg:G | isotropic] [--omega0 W | W1,W2,...]
+                                               [--cloud LO,HI[,G]]
 
 default: a point source at (6371 km, 0, 0) emitting isotropically; ``--cone``: a 0.3 rad cone pointing up (+x) from a 1 km disc;
 ``--beam-down``: a 10 km gaussian beam entering from 100 km above the surface along -x; ``--default``: the same step list from
@@ -27,6 +28,10 @@ interacting photon with probability 1 - W and leaves it at rest where it was abs
 single-scattering albedo per altitude shell: the three shells between the ``--shells`` radii (ground, 10, 50, 100 km) with
 three values, the forty 5 km shells of ``--profile`` with forty.  One launch per light step; the photons absorbed per layer are
 printed beside the top-of-atmosphere and ground counts.
+``--cloud LO,HI[,G]`` (altitudes in metres) gives the atmosphere a cloud layer: a LayeredPhaseStep in the place of the phase
+function scatters by Rayleigh's law everywhere and, between the altitudes LO and HI, by a mixture of one part Rayleigh and nine
+parts Henyey-Greenstein with the mean cosine G (default 0.85).  One launch per light step; the photons re-directed per layer and
+per law are printed beside the shell counts.  Not together with ``--phase``: a pass holds one phase step.
 """
 import os
 import sys
@@ -54,6 +59,16 @@ omega0 = None
 if "--omega0" in argv:
     at = argv.index("--omega0")
     omega0 = [float(x) for x in (argv.pop(at + 1) if at + 1 < len(argv) else "").split(",")]
+cloud = None
+if "--cloud" in argv:
+    at = argv.index("--cloud")
+    cloud = [float(x) for x in (argv.pop(at + 1) if at + 1 < len(argv) else "").split(",")]
+    if len(cloud) not in (2, 3) or not 0.0 < cloud[0] < cloud[1] < 1000e3:
+        sys.exit("--cloud LO,HI[,G]: two altitudes in metres, 0 < LO < HI < 1000 km, and optionally the cloud's mean cosine")
+    if phase is not None:
+        sys.exit("--cloud and --phase: a pass holds one phase step")
+    cloud = (cloud[0], cloud[1], cloud[2] if len(cloud) == 3 else 0.85)
+CLOUD_WEIGHTS = [[1, 0], [0.1, 0.9], [1, 0]]                  # below the cloud, in it, above it: (Rayleigh, Henyey-Greenstein)
 args = [a for a in argv if not a.startswith("--")]
 n = int(float(args[0])) if len(args) > 0 else 100_000_000
 passes = int(args[1]) if len(args) > 1 else 200
@@ -90,6 +105,8 @@ def run(ground):
         medium = light.AbsorptionStep(omega0[0] if layer_edges is None else omega0, edges=layer_edges)
         sim.add_step("absorb", medium)
     angles = light.PhaseFunctionStep(*phase) if phase is not None else None
+    if cloud is not None:                                      # from the Earth's centre to 1000 km up: Rayleigh, but for the cloud
+        angles = light.LayeredPhaseStep(["rayleigh", ("hg", cloud[2])], CLOUD_WEIGHTS, edges=[0.0, R + cloud[0], R + cloud[1], R + 1000e3])
     if angles is not None:                                     # directly behind the scatter step (steps run in the order they were added)
         sim.add_step("phase", angles)
     signs = light.ScatterSignMeasureStep(None, True)
@@ -134,7 +151,12 @@ for row in signs.data[-3:]:
 for row in shells.data[-3:]:
     print("[t, N, crossed x = R + 20 km, crossed y = 0]:", [float(x) for x in row])
 print("scattered in the last step:", sim.hits)
-if angles is not None:
+if cloud is not None:
+    by_layer, by_law = (np.sum([row[k] for row in angles.data], axis=0) for k in (3, 4))
+    print("cloud between %g and %g km (0.1 rayleigh + 0.9 hg, g = %g) in a rayleigh atmosphere: %d photons scattered, %d re-directed over %d passes" % (
+        cloud[0] / 1e3, cloud[1] / 1e3, cloud[2], sum(int(row[1]) for row in angles.data), sum(int(row[2]) for row in angles.data), len(angles.data)))
+    print("  by_layer [below, cloud, above]: %s   by_law [rayleigh, hg]: %s" % (by_layer.tolist(), by_law.tolist()))
+elif angles is not None:
     print("phase function %s (g = %g): %d photons re-directed over %d passes" % (angles.phase, angles.g, sum(int(row[1]) for row in angles.data), len(angles.data)))
 if profile is not None and profile.data:
     t, N, shells_now = profile.data[-1]

@@ -759,6 +759,56 @@ int pcl_step_absorb_scattered(pcl_ctx *ctx, int n_layers, const double *omega0_h
                               const double *center_host, int n_E_bins, const double *E_edges_host, uint64_t seed, uint32_t pass,
                               int64_t *counts_out_host /* [2 + L'] */, int64_t *E_hist_out_host /* [L' * n_E_bins] or NULL */);
 
+/* Phase functions by layer (LayeredPhaseStep): pcl_step_phase_redirect with a law that depends on where the photon stands, and with
+ * tabulated laws.  Called where pcl_step_phase_redirect would be called (directly behind the scatter step of a pass, before or behind
+ * pcl_step_absorb_scattered), it re-directs the photons that step scattered in ONE sweep of the resident store.  Each of the L' =
+ * max(n_layers, 1) radial layers mixes the n_laws = M laws with its own weights.  A pass holds ONE phase step: this entry point
+ * shares the blocks 10 and 11 with pcl_step_phase_redirect and must not be called in a pass in which that one, or this one, has
+ * already been called with the same ``pass``.  Nothing is removed; r, dr, E, ids and kinds are not written, E is not asked for and r
+ * only with layers.  All arithmetic is fp64, every operation rounded once, in the order written.
+ *   scattered  iff  the particle is a photon, (dv0 != 0 or dv1 != 0 or dv2 != 0), and o = v - dv has 0 < o.o < inf
+ *                   (pcl_step_phase_redirect's "re-directed")
+ *   n_layers == 0:  b = 0 for everybody.   n_layers = L >= 1:  the layer b of q = (d0*d0 + d1*d1) + d2*d2, d = r - center, in
+ *                   e2_k = e_k*e_k exactly as pcl_step_absorb_scattered finds it (last layer closed, NaN: in no layer, no square root)
+ *   outside every layer:  counted as scattered, not written: the photon keeps the direction the scatter step gave it
+ *   inside:         re-directed.  The law: M == 1: j = 0;  otherwise j = the first law with u_s < cum_host[b*M + j], u_s = u53(w0, w1)
+ *                   of the block (id_lo, id_hi, pass, 13).  (Whether that block is computed for a row that is one-hot is the
+ *                   kernel's business: the first positive entry of such a row is 1 and 0 <= u_s < 1.)
+ *   block A (id_lo, id_hi, pass, 10): u_a = u53(w0, w1), u_b = u53(w2, w3);  mu by the law's kind:
+ *     PCL_PHASE_ISOTROPIC, PCL_PHASE_HG with g_host[j], PCL_PHASE_RAYLEIGH (block B (id_lo, id_hi, pass, 11)): the lines of
+ *     pcl_step_phase_redirect, bit for bit
+ *     PCL_PHASE_TABLE: a piecewise-constant density on K bins with the nodes mu_0 = -1 < ... < mu_K = 1 and the cumulative values
+ *     F_0 = 0 < ... < F_K = 1 (made by the caller: F = cumsum(p_k*(mu_(k+1) - mu_k)) / sum);  k = the bin of u_a in F ([F_k, F_(k+1)),
+ *     always inside);  s_k = (mu_(k+1) - mu_k) / (F_(k+1) - F_k), made by the library on the host: two subtractions and one division,
+ *     each rounded once;  mu = min(max(mu_k + (u_a - F_k)*s_k, mu_k), mu_(k+1))
+ *   then s, psi, the frame about w = o / sqrt(o.o), dir, v = c*dir and dv = v - o exactly as pcl_step_phase_redirect.
+ * So a call with one law and no layers leaves the store bit for bit as pcl_step_phase_redirect with that law, seed and pass leaves
+ * it.  The word 13 is used by nothing else (scatter kernels 0 and 1, fill and source 2..5, pcl_step_surface_reflect 8 and 9,
+ * pcl_step_phase_redirect 10 and 11, pcl_step_absorb_scattered 12).
+ * kinds_host: M ints, 1 <= M <= PCL_LPHASE_MAX_LAWS.  g_host: M doubles, read for PCL_PHASE_HG laws only (finite, |g| < 1; may be
+ * NULL without such a law).  n_bins_host: M ints, read for PCL_PHASE_TABLE laws only: K, 1 <= K <= PCL_LPHASE_MAX_NODES, the sum
+ * over the tables at most PCL_LPHASE_MAX_TOTAL_NODES.  mu_host, F_host: the K + 1 nodes and cumulative values of the tables one behind
+ * the other, in the order of the laws (all three may be NULL without a table).  cum_host: L' rows of M cumulative weights, each row
+ * not decreasing from a value >= 0 and ending in exactly 1.  edges_host, center_host: as pcl_step_absorb_scattered, 1 <= L <=
+ * PCL_LPHASE_MAX_LAYERS, ignored with n_layers == 0.  ``c``: the speed of light in code units.  The tables (at the limits about 54
+ * KiB) and the cells stay below 64 KiB of LDS; a call is sized by what it uses.
+ * counts_out_host[0] = photons scattered, [1] = re-directed, [2 + b] = re-directed in layer b, [2 + L' + j] = re-directed by law j.
+ * A store that is not uniform costs the host traffic it costs pcl_step_surface_reflect.  PCL_ERR_ARG (NULL kinds, weights or counts,
+ * M or L outside their limits, an unknown kind, a bad g, a table with bad counts, nodes that do not rise from -1 to 1, cumulative
+ * values that do not rise strictly from 0 to 1, a row of weights that decreases or does not end in 1, bad edges or centre, c not
+ * finite) is returned before anything is launched or written; PCL_ERR_STATE without a store; an empty store answers zeros without a
+ * launch.  Host pointers; one device allocation per call, handed back on every way out; synchronises once, with the copy of the
+ * tallies.  pcl_last_error() is generic, as for pcl_step_surface_reflect, whose source file these two entry points share. */
+#define PCL_PHASE_TABLE 3
+#define PCL_LPHASE_MAX_LAWS 8
+#define PCL_LPHASE_MAX_LAYERS 64
+#define PCL_LPHASE_MAX_NODES 1024       /* bins of one table */
+#define PCL_LPHASE_MAX_TOTAL_NODES 2048 /* bins of all tables of a call */
+int pcl_step_phase_layered(pcl_ctx *ctx, int n_laws, const int *kinds_host, const double *g_host, const int *n_bins_host,
+                           const double *mu_host, const double *F_host, int n_layers, const double *cum_host,
+                           const double *edges_host, const double *center_host, double c, uint64_t seed, uint32_t pass,
+                           int64_t *counts_out_host /* [2 + L' + M] */);
+
 /* ---- Device groups: several GPUs from ONE process ---------------------------------------------------------------
  * The reference is a single process with one simulation thread (physicl/__init__.py:400-432, 501-524); this is how
  * a host written against this ABI uses a node's GPUs the same way, without one process per GPU.  A group owns one
@@ -832,6 +882,12 @@ int pcl_group_step_phase_redirect(pcl_group *group, int phase, double g, double 
 int pcl_group_step_absorb_scattered(pcl_group *group, int n_layers, const double *omega0_host, const double *edges_host,
                                     const double *center_host, int n_E_bins, const double *E_edges_host, uint64_t seed, uint32_t pass,
                                     int64_t *counts_out_host, int64_t *E_hist_out_host);
+/* pcl_step_phase_layered on every shard (side by side), the tallies summed over the group's devices; the arguments are checked
+ * once for the group, before any shard is written */
+int pcl_group_step_phase_layered(pcl_group *group, int n_laws, const int *kinds_host, const double *g_host, const int *n_bins_host,
+                                 const double *mu_host, const double *F_host, int n_layers, const double *cum_host,
+                                 const double *edges_host, const double *center_host, double c, uint64_t seed, uint32_t pass,
+                                 int64_t *counts_out_host);
 
 /* ---------------------------------------------------------------- the counters' collective (one process per GPU)
  * The path shards by global index with no data-path exchange; the only global quantities are the int64

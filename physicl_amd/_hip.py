@@ -30,6 +30,8 @@ SHELL_MAX_SHELLS, SHELL_MAX_BINS, SHELL_MAX_CELLS = 16, 1024, 8192              
 SURFACE_MODES = {"lambertian": 0, "specular": 1}                             # PCL_SURFACE_LAMBERTIAN, PCL_SURFACE_SPECULAR
 ABSORB_MAX_LAYERS, ABSORB_MAX_BINS, ABSORB_MAX_CELLS = 64, 1024, 12288           # PCL_ABSORB_MAX_LAYERS ...
 PHASE_FUNCTIONS = {"isotropic": 0, "hg": 1, "rayleigh": 2}                   # PCL_PHASE_ISOTROPIC, PCL_PHASE_HG, PCL_PHASE_RAYLEIGH
+PHASE_TABLE = 3                                                              # PCL_PHASE_TABLE: a law of pcl_step_phase_layered only
+LPHASE_MAX_LAWS, LPHASE_MAX_LAYERS, LPHASE_MAX_NODES, LPHASE_MAX_TOTAL_NODES = 8, 64, 1024, 2048       # PCL_LPHASE_MAX_LAWS ...
 PROF_NEWTON, PROF_SCATTER, PROF_DELETE_MASK, PROF_COMPACT, PROF_COUNTERS, PROF_FUSED, PROF_MULTI, PROF_ONEPASS, \
     PROF_DELETE_AHEAD = range(9)
 PROF_NAMES = {PROF_NEWTON: "k_newton", PROF_SCATTER: "k_scatter", PROF_DELETE_MASK: "k_delete_mask",
@@ -154,6 +156,7 @@ _PROTOTYPES = {
     "pcl_step_surface_reflect": [_vp, c_double, _vp, c_double, c_int, c_double, c_uint64, c_uint32, _vp],
     "pcl_step_phase_redirect": [_vp, c_int, c_double, c_double, c_uint64, c_uint32, _vp],
     "pcl_step_absorb_scattered": [_vp, c_int, _vp, _vp, _vp, c_int, _vp, c_uint64, c_uint32, _vp, _vp],
+    "pcl_step_phase_layered": [_vp, c_int, _vp, _vp, _vp, _vp, _vp, c_int, _vp, _vp, _vp, c_double, c_uint64, c_uint32, _vp],
     # device groups: several GPUs from one process (the C-level counterpart of physicl_amd.multidev.MultiDevice)
     "pcl_group_create": [c_int, POINTER(c_int), POINTER(_vp)],
     "pcl_group_destroy": [_vp],
@@ -183,6 +186,7 @@ _PROTOTYPES = {
     "pcl_group_step_surface_reflect": [_vp, c_double, _vp, c_double, c_int, c_double, c_uint64, c_uint32, _vp],
     "pcl_group_step_phase_redirect": [_vp, c_int, c_double, c_double, c_uint64, c_uint32, _vp],
     "pcl_group_step_absorb_scattered": [_vp, c_int, _vp, _vp, _vp, c_int, _vp, c_uint64, c_uint32, _vp, _vp],
+    "pcl_group_step_phase_layered": [_vp, c_int, _vp, _vp, _vp, _vp, _vp, c_int, _vp, _vp, _vp, c_double, c_uint64, c_uint32, _vp],
 }
 EXPORTS = sorted(list(_PROTOTYPES) + ["pcl_last_error"])
 
@@ -376,6 +380,37 @@ def _absorb(entry, handle, omega0, edges, center, E_edges, seed, n_pass):
     check(entry(handle, L, om.ctypes.data, ptr(ed), ptr(ce), nE, ptr(Ee), int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_pass) & 0xFFFFFFFF,
                 counts.ctypes.data, ptr(hist)))
     return int(counts[0]), int(counts[1]), counts[2:].copy(), hist
+
+
+def _phase_layered(entry, handle, laws, cum, edges, center, c, seed, n_pass):
+    """One call of pcl_step_phase_layered / pcl_group_step_phase_layered: (scattered, redirected, by_layer int64[L'], by_law
+    int64[M]).  ``laws``: a sequence of ``(kind, g, mu, F)`` -- kind "isotropic", "hg", "rayleigh", "table" or the header's numbers,
+    ``mu`` and ``F`` the K + 1 nodes and cumulative values of a table (None otherwise); ``cum``: the cumulative weights, one row
+    of M per layer; the edges go over as given (the library squares them, and makes the tables' slopes); ``n_pass``: the caller's
+    own pass counter (a Philox counter word)."""
+    M = len(laws)
+    kinds = np.array([int(PHASE_TABLE if k == "table" else PHASE_FUNCTIONS.get(k, k)) for k, _, _, _ in laws], dtype=np.int32)
+    g = np.array([float(x) for _, x, _, _ in laws], dtype=np.float64)
+    tabs = [(np.ascontiguousarray(m, dtype=np.float64).reshape(-1), np.ascontiguousarray(f, dtype=np.float64).reshape(-1))
+            for _, _, m, f in laws if m is not None]
+    if any(len(m) != len(f) for m, f in tabs):
+        raise ValueError("a table's mu and F must hold the same number of nodes")
+    n_bins = np.zeros(M, dtype=np.int32)
+    n_bins[[j for j, law in enumerate(laws) if law[2] is not None]] = [len(m) - 1 for m, _ in tabs]
+    mu = np.concatenate([m for m, _ in tabs]) if tabs else None
+    F = np.concatenate([f for _, f in tabs]) if tabs else None
+    ed = None if edges is None else np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+    L = 0 if ed is None else len(ed) - 1
+    rows = max(L, 1)
+    cu = np.ascontiguousarray(cum, dtype=np.float64).reshape(-1)
+    if len(cu) != rows * M:
+        raise ValueError("cum holds %d values for %d layers of %d laws" % (len(cu), rows, M))
+    ce = None if center is None else np.ascontiguousarray(center, dtype=np.float64).reshape(3)
+    counts = np.zeros(2 + rows + M, dtype=np.int64)
+    ptr = lambda a: None if a is None else a.ctypes.data                                                       # noqa: E731
+    check(entry(handle, M, kinds.ctypes.data, g.ctypes.data, n_bins.ctypes.data, ptr(mu), ptr(F), L, cu.ctypes.data, ptr(ed), ptr(ce),
+                float(c), int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_pass) & 0xFFFFFFFF, counts.ctypes.data))
+    return int(counts[0]), int(counts[1]), counts[2:2 + rows].copy(), counts[2 + rows:].copy()
 
 
 class SourceStruct(ctypes.Structure):
@@ -969,6 +1004,13 @@ class Device:
         absorbed, absorbed_by_layer int64[L'], E_hist int64[L', B_E] | None)``.  AbsorptionStep."""
         return _absorb(self.lib.pcl_step_absorb_scattered, self.ctx, omega0, edges, center, E_edges, seed, n_pass)
 
+    def phase_layered(self, laws, cum, edges=None, center=None, c=0.0, seed=0, n_pass=0):
+        """The photons the scatter step of this pass has hit get a direction about the one they had before, drawn from a law
+        that the radial layer they stand in chooses: ``laws`` are ``(kind, g, mu, F)``, row ``b`` of ``cum`` the cumulative
+        weights of the laws in layer ``b`` (pcl_step_phase_layered).  ``(scattered, redirected, by_layer int64[L'], by_law
+        int64[M])``.  LayeredPhaseStep."""
+        return _phase_layered(self.lib.pcl_step_phase_layered, self.ctx, laws, cum, edges, center, c, seed, n_pass)
+
 
 class DeviceGroup:
     """``pcl_group_*``: several contexts in one process, sharded by global index, behind the C ABI (the shim owns the
@@ -1080,6 +1122,10 @@ class DeviceGroup:
     def absorb_scattered(self, omega0, edges=None, center=None, E_edges=None, seed=0, n_pass=0):
         """``Device.absorb_scattered`` on every context of the group, the tallies summed (pcl_group_step_absorb_scattered)."""
         return _absorb(self.lib.pcl_group_step_absorb_scattered, self.g, omega0, edges, center, E_edges, seed, n_pass)
+
+    def phase_layered(self, laws, cum, edges=None, center=None, c=0.0, seed=0, n_pass=0):
+        """``Device.phase_layered`` on every context of the group, the tallies summed (pcl_group_step_phase_layered)."""
+        return _phase_layered(self.lib.pcl_group_step_phase_layered, self.g, laws, cum, edges, center, c, seed, n_pass)
 
     def download(self, field, n=None, offset=0, dtype=None):
         n = self.count - offset if n is None else n

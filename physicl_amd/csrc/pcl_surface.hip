@@ -69,6 +69,23 @@
 //   inside iff e2_0 <= q <= e2_L (NaN: false);  b = the bin of q in e2 = e*e: [e2_b, e2_(b+1)), the last one closed
 //   inside and omega0_b < 1:  u = u53(w0, w1) of counter (id_lo, id_hi, pass, 12);  absorbed iff not (u < omega0_b)
 //   absorbed:  v_k = 0;  dv_k = 0       (NOT the ground's dv = -v_old: a later sweep of this pass must see "did not scatter")
+//
+// Phase functions by layer (LayeredPhaseStep): the phase function's sweep with the absorber's layer search in front of the draw.
+// Each radial layer mixes up to eight laws -- isotropic, Henyey-Greenstein, Rayleigh, or a tabulated piecewise-constant density --
+// and a photon scattered inside a layer draws its law from the layer's weights, then its angle from the law.
+//
+//   k_phase_layered<T>     k_phase_redirect's sweep of the three dv rows; a scattered lane loads v and, with layers, r, and looks q
+//                          up in the squared edges.  Lanes inside a layer choose a law (one more Philox block, counter word 13, only
+//                          where the layer's row of weights is not one-hot), draw mu by that law -- a table by a binary search of
+//                          its cumulative values and one multiply-add -- and turn about the old direction as k_phase_redirect does.
+//                          All tables (cumulative weights, squared edges, g, and mu, F and the slopes of the tabulated laws) sit in
+//                          dynamic LDS in front of the workgroup-private uint32 cells [scattered, re-directed | by layer | by law].
+//
+// Operation order (what light._layered_phase_redirect restates with numpy):
+//   scattered iff a photon, dv != 0 and 0 < oo < inf (o, oo as above);  b: the absorber's layer of q (no layers: 0);  outside: counted
+//   as scattered, not written;  inside:  law j = the first with u_s < C[b][j], u_s = u53(w0, w1) of counter (id_lo, id_hi, pass, 13)
+//   isotropic, hg, rayleigh: the lines above, with the blocks 10 and 11;  table: k = the bin of u_a in F;
+//   mu = min(max(mu_k + (u_a - F_k)*s_k, mu_k), mu_(k+1)),  s_k = (mu_(k+1) - mu_k) / (F_(k+1) - F_k) made on the host;  then as above
 #include "pcl_sweep.h"
 
 #include "pcl_device.h" // (after the HIP runtime and the ABI's header, which pcl_sweep.h brings)
@@ -360,6 +377,147 @@ __global__ void __launch_bounds__(kBlock) k_absorb_scattered(absorb_args<T> a) {
         if (s_cnt[k]) atomicAdd(&a.out[k], (unsigned long long)s_cnt[k]);
 }
 
+// The counter word of the draw that chooses a law (the header lists who uses which word: 13 is this kernel's alone).
+constexpr uint32_t kLawWord = 13;
+
+template <typename T>
+struct lphase_args {
+    const T *r[3];
+    T *v[3], *dv[3];
+    const unsigned char *kind;   // NULL: every particle is a photon
+    const int64_t *ids;          // NULL: the id of slot i is id_base + i
+    const double *tables;        // C (L' x M) | e*e of the layer edges (L + 1, if L) | g (M) | mu, F, s (n_nodes each) | the laws' ints
+    unsigned long long *out;     // scattered, re-directed | by layer [L'] | by law [M]; device, zeroed by the entry point
+    int64_t N, ts, id_base;      // particles, tile stride of the slab (elements), id of slot 0
+    int tile_log;                // log2 of the tile length
+    int n_layers, n_laws;        // L (0: one row of C everywhere, L' = 1), M
+    int n_nodes;                 // the nodes of all tables, K + 1 each (0 without a table)
+    double c[3], speed;
+    uint32_t k0, k1, pass;       // Philox key (seed_lo, seed_hi), the step's own pass counter
+};
+
+template <typename T>
+__global__ void __launch_bounds__(kBlock) k_phase_layered(lphase_args<T> a) {
+    extern __shared__ double s_mem[];                                  // tables | scattered, re-directed | by layer | by law
+    const int L = a.n_layers, Lp = L > 0 ? L : 1, M = a.n_laws, Tn = a.n_nodes;
+    const int n_dbl = Lp * M + (L ? L + 1 : 0) + M + 3 * Tn;
+    const int n_tab = n_dbl + (3 * M + 1) / 2;                         // three ints per law, packed behind the doubles
+    const int n_cells = 2 + Lp + M;
+    const double *s_C = s_mem;
+    const double *s_e2 = s_C + Lp * M;
+    const double *s_g = s_e2 + (L ? L + 1 : 0);
+    const double *s_mu = s_g + M;
+    const double *s_F = s_mu + Tn;
+    const double *s_s = s_F + Tn;
+    const int *s_kind = reinterpret_cast<const int *>(s_mem + n_dbl);  // PCL_PHASE_* of law j
+    const int *s_off = s_kind + M;                                     // a table's first node in mu, F and s
+    const int *s_K = s_off + M;                                        // a table's bins
+    uint32_t *s_cnt = reinterpret_cast<uint32_t *>(s_mem + n_tab);
+    uint32_t *s_lay = s_cnt + 2;
+    uint32_t *s_law = s_lay + Lp;
+    for (int k = threadIdx.x; k < n_tab; k += kBlock) s_mem[k] = a.tables[k];
+    for (int k = threadIdx.x; k < n_cells; k += kBlock) s_cnt[k] = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    // whole waves run the same number of trips (the ballots below need every lane of the wave inside the loop)
+    const int64_t n_round = (a.N + 63) / 64 * 64;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n_round; i += stride) {
+        const bool in = i < a.N;
+        const int64_t ti = tile_index(i, a.tile_log, a.ts);
+        double d[3] = {0.0, 0.0, 0.0}, o[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            if (in) d[k] = (double)a.dv[k][ti];                         // fp32 widens exactly
+        // scattered in this pass: the rule of k_phase_redirect, the old velocity's length included
+        bool go = in && (d[0] != 0.0 || d[1] != 0.0 || d[2] != 0.0);
+        if (go && a.kind) go = a.kind[i] != 0;
+        if (go) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) o[k] = __dsub_rn((double)a.v[k][ti], d[k]);      // the velocity before the scatter
+        }
+        const double oo = dot3(o, o);
+        go = go && oo > 0.0 && oo < INFINITY;
+        int b = go && L == 0 ? 0 : -1;                                  // the layer; -1: outside every layer, left as the scatter step left it
+        if (go && L > 0) {
+            double x[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) x[k] = __dsub_rn((double)a.r[k][ti], a.c[k]);
+            const double q = dot3(x, x);
+            if (q >= s_e2[0] && q <= s_e2[L]) b = bin_of(s_e2, L, q);   // NaN: in no layer
+        }
+        const bool turn = b >= 0;
+        const uint32_t n_go = (uint32_t)__popcll(__ballot(go)), n_turn = (uint32_t)__popcll(__ballot(turn));
+        if (lane == 0 && n_go) atomicAdd(&s_cnt[0], n_go);
+        if (lane == 0 && n_turn) {
+            atomicAdd(&s_cnt[1], n_turn);
+            if (Lp == 1) atomicAdd(&s_lay[0], n_turn);                  // one layer, one law: the wave's count, not a lane's
+            if (M == 1) atomicAdd(&s_law[0], n_turn);
+        }
+        if (!turn) continue;    // lanes that are left alone wait at the loop's head: no ballot below this line
+        const uint64_t id = (uint64_t)(a.ids ? a.ids[i] : a.id_base + i);
+        int j = 0;
+        if (M > 1) {
+            const double *row = s_C + b * M;                            // cumulative, ends in 1: the first j with u_s < row[j]
+            while (j < M - 1 && !(row[j] > 0.0)) ++j;                   // (u_s >= 0: a law without weight is never the first)
+            if (row[j] < 1.0) {                                         // a one-hot row draws nothing
+                const pcl_u32x4 ws = pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, kLawWord, a.k0, a.k1);
+                const double u_s = pcl_u53(ws.x, ws.y);
+                while (j < M - 1 && !(u_s < row[j])) ++j;
+            }
+            atomicAdd(&s_law[j], 1u);
+        }
+        if (Lp > 1) atomicAdd(&s_lay[b], 1u);
+        const double on = __dsqrt_rn(oo);
+        double w[3], dir[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) w[k] = __ddiv_rn(o[k], on);
+        const pcl_u32x4 wa = pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, 10u, a.k0, a.k1);
+        const double u_a = pcl_u53(wa.x, wa.y), u_b = pcl_u53(wa.z, wa.w);
+        const int law = s_kind[j];
+        const double g = s_g[j];
+        double mu = __dsub_rn(1.0, __dmul_rn(2.0, u_a));                                             // uniform on the sphere
+        if (law == PCL_PHASE_HG && g != 0.0) {                                                       // the lines of k_phase_redirect
+            const double gg = __dmul_rn(g, g), g2 = __dmul_rn(2.0, g);
+            const double q = __ddiv_rn(__dsub_rn(1.0, gg), __dadd_rn(__dsub_rn(1.0, g), __dmul_rn(g2, u_a)));
+            mu = fmin(fmax(__ddiv_rn(__dsub_rn(__dadd_rn(1.0, gg), __dmul_rn(q, q)), g2), -1.0), 1.0);
+        } else if (law == PCL_PHASE_RAYLEIGH) {
+            const double s4 = __dmul_rn(u_a, 4.0), jq = floor(s4);
+            const double gq = __dsub_rn(__dmul_rn(2.0, __dsub_rn(s4, jq)), 1.0);
+            mu = gq;
+            if (jq == 3.0) {                                            // one lane in four: the 3/2 mu^2 part
+                const pcl_u32x4 wb = pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, 11u, a.k0, a.k1);
+                mu = copysign(fmax(fmax(fabs(gq), pcl_u53(wb.x, wb.y)), pcl_u53(wb.z, wb.w)), gq);
+            }
+        } else if (law == PCL_PHASE_TABLE) {                            // the inverse of a piecewise linear F: 0 <= u_a < 1 is inside
+            const int off = s_off[j];
+            const int kb = off + bin_of(s_F + off, s_K[j], u_a);
+            const double lo = s_mu[kb], hi = s_mu[kb + 1];
+            mu = fmin(fmax(__dadd_rn(lo, __dmul_rn(__dsub_rn(u_a, s_F[kb]), s_s[kb])), lo), hi);
+        }
+        const double s = __dsqrt_rn(__dmul_rn(__dsub_rn(1.0, mu), __dadd_rn(1.0, mu)));
+        double sn, cs;
+        pcl_sincos_2pi(__dmul_rn(__dmul_rn(u_b, 2.0), PCL_PI), &sn, &cs);                            // the scatter step's angle
+        const double sc = __dmul_rn(s, cs), ss = __dmul_rn(s, sn);
+        const double sg = copysign(1.0, w[2]);                                                       // the frame of k_surface_reflect
+        const double aa = __ddiv_rn(-1.0, __dadd_rn(sg, w[2]));
+        const double bb = __dmul_rn(__dmul_rn(w[0], w[1]), aa), sw0 = __dmul_rn(sg, w[0]);
+        const double e1[3] = {__dadd_rn(1.0, __dmul_rn(__dmul_rn(sw0, w[0]), aa)), __dmul_rn(sg, bb), -sw0};
+        const double e2[3] = {bb, __dadd_rn(sg, __dmul_rn(__dmul_rn(w[1], w[1]), aa)), -w[1]};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            dir[k] = __dadd_rn(__dadd_rn(__dmul_rn(sc, e1[k]), __dmul_rn(ss, e2[k])), __dmul_rn(mu, w[k]));
+            const double vk = __dmul_rn(a.speed, dir[k]);
+            a.v[k][ti] = (T)vk;
+            a.dv[k][ti] = (T)__dsub_rn(vk, o[k]);
+        }
+    }
+    __syncthreads();
+    // pcl_sweep::flush_cells, written out, for the reason given in k_absorb_scattered: the count is not a literal
+    for (int k = threadIdx.x; k < n_cells; k += kBlock)
+        if (s_cnt[k]) atomicAdd(&a.out[k], (unsigned long long)s_cnt[k]);
+}
+
 struct surface_spec { // a call's arguments, checked
     double c[3] = {0.0, 0.0, 0.0};
     double R2 = 0.0, albedo = 1.0, speed = 0.0;
@@ -638,6 +796,158 @@ int group_absorb_scattered(pcl_group *group, int n_layers, const double *omega0_
     return PCL_OK;
 }
 
+struct lphase_spec { // a call's arguments, checked; what the kernel reads
+    int n_layers = 0, n_laws = 0, n_nodes = 0;
+    double c[3] = {0.0, 0.0, 0.0};
+    double speed = 0.0;
+    std::vector<double> tables; // C | e*e | g | mu | F | s | the laws' ints
+    int rows() const { return n_layers > 0 ? n_layers : 1; }
+    size_t cells() const { return (size_t)2 + (size_t)rows() + (size_t)n_laws; }
+    size_t lds() const { return tables.size() * sizeof(double) + cells() * sizeof(uint32_t); }
+};
+
+// Everything PCL_ERR_ARG stands for except the NULL context; nothing is launched or written before this has passed.
+bool check_lphase(int n_laws, const int *kinds, const double *g, const int *n_bins, const double *mu, const double *F, int n_layers,
+                  const double *cum, const double *edges, const double *center, double c, const int64_t *counts_out, lphase_spec &s) {
+    if (!kinds || !cum || !counts_out || n_laws < 1 || n_laws > PCL_LPHASE_MAX_LAWS) return false;
+    if (n_layers < 0 || n_layers > PCL_LPHASE_MAX_LAYERS || !std::isfinite(c)) return false;
+    s.n_layers = n_layers; s.n_laws = n_laws; s.speed = c;
+    const int M = n_laws;
+    for (int b = 0; b < s.rows(); ++b) {                                // a row of C: cumulative, from >= 0 up to exactly 1
+        double prev = 0.0;
+        for (int j = 0; j < M; ++j) {
+            const double x = cum[(size_t)b * M + j];
+            if (!(x >= prev && x <= 1.0)) return false;                 // (NaN as well)
+            s.tables.push_back(prev = x);
+        }
+        if (prev != 1.0) return false;
+    }
+    if (n_layers > 0 && (!edges || !check_edges(edges, n_layers, kEdgeSquare, &s.tables))) return false;
+    std::vector<int> ints((size_t)3 * M, 0);                            // kind | first node | bins
+    int64_t total_bins = 0;
+    for (int j = 0; j < M; ++j) {
+        const int kind = kinds[j];
+        double gj = 0.0;
+        if (kind == PCL_PHASE_HG) {
+            if (!g || !(std::isfinite(g[j]) && std::fabs(g[j]) < 1.0)) return false;
+            gj = g[j];
+        } else if (kind == PCL_PHASE_TABLE) {
+            if (!n_bins || !mu || !F || n_bins[j] < 1 || n_bins[j] > PCL_LPHASE_MAX_NODES) return false;
+            total_bins += n_bins[j];
+        } else if (kind != PCL_PHASE_ISOTROPIC && kind != PCL_PHASE_RAYLEIGH) {
+            return false;
+        }
+        ints[(size_t)j] = kind;
+        s.tables.push_back(gj);
+    }
+    if (total_bins > PCL_LPHASE_MAX_TOTAL_NODES) return false;
+    std::vector<double> nodes, cumul, slope;
+    for (int j = 0; j < M; ++j) {
+        if (kinds[j] != PCL_PHASE_TABLE) continue;
+        const int K = n_bins[j];
+        const size_t at = nodes.size();                                 // the tables' nodes follow one another, in the order of the laws
+        ints[(size_t)M + j] = (int)at;
+        ints[(size_t)2 * M + j] = K;
+        const double *m = mu + at, *f = F + at;
+        if (m[0] != -1.0 || m[K] != 1.0 || f[0] != 0.0 || f[K] != 1.0) return false;
+        for (int k = 0; k <= K; ++k) {
+            if (k > 0 && (!(m[k] > m[k - 1]) || !(f[k] > f[k - 1]))) return false;       // (NaN as well)
+            nodes.push_back(m[k]);
+            cumul.push_back(f[k]);
+            const double sl = k < K ? (m[k + 1] - m[k]) / (f[k + 1] - f[k]) : 0.0;       // one rounding each; the last node has no bin
+            if (!std::isfinite(sl)) return false;
+            slope.push_back(sl);
+        }
+    }
+    s.n_nodes = (int)nodes.size();
+    s.tables.insert(s.tables.end(), nodes.begin(), nodes.end());
+    s.tables.insert(s.tables.end(), cumul.begin(), cumul.end());
+    s.tables.insert(s.tables.end(), slope.begin(), slope.end());
+    const size_t n_dbl = s.tables.size();
+    s.tables.resize(n_dbl + ((size_t)3 * M + 1) / 2, 0.0);
+    memcpy(s.tables.data() + n_dbl, ints.data(), ints.size() * sizeof(int));
+    if (s.lds() >= (size_t)64 * 1024) return false;                    // the workgroup's tables and cells stay below 64 KiB of LDS
+    if (center)
+        for (int k = 0; k < 3; ++k) {
+            if (!std::isfinite(center[k])) return false;
+            s.c[k] = center[k];
+        }
+    return true;
+}
+
+template <typename T>
+int launch_lphase(pcl_ctx *ctx, const store_view &v, const lphase_spec &s, uint64_t seed, uint32_t pass, int64_t id_base,
+                  const int64_t *ids, const unsigned char *kind, const double *tables_dev, unsigned long long *out_dev) {
+    lphase_args<T> a{};
+    for (int k = 0; k < 3; ++k) {
+        void *r = nullptr, *vel = nullptr, *dv = nullptr;
+        if (s.n_layers > 0) PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_R0 + k, &r));
+        PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_V0 + k, &vel));
+        PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_DV0 + k, &dv));
+        a.r[k] = static_cast<const T *>(r); a.v[k] = static_cast<T *>(vel); a.dv[k] = static_cast<T *>(dv);
+        a.c[k] = s.c[k];
+    }
+    a.kind = kind; a.ids = ids; a.tables = tables_dev; a.out = out_dev;
+    a.N = v.N; a.ts = v.ts; a.id_base = id_base; a.tile_log = v.tile_log;
+    a.n_layers = s.n_layers; a.n_laws = s.n_laws; a.n_nodes = s.n_nodes; a.speed = s.speed;
+    a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32); a.pass = pass;
+    const size_t lds = s.lds();                                         // what this call uses: a few hundred bytes without a table
+    const int64_t grid = balanced_grid(v.N, v.n_cu, resident_per_cu(lds));
+    hipLaunchKernelGGL(k_phase_layered<T>, dim3((unsigned)grid), dim3(kBlock), lds, v.stream, a);
+    return hipGetLastError() == hipSuccess ? PCL_OK : PCL_ERR_HIP;
+}
+
+int phase_layered(pcl_ctx *ctx, int n_laws, const int *kinds, const double *g, const int *n_bins, const double *mu, const double *F,
+                  int n_layers, const double *cum, const double *edges, const double *center, double c, uint64_t seed, uint32_t pass,
+                  int64_t *counts_out_host) {
+    lphase_spec s;
+    if (!ctx || !check_lphase(n_laws, kinds, g, n_bins, mu, F, n_layers, cum, edges, center, c, counts_out_host, s)) return bad_argument(ctx);
+    store_view v;                                                       // E is never asked for, as in phase_redirect
+    PCL_SWEEP_TRY(open_store(ctx, PCL_DV0, &v));
+    const size_t cells = s.cells();
+    memset(counts_out_host, 0, cells * sizeof(int64_t));
+    if (v.N <= 0) return PCL_OK;
+    std::vector<uint8_t> kind_host;                                     // a store that is not uniform: as surface_reflect
+    std::vector<int64_t> ids_host;
+    bool mixed = false;
+    int64_t id_base = 0;
+    PCL_SWEEP_TRY(kind_bytes(ctx, v.N, kind_host, &mixed));
+    PCL_SWEEP_TRY(id_words(ctx, v.N, ids_host, &id_base));
+    const size_t out_bytes = cells * sizeof(uint64_t), tab_bytes = s.tables.size() * sizeof(double);
+    const size_t id_bytes = ids_host.size() * sizeof(int64_t);
+    dev_block blk(ctx);
+    PCL_SWEEP_TRY(stage(blk, v.stream, out_bytes, s.tables.data(), tab_bytes, kind_host, ids_host));
+    char *base = static_cast<char *>(blk.p);
+    const double *tables_dev = reinterpret_cast<const double *>(base + out_bytes);
+    const int64_t *ids = id_bytes ? reinterpret_cast<const int64_t *>(base + out_bytes + tab_bytes) : nullptr;
+    const unsigned char *kind = mixed ? reinterpret_cast<const unsigned char *>(base + out_bytes + tab_bytes + id_bytes) : nullptr;
+    unsigned long long *out_dev = reinterpret_cast<unsigned long long *>(base);
+    PCL_SWEEP_TRY(v.dtype == PCL_DTYPE_F64 ? launch_lphase<double>(ctx, v, s, seed, pass, id_base, ids, kind, tables_dev, out_dev)
+                                           : launch_lphase<float>(ctx, v, s, seed, pass, id_base, ids, kind, tables_dev, out_dev));
+    return pcl_d2h(ctx, counts_out_host, base, (int64_t)out_bytes);    // the call's one synchronisation (a count is below 2^63)
+}
+
+int group_phase_layered(pcl_group *group, int n_laws, const int *kinds, const double *g, const int *n_bins, const double *mu,
+                        const double *F, int n_layers, const double *cum, const double *edges, const double *center, double c,
+                        uint64_t seed, uint32_t pass, int64_t *counts_out_host) {
+    std::vector<pcl_ctx *> ctx;
+    PCL_SWEEP_TRY(shards_of(group, ctx));
+    const int n = (int)ctx.size();
+    lphase_spec s;
+    if (n < 1 || !check_lphase(n_laws, kinds, g, n_bins, mu, F, n_layers, cum, edges, center, c, counts_out_host, s))
+        return bad_argument(n > 0 ? ctx[0] : nullptr);
+    const size_t cells = s.cells();
+    std::vector<std::vector<int64_t>> part((size_t)n, std::vector<int64_t>(cells, 0));
+    PCL_SWEEP_TRY(for_each_shard(ctx, [&](int sh, pcl_ctx *one) {
+        return pcl_step_phase_layered(one, n_laws, kinds, g, n_bins, mu, F, n_layers, cum, edges, center, c, seed, pass,
+                                      part[(size_t)sh].data());
+    }));
+    memset(counts_out_host, 0, cells * sizeof(int64_t));
+    for (int sh = 0; sh < n; ++sh)
+        for (size_t k = 0; k < cells; ++k) counts_out_host[k] += part[(size_t)sh][k];
+    return PCL_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -676,6 +986,25 @@ int pcl_group_step_absorb_scattered(pcl_group *group, int n_layers, const double
     return guarded([&] {
         return group_absorb_scattered(group, n_layers, omega0_host, edges_host, center_host, n_E_bins, E_edges_host, seed, pass,
                                       counts_out_host, E_hist_out_host);
+    });
+}
+
+int pcl_step_phase_layered(pcl_ctx *ctx, int n_laws, const int *kinds_host, const double *g_host, const int *n_bins_host,
+                           const double *mu_host, const double *F_host, int n_layers, const double *cum_host, const double *edges_host,
+                           const double *center_host, double c, uint64_t seed, uint32_t pass, int64_t *counts_out_host) {
+    return guarded([&] {
+        return phase_layered(ctx, n_laws, kinds_host, g_host, n_bins_host, mu_host, F_host, n_layers, cum_host, edges_host, center_host, c,
+                             seed, pass, counts_out_host);
+    });
+}
+
+int pcl_group_step_phase_layered(pcl_group *group, int n_laws, const int *kinds_host, const double *g_host, const int *n_bins_host,
+                                 const double *mu_host, const double *F_host, int n_layers, const double *cum_host,
+                                 const double *edges_host, const double *center_host, double c, uint64_t seed, uint32_t pass,
+                                 int64_t *counts_out_host) {
+    return guarded([&] {
+        return group_phase_layered(group, n_laws, kinds_host, g_host, n_bins_host, mu_host, F_host, n_layers, cum_host, edges_host,
+                                   center_host, c, seed, pass, counts_out_host);
     });
 }
 

@@ -1177,6 +1177,273 @@ class AbsorptionStep(DeviceStep, MeasureStep):
     terminate = tally.TallyStep.terminate                # (a row holds arrays: written as the tally steps write theirs, as plain lists)
 
 
+# ---------------------------------------------------------------------------------------------- phase functions by layer
+def _check_table_law(j, mu_edges, p, max_bins):
+    """(mu, F) of the tabulated law ``laws[j]``: the K + 1 nodes and cumulative values as float64 arrays, or ValueError."""
+    try:
+        mu, p = np.array(mu_edges, dtype=np.float64), np.array(p, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("laws[%d]: a table's mu_edges and p must be sequences of numbers" % j) from None
+    if mu.ndim != 1 or len(mu) < 2:
+        raise ValueError("laws[%d]: a table's mu_edges must be a 1-D sequence of at least two values, got shape %r" % (j, mu.shape))
+    K = len(mu) - 1
+    if K > max_bins:
+        raise ValueError("laws[%d]: the table has %d bins, at most %d are supported" % (j, K, max_bins))
+    if not (np.all(np.isfinite(mu)) and np.all(np.diff(mu) > 0) and mu[0] == -1.0 and mu[-1] == 1.0):
+        raise ValueError("laws[%d]: a table's mu_edges must rise strictly from exactly -1.0 to exactly 1.0" % j)
+    if p.shape != (K,):
+        raise ValueError("laws[%d]: a table's p must hold one value per bin (%d), got shape %r" % (j, K, p.shape))
+    if not (np.all(np.isfinite(p)) and np.all(p > 0)):
+        raise ValueError("laws[%d]: a table's p must be finite and > 0 in every bin" % j)
+    with np.errstate(over="ignore", invalid="ignore"):
+        m = p * (mu[1:] - mu[:-1])
+        F = np.concatenate([[0.0], np.cumsum(m) / np.sum(m)])
+    F[-1] = 1.0
+    if not (np.all(np.isfinite(F)) and np.all(np.diff(F) > 0)):
+        raise ValueError("laws[%d]: the table's cumulative distribution is not strictly increasing in float64 (a bin of no weight "
+                         "beside its neighbours)" % j)
+    return np.ascontiguousarray(mu), np.ascontiguousarray(F)
+
+
+def _check_layered_phase(laws, weights, edges, center):
+    """(laws as ``(kind, g, mu, F)`` tuples -- mu and F the nodes and cumulative values of a table, None otherwise --, weights as a
+    float64 array [L'][M], their cumulative rows C, edges or None, centre) of a LayeredPhaseStep, or ValueError for everything
+    pcl_step_phase_layered would refuse."""
+    from ._hip import LPHASE_MAX_LAWS, LPHASE_MAX_LAYERS, LPHASE_MAX_NODES, LPHASE_MAX_TOTAL_NODES      # (the header's limits: one place)
+    if isinstance(laws, str) or not isinstance(laws, collections.abc.Sequence):
+        raise ValueError("laws must be a sequence of laws: 'isotropic', 'rayleigh', ('hg', g) or ('table', mu_edges, p)")
+    M = len(laws)
+    if not 1 <= M <= LPHASE_MAX_LAWS:
+        raise ValueError("laws must hold 1 to %d laws, got %d" % (LPHASE_MAX_LAWS, M))
+    out, total = [], 0
+    for j, law in enumerate(laws):
+        if isinstance(law, str) and law in ("isotropic", "rayleigh"):
+            out.append((law, 0.0, None, None))
+        elif isinstance(law, (tuple, list)) and len(law) == 2 and isinstance(law[0], str) and law[0] == "hg":
+            try:
+                g = float(np.asarray(law[1], dtype=np.float64).reshape(()))
+            except (TypeError, ValueError):
+                raise ValueError("laws[%d]: g must be a number" % j) from None
+            if not (np.isfinite(g) and abs(g) < 1.0):
+                raise ValueError("laws[%d]: g must be finite with |g| < 1, got %r" % (j, g))
+            out.append(("hg", g, None, None))
+        elif isinstance(law, (tuple, list)) and len(law) == 3 and isinstance(law[0], str) and law[0] == "table":
+            mu, F = _check_table_law(j, law[1], law[2], LPHASE_MAX_NODES)
+            total += len(mu) - 1
+            out.append(("table", 0.0, mu, F))
+        else:
+            raise ValueError("laws[%d] must be 'isotropic', 'rayleigh', ('hg', g) or ('table', mu_edges, p), got %r" % (j, law))
+    if total > LPHASE_MAX_TOTAL_NODES:
+        raise ValueError("the tables of laws have %d bins in total, at most %d are supported" % (total, LPHASE_MAX_TOTAL_NODES))
+    if edges is not None:
+        edges = tally.check_edges("edges", edges, LPHASE_MAX_LAYERS, "square")      # (the device compares q with e*e)
+    rows = 1 if edges is None else len(edges) - 1
+    if weights is None:
+        if M > 1:
+            raise ValueError("weights may be omitted only with one law, laws holds %d" % M)
+        w = np.ones((rows, 1), dtype=np.float64)
+    else:
+        try:
+            w = np.array(weights, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("weights must be numbers: one row per layer, one value per law") from None
+        if edges is None and w.shape == (M,):
+            w = w.reshape(1, M)
+        if w.shape != (rows, M):
+            raise ValueError("weights must have the shape [%d][%d] (layers, laws), got %r" % (rows, M, w.shape))
+    with np.errstate(over="ignore", invalid="ignore"):
+        cs = np.cumsum(w, axis=1)
+    if not (np.all(np.isfinite(w)) and np.all(w >= 0) and np.all(np.isfinite(cs)) and np.all(cs[:, -1] > 0)):
+        raise ValueError("weights must be finite and >= 0, with a positive sum in every row, got %r" % (weights,))
+    cum = cs / cs[:, -1:]
+    cum[:, -1] = 1.0
+    return out, np.ascontiguousarray(w), np.ascontiguousarray(cum), edges, tally.check_center(center)
+
+
+def _layered_phase_redirect(r, v, dv, photon, ids, laws, weights, edges, center, c, seed, n_pass, dtype=np.float64):
+    """What pcl_step_phase_layered makes of (n, 3) float64 positions, velocities and last velocity changes, who is a photon and the
+    particles' ids, with numpy -- every operation the device's operation in the device's order, one rounding each
+    (include/physicl_hip.h), and what is written rounded once to ``dtype``.  Everything but sin / cos of the azimuth (libm here, the
+    library's own on the device) is the device's bit for bit.  A dict: ``v, dv`` the new state (float64 arrays; rows that are not
+    re-directed are the arguments'), the boolean masks ``scattered`` (a photon with a non-zero dv and an old velocity whose length
+    can be worked with) and ``redirected`` (those of them inside a layer), per row ``layer`` and ``law`` (int64, -1 for a row that
+    is not re-directed), ``mu`` and ``w`` (NaN there), and the tallies ``by_layer`` (int64 [L']) and ``by_law`` (int64 [M])."""
+    laws, _, cum, edges, center = _check_layered_phase(laws, weights, edges, center)
+    return _layered_phase_apply(r, v, dv, photon, ids, laws, cum, edges, center, c, seed, n_pass, dtype)
+
+
+def _layered_phase_apply(r, v, dv, photon, ids, laws, cum, edges, center, c, seed, n_pass, dtype=np.float64):
+    """``_layered_phase_redirect`` behind its checks: ``laws`` and ``cum`` as ``_check_layered_phase`` returns them."""
+    r, v, dv = (np.array(a, dtype=np.float64).reshape(-1, 3) for a in (r, v, dv))
+    n = len(v)
+    M, rows = len(laws), len(cum)
+    c = np.float64(c)
+    with np.errstate(invalid="ignore", over="ignore"):
+        o_all = v - dv
+        oo = _dot3(o_all, o_all)
+        scattered = ((dv[:, 0] != 0) | (dv[:, 1] != 0) | (dv[:, 2] != 0)) & np.asarray(photon, dtype=bool).reshape(-1) & (oo > 0) & (oo < np.inf)
+        at = np.flatnonzero(scattered)
+        layer = np.full(n, -1, dtype=np.int64)
+        if edges is None:
+            layer[at] = 0
+        else:
+            e2 = edges * edges
+            d = r[at] - center
+            q = _dot3(d, d)
+            inside = (q >= e2[0]) & (q <= e2[-1])                                   # NaN: in no layer
+            layer[at[inside]] = np.clip(np.searchsorted(e2, q[inside], side="right") - 1, 0, rows - 1)   # the last layer is closed
+    go = layer >= 0
+    at = np.flatnonzero(go)
+    ids = np.asarray(ids).reshape(-1)[at]
+    b = layer[at]
+    pick = np.zeros(len(at), dtype=np.int64)
+    if M > 1:                                                  # the first law with u_s < C[b][j]: C does not decrease and ends in 1
+        u_s = _philox_block(ids, seed, n_pass, 13)[0]
+        pick = (cum[b] <= u_s[:, None]).sum(axis=1).astype(np.int64)
+    law = np.full(n, -1, dtype=np.int64)
+    law[at] = pick
+    out = {"scattered": scattered, "redirected": go, "layer": layer, "law": law, "mu": np.full(n, np.nan), "w": np.full((n, 3), np.nan),
+           "by_layer": np.bincount(b, minlength=rows).astype(np.int64), "by_law": np.bincount(pick, minlength=M).astype(np.int64)}
+    o = o_all[at]
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        w = o / np.sqrt(oo[at])[:, None]
+        u_a, u_b = _philox_block(ids, seed, n_pass, 10)
+        mu = 1.0 - 2.0 * u_a                                   # uniform on the sphere
+        for j, (kind, g, nodes, F) in enumerate(laws):
+            mine = np.flatnonzero(pick == j)
+            ua = u_a[mine]
+            if kind == "hg" and g != 0.0:
+                g = np.float64(g)
+                gg, g2 = g * g, 2.0 * g
+                q = (1.0 - gg) / ((1.0 - g) + g2 * ua)
+                mu[mine] = np.fmin(np.fmax(((1.0 + gg) - q * q) / g2, -1.0), 1.0)
+            elif kind == "rayleigh":
+                s4 = ua * 4.0
+                jq = np.floor(s4)
+                gq = 2.0 * (s4 - jq) - 1.0
+                part = jq == 3.0                               # one in four: the 3/2 mu^2 part of 3/8 (1 + mu^2)
+                u_c, u_d = _philox_block(ids[mine][part], seed, n_pass, 11)
+                gq[part] = np.copysign(np.fmax(np.fmax(np.abs(gq[part]), u_c), u_d), gq[part])
+                mu[mine] = gq
+            elif kind == "table":                              # the inverse of the piecewise linear F
+                K = len(nodes) - 1
+                slope = (nodes[1:] - nodes[:-1]) / (F[1:] - F[:-1])
+                k = np.clip(np.searchsorted(F, ua, side="right") - 1, 0, K - 1)
+                mu[mine] = np.fmin(np.fmax(nodes[k] + (ua - F[k]) * slope[k], nodes[k]), nodes[k + 1])
+        sn = np.sqrt((1.0 - mu) * (1.0 + mu))
+        psi = (u_b * 2.0) * np.pi
+        sc, ss = sn * np.cos(psi), sn * np.sin(psi)
+        w0, w1, w2 = w[:, 0], w[:, 1], w[:, 2]
+        sg = np.copysign(1.0, w2)                          # the frame of _surface_bounce, about w
+        aa = -1.0 / (sg + w2)
+        bb, sw0 = (w0 * w1) * aa, sg * w0
+        e1 = np.stack([1.0 + (sw0 * w0) * aa, sg * bb, -sw0], axis=1)
+        e2v = np.stack([bb, sg + (w1 * w1) * aa, -w1], axis=1)
+        direction = (sc[:, None] * e1 + ss[:, None] * e2v) + mu[:, None] * w
+        v_new = c * direction
+        dv_new = v_new - o
+    v[at], dv[at] = v_new.astype(dtype).astype(np.float64), dv_new.astype(dtype).astype(np.float64)
+    out["v"], out["dv"] = v, dv
+    out["mu"][at], out["w"][at] = mu, w
+    return out
+
+
+class LayeredPhaseStep(DeviceStep, MeasureStep):
+    """Phase functions by radial layer, mixed and tabulated (not in the reference).  ``PhaseFunctionStep`` applies one law to the
+    whole of space; this step, placed where a ``PhaseFunctionStep`` would stand -- directly BEHIND the scatter step of a pass
+    (measures may stand between), before or behind an ``AbsorptionStep`` --, lets the law depend on where the photon stands: a
+    Rayleigh atmosphere with a cloud or aerosol layer of another law inside it.
+
+    * ``laws``: 1 to 8 laws, each ``"isotropic"``, ``"rayleigh"``, ``("hg", g)`` with ``|g| < 1``, or ``("table", mu_edges, p)``:
+      a piecewise-constant phase function on ``K`` bins (``1 <= K <= 1024``, 2048 bins over all tables of a step) whose ``K + 1``
+      edges rise strictly from exactly -1.0 to exactly 1.0, ``p`` the relative density per bin (finite, > 0; the step normalises
+      it).  A table whose cumulative distribution is not strictly increasing in float64 is refused.
+    * ``edges``: None -- one layer that holds everything -- or ``L + 1`` radii about ``center`` by ``AbsorptionStep``'s rule in
+      every detail (at most 64 layers; layer ``b`` holds a photon iff ``e_b**2 <= q < e_(b+1)**2``, the last layer closed, no
+      square root).
+    * ``weights``: shape ``[L][M]`` (``[M]`` is accepted without ``edges``), finite and >= 0 with a positive sum in every row: row
+      ``b`` is the probability with which an interaction in layer ``b`` uses each law.  May be omitted with one law.
+
+    "Scattered in this pass" is ``PhaseFunctionStep``'s rule: a photon with ``dv != 0`` whose old velocity ``o = v - dv`` has
+    ``0 < o.o < inf``.  Such a photon inside a layer is re-directed about ``o/|o|``; outside every layer (or with a NaN in ``q``) it
+    keeps the direction the scatter step gave it and is counted as scattered, not as re-directed.  Plain ``Object``s are never
+    touched; ``r``, ``dr``, ``E``, ids and kinds are left alone.  After each run ``self.scattered`` and ``self.redirected`` hold the
+    pass's counts and ``self.by_layer`` (int64 ``[L]``, ``[1]`` without edges) and ``self.by_law`` (int64 ``[M]``) the re-directed
+    photons by layer and by law, all global over shards and ranks; ``self.data`` gains the row ``[t, scattered, redirected, by_layer,
+    by_law]`` and ``out_fn`` takes the rows at the end.  The arithmetic is written out in include/physicl_hip.h
+    (pcl_step_phase_layered); ``_layered_phase_redirect`` restates it with numpy.
+
+    The angle is drawn from the Philox blocks ``PhaseFunctionStep`` draws from (counter words 10 and 11), the law from a block of
+    this step's own (word 13), keyed by ``sim.seed``, the photon's id and the step's own pass counter: with one law and no edges
+    the step leaves the store bit for bit as ``PhaseFunctionStep`` with that law leaves it.  Sharing the words means A PASS HOLDS
+    ONE PHASE STEP: at its first run the step raises ``ValueError`` if the simulation's steps hold another ``PhaseFunctionStep`` or
+    ``LayeredPhaseStep``.  Under the reference's Python semantics (``cl_on=False``) a hit leaves ``dv = v_old``, the rule above does
+    not hold, and the step raises ``ValueError``.
+
+    One launch per light step: the K-passes-per-launch kernels cannot re-direct a photon between two of their passes, and
+    ``sim.launch_note`` says so.  On host-resident objects (``step.run(sim)`` outside a device loop) the same state is made with
+    numpy, the ids being the places in the object list."""
+    _fuse_role = None
+    _NOTE = "one launch per light step: a LayeredPhaseStep re-directs the scattered photons behind every pass, which the " \
+            "K-passes-per-launch kernels cannot carry"
+
+    def __init__(self, laws, weights=None, edges=None, center=(0, 0, 0), out_fn=None):
+        MeasureStep.__init__(self, out_fn)
+        self._laws, self.weights, self.cum, self.edges, self.center = _check_layered_phase(laws, weights, edges, center)
+        self.laws = [k if k in ("isotropic", "rayleigh") else ("hg", g) if k == "hg" else ("table", mu, F) for k, g, mu, F in self._laws]
+        self.scattered = self.redirected = 0
+        self.by_layer = np.zeros(len(self.cum), dtype=np.int64)
+        self.by_law = np.zeros(len(self._laws), dtype=np.int64)
+        self._pass = 0                                   # the step's own Philox counter word: one per run
+
+    def _record_pass(self, sim, scattered, redirected, by_layer, by_law):
+        self.scattered, self.redirected = int(scattered), int(redirected)
+        self.by_layer, self.by_law = np.array(by_layer, dtype=np.int64), np.array(by_law, dtype=np.int64)
+        self.data.append(tally.object_row([tally._snap(sim.t), self.scattered, self.redirected, self.by_layer.copy(), self.by_law.copy()]))
+
+    def _refuse(self, sim):
+        if getattr(sim, "_py_semantics", None) is not None and sim._py_semantics():
+            raise ValueError("LayeredPhaseStep needs cl_on=True: under the reference's Python semantics a scattered photon is left "
+                             "with dv = v_old, not v' - v_old, so its direction before the scatter cannot be read off the store")
+        if self._pass == 0:                              # the words 10 and 11 are drawn from once per photon and pass
+            steps = getattr(sim, "steps", None) or {}
+            for other in (steps.values() if isinstance(steps, dict) else steps):
+                if other is not self and isinstance(other, (PhaseFunctionStep, LayeredPhaseStep)):
+                    raise ValueError("a pass holds one phase step: the simulation's steps hold a %s beside this LayeredPhaseStep, and "
+                                     "both would draw from the same Philox blocks" % type(other).__name__)
+
+    def _device_run(self, sim):
+        self._refuse(sim)
+        if getattr(sim, "launch_note", self._NOTE) is None and sim._k_wanted() > 1:      # (a device run only: the host path says nothing)
+            sim.launch_note = self._NOTE
+        self._pass += 1
+        scattered, redirected, by_layer, by_law = sim._dev.phase_layered(self._laws, self.cum, self.edges, self.center, _c_h_literals()[0],
+                                                                         sim.seed, self._pass)
+        sim._scattered = True                            # velocities were replaced on the device
+        # one payload (every rank issues it, also with an empty shard)
+        _, (both, by_layer, by_law) = tally.reduce_parts(sim, [np.array([scattered, redirected], dtype=np.int64), np.asarray(by_layer),
+                                                               np.asarray(by_law)])
+        self._record_pass(sim, both[0], both[1], by_layer, by_law)
+
+    def run(self, sim):
+        self._refuse(sim)
+        if getattr(sim, "_residency", None) == "host" and getattr(sim, "_batch", None) is None \
+                and (sim.comm is None or sim.comm.world == 1):
+            objs = list(sim.objects)
+            self._pass += 1
+            photon = np.array([type(o) is PhotonObject for o in objs], dtype=bool)
+            new = _layered_phase_apply(tally.vec3(objs, "r"), tally.vec3(objs, "v"), tally.vec3(objs, "dv"), photon, np.arange(len(objs)),
+                                       self._laws, self.cum, self.edges, self.center, _c_h_literals()[0], getattr(sim, "seed", 0), self._pass)
+            for k in np.flatnonzero(new["redirected"]).tolist():
+                o = objs[k]
+                o.v, o.dv = np.array(new["v"][k], dtype=np.double), np.array(new["dv"][k], dtype=np.double)   # plain arrays, as a scatter leaves them
+            self._record_pass(sim, new["scattered"].sum(), new["redirected"].sum(), new["by_layer"], new["by_law"])
+            return None
+        return DeviceStep.run(self, sim)
+
+    terminate = tally.TallyStep.terminate                # (a row holds arrays: written as the tally steps write theirs, as plain lists)
+
+
 def _DEFAULT_ID_INFO(x):
     """The reference's default ``lambda x: str(type(x))`` (light.py:438), recognised by identity.  The label goes into the trace
     table's first column: this package's own classes read as the reference's (``<class 'physicl.light.PhotonObject'>``, what a

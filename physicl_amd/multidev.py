@@ -288,6 +288,10 @@ class MultiDevice:
         return (sum(o[0] for o in outs), sum(o[1] for o in outs), self._sum([o[2] for o in outs]),
                 None if hists[0] is None else self._sum(hists))
 
+    def phase_layered(self, *a, **kw):
+        outs = self._each(lambda s: s.phase_layered(*a, **kw))
+        return (sum(o[0] for o in outs), sum(o[1] for o in outs), self._sum([o[2] for o in outs]), self._sum([o[3] for o in outs]))
+
     def plane_energies(self, plane, n_hint=None):
         return self._concat(self._each(lambda s: s.plane_energies(plane)))      # (a shard does not know its share of the hint)
 
