@@ -4,7 +4,7 @@ examples (n(r) = 2.5e25 m^-3 * exp(-(|r| - 6371 km) / 8.6 km)) with photons that
 
     python examples/point_source_atmosphere.py [n_photons] [passes] [--cone | --beam-down | --default] [--profile] [--shells]
                                                [--ground [ALBEDO]] [--phase rayleigh | hg:G | isotropic] [--omega0 W | W1,W2,...]
-                                               [--cloud LO,HI[,G]]
+                                               [--cloud LO,HI[,G]] [--recycle [TOP]]
 
 default: a point source at (6371 km, 0, 0) emitting isotropically; ``--cone``: a 0.3 rad cone pointing up (+x) from a 1 km disc;
 ``--beam-down``: a 10 km gaussian beam entering from 100 km above the surface along -x; ``--default``: the same step list from
@@ -32,6 +32,10 @@ printed beside the top-of-atmosphere and ground counts.
 function scatters by Rayleigh's law everywhere and, between the altitudes LO and HI, by a mixture of one part Rayleigh and nine
 parts Henyey-Greenstein with the mean cosine G (default 0.85).  One launch per light step; the photons re-directed per layer and
 per law are printed beside the shell counts.  Not together with ``--phase``: a pass holds one phase step.
+``--recycle [TOP]`` (an altitude in metres, default 100 km) makes the source a continuous one: a RecycleStep at the end of every pass
+gives the slots of the photons at rest (absorbed by the ground or the medium) and of those above TOP back to the source.  The
+population stays constant; the emission rate (photons recycled per pass) and the counts at rest and through the top are printed as
+they settle to the steady state.  One launch per light step.  Not with ``--default``: the step re-emits from a PhotonSource.
 """
 import os
 import sys
@@ -68,6 +72,16 @@ if "--cloud" in argv:
     if phase is not None:
         sys.exit("--cloud and --phase: a pass holds one phase step")
     cloud = (cloud[0], cloud[1], cloud[2] if len(cloud) == 3 else 0.85)
+recycle_top = None
+if "--recycle" in argv:
+    at = argv.index("--recycle")
+    recycle_top = 100e3
+    if at + 1 < len(argv) and not argv[at + 1].startswith("--"):
+        recycle_top = float(argv.pop(at + 1))
+    if not recycle_top > 0.0:
+        sys.exit("--recycle TOP: an altitude in metres above the ground")
+    if "--default" in argv:
+        sys.exit("--recycle needs a source: not with --default")
 CLOUD_WEIGHTS = [[1, 0], [0.1, 0.9], [1, 0]]                  # below the cloud, in it, above it: (Rayleigh, Henyey-Greenstein)
 args = [a for a in argv if not a.startswith("--")]
 n = int(float(args[0])) if len(args) > 0 else 100_000_000
@@ -113,7 +127,7 @@ def run(ground):
     sim.add_step(3, signs)
     shells = light.ScatterMeasureStep(None, True, [[R + 20e3, np.nan, np.nan], [np.nan, 0.0, np.nan]])   # 20 km up; the plane y = 0
     sim.add_step(4, shells)
-    profile = image = tally = floor = None
+    profile = image = tally = floor = lamp = None
     if "--profile" in sys.argv:                                # behind the last light step: the 32-pass launches are kept
         profile = light.PositionGridMeasureStep(None, ("r",), [PROFILE_RADII], every=32)
         image = light.PositionGridMeasureStep(None, ("y", "z"), [np.linspace(-300e3, 300e3, 129)] * 2, every=32, measure_n=False)
@@ -125,13 +139,16 @@ def run(ground):
     if ground is not None:                                     # last in the pass: the tally before it sees the incoming move
         floor = light.SurfaceReflectStep(R, albedo=ground)
         sim.add_step(8, floor)
+    if recycle_top is not None:                                # the very last: behind the ground
+        lamp = light.RecycleStep(source, top=R + recycle_top)
+        sim.add_step(9, lamp)
     sim.add_objs(light.generate_photons_bulk(n, min=light.E_from_wavelength(700e-9), max=light.E_from_wavelength(200e-9), seed=1234, source=source))
     sim.prepare()                                              # the photons are created now: run_time below is stepping only
     sim.start()
     sim.join()
     if sim.error is not None:
         raise sim.error
-    return sim, signs, shells, profile, image, tally, floor, angles, medium
+    return sim, signs, shells, profile, image, tally, floor, angles, medium, lamp
 
 
 bare_top = None
@@ -141,7 +158,7 @@ if albedo is not None and "--shells" in sys.argv:              # the same run wi
     print("without the ground: %d photons x %d steps in %.2f s" % (n, len(bare[0].ts), bare[0].run_time))
     bare[0].close(download=False)
     del bare
-sim, signs, shells, profile, image, tally, floor, angles, medium = run(albedo)
+sim, signs, shells, profile, image, tally, floor, angles, medium, lamp = run(albedo)
 steps = len(sim.ts)
 print("source:", source)
 print("%d photons x %d steps in %.2f s  ->  %.3g particle-steps/s" % (n, steps, sim.run_time, n * steps / sim.run_time))
@@ -187,3 +204,11 @@ if medium is not None:
     if tally is not None:
         print("  beside it: %d left through the top of the atmosphere (100 km)%s" % (
             int(sum(row[2][3] for row in tally.data)), "" if floor is None else ", %d absorbed by the ground" % sum(int(row[2]) for row in floor.data)))
+if lamp is not None:
+    rate = [int(row[1]) + int(row[2]) for row in lamp.data]
+    print("a continuous source (photons at rest or above %g km go back to it): %d re-emitted over %d passes, the population stays at %d" % (
+        recycle_top / 1e3, sum(rate), len(rate), int(signs.data[-1][1])))
+    every = max(len(rate) // 8, 1)
+    for k in range(every - 1, len(rate), every):                # the emission rate settling, pass by pass
+        row = lamp.data[k]
+        print("  pass %4d: emission rate %d per pass (%d at rest: the ground and the medium, %d through the top)" % (k + 1, rate[k], int(row[1]), int(row[2])))

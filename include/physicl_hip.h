@@ -809,6 +809,48 @@ int pcl_step_phase_layered(pcl_ctx *ctx, int n_laws, const int *kinds_host, cons
                            const double *edges_host, const double *center_host, double c, uint64_t seed, uint32_t pass,
                            int64_t *counts_out_host /* [2 + L' + M] */);
 
+/* A continuous source (RecycleStep): the last call of a pass, behind pcl_step_surface_reflect if there is one.  A photon the ground
+ * or the medium has absorbed stays in the store at rest, one that has left through the top of the atmosphere flies on for ever:
+ * this call gives the slots of both back to a photon source, in ONE sweep of the resident store.  The population stays constant and
+ * the store dense; ids and kinds are never written, nothing is removed.  All arithmetic is fp64, unfused, every operation rounded
+ * once, in the order written; an fp32 store's values are widened first (exact) and what is written is rounded once to the store's
+ * dtype.
+ *   rest   =  at_rest and v0 == 0 and v1 == 0 and v2 == 0                            (-0.0 counts as 0; a NaN in v: not at rest)
+ *   d = r - center;  q = (d0*d0 + d1*d1) + d2*d2;  top2 = top*top (made on the host)
+ *   gone   =  top > 0 (a top is given) and not rest and q > top2         (exactly on the sphere: not gone; NaN: not gone; inf: gone)
+ *   spent  =  the particle is a photon and (rest or gone)
+ * Plain Objects (kind 0) are never spent.  A particle that is not spent is not written at all.  The v rows are read only with
+ * at_rest, the r rows only with a top.  A spent photon is re-emitted by ``src`` with exactly the arithmetic written out above for
+ * pcl_store_apply_source -- mu per angular mode, s, psi, the frame e1, e2, d, rho and phi per spatial mode, the same sin / cos --
+ * from blocks of its own: key (seed_lo, seed_hi), u53 as there,
+ *   direction:  counter (id_lo, id_hi, pass, 14): u_a = u53(w0, w1), u_b = u53(w2, w3)      (a beam draws nothing: v = c*d)
+ *   position:   counter (id_lo, id_hi, pass, 15): u_c = u53(w0, w1), u_d = u53(w2, w3)      (a point draws nothing: r = origin)
+ *   dr = 0;  dv = 0                                                          (a newborn has not moved and has not scattered)
+ * and, unlike the fill, EVERY row r, v, dr, dv of a spent photon is written, for a beam and a point source too.
+ *   n_E > 0:    u = u53(w0, w1) of the counter (id_lo, id_hi, pass, 16);  E = grid_host[x] for the first x with cdf_host[x] >= u
+ *               -- the table form of pcl_store_fill_photons_table, found by a binary search: compares only, bit for bit restatable.
+ *   n_E == 0:   E is neither written nor asked for: a recycled photon keeps its energy.  Exact for a monochromatic source, or
+ *               wherever no sink depends on E.
+ * ``pass`` is the caller's own counter: a slot keeps its id, and every re-emission draws new numbers because ``pass`` moves.  The
+ * words 14, 15 and 16 are used by nothing else (scatter kernels 0 and 1, fill and source 2..5, pcl_step_surface_reflect 8 and 9,
+ * pcl_step_phase_redirect 10 and 11, pcl_step_absorb_scattered 12, pcl_step_phase_layered 13), so every other step draws what it drew,
+ * and a photon is re-emitted the same way however the run is sharded.
+ * ``c`` = the speed of light in code units.  ``top`` <= 0: no top.  center_host: 3 finite doubles, NULL = the origin.  cdf_host,
+ * grid_host: n_E doubles each, 0 <= n_E <= PCL_RECYCLE_MAX_BINS (the table sits in 16 KiB of LDS at the most); cdf non-decreasing,
+ * its last value exactly 1; grid finite.
+ * counts_out_host[0] = photons recycled because they were at rest, [1] = because they were beyond the top, by this call.
+ * A store that is not uniform costs the host traffic it costs pcl_step_surface_reflect.  PCL_ERR_ARG (NULL src or counts, unknown
+ * mode, non-finite frame / origin / c / centre, cos_half_angle outside [-1, 1] for a cone, radius negative or not finite for a disc /
+ * gaussian, top not finite or its square not finite, neither at_rest nor a top, n_E outside 0 .. PCL_RECYCLE_MAX_BINS, a NULL table
+ * with n_E > 0, a cdf that decreases or does not end in 1, a grid that is not finite) is returned before anything is launched or
+ * written; PCL_ERR_STATE without a store; an empty store answers zeros without a launch.  Host pointers; one device allocation per
+ * call, handed back on every way out; synchronises once, with the copy of the two counts.  pcl_last_error() is generic, as for
+ * pcl_step_surface_reflect, whose source file these two entry points share (physicl_amd/csrc/pcl_surface.hip). */
+#define PCL_RECYCLE_MAX_BINS 1024
+int pcl_step_recycle_spent(pcl_ctx *ctx, const pcl_source *src, double c, int at_rest, double top /* <= 0: none */,
+                           const double *center_host, int n_E, const double *cdf_host, const double *grid_host, uint64_t seed,
+                           uint32_t pass, int64_t *counts_out_host /* [2]: at rest, escaped */);
+
 /* ---- Device groups: several GPUs from ONE process ---------------------------------------------------------------
  * The reference is a single process with one simulation thread (physicl/__init__.py:400-432, 501-524); this is how
  * a host written against this ABI uses a node's GPUs the same way, without one process per GPU.  A group owns one
@@ -888,6 +930,11 @@ int pcl_group_step_phase_layered(pcl_group *group, int n_laws, const int *kinds_
                                  const double *mu_host, const double *F_host, int n_layers, const double *cum_host,
                                  const double *edges_host, const double *center_host, double c, uint64_t seed, uint32_t pass,
                                  int64_t *counts_out_host);
+/* pcl_step_recycle_spent on every shard (side by side), the two counts summed over the group's devices; the arguments are checked
+ * once for the group, before any shard is written (ids are global: the same photons are re-emitted the same way) */
+int pcl_group_step_recycle_spent(pcl_group *group, const pcl_source *src, double c, int at_rest, double top,
+                                 const double *center_host, int n_E, const double *cdf_host, const double *grid_host, uint64_t seed,
+                                 uint32_t pass, int64_t *counts_out_host);
 
 /* ---------------------------------------------------------------- the counters' collective (one process per GPU)
  * The path shards by global index with no data-path exchange; the only global quantities are the int64

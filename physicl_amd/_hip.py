@@ -32,6 +32,7 @@ ABSORB_MAX_LAYERS, ABSORB_MAX_BINS, ABSORB_MAX_CELLS = 64, 1024, 12288          
 PHASE_FUNCTIONS = {"isotropic": 0, "hg": 1, "rayleigh": 2}                   # PCL_PHASE_ISOTROPIC, PCL_PHASE_HG, PCL_PHASE_RAYLEIGH
 PHASE_TABLE = 3                                                              # PCL_PHASE_TABLE: a law of pcl_step_phase_layered only
 LPHASE_MAX_LAWS, LPHASE_MAX_LAYERS, LPHASE_MAX_NODES, LPHASE_MAX_TOTAL_NODES = 8, 64, 1024, 2048       # PCL_LPHASE_MAX_LAWS ...
+RECYCLE_MAX_BINS = 1024                                                      # PCL_RECYCLE_MAX_BINS: bins of a RecycleStep's spectrum
 PROF_NEWTON, PROF_SCATTER, PROF_DELETE_MASK, PROF_COMPACT, PROF_COUNTERS, PROF_FUSED, PROF_MULTI, PROF_ONEPASS, \
     PROF_DELETE_AHEAD = range(9)
 PROF_NAMES = {PROF_NEWTON: "k_newton", PROF_SCATTER: "k_scatter", PROF_DELETE_MASK: "k_delete_mask",
@@ -157,6 +158,7 @@ _PROTOTYPES = {
     "pcl_step_phase_redirect": [_vp, c_int, c_double, c_double, c_uint64, c_uint32, _vp],
     "pcl_step_absorb_scattered": [_vp, c_int, _vp, _vp, _vp, c_int, _vp, c_uint64, c_uint32, _vp, _vp],
     "pcl_step_phase_layered": [_vp, c_int, _vp, _vp, _vp, _vp, _vp, c_int, _vp, _vp, _vp, c_double, c_uint64, c_uint32, _vp],
+    "pcl_step_recycle_spent": [_vp, _vp, c_double, c_int, c_double, _vp, c_int, _vp, _vp, c_uint64, c_uint32, _vp],
     # device groups: several GPUs from one process (the C-level counterpart of physicl_amd.multidev.MultiDevice)
     "pcl_group_create": [c_int, POINTER(c_int), POINTER(_vp)],
     "pcl_group_destroy": [_vp],
@@ -187,6 +189,7 @@ _PROTOTYPES = {
     "pcl_group_step_phase_redirect": [_vp, c_int, c_double, c_double, c_uint64, c_uint32, _vp],
     "pcl_group_step_absorb_scattered": [_vp, c_int, _vp, _vp, _vp, c_int, _vp, c_uint64, c_uint32, _vp, _vp],
     "pcl_group_step_phase_layered": [_vp, c_int, _vp, _vp, _vp, _vp, _vp, c_int, _vp, _vp, _vp, c_double, c_uint64, c_uint32, _vp],
+    "pcl_group_step_recycle_spent": [_vp, _vp, c_double, c_int, c_double, _vp, c_int, _vp, _vp, c_uint64, c_uint32, _vp],
 }
 EXPORTS = sorted(list(_PROTOTYPES) + ["pcl_last_error"])
 
@@ -419,14 +422,37 @@ class SourceStruct(ctypes.Structure):
                 ("angular", c_int), ("spatial", c_int), ("cos_half_angle", c_double), ("radius", c_double)]
 
 
-def _source(entry, handle, src, c, seed):
-    """One call of pcl_store_apply_source / pcl_group_apply_source.  ``src``: a light.PhotonSource, or anything with its
-    attributes (origin, e1, e2, d: three numbers each; angular, spatial: names or the header's numbers; cos_half_angle,
-    radius)."""
+def _source_struct(src):
+    """``pcl_source`` of a light.PhotonSource, or of anything with its attributes (origin, e1, e2, d: three numbers each;
+    angular, spatial: names or the header's numbers; cos_half_angle, radius)."""
     vec = lambda a: (c_double * 3)(*[float(x) for x in a])                                                     # noqa: E731
-    st = SourceStruct(vec(src.origin), vec(src.e1), vec(src.e2), vec(src.d), int(SRC_ANGULAR.get(src.angular, src.angular)),
-                      int(SRC_SPATIAL.get(src.spatial, src.spatial)), float(src.cos_half_angle), float(src.radius))
+    return SourceStruct(vec(src.origin), vec(src.e1), vec(src.e2), vec(src.d), int(SRC_ANGULAR.get(src.angular, src.angular)),
+                        int(SRC_SPATIAL.get(src.spatial, src.spatial)), float(src.cos_half_angle), float(src.radius))
+
+
+def _source(entry, handle, src, c, seed):
+    """One call of pcl_store_apply_source / pcl_group_apply_source.  ``src``: what ``_source_struct`` takes."""
+    st = _source_struct(src)
     check(entry(handle, ctypes.addressof(st), float(c), int(seed)))
+
+
+def _recycle(entry, handle, src, c, at_rest, top, center, spectrum, seed, n_pass):
+    """One call of pcl_step_recycle_spent / pcl_group_step_recycle_spent: (at_rest, escaped) of this call.  ``src``: what
+    ``_source_struct`` takes; ``top``: None or a radius about ``center``; ``spectrum``: None or ``(grid, cdf)``; ``n_pass``: the
+    caller's own pass counter (a Philox counter word)."""
+    st = _source_struct(src)
+    ce = None if center is None else np.ascontiguousarray(center, dtype=np.float64).reshape(3)
+    grid = cdf = None
+    if spectrum is not None:
+        grid, cdf = (np.ascontiguousarray(a, dtype=np.float64).reshape(-1) for a in spectrum)
+        if len(grid) != len(cdf):
+            raise ValueError("spectrum: grid and cdf must hold the same number of values")
+    counts = np.zeros(2, dtype=np.int64)
+    ptr = lambda a: None if a is None else a.ctypes.data                                                       # noqa: E731
+    check(entry(handle, ctypes.addressof(st), float(c), int(bool(at_rest)), 0.0 if top is None else float(top), ptr(ce),
+                0 if cdf is None else len(cdf), ptr(cdf), ptr(grid), int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_pass) & 0xFFFFFFFF,
+                counts.ctypes.data))
+    return int(counts[0]), int(counts[1])
 
 
 def _scatter(sc, required=False, lazy=False, empty_expr=b""):
@@ -1011,6 +1037,12 @@ class Device:
         int64[M])``.  LayeredPhaseStep."""
         return _phase_layered(self.lib.pcl_step_phase_layered, self.ctx, laws, cum, edges, center, c, seed, n_pass)
 
+    def recycle_spent(self, src, c, at_rest=True, top=None, center=None, spectrum=None, seed=0, n_pass=0):
+        """The photons at rest (``at_rest``) and those beyond the sphere of ``top`` about ``center`` (None: no top, the origin) are
+        re-emitted by the ``light.PhotonSource`` ``src`` with speed ``c``, in one sweep (pcl_step_recycle_spent): new r and v, dr =
+        dv = 0, and -- with ``spectrum=(grid, cdf)`` -- a new E; ids and kinds stay.  ``(at_rest, escaped)``.  RecycleStep."""
+        return _recycle(self.lib.pcl_step_recycle_spent, self.ctx, src, c, at_rest, top, center, spectrum, seed, n_pass)
+
 
 class DeviceGroup:
     """``pcl_group_*``: several contexts in one process, sharded by global index, behind the C ABI (the shim owns the
@@ -1126,6 +1158,10 @@ class DeviceGroup:
     def phase_layered(self, laws, cum, edges=None, center=None, c=0.0, seed=0, n_pass=0):
         """``Device.phase_layered`` on every context of the group, the tallies summed (pcl_group_step_phase_layered)."""
         return _phase_layered(self.lib.pcl_group_step_phase_layered, self.g, laws, cum, edges, center, c, seed, n_pass)
+
+    def recycle_spent(self, src, c, at_rest=True, top=None, center=None, spectrum=None, seed=0, n_pass=0):
+        """``Device.recycle_spent`` on every context of the group, the counts summed (pcl_group_step_recycle_spent)."""
+        return _recycle(self.lib.pcl_group_step_recycle_spent, self.g, src, c, at_rest, top, center, spectrum, seed, n_pass)
 
     def download(self, field, n=None, offset=0, dtype=None):
         n = self.count - offset if n is None else n

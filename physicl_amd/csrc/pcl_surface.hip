@@ -1,4 +1,4 @@
-// pcl_surface.hip -- the sweeps that rewrite photons: two that re-direct them, one that absorbs them.
+// pcl_surface.hip -- the sweeps that rewrite photons: they re-direct them, absorb them, and re-emit the spent ones.
 //
 // A reflecting sphere (SurfaceReflectStep): the ground of a radial problem.  Photons whose last move took
 // them into the sphere are put back: reflected at the point where the move met the sphere (specular, or cosine-weighted about
@@ -86,6 +86,22 @@
 //   as scattered, not written;  inside:  law j = the first with u_s < C[b][j], u_s = u53(w0, w1) of counter (id_lo, id_hi, pass, 13)
 //   isotropic, hg, rayleigh: the lines above, with the blocks 10 and 11;  table: k = the bin of u_a in F;
 //   mu = min(max(mu_k + (u_a - F_k)*s_k, mu_k), mu_(k+1)),  s_k = (mu_(k+1) - mu_k) / (F_(k+1) - F_k) made on the host;  then as above
+//
+// A continuous source (RecycleStep): the photons the ground or the medium has left at rest, and those beyond the top of the
+// atmosphere, are given back to a photon source: their slots are re-emitted, ids and kinds stay, the population is constant.
+//
+//   k_recycle_spent<T>     one grid-stride sweep: per slot the three v rows (only with at_rest; a lane whose v0 is not zero is
+//                          decided and loads no more of them) and, for lanes that are not at rest, the three r rows (only with a
+//                          top); two ballots + popcounts per wave for the two counters.  Only
+//                          spent lanes go on: they load their id, draw the source's direction and position -- the lines of
+//                          k_apply_source (pcl_source.hip) repeated, with counter words of their own -- and write r, v, dr = 0 and
+//                          dv = 0; with a spectrum they look a third draw up in the cumulative table (dynamic LDS, at most 16 KiB, in
+//                          front of the two cells) and write E.
+//
+// Operation order (what light._recycle_spent restates with numpy):
+//   rest = at_rest and v0 == 0 and v1 == 0 and v2 == 0;  d = r - center;  q = d.d;  gone = a top, not rest and q > top*top
+//   spent iff a photon and (rest or gone);  direction: counter (id_lo, id_hi, pass, 14), position: (id_lo, id_hi, pass, 15), by the
+//   arithmetic of pcl_store_apply_source;  dr = dv = 0;  E = grid[x], the first x with cdf[x] >= u53(w0, w1) of (id_lo, id_hi, pass, 16)
 #include "pcl_sweep.h"
 
 #include "pcl_device.h" // (after the HIP runtime and the ABI's header, which pcl_sweep.h brings)
@@ -515,6 +531,126 @@ __global__ void __launch_bounds__(kBlock) k_phase_layered(lphase_args<T> a) {
     __syncthreads();
     // pcl_sweep::flush_cells, written out, for the reason given in k_absorb_scattered: the count is not a literal
     for (int k = threadIdx.x; k < n_cells; k += kBlock)
+        if (s_cnt[k]) atomicAdd(&a.out[k], (unsigned long long)s_cnt[k]);
+}
+
+// The counter words of a re-emission (the header lists who uses which word: 14, 15 and 16 are this kernel's alone).
+constexpr uint32_t kRecycleDirWord = 14, kRecyclePosWord = 15, kRecycleEnergyWord = 16;
+
+template <typename T>
+struct recycle_args {
+    T *r[3], *v[3], *dr[3], *dv[3];
+    T *E;                        // NULL without a spectrum: a recycled photon keeps its energy
+    const unsigned char *kind;   // NULL: every particle is a photon
+    const int64_t *ids;          // NULL: the id of slot i is id_base + i
+    const double *tables;        // cdf (n_E) | grid (n_E), device; unused without a spectrum
+    unsigned long long *out;     // [2]: at rest, escaped; device, zeroed by the entry point
+    int64_t N, ts, id_base;      // particles, tile stride of the slab (elements), id of slot 0
+    int tile_log;                // log2 of the tile length
+    int at_rest, has_top, n_E;   // the two criteria, the bins of the spectrum (0: none)
+    int angular, spatial;        // PCL_SRC_*
+    double c[3], top2;           // the centre, top*top (made on the host)
+    double origin[3], e1[3], e2[3], d[3];
+    double speed, cos_half_angle, radius;
+    uint32_t k0, k1, pass;       // Philox key (seed_lo, seed_hi), the step's own pass counter
+};
+
+template <typename T>
+__global__ void __launch_bounds__(kBlock) k_recycle_spent(recycle_args<T> a) {
+    extern __shared__ double s_mem[];                                  // cdf | grid | at rest, escaped
+    const int nE = a.n_E;
+    const double *s_cdf = s_mem;
+    const double *s_grid = s_mem + nE;
+    uint32_t *s_cnt = reinterpret_cast<uint32_t *>(s_mem + 2 * nE);
+    for (int k = threadIdx.x; k < 2 * nE; k += kBlock) s_mem[k] = a.tables[k];
+    if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    // whole waves run the same number of trips (the ballots below need every lane of the wave inside the loop)
+    const int64_t n_round = (a.N + 63) / 64 * 64;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n_round; i += stride) {
+        const bool in = i < a.N;
+        const int64_t ti = tile_index(i, a.tile_log, a.ts);
+        bool rest = false, gone = false;
+        if (in && a.at_rest)                                            // -0.0 == 0; a NaN is not at rest (fp32 widens exactly)
+            rest = (double)a.v[0][ti] == 0.0 && (double)a.v[1][ti] == 0.0 && (double)a.v[2][ti] == 0.0;
+        if (in && a.has_top && !rest) {
+            double x[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) x[k] = __dsub_rn((double)a.r[k][ti], a.c[k]);
+            gone = dot3(x, x) > a.top2;                                 // on the sphere: not gone; NaN: not gone; inf: gone
+        }
+        if ((rest || gone) && a.kind && a.kind[i] == 0) rest = gone = false;             // plain Objects are never spent
+        const uint32_t n_rest = (uint32_t)__popcll(__ballot(rest)), n_gone = (uint32_t)__popcll(__ballot(gone));
+        if (lane == 0 && n_rest) atomicAdd(&s_cnt[0], n_rest);
+        if (lane == 0 && n_gone) atomicAdd(&s_cnt[1], n_gone);
+        if (!(rest || gone)) continue;   // lanes that are left alone wait at the loop's head: no ballot below this line
+        const uint64_t id = (uint64_t)(a.ids ? a.ids[i] : a.id_base + i);
+        // the lines of k_apply_source (pcl_source.hip), repeated: only the counters differ, and every row is written
+        double vel[3], pos[3];
+        if (a.angular == PCL_SRC_BEAM) {                                // a constant: no draw
+#pragma unroll
+            for (int k = 0; k < 3; ++k) vel[k] = __dmul_rn(a.speed, a.d[k]);
+        } else {
+            const pcl_u32x4 w = pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, kRecycleDirWord, a.k0, a.k1);
+            const double u_a = pcl_u53(w.x, w.y), u_b = pcl_u53(w.z, w.w);
+            double mu;                                                  // cosine of the polar angle about d
+            if (a.angular == PCL_SRC_ISOTROPIC)
+                mu = __dsub_rn(1.0, __dmul_rn(2.0, u_a));                                             // uniform on the sphere
+            else if (a.angular == PCL_SRC_CONE)
+                mu = __dsub_rn(1.0, __dmul_rn(u_a, __dsub_rn(1.0, a.cos_half_angle)));                // uniform in solid angle
+            else
+                mu = __dsqrt_rn(__dsub_rn(1.0, u_a));                                                 // cosine-weighted hemisphere
+            const double s = __dsqrt_rn(__dmul_rn(__dsub_rn(1.0, mu), __dadd_rn(1.0, mu)));
+            double sn, cs;
+            pcl_sincos_2pi(__dmul_rn(__dmul_rn(u_b, 2.0), PCL_PI), &sn, &cs);                         // the scatter step's angle
+            const double sc = __dmul_rn(s, cs), ss = __dmul_rn(s, sn);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const double dir = __dadd_rn(__dadd_rn(__dmul_rn(sc, a.e1[k]), __dmul_rn(ss, a.e2[k])), __dmul_rn(mu, a.d[k]));
+                vel[k] = __dmul_rn(a.speed, dir);
+            }
+        }
+        if (a.spatial == PCL_SRC_POINT) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) pos[k] = a.origin[k];
+        } else {
+            const pcl_u32x4 w = pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, kRecyclePosWord, a.k0, a.k1);
+            const double u_c = pcl_u53(w.x, w.y), u_d = pcl_u53(w.z, w.w);
+            double rho;
+            if (a.spatial == PCL_SRC_DISC)
+                rho = __dmul_rn(a.radius, __dsqrt_rn(u_c));                                           // uniform over the disc
+            else                                                                                      // 1 - u_c is in (0, 1]
+                rho = __dmul_rn(a.radius, __dsqrt_rn(__dmul_rn(-2.0, log(__dsub_rn(1.0, u_c)))));
+            double sn, cs;
+            pcl_sincos_2pi(__dmul_rn(__dmul_rn(u_d, 2.0), PCL_PI), &sn, &cs);
+            const double rc = __dmul_rn(rho, cs), rs = __dmul_rn(rho, sn);
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                pos[k] = __dadd_rn(a.origin[k], __dadd_rn(__dmul_rn(rc, a.e1[k]), __dmul_rn(rs, a.e2[k])));
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {                                   // a newborn has not moved and has not scattered
+            a.r[k][ti] = (T)pos[k];
+            a.v[k][ti] = (T)vel[k];
+            a.dr[k][ti] = (T)0.0;
+            a.dv[k][ti] = (T)0.0;
+        }
+        if (nE) {                                                       // the first x with cdf[x] >= u (cdf ends in 1 > u): compares only
+            const pcl_u32x4 w = pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, kRecycleEnergyWord, a.k0, a.k1);
+            const double u = pcl_u53(w.x, w.y);
+            int lo = 0, hi = nE - 1;
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (s_cdf[mid] >= u) hi = mid; else lo = mid + 1;
+            }
+            a.E[ti] = (T)s_grid[lo];
+        }
+    }
+    __syncthreads();
+    // pcl_sweep::flush_cells, written out, for the reason given in k_absorb_scattered: a further caller changes the older kernels
+    for (int k = threadIdx.x; k < 2; k += kBlock)
         if (s_cnt[k]) atomicAdd(&a.out[k], (unsigned long long)s_cnt[k]);
 }
 
@@ -948,6 +1084,127 @@ int group_phase_layered(pcl_group *group, int n_laws, const int *kinds, const do
     return PCL_OK;
 }
 
+struct recycle_spec { // a call's arguments, checked
+    double c[3] = {0.0, 0.0, 0.0};
+    double top2 = 0.0, speed = 0.0;
+    bool at_rest = false, has_top = false;
+    int n_E = 0;
+    std::vector<double> tables; // cdf | grid
+    size_t lds() const { return tables.size() * sizeof(double) + 2 * sizeof(uint32_t); }
+};
+
+bool finite3(const double *x) { return std::isfinite(x[0]) && std::isfinite(x[1]) && std::isfinite(x[2]); }
+
+// Everything PCL_ERR_ARG stands for except the NULL context; nothing is launched or written before this has passed.  The source
+// is checked as pcl_store_apply_source checks it.
+bool check_recycle(const pcl_source *src, double c, int at_rest, double top, const double *center, int n_E, const double *cdf,
+                   const double *grid, const int64_t *counts_out, recycle_spec &s) {
+    if (!src || !counts_out) return false;
+    if (src->angular < PCL_SRC_BEAM || src->angular > PCL_SRC_LAMBERTIAN || src->spatial < PCL_SRC_POINT || src->spatial > PCL_SRC_GAUSSIAN)
+        return false;
+    if (!finite3(src->origin) || !finite3(src->e1) || !finite3(src->e2) || !finite3(src->d) || !std::isfinite(c)) return false;
+    if (src->angular == PCL_SRC_CONE && !(src->cos_half_angle >= -1.0 && src->cos_half_angle <= 1.0)) return false;
+    if (src->spatial != PCL_SRC_POINT && !(std::isfinite(src->radius) && src->radius >= 0.0)) return false;
+    if (!std::isfinite(top)) return false;
+    s.at_rest = at_rest != 0; s.has_top = top > 0.0; s.speed = c;
+    if (s.has_top && !std::isfinite(s.top2 = top * top)) return false;
+    if (!s.at_rest && !s.has_top) return false;                         // neither criterion: nobody could ever be spent
+    if (center) {
+        if (!finite3(center)) return false;
+        for (int k = 0; k < 3; ++k) s.c[k] = center[k];
+    }
+    if (n_E < 0 || n_E > PCL_RECYCLE_MAX_BINS || (n_E > 0 && (!cdf || !grid))) return false;
+    s.n_E = n_E;
+    double prev = -INFINITY;
+    for (int k = 0; k < n_E; ++k) {
+        if (!(cdf[k] >= prev)) return false;                            // (NaN as well)
+        s.tables.push_back(prev = cdf[k]);
+    }
+    if (n_E > 0 && prev != 1.0) return false;
+    for (int k = 0; k < n_E; ++k) {
+        if (!std::isfinite(grid[k])) return false;
+        s.tables.push_back(grid[k]);
+    }
+    return true;
+}
+
+template <typename T>
+int launch_recycle(pcl_ctx *ctx, const store_view &v, const recycle_spec &s, const pcl_source *src, uint64_t seed, uint32_t pass,
+                   int64_t id_base, const int64_t *ids, const unsigned char *kind, const double *tables_dev, unsigned long long *out_dev) {
+    recycle_args<T> a{};
+    for (int k = 0; k < 3; ++k) {
+        void *r = nullptr, *vel = nullptr, *dr = nullptr, *dv = nullptr;
+        PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_R0 + k, &r));
+        PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_V0 + k, &vel));
+        PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_DR0 + k, &dr));
+        PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_DV0 + k, &dv));
+        a.r[k] = static_cast<T *>(r); a.v[k] = static_cast<T *>(vel);
+        a.dr[k] = static_cast<T *>(dr); a.dv[k] = static_cast<T *>(dv);
+        a.c[k] = s.c[k];
+        a.origin[k] = src->origin[k]; a.e1[k] = src->e1[k]; a.e2[k] = src->e2[k]; a.d[k] = src->d[k];
+    }
+    // E is asked for only with a spectrum: the pointer costs a wavelength-dependent scatter step its term cache (pcl_shell.hip).
+    void *E = nullptr;
+    if (s.n_E > 0) PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_E, &E));
+    a.E = static_cast<T *>(E); a.kind = kind; a.ids = ids; a.tables = tables_dev; a.out = out_dev;
+    a.N = v.N; a.ts = v.ts; a.id_base = id_base; a.tile_log = v.tile_log;
+    a.at_rest = s.at_rest; a.has_top = s.has_top; a.n_E = s.n_E; a.angular = src->angular; a.spatial = src->spatial;
+    a.top2 = s.top2; a.speed = s.speed; a.cos_half_angle = src->cos_half_angle; a.radius = src->radius;
+    a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32); a.pass = pass;
+    const size_t lds = s.lds();                                         // 16 KiB of tables at the most: eight workgroups a CU still
+    const int64_t grid = balanced_grid(v.N, v.n_cu, resident_per_cu(lds));
+    hipLaunchKernelGGL(k_recycle_spent<T>, dim3((unsigned)grid), dim3(kBlock), lds, v.stream, a);
+    return hipGetLastError() == hipSuccess ? PCL_OK : PCL_ERR_HIP;
+}
+
+int recycle_spent(pcl_ctx *ctx, const pcl_source *src, double c, int at_rest, double top, const double *center_host, int n_E,
+                  const double *cdf_host, const double *grid_host, uint64_t seed, uint32_t pass, int64_t *counts_out_host) {
+    recycle_spec s;
+    if (!ctx || !check_recycle(src, c, at_rest, top, center_host, n_E, cdf_host, grid_host, counts_out_host, s)) return bad_argument(ctx);
+    store_view v;
+    PCL_SWEEP_TRY(open_store(ctx, PCL_R0, &v));
+    counts_out_host[0] = counts_out_host[1] = 0;
+    if (v.N <= 0) return PCL_OK;
+    std::vector<uint8_t> kind_host;                                     // a store that is not uniform: as surface_reflect
+    std::vector<int64_t> ids_host;
+    bool mixed = false;
+    int64_t id_base = 0;
+    PCL_SWEEP_TRY(kind_bytes(ctx, v.N, kind_host, &mixed));
+    PCL_SWEEP_TRY(id_words(ctx, v.N, ids_host, &id_base));
+    const size_t out_bytes = 2 * sizeof(uint64_t), tab_bytes = s.tables.size() * sizeof(double);
+    const size_t id_bytes = ids_host.size() * sizeof(int64_t);
+    dev_block blk(ctx);
+    PCL_SWEEP_TRY(stage(blk, v.stream, out_bytes, s.tables.data(), tab_bytes, kind_host, ids_host));
+    char *base = static_cast<char *>(blk.p);
+    const double *tables_dev = reinterpret_cast<const double *>(base + out_bytes);
+    const int64_t *ids = id_bytes ? reinterpret_cast<const int64_t *>(base + out_bytes + tab_bytes) : nullptr;
+    const unsigned char *kind = mixed ? reinterpret_cast<const unsigned char *>(base + out_bytes + tab_bytes + id_bytes) : nullptr;
+    unsigned long long *out_dev = reinterpret_cast<unsigned long long *>(base);
+    PCL_SWEEP_TRY(v.dtype == PCL_DTYPE_F64 ? launch_recycle<double>(ctx, v, s, src, seed, pass, id_base, ids, kind, tables_dev, out_dev)
+                                           : launch_recycle<float>(ctx, v, s, src, seed, pass, id_base, ids, kind, tables_dev, out_dev));
+    return pcl_d2h(ctx, counts_out_host, base, (int64_t)out_bytes);    // the call's one synchronisation (a count is below 2^63)
+}
+
+int group_recycle_spent(pcl_group *group, const pcl_source *src, double c, int at_rest, double top, const double *center_host, int n_E,
+                        const double *cdf_host, const double *grid_host, uint64_t seed, uint32_t pass, int64_t *counts_out_host) {
+    std::vector<pcl_ctx *> ctx;
+    PCL_SWEEP_TRY(shards_of(group, ctx));
+    const int n = (int)ctx.size();
+    recycle_spec s;
+    if (n < 1 || !check_recycle(src, c, at_rest, top, center_host, n_E, cdf_host, grid_host, counts_out_host, s))
+        return bad_argument(n > 0 ? ctx[0] : nullptr);
+    std::vector<int64_t> part((size_t)2 * n, 0);
+    PCL_SWEEP_TRY(for_each_shard(ctx, [&](int g, pcl_ctx *one) {
+        return pcl_step_recycle_spent(one, src, c, at_rest, top, center_host, n_E, cdf_host, grid_host, seed, pass, &part[(size_t)2 * g]);
+    }));
+    counts_out_host[0] = counts_out_host[1] = 0;
+    for (int g = 0; g < n; ++g) {
+        counts_out_host[0] += part[(size_t)2 * g];
+        counts_out_host[1] += part[(size_t)2 * g + 1];
+    }
+    return PCL_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -1005,6 +1262,21 @@ int pcl_group_step_phase_layered(pcl_group *group, int n_laws, const int *kinds_
     return guarded([&] {
         return group_phase_layered(group, n_laws, kinds_host, g_host, n_bins_host, mu_host, F_host, n_layers, cum_host, edges_host,
                                    center_host, c, seed, pass, counts_out_host);
+    });
+}
+
+int pcl_step_recycle_spent(pcl_ctx *ctx, const pcl_source *src, double c, int at_rest, double top, const double *center_host, int n_E,
+                           const double *cdf_host, const double *grid_host, uint64_t seed, uint32_t pass, int64_t *counts_out_host) {
+    return guarded([&] {
+        return recycle_spent(ctx, src, c, at_rest, top, center_host, n_E, cdf_host, grid_host, seed, pass, counts_out_host);
+    });
+}
+
+int pcl_group_step_recycle_spent(pcl_group *group, const pcl_source *src, double c, int at_rest, double top, const double *center_host,
+                                 int n_E, const double *cdf_host, const double *grid_host, uint64_t seed, uint32_t pass,
+                                 int64_t *counts_out_host) {
+    return guarded([&] {
+        return group_recycle_spent(group, src, c, at_rest, top, center_host, n_E, cdf_host, grid_host, seed, pass, counts_out_host);
     });
 }
 

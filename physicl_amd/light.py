@@ -1444,6 +1444,200 @@ class LayeredPhaseStep(DeviceStep, MeasureStep):
     terminate = tally.TallyStep.terminate                # (a row holds arrays: written as the tally steps write theirs, as plain lists)
 
 
+# ---------------------------------------------------------------------------------------------- a continuous source
+def _check_recycle(source, top, center, at_rest, spectrum):
+    """(source, top or None, centre, at_rest, spectrum as (grid, cdf) float64 arrays or None) of a RecycleStep, or ValueError for
+    everything pcl_step_recycle_spent would refuse."""
+    from ._hip import RECYCLE_MAX_BINS                        # (the header's limit: one place)
+    if not isinstance(source, PhotonSource):
+        raise ValueError("source must be a PhotonSource, got %r" % (source,))
+    if top is not None:
+        try:
+            top = float(np.asarray(top, dtype=np.float64).reshape(()))
+        except (TypeError, ValueError):
+            raise ValueError("top must be None or a number") from None
+        if not (np.isfinite(top) and top > 0 and np.isfinite(top * top)):
+            raise ValueError("top must be finite and positive (its square finite, too), got %r" % (top,))
+    center = tally.check_center(center)
+    at_rest = bool(at_rest)
+    if not at_rest and top is None:
+        raise ValueError("at_rest and top: at least one of the two criteria must be on")
+    if spectrum is not None:
+        if isinstance(spectrum, PhotonBatch):
+            if spectrum.table is None:
+                raise ValueError("spectrum: this PhotonBatch has no table (make it with generate_photons_bulk(T=...))")
+            cdf, grid = spectrum.table                         # (a batch keeps the fill's order)
+        else:
+            try:
+                grid, cdf = spectrum
+            except (TypeError, ValueError):
+                raise ValueError("spectrum must be None, (grid, cdf) or a PhotonBatch with a table") from None
+        try:
+            grid, cdf = np.array(grid, dtype=np.float64), np.array(cdf, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("spectrum: grid and cdf must be sequences of numbers") from None
+        if grid.ndim != 1 or cdf.ndim != 1 or len(grid) != len(cdf) or not 1 <= len(cdf) <= RECYCLE_MAX_BINS:
+            raise ValueError("spectrum: grid and cdf must be two sequences of one length between 1 and %d, got shapes %r and %r"
+                             % (RECYCLE_MAX_BINS, grid.shape, cdf.shape))
+        if not np.all(np.isfinite(grid)):
+            raise ValueError("spectrum: grid must be finite")
+        if np.any(np.isnan(cdf)) or np.any(np.diff(cdf) < 0) or cdf[-1] != 1.0:
+            raise ValueError("spectrum: cdf must not decrease and must end in exactly 1")
+        spectrum = (np.ascontiguousarray(grid), np.ascontiguousarray(cdf))
+    return source, top, center, at_rest, spectrum
+
+
+def _source_emit(ids, source, c, seed, word2, dir_word, pos_word):
+    """(v, r) as (n, 3) float64 arrays: what pcl_store_apply_source's arithmetic (include/physicl_hip.h) makes of the Philox blocks
+    (id_lo, id_hi, word2, dir_word) and (id_lo, id_hi, word2, pos_word) per id -- every operation the device's, one rounding
+    each; sin / cos and the gaussian's log are libm's here, the library's own on the device."""
+    ids = np.asarray(ids).reshape(-1)
+    n = len(ids)
+    c = np.float64(c)
+    d, e1, e2, origin = (np.asarray(x, dtype=np.float64) for x in (source.d, source.e1, source.e2, source.origin))
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        if source.angular == "beam":
+            v = np.tile(c * d, (n, 1))
+        else:
+            u_a, u_b = _philox_block(ids, seed, word2, dir_word)
+            if source.angular == "isotropic":
+                mu = 1.0 - 2.0 * u_a
+            elif source.angular == "cone":
+                mu = 1.0 - u_a * (1.0 - np.float64(source.cos_half_angle))
+            else:
+                mu = np.sqrt(1.0 - u_a)
+            s = np.sqrt((1.0 - mu) * (1.0 + mu))
+            psi = (u_b * 2.0) * np.pi
+            sc, ss = s * np.cos(psi), s * np.sin(psi)
+            v = c * ((sc[:, None] * e1 + ss[:, None] * e2) + mu[:, None] * d)
+        if source.spatial == "point":
+            r = np.tile(origin, (n, 1))
+        else:
+            u_c, u_d = _philox_block(ids, seed, word2, pos_word)
+            radius = np.float64(source.radius)
+            rho = radius * np.sqrt(u_c) if source.spatial == "disc" else radius * np.sqrt(-2.0 * np.log(1.0 - u_c))
+            phi = (u_d * 2.0) * np.pi
+            rc, rs = rho * np.cos(phi), rho * np.sin(phi)
+            r = origin + (rc[:, None] * e1 + rs[:, None] * e2)
+    return v.reshape(n, 3), r.reshape(n, 3)
+
+
+_RECYCLE_WORDS = (14, 15, 16)                                 # direction, position, energy (the header lists the words taken)
+
+
+def _recycle_spent(r, v, E, photon, ids, source, top, center, at_rest, spectrum, c, seed, n_pass, dtype=np.float64):
+    """What pcl_step_recycle_spent makes of (n, 3) float64 positions and velocities, the energies, who is a photon and the
+    particles' ids, with numpy -- every operation the device's operation in the device's order, one rounding each
+    (include/physicl_hip.h), and what is written rounded once to ``dtype``.  The rule, a beam, a point and the table look-up are the
+    device's bit for bit; sin / cos and the gaussian's log are libm's here.  ``spectrum``: None or ``(grid, cdf)``.  A dict: ``r, v,
+    dr, dv, E`` the new state (float64 arrays; rows of particles that are not spent are the arguments', ``dr`` and ``dv`` hold NaN
+    there: the sweep does not write them) and the boolean masks ``at_rest``, ``escaped`` and ``spent``."""
+    r, v = (np.array(a, dtype=np.float64).reshape(-1, 3) for a in (r, v))
+    n = len(r)
+    E = np.full(n, np.nan) if E is None else np.array(E, dtype=np.float64).reshape(-1)
+    photon = np.asarray(photon, dtype=bool).reshape(-1)
+    with np.errstate(invalid="ignore", over="ignore"):
+        rest = np.zeros(n, dtype=bool)
+        if at_rest:
+            rest = (v[:, 0] == 0) & (v[:, 1] == 0) & (v[:, 2] == 0)
+        gone = np.zeros(n, dtype=bool)
+        if top is not None:
+            d = r - np.asarray(center, dtype=np.float64)
+            gone = ~rest & (_dot3(d, d) > np.float64(top) * np.float64(top))
+    rest, gone = rest & photon, gone & photon
+    spent = rest | gone
+    at = np.flatnonzero(spent)
+    ids = np.asarray(ids).reshape(-1)[at]
+    v_new, r_new = _source_emit(ids, source, c, seed, n_pass, _RECYCLE_WORDS[0], _RECYCLE_WORDS[1])
+    dr, dv = np.full((n, 3), np.nan), np.full((n, 3), np.nan)
+    r[at], v[at] = r_new.astype(dtype).astype(np.float64), v_new.astype(dtype).astype(np.float64)
+    dr[at], dv[at] = 0.0, 0.0
+    if spectrum is not None:
+        grid, cdf = (np.asarray(a, dtype=np.float64) for a in spectrum)
+        u = _philox_block(ids, seed, n_pass, _RECYCLE_WORDS[2])[0]
+        E[at] = grid[np.searchsorted(cdf, u, side="left")].astype(dtype).astype(np.float64)   # the first x with cdf[x] >= u
+    return {"r": r, "v": v, "dr": dr, "dv": dv, "E": E, "at_rest": rest, "escaped": gone, "spent": spent}
+
+
+class RecycleStep(DeviceStep, MeasureStep):
+    """A continuous source (not in the reference): the LAST step of a pass, behind a ``SurfaceReflectStep`` if there is one.  A photon
+    the ground or the medium has absorbed stays in the store at rest, one that has left through the top of the atmosphere flies on for
+    ever; this step gives the slots of both back to ``source``, a ``PhotonSource``.  The population stays constant
+    (``len(sim.objects)`` does not change), the store dense and uniform, and the run converges to the steady state of a lamp that
+    keeps emitting: ``self.recycled`` per pass is the source's emission rate.
+
+    * ``at_rest=True``: a photon with ``v == (0, 0, 0)`` is spent (``-0.0`` counts as 0; a NaN in ``v`` is not at rest);
+    * ``top``: None, or a positive radius about ``center`` (code units): a photon that is not at rest is spent iff ``q > top*top``,
+      ``q = (d0*d0 + d1*d1) + d2*d2`` the squared distance from ``center`` in float64.  Exactly on the sphere is not gone, a NaN in
+      ``r`` is not gone, ``q = inf`` is gone.  At least one of ``at_rest`` and ``top`` must be on.
+    * ``spectrum=None``: every slot keeps its colour -- a recycled photon keeps its ``E``, and ``E`` is not even asked for, so a
+      wavelength-dependent scatter step keeps its term cache.  That is exact for a monochromatic source, or wherever no sink depends
+      on ``E``.  With ``wavelength_dep_scattering`` plus an ``AbsorptionStep``, blue slots die and are re-emitted more often, and the
+      population drifts blue: give the spectrum.
+    * ``spectrum=(grid, cdf)``: two float64 sequences of one length between 1 and 1024, ``cdf`` not decreasing and ending in exactly
+      1: a recycled photon gets ``E = grid[x]`` for the first ``x`` with ``cdf[x] >= u`` (the table of ``generate_photons_bulk(T=...)``);
+      or the ``PhotonBatch`` such a call returned, whose table is taken.  (After a device run with a spectrum the energies live on the
+      device: read them with ``sim.download``.)
+
+    A spent photon is re-emitted the way ``generate_photons_bulk(source=)`` created it (include/physicl_hip.h:
+    pcl_store_apply_source), from Philox blocks keyed by ``sim.seed``, its id and a pass counter of the step's own, in counter words
+    no other kernel uses (14, 15, 16): ``r`` and ``v`` from the source, ``dr = dv = 0`` -- a newborn has not moved and has not scattered.
+    Ids and kinds are never written: a slot keeps its id, every re-emission draws new numbers because the pass counter moves, and a
+    sharded run recycles the same photons the same way.  Plain ``Object``s are never spent; a particle that is not spent is not
+    written at all.  ``_recycle_spent`` restates the sweep with numpy.
+
+    After each run ``self.at_rest``, ``self.escaped`` and ``self.recycled`` (their sum) hold the pass's counts (global over shards and
+    ranks) and ``self.data`` gains the row ``[t, at_rest, escaped]``; ``out_fn`` takes the rows at the end of the run.  The step reads
+    no ``dv`` rule, so it works under ``cl_on=False`` as well.
+
+    One launch per light step: the K-passes-per-launch kernels cannot re-emit a photon between two of their passes, and
+    ``sim.launch_note`` says so.  On host-resident objects (``step.run(sim)`` outside a device loop) the same state is made with
+    numpy, the ids being the places in the object list."""
+    _fuse_role = None
+    _NOTE = "one launch per light step: a RecycleStep re-emits the spent photons behind every pass, which the " \
+            "K-passes-per-launch kernels cannot carry"
+
+    def __init__(self, source, top=None, center=(0, 0, 0), at_rest=True, spectrum=None, out_fn=None):
+        MeasureStep.__init__(self, out_fn)
+        self.source, self.top, self.center, self.rest_on, self.spectrum = _check_recycle(source, top, center, at_rest, spectrum)
+        self.at_rest = self.escaped = self.recycled = 0
+        self._pass = 0                                   # the step's own Philox counter word: one per run
+
+    def _record_pass(self, sim, at_rest, escaped):
+        self.at_rest, self.escaped = int(at_rest), int(escaped)
+        self.recycled = self.at_rest + self.escaped
+        self.data.append(tally.object_row([tally._snap(sim.t), self.at_rest, self.escaped]))
+
+    def _device_run(self, sim):
+        if getattr(sim, "launch_note", self._NOTE) is None and sim._k_wanted() > 1:      # (a device run only: the host path says nothing)
+            sim.launch_note = self._NOTE
+        self._pass += 1
+        counts = sim._dev.recycle_spent(self.source, _c_h_literals()[0], self.rest_on, self.top, self.center, self.spectrum, sim.seed, self._pass)
+        sim._scattered = True                            # velocities were replaced on the device
+        # (every rank issues it, also with an empty shard)
+        _, (both,) = tally.reduce_parts(sim, [np.array(counts, dtype=np.int64)])
+        self._record_pass(sim, both[0], both[1])
+
+    def run(self, sim):
+        if getattr(sim, "_residency", None) == "host" and getattr(sim, "_batch", None) is None \
+                and (sim.comm is None or sim.comm.world == 1):
+            objs = list(sim.objects)
+            self._pass += 1
+            E, photon = tally.photon_energies(objs, PhotonObject)
+            new = _recycle_spent(tally.vec3(objs, "r"), tally.vec3(objs, "v"), E, photon, np.arange(len(objs)), self.source, self.top,
+                                 self.center, self.rest_on, self.spectrum, _c_h_literals()[0], getattr(sim, "seed", 0), self._pass)
+            for k in np.flatnonzero(new["spent"]).tolist():
+                o = objs[k]
+                o.r = Measurement._from_code(new["r"][k], like=o.r, units="m**1")
+                o.dr = Measurement._from_code(new["dr"][k], units="m**1")
+                o.v, o.dv = np.array(new["v"][k], dtype=np.double), np.array(new["dv"][k], dtype=np.double)   # plain arrays, as a scatter leaves them
+                if self.spectrum is not None:
+                    o.E = Measurement._from_code(new["E"][k], like=o.E, units="J**1") if isinstance(o.E, Measurement) else np.double(new["E"][k])
+            self._record_pass(sim, new["at_rest"].sum(), new["escaped"].sum())
+            return None
+        return DeviceStep.run(self, sim)
+
+
 def _DEFAULT_ID_INFO(x):
     """The reference's default ``lambda x: str(type(x))`` (light.py:438), recognised by identity.  The label goes into the trace
     table's first column: this package's own classes read as the reference's (``<class 'physicl.light.PhotonObject'>``, what a
