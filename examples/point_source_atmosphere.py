@@ -4,7 +4,7 @@ examples (n(r) = 2.5e25 m^-3 * exp(-(|r| - 6371 km) / 8.6 km)) with photons that
 
     python examples/point_source_atmosphere.py [n_photons] [passes] [--cone | --beam-down | --default] [--profile] [--shells]
                                                [--ground [ALBEDO]] [--phase rayleigh | hg:G | isotropic] [--omega0 W | W1,W2,...]
-                                               [--cloud LO,HI[,G]] [--recycle [TOP]]
+                                               [--cloud LO,HI[,G]] [--recycle [TOP]] [--gas LO,HI,K[,EMIN,EMAX]] [--blue-sky]
 
 default: a point source at (6371 km, 0, 0) emitting isotropically; ``--cone``: a 0.3 rad cone pointing up (+x) from a 1 km disc;
 ``--beam-down``: a 10 km gaussian beam entering from 100 km above the surface along -x; ``--default``: the same step list from
@@ -36,6 +36,12 @@ per law are printed beside the shell counts.  Not together with ``--phase``: a p
 gives the slots of the photons at rest (absorbed by the ground or the medium) and of those above TOP back to the source.  The
 population stays constant; the emission rate (photons recycled per pass) and the counts at rest and through the top are printed as
 they settle to the steady state.  One launch per light step.  Not with ``--default``: the step re-emits from a PhotonSource.
+``--gas LO,HI,K[,EMIN,EMAX]`` puts an absorbing shell between the altitudes LO and HI (metres): a PathAbsorptionStep behind the scatter,
+absorption and phase steps absorbs every photon that moves there with the probability 1 - exp(-K c dt) per pass -- K the absorption
+coefficient per metre --, whether it scattered or not, and leaves it at rest.  With EMIN,EMAX (joules) only photons whose energy lies
+in that band are absorbed: the escaping spectrum gets a band.  One launch per light step; ``absorbed_by_cell`` summed over the
+passes is printed beside the shell counts.  ``--blue-sky`` makes the scatter step wavelength dependent (lambda**-4, scaled so that
+550 nm scatters as the grey atmosphere does); with a band the gas then asks for E in every pass, which drops that step's term cache.
 """
 import os
 import sys
@@ -82,6 +88,12 @@ if "--recycle" in argv:
         sys.exit("--recycle TOP: an altitude in metres above the ground")
     if "--default" in argv:
         sys.exit("--recycle needs a source: not with --default")
+gas = None
+if "--gas" in argv:
+    at = argv.index("--gas")
+    gas = [float(x) for x in (argv.pop(at + 1) if at + 1 < len(argv) else "").split(",")]
+    if len(gas) not in (3, 5) or not 0.0 <= gas[0] < gas[1] or not gas[2] >= 0.0 or (len(gas) == 5 and not gas[3] < gas[4]):
+        sys.exit("--gas LO,HI,K[,EMIN,EMAX]: two altitudes in metres, 0 <= LO < HI, a coefficient per metre and optionally an energy band in joules")
 CLOUD_WEIGHTS = [[1, 0], [0.1, 0.9], [1, 0]]                  # below the cloud, in it, above it: (Rayleigh, Henyey-Greenstein)
 args = [a for a in argv if not a.startswith("--")]
 n = int(float(args[0])) if len(args) > 0 else 100_000_000
@@ -113,7 +125,9 @@ def run(ground):
     sim.add_step(0, phys.UpdateTimeStep(lambda c: dt))
     sim.add_step(1, newton.NewtonianKinematicsStep())
     # (the reference hands the kernel A := n, n := A: with variable_n the user's n scales the expression -- a cross-section of 4e-30 m^2)
-    sim.add_step(2, light.ScatterIsotropicStep(n=4e-30, A=1.0, variable_n=True, variable_n_fn=cl_n))
+    blue = "--blue-sky" in sys.argv                           # lambda**-4, equal to the grey cross-section at 550 nm
+    sim.add_step(2, light.ScatterIsotropicStep(n=4e-30 * (550e-9 ** 4 if blue else 1.0), A=1.0, variable_n=True, variable_n_fn=cl_n,
+                                               wavelength_dep_scattering=blue))
     medium = None
     if omega0 is not None:                                     # behind the scatter step, before the phase function
         medium = light.AbsorptionStep(omega0[0] if layer_edges is None else omega0, edges=layer_edges)
@@ -123,6 +137,11 @@ def run(ground):
         angles = light.LayeredPhaseStep(["rayleigh", ("hg", cloud[2])], CLOUD_WEIGHTS, edges=[0.0, R + cloud[0], R + cloud[1], R + 1000e3])
     if angles is not None:                                     # directly behind the scatter step (steps run in the order they were added)
         sim.add_step("phase", angles)
+    vapour = None
+    if gas is not None:                                        # behind the scatter, absorption and phase steps, before the ground
+        vapour = light.PathAbsorptionStep([gas[2]] if len(gas) == 3 else [[gas[2]]], edges=[R + gas[0], R + gas[1]],
+                                          E_edges=None if len(gas) == 3 else gas[3:5])
+        sim.add_step("gas", vapour)
     signs = light.ScatterSignMeasureStep(None, True)
     sim.add_step(3, signs)
     shells = light.ScatterMeasureStep(None, True, [[R + 20e3, np.nan, np.nan], [np.nan, 0.0, np.nan]])   # 20 km up; the plane y = 0
@@ -148,7 +167,7 @@ def run(ground):
     sim.join()
     if sim.error is not None:
         raise sim.error
-    return sim, signs, shells, profile, image, tally, floor, angles, medium, lamp
+    return sim, signs, shells, profile, image, tally, floor, angles, medium, lamp, vapour
 
 
 bare_top = None
@@ -158,7 +177,7 @@ if albedo is not None and "--shells" in sys.argv:              # the same run wi
     print("without the ground: %d photons x %d steps in %.2f s" % (n, len(bare[0].ts), bare[0].run_time))
     bare[0].close(download=False)
     del bare
-sim, signs, shells, profile, image, tally, floor, angles, medium, lamp = run(albedo)
+sim, signs, shells, profile, image, tally, floor, angles, medium, lamp, vapour = run(albedo)
 steps = len(sim.ts)
 print("source:", source)
 print("%d photons x %d steps in %.2f s  ->  %.3g particle-steps/s" % (n, steps, sim.run_time, n * steps / sim.run_time))
@@ -201,6 +220,14 @@ if medium is not None:
     else:
         for b in range(len(by_layer)):
             print("  %5.1f - %5.1f km: %d absorbed" % ((layer_edges[b] - R) / 1e3, (layer_edges[b + 1] - R) / 1e3, by_layer[b]))
+    if tally is not None:
+        print("  beside it: %d left through the top of the atmosphere (100 km)%s" % (
+            int(sum(row[2][3] for row in tally.data)), "" if floor is None else ", %d absorbed by the ground" % sum(int(row[2]) for row in floor.data)))
+if vapour is not None:
+    cells = np.sum([row[3] for row in vapour.data], axis=0)
+    print("a gas between %g and %g km (k = %g per m%s): %d photons exposed, %d absorbed over %d passes; absorbed_by_cell %s" % (
+        gas[0] / 1e3, gas[1] / 1e3, gas[2], "" if len(gas) == 3 else ", E in [%g, %g] J" % (gas[3], gas[4]), sum(int(row[1]) for row in vapour.data),
+        sum(int(row[2]) for row in vapour.data), len(vapour.data), cells.tolist()))
     if tally is not None:
         print("  beside it: %d left through the top of the atmosphere (100 km)%s" % (
             int(sum(row[2][3] for row in tally.data)), "" if floor is None else ", %d absorbed by the ground" % sum(int(row[2]) for row in floor.data)))

@@ -851,6 +851,55 @@ int pcl_step_recycle_spent(pcl_ctx *ctx, const pcl_source *src, double c, int at
                            const double *center_host, int n_E, const double *cdf_host, const double *grid_host, uint64_t seed,
                            uint32_t pass, int64_t *counts_out_host /* [2]: at rest, escaped */);
 
+/* Absorption along the path (PathAbsorptionStep): a gas that absorbs without scattering -- Beer-Lambert over the move a photon has
+ * just made, with a coefficient that depends on the radial layer it stands in and on the band its energy falls in.  Called anywhere
+ * behind pcl_step_newton in a pass (before or behind the scatter, phase, absorption and ground calls, before
+ * pcl_step_recycle_spent), it absorbs in ONE sweep of the resident store.  A photon moves c*dt in every pass, across a bounce off the
+ * ground too, so the path length is not read from the store: the host makes the probability of absorption per pass,
+ * p = -expm1(-k * (c*dt)), and the device only ever sees p.  Nothing is removed; r, dr, E, ids and kinds are never written.  All
+ * arithmetic is fp64, unfused, every operation rounded once, in the order written; an fp32 store's values are widened first (exact);
+ * what is written is zero.  L' = max(n_layers, 1), B' = max(n_E_bins, 1).
+ *   at rest   iff  v0 == 0 and v1 == 0 and v2 == 0            (-0.0 counts as 0; a NaN in v: moving).  A slot at rest is skipped,
+ *                  and nothing more is loaded for it; a slot with v0 != 0 is decided by v0 alone and loads neither v1 nor v2.
+ *   a moving particle that is not a photon (kind 0) is skipped.
+ *   n_layers == 0:  b = 0;  edges_host and center_host are ignored, r is not read
+ *   n_layers = L >= 1:  d = r - center;  q = (d0*d0 + d1*d1) + d2*d2;  e2_k = e_k*e_k (made on the host);  inside iff e2_0 <= q and
+ *                  q <= e2_L (NaN: not inside);  b = the layer with e2_b <= q < e2_(b+1), the last one closed (numpy.histogram);
+ *                  no square root is taken -- the layer pcl_step_absorb_scattered finds.  A photon in no layer is skipped.
+ *   n_E_bins == 0:  e = 0;  E is neither read nor asked for (pcl_store_field_ptr): a wavelength-dependent scatter step keeps its
+ *                  lambda^-4 cache
+ *   n_E_bins = B >= 1:  e = the bin of E (widened to double) in E_edges_host: [E_e, E_(e+1)), the last one closed; NaN and
+ *                  energies outside the edges are in no band: the photon is skipped.  (Asking for E drops that cache, every pass: the
+ *                  ABI has no read-only accessor.)
+ *   exposed   =    a moving photon with a layer and a band;  p = p_host[b * B' + e]
+ *   p == 0:        nothing is drawn.   p > 0:  u = u53(w0, w1) of the block below;  absorbed iff u < p       (p == 1: every one)
+ *   absorbed:      v = 0;  dv = 0          (pcl_step_absorb_scattered's convention, for its reason: a later phase or absorption
+ *                  call of the pass leaves the photon alone, and pcl_step_recycle_spent with at_rest picks it up)
+ * A photon that is not absorbed is not written at all.  Compare, subtract, multiply and add only -- no transcendental function, no
+ * division, no square root: everything can be restated bit for bit.  The draw is the Philox4x32-10 block with the key (seed_lo,
+ * seed_hi) and the counter (id_lo, id_hi, pass, 17), u53 of pcl_store_apply_source; ``pass`` is the caller's own counter.  The word
+ * 17 is used by nothing else (scatter kernels 0 and 1, fill and source 2..5, pcl_step_surface_reflect 8 and 9,
+ * pcl_step_phase_redirect 10 and 11, pcl_step_absorb_scattered 12, pcl_step_phase_layered 13, pcl_step_recycle_spent 14, 15 and 16),
+ * so every other step draws what it drew, and a photon draws the same number however the run is sharded.
+ * p_host: L' * B' doubles in [0, 1], row b the layer, column e the band.  edges_host: L + 1 radii as for
+ * pcl_step_absorb_scattered, 1 <= L <= PCL_PATH_ABSORB_MAX_LAYERS.  E_edges_host: B + 1 finite, strictly increasing doubles, 1 <= B
+ * <= PCL_PATH_ABSORB_MAX_BANDS.  L' * B' may not exceed PCL_PATH_ABSORB_MAX_CELLS: a workgroup's uint32 cells (16 KiB), the
+ * probabilities (32 KiB) and the two edge tables stay below 64 KiB of LDS.  center_host: 3 finite doubles, NULL = the origin.
+ * counts_out_host[0] = photons exposed, [1] = absorbed, by this call;  cells_out_host[b * B' + e] = absorbed in layer b and band e.
+ * A store that is not uniform costs the host traffic it costs pcl_step_surface_reflect; the ids go along only if some p > 0.
+ * PCL_ERR_ARG (NULL p, counts or cells, L outside 0 .. PCL_PATH_ABSORB_MAX_LAYERS, B outside 0 .. PCL_PATH_ABSORB_MAX_BANDS, too
+ * many cells, a p outside [0, 1] or NaN, NULL or bad edges with L > 0, NULL or bad E edges with B > 0, a centre that is not finite)
+ * is returned before the store is looked at, and nothing is launched or written; PCL_ERR_STATE without a store; an empty store
+ * answers zeros without a launch.  Host pointers; one device allocation per call, handed back on every way out; synchronises once,
+ * with the copy of the tallies.  pcl_last_error() is generic, as for pcl_step_surface_reflect, whose source file these two entry
+ * points share (physicl_amd/csrc/pcl_surface.hip). */
+#define PCL_PATH_ABSORB_MAX_LAYERS 64
+#define PCL_PATH_ABSORB_MAX_BANDS 1024
+#define PCL_PATH_ABSORB_MAX_CELLS 4096 /* L' * B' */
+int pcl_step_absorb_path(pcl_ctx *ctx, int n_layers, int n_E_bins, const double *p_host, const double *edges_host,
+                         const double *center_host, const double *E_edges_host, uint64_t seed, uint32_t pass,
+                         int64_t *counts_out_host /* [2]: exposed, absorbed */, int64_t *cells_out_host /* [L' * B'] */);
+
 /* ---- Device groups: several GPUs from ONE process ---------------------------------------------------------------
  * The reference is a single process with one simulation thread (physicl/__init__.py:400-432, 501-524); this is how
  * a host written against this ABI uses a node's GPUs the same way, without one process per GPU.  A group owns one
@@ -935,6 +984,11 @@ int pcl_group_step_phase_layered(pcl_group *group, int n_laws, const int *kinds_
 int pcl_group_step_recycle_spent(pcl_group *group, const pcl_source *src, double c, int at_rest, double top,
                                  const double *center_host, int n_E, const double *cdf_host, const double *grid_host, uint64_t seed,
                                  uint32_t pass, int64_t *counts_out_host);
+/* pcl_step_absorb_path on every shard (side by side), the counts and the cells summed over the group's devices; the arguments are
+ * checked once for the group, before any shard is written (ids are global: the same photons are absorbed) */
+int pcl_group_step_absorb_path(pcl_group *group, int n_layers, int n_E_bins, const double *p_host, const double *edges_host,
+                               const double *center_host, const double *E_edges_host, uint64_t seed, uint32_t pass,
+                               int64_t *counts_out_host, int64_t *cells_out_host);
 
 /* ---------------------------------------------------------------- the counters' collective (one process per GPU)
  * The path shards by global index with no data-path exchange; the only global quantities are the int64

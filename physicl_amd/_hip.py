@@ -33,6 +33,7 @@ PHASE_FUNCTIONS = {"isotropic": 0, "hg": 1, "rayleigh": 2}                   # P
 PHASE_TABLE = 3                                                              # PCL_PHASE_TABLE: a law of pcl_step_phase_layered only
 LPHASE_MAX_LAWS, LPHASE_MAX_LAYERS, LPHASE_MAX_NODES, LPHASE_MAX_TOTAL_NODES = 8, 64, 1024, 2048       # PCL_LPHASE_MAX_LAWS ...
 RECYCLE_MAX_BINS = 1024                                                      # PCL_RECYCLE_MAX_BINS: bins of a RecycleStep's spectrum
+PATH_ABSORB_MAX_LAYERS, PATH_ABSORB_MAX_BANDS, PATH_ABSORB_MAX_CELLS = 64, 1024, 4096          # PCL_PATH_ABSORB_MAX_LAYERS ...
 PROF_NEWTON, PROF_SCATTER, PROF_DELETE_MASK, PROF_COMPACT, PROF_COUNTERS, PROF_FUSED, PROF_MULTI, PROF_ONEPASS, \
     PROF_DELETE_AHEAD = range(9)
 PROF_NAMES = {PROF_NEWTON: "k_newton", PROF_SCATTER: "k_scatter", PROF_DELETE_MASK: "k_delete_mask",
@@ -159,6 +160,7 @@ _PROTOTYPES = {
     "pcl_step_absorb_scattered": [_vp, c_int, _vp, _vp, _vp, c_int, _vp, c_uint64, c_uint32, _vp, _vp],
     "pcl_step_phase_layered": [_vp, c_int, _vp, _vp, _vp, _vp, _vp, c_int, _vp, _vp, _vp, c_double, c_uint64, c_uint32, _vp],
     "pcl_step_recycle_spent": [_vp, _vp, c_double, c_int, c_double, _vp, c_int, _vp, _vp, c_uint64, c_uint32, _vp],
+    "pcl_step_absorb_path": [_vp, c_int, c_int, _vp, _vp, _vp, _vp, c_uint64, c_uint32, _vp, _vp],
     # device groups: several GPUs from one process (the C-level counterpart of physicl_amd.multidev.MultiDevice)
     "pcl_group_create": [c_int, POINTER(c_int), POINTER(_vp)],
     "pcl_group_destroy": [_vp],
@@ -190,6 +192,7 @@ _PROTOTYPES = {
     "pcl_group_step_absorb_scattered": [_vp, c_int, _vp, _vp, _vp, c_int, _vp, c_uint64, c_uint32, _vp, _vp],
     "pcl_group_step_phase_layered": [_vp, c_int, _vp, _vp, _vp, _vp, _vp, c_int, _vp, _vp, _vp, c_double, c_uint64, c_uint32, _vp],
     "pcl_group_step_recycle_spent": [_vp, _vp, c_double, c_int, c_double, _vp, c_int, _vp, _vp, c_uint64, c_uint32, _vp],
+    "pcl_group_step_absorb_path": [_vp, c_int, c_int, _vp, _vp, _vp, _vp, c_uint64, c_uint32, _vp, _vp],
 }
 EXPORTS = sorted(list(_PROTOTYPES) + ["pcl_last_error"])
 
@@ -453,6 +456,26 @@ def _recycle(entry, handle, src, c, at_rest, top, center, spectrum, seed, n_pass
                 0 if cdf is None else len(cdf), ptr(cdf), ptr(grid), int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_pass) & 0xFFFFFFFF,
                 counts.ctypes.data))
     return int(counts[0]), int(counts[1])
+
+
+def _absorb_path(entry, handle, p, edges, center, E_edges, seed, n_pass):
+    """One call of pcl_step_absorb_path / pcl_group_step_absorb_path: (exposed, absorbed, absorbed_by_cell int64[L', B']).  ``p``: the
+    probability of absorption per pass, L' = max(layers, 1) rows of B' = max(bands, 1) values (any shape of that size); the edges go
+    over as given (the library squares the radii); ``n_pass``: the caller's own pass counter (a Philox counter word)."""
+    pr = np.ascontiguousarray(p, dtype=np.float64).reshape(-1)
+    ed = None if edges is None else np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+    Ee = None if E_edges is None else np.ascontiguousarray(E_edges, dtype=np.float64).reshape(-1)
+    L, B = (0 if e is None else len(e) - 1 for e in (ed, Ee))
+    rows, cols = max(L, 1), max(B, 1)
+    if len(pr) != rows * cols:
+        raise ValueError("p holds %d values for %d layers of %d bands" % (len(pr), rows, cols))
+    ce = None if center is None else np.ascontiguousarray(center, dtype=np.float64).reshape(3)
+    counts = np.zeros(2, dtype=np.int64)
+    cells = np.zeros((rows, cols), dtype=np.int64)
+    ptr = lambda a: None if a is None else a.ctypes.data                                                       # noqa: E731
+    check(entry(handle, L, B, pr.ctypes.data, ptr(ed), ptr(ce), ptr(Ee), int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_pass) & 0xFFFFFFFF,
+                counts.ctypes.data, cells.ctypes.data))
+    return int(counts[0]), int(counts[1]), cells
 
 
 def _scatter(sc, required=False, lazy=False, empty_expr=b""):
@@ -1043,6 +1066,13 @@ class Device:
         dv = 0, and -- with ``spectrum=(grid, cdf)`` -- a new E; ids and kinds stay.  ``(at_rest, escaped)``.  RecycleStep."""
         return _recycle(self.lib.pcl_step_recycle_spent, self.ctx, src, c, at_rest, top, center, spectrum, seed, n_pass)
 
+    def absorb_path(self, p, edges=None, center=None, E_edges=None, seed=0, n_pass=0):
+        """Every moving photon is absorbed with the probability ``p`` of the radial layer (``edges`` about ``center``) it stands in
+        and the band (``E_edges``) its energy falls in -- ``p``: max(L, 1) rows of max(B, 1) values --, and is left at rest where it is
+        (v = 0, dv = 0), in one sweep (pcl_step_absorb_path).  ``(exposed, absorbed, absorbed_by_cell int64[L', B'])``.
+        PathAbsorptionStep."""
+        return _absorb_path(self.lib.pcl_step_absorb_path, self.ctx, p, edges, center, E_edges, seed, n_pass)
+
 
 class DeviceGroup:
     """``pcl_group_*``: several contexts in one process, sharded by global index, behind the C ABI (the shim owns the
@@ -1162,6 +1192,10 @@ class DeviceGroup:
     def recycle_spent(self, src, c, at_rest=True, top=None, center=None, spectrum=None, seed=0, n_pass=0):
         """``Device.recycle_spent`` on every context of the group, the counts summed (pcl_group_step_recycle_spent)."""
         return _recycle(self.lib.pcl_group_step_recycle_spent, self.g, src, c, at_rest, top, center, spectrum, seed, n_pass)
+
+    def absorb_path(self, p, edges=None, center=None, E_edges=None, seed=0, n_pass=0):
+        """``Device.absorb_path`` on every context of the group, the tallies summed (pcl_group_step_absorb_path)."""
+        return _absorb_path(self.lib.pcl_group_step_absorb_path, self.g, p, edges, center, E_edges, seed, n_pass)
 
     def download(self, field, n=None, offset=0, dtype=None):
         n = self.count - offset if n is None else n

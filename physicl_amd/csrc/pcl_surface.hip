@@ -102,6 +102,23 @@
 //   rest = at_rest and v0 == 0 and v1 == 0 and v2 == 0;  d = r - center;  q = d.d;  gone = a top, not rest and q > top*top
 //   spent iff a photon and (rest or gone);  direction: counter (id_lo, id_hi, pass, 14), position: (id_lo, id_hi, pass, 15), by the
 //   arithmetic of pcl_store_apply_source;  dr = dv = 0;  E = grid[x], the first x with cdf[x] >= u53(w0, w1) of (id_lo, id_hi, pass, 16)
+//
+// Absorption along the path (PathAbsorptionStep): a gas that absorbs without scattering.  Every moving photon is exposed once per
+// pass; the chance that it is absorbed over the move it has made, p = 1 - exp(-k c dt), is made on the host per radial layer and
+// energy band, and the kernel only compares a draw with it.
+//
+//   k_absorb_path<T>       one grid-stride sweep: per slot v0 (a lane at rest -- k_recycle_spent's test -- loads v1 and v2 as well and
+//                          nothing more; a moving lane is decided by v0 alone); moving lanes load, with layers, r and look q up in
+//                          the squared edges (the absorber's search) and, with bands, E and look it up in the energy edges; a lane
+//                          with a layer and a band is exposed, and if its cell's p is not zero it loads its id and draws; absorbed
+//                          lanes write zeros to v and dv and add to their cell.  Two ballots + popcounts per wave for the two
+//                          counters.  The tables (p, squared edges, energy edges) sit in dynamic LDS in front of the
+//                          workgroup-private uint32 cells [exposed, absorbed | by cell].  r, dr and E are never written.
+//
+// Operation order (what light._absorb_path restates with numpy):
+//   moving iff not (v0 == 0 and v1 == 0 and v2 == 0), a photon;  b: the absorber's layer of q (no layers: 0);  e: the bin of E in the
+//   energy edges, the last one closed (no bands: 0);  exposed iff both exist;  p = P[b][e];  p > 0: u = u53(w0, w1) of counter
+//   (id_lo, id_hi, pass, 17);  absorbed iff u < p:  v_k = 0;  dv_k = 0
 #include "pcl_sweep.h"
 
 #include "pcl_device.h" // (after the HIP runtime and the ABI's header, which pcl_sweep.h brings)
@@ -651,6 +668,89 @@ __global__ void __launch_bounds__(kBlock) k_recycle_spent(recycle_args<T> a) {
     __syncthreads();
     // pcl_sweep::flush_cells, written out, for the reason given in k_absorb_scattered: a further caller changes the older kernels
     for (int k = threadIdx.x; k < 2; k += kBlock)
+        if (s_cnt[k]) atomicAdd(&a.out[k], (unsigned long long)s_cnt[k]);
+}
+
+// The counter word of the draw along the path (the header lists who uses which word: 17 is this kernel's alone).
+constexpr uint32_t kPathAbsorbWord = 17;
+
+template <typename T>
+struct pabsorb_args {
+    const T *r[3];               // read only with layers
+    T *v[3], *dv[3];
+    const T *E;                  // NULL without energy bands
+    const unsigned char *kind;   // NULL: every particle is a photon
+    const int64_t *ids;          // NULL: the id of slot i is id_base + i
+    const double *tables;        // p (L' x B') | e*e of the layer edges (L + 1, if L) | E edges (B + 1, if B), device
+    unsigned long long *out;     // exposed, absorbed | absorbed by cell [L' x B']; device, zeroed by the entry point
+    int64_t N, ts, id_base;      // particles, tile stride of the slab (elements), id of slot 0
+    int tile_log;                // log2 of the tile length
+    int n_layers, n_E;           // L (0: one row of p everywhere, L' = 1), B (0: one column for every energy, B' = 1)
+    double c[3];
+    uint32_t k0, k1, pass;       // Philox key (seed_lo, seed_hi), the step's own pass counter
+};
+
+template <typename T>
+__global__ void __launch_bounds__(kBlock) k_absorb_path(pabsorb_args<T> a) {
+    extern __shared__ double s_mem[];                                  // p | e*e | E edges | exposed, absorbed | by cell
+    const int L = a.n_layers, Lp = L > 0 ? L : 1, nE = a.n_E, Bp = nE > 0 ? nE : 1;
+    const int n_tab = Lp * Bp + (L ? L + 1 : 0) + (nE ? nE + 1 : 0);
+    const int n_cells = 2 + Lp * Bp;
+    const double *s_p = s_mem;
+    const double *s_e2 = s_p + Lp * Bp;
+    const double *s_E = s_e2 + (L ? L + 1 : 0);
+    uint32_t *s_cnt = reinterpret_cast<uint32_t *>(s_mem + n_tab);
+    uint32_t *s_cell = s_cnt + 2;
+    for (int k = threadIdx.x; k < n_tab; k += kBlock) s_mem[k] = a.tables[k];
+    for (int k = threadIdx.x; k < n_cells; k += kBlock) s_cnt[k] = 0;  // (the cells follow the two counts)
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    // whole waves run the same number of trips (the ballots below need every lane of the wave inside the loop)
+    const int64_t n_round = (a.N + 63) / 64 * 64;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n_round; i += stride) {
+        const bool in = i < a.N;
+        const int64_t ti = tile_index(i, a.tile_log, a.ts);
+        // moving: k_recycle_spent's "at rest", negated -- -0.0 == 0, a NaN moves, and a lane whose v0 is not zero loads no more of v
+        bool go = in && !((double)a.v[0][ti] == 0.0 && (double)a.v[1][ti] == 0.0 && (double)a.v[2][ti] == 0.0);
+        if (go && a.kind) go = a.kind[i] != 0;                          // plain Objects are never touched
+        int b = go && L == 0 ? 0 : -1;                                  // the layer; -1: in no layer
+        if (go && L > 0) {
+            double x[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) x[k] = __dsub_rn((double)a.r[k][ti], a.c[k]);   // fp32 widens exactly
+            const double q = dot3(x, x);
+            if (q >= s_e2[0] && q <= s_e2[L]) b = bin_of(s_e2, L, q);   // NaN: in no layer
+        }
+        int cell = b >= 0 && nE == 0 ? b : -1;                          // b * B' + e; -1: not exposed
+        if (b >= 0 && nE > 0) {
+            const double e = (double)a.E[ti];
+            if (e >= s_E[0] && e <= s_E[nE]) cell = b * nE + bin_of(s_E, nE, e);         // NaN and under/overflow: in no band
+        }
+        const bool exposed = cell >= 0;
+        bool gone = false;
+        if (exposed) {
+            const double p = s_p[cell];
+            if (p > 0.0) {                                              // a transparent cell draws nothing
+                const uint64_t id = (uint64_t)(a.ids ? a.ids[i] : a.id_base + i);
+                const pcl_u32x4 w = pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, kPathAbsorbWord, a.k0, a.k1);
+                gone = pcl_u53(w.x, w.y) < p;                           // u < 1: p == 1 absorbs everybody
+            }
+        }
+        const uint32_t n_exp = (uint32_t)__popcll(__ballot(exposed)), n_gone = (uint32_t)__popcll(__ballot(gone));
+        if (lane == 0 && n_exp) atomicAdd(&s_cnt[0], n_exp);
+        if (lane == 0 && n_gone) atomicAdd(&s_cnt[1], n_gone);
+        if (!gone) continue;    // lanes that are left alone wait at the loop's head: no ballot below this line
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {                                   // parked where it is, at rest; "did not scatter"
+            a.v[k][ti] = (T)0.0;
+            a.dv[k][ti] = (T)0.0;
+        }
+        atomicAdd(&s_cell[cell], 1u);
+    }
+    __syncthreads();
+    // pcl_sweep::flush_cells, written out, for the reason given in k_absorb_scattered: the count is not a literal
+    for (int k = threadIdx.x; k < n_cells; k += kBlock)
         if (s_cnt[k]) atomicAdd(&a.out[k], (unsigned long long)s_cnt[k]);
 }
 
@@ -1205,6 +1305,128 @@ int group_recycle_spent(pcl_group *group, const pcl_source *src, double c, int a
     return PCL_OK;
 }
 
+struct pabsorb_spec { // a call's arguments, checked; what the kernel compares against
+    int n_layers = 0, n_E = 0;
+    double c[3] = {0.0, 0.0, 0.0};
+    bool draws = false;         // some cell has p > 0: the ids are needed
+    std::vector<double> tables; // p | e*e | E edges
+    size_t rows() const { return n_layers > 0 ? (size_t)n_layers : 1; }
+    size_t cols() const { return n_E > 0 ? (size_t)n_E : 1; }
+    size_t cells() const { return (size_t)2 + rows() * cols(); }       // exposed, absorbed | by cell
+    size_t lds() const { return tables.size() * sizeof(double) + cells() * sizeof(uint32_t); }
+};
+
+// Everything PCL_ERR_ARG stands for except the NULL context; nothing is launched or written before this has passed.
+bool check_pabsorb(int n_layers, int n_E, const double *p, const double *edges, const double *center, const double *E_edges,
+                   const int64_t *counts_out, const int64_t *cells_out, pabsorb_spec &s) {
+    if (!p || !counts_out || !cells_out || n_layers < 0 || n_layers > PCL_PATH_ABSORB_MAX_LAYERS) return false;
+    if (n_E < 0 || n_E > PCL_PATH_ABSORB_MAX_BANDS) return false;
+    s.n_layers = n_layers; s.n_E = n_E;
+    const size_t n_p = s.rows() * s.cols();
+    if (n_p > PCL_PATH_ABSORB_MAX_CELLS) return false;                  // the workgroup's cells and tables stay below 64 KiB of LDS
+    for (size_t k = 0; k < n_p; ++k) {
+        if (!(p[k] >= 0.0 && p[k] <= 1.0)) return false;                // (NaN as well)
+        s.draws = s.draws || p[k] > 0.0;
+        s.tables.push_back(p[k]);
+    }
+    if (n_layers > 0 && (!edges || !check_edges(edges, n_layers, kEdgeSquare, &s.tables))) return false;
+    if (n_E > 0 && (!E_edges || !check_edges(E_edges, n_E, kEdgePlain, &s.tables))) return false;
+    if (center)
+        for (int k = 0; k < 3; ++k) {
+            if (!std::isfinite(center[k])) return false;
+            s.c[k] = center[k];
+        }
+    return true;
+}
+
+void zero_pabsorb(const pabsorb_spec &s, int64_t *counts, int64_t *cells) {
+    counts[0] = counts[1] = 0;
+    memset(cells, 0, (s.cells() - 2) * sizeof(int64_t));
+}
+
+template <typename T>
+int launch_pabsorb(pcl_ctx *ctx, const store_view &v, const pabsorb_spec &s, uint64_t seed, uint32_t pass, int64_t id_base,
+                   const int64_t *ids, const unsigned char *kind, const double *tables_dev, unsigned long long *out_dev) {
+    pabsorb_args<T> a{};
+    for (int k = 0; k < 3; ++k) {
+        void *r = nullptr, *vel = nullptr, *dv = nullptr;
+        if (s.n_layers > 0) PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_R0 + k, &r));
+        PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_V0 + k, &vel));
+        PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_DV0 + k, &dv));     // (what makes a lazy dv real: an absorbed photon's is written)
+        a.r[k] = static_cast<const T *>(r); a.v[k] = static_cast<T *>(vel); a.dv[k] = static_cast<T *>(dv);
+        a.c[k] = s.c[k];
+    }
+    // E is asked for only with energy bands: the pointer costs a wavelength-dependent scatter step its term cache (pcl_shell.hip).
+    void *E = nullptr;
+    if (s.n_E > 0) PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_E, &E));
+    a.E = static_cast<const T *>(E); a.kind = kind; a.ids = ids; a.tables = tables_dev; a.out = out_dev;
+    a.N = v.N; a.ts = v.ts; a.id_base = id_base; a.tile_log = v.tile_log;
+    a.n_layers = s.n_layers; a.n_E = s.n_E;
+    a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32); a.pass = pass;
+    const size_t lds = s.lds();                                         // what this call uses: 24 B for a grey gas everywhere
+    const int64_t grid = balanced_grid(v.N, v.n_cu, resident_per_cu(lds));
+    hipLaunchKernelGGL(k_absorb_path<T>, dim3((unsigned)grid), dim3(kBlock), lds, v.stream, a);
+    return hipGetLastError() == hipSuccess ? PCL_OK : PCL_ERR_HIP;
+}
+
+int absorb_path(pcl_ctx *ctx, int n_layers, int n_E_bins, const double *p_host, const double *edges_host, const double *center_host,
+                const double *E_edges_host, uint64_t seed, uint32_t pass, int64_t *counts_out_host, int64_t *cells_out_host) {
+    pabsorb_spec s;
+    if (!ctx || !check_pabsorb(n_layers, n_E_bins, p_host, edges_host, center_host, E_edges_host, counts_out_host, cells_out_host, s))
+        return bad_argument(ctx);
+    store_view v;
+    PCL_SWEEP_TRY(open_store(ctx, PCL_V0, &v));
+    zero_pabsorb(s, counts_out_host, cells_out_host);
+    if (v.N <= 0) return PCL_OK;
+    std::vector<uint8_t> kind_host;                                     // a store that is not uniform: as surface_reflect;
+    std::vector<int64_t> ids_host;                                      // the ids only if somebody may draw
+    bool mixed = false;
+    int64_t id_base = 0;
+    PCL_SWEEP_TRY(kind_bytes(ctx, v.N, kind_host, &mixed));
+    if (s.draws) PCL_SWEEP_TRY(id_words(ctx, v.N, ids_host, &id_base));
+    const size_t cells = s.cells();
+    const size_t out_bytes = cells * sizeof(uint64_t), tab_bytes = s.tables.size() * sizeof(double);
+    const size_t id_bytes = ids_host.size() * sizeof(int64_t);
+    dev_block blk(ctx);
+    PCL_SWEEP_TRY(stage(blk, v.stream, out_bytes, s.tables.data(), tab_bytes, kind_host, ids_host));
+    char *base = static_cast<char *>(blk.p);
+    const double *tables_dev = reinterpret_cast<const double *>(base + out_bytes);
+    const int64_t *ids = id_bytes ? reinterpret_cast<const int64_t *>(base + out_bytes + tab_bytes) : nullptr;
+    const unsigned char *kind = mixed ? reinterpret_cast<const unsigned char *>(base + out_bytes + tab_bytes + id_bytes) : nullptr;
+    unsigned long long *out_dev = reinterpret_cast<unsigned long long *>(base);
+    PCL_SWEEP_TRY(v.dtype == PCL_DTYPE_F64 ? launch_pabsorb<double>(ctx, v, s, seed, pass, id_base, ids, kind, tables_dev, out_dev)
+                                           : launch_pabsorb<float>(ctx, v, s, seed, pass, id_base, ids, kind, tables_dev, out_dev));
+    std::vector<int64_t> out(cells);
+    PCL_SWEEP_TRY(pcl_d2h(ctx, out.data(), base, (int64_t)out_bytes)); // the call's one synchronisation (a count is below 2^63)
+    counts_out_host[0] = out[0]; counts_out_host[1] = out[1];
+    memcpy(cells_out_host, out.data() + 2, (cells - 2) * sizeof(int64_t));
+    return PCL_OK;
+}
+
+int group_absorb_path(pcl_group *group, int n_layers, int n_E_bins, const double *p_host, const double *edges_host,
+                      const double *center_host, const double *E_edges_host, uint64_t seed, uint32_t pass, int64_t *counts_out_host,
+                      int64_t *cells_out_host) {
+    std::vector<pcl_ctx *> ctx;
+    PCL_SWEEP_TRY(shards_of(group, ctx));
+    const int n = (int)ctx.size();
+    pabsorb_spec s;
+    if (n < 1 || !check_pabsorb(n_layers, n_E_bins, p_host, edges_host, center_host, E_edges_host, counts_out_host, cells_out_host, s))
+        return bad_argument(n > 0 ? ctx[0] : nullptr);
+    const size_t cells = s.cells();
+    std::vector<std::vector<int64_t>> part((size_t)n, std::vector<int64_t>(cells, 0));
+    PCL_SWEEP_TRY(for_each_shard(ctx, [&](int g, pcl_ctx *one) {
+        int64_t *p = part[(size_t)g].data();
+        return pcl_step_absorb_path(one, n_layers, n_E_bins, p_host, edges_host, center_host, E_edges_host, seed, pass, p, p + 2);
+    }));
+    zero_pabsorb(s, counts_out_host, cells_out_host);
+    for (int g = 0; g < n; ++g) {
+        const int64_t *p = part[(size_t)g].data();
+        counts_out_host[0] += p[0]; counts_out_host[1] += p[1];
+        for (size_t k = 2; k < cells; ++k) cells_out_host[k - 2] += p[k];
+    }
+    return PCL_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -1277,6 +1499,24 @@ int pcl_group_step_recycle_spent(pcl_group *group, const pcl_source *src, double
                                  int64_t *counts_out_host) {
     return guarded([&] {
         return group_recycle_spent(group, src, c, at_rest, top, center_host, n_E, cdf_host, grid_host, seed, pass, counts_out_host);
+    });
+}
+
+int pcl_step_absorb_path(pcl_ctx *ctx, int n_layers, int n_E_bins, const double *p_host, const double *edges_host,
+                         const double *center_host, const double *E_edges_host, uint64_t seed, uint32_t pass, int64_t *counts_out_host,
+                         int64_t *cells_out_host) {
+    return guarded([&] {
+        return absorb_path(ctx, n_layers, n_E_bins, p_host, edges_host, center_host, E_edges_host, seed, pass, counts_out_host,
+                           cells_out_host);
+    });
+}
+
+int pcl_group_step_absorb_path(pcl_group *group, int n_layers, int n_E_bins, const double *p_host, const double *edges_host,
+                               const double *center_host, const double *E_edges_host, uint64_t seed, uint32_t pass,
+                               int64_t *counts_out_host, int64_t *cells_out_host) {
+    return guarded([&] {
+        return group_absorb_path(group, n_layers, n_E_bins, p_host, edges_host, center_host, E_edges_host, seed, pass, counts_out_host,
+                                 cells_out_host);
     });
 }
 

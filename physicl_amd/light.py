@@ -1638,6 +1638,180 @@ class RecycleStep(DeviceStep, MeasureStep):
         return DeviceStep.run(self, sim)
 
 
+# ---------------------------------------------------------------------------------------------- absorption along the path
+def _check_path_absorb(k, edges, center, E_edges):
+    """(k as a float64 array [max(L, 1)][max(B, 1)], edges or None, centre, energy edges or None) of a PathAbsorptionStep, or
+    ValueError for everything pcl_step_absorb_path would refuse."""
+    from ._hip import PATH_ABSORB_MAX_BANDS, PATH_ABSORB_MAX_CELLS, PATH_ABSORB_MAX_LAYERS      # (the header's limits: one place)
+    try:
+        ka = np.array(k, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("k must be a number, or numbers per layer and / or energy band") from None
+    if edges is not None:
+        edges = tally.check_edges("edges", edges, PATH_ABSORB_MAX_LAYERS, "square")        # (the device compares q with e*e)
+    if E_edges is not None:
+        E_edges = tally.check_edges("E_edges", E_edges, PATH_ABSORB_MAX_BANDS)
+    want = tuple(len(e) - 1 for e in (edges, E_edges) if e is not None)
+    if ka.shape != want:
+        raise ValueError("k must have the shape %r -- %s -- got %r" % (want, {
+            (False, False): "one number without edges and E_edges", (True, False): "one value per layer of edges",
+            (False, True): "one value per band of E_edges", (True, True): "layers of edges by bands of E_edges"}[
+                (edges is not None, E_edges is not None)], ka.shape))
+    if not np.all(np.isfinite(ka) & (ka >= 0.0)):             # (False for NaN as well)
+        raise ValueError("k must be finite and not negative, got %r" % (k,))
+    rows, cols = (1 if e is None else len(e) - 1 for e in (edges, E_edges))
+    if rows * cols > PATH_ABSORB_MAX_CELLS:
+        raise ValueError("k: %d layers of edges x %d bands of E_edges are %d cells, at most %d are supported" % (rows, cols, rows * cols, PATH_ABSORB_MAX_CELLS))
+    return np.ascontiguousarray(ka.reshape(rows, cols)), edges, tally.check_center(center), E_edges
+
+
+def _path_probability(k, c, dt):
+    """The chance that a photon is absorbed over one pass's move, float64: ``tau = k * (c * dt)``, ``p = -expm1(-tau)`` -- made on the
+    host, the device only ever sees ``p``.  ValueError for a ``dt`` that is not finite or is negative."""
+    try:
+        dt = float(np.asarray(dt, dtype=np.float64).reshape(()))
+    except (TypeError, ValueError):
+        raise ValueError("dt must be a number, got %r" % (dt,)) from None
+    if not (np.isfinite(dt) and dt >= 0.0):
+        raise ValueError("dt must be finite and not negative, got %r" % (dt,))
+    with np.errstate(over="ignore"):
+        tau = np.asarray(k, dtype=np.float64) * (np.float64(c) * np.float64(dt))
+    return -np.expm1(-tau)
+
+
+_PATH_ABSORB_WORD = 17                                        # the draw's counter word (the header lists the words taken)
+
+
+def _absorb_path(r, v, dv, E, photon, ids, p, edges, center, E_edges, seed, n_pass, dtype=np.float64):
+    """What pcl_step_absorb_path makes of (n, 3) float64 positions, velocities and last velocity changes, the energies, who is a
+    photon and the particles' ids, with numpy -- every operation the device's operation in the device's order, one rounding each
+    (include/physicl_hip.h): no transcendental function, no division and no square root, so everything is the device's bit for bit.
+    ``p``: the probabilities, max(L, 1) rows of max(B, 1) values.  What is written is zero, in any ``dtype``.  A dict: ``v, dv`` the new
+    state (float64 arrays; rows that are not absorbed are the arguments'), the boolean masks ``exposed`` and ``absorbed``, ``layer``
+    and ``band`` (int64: of every moving photon, -1 for none) and the tally ``absorbed_by_cell`` (int64 [L', B'])."""
+    r, v, dv = (np.array(a, dtype=np.float64).reshape(-1, 3) for a in (r, v, dv))
+    n = len(v)
+    rows, cols = (1 if e is None else len(e) - 1 for e in (edges, E_edges))
+    p = np.asarray(p, dtype=np.float64).reshape(rows, cols)
+    with np.errstate(invalid="ignore", over="ignore"):
+        rest = (v[:, 0] == 0) & (v[:, 1] == 0) & (v[:, 2] == 0)                     # -0.0 == 0; a NaN moves
+        at = np.flatnonzero(~rest & np.asarray(photon, dtype=bool).reshape(-1))
+        layer, band = np.full(n, -1, dtype=np.int64), np.full(n, -1, dtype=np.int64)
+        if edges is None:
+            layer[at] = 0
+        else:
+            e = np.asarray(edges, dtype=np.float64)
+            e2 = e * e
+            d = r[at] - np.asarray(center, dtype=np.float64)
+            q = _dot3(d, d)
+            inside = (q >= e2[0]) & (q <= e2[-1])                                   # NaN: in no layer
+            layer[at[inside]] = np.clip(np.searchsorted(e2, q[inside], side="right") - 1, 0, rows - 1)   # the last layer is closed
+        at = at[layer[at] >= 0]
+        if E_edges is None:
+            band[at] = 0
+        else:                                                  # numpy.histogram's bins: [e_b, e_b+1), the last one closed
+            eb, val = np.asarray(E_edges, dtype=np.float64), np.asarray(E, dtype=np.float64).reshape(-1)[at]
+            ok = (val >= eb[0]) & (val <= eb[-1])                                   # NaN and under/overflow: in no band
+            band[at[ok]] = np.clip(np.searchsorted(eb, val[ok], side="right") - 1, 0, cols - 1)
+    exposed = band >= 0
+    draws = np.flatnonzero(exposed)
+    draws = draws[p[layer[draws], band[draws]] > 0.0]          # a transparent cell draws nothing
+    u = _philox_block(np.asarray(ids).reshape(-1)[draws], seed, n_pass, _PATH_ABSORB_WORD)[0]
+    gone = draws[u < p[layer[draws], band[draws]]]
+    absorbed = np.zeros(n, dtype=bool)
+    absorbed[gone] = True
+    v[gone], dv[gone] = np.zeros(3, dtype=dtype), np.zeros(3, dtype=dtype)
+    cells = np.bincount(layer[gone] * cols + band[gone], minlength=rows * cols).astype(np.int64).reshape(rows, cols)
+    return {"v": v, "dv": dv, "exposed": exposed, "absorbed": absorbed, "layer": layer, "band": band, "absorbed_by_cell": cells}
+
+
+class PathAbsorptionStep(DeviceStep, MeasureStep):
+    """A gas that absorbs without scattering (not in the reference): continuous, Beer-Lambert absorption along the move every photon
+    makes in a pass, with a coefficient that depends on the radial layer the photon stands in and on the band its energy falls in --
+    ozone above a thin Rayleigh atmosphere, a water-vapour band.  ``AbsorptionStep`` acts on the photons the scatter step made
+    interact, and its ``omega0`` is grey; this step needs no scatter step at all.  It stands anywhere BEHIND the Newton step of a pass
+    (before or behind the scatter, phase, absorption and ground steps) and before a ``RecycleStep``.  In front of a
+    ``SurfaceReflectStep`` let the innermost edge be the ground's radius or above it: the ground decides by ``r`` and ``dr`` alone, so a
+    photon parked below it would be bounced off again; one that stands in no layer is left to the ground.
+
+    * ``k``: the absorption coefficient per unit length (code units), finite and not negative: one number; ``[L]`` numbers with
+      ``edges`` only; ``[B]`` with ``E_edges`` only; ``[L][B]`` with both.
+    * ``edges``: ``L + 1`` finite, non-negative, strictly increasing radii about ``center`` (at most 64 layers), ``AbsorptionStep``'s
+      rule exactly: layer ``b`` holds a photon iff ``e_b**2 <= q < e_(b+1)**2``, the last layer closed, ``q = (d0*d0 + d1*d1) + d2*d2``
+      in float64; no square root is taken; a NaN is in no layer.
+    * ``E_edges``: ``B + 1`` finite, strictly increasing energy edges in the unit E is stored in (at most 1024 bands, and at most 4096
+      cells of layers x bands): ``numpy.histogram``'s bins, the last one closed; a NaN or an energy outside the edges is in no band.
+      Without ``E_edges`` the gas is grey and E is not even asked for, so a wavelength-dependent scatter step keeps its term cache;
+      with them that cache is dropped every pass (the library has no read-only access to E).
+
+    A photon moves ``c*dt`` in every pass -- across a bounce off the ground too --, so the path length is not read from the store:
+    per pass the host makes ``tau = k * (c * dt)`` from the simulation's current ``dt`` and ``p = -numpy.expm1(-tau)`` in float64
+    (``_path_probability``), and the device only ever sees ``p``.  A ``dt`` that is not finite or is negative is refused.
+
+    Every moving photon with a layer and a band is EXPOSED; a photon at rest (``v == (0, 0, 0)``; ``-0.0`` counts as 0, a NaN moves), a
+    plain ``Object`` and a photon in no layer or no band are skipped.  An exposed photon is absorbed iff ``u < p`` (``p == 0`` draws
+    nothing, ``p == 1`` absorbs every one), ``u`` from a Philox block keyed by ``sim.seed``, the photon's id and a pass counter of the
+    step's own, in a counter word no other kernel uses (17): every other step draws what it draws without this one, and a photon
+    draws the same number however the run is sharded.  An absorbed photon is parked at rest where it is, ``v = 0`` and ``dv = 0`` --
+    ``AbsorptionStep``'s convention and for its reason: a phase or absorption step later in the pass leaves it alone, and
+    ``RecycleStep(at_rest=True)`` gives its slot back to the source.  A photon that is not absorbed is not written at all; ``r``,
+    ``dr``, ``E``, ids and kinds are never written.  The analog treatment keeps E the photon's colour (it is no statistical weight).
+
+    After each run ``self.exposed`` and ``self.absorbed`` hold the pass's counts and ``self.absorbed_by_cell`` an int64 array
+    ``[max(L, 1)][max(B, 1)]`` -- a heating profile by colour --, global over shards and ranks; ``self.data`` gains the row ``[t,
+    exposed, absorbed, absorbed_by_cell]``; ``out_fn`` takes the rows at the end.  The rule is written out in include/physicl_hip.h
+    (pcl_step_absorb_path); ``_absorb_path`` restates every bit of it with numpy.  The step reads no ``dv`` rule, so it works under
+    ``cl_on=False`` as well.
+
+    One launch per light step: the K-passes-per-launch kernels cannot absorb a photon between two of their passes, and
+    ``sim.launch_note`` says so.  On host-resident objects (``step.run(sim)`` outside a device loop) the same state is made with
+    numpy, the ids being the places in the object list."""
+    _fuse_role = None
+    _NOTE = "one launch per light step: a PathAbsorptionStep absorbs moving photons behind every pass, which the " \
+            "K-passes-per-launch kernels cannot carry"
+
+    def __init__(self, k, edges=None, center=(0, 0, 0), E_edges=None, out_fn=None):
+        MeasureStep.__init__(self, out_fn)
+        self.k, self.edges, self.center, self.E_edges = _check_path_absorb(k, edges, center, E_edges)
+        self.exposed = self.absorbed = 0
+        self.absorbed_by_cell = np.zeros(self.k.shape, dtype=np.int64)
+        self._pass = 0                                   # the step's own Philox counter word: one per run
+
+    def _record_pass(self, sim, exposed, absorbed, cells):
+        self.exposed, self.absorbed = int(exposed), int(absorbed)
+        self.absorbed_by_cell = np.array(cells, dtype=np.int64).reshape(self.k.shape)
+        self.data.append(tally.object_row([tally._snap(sim.t), self.exposed, self.absorbed, self.absorbed_by_cell.copy()]))
+
+    def _device_run(self, sim):
+        p = _path_probability(self.k, _c_h_literals()[0], sim._dt_code())
+        if getattr(sim, "launch_note", self._NOTE) is None and sim._k_wanted() > 1:      # (a device run only: the host path says nothing)
+            sim.launch_note = self._NOTE
+        self._pass += 1
+        exposed, absorbed, cells = sim._dev.absorb_path(p, self.edges, self.center, self.E_edges, sim.seed, self._pass)
+        sim._scattered = True                            # velocities were replaced on the device
+        # (every rank issues it, also with an empty shard)
+        _, (both, cells) = tally.reduce_parts(sim, [np.array([exposed, absorbed], dtype=np.int64), np.asarray(cells, dtype=np.int64)])
+        self._record_pass(sim, both[0], both[1], cells)
+
+    def run(self, sim):
+        if getattr(sim, "_residency", None) == "host" and getattr(sim, "_batch", None) is None \
+                and (sim.comm is None or sim.comm.world == 1):
+            p = _path_probability(self.k, _c_h_literals()[0], np.asarray(sim.dt))
+            objs = list(sim.objects)
+            self._pass += 1
+            E, photon = tally.photon_energies(objs, PhotonObject)
+            new = _absorb_path(tally.vec3(objs, "r"), tally.vec3(objs, "v"), tally.vec3(objs, "dv"), E, photon, np.arange(len(objs)), p,
+                               self.edges, self.center, self.E_edges, getattr(sim, "seed", 0), self._pass)
+            for k in np.flatnonzero(new["absorbed"]).tolist():
+                o = objs[k]
+                o.v, o.dv = np.array(new["v"][k], dtype=np.double), np.array(new["dv"][k], dtype=np.double)   # plain arrays, as a scatter leaves them
+            self._record_pass(sim, new["exposed"].sum(), new["absorbed"].sum(), new["absorbed_by_cell"])
+            return None
+        return DeviceStep.run(self, sim)
+
+    terminate = tally.TallyStep.terminate                # (a row holds arrays: written as the tally steps write theirs, as plain lists)
+
+
 def _DEFAULT_ID_INFO(x):
     """The reference's default ``lambda x: str(type(x))`` (light.py:438), recognised by identity.  The label goes into the trace
     table's first column: this package's own classes read as the reference's (``<class 'physicl.light.PhotonObject'>``, what a

@@ -296,6 +296,10 @@ class MultiDevice:
         outs = self._each(lambda s: s.recycle_spent(*a, **kw))   # (ids are global: every shard re-emits its own photons)
         return sum(o[0] for o in outs), sum(o[1] for o in outs)
 
+    def absorb_path(self, *a, **kw):
+        outs = self._each(lambda s: s.absorb_path(*a, **kw))     # (ids are global: every shard absorbs its own photons)
+        return sum(o[0] for o in outs), sum(o[1] for o in outs), self._sum([o[2] for o in outs])
+
     def plane_energies(self, plane, n_hint=None):
         return self._concat(self._each(lambda s: s.plane_energies(plane)))      # (a shard does not know its share of the hint)
 
