@@ -160,7 +160,7 @@ int lds_cells_now() { // the switch-over of this call
 }
 
 template <typename T>
-int launch_grid(pcl_ctx *ctx, const store_view &v, const grid_spec &s, const double *edges_dev, unsigned long long *grid_dev) {
+int launch_grid(pcl_ctx *ctx, const store_view &v, const grid_spec &s, const staged &st) {
     grid_args<T> a{};
     for (int k = 0; k < 3; ++k) {
         if (!((s.rows >> k) & 1)) continue;
@@ -168,7 +168,7 @@ int launch_grid(pcl_ctx *ctx, const store_view &v, const grid_spec &s, const dou
         PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_R0 + k, &r));
         a.r[k] = static_cast<const T *>(r);
     }
-    a.edges = edges_dev; a.grid = grid_dev;
+    a.edges = st.tables; a.grid = st.out;
     a.N = v.N; a.ts = v.ts; a.tile_log = v.tile_log;
     a.n_axes = s.n_axes; a.n_edges = s.n_edges; a.n_cells = (int)s.cells; a.rows = s.rows;
     for (int k = 0; k < s.n_axes; ++k) { a.coord[k] = s.coord[k]; a.n_bins[k] = s.n_bins[k]; a.edge_at[k] = s.edge_at[k]; }
@@ -185,20 +185,17 @@ int position_grid(pcl_ctx *ctx, int n_axes, const int *coords_host, const int *n
                   const double *center_host, int64_t *grid_out_host) {
     grid_spec s;
     if (!ctx || !check_spec(n_axes, coords_host, n_bins_host, edges_host, center_host, grid_out_host, s)) return bad_argument(ctx);
+    const spans out = {{grid_out_host, (size_t)s.cells}};
     store_view v;
+    staged st(ctx);
     PCL_SWEEP_TRY(open_store(ctx, PCL_R0 + (s.rows & 1 ? 0 : (s.rows & 2 ? 1 : 2)), &v)); // the first row some axis needs
-    const size_t out_bytes = (size_t)s.cells * sizeof(uint64_t), edge_bytes = (size_t)s.n_edges * sizeof(double);
     if (v.N <= 0) {
-        memset(grid_out_host, 0, out_bytes);
+        zero_spans(out);
         return PCL_OK;
     }
-    dev_block blk(ctx);
-    PCL_SWEEP_TRY(stage(blk, v.stream, out_bytes, s.edges.data(), edge_bytes));
-    char *base = static_cast<char *>(blk.p);
-    const double *edges_dev = reinterpret_cast<const double *>(base + out_bytes);
-    unsigned long long *grid_dev = reinterpret_cast<unsigned long long *>(base);
-    PCL_SWEEP_TRY(v.dtype == PCL_DTYPE_F64 ? launch_grid<double>(ctx, v, s, edges_dev, grid_dev) : launch_grid<float>(ctx, v, s, edges_dev, grid_dev));
-    return pcl_d2h(ctx, grid_out_host, base, (int64_t)out_bytes); // the call's one synchronisation (a count is below 2^63)
+    PCL_SWEEP_TRY(stage(st, v, (size_t)s.cells, s.edges.data(), (size_t)s.n_edges, false, false)); // positions only: no ids, no kinds
+    PCL_SWEEP_TRY(PCL_SWEEP_LAUNCH(v, launch_grid, ctx, v, s, st));
+    return fetch(st, out);
 }
 
 int group_position_grid(pcl_group *group, int n_axes, const int *coords_host, const int *n_bins_host, const double *edges_host,
@@ -209,15 +206,9 @@ int group_position_grid(pcl_group *group, int n_axes, const int *coords_host, co
     grid_spec s;
     if (n < 1 || !check_spec(n_axes, coords_host, n_bins_host, edges_host, center_host, grid_out_host, s))
         return bad_argument(n > 0 ? ctx[0] : nullptr);
-    const size_t cells = (size_t)s.cells;
-    std::vector<std::vector<int64_t>> part((size_t)n, std::vector<int64_t>(cells, 0));
-    PCL_SWEEP_TRY(for_each_shard(ctx, [&](int g, pcl_ctx *c) {
-        return pcl_step_position_grid(c, n_axes, coords_host, n_bins_host, edges_host, center_host, part[(size_t)g].data());
-    }));
-    memset(grid_out_host, 0, cells * sizeof(int64_t));
-    for (int g = 0; g < n; ++g)
-        for (size_t k = 0; k < cells; ++k) grid_out_host[k] += part[(size_t)g][k];
-    return PCL_OK;
+    return sum_shards(ctx, {{grid_out_host, (size_t)s.cells}}, [&](pcl_ctx *one, int64_t *p) {
+        return pcl_step_position_grid(one, n_axes, coords_host, n_bins_host, edges_host, center_host, p);
+    });
 }
 
 } // namespace

@@ -110,6 +110,10 @@ struct shell_spec { // a call's arguments, checked; what the kernel compares aga
     double c[3] = {0.0, 0.0, 0.0};
     std::vector<double> tables; // E edges | w_b | R*R
     size_t cells() const { return (size_t)2 * n_shells * (1 + n_E + n_mu); }
+    spans out(int64_t *counts, int64_t *E_hist, int64_t *mu_hist) const {
+        const size_t n_cnt = (size_t)2 * n_shells;
+        return {{counts, n_cnt}, {E_hist, n_cnt * n_E}, {mu_hist, n_cnt * n_mu}};
+    }
 };
 
 // n + 1 finite, strictly increasing edges, 1 <= n <= PCL_SHELL_MAX_BINS -- or none at all (NULL or not, 0 bins)
@@ -139,15 +143,8 @@ bool check_spec(int n_shells, const double *radii, const double *center, const d
     return true;
 }
 
-void zero_outputs(const shell_spec &s, int64_t *counts, int64_t *E_hist, int64_t *mu_hist) {
-    memset(counts, 0, (size_t)2 * s.n_shells * sizeof(int64_t));
-    if (s.n_E) memset(E_hist, 0, (size_t)2 * s.n_shells * s.n_E * sizeof(int64_t));
-    if (s.n_mu) memset(mu_hist, 0, (size_t)2 * s.n_shells * s.n_mu * sizeof(int64_t));
-}
-
 template <typename T>
-int launch_shell(pcl_ctx *ctx, const store_view &v, const shell_spec &s, const void *E, const unsigned char *kind, const double *tables_dev,
-                 unsigned long long *out_dev) {
+int launch_shell(pcl_ctx *ctx, const store_view &v, const shell_spec &s, const void *E, const staged &st) {
     shell_args<T> a{};
     for (int k = 0; k < 3; ++k) {
         void *r = nullptr, *dr = nullptr;
@@ -157,7 +154,7 @@ int launch_shell(pcl_ctx *ctx, const store_view &v, const shell_spec &s, const v
         a.dr[k] = static_cast<const T *>(dr);
         a.c[k] = s.c[k];
     }
-    a.E = static_cast<const T *>(E); a.kind = kind; a.tables = tables_dev; a.out = out_dev;
+    a.E = static_cast<const T *>(E); a.kind = st.kind; a.tables = st.tables; a.out = st.out;
     a.N = v.N; a.ts = v.ts; a.tile_log = v.tile_log;
     a.n_shells = s.n_shells; a.n_E = s.n_E; a.n_mu = s.n_mu;
     const size_t lds = s.tables.size() * sizeof(double) + s.cells() * sizeof(uint32_t);
@@ -174,34 +171,20 @@ int shell_crossings(pcl_ctx *ctx, int n_shells, const double *radii_host, const 
                             E_hist_out_host, mu_hist_out_host, s))
         return bad_argument(ctx);
     // E is asked for only with energy bins: the pointer costs a wavelength-dependent scatter step its term cache.
+    const spans out = s.out(counts_out_host, E_hist_out_host, mu_hist_out_host);
     store_view v;
+    staged st(ctx);
     void *E = nullptr;
     PCL_SWEEP_TRY(open_store(ctx, PCL_R0, &v));
     if (s.n_E) PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_E, &E));
     if (v.N <= 0) {
-        zero_outputs(s, counts_out_host, E_hist_out_host, mu_hist_out_host);
+        zero_spans(out);
         return PCL_OK;
     }
-    std::vector<uint8_t> kind_host; // go along when energies are binned and the store holds a plain Object
-    bool mixed = false;
-    if (s.n_E) PCL_SWEEP_TRY(kind_bytes(ctx, v.N, kind_host, &mixed));
-    const size_t cells = s.cells();
-    const size_t out_bytes = cells * sizeof(uint64_t), tab_bytes = s.tables.size() * sizeof(double);
-    dev_block blk(ctx);
-    PCL_SWEEP_TRY(stage(blk, v.stream, out_bytes, s.tables.data(), tab_bytes, kind_host));
-    char *base = static_cast<char *>(blk.p);
-    const unsigned char *kind = mixed ? reinterpret_cast<const unsigned char *>(base + out_bytes + tab_bytes) : nullptr;
-    const double *tables_dev = reinterpret_cast<const double *>(base + out_bytes);
-    unsigned long long *out_dev = reinterpret_cast<unsigned long long *>(base);
-    PCL_SWEEP_TRY(v.dtype == PCL_DTYPE_F64 ? launch_shell<double>(ctx, v, s, E, kind, tables_dev, out_dev)
-                                           : launch_shell<float>(ctx, v, s, E, kind, tables_dev, out_dev));
-    std::vector<int64_t> out(cells);
-    PCL_SWEEP_TRY(pcl_d2h(ctx, out.data(), base, (int64_t)out_bytes)); // the call's one synchronisation (a count is below 2^63)
-    const size_t n_cnt = (size_t)2 * s.n_shells;
-    memcpy(counts_out_host, out.data(), n_cnt * sizeof(int64_t));
-    if (s.n_E) memcpy(E_hist_out_host, out.data() + n_cnt, n_cnt * s.n_E * sizeof(int64_t));
-    if (s.n_mu) memcpy(mu_hist_out_host, out.data() + n_cnt * (1 + s.n_E), n_cnt * s.n_mu * sizeof(int64_t));
-    return PCL_OK;
+    // the kinds go along when energies are binned and the store holds a plain Object; nothing is drawn: no ids
+    PCL_SWEEP_TRY(stage(st, v, s.cells(), s.tables.data(), s.tables.size(), false, s.n_E > 0));
+    PCL_SWEEP_TRY(PCL_SWEEP_LAUNCH(v, launch_shell, ctx, v, s, E, st));
+    return fetch(st, out);
 }
 
 int group_shell_crossings(pcl_group *group, int n_shells, const double *radii_host, const double *center_host,
@@ -214,21 +197,11 @@ int group_shell_crossings(pcl_group *group, int n_shells, const double *radii_ho
     if (n < 1 || !check_spec(n_shells, radii_host, center_host, E_edges_host, n_E_bins, mu_edges_host, n_mu_bins, counts_out_host,
                              E_hist_out_host, mu_hist_out_host, s))
         return bad_argument(n > 0 ? ctx[0] : nullptr);
-    const size_t n_cnt = (size_t)2 * n_shells, at_E = n_cnt, at_mu = n_cnt * (1 + (size_t)n_E_bins);
-    std::vector<std::vector<int64_t>> part((size_t)n, std::vector<int64_t>(s.cells(), 0));
-    PCL_SWEEP_TRY(for_each_shard(ctx, [&](int g, pcl_ctx *c) {
-        int64_t *p = part[(size_t)g].data();
-        return pcl_step_shell_crossings(c, n_shells, radii_host, center_host, E_edges_host, n_E_bins, mu_edges_host, n_mu_bins, p, p + at_E,
-                                        p + at_mu);
-    }));
-    zero_outputs(s, counts_out_host, E_hist_out_host, mu_hist_out_host);
-    for (int g = 0; g < n; ++g) {
-        const int64_t *p = part[(size_t)g].data();
-        for (size_t k = 0; k < n_cnt; ++k) counts_out_host[k] += p[k];
-        for (size_t k = 0; k < n_cnt * (size_t)n_E_bins; ++k) E_hist_out_host[k] += p[at_E + k];
-        for (size_t k = 0; k < n_cnt * (size_t)n_mu_bins; ++k) mu_hist_out_host[k] += p[at_mu + k];
-    }
-    return PCL_OK;
+    const size_t n_cnt = (size_t)2 * n_shells;
+    return sum_shards(ctx, s.out(counts_out_host, E_hist_out_host, mu_hist_out_host), [&](pcl_ctx *one, int64_t *p) {
+        return pcl_step_shell_crossings(one, n_shells, radii_host, center_host, E_edges_host, n_E_bins, mu_edges_host, n_mu_bins, p,
+                                        p + n_cnt, p + n_cnt * (1 + (size_t)n_E_bins));
+    });
 }
 
 } // namespace

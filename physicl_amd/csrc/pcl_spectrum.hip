@@ -79,11 +79,11 @@ __global__ void __launch_bounds__(kBlock) k_plane_spectra(spectrum_args<T> a) {
 }
 
 template <typename T>
-int launch_spectra(pcl_ctx *ctx, const store_view &v, const void *E, const unsigned char *kind, const double *edges_dev,
-                   unsigned long long *hist_dev, const double *planes_host, const int *ax, int ax_used, int n_planes, int n_bins) {
+int launch_spectra(pcl_ctx *ctx, const store_view &v, const void *E, const staged &st, const double *planes_host, const int *ax,
+                   int ax_used, int n_planes, int n_bins) {
     spectrum_args<T> a{};
-    a.E = static_cast<const T *>(E); a.kind = kind; a.edges = edges_dev;
-    a.hist = hist_dev; a.counts = hist_dev + (size_t)n_planes * n_bins;
+    a.E = static_cast<const T *>(E); a.kind = st.kind; a.edges = st.tables;
+    a.hist = st.out; a.counts = st.out + (size_t)n_planes * n_bins;
     a.N = v.N; a.ts = v.ts; a.tile_log = v.tile_log; a.n_planes = n_planes; a.n_bins = n_bins; a.ax_used = ax_used;
     for (int p = 0; p < n_planes; ++p) {
         a.ax[p] = ax[p];
@@ -115,31 +115,16 @@ int plane_spectra(pcl_ctx *ctx, const double *planes_host, int n_planes, const d
         if (std::isnan(loc[ax[p]])) return bad_argument(ctx);
         ax_used |= 1 << ax[p];
     }
+    const spans out = {{hist_out_host, (size_t)n_planes * n_bins}, {counts_out_host, (size_t)n_planes}};
     void *E = nullptr;
     store_view v;
+    staged st(ctx);
     PCL_SWEEP_TRY(open_store(ctx, PCL_E, &v, &E));
-    for (int p = 0; p < n_planes; ++p) counts_out_host[p] = 0;
-    memset(hist_out_host, 0, (size_t)n_planes * n_bins * sizeof(int64_t));
+    zero_spans(out);
     if (v.N <= 0) return PCL_OK;
-    std::vector<uint8_t> kind_host;
-    bool mixed = false;
-    PCL_SWEEP_TRY(kind_bytes(ctx, v.N, kind_host, &mixed));
-    const size_t cells = (size_t)n_planes * n_bins;
-    const size_t out_bytes = (cells + n_planes) * sizeof(uint64_t), edge_bytes = (size_t)(n_bins + 1) * sizeof(double);
-    dev_block blk(ctx);
-    PCL_SWEEP_TRY(stage(blk, v.stream, out_bytes, edges_host, edge_bytes, kind_host));
-    char *base = static_cast<char *>(blk.p);
-    const double *edges_dev = reinterpret_cast<const double *>(base + out_bytes);
-    const unsigned char *kind = mixed ? reinterpret_cast<const unsigned char *>(base + out_bytes + edge_bytes) : nullptr;
-    unsigned long long *hist_dev = reinterpret_cast<unsigned long long *>(base);
-    PCL_SWEEP_TRY(v.dtype == PCL_DTYPE_F64
-                      ? launch_spectra<double>(ctx, v, E, kind, edges_dev, hist_dev, planes_host, ax, ax_used, n_planes, n_bins)
-                      : launch_spectra<float>(ctx, v, E, kind, edges_dev, hist_dev, planes_host, ax, ax_used, n_planes, n_bins));
-    std::vector<uint64_t> out(cells + n_planes);
-    PCL_SWEEP_TRY(pcl_d2h(ctx, out.data(), base, (int64_t)out_bytes)); // the call's one synchronisation
-    for (size_t k = 0; k < cells; ++k) hist_out_host[k] = (int64_t)out[k];
-    for (int p = 0; p < n_planes; ++p) counts_out_host[p] = (int64_t)out[cells + p];
-    return PCL_OK;
+    PCL_SWEEP_TRY(stage(st, v, cells_of(out), edges_host, (size_t)n_bins + 1, false));   // nothing is drawn: no ids
+    PCL_SWEEP_TRY(PCL_SWEEP_LAUNCH(v, launch_spectra, ctx, v, E, st, planes_host, ax, ax_used, n_planes, n_bins));
+    return fetch(st, out);
 }
 
 int group_plane_spectra(pcl_group *group, const double *planes_host, int n_planes, const double *edges_host, int n_bins,
@@ -150,17 +135,9 @@ int group_plane_spectra(pcl_group *group, const double *planes_host, int n_plane
     if (n < 1 || !counts_out_host || !hist_out_host || n_planes < 1 || n_planes > PCL_MAX_PLANES || n_bins < 1 || n_bins > PCL_SPECTRUM_MAX_BINS)
         return bad_argument(n > 0 ? ctx[0] : nullptr);
     const size_t cells = (size_t)n_planes * n_bins;
-    std::vector<std::vector<int64_t>> part((size_t)n, std::vector<int64_t>(cells + n_planes, 0));
-    PCL_SWEEP_TRY(for_each_shard(ctx, [&](int g, pcl_ctx *c) {
-        return pcl_step_plane_spectra(c, planes_host, n_planes, edges_host, n_bins, part[(size_t)g].data() + cells, part[(size_t)g].data());
-    }));
-    for (int p = 0; p < n_planes; ++p) counts_out_host[p] = 0;
-    memset(hist_out_host, 0, cells * sizeof(int64_t));
-    for (int g = 0; g < n; ++g) {
-        for (size_t k = 0; k < cells; ++k) hist_out_host[k] += part[(size_t)g][k];
-        for (int p = 0; p < n_planes; ++p) counts_out_host[p] += part[(size_t)g][cells + p];
-    }
-    return PCL_OK;
+    return sum_shards(ctx, {{hist_out_host, cells}, {counts_out_host, (size_t)n_planes}}, [&](pcl_ctx *one, int64_t *p) {
+        return pcl_step_plane_spectra(one, planes_host, n_planes, edges_host, n_bins, p + cells, p);
+    });
 }
 
 } // namespace

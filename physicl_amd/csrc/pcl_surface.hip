@@ -776,8 +776,7 @@ bool check_spec(double radius, const double *center, double albedo, int mode, do
 }
 
 template <typename T>
-int launch_surface(pcl_ctx *ctx, const store_view &v, const surface_spec &s, uint64_t seed, uint32_t pass, int64_t id_base,
-                   const int64_t *ids, const unsigned char *kind, unsigned long long *out_dev) {
+int launch_surface(pcl_ctx *ctx, const store_view &v, const surface_spec &s, uint64_t seed, uint32_t pass, const staged &st) {
     surface_args<T> a{};
     for (int k = 0; k < 3; ++k) {
         void *r = nullptr, *vel = nullptr, *dr = nullptr, *dv = nullptr;
@@ -789,8 +788,8 @@ int launch_surface(pcl_ctx *ctx, const store_view &v, const surface_spec &s, uin
         a.dr[k] = static_cast<T *>(dr); a.dv[k] = static_cast<T *>(dv);
         a.c[k] = s.c[k];
     }
-    a.kind = kind; a.ids = ids; a.out = out_dev;
-    a.N = v.N; a.ts = v.ts; a.id_base = id_base; a.tile_log = v.tile_log; a.mode = s.mode;
+    a.kind = st.kind; a.ids = st.ids; a.out = st.out;
+    a.N = v.N; a.ts = v.ts; a.id_base = st.id_base; a.tile_log = v.tile_log; a.mode = s.mode;
     a.R2 = s.R2; a.albedo = s.albedo; a.speed = s.speed;
     a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32); a.pass = pass;
     const int64_t grid = balanced_grid(v.N, v.n_cu, resident_per_cu(2 * sizeof(uint32_t)));
@@ -803,28 +802,15 @@ int surface_reflect(pcl_ctx *ctx, double radius, const double *center_host, doub
     surface_spec s;
     if (!ctx || !check_spec(radius, center_host, albedo, mode, c, counts_out_host, s)) return bad_argument(ctx);
     // E is never asked for: the pointer costs a wavelength-dependent scatter step its term cache (pcl_shell.hip).
+    const spans out = {{counts_out_host, 2}};
     store_view v;
+    staged st(ctx);
     PCL_SWEEP_TRY(open_store(ctx, PCL_R0, &v));
-    counts_out_host[0] = counts_out_host[1] = 0;
+    zero_spans(out);
     if (v.N <= 0) return PCL_OK;
-    // a store that is not uniform: the kinds go along if it holds a plain Object, the ids if they are not id[0] + index --
-    // both come over the host link and go back up, every call (pcl_sweep::id_words / kind_bytes say what that costs)
-    std::vector<uint8_t> kind_host;
-    std::vector<int64_t> ids_host;
-    bool mixed = false;
-    int64_t id_base = 0;
-    PCL_SWEEP_TRY(kind_bytes(ctx, v.N, kind_host, &mixed));
-    PCL_SWEEP_TRY(id_words(ctx, v.N, ids_host, &id_base));
-    const size_t out_bytes = 2 * sizeof(uint64_t), id_bytes = ids_host.size() * sizeof(int64_t);
-    dev_block blk(ctx);
-    PCL_SWEEP_TRY(stage(blk, v.stream, out_bytes, nullptr, 0, kind_host, ids_host));
-    char *base = static_cast<char *>(blk.p);
-    const int64_t *ids = id_bytes ? reinterpret_cast<const int64_t *>(base + out_bytes) : nullptr;
-    const unsigned char *kind = mixed ? reinterpret_cast<const unsigned char *>(base + out_bytes + id_bytes) : nullptr;
-    unsigned long long *out_dev = reinterpret_cast<unsigned long long *>(base);
-    PCL_SWEEP_TRY(v.dtype == PCL_DTYPE_F64 ? launch_surface<double>(ctx, v, s, seed, pass, id_base, ids, kind, out_dev)
-                                           : launch_surface<float>(ctx, v, s, seed, pass, id_base, ids, kind, out_dev));
-    return pcl_d2h(ctx, counts_out_host, base, (int64_t)out_bytes); // the call's one synchronisation (a count is below 2^63)
+    PCL_SWEEP_TRY(stage(st, v, 2, nullptr, 0, true));
+    PCL_SWEEP_TRY(PCL_SWEEP_LAUNCH(v, launch_surface, ctx, v, s, seed, pass, st));
+    return fetch(st, out);
 }
 
 int group_surface_reflect(pcl_group *group, double radius, const double *center_host, double albedo, int mode, double c,
@@ -834,16 +820,9 @@ int group_surface_reflect(pcl_group *group, double radius, const double *center_
     const int n = (int)ctx.size();
     surface_spec s;
     if (n < 1 || !check_spec(radius, center_host, albedo, mode, c, counts_out_host, s)) return bad_argument(n > 0 ? ctx[0] : nullptr);
-    std::vector<int64_t> part((size_t)2 * n, 0);
-    PCL_SWEEP_TRY(for_each_shard(ctx, [&](int g, pcl_ctx *one) {
-        return pcl_step_surface_reflect(one, radius, center_host, albedo, mode, c, seed, pass, &part[(size_t)2 * g]);
-    }));
-    counts_out_host[0] = counts_out_host[1] = 0;
-    for (int g = 0; g < n; ++g) {
-        counts_out_host[0] += part[(size_t)2 * g];
-        counts_out_host[1] += part[(size_t)2 * g + 1];
-    }
-    return PCL_OK;
+    return sum_shards(ctx, {{counts_out_host, 2}}, [&](pcl_ctx *one, int64_t *p) {
+        return pcl_step_surface_reflect(one, radius, center_host, albedo, mode, c, seed, pass, p);
+    });
 }
 
 // Everything PCL_ERR_ARG stands for except the NULL context (g is looked at for Henyey-Greenstein only)
@@ -854,8 +833,8 @@ bool check_phase(int phase, double g, double c, const int64_t *count_out) {
 }
 
 template <typename T>
-int launch_phase(pcl_ctx *ctx, const store_view &v, int phase, double g, double c, uint64_t seed, uint32_t pass, int64_t id_base,
-                 const int64_t *ids, const unsigned char *kind, unsigned long long *out_dev) {
+int launch_phase(pcl_ctx *ctx, const store_view &v, int phase, double g, double c, uint64_t seed, uint32_t pass,
+                 const staged &st) {
     phase_args<T> a{};
     for (int k = 0; k < 3; ++k) {
         void *vel = nullptr, *dv = nullptr;
@@ -863,8 +842,8 @@ int launch_phase(pcl_ctx *ctx, const store_view &v, int phase, double g, double 
         PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_DV0 + k, &dv));     // (what makes a lazy dv real)
         a.v[k] = static_cast<T *>(vel); a.dv[k] = static_cast<T *>(dv);
     }
-    a.kind = kind; a.ids = ids; a.out = out_dev;
-    a.N = v.N; a.ts = v.ts; a.id_base = id_base; a.tile_log = v.tile_log; a.phase = phase;
+    a.kind = st.kind; a.ids = st.ids; a.out = st.out;
+    a.N = v.N; a.ts = v.ts; a.id_base = st.id_base; a.tile_log = v.tile_log; a.phase = phase;
     a.g = g; a.speed = c;
     a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32); a.pass = pass;
     const int64_t grid = balanced_grid(v.N, v.n_cu, resident_per_cu(sizeof(uint32_t)));
@@ -874,26 +853,15 @@ int launch_phase(pcl_ctx *ctx, const store_view &v, int phase, double g, double 
 
 int phase_redirect(pcl_ctx *ctx, int phase, double g, double c, uint64_t seed, uint32_t pass, int64_t *count_out_host) {
     if (!ctx || !check_phase(phase, g, c, count_out_host)) return bad_argument(ctx);
+    const spans out = {{count_out_host, 1}};
     store_view v;                                                       // E is never asked for, as above
+    staged st(ctx);
     PCL_SWEEP_TRY(open_store(ctx, PCL_DV0, &v));
-    count_out_host[0] = 0;
+    zero_spans(out);
     if (v.N <= 0) return PCL_OK;
-    std::vector<uint8_t> kind_host;                                     // a store that is not uniform: as surface_reflect
-    std::vector<int64_t> ids_host;
-    bool mixed = false;
-    int64_t id_base = 0;
-    PCL_SWEEP_TRY(kind_bytes(ctx, v.N, kind_host, &mixed));
-    PCL_SWEEP_TRY(id_words(ctx, v.N, ids_host, &id_base));
-    const size_t out_bytes = sizeof(uint64_t), id_bytes = ids_host.size() * sizeof(int64_t);
-    dev_block blk(ctx);
-    PCL_SWEEP_TRY(stage(blk, v.stream, out_bytes, nullptr, 0, kind_host, ids_host));
-    char *base = static_cast<char *>(blk.p);
-    const int64_t *ids = id_bytes ? reinterpret_cast<const int64_t *>(base + out_bytes) : nullptr;
-    const unsigned char *kind = mixed ? reinterpret_cast<const unsigned char *>(base + out_bytes + id_bytes) : nullptr;
-    unsigned long long *out_dev = reinterpret_cast<unsigned long long *>(base);
-    PCL_SWEEP_TRY(v.dtype == PCL_DTYPE_F64 ? launch_phase<double>(ctx, v, phase, g, c, seed, pass, id_base, ids, kind, out_dev)
-                                           : launch_phase<float>(ctx, v, phase, g, c, seed, pass, id_base, ids, kind, out_dev));
-    return pcl_d2h(ctx, count_out_host, base, (int64_t)out_bytes);     // the call's one synchronisation
+    PCL_SWEEP_TRY(stage(st, v, 1, nullptr, 0, true));
+    PCL_SWEEP_TRY(PCL_SWEEP_LAUNCH(v, launch_phase, ctx, v, phase, g, c, seed, pass, st));
+    return fetch(st, out);
 }
 
 int group_phase_redirect(pcl_group *group, int phase, double g, double c, uint64_t seed, uint32_t pass, int64_t *count_out_host) {
@@ -901,13 +869,9 @@ int group_phase_redirect(pcl_group *group, int phase, double g, double c, uint64
     PCL_SWEEP_TRY(shards_of(group, ctx));
     const int n = (int)ctx.size();
     if (n < 1 || !check_phase(phase, g, c, count_out_host)) return bad_argument(n > 0 ? ctx[0] : nullptr);
-    std::vector<int64_t> part((size_t)n, 0);
-    PCL_SWEEP_TRY(for_each_shard(ctx, [&](int s, pcl_ctx *one) {
-        return pcl_step_phase_redirect(one, phase, g, c, seed, pass, &part[(size_t)s]);
-    }));
-    count_out_host[0] = 0;
-    for (int s = 0; s < n; ++s) count_out_host[0] += part[(size_t)s];
-    return PCL_OK;
+    return sum_shards(ctx, {{count_out_host, 1}}, [&](pcl_ctx *one, int64_t *p) {
+        return pcl_step_phase_redirect(one, phase, g, c, seed, pass, p);
+    });
 }
 
 struct absorb_spec { // a call's arguments, checked; what the kernel compares against
@@ -917,6 +881,7 @@ struct absorb_spec { // a call's arguments, checked; what the kernel compares ag
     std::vector<double> tables; // omega0 | e*e | E edges
     int rows() const { return n_layers > 0 ? n_layers : 1; }
     size_t cells() const { return (size_t)2 + (size_t)rows() * (1 + (size_t)n_E); }
+    spans out(int64_t *counts, int64_t *E_hist) const { return {{counts, (size_t)2 + rows()}, {E_hist, (size_t)rows() * n_E}}; }
 };
 
 // Everything PCL_ERR_ARG stands for except the NULL context; nothing is launched or written before this has passed.
@@ -941,14 +906,9 @@ bool check_absorb(int n_layers, const double *omega0, const double *edges, const
     return true;
 }
 
-void zero_absorb(const absorb_spec &s, int64_t *counts, int64_t *E_hist) {
-    memset(counts, 0, (size_t)(2 + s.rows()) * sizeof(int64_t));
-    if (s.n_E) memset(E_hist, 0, (size_t)s.rows() * s.n_E * sizeof(int64_t));
-}
-
 template <typename T>
-int launch_absorb(pcl_ctx *ctx, const store_view &v, const absorb_spec &s, const void *E, uint64_t seed, uint32_t pass, int64_t id_base,
-                  const int64_t *ids, const unsigned char *kind, const double *tables_dev, unsigned long long *out_dev) {
+int launch_absorb(pcl_ctx *ctx, const store_view &v, const absorb_spec &s, const void *E, uint64_t seed, uint32_t pass,
+                  const staged &st) {
     absorb_args<T> a{};
     for (int k = 0; k < 3; ++k) {
         void *r = nullptr, *vel = nullptr, *dv = nullptr;
@@ -958,8 +918,8 @@ int launch_absorb(pcl_ctx *ctx, const store_view &v, const absorb_spec &s, const
         a.r[k] = static_cast<const T *>(r); a.v[k] = static_cast<T *>(vel); a.dv[k] = static_cast<T *>(dv);
         a.c[k] = s.c[k];
     }
-    a.E = static_cast<const T *>(E); a.kind = kind; a.ids = ids; a.tables = tables_dev; a.out = out_dev;
-    a.N = v.N; a.ts = v.ts; a.id_base = id_base; a.tile_log = v.tile_log;
+    a.E = static_cast<const T *>(E); a.kind = st.kind; a.ids = st.ids; a.tables = st.tables; a.out = st.out;
+    a.N = v.N; a.ts = v.ts; a.id_base = st.id_base; a.tile_log = v.tile_log;
     a.n_layers = s.n_layers; a.n_E = s.n_E;
     a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32); a.pass = pass;
     const size_t lds = s.tables.size() * sizeof(double) + s.cells() * sizeof(uint32_t);
@@ -974,37 +934,18 @@ int absorb_scattered(pcl_ctx *ctx, int n_layers, const double *omega0_host, cons
     absorb_spec s;
     if (!ctx || !check_absorb(n_layers, omega0_host, edges_host, center_host, n_E_bins, E_edges_host, counts_out_host, E_hist_out_host, s))
         return bad_argument(ctx);
+    const spans out = s.out(counts_out_host, E_hist_out_host);
     store_view v;
+    staged st(ctx);
     PCL_SWEEP_TRY(open_store(ctx, PCL_DV0, &v));
-    zero_absorb(s, counts_out_host, E_hist_out_host);
+    zero_spans(out);
     if (v.N <= 0) return PCL_OK;
     // E is asked for only with energy bins: the pointer costs a wavelength-dependent scatter step its term cache (pcl_shell.hip).
     void *E = nullptr;
     if (s.n_E) PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_E, &E));
-    std::vector<uint8_t> kind_host;                                     // a store that is not uniform: as surface_reflect;
-    std::vector<int64_t> ids_host;                                      // the ids only if somebody may draw
-    bool mixed = false;
-    int64_t id_base = 0;
-    PCL_SWEEP_TRY(kind_bytes(ctx, v.N, kind_host, &mixed));
-    if (s.draws) PCL_SWEEP_TRY(id_words(ctx, v.N, ids_host, &id_base));
-    const size_t cells = s.cells();
-    const size_t out_bytes = cells * sizeof(uint64_t), tab_bytes = s.tables.size() * sizeof(double);
-    const size_t id_bytes = ids_host.size() * sizeof(int64_t);
-    dev_block blk(ctx);
-    PCL_SWEEP_TRY(stage(blk, v.stream, out_bytes, s.tables.data(), tab_bytes, kind_host, ids_host));
-    char *base = static_cast<char *>(blk.p);
-    const double *tables_dev = reinterpret_cast<const double *>(base + out_bytes);
-    const int64_t *ids = id_bytes ? reinterpret_cast<const int64_t *>(base + out_bytes + tab_bytes) : nullptr;
-    const unsigned char *kind = mixed ? reinterpret_cast<const unsigned char *>(base + out_bytes + tab_bytes + id_bytes) : nullptr;
-    unsigned long long *out_dev = reinterpret_cast<unsigned long long *>(base);
-    PCL_SWEEP_TRY(v.dtype == PCL_DTYPE_F64 ? launch_absorb<double>(ctx, v, s, E, seed, pass, id_base, ids, kind, tables_dev, out_dev)
-                                           : launch_absorb<float>(ctx, v, s, E, seed, pass, id_base, ids, kind, tables_dev, out_dev));
-    std::vector<int64_t> out(cells);
-    PCL_SWEEP_TRY(pcl_d2h(ctx, out.data(), base, (int64_t)out_bytes)); // the call's one synchronisation (a count is below 2^63)
-    const size_t n_cnt = (size_t)2 + s.rows();
-    memcpy(counts_out_host, out.data(), n_cnt * sizeof(int64_t));
-    if (s.n_E) memcpy(E_hist_out_host, out.data() + n_cnt, (cells - n_cnt) * sizeof(int64_t));
-    return PCL_OK;
+    PCL_SWEEP_TRY(stage(st, v, s.cells(), s.tables.data(), s.tables.size(), s.draws));   // the ids only if somebody may draw
+    PCL_SWEEP_TRY(PCL_SWEEP_LAUNCH(v, launch_absorb, ctx, v, s, E, seed, pass, st));
+    return fetch(st, out);
 }
 
 int group_absorb_scattered(pcl_group *group, int n_layers, const double *omega0_host, const double *edges_host, const double *center_host,
@@ -1016,20 +957,10 @@ int group_absorb_scattered(pcl_group *group, int n_layers, const double *omega0_
     absorb_spec s;
     if (n < 1 || !check_absorb(n_layers, omega0_host, edges_host, center_host, n_E_bins, E_edges_host, counts_out_host, E_hist_out_host, s))
         return bad_argument(n > 0 ? ctx[0] : nullptr);
-    const size_t n_cnt = (size_t)2 + s.rows(), cells = s.cells();
-    std::vector<std::vector<int64_t>> part((size_t)n, std::vector<int64_t>(cells, 0));
-    PCL_SWEEP_TRY(for_each_shard(ctx, [&](int g, pcl_ctx *one) {
-        int64_t *p = part[(size_t)g].data();
+    return sum_shards(ctx, s.out(counts_out_host, E_hist_out_host), [&](pcl_ctx *one, int64_t *p) {
         return pcl_step_absorb_scattered(one, n_layers, omega0_host, edges_host, center_host, n_E_bins, E_edges_host, seed, pass, p,
-                                         n_E_bins ? p + n_cnt : nullptr);
-    }));
-    zero_absorb(s, counts_out_host, E_hist_out_host);
-    for (int g = 0; g < n; ++g) {
-        const int64_t *p = part[(size_t)g].data();
-        for (size_t k = 0; k < n_cnt; ++k) counts_out_host[k] += p[k];
-        for (size_t k = n_cnt; k < cells; ++k) E_hist_out_host[k - n_cnt] += p[k];
-    }
-    return PCL_OK;
+                                         n_E_bins ? p + 2 + s.rows() : nullptr);
+    });
 }
 
 struct lphase_spec { // a call's arguments, checked; what the kernel reads
@@ -1112,8 +1043,7 @@ bool check_lphase(int n_laws, const int *kinds, const double *g, const int *n_bi
 }
 
 template <typename T>
-int launch_lphase(pcl_ctx *ctx, const store_view &v, const lphase_spec &s, uint64_t seed, uint32_t pass, int64_t id_base,
-                  const int64_t *ids, const unsigned char *kind, const double *tables_dev, unsigned long long *out_dev) {
+int launch_lphase(pcl_ctx *ctx, const store_view &v, const lphase_spec &s, uint64_t seed, uint32_t pass, const staged &st) {
     lphase_args<T> a{};
     for (int k = 0; k < 3; ++k) {
         void *r = nullptr, *vel = nullptr, *dv = nullptr;
@@ -1123,8 +1053,8 @@ int launch_lphase(pcl_ctx *ctx, const store_view &v, const lphase_spec &s, uint6
         a.r[k] = static_cast<const T *>(r); a.v[k] = static_cast<T *>(vel); a.dv[k] = static_cast<T *>(dv);
         a.c[k] = s.c[k];
     }
-    a.kind = kind; a.ids = ids; a.tables = tables_dev; a.out = out_dev;
-    a.N = v.N; a.ts = v.ts; a.id_base = id_base; a.tile_log = v.tile_log;
+    a.kind = st.kind; a.ids = st.ids; a.tables = st.tables; a.out = st.out;
+    a.N = v.N; a.ts = v.ts; a.id_base = st.id_base; a.tile_log = v.tile_log;
     a.n_layers = s.n_layers; a.n_laws = s.n_laws; a.n_nodes = s.n_nodes; a.speed = s.speed;
     a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32); a.pass = pass;
     const size_t lds = s.lds();                                         // what this call uses: a few hundred bytes without a table
@@ -1138,29 +1068,15 @@ int phase_layered(pcl_ctx *ctx, int n_laws, const int *kinds, const double *g, c
                   int64_t *counts_out_host) {
     lphase_spec s;
     if (!ctx || !check_lphase(n_laws, kinds, g, n_bins, mu, F, n_layers, cum, edges, center, c, counts_out_host, s)) return bad_argument(ctx);
+    const spans out = {{counts_out_host, s.cells()}};
     store_view v;                                                       // E is never asked for, as in phase_redirect
+    staged st(ctx);
     PCL_SWEEP_TRY(open_store(ctx, PCL_DV0, &v));
-    const size_t cells = s.cells();
-    memset(counts_out_host, 0, cells * sizeof(int64_t));
+    zero_spans(out);
     if (v.N <= 0) return PCL_OK;
-    std::vector<uint8_t> kind_host;                                     // a store that is not uniform: as surface_reflect
-    std::vector<int64_t> ids_host;
-    bool mixed = false;
-    int64_t id_base = 0;
-    PCL_SWEEP_TRY(kind_bytes(ctx, v.N, kind_host, &mixed));
-    PCL_SWEEP_TRY(id_words(ctx, v.N, ids_host, &id_base));
-    const size_t out_bytes = cells * sizeof(uint64_t), tab_bytes = s.tables.size() * sizeof(double);
-    const size_t id_bytes = ids_host.size() * sizeof(int64_t);
-    dev_block blk(ctx);
-    PCL_SWEEP_TRY(stage(blk, v.stream, out_bytes, s.tables.data(), tab_bytes, kind_host, ids_host));
-    char *base = static_cast<char *>(blk.p);
-    const double *tables_dev = reinterpret_cast<const double *>(base + out_bytes);
-    const int64_t *ids = id_bytes ? reinterpret_cast<const int64_t *>(base + out_bytes + tab_bytes) : nullptr;
-    const unsigned char *kind = mixed ? reinterpret_cast<const unsigned char *>(base + out_bytes + tab_bytes + id_bytes) : nullptr;
-    unsigned long long *out_dev = reinterpret_cast<unsigned long long *>(base);
-    PCL_SWEEP_TRY(v.dtype == PCL_DTYPE_F64 ? launch_lphase<double>(ctx, v, s, seed, pass, id_base, ids, kind, tables_dev, out_dev)
-                                           : launch_lphase<float>(ctx, v, s, seed, pass, id_base, ids, kind, tables_dev, out_dev));
-    return pcl_d2h(ctx, counts_out_host, base, (int64_t)out_bytes);    // the call's one synchronisation (a count is below 2^63)
+    PCL_SWEEP_TRY(stage(st, v, s.cells(), s.tables.data(), s.tables.size(), true));
+    PCL_SWEEP_TRY(PCL_SWEEP_LAUNCH(v, launch_lphase, ctx, v, s, seed, pass, st));
+    return fetch(st, out);
 }
 
 int group_phase_layered(pcl_group *group, int n_laws, const int *kinds, const double *g, const int *n_bins, const double *mu,
@@ -1172,16 +1088,9 @@ int group_phase_layered(pcl_group *group, int n_laws, const int *kinds, const do
     lphase_spec s;
     if (n < 1 || !check_lphase(n_laws, kinds, g, n_bins, mu, F, n_layers, cum, edges, center, c, counts_out_host, s))
         return bad_argument(n > 0 ? ctx[0] : nullptr);
-    const size_t cells = s.cells();
-    std::vector<std::vector<int64_t>> part((size_t)n, std::vector<int64_t>(cells, 0));
-    PCL_SWEEP_TRY(for_each_shard(ctx, [&](int sh, pcl_ctx *one) {
-        return pcl_step_phase_layered(one, n_laws, kinds, g, n_bins, mu, F, n_layers, cum, edges, center, c, seed, pass,
-                                      part[(size_t)sh].data());
-    }));
-    memset(counts_out_host, 0, cells * sizeof(int64_t));
-    for (int sh = 0; sh < n; ++sh)
-        for (size_t k = 0; k < cells; ++k) counts_out_host[k] += part[(size_t)sh][k];
-    return PCL_OK;
+    return sum_shards(ctx, {{counts_out_host, s.cells()}}, [&](pcl_ctx *one, int64_t *p) {
+        return pcl_step_phase_layered(one, n_laws, kinds, g, n_bins, mu, F, n_layers, cum, edges, center, c, seed, pass, p);
+    });
 }
 
 struct recycle_spec { // a call's arguments, checked
@@ -1230,7 +1139,7 @@ bool check_recycle(const pcl_source *src, double c, int at_rest, double top, con
 
 template <typename T>
 int launch_recycle(pcl_ctx *ctx, const store_view &v, const recycle_spec &s, const pcl_source *src, uint64_t seed, uint32_t pass,
-                   int64_t id_base, const int64_t *ids, const unsigned char *kind, const double *tables_dev, unsigned long long *out_dev) {
+                   const staged &st) {
     recycle_args<T> a{};
     for (int k = 0; k < 3; ++k) {
         void *r = nullptr, *vel = nullptr, *dr = nullptr, *dv = nullptr;
@@ -1246,8 +1155,8 @@ int launch_recycle(pcl_ctx *ctx, const store_view &v, const recycle_spec &s, con
     // E is asked for only with a spectrum: the pointer costs a wavelength-dependent scatter step its term cache (pcl_shell.hip).
     void *E = nullptr;
     if (s.n_E > 0) PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_E, &E));
-    a.E = static_cast<T *>(E); a.kind = kind; a.ids = ids; a.tables = tables_dev; a.out = out_dev;
-    a.N = v.N; a.ts = v.ts; a.id_base = id_base; a.tile_log = v.tile_log;
+    a.E = static_cast<T *>(E); a.kind = st.kind; a.ids = st.ids; a.tables = st.tables; a.out = st.out;
+    a.N = v.N; a.ts = v.ts; a.id_base = st.id_base; a.tile_log = v.tile_log;
     a.at_rest = s.at_rest; a.has_top = s.has_top; a.n_E = s.n_E; a.angular = src->angular; a.spatial = src->spatial;
     a.top2 = s.top2; a.speed = s.speed; a.cos_half_angle = src->cos_half_angle; a.radius = src->radius;
     a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32); a.pass = pass;
@@ -1261,28 +1170,15 @@ int recycle_spent(pcl_ctx *ctx, const pcl_source *src, double c, int at_rest, do
                   const double *cdf_host, const double *grid_host, uint64_t seed, uint32_t pass, int64_t *counts_out_host) {
     recycle_spec s;
     if (!ctx || !check_recycle(src, c, at_rest, top, center_host, n_E, cdf_host, grid_host, counts_out_host, s)) return bad_argument(ctx);
+    const spans out = {{counts_out_host, 2}};
     store_view v;
+    staged st(ctx);
     PCL_SWEEP_TRY(open_store(ctx, PCL_R0, &v));
-    counts_out_host[0] = counts_out_host[1] = 0;
+    zero_spans(out);
     if (v.N <= 0) return PCL_OK;
-    std::vector<uint8_t> kind_host;                                     // a store that is not uniform: as surface_reflect
-    std::vector<int64_t> ids_host;
-    bool mixed = false;
-    int64_t id_base = 0;
-    PCL_SWEEP_TRY(kind_bytes(ctx, v.N, kind_host, &mixed));
-    PCL_SWEEP_TRY(id_words(ctx, v.N, ids_host, &id_base));
-    const size_t out_bytes = 2 * sizeof(uint64_t), tab_bytes = s.tables.size() * sizeof(double);
-    const size_t id_bytes = ids_host.size() * sizeof(int64_t);
-    dev_block blk(ctx);
-    PCL_SWEEP_TRY(stage(blk, v.stream, out_bytes, s.tables.data(), tab_bytes, kind_host, ids_host));
-    char *base = static_cast<char *>(blk.p);
-    const double *tables_dev = reinterpret_cast<const double *>(base + out_bytes);
-    const int64_t *ids = id_bytes ? reinterpret_cast<const int64_t *>(base + out_bytes + tab_bytes) : nullptr;
-    const unsigned char *kind = mixed ? reinterpret_cast<const unsigned char *>(base + out_bytes + tab_bytes + id_bytes) : nullptr;
-    unsigned long long *out_dev = reinterpret_cast<unsigned long long *>(base);
-    PCL_SWEEP_TRY(v.dtype == PCL_DTYPE_F64 ? launch_recycle<double>(ctx, v, s, src, seed, pass, id_base, ids, kind, tables_dev, out_dev)
-                                           : launch_recycle<float>(ctx, v, s, src, seed, pass, id_base, ids, kind, tables_dev, out_dev));
-    return pcl_d2h(ctx, counts_out_host, base, (int64_t)out_bytes);    // the call's one synchronisation (a count is below 2^63)
+    PCL_SWEEP_TRY(stage(st, v, 2, s.tables.data(), s.tables.size(), true));
+    PCL_SWEEP_TRY(PCL_SWEEP_LAUNCH(v, launch_recycle, ctx, v, s, src, seed, pass, st));
+    return fetch(st, out);
 }
 
 int group_recycle_spent(pcl_group *group, const pcl_source *src, double c, int at_rest, double top, const double *center_host, int n_E,
@@ -1293,16 +1189,9 @@ int group_recycle_spent(pcl_group *group, const pcl_source *src, double c, int a
     recycle_spec s;
     if (n < 1 || !check_recycle(src, c, at_rest, top, center_host, n_E, cdf_host, grid_host, counts_out_host, s))
         return bad_argument(n > 0 ? ctx[0] : nullptr);
-    std::vector<int64_t> part((size_t)2 * n, 0);
-    PCL_SWEEP_TRY(for_each_shard(ctx, [&](int g, pcl_ctx *one) {
-        return pcl_step_recycle_spent(one, src, c, at_rest, top, center_host, n_E, cdf_host, grid_host, seed, pass, &part[(size_t)2 * g]);
-    }));
-    counts_out_host[0] = counts_out_host[1] = 0;
-    for (int g = 0; g < n; ++g) {
-        counts_out_host[0] += part[(size_t)2 * g];
-        counts_out_host[1] += part[(size_t)2 * g + 1];
-    }
-    return PCL_OK;
+    return sum_shards(ctx, {{counts_out_host, 2}}, [&](pcl_ctx *one, int64_t *p) {
+        return pcl_step_recycle_spent(one, src, c, at_rest, top, center_host, n_E, cdf_host, grid_host, seed, pass, p);
+    });
 }
 
 struct pabsorb_spec { // a call's arguments, checked; what the kernel compares against
@@ -1314,6 +1203,7 @@ struct pabsorb_spec { // a call's arguments, checked; what the kernel compares a
     size_t cols() const { return n_E > 0 ? (size_t)n_E : 1; }
     size_t cells() const { return (size_t)2 + rows() * cols(); }       // exposed, absorbed | by cell
     size_t lds() const { return tables.size() * sizeof(double) + cells() * sizeof(uint32_t); }
+    spans out(int64_t *counts, int64_t *by_cell) const { return {{counts, 2}, {by_cell, cells() - 2}}; }
 };
 
 // Everything PCL_ERR_ARG stands for except the NULL context; nothing is launched or written before this has passed.
@@ -1339,14 +1229,8 @@ bool check_pabsorb(int n_layers, int n_E, const double *p, const double *edges, 
     return true;
 }
 
-void zero_pabsorb(const pabsorb_spec &s, int64_t *counts, int64_t *cells) {
-    counts[0] = counts[1] = 0;
-    memset(cells, 0, (s.cells() - 2) * sizeof(int64_t));
-}
-
 template <typename T>
-int launch_pabsorb(pcl_ctx *ctx, const store_view &v, const pabsorb_spec &s, uint64_t seed, uint32_t pass, int64_t id_base,
-                   const int64_t *ids, const unsigned char *kind, const double *tables_dev, unsigned long long *out_dev) {
+int launch_pabsorb(pcl_ctx *ctx, const store_view &v, const pabsorb_spec &s, uint64_t seed, uint32_t pass, const staged &st) {
     pabsorb_args<T> a{};
     for (int k = 0; k < 3; ++k) {
         void *r = nullptr, *vel = nullptr, *dv = nullptr;
@@ -1359,8 +1243,8 @@ int launch_pabsorb(pcl_ctx *ctx, const store_view &v, const pabsorb_spec &s, uin
     // E is asked for only with energy bands: the pointer costs a wavelength-dependent scatter step its term cache (pcl_shell.hip).
     void *E = nullptr;
     if (s.n_E > 0) PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_E, &E));
-    a.E = static_cast<const T *>(E); a.kind = kind; a.ids = ids; a.tables = tables_dev; a.out = out_dev;
-    a.N = v.N; a.ts = v.ts; a.id_base = id_base; a.tile_log = v.tile_log;
+    a.E = static_cast<const T *>(E); a.kind = st.kind; a.ids = st.ids; a.tables = st.tables; a.out = st.out;
+    a.N = v.N; a.ts = v.ts; a.id_base = st.id_base; a.tile_log = v.tile_log;
     a.n_layers = s.n_layers; a.n_E = s.n_E;
     a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32); a.pass = pass;
     const size_t lds = s.lds();                                         // what this call uses: 24 B for a grey gas everywhere
@@ -1374,33 +1258,15 @@ int absorb_path(pcl_ctx *ctx, int n_layers, int n_E_bins, const double *p_host, 
     pabsorb_spec s;
     if (!ctx || !check_pabsorb(n_layers, n_E_bins, p_host, edges_host, center_host, E_edges_host, counts_out_host, cells_out_host, s))
         return bad_argument(ctx);
+    const spans out = s.out(counts_out_host, cells_out_host);
     store_view v;
+    staged st(ctx);
     PCL_SWEEP_TRY(open_store(ctx, PCL_V0, &v));
-    zero_pabsorb(s, counts_out_host, cells_out_host);
+    zero_spans(out);
     if (v.N <= 0) return PCL_OK;
-    std::vector<uint8_t> kind_host;                                     // a store that is not uniform: as surface_reflect;
-    std::vector<int64_t> ids_host;                                      // the ids only if somebody may draw
-    bool mixed = false;
-    int64_t id_base = 0;
-    PCL_SWEEP_TRY(kind_bytes(ctx, v.N, kind_host, &mixed));
-    if (s.draws) PCL_SWEEP_TRY(id_words(ctx, v.N, ids_host, &id_base));
-    const size_t cells = s.cells();
-    const size_t out_bytes = cells * sizeof(uint64_t), tab_bytes = s.tables.size() * sizeof(double);
-    const size_t id_bytes = ids_host.size() * sizeof(int64_t);
-    dev_block blk(ctx);
-    PCL_SWEEP_TRY(stage(blk, v.stream, out_bytes, s.tables.data(), tab_bytes, kind_host, ids_host));
-    char *base = static_cast<char *>(blk.p);
-    const double *tables_dev = reinterpret_cast<const double *>(base + out_bytes);
-    const int64_t *ids = id_bytes ? reinterpret_cast<const int64_t *>(base + out_bytes + tab_bytes) : nullptr;
-    const unsigned char *kind = mixed ? reinterpret_cast<const unsigned char *>(base + out_bytes + tab_bytes + id_bytes) : nullptr;
-    unsigned long long *out_dev = reinterpret_cast<unsigned long long *>(base);
-    PCL_SWEEP_TRY(v.dtype == PCL_DTYPE_F64 ? launch_pabsorb<double>(ctx, v, s, seed, pass, id_base, ids, kind, tables_dev, out_dev)
-                                           : launch_pabsorb<float>(ctx, v, s, seed, pass, id_base, ids, kind, tables_dev, out_dev));
-    std::vector<int64_t> out(cells);
-    PCL_SWEEP_TRY(pcl_d2h(ctx, out.data(), base, (int64_t)out_bytes)); // the call's one synchronisation (a count is below 2^63)
-    counts_out_host[0] = out[0]; counts_out_host[1] = out[1];
-    memcpy(cells_out_host, out.data() + 2, (cells - 2) * sizeof(int64_t));
-    return PCL_OK;
+    PCL_SWEEP_TRY(stage(st, v, s.cells(), s.tables.data(), s.tables.size(), s.draws));   // the ids only if somebody may draw
+    PCL_SWEEP_TRY(PCL_SWEEP_LAUNCH(v, launch_pabsorb, ctx, v, s, seed, pass, st));
+    return fetch(st, out);
 }
 
 int group_absorb_path(pcl_group *group, int n_layers, int n_E_bins, const double *p_host, const double *edges_host,
@@ -1412,19 +1278,9 @@ int group_absorb_path(pcl_group *group, int n_layers, int n_E_bins, const double
     pabsorb_spec s;
     if (n < 1 || !check_pabsorb(n_layers, n_E_bins, p_host, edges_host, center_host, E_edges_host, counts_out_host, cells_out_host, s))
         return bad_argument(n > 0 ? ctx[0] : nullptr);
-    const size_t cells = s.cells();
-    std::vector<std::vector<int64_t>> part((size_t)n, std::vector<int64_t>(cells, 0));
-    PCL_SWEEP_TRY(for_each_shard(ctx, [&](int g, pcl_ctx *one) {
-        int64_t *p = part[(size_t)g].data();
+    return sum_shards(ctx, s.out(counts_out_host, cells_out_host), [&](pcl_ctx *one, int64_t *p) {
         return pcl_step_absorb_path(one, n_layers, n_E_bins, p_host, edges_host, center_host, E_edges_host, seed, pass, p, p + 2);
-    }));
-    zero_pabsorb(s, counts_out_host, cells_out_host);
-    for (int g = 0; g < n; ++g) {
-        const int64_t *p = part[(size_t)g].data();
-        counts_out_host[0] += p[0]; counts_out_host[1] += p[1];
-        for (size_t k = 2; k < cells; ++k) cells_out_host[k - 2] += p[k];
-    }
-    return PCL_OK;
+    });
 }
 
 } // namespace

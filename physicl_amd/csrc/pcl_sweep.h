@@ -8,6 +8,7 @@
 
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <vector>
 
 namespace pcl_sweep {
@@ -62,12 +63,53 @@ inline bool check_edges(const double *e, int n_bins, edge_transform t, std::vect
     return true;
 }
 
+// A call's one device block: out_bytes of zeroed tallies at 0 | the tables (if any) | the ids (if any; out_bytes and tab_bytes
+// are multiples of 8) | the kind bytes (if any).  Where each part starts, and the size of the whole.
+struct block_layout { size_t tables, ids, kind, total; };
+
+inline block_layout layout_of(size_t out_bytes, size_t tab_bytes, size_t n_ids, size_t n_kind) {
+    block_layout at;
+    at.tables = out_bytes;
+    at.ids = at.tables + tab_bytes;
+    at.kind = at.ids + n_ids * sizeof(int64_t);
+    at.total = at.kind + n_kind;
+    return at;
+}
+
+// A call's outputs: the caller's arrays, in the order of the tallies' cells.  An array nobody asked for is a span of length 0
+// and may be NULL: it is never handed to memset / memcpy.
+struct span { int64_t *p; size_t n; };
+typedef std::vector<span> spans;
+
+inline size_t cells_of(const spans &out) {
+    size_t n = 0;
+    for (const span &s : out) n += s.n;
+    return n;
+}
+
+inline void zero_spans(const spans &out) {
+    for (const span &s : out)
+        if (s.n) memset(s.p, 0, s.n * sizeof(int64_t));
+}
+
+// flat[0 .. cells_of(out)) written over the spans / added onto them
+inline void copy_to_spans(const spans &out, const int64_t *flat) {
+    for (const span &s : out) {
+        if (s.n) memcpy(s.p, flat, s.n * sizeof(int64_t));
+        flat += s.n;
+    }
+}
+
+inline void add_to_spans(const spans &out, const int64_t *flat) {
+    for (const span &s : out)
+        for (size_t k = 0; k < s.n; ++k) s.p[k] += *flat++;
+}
+
 } // namespace pcl_sweep
 
 #ifdef __HIPCC__
 #include <hip/hip_runtime.h>
 
-#include <cstring>
 #include <new>
 #include <system_error>
 #include <thread>
@@ -128,7 +170,7 @@ inline int open_store(pcl_ctx *ctx, int first_field, store_view *v, void **first
 }
 
 // Plain Objects carry no energy.  *mixed: the store holds some, and ``kind`` then its N kind bytes (the ABI hands them out
-// on the host only) for stage() to put behind the tables; empty otherwise.
+// on the host only) for stage() to put behind the ids; empty otherwise.
 inline int kind_bytes(pcl_ctx *ctx, int64_t N, std::vector<uint8_t> &kind, bool *mixed) {
     int uniform = 0;
     *mixed = false;
@@ -161,22 +203,59 @@ inline int id_words(pcl_ctx *ctx, int64_t N, std::vector<int64_t> &ids, int64_t 
     return PCL_OK;
 }
 
-// A call's one device block, on the store's stream: out_bytes of zeroed tallies | the tables (if any) | the ids (if any; out_bytes
-// and tab_bytes are multiples of 8) | the kind bytes (if any)
-inline int stage(dev_block &blk, hipStream_t stream, size_t out_bytes, const double *tables, size_t tab_bytes,
-                 const std::vector<uint8_t> &kind = {}, const std::vector<int64_t> &ids = {}) {
-    const size_t id_bytes = ids.size() * sizeof(int64_t);
-    PCL_SWEEP_TRY(pcl_dev_alloc(blk.ctx, (int64_t)(out_bytes + tab_bytes + id_bytes + kind.size()), &blk.p));
-    char *base = static_cast<char *>(blk.p);
-    if (hipMemsetAsync(base, 0, out_bytes, stream) != hipSuccess) return PCL_ERR_HIP;
-    if (tab_bytes && hipMemcpyAsync(base + out_bytes, tables, tab_bytes, hipMemcpyHostToDevice, stream) != hipSuccess) return PCL_ERR_HIP;
-    if (id_bytes && hipMemcpyAsync(base + out_bytes + tab_bytes, ids.data(), id_bytes, hipMemcpyHostToDevice, stream) != hipSuccess)
+// A call's device block (layout_of) as the kernels see it: typed pointers into it -- ids and kind NULL where the part is not there --,
+// the id of slot 0, and the host copies of ids and kinds, which the copies on the stream read until the call's synchronisation.
+struct staged {
+    dev_block blk;
+    unsigned long long *out = nullptr;
+    const double *tables = nullptr;
+    const int64_t *ids = nullptr;
+    const unsigned char *kind = nullptr;
+    int64_t id_base = 0;
+    size_t out_bytes = 0;
+    std::vector<int64_t> ids_host;
+    std::vector<uint8_t> kind_host;
+    explicit staged(pcl_ctx *c) : blk(c) {}
+};
+
+// Fills it on the store's stream: ``cells`` zeroed tallies, the n_tables doubles of ``tables``, and what a store that is not
+// uniform makes necessary -- the kinds if it holds a plain Object (want_kinds), the ids if they are not id[0] + index (want_ids:
+// a unit that draws).  Both come over the host link and go back up, every call (kind_bytes / id_words say what that costs).
+inline int stage(staged &st, const store_view &v, size_t cells, const double *tables, size_t n_tables, bool want_ids,
+                 bool want_kinds = true) {
+    pcl_ctx *ctx = st.blk.ctx;
+    bool mixed = false;
+    if (want_kinds) PCL_SWEEP_TRY(kind_bytes(ctx, v.N, st.kind_host, &mixed));
+    if (want_ids) PCL_SWEEP_TRY(id_words(ctx, v.N, st.ids_host, &st.id_base));
+    const size_t tab_bytes = n_tables * sizeof(double), id_bytes = st.ids_host.size() * sizeof(int64_t);
+    st.out_bytes = cells * sizeof(uint64_t);
+    const block_layout at = layout_of(st.out_bytes, tab_bytes, st.ids_host.size(), st.kind_host.size());
+    PCL_SWEEP_TRY(pcl_dev_alloc(ctx, (int64_t)at.total, &st.blk.p));
+    char *base = static_cast<char *>(st.blk.p);
+    if (hipMemsetAsync(base, 0, st.out_bytes, v.stream) != hipSuccess) return PCL_ERR_HIP;
+    if (tab_bytes && hipMemcpyAsync(base + at.tables, tables, tab_bytes, hipMemcpyHostToDevice, v.stream) != hipSuccess) return PCL_ERR_HIP;
+    if (id_bytes && hipMemcpyAsync(base + at.ids, st.ids_host.data(), id_bytes, hipMemcpyHostToDevice, v.stream) != hipSuccess)
         return PCL_ERR_HIP;
-    if (!kind.empty() &&
-        hipMemcpyAsync(base + out_bytes + tab_bytes + id_bytes, kind.data(), kind.size(), hipMemcpyHostToDevice, stream) != hipSuccess)
+    if (mixed && hipMemcpyAsync(base + at.kind, st.kind_host.data(), st.kind_host.size(), hipMemcpyHostToDevice, v.stream) != hipSuccess)
         return PCL_ERR_HIP;
+    st.out = reinterpret_cast<unsigned long long *>(base);
+    st.tables = reinterpret_cast<const double *>(base + at.tables);
+    st.ids = id_bytes ? reinterpret_cast<const int64_t *>(base + at.ids) : nullptr;
+    st.kind = mixed ? reinterpret_cast<const unsigned char *>(base + at.kind) : nullptr;
     return PCL_OK;
 }
+
+// The call's one synchronisation: the tallies come back onto the caller's arrays (a count is below 2^63)
+inline int fetch(const staged &st, const spans &out) {
+    if (out.size() == 1) return pcl_d2h(st.blk.ctx, out[0].p, st.out, (int64_t)st.out_bytes);
+    std::vector<int64_t> flat(st.out_bytes / sizeof(int64_t));
+    PCL_SWEEP_TRY(pcl_d2h(st.blk.ctx, flat.data(), st.out, (int64_t)st.out_bytes));
+    copy_to_spans(out, flat.data());
+    return PCL_OK;
+}
+
+// launch<double> or launch<float>, as the store's elements are
+#define PCL_SWEEP_LAUNCH(v, launch, ...) ((v).dtype == PCL_DTYPE_F64 ? launch<double>(__VA_ARGS__) : launch<float>(__VA_ARGS__))
 
 inline int shards_of(pcl_group *group, std::vector<pcl_ctx *> &ctx) {
     int n = 0;
@@ -206,6 +285,18 @@ int for_each_shard(const std::vector<pcl_ctx *> &ctx, F fn) {
     if (n > 0) one(0);
     for (auto &t : th) t.join();
     for (int g = 0; g < n; ++g) PCL_SWEEP_TRY(rcs[(size_t)g]);
+    return PCL_OK;
+}
+
+// The group form of a sweep: fn(ctx, flat) -- the unit's own pcl_step_* entry on one shard, its outputs laid out in ``flat`` in
+// the order of the cells -- for the shards side by side.  Only when every shard has succeeded are the caller's arrays zeroed
+// and the shards' tallies added up: a failing shard leaves them as they were.
+template <typename F>
+int sum_shards(const std::vector<pcl_ctx *> &ctx, const spans &out, F fn) {
+    std::vector<std::vector<int64_t>> part(ctx.size(), std::vector<int64_t>(cells_of(out), 0));
+    PCL_SWEEP_TRY(for_each_shard(ctx, [&](int g, pcl_ctx *one) { return fn(one, part[(size_t)g].data()); }));
+    zero_spans(out);
+    for (const std::vector<int64_t> &p : part) add_to_spans(out, p.data());
     return PCL_OK;
 }
 

@@ -689,6 +689,11 @@ class ShellCrossingMeasureStep(tally.TallyStep):
 _U32 = np.uint64(0xFFFFFFFF)
 
 
+def _photons(objs):
+    """Who is a photon -- exactly ``PhotonObject``, as the light steps decide it."""
+    return np.array([type(o) is PhotonObject for o in objs], dtype=bool)
+
+
 def _philox_block(ids, seed, word2, word3):
     """(u53(w0, w1), u53(w2, w3)) of the Philox4x32-10 block with counter (id_lo, id_hi, word2, word3) and key (seed_lo,
     seed_hi) per id, with numpy -- the block and the 53-bit uniform of include/physicl_hip.h (pcl_store_apply_source)."""
@@ -794,7 +799,7 @@ def _surface_bounce(r, dr, v, photon, ids, radius, center, albedo, mode, c, seed
     return out
 
 
-class SurfaceReflectStep(DeviceStep, MeasureStep):
+class SurfaceReflectStep(tally.WriterStep):
     """A reflecting sphere: the ground of a radial problem (not in the reference).  Every photon whose last move took it into
     the sphere of ``radius`` about ``center`` (code units) is put back: reflected at the point where the move met the sphere
     -- ``mode="lambertian"``: cosine-weighted about the outward normal, ``"specular"``: mirrored -- with the rest of the move
@@ -826,7 +831,6 @@ class SurfaceReflectStep(DeviceStep, MeasureStep):
     One launch per light step: the K-passes-per-launch kernels cannot bounce a photon between two of their passes, and
     ``sim.launch_note`` says so.  On host-resident objects (``step.run(sim)`` outside a device loop) the same state is made with
     numpy, the ids being the places in the object list -- what an upload would give them."""
-    _fuse_role = None
     _NOTE = "one launch per light step: a SurfaceReflectStep bounces photons off its sphere behind every pass, which the " \
             "K-passes-per-launch kernels cannot carry"
 
@@ -840,30 +844,19 @@ class SurfaceReflectStep(DeviceStep, MeasureStep):
         self.reflected, self.absorbed = int(reflected), int(absorbed)
         self.data.append(tally.object_row([tally._snap(sim.t), self.reflected, self.absorbed]))
 
-    def _device_run(self, sim):
-        if getattr(sim, "launch_note", self._NOTE) is None and sim._k_wanted() > 1:      # (a device run only: the host path says nothing)
-            sim.launch_note = self._NOTE
-        self._pass += 1
-        counts = sim._dev.surface_reflect(self.radius, self.center, self.albedo, self.mode, _c_h_literals()[0], sim.seed, self._pass)
-        sim._scattered = True                            # velocities were replaced on the device
-        self._record_pass(sim, *sim._global(list(counts)))   # (every rank issues it, also with an empty shard)
+    _writes = ("r", "dr", "v", "dv")
 
-    def run(self, sim):
-        if getattr(sim, "_residency", None) == "host" and getattr(sim, "_batch", None) is None \
-                and (sim.comm is None or sim.comm.world == 1):
-            objs = list(sim.objects)
-            self._pass += 1
-            photon = np.array([type(o) is PhotonObject for o in objs], dtype=bool)
-            new = _surface_bounce(tally.vec3(objs, "r"), tally.vec3(objs, "dr"), tally.vec3(objs, "v"), photon, np.arange(len(objs)),
-                                  self.radius, self.center, self.albedo, self.mode, _c_h_literals()[0], getattr(sim, "seed", 0), self._pass)
-            for k in np.flatnonzero(new["hit"]).tolist():
-                o = objs[k]
-                o.r = Measurement._from_code(new["r"][k], like=o.r, units="m**1")
-                o.dr = Measurement._from_code(new["dr"][k], units="m**1")
-                o.v, o.dv = np.array(new["v"][k], dtype=np.double), np.array(new["dv"][k], dtype=np.double)   # plain arrays, as a scatter leaves them
-            self._record_pass(sim, new["reflected"].sum(), new["absorbed"].sum())
-            return None
-        return DeviceStep.run(self, sim)
+    def _sweep(self, sim, prep):
+        return [np.array(sim._dev.surface_reflect(self.radius, self.center, self.albedo, self.mode, _c_h_literals()[0], sim.seed, self._pass),
+                         dtype=np.int64)]
+
+    def _reduce(self, sim, parts):
+        return [sim._global(parts[0].tolist())]          # the two counts alone, as ever
+
+    def _host_sweep(self, objs, ids, seed, prep):
+        new = _surface_bounce(tally.vec3(objs, "r"), tally.vec3(objs, "dr"), tally.vec3(objs, "v"), _photons(objs), ids,
+                              self.radius, self.center, self.albedo, self.mode, _c_h_literals()[0], seed, self._pass)
+        return new, new["hit"], (new["reflected"].sum(), new["absorbed"].sum())
 
 
 # ---------------------------------------------------------------------------------------------- phase functions
@@ -937,7 +930,7 @@ def _phase_redirect(v, dv, photon, ids, phase, g, c, seed, n_pass, dtype=np.floa
     return out
 
 
-class PhaseFunctionStep(DeviceStep, MeasureStep):
+class PhaseFunctionStep(tally.WriterStep):
     """The scattering angle of a pass (not in the reference).  ``ScatterIsotropicStep`` decides who scatters and gives a hit
     photon a direction whose polar angle is uniform about the x axis -- which bunches directions at the poles of x and does not
     depend on where the photon came from.  This step, placed directly BEHIND the scatter step (measures may stand between),
@@ -963,7 +956,6 @@ class PhaseFunctionStep(DeviceStep, MeasureStep):
     One launch per light step: the K-passes-per-launch kernels cannot re-direct a photon between two of their passes, and
     ``sim.launch_note`` says so.  On host-resident objects (``step.run(sim)`` outside a device loop) the same state is made with
     numpy, the ids being the places in the object list."""
-    _fuse_role = None
     _NOTE = "one launch per light step: a PhaseFunctionStep re-directs the scattered photons behind every pass, which the " \
             "K-passes-per-launch kernels cannot carry"
 
@@ -977,36 +969,21 @@ class PhaseFunctionStep(DeviceStep, MeasureStep):
         self.redirected = int(redirected)
         self.data.append(tally.object_row([tally._snap(sim.t), self.redirected]))
 
-    @staticmethod
-    def _refuse_py_semantics(sim):
+    def _refuse(self, sim):
         if getattr(sim, "_py_semantics", None) is not None and sim._py_semantics():
             raise ValueError("PhaseFunctionStep needs cl_on=True: under the reference's Python semantics a scattered photon is left "
                              "with dv = v_old, not v' - v_old, so its direction before the scatter cannot be read off the store")
 
-    def _device_run(self, sim):
-        self._refuse_py_semantics(sim)
-        if getattr(sim, "launch_note", self._NOTE) is None and sim._k_wanted() > 1:      # (a device run only: the host path says nothing)
-            sim.launch_note = self._NOTE
-        self._pass += 1
-        count = sim._dev.phase_redirect(self.phase, self.g, _c_h_literals()[0], sim.seed, self._pass)
-        sim._scattered = True                            # velocities were replaced on the device
-        self._record_pass(sim, sim._global([count])[0])  # (every rank issues it, also with an empty shard)
+    def _sweep(self, sim, prep):
+        return [np.array([sim._dev.phase_redirect(self.phase, self.g, _c_h_literals()[0], sim.seed, self._pass)], dtype=np.int64)]
 
-    def run(self, sim):
-        self._refuse_py_semantics(sim)
-        if getattr(sim, "_residency", None) == "host" and getattr(sim, "_batch", None) is None \
-                and (sim.comm is None or sim.comm.world == 1):
-            objs = list(sim.objects)
-            self._pass += 1
-            photon = np.array([type(o) is PhotonObject for o in objs], dtype=bool)
-            new = _phase_redirect(tally.vec3(objs, "v"), tally.vec3(objs, "dv"), photon, np.arange(len(objs)), self.phase, self.g,
-                                  _c_h_literals()[0], getattr(sim, "seed", 0), self._pass)
-            for k in np.flatnonzero(new["redirected"]).tolist():
-                o = objs[k]
-                o.v, o.dv = np.array(new["v"][k], dtype=np.double), np.array(new["dv"][k], dtype=np.double)   # plain arrays, as a scatter leaves them
-            self._record_pass(sim, new["redirected"].sum())
-            return None
-        return DeviceStep.run(self, sim)
+    def _reduce(self, sim, parts):
+        return [sim._global(parts[0].tolist())]          # the count alone, as ever
+
+    def _host_sweep(self, objs, ids, seed, prep):
+        new = _phase_redirect(tally.vec3(objs, "v"), tally.vec3(objs, "dv"), _photons(objs), ids, self.phase, self.g,
+                              _c_h_literals()[0], seed, self._pass)
+        return new, new["redirected"], (new["redirected"].sum(),)
 
 
 # ---------------------------------------------------------------------------------------------- absorbing media
@@ -1081,7 +1058,7 @@ def _absorb_scattered(r, v, dv, E, photon, ids, omega0, edges, center, E_bins, s
     return out
 
 
-class AbsorptionStep(DeviceStep, MeasureStep):
+class AbsorptionStep(tally.WriterStep):
     """An absorbing medium (not in the reference): the single-scattering albedo ``omega0``, the chance that an interaction is a
     scatter and not an absorption.  ``ScatterIsotropicStep`` decides who interacts; this step, placed anywhere BEHIND the scatter
     step of a pass and before the next Newton step (before or behind a ``PhaseFunctionStep``; measures may stand between), lets
@@ -1120,7 +1097,6 @@ class AbsorptionStep(DeviceStep, MeasureStep):
     One launch per light step: the K-passes-per-launch kernels cannot absorb a photon between two of their passes, and
     ``sim.launch_note`` says so.  On host-resident objects (``step.run(sim)`` outside a device loop) the same state is made with
     numpy, the ids being the places in the object list."""
-    _fuse_role = None
     _NOTE = "one launch per light step: an AbsorptionStep absorbs interacting photons behind every pass, which the " \
             "K-passes-per-launch kernels cannot carry"
 
@@ -1140,39 +1116,20 @@ class AbsorptionStep(DeviceStep, MeasureStep):
         cells = [self.absorbed_by_layer.copy()] + ([] if self.E_hist is None else [self.E_hist.copy()])
         self.data.append(tally.object_row([tally._snap(sim.t), self.interacted, self.absorbed] + cells))
 
-    @staticmethod
-    def _refuse_py_semantics(sim):
+    def _refuse(self, sim):
         if getattr(sim, "_py_semantics", None) is not None and sim._py_semantics():
             raise ValueError("AbsorptionStep needs cl_on=True: under the reference's Python semantics a scattered photon is left "
                              "with dv = v_old, not v' - v_old, so who interacted in this pass cannot be read off the store")
 
-    def _device_run(self, sim):
-        self._refuse_py_semantics(sim)
-        if getattr(sim, "launch_note", self._NOTE) is None and sim._k_wanted() > 1:      # (a device run only: the host path says nothing)
-            sim.launch_note = self._NOTE
-        self._pass += 1
+    def _sweep(self, sim, prep):
         interacted, absorbed, by_layer, E_hist = sim._dev.absorb_scattered(self.omega0, self.edges, self.center, self.E_bins, sim.seed, self._pass)
-        sim._scattered = True                            # velocities were replaced on the device
-        # one payload, cut like the shell step's row where it is longer than one call of the library's own communicator carries
-        # (every rank issues it, also with an empty shard)
-        _, (both, by_layer, E_hist) = tally.reduce_parts(sim, [np.array([interacted, absorbed], dtype=np.int64), np.asarray(by_layer), E_hist])
-        self._record_pass(sim, both[0], both[1], by_layer, E_hist)
+        return [np.array([interacted, absorbed], dtype=np.int64), np.asarray(by_layer), E_hist]
 
-    def run(self, sim):
-        self._refuse_py_semantics(sim)
-        if getattr(sim, "_residency", None) == "host" and getattr(sim, "_batch", None) is None \
-                and (sim.comm is None or sim.comm.world == 1):
-            objs = list(sim.objects)
-            self._pass += 1
-            E, photon = tally.photon_energies(objs, PhotonObject)
-            new = _absorb_scattered(tally.vec3(objs, "r"), tally.vec3(objs, "v"), tally.vec3(objs, "dv"), E, photon, np.arange(len(objs)),
-                                    self.omega0, self.edges, self.center, self.E_bins, getattr(sim, "seed", 0), self._pass)
-            for k in np.flatnonzero(new["absorbed"]).tolist():
-                o = objs[k]
-                o.v, o.dv = np.array(new["v"][k], dtype=np.double), np.array(new["dv"][k], dtype=np.double)   # plain arrays, as a scatter leaves them
-            self._record_pass(sim, new["interacted"].sum(), new["absorbed"].sum(), new["absorbed_by_layer"], new["E_hist"])
-            return None
-        return DeviceStep.run(self, sim)
+    def _host_sweep(self, objs, ids, seed, prep):
+        E, photon = tally.photon_energies(objs, PhotonObject)
+        new = _absorb_scattered(tally.vec3(objs, "r"), tally.vec3(objs, "v"), tally.vec3(objs, "dv"), E, photon, ids,
+                                self.omega0, self.edges, self.center, self.E_bins, seed, self._pass)
+        return new, new["absorbed"], (new["interacted"].sum(), new["absorbed"].sum(), new["absorbed_by_layer"], new["E_hist"])
 
     terminate = tally.TallyStep.terminate                # (a row holds arrays: written as the tally steps write theirs, as plain lists)
 
@@ -1348,7 +1305,7 @@ def _layered_phase_apply(r, v, dv, photon, ids, laws, cum, edges, center, c, see
     return out
 
 
-class LayeredPhaseStep(DeviceStep, MeasureStep):
+class LayeredPhaseStep(tally.WriterStep):
     """Phase functions by radial layer, mixed and tabulated (not in the reference).  ``PhaseFunctionStep`` applies one law to the
     whole of space; this step, placed where a ``PhaseFunctionStep`` would stand -- directly BEHIND the scatter step of a pass
     (measures may stand between), before or behind an ``AbsorptionStep`` --, lets the law depend on where the photon stands: a
@@ -1383,7 +1340,6 @@ class LayeredPhaseStep(DeviceStep, MeasureStep):
     One launch per light step: the K-passes-per-launch kernels cannot re-direct a photon between two of their passes, and
     ``sim.launch_note`` says so.  On host-resident objects (``step.run(sim)`` outside a device loop) the same state is made with
     numpy, the ids being the places in the object list."""
-    _fuse_role = None
     _NOTE = "one launch per light step: a LayeredPhaseStep re-directs the scattered photons behind every pass, which the " \
             "K-passes-per-launch kernels cannot carry"
 
@@ -1412,34 +1368,15 @@ class LayeredPhaseStep(DeviceStep, MeasureStep):
                     raise ValueError("a pass holds one phase step: the simulation's steps hold a %s beside this LayeredPhaseStep, and "
                                      "both would draw from the same Philox blocks" % type(other).__name__)
 
-    def _device_run(self, sim):
-        self._refuse(sim)
-        if getattr(sim, "launch_note", self._NOTE) is None and sim._k_wanted() > 1:      # (a device run only: the host path says nothing)
-            sim.launch_note = self._NOTE
-        self._pass += 1
+    def _sweep(self, sim, prep):
         scattered, redirected, by_layer, by_law = sim._dev.phase_layered(self._laws, self.cum, self.edges, self.center, _c_h_literals()[0],
                                                                          sim.seed, self._pass)
-        sim._scattered = True                            # velocities were replaced on the device
-        # one payload (every rank issues it, also with an empty shard)
-        _, (both, by_layer, by_law) = tally.reduce_parts(sim, [np.array([scattered, redirected], dtype=np.int64), np.asarray(by_layer),
-                                                               np.asarray(by_law)])
-        self._record_pass(sim, both[0], both[1], by_layer, by_law)
+        return [np.array([scattered, redirected], dtype=np.int64), np.asarray(by_layer), np.asarray(by_law)]
 
-    def run(self, sim):
-        self._refuse(sim)
-        if getattr(sim, "_residency", None) == "host" and getattr(sim, "_batch", None) is None \
-                and (sim.comm is None or sim.comm.world == 1):
-            objs = list(sim.objects)
-            self._pass += 1
-            photon = np.array([type(o) is PhotonObject for o in objs], dtype=bool)
-            new = _layered_phase_apply(tally.vec3(objs, "r"), tally.vec3(objs, "v"), tally.vec3(objs, "dv"), photon, np.arange(len(objs)),
-                                       self._laws, self.cum, self.edges, self.center, _c_h_literals()[0], getattr(sim, "seed", 0), self._pass)
-            for k in np.flatnonzero(new["redirected"]).tolist():
-                o = objs[k]
-                o.v, o.dv = np.array(new["v"][k], dtype=np.double), np.array(new["dv"][k], dtype=np.double)   # plain arrays, as a scatter leaves them
-            self._record_pass(sim, new["scattered"].sum(), new["redirected"].sum(), new["by_layer"], new["by_law"])
-            return None
-        return DeviceStep.run(self, sim)
+    def _host_sweep(self, objs, ids, seed, prep):
+        new = _layered_phase_apply(tally.vec3(objs, "r"), tally.vec3(objs, "v"), tally.vec3(objs, "dv"), _photons(objs), ids,
+                                   self._laws, self.cum, self.edges, self.center, _c_h_literals()[0], seed, self._pass)
+        return new, new["redirected"], (new["scattered"].sum(), new["redirected"].sum(), new["by_layer"], new["by_law"])
 
     terminate = tally.TallyStep.terminate                # (a row holds arrays: written as the tally steps write theirs, as plain lists)
 
@@ -1559,7 +1496,7 @@ def _recycle_spent(r, v, E, photon, ids, source, top, center, at_rest, spectrum,
     return {"r": r, "v": v, "dr": dr, "dv": dv, "E": E, "at_rest": rest, "escaped": gone, "spent": spent}
 
 
-class RecycleStep(DeviceStep, MeasureStep):
+class RecycleStep(tally.WriterStep):
     """A continuous source (not in the reference): the LAST step of a pass, behind a ``SurfaceReflectStep`` if there is one.  A photon
     the ground or the medium has absorbed stays in the store at rest, one that has left through the top of the atmosphere flies on for
     ever; this step gives the slots of both back to ``source``, a ``PhotonSource``.  The population stays constant
@@ -1593,7 +1530,6 @@ class RecycleStep(DeviceStep, MeasureStep):
     One launch per light step: the K-passes-per-launch kernels cannot re-emit a photon between two of their passes, and
     ``sim.launch_note`` says so.  On host-resident objects (``step.run(sim)`` outside a device loop) the same state is made with
     numpy, the ids being the places in the object list."""
-    _fuse_role = None
     _NOTE = "one launch per light step: a RecycleStep re-emits the spent photons behind every pass, which the " \
             "K-passes-per-launch kernels cannot carry"
 
@@ -1608,34 +1544,19 @@ class RecycleStep(DeviceStep, MeasureStep):
         self.recycled = self.at_rest + self.escaped
         self.data.append(tally.object_row([tally._snap(sim.t), self.at_rest, self.escaped]))
 
-    def _device_run(self, sim):
-        if getattr(sim, "launch_note", self._NOTE) is None and sim._k_wanted() > 1:      # (a device run only: the host path says nothing)
-            sim.launch_note = self._NOTE
-        self._pass += 1
-        counts = sim._dev.recycle_spent(self.source, _c_h_literals()[0], self.rest_on, self.top, self.center, self.spectrum, sim.seed, self._pass)
-        sim._scattered = True                            # velocities were replaced on the device
-        # (every rank issues it, also with an empty shard)
-        _, (both,) = tally.reduce_parts(sim, [np.array(counts, dtype=np.int64)])
-        self._record_pass(sim, both[0], both[1])
+    @property
+    def _writes(self):                                   # a recycled photon keeps its E without a spectrum
+        return ("r", "dr", "v", "dv") + (() if self.spectrum is None else ("E",))
 
-    def run(self, sim):
-        if getattr(sim, "_residency", None) == "host" and getattr(sim, "_batch", None) is None \
-                and (sim.comm is None or sim.comm.world == 1):
-            objs = list(sim.objects)
-            self._pass += 1
-            E, photon = tally.photon_energies(objs, PhotonObject)
-            new = _recycle_spent(tally.vec3(objs, "r"), tally.vec3(objs, "v"), E, photon, np.arange(len(objs)), self.source, self.top,
-                                 self.center, self.rest_on, self.spectrum, _c_h_literals()[0], getattr(sim, "seed", 0), self._pass)
-            for k in np.flatnonzero(new["spent"]).tolist():
-                o = objs[k]
-                o.r = Measurement._from_code(new["r"][k], like=o.r, units="m**1")
-                o.dr = Measurement._from_code(new["dr"][k], units="m**1")
-                o.v, o.dv = np.array(new["v"][k], dtype=np.double), np.array(new["dv"][k], dtype=np.double)   # plain arrays, as a scatter leaves them
-                if self.spectrum is not None:
-                    o.E = Measurement._from_code(new["E"][k], like=o.E, units="J**1") if isinstance(o.E, Measurement) else np.double(new["E"][k])
-            self._record_pass(sim, new["at_rest"].sum(), new["escaped"].sum())
-            return None
-        return DeviceStep.run(self, sim)
+    def _sweep(self, sim, prep):
+        return [np.array(sim._dev.recycle_spent(self.source, _c_h_literals()[0], self.rest_on, self.top, self.center, self.spectrum, sim.seed,
+                                                self._pass), dtype=np.int64)]
+
+    def _host_sweep(self, objs, ids, seed, prep):
+        E, photon = tally.photon_energies(objs, PhotonObject)
+        new = _recycle_spent(tally.vec3(objs, "r"), tally.vec3(objs, "v"), E, photon, ids, self.source, self.top,
+                             self.center, self.rest_on, self.spectrum, _c_h_literals()[0], seed, self._pass)
+        return new, new["spent"], (new["at_rest"].sum(), new["escaped"].sum())
 
 
 # ---------------------------------------------------------------------------------------------- absorption along the path
@@ -1725,7 +1646,7 @@ def _absorb_path(r, v, dv, E, photon, ids, p, edges, center, E_edges, seed, n_pa
     return {"v": v, "dv": dv, "exposed": exposed, "absorbed": absorbed, "layer": layer, "band": band, "absorbed_by_cell": cells}
 
 
-class PathAbsorptionStep(DeviceStep, MeasureStep):
+class PathAbsorptionStep(tally.WriterStep):
     """A gas that absorbs without scattering (not in the reference): continuous, Beer-Lambert absorption along the move every photon
     makes in a pass, with a coefficient that depends on the radial layer the photon stands in and on the band its energy falls in --
     ozone above a thin Rayleigh atmosphere, a water-vapour band.  ``AbsorptionStep`` acts on the photons the scatter step made
@@ -1766,7 +1687,6 @@ class PathAbsorptionStep(DeviceStep, MeasureStep):
     One launch per light step: the K-passes-per-launch kernels cannot absorb a photon between two of their passes, and
     ``sim.launch_note`` says so.  On host-resident objects (``step.run(sim)`` outside a device loop) the same state is made with
     numpy, the ids being the places in the object list."""
-    _fuse_role = None
     _NOTE = "one launch per light step: a PathAbsorptionStep absorbs moving photons behind every pass, which the " \
             "K-passes-per-launch kernels cannot carry"
 
@@ -1782,32 +1702,18 @@ class PathAbsorptionStep(DeviceStep, MeasureStep):
         self.absorbed_by_cell = np.array(cells, dtype=np.int64).reshape(self.k.shape)
         self.data.append(tally.object_row([tally._snap(sim.t), self.exposed, self.absorbed, self.absorbed_by_cell.copy()]))
 
-    def _device_run(self, sim):
-        p = _path_probability(self.k, _c_h_literals()[0], sim._dt_code())
-        if getattr(sim, "launch_note", self._NOTE) is None and sim._k_wanted() > 1:      # (a device run only: the host path says nothing)
-            sim.launch_note = self._NOTE
-        self._pass += 1
-        exposed, absorbed, cells = sim._dev.absorb_path(p, self.edges, self.center, self.E_edges, sim.seed, self._pass)
-        sim._scattered = True                            # velocities were replaced on the device
-        # (every rank issues it, also with an empty shard)
-        _, (both, cells) = tally.reduce_parts(sim, [np.array([exposed, absorbed], dtype=np.int64), np.asarray(cells, dtype=np.int64)])
-        self._record_pass(sim, both[0], both[1], cells)
+    def _prepare(self, sim, on_host):                    # p of this pass's dt; a dt that is refused raises here
+        return _path_probability(self.k, _c_h_literals()[0], np.asarray(sim.dt) if on_host else sim._dt_code())
 
-    def run(self, sim):
-        if getattr(sim, "_residency", None) == "host" and getattr(sim, "_batch", None) is None \
-                and (sim.comm is None or sim.comm.world == 1):
-            p = _path_probability(self.k, _c_h_literals()[0], np.asarray(sim.dt))
-            objs = list(sim.objects)
-            self._pass += 1
-            E, photon = tally.photon_energies(objs, PhotonObject)
-            new = _absorb_path(tally.vec3(objs, "r"), tally.vec3(objs, "v"), tally.vec3(objs, "dv"), E, photon, np.arange(len(objs)), p,
-                               self.edges, self.center, self.E_edges, getattr(sim, "seed", 0), self._pass)
-            for k in np.flatnonzero(new["absorbed"]).tolist():
-                o = objs[k]
-                o.v, o.dv = np.array(new["v"][k], dtype=np.double), np.array(new["dv"][k], dtype=np.double)   # plain arrays, as a scatter leaves them
-            self._record_pass(sim, new["exposed"].sum(), new["absorbed"].sum(), new["absorbed_by_cell"])
-            return None
-        return DeviceStep.run(self, sim)
+    def _sweep(self, sim, p):
+        exposed, absorbed, cells = sim._dev.absorb_path(p, self.edges, self.center, self.E_edges, sim.seed, self._pass)
+        return [np.array([exposed, absorbed], dtype=np.int64), np.asarray(cells, dtype=np.int64)]
+
+    def _host_sweep(self, objs, ids, seed, p):
+        E, photon = tally.photon_energies(objs, PhotonObject)
+        new = _absorb_path(tally.vec3(objs, "r"), tally.vec3(objs, "v"), tally.vec3(objs, "dv"), E, photon, ids, p,
+                           self.edges, self.center, self.E_edges, seed, self._pass)
+        return new, new["absorbed"], (new["exposed"].sum(), new["absorbed"].sum(), new["absorbed_by_cell"])
 
     terminate = tally.TallyStep.terminate                # (a row holds arrays: written as the tally steps write theirs, as plain lists)
 

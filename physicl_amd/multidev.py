@@ -275,30 +275,29 @@ class MultiDevice:
         parts = self._each(lambda s: s.shell_crossings(radii, center, E_edges, mu_edges))
         return tuple(None if part[0] is None else self._sum(list(part)) for part in zip(*parts))
 
+    def _sum_parts(self, name, *a, **kw):
+        """``name`` on every shard, the answers -- a count, or a tuple of counts and tallies -- added up position by position
+        (a tally that was not asked for stays None; ids are global, so every shard writes its own photons)."""
+        outs = self._each(lambda s: getattr(s, name)(*a, **kw))
+        return tuple(self._sum(list(part)) for part in zip(*outs)) if isinstance(outs[0], tuple) else self._sum(outs)
+
     def surface_reflect(self, *a, **kw):
-        outs = self._each(lambda s: s.surface_reflect(*a, **kw))
-        return sum(o[0] for o in outs), sum(o[1] for o in outs)
+        return self._sum_parts("surface_reflect", *a, **kw)
 
     def phase_redirect(self, *a, **kw):
-        return sum(self._each(lambda s: s.phase_redirect(*a, **kw)))
+        return self._sum_parts("phase_redirect", *a, **kw)
 
     def absorb_scattered(self, *a, **kw):
-        outs = self._each(lambda s: s.absorb_scattered(*a, **kw))
-        hists = [o[3] for o in outs]
-        return (sum(o[0] for o in outs), sum(o[1] for o in outs), self._sum([o[2] for o in outs]),
-                None if hists[0] is None else self._sum(hists))
+        return self._sum_parts("absorb_scattered", *a, **kw)
 
     def phase_layered(self, *a, **kw):
-        outs = self._each(lambda s: s.phase_layered(*a, **kw))
-        return (sum(o[0] for o in outs), sum(o[1] for o in outs), self._sum([o[2] for o in outs]), self._sum([o[3] for o in outs]))
+        return self._sum_parts("phase_layered", *a, **kw)
 
     def recycle_spent(self, *a, **kw):
-        outs = self._each(lambda s: s.recycle_spent(*a, **kw))   # (ids are global: every shard re-emits its own photons)
-        return sum(o[0] for o in outs), sum(o[1] for o in outs)
+        return self._sum_parts("recycle_spent", *a, **kw)
 
     def absorb_path(self, *a, **kw):
-        outs = self._each(lambda s: s.absorb_path(*a, **kw))     # (ids are global: every shard absorbs its own photons)
-        return sum(o[0] for o in outs), sum(o[1] for o in outs), self._sum([o[2] for o in outs])
+        return self._sum_parts("absorb_path", *a, **kw)
 
     def plane_energies(self, plane, n_hint=None):
         return self._concat(self._each(lambda s: s.plane_energies(plane)))      # (a shard does not know its share of the hint)

@@ -1,10 +1,12 @@
 """The host side of a tally measure step, once -- the counterpart of csrc/pcl_sweep.h: the bin-edge and centre checks, the
 state of host-resident Python objects as arrays, the one collective of a pass, and ``TallyStep``, the base class that turns
-"one sweep of the store -> one collective -> one object row" into three hooks.  The steps themselves, and the numpy
+"one sweep of the store -> one collective -> one object row" into three hooks -- and ``WriterStep``, the same for the steps
+whose sweep writes the store.  The steps themselves, and the numpy
 restatements of their sweeps that the host-plugin path answers with, are in light.py.  NumPy only."""
 import numpy as np
 
 from .core import DeviceStep, MeasureStep, _snap
+from .units import Measurement
 
 ALLREDUCE_CHUNK = 2048       # values one pcl_comm_allreduce_sum_i64 call takes (physicl_amd.comm.NativeCounterComm)
 
@@ -45,6 +47,12 @@ def check_center(center):
 
 
 # ---------------------------------------------------------------------------------------------- host-resident objects
+def host_resident(sim):
+    """Whether a step is called as a host plugin on host-resident Python objects: they hold the state."""
+    return getattr(sim, "_residency", None) == "host" and getattr(sim, "_batch", None) is None \
+        and (sim.comm is None or sim.comm.world == 1)
+
+
 def vec3(objs, attr):
     """``obj.<attr>`` of every object as an (n, 3) float64 array."""
     return np.array([np.asarray(getattr(o, attr), dtype=np.float64).reshape(3) for o in objs], dtype=np.float64).reshape(len(objs), 3)
@@ -123,8 +131,7 @@ class TallyStep(DeviceStep, MeasureStep):
             self._take(sim)
 
     def run(self, sim):
-        if getattr(sim, "_residency", None) == "host" and getattr(sim, "_batch", None) is None \
-                and (sim.comm is None or sim.comm.world == 1):
+        if host_resident(sim):
             # called as a host plugin on host-resident objects: they hold the state, so nothing is uploaded for a
             # measurement.  float64 on both sides (core.py allocates no other store), so the row does not depend on where
             # the objects reside
@@ -140,3 +147,69 @@ class TallyStep(DeviceStep, MeasureStep):
         with open(self.out_fn, "w") as f:              # an array cell is written as a list cell is: a (nested) plain list of integers
             for row in self.data:
                 f.write(", ".join(str(x.tolist() if isinstance(x, np.ndarray) else x) for x in list(row)) + "\n")
+
+
+class WriterStep(DeviceStep, MeasureStep):
+    """A step that WRITES the store in one sweep behind a pass, draws from Philox blocks keyed by a pass counter of its own
+    (``_pass``: one per run) and records the sweep's tallies.  "refuse -> prepare -> move ``_pass`` -> one sweep -> one collective
+    -> ``_record_pass``", on the device and -- with numpy, float64 -- on host-resident objects, is here once.  A subclass sets
+    ``_NOTE`` (what ``sim.launch_note`` says: the K-passes-per-launch kernels cannot carry the step) and ``_writes`` (which of
+    ``r``, ``dr``, ``v``, ``dv``, ``E`` the host path writes back), keeps its own ``__init__`` and ``_record_pass``, and supplies:
+
+    * ``_refuse(sim)`` and ``_prepare(sim, on_host)`` (both optional): raise what the step cannot run under, and work out what a
+      pass needs ahead of its sweep; both run before ``_pass`` moves, so a refused call leaves the step as it was;
+    * ``_sweep(sim, prep)``: the device sweep, its tallies as a list of int64 arrays (None: not asked for), the scalar counts
+      together in the first;
+    * ``_host_sweep(objs, ids, seed, prep)``: the numpy restatement on the Python objects -- ``(new, mask, record)``: the new
+      state by field name, who is written back, and ``_record_pass``'s arguments behind ``sim``.
+
+    ``_reduce(sim, parts)`` is the pass's ONE collective (every rank issues it, also with an empty shard)."""
+    _fuse_role = None
+    _NOTE = None
+    _writes = ("v", "dv")
+
+    def _refuse(self, sim):
+        pass
+
+    def _prepare(self, sim, on_host):
+        return None
+
+    def _sweep(self, sim, prep):
+        raise NotImplementedError
+
+    def _host_sweep(self, objs, ids, seed, prep):
+        raise NotImplementedError
+
+    def _reduce(self, sim, parts):
+        # one payload, cut where it is longer than one call of the library's own communicator carries
+        return reduce_parts(sim, parts)[1]
+
+    def _device_run(self, sim):
+        self._refuse(sim)
+        prep = self._prepare(sim, False)
+        if getattr(sim, "launch_note", self._NOTE) is None and sim._k_wanted() > 1:      # (a device run only: the host path says nothing)
+            sim.launch_note = self._NOTE
+        self._pass += 1
+        parts = self._sweep(sim, prep)
+        sim._scattered = True                            # velocities were replaced on the device
+        parts = self._reduce(sim, parts)
+        self._record_pass(sim, *parts[0], *parts[1:])
+
+    def run(self, sim):
+        self._refuse(sim)
+        if not host_resident(sim):
+            return DeviceStep.run(self, sim)
+        prep = self._prepare(sim, True)
+        objs = list(sim.objects)
+        self._pass += 1
+        new, mask, record = self._host_sweep(objs, np.arange(len(objs)), getattr(sim, "seed", 0), prep)
+        for k in np.flatnonzero(mask).tolist():
+            o = objs[k]
+            if "r" in self._writes:
+                o.r = Measurement._from_code(new["r"][k], like=o.r, units="m**1")
+                o.dr = Measurement._from_code(new["dr"][k], units="m**1")
+            o.v, o.dv = np.array(new["v"][k], dtype=np.double), np.array(new["dv"][k], dtype=np.double)   # plain arrays, as a scatter leaves them
+            if "E" in self._writes:
+                o.E = Measurement._from_code(new["E"][k], like=o.E, units="J**1") if isinstance(o.E, Measurement) else np.double(new["E"][k])
+        self._record_pass(sim, *record)
+        return None

@@ -4,12 +4,15 @@ tests/native/sweep_host.cpp includes the header as a plain C++ program, is built
 undefined-behaviour sanitizers and run as a child process (it is not loaded into Python).  Its answers are held against
 
 * the properties a sweep's geometry needs (every workgroup takes ``trips`` or ``trips - 1`` trips, fewer than 2^32 slots);
-* literal transcriptions, kept here, of what pcl_spectrum.hip / pcl_shell.hip / pcl_grid.hip did in place before the header.
+* literal transcriptions, kept here, of what pcl_spectrum.hip / pcl_shell.hip / pcl_grid.hip did in place before the header,
+  and of the offsets into a call's device block that every entry of pcl_surface.hip derived by hand before ``layout_of``;
+* numpy slicing, for the zero / copy / add of a call's output spans (an empty span is NULL there, as a caller may pass it).
 """
 import math
 import os
 import subprocess
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -152,6 +155,65 @@ def test_edge_check(ask):
         assert tok[0] == ("1" if want_ok else "0"), (e, t, line)
         if want_ok:                                                # bit for bit (a signed zero included)
             assert [float.fromhex(x).hex() for x in tok[1:]] == [float(x).hex() for x in want], (e, t, line)
+
+
+# ------------------------------------------------------------------------------------------------ the staged block
+def block_as_the_units_had_it(out_bytes, tab_bytes, n_ids, n_kind):
+    """Where a call's tables, ids and kind bytes start, and the size of its device block: ``base + out_bytes (+ tab_bytes (+
+    id_bytes))`` as every entry of pcl_surface.hip derived its pointers, and the sum stage() allocated, before layout_of."""
+    id_bytes = n_ids * 8
+    tables = out_bytes
+    ids = out_bytes + tab_bytes
+    kind = out_bytes + tab_bytes + id_bytes
+    return tables, ids, kind, out_bytes + tab_bytes + id_bytes + n_kind
+
+
+LAYOUT_CASES = [
+    (16, 0, 0, 0),                                                 # no tables, no ids, no kinds
+    (16, 40, 0, 0), (8 * 26, 8 * 13, 0, 0),                        # tables only
+    (16, 0, 1000, 0), (16, 24, 1000, 0),                           # ids without kinds
+    (16, 0, 0, 1000), (16, 24, 0, 1001),                           # kinds without ids
+    (8 * 30, 8 * 21, 4097, 4097), (16, 8 * 2048, 10 ** 8, 10 ** 8),   # everything present
+    (8, 0, 0, 0), (8, 0, 3, 3), (8, 8, 3, 0), (8, 8, 0, 3), (8, 16, 5, 5),   # an out_bytes of one cell
+]
+
+
+def test_block_layout(ask):
+    got = ask(["layout %d %d %d %d" % c for c in LAYOUT_CASES])
+    for c, line in zip(LAYOUT_CASES, got):
+        assert tuple(int(x) for x in line.split()) == block_as_the_units_had_it(*c), c
+
+
+# ------------------------------------------------------------------------------------------------ the output spans
+SPAN_CASES = [
+    ("absorption, L=0, n_E=0: E_hist NULL", [2 + 1, 0]),
+    ("absorption, L=3, n_E=8", [2 + 3, 3 * 8]),
+    ("path absorption, 1 x 1 cells", [2, 1]),
+    ("path absorption, 2 x 3 cells", [2, 6]),
+    ("shell, 2 shells, no energy bins (NULL), 5 mu bins", [4, 0, 20]),
+]
+
+
+def test_output_spans(ask):
+    rs = np.random.RandomState(11)
+    asked, want = [], []
+    for _, lens in SPAN_CASES:
+        cells = sum(lens)
+        before = np.concatenate([1000 * (i + 1) + np.arange(n, dtype=np.int64) for i, n in enumerate(lens)])
+        flat = rs.randint(-2 ** 40, 2 ** 40, cells).astype(np.int64)
+        head = "%d %s" % (len(lens), " ".join(str(n) for n in lens))
+        vals = " ".join(str(int(x)) for x in flat)
+        for op in ("zero", "copy", "add"):
+            asked.append("spans %s %s%s" % (op, head, "" if op == "zero" else " " + vals))
+            after, at = [], 0
+            for n in lens:                                         # span by span, with numpy slicing
+                was, new = before[at:at + n], flat[at:at + n]
+                after.append(np.zeros(n, dtype=np.int64) if op == "zero" else new.copy() if op == "copy" else was + new)
+                at += n
+            want.append([cells] + np.concatenate(after).tolist())
+    got = ask(asked)                                               # (exit status 0 under the sanitizers: the NULL spans were not touched)
+    for line, line_want, q in zip(got, want, asked):
+        assert [int(x) for x in line.split()] == line_want, q
 
 
 # ------------------------------------------------------------------------------------------------ the core
