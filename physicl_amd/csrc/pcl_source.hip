@@ -18,10 +18,12 @@
 #include "pcl_sweep.h"
 
 #include "pcl_device.h" // (after the HIP runtime and the ABI's header, which pcl_sweep.h brings)
+#include "pcl_rules.h"  // (after both)
 
 namespace {
 
 using namespace pcl_sweep;
+using namespace pcl_rules;
 
 template <typename T>
 struct source_args {
@@ -49,22 +51,16 @@ __global__ void __launch_bounds__(kBlock) k_apply_source(source_args<T> a) {
             } else {
                 const pcl_u32x4 w = pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), 0xFFFFFFFFu, 4u, k0, k1);
                 const double u_a = pcl_u53(w.x, w.y), u_b = pcl_u53(w.z, w.w);
-                double mu; // cosine of the polar angle about d
+                double mu;      // source_mu, in place in both emitters (a helper changes the kernels): the cosine of the polar angle about d
                 if (a.angular == PCL_SRC_ISOTROPIC)
                     mu = __dsub_rn(1.0, __dmul_rn(2.0, u_a));                                         // uniform on the sphere
                 else if (a.angular == PCL_SRC_CONE)
                     mu = __dsub_rn(1.0, __dmul_rn(u_a, __dsub_rn(1.0, a.cos_half_angle)));            // uniform in solid angle
                 else
                     mu = __dsqrt_rn(__dsub_rn(1.0, u_a));                                             // cosine-weighted hemisphere
-                const double s = __dsqrt_rn(__dmul_rn(__dsub_rn(1.0, mu), __dadd_rn(1.0, mu)));
-                double sn, cs;
-                pcl_sincos_2pi(__dmul_rn(__dmul_rn(u_b, 2.0), PCL_PI), &sn, &cs);                     // the scatter step's angle
-                const double sc = __dmul_rn(s, cs), ss = __dmul_rn(s, sn);
+                double sc, ss; polar(mu, u_b, &sc, &ss);
 #pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    const double dir = __dadd_rn(__dadd_rn(__dmul_rn(sc, a.e1[k]), __dmul_rn(ss, a.e2[k])), __dmul_rn(mu, a.d[k]));
-                    a.v[k][ti] = (T)__dmul_rn(a.c, dir);
-                }
+                for (int k = 0; k < 3; ++k) a.v[k][ti] = (T)__dmul_rn(a.c, turned(sc, ss, mu, a.e1[k], a.e2[k], a.d[k]));
             }
         }
         if (write_r) {
@@ -74,14 +70,12 @@ __global__ void __launch_bounds__(kBlock) k_apply_source(source_args<T> a) {
             } else {
                 const pcl_u32x4 w = pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), 0xFFFFFFFFu, 5u, k0, k1);
                 const double u_c = pcl_u53(w.x, w.y), u_d = pcl_u53(w.z, w.w);
-                double rho;
+                double rho;     // source_rho, in place in both emitters (a helper changes the kernels): the distance from the origin
                 if (a.spatial == PCL_SRC_DISC)
                     rho = __dmul_rn(a.radius, __dsqrt_rn(u_c));                                       // uniform over the disc
                 else                                                                                  // 1 - u_c is in (0, 1]
                     rho = __dmul_rn(a.radius, __dsqrt_rn(__dmul_rn(-2.0, log(__dsub_rn(1.0, u_c)))));
-                double sn, cs;
-                pcl_sincos_2pi(__dmul_rn(__dmul_rn(u_d, 2.0), PCL_PI), &sn, &cs);
-                const double rc = __dmul_rn(rho, cs), rs = __dmul_rn(rho, sn);
+                double rc, rs; azimuth(rho, u_d, &rc, &rs);
 #pragma unroll
                 for (int k = 0; k < 3; ++k)
                     a.r[k][ti] = (T)__dadd_rn(a.origin[k], __dadd_rn(__dmul_rn(rc, a.e1[k]), __dmul_rn(rs, a.e2[k])));

@@ -10,6 +10,11 @@
 // and the source hash the counter records are tied to (physicl_amd/build.py: csrc_sha) are not touched by anything here.  The
 // scaffold it shares with the other units of its kind is pcl_sweep.h.
 //
+// The rules the six sweeps share are stated once in pcl_rules.h (pcl_source.hip includes it, too), where a helper leaves every
+// kernel the same machine code (tools/compare_unit_asm.py).  These change a kernel and stay written out, each under a comment that
+// names the rule: scattered / workable (dv != 0, 0 < o.o < inf), at_rest, dist2 and closed_bin (the radial layer, the bin of E),
+// law_mu, source_mu and source_rho, park.  physicl_amd/light.py states every rule once for the numpy restatements, by these names.
+//
 //   k_surface_reflect<T>   one grid-stride sweep of the tiled slab: per slot r and dr of the three axes (48 B in fp64), widened
 //                          to double; the shell sweep's q_now and q_prev against R*R decide who is hit; one ballot + popcount
 //                          per wave for the two counters (LDS cells, flushed with 64-bit atomics).  Only lanes that are hit go
@@ -23,17 +28,14 @@
 //   x_k = p_k + t*m_k;  nrm_k = x_k / sqrt(x.x);  sa = sqrt(a);  w = (1 - t)*sa
 //   absorbed (u_0 >= albedo):  r_k = center_k + x_k;  v_k = 0;  dr_k = x_k - p_k;  dv_k = 0 - v_old_k
 //   specular:    mh_k = m_k / sa;  dn = mh.nrm;  dir_k = mh_k - (2*dn)*nrm_k
-//   lambertian:  mu = sqrt(1 - u_a);  s = sqrt((1 - mu)*(1 + mu));  psi = (u_b*2)*pi;  sc = s*cos psi;  ss = s*sin psi
-//                sg = copysign(1, n2);  aa = -1/(sg + n2);  bb = (n0*n1)*aa;  sn0 = sg*n0
-//                e1 = (1 + (sn0*n0)*aa, sg*bb, -sn0);  e2 = (bb, sg + (n1*n1)*aa, -n1)        (Duff et al. 2017, branch-free)
-//                dir_k = (sc*e1_k + ss*e2_k) + mu*nrm_k
+//   lambertian:  mu = sqrt(1 - u_a);  s = sqrt((1 - mu)*(1 + mu));  psi = (u_b*2)*pi;  sc = s*cos psi;  ss = s*sin psi   (polar)
+//                e1, e2 = the frame about nrm (frame);  dir_k = (sc*e1_k + ss*e2_k) + mu*nrm_k                         (turned)
 //   reflected:   v_k = c*dir_k;  dv_k = v_k - v_old_k;  dr_k = w*dir_k;  r_k = center_k + (x_k + dr_k)
 //
 // A phase function (PhaseFunctionStep): the photons the scatter step of this pass has hit (dv != 0) get a direction drawn about
 // the direction they had BEFORE the scatter -- uniform on the sphere, Henyey-Greenstein or Rayleigh.  It joined this unit rather
 // than a new one: the unit already includes pcl_device.h for the draws and holds the frame that turns (mu, psi) about an axis into
-// a direction ("Adding a unit on the public ABI").  The frame is written out a second time below; k_surface_reflect
-// is the code it was.
+// a direction ("Adding a unit on the public ABI").
 //
 //   k_phase_redirect<T>    one grid-stride sweep: per slot the three dv rows (24 B in fp64), widened to double; lanes with a
 //                          non-zero dv load v, and those whose old velocity o = v - dv has a length that can be worked with are
@@ -43,15 +45,10 @@
 // Operation order (what light._phase_redirect restates with numpy):
 //   scattered iff a photon and (dv0 != 0 or dv1 != 0 or dv2 != 0);  o_k = v_k - dv_k;  oo = o.o;  go on iff 0 < oo < inf
 //   on = sqrt(oo);  w_k = o_k / on;  block A = counter (id_lo, id_hi, pass, 10): u_a, u_b
-//   isotropic:  mu = 1 - 2*u_a
-//   hg:         g == 0: the isotropic line;  q = (1 - g*g) / ((1 - g) + (2*g)*u_a);  mu = min(max(((1 + g*g) - q*q) / (2*g), -1), 1)
-//               (for tiny |g| the difference (1 + g*g) - q*q is of the order g: mu is good to about ulp(1)/|g| -- harmless, the law
-//               is flat to first order in g there)
-//   rayleigh:   3/8 (1 + mu^2) = 3/4 uniform + 1/4 (3/2 mu^2):  s4 = u_a*4;  j = floor(s4);  f = s4 - j (both exact);  gq = 2*f - 1
-//               j < 3: mu = gq;  j == 3: block B = counter (id_lo, id_hi, pass, 11): u_c, u_d;
-//               mu = copysign(max(max(|gq|, u_c), u_d), gq)      (the largest of three uniforms has density 3 x^2)
-//   s = sqrt((1 - mu)*(1 + mu));  psi = (u_b*2)*pi;  sc = s*cos psi;  ss = s*sin psi;  the frame e1, e2 about w as above about nrm
-//   dir_k = (sc*e1_k + ss*e2_k) + mu*w_k;  v_k = c*dir_k;  dv_k = v_k - o_k
+//   mu by the law (law_mu; include/physicl_hip.h writes the lines out): isotropic 1 - 2*u_a;  hg by the closed inverse, g == 0 the
+//   isotropic line (for tiny |g| mu is good to about ulp(1)/|g| -- harmless, the law is flat to first order in g there);  rayleigh
+//   3/4 uniform + 1/4 (3/2 mu^2): one lane in four takes the largest of three uniforms, block B = counter (id_lo, id_hi, pass, 11)
+//   sc, ss = polar(mu, u_b);  e1, e2 = frame(w);  dir_k = (sc*e1_k + ss*e2_k) + mu*w_k;  v_k = c*dir_k;  dv_k = v_k - o_k
 //
 // An absorbing medium (AbsorptionStep): of the photons the scatter step of this pass has hit (dv != 0), those whose draw falls
 // above the single-scattering albedo omega0 of the layer they stand in are absorbed: left in the store at rest where they are.
@@ -92,11 +89,11 @@
 //
 //   k_recycle_spent<T>     one grid-stride sweep: per slot the three v rows (only with at_rest; a lane whose v0 is not zero is
 //                          decided and loads no more of them) and, for lanes that are not at rest, the three r rows (only with a
-//                          top); two ballots + popcounts per wave for the two counters.  Only
-//                          spent lanes go on: they load their id, draw the source's direction and position -- the lines of
-//                          k_apply_source (pcl_source.hip) repeated, with counter words of their own -- and write r, v, dr = 0 and
-//                          dv = 0; with a spectrum they look a third draw up in the cumulative table (dynamic LDS, at most 16 KiB, in
-//                          front of the two cells) and write E.
+//                          top); two ballots + popcounts per wave for the two counters.  Only spent lanes go on: they load their
+//                          id, draw the source's direction and position -- k_apply_source's emission (pcl_source.hip) with counter
+//                          words of their own: the helpers are shared, source_mu and source_rho written out in both -- and write
+//                          r, v, dr = 0 and dv = 0; with a spectrum they look a third draw up in the cumulative table (dynamic
+//                          LDS, at most 16 KiB, in front of the two cells) and write E.
 //
 // Operation order (what light._recycle_spent restates with numpy):
 //   rest = at_rest and v0 == 0 and v1 == 0 and v2 == 0;  d = r - center;  q = d.d;  gone = a top, not rest and q > top*top
@@ -122,10 +119,12 @@
 #include "pcl_sweep.h"
 
 #include "pcl_device.h" // (after the HIP runtime and the ABI's header, which pcl_sweep.h brings)
+#include "pcl_rules.h"  // (after both)
 
 namespace {
 
 using namespace pcl_sweep;
+using namespace pcl_rules;
 
 template <typename T>
 struct surface_args {
@@ -140,20 +139,14 @@ struct surface_args {
     uint32_t k0, k1, pass;       // Philox key (seed_lo, seed_hi), the step's own pass counter
 };
 
-__device__ __forceinline__ double dot3(const double *x, const double *y) {
-    return __dadd_rn(__dadd_rn(__dmul_rn(x[0], y[0]), __dmul_rn(x[1], y[1])), __dmul_rn(x[2], y[2]));
-}
-
 template <typename T>
 __global__ void __launch_bounds__(kBlock) k_surface_reflect(surface_args<T> a) {
     __shared__ uint32_t s_cnt[2];                                       // reflected, absorbed
     if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0;
     __syncthreads();
     const int lane = threadIdx.x & 63;
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    // whole waves run the same number of trips (the ballots below need every lane of the wave inside the loop)
-    const int64_t n_round = (a.N + 63) / 64 * 64;
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n_round; i += stride) {
+    const int64_t stride = grid_stride(), n_round = whole_waves(a.N);   // (the ballots below need whole waves inside the loop)
+    for (int64_t i = first_slot(); i < n_round; i += stride) {
         const bool in = i < a.N;
         const int64_t ti = tile_index(i, a.tile_log, a.ts);
         double d[3] = {0.0, 0.0, 0.0}, m[3] = {0.0, 0.0, 0.0}, p[3];
@@ -172,11 +165,8 @@ __global__ void __launch_bounds__(kBlock) k_surface_reflect(surface_args<T> a) {
         uint64_t id = 0;
         bool refl = hit;
         if (hit) {
-            id = (uint64_t)(a.ids ? a.ids[i] : a.id_base + i);
-            if (a.albedo < 1.0) {
-                const pcl_u32x4 w0 = pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, 9u, a.k0, a.k1);
-                refl = pcl_u53(w0.x, w0.y) < a.albedo;
-            }
+            id = id_of(a.ids, a.id_base, i);
+            if (a.albedo < 1.0) refl = first_u53(pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, 9u, a.k0, a.k1)) < a.albedo;
         }
         const uint32_t n_hit = (uint32_t)__popcll(__ballot(hit)), n_refl = (uint32_t)__popcll(__ballot(refl));
         if (lane == 0 && n_refl) atomicAdd(&s_cnt[0], n_refl);
@@ -212,21 +202,13 @@ __global__ void __launch_bounds__(kBlock) k_surface_reflect(surface_args<T> a) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) dir[k] = __dsub_rn(mh[k], __dmul_rn(dn2, nrm[k]));
         } else {
-            const pcl_u32x4 w = pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, 8u, a.k0, a.k1);
-            const double u_a = pcl_u53(w.x, w.y), u_b = pcl_u53(w.z, w.w);
+            double u_a, u_b, sc, ss, e1[3], e2[3];
+            pair_u53(pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, 8u, a.k0, a.k1), &u_a, &u_b);
             const double mu = __dsqrt_rn(__dsub_rn(1.0, u_a));                                       // cosine-weighted hemisphere
-            const double s = __dsqrt_rn(__dmul_rn(__dsub_rn(1.0, mu), __dadd_rn(1.0, mu)));
-            double sn, cs;
-            pcl_sincos_2pi(__dmul_rn(__dmul_rn(u_b, 2.0), PCL_PI), &sn, &cs);                        // the scatter step's angle
-            const double sc = __dmul_rn(s, cs), ss = __dmul_rn(s, sn);
-            const double sg = copysign(1.0, nrm[2]);
-            const double aa = __ddiv_rn(-1.0, __dadd_rn(sg, nrm[2]));
-            const double bb = __dmul_rn(__dmul_rn(nrm[0], nrm[1]), aa), sn0 = __dmul_rn(sg, nrm[0]);
-            const double e1[3] = {__dadd_rn(1.0, __dmul_rn(__dmul_rn(sn0, nrm[0]), aa)), __dmul_rn(sg, bb), -sn0};
-            const double e2[3] = {bb, __dadd_rn(sg, __dmul_rn(__dmul_rn(nrm[1], nrm[1]), aa)), -nrm[1]};
+            polar(mu, u_b, &sc, &ss);
+            frame(nrm, e1, e2);
 #pragma unroll
-            for (int k = 0; k < 3; ++k)
-                dir[k] = __dadd_rn(__dadd_rn(__dmul_rn(sc, e1[k]), __dmul_rn(ss, e2[k])), __dmul_rn(mu, nrm[k]));
+            for (int k = 0; k < 3; ++k) dir[k] = turned(sc, ss, mu, e1[k], e2[k], nrm[k]);
         }
         const double w = __dmul_rn(__dsub_rn(1.0, t), sa);              // the rest of the move, flown along the new direction
 #pragma unroll
@@ -261,17 +243,15 @@ __global__ void __launch_bounds__(kBlock) k_phase_redirect(phase_args<T> a) {
     if (threadIdx.x == 0) s_cnt[0] = 0;
     __syncthreads();
     const int lane = threadIdx.x & 63;
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    // whole waves run the same number of trips (the ballot below needs every lane of the wave inside the loop)
-    const int64_t n_round = (a.N + 63) / 64 * 64;
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n_round; i += stride) {
+    const int64_t stride = grid_stride(), n_round = whole_waves(a.N);   // (the ballots below need whole waves inside the loop)
+    for (int64_t i = first_slot(); i < n_round; i += stride) {
         const bool in = i < a.N;
         const int64_t ti = tile_index(i, a.tile_log, a.ts);
         double d[3] = {0.0, 0.0, 0.0}, o[3] = {0.0, 0.0, 0.0};
 #pragma unroll
         for (int k = 0; k < 3; ++k)
             if (in) d[k] = (double)a.dv[k][ti];                         // fp32 widens exactly
-        // scattered in this pass: the scatter step left dv = v' - v_old on a hit, 0 on a miss (NaN != 0 is true)
+        // scattered, written out (a helper changes the kernel): the scatter step left dv = v' - v_old on a hit, 0 on a miss (NaN != 0)
         bool go = in && (d[0] != 0.0 || d[1] != 0.0 || d[2] != 0.0);
         if (go && a.kind) go = a.kind[i] != 0;
         if (go) {
@@ -283,13 +263,13 @@ __global__ void __launch_bounds__(kBlock) k_phase_redirect(phase_args<T> a) {
         const uint32_t n_go = (uint32_t)__popcll(__ballot(go));
         if (lane == 0 && n_go) atomicAdd(&s_cnt[0], n_go);
         if (!go) continue;      // lanes that are left alone wait at the loop's head: no ballot below this line
-        const uint64_t id = (uint64_t)(a.ids ? a.ids[i] : a.id_base + i);
+        const uint64_t id = id_of(a.ids, a.id_base, i);
         const double on = __dsqrt_rn(oo);
-        double w[3], dir[3];
+        double w[3], sc, ss, e1[3], e2[3];
 #pragma unroll
         for (int k = 0; k < 3; ++k) w[k] = __ddiv_rn(o[k], on);
-        const pcl_u32x4 wa = pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, 10u, a.k0, a.k1);
-        const double u_a = pcl_u53(wa.x, wa.y), u_b = pcl_u53(wa.z, wa.w);
+        double u_a, u_b;
+        pair_u53(pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, 10u, a.k0, a.k1), &u_a, &u_b);
         double mu = __dsub_rn(1.0, __dmul_rn(2.0, u_a));                                             // uniform on the sphere
         if (a.phase == PCL_PHASE_HG && a.g != 0.0) {
             const double gg = __dmul_rn(a.g, a.g), g2 = __dmul_rn(2.0, a.g);
@@ -300,23 +280,15 @@ __global__ void __launch_bounds__(kBlock) k_phase_redirect(phase_args<T> a) {
             const double gq = __dsub_rn(__dmul_rn(2.0, __dsub_rn(s4, j)), 1.0);
             mu = gq;
             if (j == 3.0) {                                             // one lane in four: the 3/2 mu^2 part
-                const pcl_u32x4 wb = pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, 11u, a.k0, a.k1);
+                const pcl_u32x4 wb = pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, 11u, a.k0, a.k1);   // (pair_u53 changes the kernel)
                 mu = copysign(fmax(fmax(fabs(gq), pcl_u53(wb.x, wb.y)), pcl_u53(wb.z, wb.w)), gq);
             }
         }
-        const double s = __dsqrt_rn(__dmul_rn(__dsub_rn(1.0, mu), __dadd_rn(1.0, mu)));
-        double sn, cs;
-        pcl_sincos_2pi(__dmul_rn(__dmul_rn(u_b, 2.0), PCL_PI), &sn, &cs);                            // the scatter step's angle
-        const double sc = __dmul_rn(s, cs), ss = __dmul_rn(s, sn);
-        const double sg = copysign(1.0, w[2]);                                                       // the frame of k_surface_reflect
-        const double aa = __ddiv_rn(-1.0, __dadd_rn(sg, w[2]));
-        const double bb = __dmul_rn(__dmul_rn(w[0], w[1]), aa), sw0 = __dmul_rn(sg, w[0]);
-        const double e1[3] = {__dadd_rn(1.0, __dmul_rn(__dmul_rn(sw0, w[0]), aa)), __dmul_rn(sg, bb), -sw0};
-        const double e2[3] = {bb, __dadd_rn(sg, __dmul_rn(__dmul_rn(w[1], w[1]), aa)), -w[1]};
+        polar(mu, u_b, &sc, &ss);
+        frame(w, e1, e2);
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            dir[k] = __dadd_rn(__dadd_rn(__dmul_rn(sc, e1[k]), __dmul_rn(ss, e2[k])), __dmul_rn(mu, w[k]));
-            const double vk = __dmul_rn(a.speed, dir[k]);
+            const double vk = __dmul_rn(a.speed, turned(sc, ss, mu, e1[k], e2[k], w[k]));
             a.v[k][ti] = (T)vk;
             a.dv[k][ti] = (T)__dsub_rn(vk, o[k]);
         }
@@ -357,34 +329,31 @@ __global__ void __launch_bounds__(kBlock) k_absorb_scattered(absorb_args<T> a) {
     for (int k = threadIdx.x; k < n_cells; k += kBlock) s_cnt[k] = 0;  // (the layers and the histograms follow the two counts)
     __syncthreads();
     const int lane = threadIdx.x & 63;
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    // whole waves run the same number of trips (the ballots below need every lane of the wave inside the loop)
-    const int64_t n_round = (a.N + 63) / 64 * 64;
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n_round; i += stride) {
+    const int64_t stride = grid_stride(), n_round = whole_waves(a.N);   // (the ballots below need whole waves inside the loop)
+    for (int64_t i = first_slot(); i < n_round; i += stride) {
         const bool in = i < a.N;
         const int64_t ti = tile_index(i, a.tile_log, a.ts);
         double d[3] = {0.0, 0.0, 0.0};
 #pragma unroll
         for (int k = 0; k < 3; ++k)
             if (in) d[k] = (double)a.dv[k][ti];                         // fp32 widens exactly
-        // interacted in this pass: the rule of k_phase_redirect (NaN != 0 is true)
+        // interacted in this pass: scattered, written out (a helper changes the kernel; NaN != 0 is true)
         bool go = in && (d[0] != 0.0 || d[1] != 0.0 || d[2] != 0.0);
         if (go && a.kind) go = a.kind[i] != 0;
         int b = go && L == 0 ? 0 : -1;                                  // the layer; -1: outside every layer, never absorbed
         if (go && L > 0) {
             double x[3];
 #pragma unroll
-            for (int k = 0; k < 3; ++k) x[k] = __dsub_rn((double)a.r[k][ti], a.c[k]);
+            for (int k = 0; k < 3; ++k) x[k] = __dsub_rn((double)a.r[k][ti], a.c[k]);   // fp32 widens exactly
             const double q = dot3(x, x);
-            if (q >= s_e2[0] && q <= s_e2[L]) b = bin_of(s_e2, L, q);   // NaN: in no layer
+            if (q >= s_e2[0] && q <= s_e2[L]) b = bin_of(s_e2, L, q);   // (dist2, closed_bin: written out) NaN: in no layer
         }
         bool gone = false;
         if (b >= 0) {
             const double om = s_om[b];
             if (om < 1.0) {                                             // a conservative layer draws nothing
-                const uint64_t id = (uint64_t)(a.ids ? a.ids[i] : a.id_base + i);
-                const pcl_u32x4 w = pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, 12u, a.k0, a.k1);
-                gone = !(pcl_u53(w.x, w.y) < om);                       // the sense of the ground's albedo draw
+                const uint64_t id = id_of(a.ids, a.id_base, i);
+                gone = !(first_u53(pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, 12u, a.k0, a.k1)) < om);      // the sense of the ground's albedo draw
             }
         }
         const uint32_t n_go = (uint32_t)__popcll(__ballot(go)), n_gone = (uint32_t)__popcll(__ballot(gone));
@@ -392,7 +361,7 @@ __global__ void __launch_bounds__(kBlock) k_absorb_scattered(absorb_args<T> a) {
         if (lane == 0 && n_gone) atomicAdd(&s_cnt[1], n_gone);
         if (!gone) continue;    // lanes that are left alone wait at the loop's head: no ballot below this line
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {                                   // parked where it is, at rest; "did not scatter"
+        for (int k = 0; k < 3; ++k) {                                   // park, written out: at rest where it is; "did not scatter"
             a.v[k][ti] = (T)0.0;
             a.dv[k][ti] = (T)0.0;
         }
@@ -452,17 +421,15 @@ __global__ void __launch_bounds__(kBlock) k_phase_layered(lphase_args<T> a) {
     for (int k = threadIdx.x; k < n_cells; k += kBlock) s_cnt[k] = 0;
     __syncthreads();
     const int lane = threadIdx.x & 63;
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    // whole waves run the same number of trips (the ballots below need every lane of the wave inside the loop)
-    const int64_t n_round = (a.N + 63) / 64 * 64;
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n_round; i += stride) {
+    const int64_t stride = grid_stride(), n_round = whole_waves(a.N);   // (the ballots below need whole waves inside the loop)
+    for (int64_t i = first_slot(); i < n_round; i += stride) {
         const bool in = i < a.N;
         const int64_t ti = tile_index(i, a.tile_log, a.ts);
         double d[3] = {0.0, 0.0, 0.0}, o[3] = {0.0, 0.0, 0.0};
 #pragma unroll
         for (int k = 0; k < 3; ++k)
             if (in) d[k] = (double)a.dv[k][ti];                         // fp32 widens exactly
-        // scattered in this pass: the rule of k_phase_redirect, the old velocity's length included
+        // scattered in this pass: scattered and workable, written out (a helper changes the kernel)
         bool go = in && (d[0] != 0.0 || d[1] != 0.0 || d[2] != 0.0);
         if (go && a.kind) go = a.kind[i] != 0;
         if (go) {
@@ -475,9 +442,9 @@ __global__ void __launch_bounds__(kBlock) k_phase_layered(lphase_args<T> a) {
         if (go && L > 0) {
             double x[3];
 #pragma unroll
-            for (int k = 0; k < 3; ++k) x[k] = __dsub_rn((double)a.r[k][ti], a.c[k]);
+            for (int k = 0; k < 3; ++k) x[k] = __dsub_rn((double)a.r[k][ti], a.c[k]);   // fp32 widens exactly
             const double q = dot3(x, x);
-            if (q >= s_e2[0] && q <= s_e2[L]) b = bin_of(s_e2, L, q);   // NaN: in no layer
+            if (q >= s_e2[0] && q <= s_e2[L]) b = bin_of(s_e2, L, q);   // (dist2, closed_bin: written out) NaN: in no layer
         }
         const bool turn = b >= 0;
         const uint32_t n_go = (uint32_t)__popcll(__ballot(go)), n_turn = (uint32_t)__popcll(__ballot(turn));
@@ -488,29 +455,28 @@ __global__ void __launch_bounds__(kBlock) k_phase_layered(lphase_args<T> a) {
             if (M == 1) atomicAdd(&s_law[0], n_turn);
         }
         if (!turn) continue;    // lanes that are left alone wait at the loop's head: no ballot below this line
-        const uint64_t id = (uint64_t)(a.ids ? a.ids[i] : a.id_base + i);
+        const uint64_t id = id_of(a.ids, a.id_base, i);
         int j = 0;
         if (M > 1) {
             const double *row = s_C + b * M;                            // cumulative, ends in 1: the first j with u_s < row[j]
             while (j < M - 1 && !(row[j] > 0.0)) ++j;                   // (u_s >= 0: a law without weight is never the first)
             if (row[j] < 1.0) {                                         // a one-hot row draws nothing
-                const pcl_u32x4 ws = pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, kLawWord, a.k0, a.k1);
-                const double u_s = pcl_u53(ws.x, ws.y);
+                const double u_s = first_u53(pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, kLawWord, a.k0, a.k1));
                 while (j < M - 1 && !(u_s < row[j])) ++j;
             }
             atomicAdd(&s_law[j], 1u);
         }
         if (Lp > 1) atomicAdd(&s_lay[b], 1u);
         const double on = __dsqrt_rn(oo);
-        double w[3], dir[3];
+        double w[3], sc, ss, e1[3], e2[3];
 #pragma unroll
         for (int k = 0; k < 3; ++k) w[k] = __ddiv_rn(o[k], on);
-        const pcl_u32x4 wa = pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, 10u, a.k0, a.k1);
-        const double u_a = pcl_u53(wa.x, wa.y), u_b = pcl_u53(wa.z, wa.w);
+        double u_a, u_b;
+        pair_u53(pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, 10u, a.k0, a.k1), &u_a, &u_b);
         const int law = s_kind[j];
         const double g = s_g[j];
         double mu = __dsub_rn(1.0, __dmul_rn(2.0, u_a));                                             // uniform on the sphere
-        if (law == PCL_PHASE_HG && g != 0.0) {                                                       // the lines of k_phase_redirect
+        if (law == PCL_PHASE_HG && g != 0.0) {                                 // law_mu, written out in both phase kernels
             const double gg = __dmul_rn(g, g), g2 = __dmul_rn(2.0, g);
             const double q = __ddiv_rn(__dsub_rn(1.0, gg), __dadd_rn(__dsub_rn(1.0, g), __dmul_rn(g2, u_a)));
             mu = fmin(fmax(__ddiv_rn(__dsub_rn(__dadd_rn(1.0, gg), __dmul_rn(q, q)), g2), -1.0), 1.0);
@@ -519,7 +485,7 @@ __global__ void __launch_bounds__(kBlock) k_phase_layered(lphase_args<T> a) {
             const double gq = __dsub_rn(__dmul_rn(2.0, __dsub_rn(s4, jq)), 1.0);
             mu = gq;
             if (jq == 3.0) {                                            // one lane in four: the 3/2 mu^2 part
-                const pcl_u32x4 wb = pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, 11u, a.k0, a.k1);
+                const pcl_u32x4 wb = pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, 11u, a.k0, a.k1);   // (pair_u53 changes the kernel)
                 mu = copysign(fmax(fmax(fabs(gq), pcl_u53(wb.x, wb.y)), pcl_u53(wb.z, wb.w)), gq);
             }
         } else if (law == PCL_PHASE_TABLE) {                            // the inverse of a piecewise linear F: 0 <= u_a < 1 is inside
@@ -528,19 +494,11 @@ __global__ void __launch_bounds__(kBlock) k_phase_layered(lphase_args<T> a) {
             const double lo = s_mu[kb], hi = s_mu[kb + 1];
             mu = fmin(fmax(__dadd_rn(lo, __dmul_rn(__dsub_rn(u_a, s_F[kb]), s_s[kb])), lo), hi);
         }
-        const double s = __dsqrt_rn(__dmul_rn(__dsub_rn(1.0, mu), __dadd_rn(1.0, mu)));
-        double sn, cs;
-        pcl_sincos_2pi(__dmul_rn(__dmul_rn(u_b, 2.0), PCL_PI), &sn, &cs);                            // the scatter step's angle
-        const double sc = __dmul_rn(s, cs), ss = __dmul_rn(s, sn);
-        const double sg = copysign(1.0, w[2]);                                                       // the frame of k_surface_reflect
-        const double aa = __ddiv_rn(-1.0, __dadd_rn(sg, w[2]));
-        const double bb = __dmul_rn(__dmul_rn(w[0], w[1]), aa), sw0 = __dmul_rn(sg, w[0]);
-        const double e1[3] = {__dadd_rn(1.0, __dmul_rn(__dmul_rn(sw0, w[0]), aa)), __dmul_rn(sg, bb), -sw0};
-        const double e2[3] = {bb, __dadd_rn(sg, __dmul_rn(__dmul_rn(w[1], w[1]), aa)), -w[1]};
+        polar(mu, u_b, &sc, &ss);
+        frame(w, e1, e2);
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            dir[k] = __dadd_rn(__dadd_rn(__dmul_rn(sc, e1[k]), __dmul_rn(ss, e2[k])), __dmul_rn(mu, w[k]));
-            const double vk = __dmul_rn(a.speed, dir[k]);
+            const double vk = __dmul_rn(a.speed, turned(sc, ss, mu, e1[k], e2[k], w[k]));
             a.v[k][ti] = (T)vk;
             a.dv[k][ti] = (T)__dsub_rn(vk, o[k]);
         }
@@ -583,10 +541,8 @@ __global__ void __launch_bounds__(kBlock) k_recycle_spent(recycle_args<T> a) {
     if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0;
     __syncthreads();
     const int lane = threadIdx.x & 63;
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    // whole waves run the same number of trips (the ballots below need every lane of the wave inside the loop)
-    const int64_t n_round = (a.N + 63) / 64 * 64;
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n_round; i += stride) {
+    const int64_t stride = grid_stride(), n_round = whole_waves(a.N);   // (the ballots below need whole waves inside the loop)
+    for (int64_t i = first_slot(); i < n_round; i += stride) {
         const bool in = i < a.N;
         const int64_t ti = tile_index(i, a.tile_log, a.ts);
         bool rest = false, gone = false;
@@ -603,46 +559,37 @@ __global__ void __launch_bounds__(kBlock) k_recycle_spent(recycle_args<T> a) {
         if (lane == 0 && n_rest) atomicAdd(&s_cnt[0], n_rest);
         if (lane == 0 && n_gone) atomicAdd(&s_cnt[1], n_gone);
         if (!(rest || gone)) continue;   // lanes that are left alone wait at the loop's head: no ballot below this line
-        const uint64_t id = (uint64_t)(a.ids ? a.ids[i] : a.id_base + i);
-        // the lines of k_apply_source (pcl_source.hip), repeated: only the counters differ, and every row is written
+        const uint64_t id = id_of(a.ids, a.id_base, i);
         double vel[3], pos[3];
         if (a.angular == PCL_SRC_BEAM) {                                // a constant: no draw
 #pragma unroll
             for (int k = 0; k < 3; ++k) vel[k] = __dmul_rn(a.speed, a.d[k]);
         } else {
-            const pcl_u32x4 w = pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, kRecycleDirWord, a.k0, a.k1);
-            const double u_a = pcl_u53(w.x, w.y), u_b = pcl_u53(w.z, w.w);
-            double mu;                                                  // cosine of the polar angle about d
+            double u_a, u_b, sc, ss;
+            pair_u53(pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, kRecycleDirWord, a.k0, a.k1), &u_a, &u_b);
+            double mu;      // source_mu, in place in both emitters (a helper changes the kernels): the cosine of the polar angle about d
             if (a.angular == PCL_SRC_ISOTROPIC)
-                mu = __dsub_rn(1.0, __dmul_rn(2.0, u_a));                                             // uniform on the sphere
+                mu = __dsub_rn(1.0, __dmul_rn(2.0, u_a));                                         // uniform on the sphere
             else if (a.angular == PCL_SRC_CONE)
-                mu = __dsub_rn(1.0, __dmul_rn(u_a, __dsub_rn(1.0, a.cos_half_angle)));                // uniform in solid angle
+                mu = __dsub_rn(1.0, __dmul_rn(u_a, __dsub_rn(1.0, a.cos_half_angle)));            // uniform in solid angle
             else
-                mu = __dsqrt_rn(__dsub_rn(1.0, u_a));                                                 // cosine-weighted hemisphere
-            const double s = __dsqrt_rn(__dmul_rn(__dsub_rn(1.0, mu), __dadd_rn(1.0, mu)));
-            double sn, cs;
-            pcl_sincos_2pi(__dmul_rn(__dmul_rn(u_b, 2.0), PCL_PI), &sn, &cs);                         // the scatter step's angle
-            const double sc = __dmul_rn(s, cs), ss = __dmul_rn(s, sn);
+                mu = __dsqrt_rn(__dsub_rn(1.0, u_a));                                             // cosine-weighted hemisphere
+            polar(mu, u_b, &sc, &ss);
 #pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const double dir = __dadd_rn(__dadd_rn(__dmul_rn(sc, a.e1[k]), __dmul_rn(ss, a.e2[k])), __dmul_rn(mu, a.d[k]));
-                vel[k] = __dmul_rn(a.speed, dir);
-            }
+            for (int k = 0; k < 3; ++k) vel[k] = __dmul_rn(a.speed, turned(sc, ss, mu, a.e1[k], a.e2[k], a.d[k]));
         }
         if (a.spatial == PCL_SRC_POINT) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) pos[k] = a.origin[k];
         } else {
-            const pcl_u32x4 w = pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, kRecyclePosWord, a.k0, a.k1);
-            const double u_c = pcl_u53(w.x, w.y), u_d = pcl_u53(w.z, w.w);
-            double rho;
+            double u_c, u_d, rc, rs;
+            pair_u53(pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, kRecyclePosWord, a.k0, a.k1), &u_c, &u_d);
+            double rho;     // source_rho, in place in both emitters (a helper changes the kernels): the distance from the origin
             if (a.spatial == PCL_SRC_DISC)
-                rho = __dmul_rn(a.radius, __dsqrt_rn(u_c));                                           // uniform over the disc
-            else                                                                                      // 1 - u_c is in (0, 1]
+                rho = __dmul_rn(a.radius, __dsqrt_rn(u_c));                                       // uniform over the disc
+            else                                                                                  // 1 - u_c is in (0, 1]
                 rho = __dmul_rn(a.radius, __dsqrt_rn(__dmul_rn(-2.0, log(__dsub_rn(1.0, u_c)))));
-            double sn, cs;
-            pcl_sincos_2pi(__dmul_rn(__dmul_rn(u_d, 2.0), PCL_PI), &sn, &cs);
-            const double rc = __dmul_rn(rho, cs), rs = __dmul_rn(rho, sn);
+            azimuth(rho, u_d, &rc, &rs);
 #pragma unroll
             for (int k = 0; k < 3; ++k)
                 pos[k] = __dadd_rn(a.origin[k], __dadd_rn(__dmul_rn(rc, a.e1[k]), __dmul_rn(rs, a.e2[k])));
@@ -655,8 +602,7 @@ __global__ void __launch_bounds__(kBlock) k_recycle_spent(recycle_args<T> a) {
             a.dv[k][ti] = (T)0.0;
         }
         if (nE) {                                                       // the first x with cdf[x] >= u (cdf ends in 1 > u): compares only
-            const pcl_u32x4 w = pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, kRecycleEnergyWord, a.k0, a.k1);
-            const double u = pcl_u53(w.x, w.y);
+            const double u = first_u53(pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, kRecycleEnergyWord, a.k0, a.k1));
             int lo = 0, hi = nE - 1;
             while (lo < hi) {
                 const int mid = (lo + hi) >> 1;
@@ -705,13 +651,11 @@ __global__ void __launch_bounds__(kBlock) k_absorb_path(pabsorb_args<T> a) {
     for (int k = threadIdx.x; k < n_cells; k += kBlock) s_cnt[k] = 0;  // (the cells follow the two counts)
     __syncthreads();
     const int lane = threadIdx.x & 63;
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    // whole waves run the same number of trips (the ballots below need every lane of the wave inside the loop)
-    const int64_t n_round = (a.N + 63) / 64 * 64;
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n_round; i += stride) {
+    const int64_t stride = grid_stride(), n_round = whole_waves(a.N);   // (the ballots below need whole waves inside the loop)
+    for (int64_t i = first_slot(); i < n_round; i += stride) {
         const bool in = i < a.N;
         const int64_t ti = tile_index(i, a.tile_log, a.ts);
-        // moving: k_recycle_spent's "at rest", negated -- -0.0 == 0, a NaN moves, and a lane whose v0 is not zero loads no more of v
+        // moving: at_rest, written out (a helper changes the kernel) and negated -- -0.0 == 0, a NaN moves, v0 != 0 loads no more of v
         bool go = in && !((double)a.v[0][ti] == 0.0 && (double)a.v[1][ti] == 0.0 && (double)a.v[2][ti] == 0.0);
         if (go && a.kind) go = a.kind[i] != 0;                          // plain Objects are never touched
         int b = go && L == 0 ? 0 : -1;                                  // the layer; -1: in no layer
@@ -720,7 +664,7 @@ __global__ void __launch_bounds__(kBlock) k_absorb_path(pabsorb_args<T> a) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) x[k] = __dsub_rn((double)a.r[k][ti], a.c[k]);   // fp32 widens exactly
             const double q = dot3(x, x);
-            if (q >= s_e2[0] && q <= s_e2[L]) b = bin_of(s_e2, L, q);   // NaN: in no layer
+            if (q >= s_e2[0] && q <= s_e2[L]) b = bin_of(s_e2, L, q);   // (dist2, closed_bin: written out) NaN: in no layer
         }
         int cell = b >= 0 && nE == 0 ? b : -1;                          // b * B' + e; -1: not exposed
         if (b >= 0 && nE > 0) {
@@ -732,9 +676,8 @@ __global__ void __launch_bounds__(kBlock) k_absorb_path(pabsorb_args<T> a) {
         if (exposed) {
             const double p = s_p[cell];
             if (p > 0.0) {                                              // a transparent cell draws nothing
-                const uint64_t id = (uint64_t)(a.ids ? a.ids[i] : a.id_base + i);
-                const pcl_u32x4 w = pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, kPathAbsorbWord, a.k0, a.k1);
-                gone = pcl_u53(w.x, w.y) < p;                           // u < 1: p == 1 absorbs everybody
+                const uint64_t id = id_of(a.ids, a.id_base, i);
+                gone = first_u53(pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, kPathAbsorbWord, a.k0, a.k1)) < p;   // u < 1: p == 1 absorbs everybody
             }
         }
         const uint32_t n_exp = (uint32_t)__popcll(__ballot(exposed)), n_gone = (uint32_t)__popcll(__ballot(gone));
@@ -742,7 +685,7 @@ __global__ void __launch_bounds__(kBlock) k_absorb_path(pabsorb_args<T> a) {
         if (lane == 0 && n_gone) atomicAdd(&s_cnt[1], n_gone);
         if (!gone) continue;    // lanes that are left alone wait at the loop's head: no ballot below this line
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {                                   // parked where it is, at rest; "did not scatter"
+        for (int k = 0; k < 3; ++k) {                                   // park, written out: at rest where it is; "did not scatter"
             a.v[k][ti] = (T)0.0;
             a.dv[k][ti] = (T)0.0;
         }

@@ -713,21 +713,137 @@ def _dot3(x, y):
     return (x[:, 0] * y[:, 0] + x[:, 1] * y[:, 1]) + x[:, 2] * y[:, 2]
 
 
+# The rules the writer sweeps share, each stated once: the restatements below are built from them, and pcl_rules.h holds the
+# device's helper wherever a kernel stays the same machine code with it.  Every line is the device's operation, one rounding each.
+def _scalar(x, message):
+    """``x`` as one float, or ValueError(message)."""
+    try:
+        return float(np.asarray(x, dtype=np.float64).reshape(()))
+    except (TypeError, ValueError):
+        raise ValueError(message) from None
+
+
+def _radius(x, name, message):
+    """A radius the device can square: one finite, positive number whose square is finite, too."""
+    x = _scalar(x, message)
+    if not (np.isfinite(x) and x > 0 and np.isfinite(x * x)):
+        raise ValueError("%s must be finite and positive (its square finite, too), got %r" % (name, x))
+    return x
+
+
+def _mean_cosine(g, where=""):
+    """The ``g`` of a Henyey-Greenstein law: one finite number with |g| < 1."""
+    g = _scalar(g, where + "g must be a number")
+    if not (np.isfinite(g) and abs(g) < 1.0):
+        raise ValueError("%sg must be finite with |g| < 1, got %r" % (where, g))
+    return g
+
+
+def _dv_rule_refusal(sim, name, what):
+    """The steps that read "scattered in this pass" off dv cannot run under the reference's Python semantics."""
+    if getattr(sim, "_py_semantics", None) is not None and sim._py_semantics():
+        raise ValueError("%s needs cl_on=True: under the reference's Python semantics a scattered photon is left "
+                         "with dv = v_old, not v' - v_old, so %s cannot be read off the store" % (name, what))
+
+
+def _stored(x, dtype):
+    """What the store holds of float64 values: rounded once to ``dtype``."""
+    return x.astype(dtype).astype(np.float64)
+
+
+def _scattered(dv, photon):
+    """Scattered / interacted in this pass: a photon with dv != 0 (the scatter step leaves 0 on a miss; NaN != 0 is true)."""
+    return ((dv[:, 0] != 0) | (dv[:, 1] != 0) | (dv[:, 2] != 0)) & np.asarray(photon, dtype=bool).reshape(-1)
+
+
+def _workable(oo):
+    """An old velocity o with o.o = oo whose direction can be worked with (NaN: False)."""
+    return (oo > 0) & (oo < np.inf)
+
+
+def _at_rest(v):
+    """v == (0, 0, 0): -0.0 == 0, a NaN moves."""
+    return (v[:, 0] == 0) & (v[:, 1] == 0) & (v[:, 2] == 0)
+
+
+def _bin_of(values, edges):
+    """numpy.histogram's bin of each value: [e_b, e_(b+1)), the last one closed; -1 outside the edges and for a NaN."""
+    nb = len(edges) - 1
+    out = np.full(len(values), -1, dtype=np.int64)
+    with np.errstate(invalid="ignore"):
+        ok = (values >= edges[0]) & (values <= edges[-1])
+    out[ok] = np.clip(np.searchsorted(edges, values[ok], side="right") - 1, 0, nb - 1)
+    return out
+
+
+def _layer_of(r_rows, edges, center):
+    """The radial layer of each position: the bin of q = d.d, d = r - center, in e*e -- no square root; no edges: layer 0."""
+    if edges is None:
+        return np.zeros(len(r_rows), dtype=np.int64)
+    e = np.asarray(edges, dtype=np.float64)
+    d = r_rows - np.asarray(center, dtype=np.float64)
+    return _bin_of(_dot3(d, d), e * e)
+
+
+def _law_mu(kind, g, nodes, F, u_a, ids, seed, n_pass):
+    """The cosine of the scattering angle by one law from u_a (Rayleigh's 3/2 mu^2 part draws block 11 as well)."""
+    if kind == "hg" and g != 0.0:
+        g = np.float64(g)
+        gg, g2 = g * g, 2.0 * g
+        q = (1.0 - gg) / ((1.0 - g) + g2 * u_a)
+        return np.fmin(np.fmax(((1.0 + gg) - q * q) / g2, -1.0), 1.0)
+    if kind == "rayleigh":
+        s4 = u_a * 4.0
+        j = np.floor(s4)
+        mu = 2.0 * (s4 - j) - 1.0
+        part = j == 3.0                                    # one in four: the 3/2 mu^2 part of 3/8 (1 + mu^2)
+        u_c, u_d = _philox_block(ids[part], seed, n_pass, 11)
+        mu[part] = np.copysign(np.fmax(np.fmax(np.abs(mu[part]), u_c), u_d), mu[part])
+        return mu
+    if kind == "table":                                    # the inverse of the piecewise linear F
+        slope = (nodes[1:] - nodes[:-1]) / (F[1:] - F[:-1])
+        k = np.clip(np.searchsorted(F, u_a, side="right") - 1, 0, len(nodes) - 2)
+        return np.fmin(np.fmax(nodes[k] + (u_a - F[k]) * slope[k], nodes[k]), nodes[k + 1])
+    return 1.0 - 2.0 * u_a                                 # uniform on the sphere
+
+
+def _azimuth(rho, u):
+    """(rho cos psi, rho sin psi) of psi = (u*2)*pi, the scatter step's angle (libm's sin / cos here)."""
+    psi = (u * 2.0) * np.pi
+    return rho * np.cos(psi), rho * np.sin(psi)
+
+
+def _polar(mu, u_b):
+    """(sc, ss): the sine to the cosine mu about the azimuth of u_b."""
+    return _azimuth(np.sqrt((1.0 - mu) * (1.0 + mu)), u_b)
+
+
+def _frame(w):
+    """(e1, e2): an orthonormal frame about the unit vectors w (Duff et al. 2017, branch-free)."""
+    w0, w1, w2 = w[:, 0], w[:, 1], w[:, 2]
+    sg = np.copysign(1.0, w2)
+    aa = -1.0 / (sg + w2)
+    bb, sw0 = (w0 * w1) * aa, sg * w0
+    return np.stack([1.0 + (sw0 * w0) * aa, sg * bb, -sw0], axis=1), np.stack([bb, sg + (w1 * w1) * aa, -w1], axis=1)
+
+
+def _direction(e1, e2, axis, sc, ss, mu):
+    """(sc*e1 + ss*e2) + mu*axis, per row; the frame and the axis one per row, or one for all rows."""
+    return (sc[:, None] * e1 + ss[:, None] * e2) + mu[:, None] * axis
+
+
+def _turn_about(w, mu, u_b):
+    """The direction at the cosine mu and the azimuth of u_b about the unit vectors w."""
+    return _direction(*_frame(w), w, *_polar(mu, u_b), mu)
+
+
 def _check_surface(radius, center, albedo, mode):
     """(radius, centre as 3 float64, albedo, mode) of a SurfaceReflectStep, or ValueError for everything
     pcl_step_surface_reflect would refuse."""
     from ._hip import SURFACE_MODES
-    try:
-        radius = float(np.asarray(radius, dtype=np.float64).reshape(()))
-    except (TypeError, ValueError):
-        raise ValueError("radius must be a number") from None
-    if not (np.isfinite(radius) and radius > 0 and np.isfinite(radius * radius)):
-        raise ValueError("radius must be finite and positive (its square finite, too), got %r" % (radius,))
+    radius = _radius(radius, "radius", "radius must be a number")
     center = tally.check_center(center)
-    try:
-        albedo = float(np.asarray(albedo, dtype=np.float64).reshape(()))
-    except (TypeError, ValueError):
-        raise ValueError("albedo must be a number") from None
+    albedo = _scalar(albedo, "albedo must be a number")
     if not 0.0 <= albedo <= 1.0:                          # (False for NaN as well)
         raise ValueError("albedo must lie in [0, 1], got %r" % (albedo,))
     if not isinstance(mode, str) or mode not in SURFACE_MODES:
@@ -771,17 +887,8 @@ def _surface_bounce(r, dr, v, photon, ids, radius, center, albedo, mode, c, seed
             direction = mh - (2.0 * _dot3(mh, nrm))[:, None] * nrm
         else:
             u_a, u_b = _philox_block(ids, seed, n_pass, 8)
-            mu = np.sqrt(1.0 - u_a)
-            sn = np.sqrt((1.0 - mu) * (1.0 + mu))
-            psi = (u_b * 2.0) * np.pi
-            sc, ss = sn * np.cos(psi), sn * np.sin(psi)
-            n0, n1, n2 = nrm[:, 0], nrm[:, 1], nrm[:, 2]
-            sg = np.copysign(1.0, n2)
-            aa = -1.0 / (sg + n2)
-            bb, sn0 = (n0 * n1) * aa, sg * n0
-            e1 = np.stack([1.0 + (sn0 * n0) * aa, sg * bb, -sn0], axis=1)
-            e2 = np.stack([bb, sg + (n1 * n1) * aa, -n1], axis=1)
-            direction = (sc[:, None] * e1 + ss[:, None] * e2) + mu[:, None] * nrm
+            mu = np.sqrt(1.0 - u_a)                            # cosine-weighted hemisphere
+            direction = _turn_about(nrm, mu, u_b)
             out["mu"][at] = mu
         w = (1.0 - t) * sa
         v_new = c * direction
@@ -793,7 +900,7 @@ def _surface_bounce(r, dr, v, photon, ids, radius, center, albedo, mode, c, seed
         for name, new in (("r", r_new), ("v", v_new), ("dr", dr_new), ("dv", dv_new)):
             full = {"r": r, "v": v, "dr": dr}.get(name)
             full = np.zeros((n, 3)) if full is None else full
-            full[at] = new.astype(dtype).astype(np.float64)
+            full[at] = _stored(new, dtype)
             out[name] = full
     out["t"][at], out["x"][at], out["nrm"][at] = t, x, nrm
     return out
@@ -866,13 +973,7 @@ def _check_phase(phase, g):
     from ._hip import PHASE_FUNCTIONS
     if not isinstance(phase, str) or phase not in PHASE_FUNCTIONS:
         raise ValueError("phase must be one of %s, got %r" % (", ".join(repr(k) for k in PHASE_FUNCTIONS), phase))
-    try:
-        g = float(np.asarray(g, dtype=np.float64).reshape(()))
-    except (TypeError, ValueError):
-        raise ValueError("g must be a number") from None
-    if not (np.isfinite(g) and abs(g) < 1.0):
-        raise ValueError("g must be finite with |g| < 1, got %r" % (g,))
-    return phase, g
+    return phase, _mean_cosine(g)
 
 
 def _phase_redirect(v, dv, photon, ids, phase, g, c, seed, n_pass, dtype=np.float64):
@@ -886,12 +987,12 @@ def _phase_redirect(v, dv, photon, ids, phase, g, c, seed, n_pass, dtype=np.floa
     v, dv = (np.array(a, dtype=np.float64).reshape(-1, 3) for a in (v, dv))
     n = len(v)
     phase, g = _check_phase(phase, g)
-    c, g = np.float64(c), np.float64(g)
+    c = np.float64(c)
     with np.errstate(invalid="ignore", over="ignore"):
-        scattered = ((dv[:, 0] != 0) | (dv[:, 1] != 0) | (dv[:, 2] != 0)) & np.asarray(photon, dtype=bool).reshape(-1)
+        scattered = _scattered(dv, photon)
         o_all = v - dv
         oo = _dot3(o_all, o_all)
-        go = scattered & (oo > 0) & (oo < np.inf)
+        go = scattered & _workable(oo)
     at = np.flatnonzero(go)
     ids = np.asarray(ids).reshape(-1)[at]
     out = {"scattered": scattered, "redirected": go, "mu": np.full(n, np.nan), "w": np.full((n, 3), np.nan)}
@@ -899,32 +1000,10 @@ def _phase_redirect(v, dv, photon, ids, phase, g, c, seed, n_pass, dtype=np.floa
     with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
         w = o / np.sqrt(oo[at])[:, None]
         u_a, u_b = _philox_block(ids, seed, n_pass, 10)
-        mu = 1.0 - 2.0 * u_a                               # uniform on the sphere
-        if phase == "hg" and g != 0.0:
-            gg, g2 = g * g, 2.0 * g
-            q = (1.0 - gg) / ((1.0 - g) + g2 * u_a)
-            mu = np.fmin(np.fmax(((1.0 + gg) - q * q) / g2, -1.0), 1.0)
-        elif phase == "rayleigh":
-            s4 = u_a * 4.0
-            j = np.floor(s4)
-            gq = 2.0 * (s4 - j) - 1.0
-            mu = gq.copy()
-            part = j == 3.0                                # one in four: the 3/2 mu^2 part of 3/8 (1 + mu^2)
-            u_c, u_d = _philox_block(ids[part], seed, n_pass, 11)
-            mu[part] = np.copysign(np.fmax(np.fmax(np.abs(gq[part]), u_c), u_d), gq[part])
-        sn = np.sqrt((1.0 - mu) * (1.0 + mu))
-        psi = (u_b * 2.0) * np.pi
-        sc, ss = sn * np.cos(psi), sn * np.sin(psi)
-        w0, w1, w2 = w[:, 0], w[:, 1], w[:, 2]
-        sg = np.copysign(1.0, w2)                          # the frame of _surface_bounce, about w
-        aa = -1.0 / (sg + w2)
-        bb, sw0 = (w0 * w1) * aa, sg * w0
-        e1 = np.stack([1.0 + (sw0 * w0) * aa, sg * bb, -sw0], axis=1)
-        e2 = np.stack([bb, sg + (w1 * w1) * aa, -w1], axis=1)
-        direction = (sc[:, None] * e1 + ss[:, None] * e2) + mu[:, None] * w
-        v_new = c * direction
+        mu = _law_mu(phase, g, None, None, u_a, ids, seed, n_pass)
+        v_new = c * _turn_about(w, mu, u_b)
         dv_new = v_new - o
-    v[at], dv[at] = v_new.astype(dtype).astype(np.float64), dv_new.astype(dtype).astype(np.float64)
+    v[at], dv[at] = _stored(v_new, dtype), _stored(dv_new, dtype)
     out["v"], out["dv"] = v, dv
     out["mu"][at], out["w"][at] = mu, w
     return out
@@ -970,9 +1049,7 @@ class PhaseFunctionStep(tally.WriterStep):
         self.data.append(tally.object_row([tally._snap(sim.t), self.redirected]))
 
     def _refuse(self, sim):
-        if getattr(sim, "_py_semantics", None) is not None and sim._py_semantics():
-            raise ValueError("PhaseFunctionStep needs cl_on=True: under the reference's Python semantics a scattered photon is left "
-                             "with dv = v_old, not v' - v_old, so its direction before the scatter cannot be read off the store")
+        _dv_rule_refusal(sim, "PhaseFunctionStep", "its direction before the scatter")
 
     def _sweep(self, sim, prep):
         return [np.array([sim._dev.phase_redirect(self.phase, self.g, _c_h_literals()[0], sim.seed, self._pass)], dtype=np.int64)]
@@ -1027,18 +1104,10 @@ def _absorb_scattered(r, v, dv, E, photon, ids, omega0, edges, center, E_bins, s
     om = np.asarray(omega0, dtype=np.float64).reshape(-1)
     rows = 1 if edges is None else len(edges) - 1
     with np.errstate(invalid="ignore", over="ignore"):
-        interacted = ((dv[:, 0] != 0) | (dv[:, 1] != 0) | (dv[:, 2] != 0)) & np.asarray(photon, dtype=bool).reshape(-1)
+        interacted = _scattered(dv, photon)
         at = np.flatnonzero(interacted)
         layer = np.full(n, -1, dtype=np.int64)
-        if edges is None:
-            layer[at] = 0
-        else:
-            e = np.asarray(edges, dtype=np.float64)
-            e2 = e * e
-            d = r[at] - np.asarray(center, dtype=np.float64)
-            q = _dot3(d, d)
-            inside = (q >= e2[0]) & (q <= e2[-1])                                   # NaN: in no layer
-            layer[at[inside]] = np.clip(np.searchsorted(e2, q[inside], side="right") - 1, 0, rows - 1)   # the last layer is closed
+        layer[at] = _layer_of(r[at], edges, center)
     draws = np.flatnonzero(layer >= 0)
     draws = draws[om[layer[draws]] < 1.0]                      # a conservative layer draws nothing
     u = _philox_block(np.asarray(ids).reshape(-1)[draws], seed, n_pass, 12)[0]
@@ -1048,12 +1117,10 @@ def _absorb_scattered(r, v, dv, E, photon, ids, omega0, edges, center, E_bins, s
     v[gone], dv[gone] = np.zeros(3, dtype=dtype), np.zeros(3, dtype=dtype)
     out = {"v": v, "dv": dv, "interacted": interacted, "absorbed": absorbed, "layer": layer,
            "absorbed_by_layer": np.bincount(layer[gone], minlength=rows).astype(np.int64), "E_hist": None}
-    if E_bins is not None:                                     # numpy.histogram's bins: [e_b, e_b+1), the last one closed
-        eb, val = np.asarray(E_bins, dtype=np.float64), np.asarray(E, dtype=np.float64).reshape(-1)[gone]
-        nb = len(eb) - 1
-        with np.errstate(invalid="ignore"):
-            ok = (val >= eb[0]) & (val <= eb[-1])
-        cell = layer[gone][ok] * nb + np.clip(np.searchsorted(eb, val[ok], side="right") - 1, 0, nb - 1)
+    if E_bins is not None:
+        nb = len(E_bins) - 1
+        eb = _bin_of(np.asarray(E, dtype=np.float64).reshape(-1)[gone], np.asarray(E_bins, dtype=np.float64))
+        cell = layer[gone][eb >= 0] * nb + eb[eb >= 0]
         out["E_hist"] = np.bincount(cell, minlength=rows * nb).astype(np.int64).reshape(rows, nb)
     return out
 
@@ -1117,9 +1184,7 @@ class AbsorptionStep(tally.WriterStep):
         self.data.append(tally.object_row([tally._snap(sim.t), self.interacted, self.absorbed] + cells))
 
     def _refuse(self, sim):
-        if getattr(sim, "_py_semantics", None) is not None and sim._py_semantics():
-            raise ValueError("AbsorptionStep needs cl_on=True: under the reference's Python semantics a scattered photon is left "
-                             "with dv = v_old, not v' - v_old, so who interacted in this pass cannot be read off the store")
+        _dv_rule_refusal(sim, "AbsorptionStep", "who interacted in this pass")
 
     def _sweep(self, sim, prep):
         interacted, absorbed, by_layer, E_hist = sim._dev.absorb_scattered(self.omega0, self.edges, self.center, self.E_bins, sim.seed, self._pass)
@@ -1177,13 +1242,7 @@ def _check_layered_phase(laws, weights, edges, center):
         if isinstance(law, str) and law in ("isotropic", "rayleigh"):
             out.append((law, 0.0, None, None))
         elif isinstance(law, (tuple, list)) and len(law) == 2 and isinstance(law[0], str) and law[0] == "hg":
-            try:
-                g = float(np.asarray(law[1], dtype=np.float64).reshape(()))
-            except (TypeError, ValueError):
-                raise ValueError("laws[%d]: g must be a number" % j) from None
-            if not (np.isfinite(g) and abs(g) < 1.0):
-                raise ValueError("laws[%d]: g must be finite with |g| < 1, got %r" % (j, g))
-            out.append(("hg", g, None, None))
+            out.append(("hg", _mean_cosine(law[1], "laws[%d]: " % j), None, None))
         elif isinstance(law, (tuple, list)) and len(law) == 3 and isinstance(law[0], str) and law[0] == "table":
             mu, F = _check_table_law(j, law[1], law[2], LPHASE_MAX_NODES)
             total += len(mu) - 1
@@ -1238,17 +1297,10 @@ def _layered_phase_apply(r, v, dv, photon, ids, laws, cum, edges, center, c, see
     with np.errstate(invalid="ignore", over="ignore"):
         o_all = v - dv
         oo = _dot3(o_all, o_all)
-        scattered = ((dv[:, 0] != 0) | (dv[:, 1] != 0) | (dv[:, 2] != 0)) & np.asarray(photon, dtype=bool).reshape(-1) & (oo > 0) & (oo < np.inf)
+        scattered = _scattered(dv, photon) & _workable(oo)
         at = np.flatnonzero(scattered)
         layer = np.full(n, -1, dtype=np.int64)
-        if edges is None:
-            layer[at] = 0
-        else:
-            e2 = edges * edges
-            d = r[at] - center
-            q = _dot3(d, d)
-            inside = (q >= e2[0]) & (q <= e2[-1])                                   # NaN: in no layer
-            layer[at[inside]] = np.clip(np.searchsorted(e2, q[inside], side="right") - 1, 0, rows - 1)   # the last layer is closed
+        layer[at] = _layer_of(r[at], edges, center)
     go = layer >= 0
     at = np.flatnonzero(go)
     ids = np.asarray(ids).reshape(-1)[at]
@@ -1265,41 +1317,13 @@ def _layered_phase_apply(r, v, dv, photon, ids, laws, cum, edges, center, c, see
     with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
         w = o / np.sqrt(oo[at])[:, None]
         u_a, u_b = _philox_block(ids, seed, n_pass, 10)
-        mu = 1.0 - 2.0 * u_a                                   # uniform on the sphere
+        mu = np.empty(len(at))
         for j, (kind, g, nodes, F) in enumerate(laws):
             mine = np.flatnonzero(pick == j)
-            ua = u_a[mine]
-            if kind == "hg" and g != 0.0:
-                g = np.float64(g)
-                gg, g2 = g * g, 2.0 * g
-                q = (1.0 - gg) / ((1.0 - g) + g2 * ua)
-                mu[mine] = np.fmin(np.fmax(((1.0 + gg) - q * q) / g2, -1.0), 1.0)
-            elif kind == "rayleigh":
-                s4 = ua * 4.0
-                jq = np.floor(s4)
-                gq = 2.0 * (s4 - jq) - 1.0
-                part = jq == 3.0                               # one in four: the 3/2 mu^2 part of 3/8 (1 + mu^2)
-                u_c, u_d = _philox_block(ids[mine][part], seed, n_pass, 11)
-                gq[part] = np.copysign(np.fmax(np.fmax(np.abs(gq[part]), u_c), u_d), gq[part])
-                mu[mine] = gq
-            elif kind == "table":                              # the inverse of the piecewise linear F
-                K = len(nodes) - 1
-                slope = (nodes[1:] - nodes[:-1]) / (F[1:] - F[:-1])
-                k = np.clip(np.searchsorted(F, ua, side="right") - 1, 0, K - 1)
-                mu[mine] = np.fmin(np.fmax(nodes[k] + (ua - F[k]) * slope[k], nodes[k]), nodes[k + 1])
-        sn = np.sqrt((1.0 - mu) * (1.0 + mu))
-        psi = (u_b * 2.0) * np.pi
-        sc, ss = sn * np.cos(psi), sn * np.sin(psi)
-        w0, w1, w2 = w[:, 0], w[:, 1], w[:, 2]
-        sg = np.copysign(1.0, w2)                          # the frame of _surface_bounce, about w
-        aa = -1.0 / (sg + w2)
-        bb, sw0 = (w0 * w1) * aa, sg * w0
-        e1 = np.stack([1.0 + (sw0 * w0) * aa, sg * bb, -sw0], axis=1)
-        e2v = np.stack([bb, sg + (w1 * w1) * aa, -w1], axis=1)
-        direction = (sc[:, None] * e1 + ss[:, None] * e2v) + mu[:, None] * w
-        v_new = c * direction
+            mu[mine] = _law_mu(kind, g, nodes, F, u_a[mine], ids[mine], seed, n_pass)
+        v_new = c * _turn_about(w, mu, u_b)
         dv_new = v_new - o
-    v[at], dv[at] = v_new.astype(dtype).astype(np.float64), dv_new.astype(dtype).astype(np.float64)
+    v[at], dv[at] = _stored(v_new, dtype), _stored(dv_new, dtype)
     out["v"], out["dv"] = v, dv
     out["mu"][at], out["w"][at] = mu, w
     return out
@@ -1358,9 +1382,7 @@ class LayeredPhaseStep(tally.WriterStep):
         self.data.append(tally.object_row([tally._snap(sim.t), self.scattered, self.redirected, self.by_layer.copy(), self.by_law.copy()]))
 
     def _refuse(self, sim):
-        if getattr(sim, "_py_semantics", None) is not None and sim._py_semantics():
-            raise ValueError("LayeredPhaseStep needs cl_on=True: under the reference's Python semantics a scattered photon is left "
-                             "with dv = v_old, not v' - v_old, so its direction before the scatter cannot be read off the store")
+        _dv_rule_refusal(sim, "LayeredPhaseStep", "its direction before the scatter")
         if self._pass == 0:                              # the words 10 and 11 are drawn from once per photon and pass
             steps = getattr(sim, "steps", None) or {}
             for other in (steps.values() if isinstance(steps, dict) else steps):
@@ -1389,12 +1411,7 @@ def _check_recycle(source, top, center, at_rest, spectrum):
     if not isinstance(source, PhotonSource):
         raise ValueError("source must be a PhotonSource, got %r" % (source,))
     if top is not None:
-        try:
-            top = float(np.asarray(top, dtype=np.float64).reshape(()))
-        except (TypeError, ValueError):
-            raise ValueError("top must be None or a number") from None
-        if not (np.isfinite(top) and top > 0 and np.isfinite(top * top)):
-            raise ValueError("top must be finite and positive (its square finite, too), got %r" % (top,))
+        top = _radius(top, "top", "top must be None or a number")
     center = tally.check_center(center)
     at_rest = bool(at_rest)
     if not at_rest and top is None:
@@ -1443,18 +1460,14 @@ def _source_emit(ids, source, c, seed, word2, dir_word, pos_word):
                 mu = 1.0 - u_a * (1.0 - np.float64(source.cos_half_angle))
             else:
                 mu = np.sqrt(1.0 - u_a)
-            s = np.sqrt((1.0 - mu) * (1.0 + mu))
-            psi = (u_b * 2.0) * np.pi
-            sc, ss = s * np.cos(psi), s * np.sin(psi)
-            v = c * ((sc[:, None] * e1 + ss[:, None] * e2) + mu[:, None] * d)
+            v = c * _direction(e1, e2, d, *_polar(mu, u_b), mu)
         if source.spatial == "point":
             r = np.tile(origin, (n, 1))
         else:
             u_c, u_d = _philox_block(ids, seed, word2, pos_word)
             radius = np.float64(source.radius)
             rho = radius * np.sqrt(u_c) if source.spatial == "disc" else radius * np.sqrt(-2.0 * np.log(1.0 - u_c))
-            phi = (u_d * 2.0) * np.pi
-            rc, rs = rho * np.cos(phi), rho * np.sin(phi)
+            rc, rs = _azimuth(rho, u_d)
             r = origin + (rc[:, None] * e1 + rs[:, None] * e2)
     return v.reshape(n, 3), r.reshape(n, 3)
 
@@ -1476,7 +1489,7 @@ def _recycle_spent(r, v, E, photon, ids, source, top, center, at_rest, spectrum,
     with np.errstate(invalid="ignore", over="ignore"):
         rest = np.zeros(n, dtype=bool)
         if at_rest:
-            rest = (v[:, 0] == 0) & (v[:, 1] == 0) & (v[:, 2] == 0)
+            rest = _at_rest(v)
         gone = np.zeros(n, dtype=bool)
         if top is not None:
             d = r - np.asarray(center, dtype=np.float64)
@@ -1487,12 +1500,12 @@ def _recycle_spent(r, v, E, photon, ids, source, top, center, at_rest, spectrum,
     ids = np.asarray(ids).reshape(-1)[at]
     v_new, r_new = _source_emit(ids, source, c, seed, n_pass, _RECYCLE_WORDS[0], _RECYCLE_WORDS[1])
     dr, dv = np.full((n, 3), np.nan), np.full((n, 3), np.nan)
-    r[at], v[at] = r_new.astype(dtype).astype(np.float64), v_new.astype(dtype).astype(np.float64)
+    r[at], v[at] = _stored(r_new, dtype), _stored(v_new, dtype)
     dr[at], dv[at] = 0.0, 0.0
     if spectrum is not None:
         grid, cdf = (np.asarray(a, dtype=np.float64) for a in spectrum)
         u = _philox_block(ids, seed, n_pass, _RECYCLE_WORDS[2])[0]
-        E[at] = grid[np.searchsorted(cdf, u, side="left")].astype(dtype).astype(np.float64)   # the first x with cdf[x] >= u
+        E[at] = _stored(grid[np.searchsorted(cdf, u, side="left")], dtype)                    # the first x with cdf[x] >= u
     return {"r": r, "v": v, "dr": dr, "dv": dv, "E": E, "at_rest": rest, "escaped": gone, "spent": spent}
 
 
@@ -1589,10 +1602,7 @@ def _check_path_absorb(k, edges, center, E_edges):
 def _path_probability(k, c, dt):
     """The chance that a photon is absorbed over one pass's move, float64: ``tau = k * (c * dt)``, ``p = -expm1(-tau)`` -- made on the
     host, the device only ever sees ``p``.  ValueError for a ``dt`` that is not finite or is negative."""
-    try:
-        dt = float(np.asarray(dt, dtype=np.float64).reshape(()))
-    except (TypeError, ValueError):
-        raise ValueError("dt must be a number, got %r" % (dt,)) from None
+    dt = _scalar(dt, "dt must be a number, got %r" % (dt,))
     if not (np.isfinite(dt) and dt >= 0.0):
         raise ValueError("dt must be finite and not negative, got %r" % (dt,))
     with np.errstate(over="ignore"):
@@ -1615,25 +1625,14 @@ def _absorb_path(r, v, dv, E, photon, ids, p, edges, center, E_edges, seed, n_pa
     rows, cols = (1 if e is None else len(e) - 1 for e in (edges, E_edges))
     p = np.asarray(p, dtype=np.float64).reshape(rows, cols)
     with np.errstate(invalid="ignore", over="ignore"):
-        rest = (v[:, 0] == 0) & (v[:, 1] == 0) & (v[:, 2] == 0)                     # -0.0 == 0; a NaN moves
-        at = np.flatnonzero(~rest & np.asarray(photon, dtype=bool).reshape(-1))
+        at = np.flatnonzero(~_at_rest(v) & np.asarray(photon, dtype=bool).reshape(-1))
         layer, band = np.full(n, -1, dtype=np.int64), np.full(n, -1, dtype=np.int64)
-        if edges is None:
-            layer[at] = 0
-        else:
-            e = np.asarray(edges, dtype=np.float64)
-            e2 = e * e
-            d = r[at] - np.asarray(center, dtype=np.float64)
-            q = _dot3(d, d)
-            inside = (q >= e2[0]) & (q <= e2[-1])                                   # NaN: in no layer
-            layer[at[inside]] = np.clip(np.searchsorted(e2, q[inside], side="right") - 1, 0, rows - 1)   # the last layer is closed
+        layer[at] = _layer_of(r[at], edges, center)
         at = at[layer[at] >= 0]
         if E_edges is None:
             band[at] = 0
-        else:                                                  # numpy.histogram's bins: [e_b, e_b+1), the last one closed
-            eb, val = np.asarray(E_edges, dtype=np.float64), np.asarray(E, dtype=np.float64).reshape(-1)[at]
-            ok = (val >= eb[0]) & (val <= eb[-1])                                   # NaN and under/overflow: in no band
-            band[at[ok]] = np.clip(np.searchsorted(eb, val[ok], side="right") - 1, 0, cols - 1)
+        else:                                                  # NaN and under/overflow: in no band
+            band[at] = _bin_of(np.asarray(E, dtype=np.float64).reshape(-1)[at], np.asarray(E_edges, dtype=np.float64))
     exposed = band >= 0
     draws = np.flatnonzero(exposed)
     draws = draws[p[layer[draws], band[draws]] > 0.0]          # a transparent cell draws nothing
