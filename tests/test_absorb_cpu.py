@@ -1,10 +1,9 @@
 """CPU: AbsorptionStep -- the constructor's refusals, the numpy restatement of the sweep (light._absorb_scattered) on a seeded
 cloud (layers, edges, who is left alone, the binomial of the draw, the tallies against numpy.histogram), the host-resident path,
-the plan the step makes, ``_device_run`` on stand-ins, the header, the refusals that need no device and the kernel's assembly.
+the plan the step makes, ``_device_run`` on stand-ins, the header and the refusals that need no device.
 Everything is exact: the sweep has no sin, cos, exp or division."""
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -418,28 +417,3 @@ def test_refused_calls_need_no_device():
         assert lib.pcl_step_absorb_scattered(None, *args) == -2, kw
         assert lib.pcl_group_step_absorb_scattered(None, *args) != 0, kw
     assert (counts == -7).all() and (hist == -7).all()
-
-
-def test_the_kernel_uses_no_scratch(tmp_path):
-    """From the unit's assembly, compiled with the library's own options: both instantiations, nothing in scratch, no VGPR
-    spills -- the metadata check of tests/test_phase_cpu.py -- and the unit's other kernels are all still there."""
-    (unit,) = [u for u in build.ADDONS if "pcl_step_absorb_scattered" in open(u["src"]).read()]
-    assert os.path.basename(unit["src"]) == "pcl_surface.hip"
-    out = str(tmp_path / "unit.s")
-    subprocess.check_call([build.HIPCC] + [f for f in build.FLAGS if f not in ("-shared", "-fPIC")] +
-                          ["--cuda-device-only", "-S", "-o", out, unit["src"]], stderr=subprocess.DEVNULL)
-    text = open(out).read()
-    kernels = re.findall(r"\.name:\s+(_Z\w*k_absorb_scattered\w*)\n(.*?)\.wavefront_size", text, re.S)
-    assert len(kernels) == 2 and not any("k_surface_reflect" in k or "k_phase_redirect" in k for k, _ in kernels), [k for k, _ in kernels]
-    for kernel, blk in kernels:
-        get = lambda k: int(re.search(r"\.%s:\s+(\d+)" % k, blk).group(1))                                  # noqa: E731
-        assert get("private_segment_fixed_size") == 0 and get("vgpr_spill_count") == 0, kernel
-    for other in ("k_surface_reflect", "k_phase_redirect"):
-        assert len(re.findall(r"\.name:\s+_Z\w*%s\w*\n" % other, text)) == 2, other
-
-
-def test_the_build_table_and_the_priced_sources_have_not_moved():
-    assert build.csrc_sha() == "b54e0443ee3f400f"
-    assert [os.path.basename(u["src"]) for u in build.UNITS] == ["physicl_hip.hip", "pcl_spectrum.hip", "pcl_source.hip", "pcl_shell.hip",
-                                                                "pcl_grid.hip", "pcl_surface.hip"]
-    assert build.ADDONS[-1]["entries"] == ("pcl_step_surface_reflect", "pcl_group_step_surface_reflect") and build.ADDONS[-1]["count"] == 2

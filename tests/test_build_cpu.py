@@ -4,8 +4,9 @@
   every ``#include "..."`` of a unit is one of its declared dependencies;
 * ``needs_build()`` and ``build_lib()`` against modification times, with no compiler run: a library newer than everything
   is left alone, one newer file recompiles the units that depend on it and no other, and the library is linked once;
-* per add-on unit: the built library exports both entry points, ``_hip`` and the header know them, and the unit's device
-  assembly, compiled with the library's own options, holds the expected instantiations with no scratch and no spills.
+* per sweep of every add-on unit: the built library exports both entry points, ``_hip`` and the header know them, and the
+  unit's device assembly, compiled once with the library's own options, holds the sweep's instantiations with no scratch and
+  no spills, within the sweep's register budget.
 """
 import ctypes
 import os
@@ -22,15 +23,23 @@ SWEEP_H = os.path.join(build.CSRC, "pcl_sweep.h")
 name = os.path.basename
 names = lambda paths: [name(p) for p in paths]                                                              # noqa: E731
 by_name = lambda rows: pytest.mark.parametrize("unit", rows, ids=[name(u["src"]) for u in rows])            # noqa: E731
-# What a unit's assembly must show beyond the instantiations without scratch or VGPR spills: no SGPR spills, a VGPR count
-# (shell: eight waves per SIMD, occupancy is left to LDS; surface: six waves per SIMD or more), instructions.
+SWEEPS = [(u, s) for u in build.ADDONS for s in u["sweeps"]]
+by_sweep = pytest.mark.parametrize("unit,sweep", SWEEPS, ids=["%s-%s" % (name(u["src"]), s["kernel"]) for u, s in SWEEPS])
+# What a sweep's kernels must show beyond the instantiations without scratch or VGPR spills: no SGPR spills, a VGPR count
+# (shell: eight waves per SIMD, occupancy is left to LDS; the surface unit's: six waves per SIMD or more), and instructions in
+# the unit's assembly.
 ASM = {
-    "pcl_spectrum.hip": {},
-    "pcl_source.hip": dict(no_sgpr_spills=True, has=["v_fma_f64"]),          # (the sincos' explicit FMAs; everything else is unfused)
-    "pcl_shell.hip": dict(no_sgpr_spills=True, vgprs=64),
+    "k_plane_spectra": {},
+    "k_apply_source": dict(no_sgpr_spills=True, has=["v_fma_f64"]),          # (the sincos' explicit FMAs; everything else is unfused)
+    "k_shell_crossings": dict(no_sgpr_spills=True, vgprs=64),
     # 64-bit adds on the device grid, 32-bit ones in LDS; q is unfused, and no square root anywhere
-    "pcl_grid.hip": dict(no_sgpr_spills=True, has=["global_atomic_add_x2", "ds_add_u32"], lacks=["v_fma_f64", "v_sqrt"]),
-    "pcl_surface.hip": dict(vgprs=80),
+    "k_position_grid": dict(no_sgpr_spills=True, has=["global_atomic_add_x2", "ds_add_u32"], lacks=["v_fma_f64", "v_sqrt"]),
+    "k_surface_reflect": dict(vgprs=80),
+    "k_phase_redirect": dict(vgprs=80),
+    "k_absorb_scattered": dict(vgprs=80),
+    "k_phase_layered": dict(vgprs=80),
+    "k_recycle_spent": dict(vgprs=80),
+    "k_absorb_path": dict(vgprs=80),
 }
 
 
@@ -49,8 +58,12 @@ def test_units_and_their_link_order():
     assert SWEEP_H not in build.CORE["deps"] and SWEEP_H not in [u["src"] for u in build.UNITS]
     for u in build.ADDONS:
         assert SWEEP_H in u["deps"] and build.ABI_HEADER in u["deps"], u["src"]
-        assert len(u["entries"]) == 2 and u["entries"][1].startswith("pcl_group_") and u["kernel"].startswith("k_")
-    assert set(ASM) == set(ORDER[1:]) and all(os.path.isfile(p) for p in table_files())
+        assert set(u) == {"src", "deps", "sweeps"} and len(u["sweeps"]) == (6 if name(u["src"]) == "pcl_surface.hip" else 1)
+        for s in u["sweeps"]:
+            assert len(s["entries"]) == 2 and s["entries"][1].startswith("pcl_group_") and s["kernel"].startswith("k_"), s
+    entries = [e for _, s in SWEEPS for e in s["entries"]]
+    assert len(set(entries)) == len(entries) == 20                     # no entry point belongs to two sweeps
+    assert [s["kernel"] for _, s in SWEEPS] == list(ASM) and all(os.path.isfile(p) for p in table_files())
 
 
 @by_name(build.UNITS)
@@ -143,28 +156,43 @@ def test_a_failing_compile_leaves_the_library_that_was_there(built, monkeypatch)
     assert open(build.LIB).read() == "before" and not os.path.exists(build.LIB + ".tmp")
 
 
-# ------------------------------------------------------------------------------------------------ per add-on unit
-@by_name(build.ADDONS)
-def test_library_exports_both_entry_points_and_the_header_declares_them(unit):
+# ------------------------------------------------------------------------------------------------ per sweep of an add-on unit
+@by_sweep
+def test_library_exports_both_entry_points_and_the_header_declares_them(unit, sweep):
     build.build_lib()
     lib = ctypes.CDLL(_hip.LIB_PATH)
     assert lib.pcl_abi_version() == 1
     text = re.sub(r"/\*.*?\*/", "", open(build.ABI_HEADER).read(), flags=re.S)
-    for entry in unit["entries"]:
+    for entry in sweep["entries"]:
         assert hasattr(lib, entry) and entry in _hip.EXPORTS and re.search(r"\b%s\s*\(" % entry, text), entry
 
 
-@by_name(build.ADDONS)
-def test_kernels_use_no_scratch(unit, tmp_path):
-    """From the unit's assembly, compiled with the library's own options: every instantiation, nothing in scratch, no spills."""
-    out = str(tmp_path / "unit.s")
-    subprocess.check_call([build.HIPCC] + [f for f in build.FLAGS if f not in ("-shared", "-fPIC")] +
-                          ["--cuda-device-only", "-S", "-o", out, unit["src"]], stderr=subprocess.DEVNULL)
-    text, want = open(out).read(), ASM[name(unit["src"])]
-    kernels = re.findall(r"\.name:\s+(_Z\w*%s\w*)\n(.*?)\.wavefront_size" % unit["kernel"], text, re.S)
-    assert len(kernels) == unit["count"], [k for k, _ in kernels]
+@pytest.fixture(scope="module")
+def assembly(tmp_path_factory):
+    """unit -> its device assembly, compiled with the library's own options; each unit is compiled once for the module."""
+    texts = {}
+
+    def get(unit):
+        src = unit["src"]
+        if src not in texts:
+            out = str(tmp_path_factory.mktemp("asm") / "unit.s")
+            subprocess.check_call([build.HIPCC] + [f for f in build.FLAGS if f not in ("-shared", "-fPIC")] +
+                                  ["--cuda-device-only", "-S", "-o", out, src], stderr=subprocess.DEVNULL)
+            print("compiled", name(src))
+            texts[src] = open(out).read()
+        return texts[src]
+    return get
+
+
+@by_sweep
+def test_kernels_use_no_scratch(unit, sweep, assembly):
+    """From the unit's assembly: every instantiation of the sweep's kernel, nothing in scratch, no spills, its budget."""
+    text, want = assembly(unit), ASM[sweep["kernel"]]
+    kernels = re.findall(r"\.name:\s+(_Z\w*%s\w*)\n(.*?)\.wavefront_size" % sweep["kernel"], text, re.S)
+    assert len(kernels) == sweep["count"], [k for k, _ in kernels]
     for kernel, blk in kernels:
         get = lambda k: int(re.search(r"\.%s:\s+(\d+)" % k, blk).group(1))                                  # noqa: E731
+        print(kernel, "vgprs", get("vgpr_count"), "sgprs", get("sgpr_count"))
         assert get("private_segment_fixed_size") == 0 and get("vgpr_spill_count") == 0, kernel
         assert get("sgpr_spill_count") == 0 or not want.get("no_sgpr_spills"), kernel
         assert "vgprs" not in want or get("vgpr_count") <= want["vgprs"], kernel

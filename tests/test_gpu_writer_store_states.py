@@ -1,5 +1,6 @@
-"""GPU: the three sweeps that write the store -- the ground, the phase function, absorption (pcl_surface.hip) -- on every state the
-hot path leaves the store in, at the level of the C ABI (``_hip.Device``).
+"""GPU: the six sweeps that write the store -- the ground, the phase function, absorption, the layered phase function, recycling,
+absorption along the path (pcl_surface.hip) -- on the states the hot path leaves the store in, at the level of the C ABI
+(``_hip.Device``).
 
 A writer cannot be checked the way the read-only sweeps are (download, sweep, restate): the download itself makes the store
 dense and dr / dv real.  So every case runs TWIN devices through one history with one set of seeds (Philox is keyed by id and
@@ -27,11 +28,27 @@ The states (tests/writer_reference.py: ``reach``), each in f64 and f32, reached 
 
 The sphere, the layers and omega0 were chosen on the CPU (the oracle's steps and the restatements on source_reference's
 population) so that every sweep has work in every state it is asked to act in; the counts are asserted, not assumed.
+
+The ground, the phase function, absorption and path absorption run on all four devices and every state (``FOUR``).  The layered
+phase function and recycling run as A and B alone, on S1, S2 and S4 (``TWIN``): the answers are equal, the stores are equal bit
+for bit behind the sweep and behind one lazy fused step and delete body, and B's "after" is the restatement of B's "before".
+
+* layered phase: the three-layer mixture (Rayleigh | 0.3 Rayleigh + 0.7 Henyey-Greenstein | Henyey-Greenstein) about the source;
+  tallies exact, rows that are not re-directed bit-identical, re-directed rows within the phase function's bounds;
+* recycle: the top is the outer edge of the second layer about the source: the photons that never scattered stand beyond it, the
+  random walkers inside.  Nobody is at rest on these states (that count is 0); a spectrum is given, so E is written as well;
+* path absorption: the gas has the three layers about the source -- the middle one transparent -- and the eight energy bands of
+  ``W.E_EDGES`` (the energies reach from 1 to 3: some photons are in no band); everybody moves in these states, the restatement
+  holds without a tolerance, and on S3 the sweep writes dv = 0 on the photons it absorbs, and the survivors carry it.
 """
 import numpy as np
 import pytest
 
 import writer_reference as W
+from layered_phase_reference import MIX_LAWS, MIX_WEIGHTS
+from path_absorb_reference import check_path_absorb
+from physicl_amd import light
+from recycle_reference import CDF, GRID, check_recycle
 
 pytestmark = pytest.mark.gpu
 
@@ -51,6 +68,8 @@ def devs(hip):
 
 
 class Ground:
+    touched = "hit"                                                    # the restatement's mask of the rows the sweep acted on
+
     def __init__(self, mode):
         self.mode, self.name = mode, "ground " + mode
 
@@ -65,8 +84,15 @@ class Ground:
         assert answer[0] > 0 and answer[1] > 0, what                   # albedo 0.5: both happen, in every state
         return ref
 
+    def survivors(self, final, ref, at, what):
+        kept = ref["hit"][at]
+        print("%s: %d of the survivors carry the ground's dv" % (what, int(kept.sum())))
+        assert kept.sum() > 0 and np.stack(final["dv"], 1)[kept].any(axis=1).all(), what
+
 
 class Phase:
+    touched = "redirected"
+
     def __init__(self, phase, g):
         self.phase, self.g, self.name = phase, g, "phase " + phase
 
@@ -81,7 +107,7 @@ class Phase:
 
 
 class Absorb:
-    name = "absorb layers"
+    name, touched = "absorb layers", "interacted"
 
     def call(self, dev, state):
         interacted, absorbed, by_layer, E_hist = dev.absorb_scattered(W.OMEGA0, W.layer_edges(state), W.Source.origin, W.E_EDGES, W.SEED, W.N_PASS)
@@ -98,12 +124,86 @@ class Absorb:
         return ref
 
 
-SWEEPS = [Ground("lambertian"), Ground("specular"), Phase(*W.LAWS[0]), Phase(*W.LAWS[1]), Absorb()]
+class PathAbsorb:
+    name, touched = "path absorb", "exposed"
+    P_GAS = np.array([np.linspace(0.1, 0.45, 8), np.zeros(8), np.linspace(0.9, 0.2, 8)])      # grey-ish, transparent, black-ish
+
+    def call(self, dev, state):
+        exposed, absorbed, cells = dev.absorb_path(self.P_GAS, W.layer_edges(state), W.Source.origin, W.E_EDGES, W.SEED, W.N_PASS)
+        return exposed, absorbed, cells.tolist()
+
+    def check(self, before, after, answer, state, what):
+        ref = check_path_absorb(before, after, answer, self.P_GAS, W.layer_edges(state), np.asarray(W.Source.origin), W.E_EDGES, W.SEED,
+                                W.N_PASS, what)
+        exposed, absorbed, cells = answer
+        by_layer = np.asarray(cells).sum(axis=1)
+        print("%s: exposed %d, absorbed %d, by layer %s" % (what, exposed, absorbed, by_layer.tolist()))
+        assert 0 < absorbed < exposed < before["count"] and by_layer[1] == 0 and by_layer[2] > 0, what      # some energies are in no band
+        assert state == "S3" or by_layer[0] > 0, what                  # (S3: nobody has scattered, next to nobody stands that far in)
+        return ref
+
+    def survivors(self, final, ref, at, what):                         # the dv the sweep left there: zeros
+        for k in range(3):
+            assert not final["dv"][k].any(), (what, "dv", k)
+        parked = ref["absorbed"][at]
+        assert parked.sum() > 0 and not np.stack(final["v"], 1)[parked].any(), what          # a parked photon stays parked
+
+
+class Layered:
+    name = "layered phase"
+
+    def call(self, dev, state):
+        laws, _, cum, edges, center = light._check_layered_phase(MIX_LAWS, MIX_WEIGHTS, W.layer_edges(state), W.Source.origin)
+        scattered, redirected, by_layer, by_law = dev.phase_layered(laws, cum, edges, center, W.C, W.SEED, W.N_PASS)
+        return scattered, redirected, by_layer.tolist(), by_law.tolist()
+
+    def check(self, before, after, answer, state, what):
+        bw, aw = W.wide(before), W.wide(after)
+        T = np.asarray(before["E"]).dtype.type
+        ref = light._layered_phase_redirect(bw["r"], bw["v"], bw["dv"], W.photons(before), before["id"], MIX_LAWS, MIX_WEIGHTS,
+                                            W.layer_edges(state), W.Source.origin, W.C, W.SEED, W.N_PASS, T)
+        scattered, redirected, by_layer, by_law = answer
+        print("%s: scattered %d, redirected %d, by layer %s, by law %s" % (what, scattered, redirected, by_layer, by_law))
+        assert (scattered, redirected) == (int(ref["scattered"].sum()), int(ref["redirected"].sum())), what
+        assert by_layer == ref["by_layer"].tolist() and by_law == ref["by_law"].tolist(), what
+        assert min(by_layer) > 0 and min(by_law) > 0 and sum(by_layer) == sum(by_law) == redirected, what  # every layer and law has work
+        go = ref["redirected"]
+        for f in set(before) - set(W.FIELDS) - {"count"}:              # E, ids, kinds
+            assert W.same_bits(before[f], after[f]), (what, f)
+        for f in W.FIELDS:                                             # not re-directed: bit-identical; r and dr: everybody
+            assert W.same_bits(aw[f][~go], bw[f][~go]), (what, f)
+        assert W.same_bits(aw["r"], bw["r"]) and W.same_bits(aw["dr"], bw["dr"]), what
+        v_unit, v_bound = (W.ulp(W.C), W.DIR_ULP) if T is np.float64 else (W.ulp(W.C, np.float32), W.DIR_ULP + 0.5)
+        v_err = np.max(np.abs(aw["v"][go] - ref["v"][go])) / v_unit
+        dv_err = np.max(np.abs(aw["dv"][go] - ref["dv"][go])) / v_unit
+        print("%s: v %.3g ulp(c) (bound %g), dv %.3g ulp(c) (bound %g)" % (what, v_err, v_bound, dv_err, v_bound + 1))
+        assert v_err <= v_bound and dv_err <= v_bound + 1.0, what
+
+
+class Recycle:
+    name = "recycle"
+
+    def call(self, dev, state):
+        top = float(W.layer_edges(state)[2])
+        return dev.recycle_spent(W.Source, W.C, True, top, W.Source.origin, (GRID, CDF), W.SEED, W.N_PASS)
+
+    def check(self, before, after, answer, state, what):
+        top = float(W.layer_edges(state)[2])
+        ref = check_recycle(before, after, answer, W.Source, top, np.asarray(W.Source.origin), True, (GRID, CDF), W.SEED, W.N_PASS,
+                            what, W.photons(before))
+        assert W.same_bits(before["kind"], after["kind"]) and before["count"] == after["count"], what
+        assert answer[0] == 0 and 0 < answer[1] < before["count"], what    # some but not all photons are outside, nobody is at rest
+        assert int(ref["spent"].sum()) == answer[1], what
+
+
+FOUR = [Ground("lambertian"), Ground("specular"), Phase(*W.LAWS[0]), Phase(*W.LAWS[1]), Absorb(), PathAbsorb()]
+TWIN = [Layered(), Recycle()]
+by_sweep = lambda sweeps: pytest.mark.parametrize("sweep", sweeps, ids=[s.name.replace(" ", "_") for s in sweeps])      # noqa: E731
 
 
 @pytest.mark.parametrize("dtype", ["f64", "f32"])
 @pytest.mark.parametrize("state", W.STATES)
-@pytest.mark.parametrize("sweep", SWEEPS, ids=[s.name.replace(" ", "_") for s in SWEEPS])
+@by_sweep(FOUR)
 def test_a_writer_sweep_on_the_store_the_hot_path_left(hip, devs, sweep, state, dtype):
     a, b, c, q = devs
     what = "%s %s %s" % (sweep.name, state, dtype)
@@ -120,8 +220,7 @@ def test_a_writer_sweep_on_the_store_the_hot_path_left(hip, devs, sweep, state, 
     assert a.is_uniform() == (state in ("S1", "S4")), what             # S2, S3: ids of their own behind densify; S5: staged ids and kinds
     ref = sweep.check(before, after_b, got_b, state, what)
     if state == "S5":
-        touched = ref.get("hit", ref.get("redirected", ref.get("interacted")))
-        assert not touched[::7].any(), what                            # plain Objects are never touched
+        assert not ref[sweep.touched][::7].any(), what                 # plain Objects are never touched
 
     # what the loop does next
     W.upload_plain(c, after_b, b.capacity, dtype)
@@ -141,7 +240,29 @@ def test_a_writer_sweep_on_the_store_the_hot_path_left(hip, devs, sweep, state, 
         assert np.array_equal(after_b["id"][at], final["id"]), what
         for k in range(3):
             assert W.same_bits(final["dv"][k], after_b["dv"][k][at]), (what, "dv", k)
-        if isinstance(sweep, Ground):
-            kept = ref["hit"][at]
-            print("%s: %d of the survivors carry the ground's dv" % (what, int(kept.sum())))
-            assert kept.sum() > 0 and np.stack(final["dv"], 1)[kept].any(axis=1).all(), what
+        if hasattr(sweep, "survivors"):
+            sweep.survivors(final, ref, at, what)
+
+
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+@pytest.mark.parametrize("state", ["S1", "S2", "S4"])
+@by_sweep(TWIN)
+def test_a_writer_sweep_on_twin_devices(hip, devs, sweep, state, dtype):
+    a, b = devs[:2]
+    what = "%s %s %s" % (sweep.name, state, dtype)
+    step = W.reach(hip, a, state, dtype)
+    assert W.reach(hip, b, state, dtype) == step
+    if state == "S2":                                                  # the alive mask is really there
+        assert a.slots > a.count and b.slots > b.count and a.slots == b.slots and a.count == b.count, what
+    before = W.snapshot(b)                                             # makes B dense and real
+    got_a, got_b = sweep.call(a, state), sweep.call(b, state)
+    assert got_a == got_b, what
+    after_a, after_b = W.snapshot(a), W.snapshot(b)
+    W.assert_same_state(after_a, after_b, what + ": A and B behind the sweep")
+    sweep.check(before, after_b, got_b, state, what)                   # B's "after" is the restatement of B's "before"
+
+    # what the loop does next: a lazy fused step with a scatter and a lazy delete body
+    assert W.aftermath(hip, a, state, step, lazy=True) == W.aftermath(hip, b, state, step, lazy=True) == 1
+    final = W.snapshot(a)
+    assert 0 < final["count"] < after_b["count"], what
+    W.assert_same_state(W.snapshot(b), final, what + ": A and B behind the aftermath")

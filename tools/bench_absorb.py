@@ -19,27 +19,9 @@ one warm-up call, the median with the spread (max - min) / median.  One JSON lin
 No ratio is fixed in advance: ``over_yardstick`` is the case's median over the first yardstick's.
 bytes_per_slot = 3 words + share_interacting * 3 words + share_absorbed * (6 words, + 1 with energy bins).
 """
-import argparse
-import json
-import os
-import statistics
-import sys
-import time
-
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from physicl_amd import _hip as hip  # noqa: E402
-
-C_LIT, H_LIT, DT = 299792458.0, 6.62607015e-34, 0.0005
-STEP = C_LIT * DT
-ORIGIN = (3.0 * STEP, -1.0 * STEP, 0.5 * STEP)
-
-
-class Isotropic:
-    origin, e1, e2, d = ORIGIN, (0.0, 1.0, 0.0), (0.0, 0.0, 1.0), (1.0, 0.0, 0.0)
-    angular, spatial, cos_half_angle, radius = "isotropic", "point", 0.0, 0.0
-
+from sweep_bench import C_LIT, DT, H_LIT, ORIGIN, STEP, Isotropic, emit, hip, main, photons, timed, yardstick
 
 # after the move every photon stands STEP from ORIGIN: about a centre 0.6 STEP off it the distances reach from 0.4 to 1.6 STEP
 CENTER = (ORIGIN[0] + 0.6 * STEP, ORIGIN[1], ORIGIN[2])
@@ -53,23 +35,10 @@ CASES = [("nobody_interacting", 0.0, 0.5, None, None),
          ("half_grey_50x50", 0.5, [0.5] * 50, LAYERS_50, E_BINS_50)]
 
 
-def stats(t):
-    med = statistics.median(t)
-    return {"s": t, "median_s": med, "spread": (max(t) - min(t)) / med}
-
-
 def bench(n, runs, dtype):
     esz = 8 if dtype == "f64" else 4
     base = {"n": n, "dtype": dtype}
-
-    def emit(case, **kw):
-        print(json.dumps(dict(base, case=case, **kw)), flush=True)
-
-    dev = hip.Device(0)
-    try:
-        dev.store_alloc(n, dtype)
-        dev.fill_photons(n, 0, C_LIT, 1.0, 3.0, 1)
-
+    with photons(n, dtype) as dev:
         def reset(p, launch):
             dev.apply_source(Isotropic, C_LIT, 1)
             dev.step_newton(DT)
@@ -77,46 +46,20 @@ def bench(n, runs, dtype):
             dev.sync()
             return hits
 
-        def yardstick(name):
-            reset(0.0, 0)
-            dev.phase_redirect("hg", 0.85, C_LIT, 1, 1)         # the first look at the store pays the core's materialise pass
-            t, got = [], 0
-            for k in range(runs):
-                t0 = time.perf_counter()
-                got = dev.phase_redirect("hg", 0.85, C_LIT, 1, 2 + k)
-                t.append(time.perf_counter() - t0)
-            y = stats(t)
-            emit(name, out=int(got), bytes_per_slot=3 * esz, GBps=3 * esz * n / y["median_s"] / 1e9, **y)
+        def phase(name):
+            y, got = yardstick(runs, lambda: reset(0.0, 0), lambda k: dev.phase_redirect("hg", 0.85, C_LIT, 1, 1 + k))
+            emit(base, name, out=int(got), bytes_per_slot=3 * esz, GBps=3 * esz * n / y["median_s"] / 1e9, **y)
             return y
-        y = yardstick("phase_nobody_scattered")
+        y = phase("phase_nobody_scattered")
         for case, p, omega0, edges, E_edges in CASES:
-            t, got, hits = [], None, 0
-            for k in range(runs + 1):
-                hits = reset(p, 1 + k)
-                t0 = time.perf_counter()
-                got = dev.absorb_scattered(omega0, edges, CENTER, E_edges, 1, 1 + k)
-                if k:                                         # (the first call is the warm-up)
-                    t.append(time.perf_counter() - t0)
-            s = stats(t)
+            s, got, hits = timed(runs, lambda k: reset(p, 1 + k), lambda k: dev.absorb_scattered(omega0, edges, CENTER, E_edges, 1, 1 + k))
             interacted, absorbed = got[0] / n, got[1] / n
             bps = (3 + 3 * interacted * (edges is not None) + (6 + (E_edges is not None)) * absorbed) * esz
-            emit(case, layers=0 if edges is None else len(edges) - 1, E_bins=0 if E_edges is None else len(E_edges) - 1,
+            emit(base, case, layers=0 if edges is None else len(edges) - 1, E_bins=0 if E_edges is None else len(E_edges) - 1,
                  share_interacting=interacted, share_absorbed=absorbed, scatter_hits=hits, bytes_per_slot=bps,
                  GBps=bps * n / s["median_s"] / 1e9, over_yardstick=s["median_s"] / y["median_s"], **s)
-        yardstick("phase_nobody_scattered_again")
-    finally:
-        dev.close()
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--n", default="10000000,100000000", help="store sizes, comma separated")
-    ap.add_argument("--runs", type=int, default=5)
-    ap.add_argument("--dtype", default="f64")
-    a = ap.parse_args()
-    for n in (int(float(x)) for x in a.n.split(",")):
-        bench(n, a.runs, a.dtype)
+        phase("phase_nobody_scattered_again")
 
 
 if __name__ == "__main__":
-    main()
+    main(bench, "10000000,100000000")

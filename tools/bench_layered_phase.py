@@ -18,28 +18,12 @@ Device.phase_redirect on the same store in the same process, at the same share s
   all_scattered_table  every photon, one 1024-bin table (Henyey-Greenstein's density at the bins' centres), no layers
 Scattered lanes also load v (3 words) and write v and dv (6 words), with layers r (3 words) too.
 """
-import argparse
-import json
-import os
-import statistics
-import sys
-import time
-
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from physicl_amd import _hip as hip  # noqa: E402
+from sweep_bench import C_LIT, DT, H_LIT, ORIGIN, STEP, Isotropic, emit, hip, main, photons, timed
 from physicl_amd import light  # noqa: E402
 
-C_LIT, H_LIT, DT = 299792458.0, 6.62607015e-34, 0.0005
-STEP = C_LIT * DT
-ORIGIN = (3.0 * STEP, -1.0 * STEP, 0.5 * STEP)
 G = 0.85
-
-
-class Isotropic:
-    origin, e1, e2, d = ORIGIN, (0.0, 1.0, 0.0), (0.0, 0.0, 1.0), (1.0, 0.0, 0.0)
-    angular, spatial, cos_half_angle, radius = "isotropic", "point", 0.0, 0.0
 
 
 def hg_table(bins):
@@ -62,28 +46,10 @@ CASES = [("nobody_scattered", 0.0, SINGLE, "phase_nobody_scattered"),
 YARDSTICKS = [("phase_nobody_scattered", 0.0), ("phase_tenth_scattered", 0.1), ("phase_all_scattered", 2.0)]
 
 
-def stats(t):
-    med = statistics.median(t)
-    return {"s": t, "median_s": med, "spread": (max(t) - min(t)) / med}
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--n", type=int, default=100_000_000)
-    ap.add_argument("--runs", type=int, default=5)
-    ap.add_argument("--dtype", default="f64")
-    a = ap.parse_args()
-    esz = 8 if a.dtype == "f64" else 4
-    base = {"n": a.n, "dtype": a.dtype}
-
-    def emit(case, **kw):
-        print(json.dumps(dict(base, case=case, **kw)), flush=True)
-
-    dev = hip.Device(0)
-    try:
-        dev.store_alloc(a.n, a.dtype)
-        dev.fill_photons(a.n, 0, C_LIT, 1.0, 3.0, 1)
-
+def bench(n, runs, dtype):
+    esz = 8 if dtype == "f64" else 4
+    base = {"n": n, "dtype": dtype}
+    with photons(n, dtype) as dev:
         def reset(p, launch):
             dev.apply_source(Isotropic, C_LIT, 1)
             dev.step_newton(DT)
@@ -91,39 +57,27 @@ def main():
             dev.sync()
             return hits
 
-        def timed(p, call):
-            t, got = [], None
-            for k in range(a.runs + 1):
-                reset(p, 1 + k)
-                t0 = time.perf_counter()
-                got = call(1 + k)
-                if k:                                         # (the first call is the warm-up)
-                    t.append(time.perf_counter() - t0)
-            return stats(t), got
-
-        def yardsticks(suffix):
+        def yardsticks(suffix):                                # the phase function behind the same preparation, state anew every call
             out = {}
             for name, p in YARDSTICKS:
-                y, got = timed(p, lambda n_pass: dev.phase_redirect("hg", G, C_LIT, 1, n_pass))
-                share = got / a.n
-                emit(name + suffix, share_scattered=share, GBps=(3 + 9 * share) * esz * a.n / y["median_s"] / 1e9, **y)
+                y, got, _ = timed(runs, lambda k: reset(p, 1 + k), lambda k: dev.phase_redirect("hg", G, C_LIT, 1, 1 + k))
+                share = got / n
+                emit(base, name + suffix, share_scattered=share, GBps=(3 + 9 * share) * esz * n / y["median_s"] / 1e9, **y)
                 out[name] = y
             return out
         yard = yardsticks("")
         for case, p, spec, against in CASES:
             laws, _, cum, edges, center = light._check_layered_phase(spec["laws"], spec["weights"], spec["edges"], CENTER)
-            s, got = timed(p, lambda n_pass: dev.phase_layered(laws, cum, edges, center, C_LIT, 1, n_pass))
+            s, got, _ = timed(runs, lambda k: reset(p, 1 + k), lambda k: dev.phase_layered(laws, cum, edges, center, C_LIT, 1, 1 + k))
             scattered, redirected, by_layer, by_law = got
-            share = scattered / a.n
+            share = scattered / n
             bps = (3 + (9 + (3 if edges is not None else 0)) * share) * esz
             y = yard[against]
-            emit(case, share_scattered=share, redirected=redirected, by_layer=by_layer.tolist(), by_law=by_law.tolist(), bytes_per_slot=bps,
-                 GBps=bps * a.n / s["median_s"] / 1e9, over_yardstick=s["median_s"] / y["median_s"],
+            emit(base, case, share_scattered=share, redirected=redirected, by_layer=by_layer.tolist(), by_law=by_law.tolist(), bytes_per_slot=bps,
+                 GBps=bps * n / s["median_s"] / 1e9, over_yardstick=s["median_s"] / y["median_s"],
                  within=bool(s["median_s"] <= y["median_s"] * (1.0 + y["spread"])), **s)
         yardsticks("_again")
-    finally:
-        dev.close()
 
 
 if __name__ == "__main__":
-    main()
+    main(bench, "100000000")

@@ -17,25 +17,7 @@ the wall time around the synchronising call, ``--runs`` repeats after one warm-u
   all_scattered        collision probability above 1: every photon; Henyey-Greenstein (g = 0.85) and Rayleigh
 Scattered lanes also load v (3 words) and write v and dv (6 words): bytes_per_slot = 3 words + share * 9 words.
 """
-import argparse
-import json
-import os
-import statistics
-import sys
-import time
-
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from physicl_amd import _hip as hip  # noqa: E402
-
-C_LIT, H_LIT, DT = 299792458.0, 6.62607015e-34, 0.0005
-STEP = C_LIT * DT
-ORIGIN = (3.0 * STEP, -1.0 * STEP, 0.5 * STEP)
-
-
-class Isotropic:
-    origin, e1, e2, d = ORIGIN, (0.0, 1.0, 0.0), (0.0, 0.0, 1.0), (1.0, 0.0, 0.0)
-    angular, spatial, cos_half_angle, radius = "isotropic", "point", 0.0, 0.0
-
+from sweep_bench import C_LIT, DT, H_LIT, ORIGIN, STEP, Isotropic, emit, hip, main, photons, timed, yardstick
 
 FAR = tuple(o + 100.0 * STEP * a for o, a in zip(ORIGIN, Isotropic.d))     # a sphere of radius STEP there: nobody is hit
 # case -> (collision probability of the scatter step that prepares the state, the laws timed)
@@ -44,28 +26,10 @@ CASES = [("nobody_scattered", 0.0, [("hg", 0.85)]),
          ("all_scattered", 2.0, [("hg", 0.85), ("rayleigh", 0.0)])]
 
 
-def stats(t):
-    med = statistics.median(t)
-    return {"s": t, "median_s": med, "spread": (max(t) - min(t)) / med}
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--n", type=int, default=100_000_000)
-    ap.add_argument("--runs", type=int, default=5)
-    ap.add_argument("--dtype", default="f64")
-    a = ap.parse_args()
-    esz = 8 if a.dtype == "f64" else 4
-    base = {"n": a.n, "dtype": a.dtype}
-
-    def emit(case, **kw):
-        print(json.dumps(dict(base, case=case, **kw)), flush=True)
-
-    dev = hip.Device(0)
-    try:
-        dev.store_alloc(a.n, a.dtype)
-        dev.fill_photons(a.n, 0, C_LIT, 1.0, 3.0, 1)
-
+def bench(n, runs, dtype):
+    esz = 8 if dtype == "f64" else 4
+    base = {"n": n, "dtype": dtype}
+    with photons(n, dtype) as dev:
         def reset(p, launch):
             dev.apply_source(Isotropic, C_LIT, 1)
             dev.step_newton(DT)
@@ -73,37 +37,21 @@ def main():
             dev.sync()
             return hits
 
-        def yardstick(name):
-            reset(0.0, 0)
-            dev.surface_reflect(STEP, FAR, 1.0, "lambertian", C_LIT, 1, 1)   # the first look at the store pays the core's materialise pass
-            t, got = [], (0, 0)
-            for k in range(a.runs):
-                t0 = time.perf_counter()
-                got = dev.surface_reflect(STEP, FAR, 1.0, "lambertian", C_LIT, 1, 2 + k)
-                t.append(time.perf_counter() - t0)
-            y = stats(t)
-            emit(name, out=int(sum(got)), GBps=6 * esz * a.n / y["median_s"] / 1e9, **y)
+        def ground(name):
+            y, got = yardstick(runs, lambda: reset(0.0, 0), lambda k: dev.surface_reflect(STEP, FAR, 1.0, "lambertian", C_LIT, 1, 1 + k))
+            emit(base, name, out=int(sum(got)), GBps=6 * esz * n / y["median_s"] / 1e9, **y)
             return y
-        y = yardstick("surface_nobody_hit")
+        y = ground("surface_nobody_hit")
         for case, p, laws in CASES:
             for phase, g in laws:
-                t, got, hits = [], 0, 0
-                for k in range(a.runs + 1):
-                    hits = reset(p, 1 + k)
-                    t0 = time.perf_counter()
-                    got = dev.phase_redirect(phase, g, C_LIT, 1, 1 + k)
-                    if k:                                     # (the first call is the warm-up)
-                        t.append(time.perf_counter() - t0)
-                s = stats(t)
-                share = got / a.n
+                s, got, hits = timed(runs, lambda k: reset(p, 1 + k), lambda k: dev.phase_redirect(phase, g, C_LIT, 1, 1 + k))
+                share = got / n
                 bps = (3 + 9 * share) * esz
-                emit(case, phase=phase, g=g, share_scattered=share, scatter_hits=hits, bytes_per_slot=bps,
-                     GBps=bps * a.n / s["median_s"] / 1e9, over_yardstick=s["median_s"] / y["median_s"],
+                emit(base, case, phase=phase, g=g, share_scattered=share, scatter_hits=hits, bytes_per_slot=bps,
+                     GBps=bps * n / s["median_s"] / 1e9, over_yardstick=s["median_s"] / y["median_s"],
                      within=bool(s["median_s"] <= y["median_s"] * (1.0 + y["spread"])), **s)
-        yardstick("surface_nobody_hit_again")
-    finally:
-        dev.close()
+        ground("surface_nobody_hit_again")
 
 
 if __name__ == "__main__":
-    main()
+    main(bench, "100000000")

@@ -16,25 +16,9 @@ call, ``--runs`` repeats after one warm-up call, the median with the spread (max
   all_hit              a beam, a sphere just ahead of it that every move enters
 Hit lanes also load v (3 words) and write r, v, dr, dv (12 words): bytes_per_slot = 6 words + share_hit * 15 words.
 """
-import argparse
-import json
-import os
-import statistics
-import sys
-import time
+from sweep_bench import C_LIT, DT, ORIGIN, STEP, Isotropic, emit, main, photons, timed, yardstick
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from physicl_amd import _hip as hip  # noqa: E402
-
-C_LIT, DT = 299792458.0, 0.0005
-STEP = C_LIT * DT
-ORIGIN = (3.0 * STEP, -1.0 * STEP, 0.5 * STEP)
-X = (1.0, 0.0, 0.0)
-
-
-class Isotropic:
-    origin, e1, e2, d = ORIGIN, (0.0, 1.0, 0.0), (0.0, 0.0, 1.0), X
-    angular, spatial, cos_half_angle, radius = "isotropic", "point", 0.0, 0.0
+X = Isotropic.d
 
 
 class Beam(Isotropic):
@@ -52,63 +36,29 @@ CASES = [("nobody_hit", Isotropic, off(100.0), STEP),
          ("all_hit", Beam, off(1.2, Beam.d), 0.5 * STEP)]
 
 
-def stats(t):
-    med = statistics.median(t)
-    return {"s": t, "median_s": med, "spread": (max(t) - min(t)) / med}
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--n", type=int, default=100_000_000)
-    ap.add_argument("--runs", type=int, default=5)
-    ap.add_argument("--dtype", default="f64")
-    a = ap.parse_args()
-    esz = 8 if a.dtype == "f64" else 4
-    base = {"n": a.n, "dtype": a.dtype}
-
-    def emit(case, **kw):
-        print(json.dumps(dict(base, case=case, **kw)), flush=True)
-
-    dev = hip.Device(0)
-    try:
-        dev.store_alloc(a.n, a.dtype)
-        dev.fill_photons(a.n, 0, C_LIT, 1.0, 3.0, 1)
-
+def bench(n, runs, dtype):
+    esz = 8 if dtype == "f64" else 4
+    base = {"n": n, "dtype": dtype}
+    with photons(n, dtype) as dev:
         def reset(source):
             dev.apply_source(source, C_LIT, 1)
             dev.step_newton(DT)
             dev.sync()
 
-        def yardstick(name):
-            reset(Isotropic)
-            dev.shell_crossings([0.5 * STEP], ORIGIN)         # the first look at the store pays the core's materialise pass
-            t = []
-            for _ in range(a.runs):
-                t0 = time.perf_counter()
-                got = dev.shell_crossings([0.5 * STEP], ORIGIN)
-                t.append(time.perf_counter() - t0)
-            y = stats(t)
-            emit(name, out=int(got[0][0].sum()), GBps=6 * esz * a.n / y["median_s"] / 1e9, **y)
+        def shells(name):
+            y, got = yardstick(runs, lambda: reset(Isotropic), lambda k: dev.shell_crossings([0.5 * STEP], ORIGIN))
+            emit(base, name, out=int(got[0][0].sum()), GBps=6 * esz * n / y["median_s"] / 1e9, **y)
             return y
-        y = yardstick("shells_1_counts")
+        y = shells("shells_1_counts")
         for case, source, center, radius in CASES:
             for mode in ("lambertian", "specular"):
-                t, got = [], (0, 0)
-                for k in range(a.runs + 1):
-                    reset(source)
-                    t0 = time.perf_counter()
-                    got = dev.surface_reflect(radius, center, 1.0, mode, C_LIT, 1, 1 + k)
-                    if k:                                     # (the first call is the warm-up)
-                        t.append(time.perf_counter() - t0)
-                s = stats(t)
-                share = sum(got) / a.n
+                s, got, _ = timed(runs, lambda k: reset(source), lambda k: dev.surface_reflect(radius, center, 1.0, mode, C_LIT, 1, 1 + k))
+                share = sum(got) / n
                 bps = (6 + 15 * share) * esz
-                emit(case, mode=mode, share_hit=share, bytes_per_slot=bps, GBps=bps * a.n / s["median_s"] / 1e9,
+                emit(base, case, mode=mode, share_hit=share, bytes_per_slot=bps, GBps=bps * n / s["median_s"] / 1e9,
                      over_shells=s["median_s"] / y["median_s"], **s)
-        yardstick("shells_1_counts_again")
-    finally:
-        dev.close()
+        shells("shells_1_counts_again")
 
 
 if __name__ == "__main__":
-    main()
+    main(bench, "100000000")

@@ -4,12 +4,14 @@ For a refactor of their host side, of pcl_sweep.h or of the build, in place of a
 
     python tools/compare_unit_asm.py <old tree> <new tree> [--md]
 
-Each unit of each tree is compiled to gfx950 assembly with the library's own options (physicl_amd/build.py: FLAGS without
--shared / -fPIC, plus --cuda-device-only -S, as tests/test_build_cpu.py does).  Per kernel the register and
-segment metadata must be equal and the instruction lines must be the same multiset (the scheduler may swap neighbours when
-a helper moves into a header, so not the same sequence).  A kernel that only the new tree has is listed as new with its
-metadata (a unit that gained a sweep: the kernels it had must still be the code they were); one that only the old tree has
-counts as a difference.  Exit status 1 if any kernel differs.
+Each tree's units are its own: every ``*.hip`` of its physicl_amd/csrc but the core, so two trees whose build tables differ
+can be compared.  Each is compiled to gfx950 assembly with this tree's options (physicl_amd/build.py: FLAGS without
+-shared / -fPIC, plus --cuda-device-only -S, as tests/test_build_cpu.py does).  The kernels of a tree are pooled by mangled
+name, so one that moved between units is compared with itself.  Per kernel the register and segment metadata must be equal and
+the instruction lines must be the same multiset (the scheduler may swap neighbours when a helper moves into a header, so not
+the same sequence).  A kernel that only the new tree has is listed as new with its metadata (a unit that gained a sweep: the
+kernels it had must still be the code they were); one that only the old tree has counts as a difference.  Exit status 1 if
+any kernel differs.
 """
 import argparse
 import collections
@@ -24,8 +26,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from physicl_amd import build  # noqa: E402
 
-UNITS = [os.path.basename(u["src"]) for u in build.ADDONS]
+CORE = os.path.basename(build.CORE["src"])
 META = ["vgpr_count", "sgpr_count", "group_segment_fixed_size", "private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count"]
+
+
+def units(tree):
+    return sorted(f for f in os.listdir(os.path.join(tree, "physicl_amd", "csrc")) if f.endswith(".hip") and f != CORE)
 
 
 def compile_unit(tree, unit, out):
@@ -36,7 +42,7 @@ def compile_unit(tree, unit, out):
 
 
 def kernels(asm):
-    """{kernel: (metadata, Counter of instruction lines)}"""
+    """{kernel: (metadata, Counter of instruction lines)} of one unit's assembly"""
     out = {}
     lines = asm.splitlines()
     # a kernel's metadata keys are sorted: .group_segment_fixed_size stands before its .name, the others behind it
@@ -50,6 +56,16 @@ def kernels(asm):
     return out
 
 
+def pooled(by_unit):
+    """{kernel: (unit, metadata, Counter)} over a tree's units; a kernel's mangled name stands in one unit only."""
+    out = {}
+    for unit, found in sorted(by_unit.items()):
+        for name, (meta, ins) in found.items():
+            assert name not in out, "%s is in %s and in %s" % (name, out[name][0], unit)
+            out[name] = (unit, meta, ins)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("old")
@@ -57,45 +73,45 @@ def main():
     ap.add_argument("--md", action="store_true", help="print a markdown table")
     a = ap.parse_args()
     with tempfile.TemporaryDirectory(prefix="pcl_cmp_") as work, ThreadPoolExecutor(max_workers=8) as pool:
-        jobs = {(side, u): pool.submit(compile_unit, tree, u, os.path.join(work, "%s_%s.s" % (side, u)))
-                for side, tree in (("old", a.old), ("new", a.new)) for u in UNITS}
-        asm = {k: kernels(j.result()) for k, j in jobs.items()}
+        jobs = {side: {u: pool.submit(compile_unit, tree, u, os.path.join(work, "%s_%s.s" % (side, u))) for u in units(tree)}
+                for side, tree in (("old", a.old), ("new", a.new))}
+        old, new = (pooled({u: kernels(j.result()) for u, j in jobs[side].items()}) for side in ("old", "new"))
     dem = lambda n: subprocess.run(["c++filt", n], capture_output=True, text=True).stdout.strip()  # noqa: E731
     dem_short = lambda n: re.sub(r"\(.*$", "", dem(n).replace("(anonymous namespace)::", "").replace("void ", ""))  # noqa: E731
     bad = 0
     if a.md:
         print("| unit | kernel | vgpr | sgpr | LDS | scratch | spills v/s | instructions | same metadata | same multiset |")
         print("|---|---|---|---|---|---|---|---|---|---|")
-    for u in UNITS:
-        old, new = asm[("old", u)], asm[("new", u)]
-        if set(old) - set(new):
-            bad += 1
-            print("%s: kernels of the old tree are missing: %s" % (u, sorted(set(old) - set(new))))
-        for name in sorted(set(new) - set(old)):
-            m1, i1 = new[name]
-            if a.md:
-                print("| %s | `%s` | %d | %d | %d | %d | %d/%d | new: %d | new | new |" % (
-                    u, dem_short(name), m1["vgpr_count"], m1["sgpr_count"], m1["group_segment_fixed_size"], m1["private_segment_fixed_size"],
-                    m1["vgpr_spill_count"], m1["sgpr_spill_count"], sum(i1.values())))
-            else:
-                print("%-18s %-44s %5d instructions  new: %s" % (u, dem_short(name), sum(i1.values()), m1))
-        for name in sorted(set(old) & set(new)):
-            (m0, i0), (m1, i1) = old[name], new[name]
-            same_m, same_i = m0 == m1, i0 == i1
-            bad += not (same_m and same_i)
-            if a.md:
-                print("| %s | `%s` | %d | %d | %d | %d | %d/%d | %d -> %d | %s | %s |" % (
-                    u, dem_short(name), m1["vgpr_count"], m1["sgpr_count"], m1["group_segment_fixed_size"], m1["private_segment_fixed_size"],
-                    m1["vgpr_spill_count"], m1["sgpr_spill_count"], sum(i0.values()), sum(i1.values()), "yes" if same_m else "NO",
-                    "yes" if same_i else "NO"))
-            else:
-                print("%-18s %-44s %5d instructions  metadata %s  multiset %s" % (u, dem_short(name), sum(i1.values()),
-                                                                                "same" if same_m else "DIFFERS", "same" if same_i else "DIFFERS"))
-            if not same_m:
-                print("    metadata: %s" % {k: (m0[k], m1[k]) for k in META if m0[k] != m1[k]})
-            if not same_i:
-                for line, n in sorted(((i0 - i1) + (i1 - i0)).items()):
-                    print("    %+d  %s" % (i1[line] - i0[line], line))
+    if set(old) - set(new):
+        bad += 1
+        print("kernels of the old tree are missing: %s" % sorted(set(old) - set(new)))
+    for name in sorted(set(new) - set(old), key=lambda k: (new[k][0], k)):
+        u, m1, i1 = new[name]
+        if a.md:
+            print("| %s | `%s` | %d | %d | %d | %d | %d/%d | new: %d | new | new |" % (
+                u, dem_short(name), m1["vgpr_count"], m1["sgpr_count"], m1["group_segment_fixed_size"], m1["private_segment_fixed_size"],
+                m1["vgpr_spill_count"], m1["sgpr_spill_count"], sum(i1.values())))
+        else:
+            print("%-18s %-44s %5d instructions  new: %s" % (u, dem_short(name), sum(i1.values()), m1))
+    for name in sorted(set(old) & set(new), key=lambda k: (new[k][0], k)):
+        (u0, m0, i0), (u, m1, i1) = old[name], new[name]
+        same_m, same_i = m0 == m1, i0 == i1
+        bad += not (same_m and same_i)
+        if a.md:
+            print("| %s | `%s` | %d | %d | %d | %d | %d/%d | %d -> %d | %s | %s |" % (
+                u, dem_short(name), m1["vgpr_count"], m1["sgpr_count"], m1["group_segment_fixed_size"], m1["private_segment_fixed_size"],
+                m1["vgpr_spill_count"], m1["sgpr_spill_count"], sum(i0.values()), sum(i1.values()), "yes" if same_m else "NO",
+                "yes" if same_i else "NO"))
+        else:
+            print("%-18s %-44s %5d instructions  metadata %s  multiset %s" % (u, dem_short(name), sum(i1.values()),
+                                                                            "same" if same_m else "DIFFERS", "same" if same_i else "DIFFERS"))
+        if u0 != u:
+            print("    moved here from %s" % u0)
+        if not same_m:
+            print("    metadata: %s" % {k: (m0[k], m1[k]) for k in META if m0[k] != m1[k]})
+        if not same_i:
+            for line, n in sorted(((i0 - i1) + (i1 - i0)).items()):
+                print("    %+d  %s" % (i1[line] - i0[line], line))
     return 1 if bad else 0
 
 
