@@ -5,6 +5,7 @@ examples (n(r) = 2.5e25 m^-3 * exp(-(|r| - 6371 km) / 8.6 km)) with photons that
     python examples/point_source_atmosphere.py [n_photons] [passes] [--cone | --beam-down | --default] [--profile] [--shells]
                                                [--ground [ALBEDO]] [--phase rayleigh | hg:G | isotropic] [--omega0 W | W1,W2,...]
                                                [--cloud LO,HI[,G]] [--recycle [TOP]] [--gas LO,HI,K[,EMIN,EMAX]] [--blue-sky]
+                                               [--camera X,Y,Z:NX,NY,NZ:RADIUS:FOV_DEG:PIXELS]
 
 default: a point source at (6371 km, 0, 0) emitting isotropically; ``--cone``: a 0.3 rad cone pointing up (+x) from a 1 km disc;
 ``--beam-down``: a 10 km gaussian beam entering from 100 km above the surface along -x; ``--default``: the same step list from
@@ -42,6 +43,12 @@ coefficient per metre --, whether it scattered or not, and leaves it at rest.  W
 in that band are absorbed: the escaping spectrum gets a band.  One launch per light step; ``absorbed_by_cell`` summed over the
 passes is printed beside the shell counts.  ``--blue-sky`` makes the scatter step wavelength dependent (lambda**-4, scaled so that
 550 nm scatters as the grey atmosphere does); with a band the gas then asks for E in every pass, which drops that step's term cache.
+``--camera X,Y,Z:NX,NY,NZ:RADIUS:FOV_DEG:PIXELS`` puts an instrument into the scene: a DetectorMeasureStep, a disc of RADIUS metres about
+(X, Y, Z) (metres from the Earth's centre) whose normal (NX, NY, NZ) points from the detector into the scene, with a square field of
+view of FOV_DEG degrees to either side and PIXELS x PIXELS pixels, e.g. ``--camera 6471000,0,0:-1,0,0:20000:60:32`` looks straight down
+from 100 km above the source.  Every pass tallies the photons that went through the disc from the front, by the direction they came
+from; ``through`` and ``seen`` summed over the passes and a coarse text rendering of the exposure ``step.image`` are printed.  One launch
+per light step, as with ``--shells``.
 """
 import os
 import sys
@@ -94,6 +101,17 @@ if "--gas" in argv:
     gas = [float(x) for x in (argv.pop(at + 1) if at + 1 < len(argv) else "").split(",")]
     if len(gas) not in (3, 5) or not 0.0 <= gas[0] < gas[1] or not gas[2] >= 0.0 or (len(gas) == 5 and not gas[3] < gas[4]):
         sys.exit("--gas LO,HI,K[,EMIN,EMAX]: two altitudes in metres, 0 <= LO < HI, a coefficient per metre and optionally an energy band in joules")
+camera = None
+if "--camera" in argv:
+    at = argv.index("--camera")
+    try:
+        where, look, rest = (argv.pop(at + 1) if at + 1 < len(argv) else "").split(":", 2)
+        camera = dict(position=[float(x) for x in where.split(",")], normal=[float(x) for x in look.split(",")])
+        camera["radius"], fov_deg, pixels = (float(x) for x in rest.split(":"))
+        camera.update(fov=np.radians(fov_deg), pixels=(int(pixels), int(pixels)))
+    except ValueError:
+        sys.exit("--camera X,Y,Z:NX,NY,NZ:RADIUS:FOV_DEG:PIXELS: a position and a normal (metres, any length), a radius in metres, the half "
+                 "angle of the field of view in degrees and the pixels per side")
 CLOUD_WEIGHTS = [[1, 0], [0.1, 0.9], [1, 0]]                  # below the cloud, in it, above it: (Rayleigh, Henyey-Greenstein)
 args = [a for a in argv if not a.startswith("--")]
 n = int(float(args[0])) if len(args) > 0 else 100_000_000
@@ -146,7 +164,7 @@ def run(ground):
     sim.add_step(3, signs)
     shells = light.ScatterMeasureStep(None, True, [[R + 20e3, np.nan, np.nan], [np.nan, 0.0, np.nan]])   # 20 km up; the plane y = 0
     sim.add_step(4, shells)
-    profile = image = tally = floor = lamp = None
+    profile = image = tally = floor = lamp = eye = None
     if "--profile" in sys.argv:                                # behind the last light step: the 32-pass launches are kept
         profile = light.PositionGridMeasureStep(None, ("r",), [PROFILE_RADII], every=32)
         image = light.PositionGridMeasureStep(None, ("y", "z"), [np.linspace(-300e3, 300e3, 129)] * 2, every=32, measure_n=False)
@@ -155,6 +173,9 @@ def run(ground):
     if "--shells" in sys.argv:                                 # the ground and three altitudes, about the Earth's centre
         tally = light.ShellCrossingMeasureStep(None, SHELL_RADII, mu_bins=np.linspace(-1.0, 1.0, 11))
         sim.add_step(7, tally)
+    if camera is not None:                                     # before the ground, as the shells: it sees the incoming move
+        eye = light.DetectorMeasureStep(None, **camera)        # (a malformed camera is a ValueError here, before anything runs)
+        sim.add_step("camera", eye)
     if ground is not None:                                     # last in the pass: the tally before it sees the incoming move
         floor = light.SurfaceReflectStep(R, albedo=ground)
         sim.add_step(8, floor)
@@ -167,7 +188,7 @@ def run(ground):
     sim.join()
     if sim.error is not None:
         raise sim.error
-    return sim, signs, shells, profile, image, tally, floor, angles, medium, lamp, vapour
+    return sim, signs, shells, profile, image, tally, floor, angles, medium, lamp, vapour, eye
 
 
 bare_top = None
@@ -177,7 +198,7 @@ if albedo is not None and "--shells" in sys.argv:              # the same run wi
     print("without the ground: %d photons x %d steps in %.2f s" % (n, len(bare[0].ts), bare[0].run_time))
     bare[0].close(download=False)
     del bare
-sim, signs, shells, profile, image, tally, floor, angles, medium, lamp, vapour = run(albedo)
+sim, signs, shells, profile, image, tally, floor, angles, medium, lamp, vapour, eye = run(albedo)
 steps = len(sim.ts)
 print("source:", source)
 print("%d photons x %d steps in %.2f s  ->  %.3g particle-steps/s" % (n, steps, sim.run_time, n * steps / sim.run_time))
@@ -239,3 +260,14 @@ if lamp is not None:
     for k in range(every - 1, len(rate), every):                # the emission rate settling, pass by pass
         row = lamp.data[k]
         print("  pass %4d: emission rate %d per pass (%d at rest: the ground and the medium, %d through the top)" % (k + 1, rate[k], int(row[1]), int(row[2])))
+if eye is not None:
+    through, seen = (sum(int(row[k]) for row in eye.data) for k in (2, 3))
+    print("the camera at %s looking along %s (disc of %g m, +-%g degrees, %d x %d pixels): %d through, %d seen over %d passes" % (
+        eye.position.tolist(), eye.frame[2].round(3).tolist(), eye.radius, np.degrees(camera["fov"]), *camera["pixels"], through, seen, len(eye.data)))
+    img = eye.image[0]
+    rows, cols = min(img.shape[0], 16), min(img.shape[1], 32)   # a coarse rendering: at most 16 lines of 32 characters, each the sum of its pixels
+    coarse = np.array([[blk.sum() for blk in np.array_split(line, cols, axis=1)] for line in np.array_split(img, rows, axis=0)])
+    shades = " .:-=+*#%@"
+    for line in coarse[::-1]:                                   # e2 upwards
+        print("  |" + "".join(shades[0 if v == 0 else 1 + min(int(8 * v / max(coarse.max(), 1)), 8)] for v in line) + "|")
+    print("  %d photons in the image, %d pixels lit, brightest pixel %d" % (img.sum(), np.count_nonzero(img), img.max()))

@@ -632,6 +632,54 @@ int pcl_step_shell_crossings(pcl_ctx *ctx, int n_shells, const double *radii_hos
                              int64_t *counts_out_host,                      /* [2][n_shells]: outward, inward */
                              int64_t *E_hist_out_host, int64_t *mu_hist_out_host);   /* may be NULL with 0 bins */
 
+/* What a radiometer sees: a pinhole camera's image of the last move (DetectorMeasureStep).  The instrument is a disc of
+ * ``radius`` > 0 (finite, R2 = radius*radius finite, made on the host) about position_host (3 finite doubles) in the plane whose
+ * normal n points from the detector into the scene; frame_host holds the orthonormal frame e1, e2, n as nine finite doubles
+ * (e1 | e2 | n; the caller makes it, nothing is normalised here, n may not be zero).  In ONE read-only sweep of the resident
+ * store the particles that went through the disc from the front in their last move are counted, sorted by the direction they
+ * came from into nx x ny pixels and -- with bands -- by energy, as int64 cells that add across devices and ranks like every
+ * other counter row.  The other way to it is a download of r and dr (48 B per particle over the host link) and numpy, every pass.
+ * All arithmetic is fp64, unfused, in the order written; an fp32 store's values are widened first (exact).  There is no division,
+ * no square root and no transcendental function, so numpy restates every cell exactly.  Per slot, plain Objects included, m = dr:
+ *   a_k = r_k - p_k;  b_k = a_k - m_k (where the move began);
+ *   s_now = (a0*n0 + a1*n1) + a2*n2;  s_prev the same over b;
+ *   crossed  iff  s_prev > 0 and s_now <= 0      -- front to back; a particle that ends exactly on the plane has arrived, one
+ *                                                   that starts on it has not; NaN: neither.  As for the shells, only the end
+ *                                                   points of the move are looked at.
+ *   D = s_prev - s_now;  H_k = b_k*D + m_k*s_prev (the hit point times D);  hh = (H0*H0 + H1*H1) + H2*H2;  lim = R2*(D*D);
+ *   through  iff  crossed and hh <= lim and lim < inf                        -- the rim is inside.
+ *   wn = -((m0*n0 + m1*n1) + m2*n2);  ax = -((m0*e1_0 + m1*e1_1) + m2*e1_2);  ay the same with e2
+ *                                                -- the direction the photon came from, in gnomonic coordinates ax/wn, ay/wn;
+ *   seen  iff  through and wn > 0 and wn < inf and x_0*wn <= ax <= x_nx*wn and y_0*wn <= ay <= y_ny*wn.
+ *   column c  iff  x_c*wn <= ax < x_(c+1)*wn, the last one closed; the row the same from the y edges.  Rounded products are
+ *   monotone in the edge because wn > 0: a binary search with one multiply per probe.
+ * Without bands (n_E_bins == 0, E_edges_host is not looked at) every seen particle adds 1 to image[0][row][col].  With bands only
+ * a PHOTON (plain Objects carry no energy) with E_0 <= E <= E_nE adds, to image[band][row][col], the band as
+ * numpy.histogram(E, bins=E_edges) finds it; a plain Object, an energy outside the bands or NaN is seen and lands in no cell.
+ * counts_out_host = [through, seen]; image_out_host: max(n_E_bins, 1) * ny * nx cells, C order, the band slowest:
+ * sum(image) <= seen <= through.
+ * x_edges_host / y_edges_host / E_edges_host: n + 1 finite, strictly increasing doubles; nx, ny in 1..PCL_DETECTOR_MAX_PIXELS,
+ * n_E_bins in 0..PCL_DETECTOR_MAX_BANDS, max(n_E_bins, 1) * ny * nx at most PCL_DETECTOR_MAX_CELLS.  Only the three edge tables
+ * sit in LDS (at most 3 x 1025 doubles); the seen particles add to their cells with 64-bit atomics on the device -- an aperture is
+ * small, so they are few.
+ * PCL_ERR_ARG (a NULL pointer, a position, frame or radius that is not finite, a zero n, radius <= 0 or its square not finite,
+ * edges not finite or not strictly increasing, a pixel, band or cell count outside its limits) is returned before the store is
+ * looked at and before anything is written; PCL_ERR_STATE without a store; an empty store answers zeros without a launch.  Host
+ * pointers; one device allocation per call, handed back on every way out; synchronises once, with the one copy of the results.
+ * The store is seen dense with dr real (pcl_store_field_ptr); E is looked at only with bands: a wavelength-dependent scatter
+ * step that follows then rebuilds its wavelength-term cache -- one more sweep of E per pass, as after pcl_step_plane_spectra --,
+ * and a camera without bands costs that step nothing.  pcl_last_error() is generic for these two entry points, as for
+ * pcl_step_plane_spectra: they are compiled from physicl_amd/csrc/pcl_shell.hip on top of the functions above. */
+#define PCL_DETECTOR_MAX_PIXELS 1024      /* per image axis */
+#define PCL_DETECTOR_MAX_BANDS 1024
+#define PCL_DETECTOR_MAX_CELLS (1 << 20)  /* max(n_E_bins, 1) * ny * nx */
+int pcl_step_detector_image(pcl_ctx *ctx, const double *position_host,      /* 3 doubles: the aperture's centre */
+                            const double *frame_host,                       /* 9 doubles: e1 | e2 | n */
+                            double radius, const double *x_edges_host, int nx, const double *y_edges_host, int ny,
+                            const double *E_edges_host, int n_E_bins,       /* NULL, 0: no bands */
+                            int64_t *counts_out_host,                       /* [2]: through, seen */
+                            int64_t *image_out_host);                       /* [max(n_E_bins, 1)][ny][nx] */
+
 /* A reflecting sphere: the ground of a radial problem (SurfaceReflectStep).  Photons whose last move took them into the sphere
  * of ``radius`` > 0 (finite, R2 = radius*radius finite, made on the host) about center_host (3 finite doubles, NULL = the
  * origin) are put back in ONE sweep of the resident store: reflected where the move met the sphere, or -- with albedo < 1 --
@@ -960,6 +1008,11 @@ int pcl_group_step_position_grid(pcl_group *group, int n_axes, const int *coords
 int pcl_group_step_shell_crossings(pcl_group *group, int n_shells, const double *radii_host, const double *center_host,
                                    const double *E_edges_host, int n_E_bins, const double *mu_edges_host, int n_mu_bins,
                                    int64_t *counts_out_host, int64_t *E_hist_out_host, int64_t *mu_hist_out_host);
+/* pcl_step_detector_image on every shard (side by side), the two counts and the image summed over the group's devices; the
+ * arguments are checked once for the group, before any shard is asked */
+int pcl_group_step_detector_image(pcl_group *group, const double *position_host, const double *frame_host, double radius,
+                                  const double *x_edges_host, int nx, const double *y_edges_host, int ny, const double *E_edges_host,
+                                  int n_E_bins, int64_t *counts_out_host, int64_t *image_out_host);
 /* pcl_step_surface_reflect on every shard (side by side), the two counts summed over the group's devices; the arguments
  * are checked once for the group, before any shard is written */
 int pcl_group_step_surface_reflect(pcl_group *group, double radius, const double *center_host, double albedo, int mode, double c,

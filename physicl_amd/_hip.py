@@ -27,6 +27,7 @@ SRC_SPATIAL = {"point": 0, "disc": 1, "gaussian": 2}                         # P
 GRID_COORDS = {"x": 0, "y": 1, "z": 2, "r": 3}                               # PCL_GRID_X ... PCL_GRID_RADIUS
 GRID_MAX_AXES, GRID_MAX_BINS, GRID_MAX_CELLS = 3, 1024, 1 << 20
 SHELL_MAX_SHELLS, SHELL_MAX_BINS, SHELL_MAX_CELLS = 16, 1024, 8192              # PCL_SHELL_MAX_SHELLS ...
+DETECTOR_MAX_PIXELS, DETECTOR_MAX_BANDS, DETECTOR_MAX_CELLS = 1024, 1024, 1 << 20      # PCL_DETECTOR_MAX_PIXELS ...
 SURFACE_MODES = {"lambertian": 0, "specular": 1}                             # PCL_SURFACE_LAMBERTIAN, PCL_SURFACE_SPECULAR
 ABSORB_MAX_LAYERS, ABSORB_MAX_BINS, ABSORB_MAX_CELLS = 64, 1024, 12288           # PCL_ABSORB_MAX_LAYERS ...
 PHASE_FUNCTIONS = {"isotropic": 0, "hg": 1, "rayleigh": 2}                   # PCL_PHASE_ISOTROPIC, PCL_PHASE_HG, PCL_PHASE_RAYLEIGH
@@ -155,6 +156,7 @@ _PROTOTYPES = {
     "pcl_step_plane_spectra": [_vp, _vp, c_int, _vp, c_int, _vp, _vp],
     "pcl_step_position_grid": [_vp, c_int, _vp, _vp, _vp, _vp, _vp],
     "pcl_step_shell_crossings": [_vp, c_int, _vp, _vp, _vp, c_int, _vp, c_int, _vp, _vp, _vp],
+    "pcl_step_detector_image": [_vp, _vp, _vp, c_double, _vp, c_int, _vp, c_int, _vp, c_int, _vp, _vp],
     "pcl_step_surface_reflect": [_vp, c_double, _vp, c_double, c_int, c_double, c_uint64, c_uint32, _vp],
     "pcl_step_phase_redirect": [_vp, c_int, c_double, c_double, c_uint64, c_uint32, _vp],
     "pcl_step_absorb_scattered": [_vp, c_int, _vp, _vp, _vp, c_int, _vp, c_uint64, c_uint32, _vp, _vp],
@@ -187,6 +189,7 @@ _PROTOTYPES = {
     "pcl_group_apply_source": [_vp, _vp, c_double, c_uint64],
     "pcl_group_step_position_grid": [_vp, c_int, _vp, _vp, _vp, _vp, _vp],
     "pcl_group_step_shell_crossings": [_vp, c_int, _vp, _vp, _vp, c_int, _vp, c_int, _vp, _vp, _vp],
+    "pcl_group_step_detector_image": [_vp, _vp, _vp, c_double, _vp, c_int, _vp, c_int, _vp, c_int, _vp, _vp],
     "pcl_group_step_surface_reflect": [_vp, c_double, _vp, c_double, c_int, c_double, c_uint64, c_uint32, _vp],
     "pcl_group_step_phase_redirect": [_vp, c_int, c_double, c_double, c_uint64, c_uint32, _vp],
     "pcl_group_step_absorb_scattered": [_vp, c_int, _vp, _vp, _vp, c_int, _vp, c_uint64, c_uint32, _vp, _vp],
@@ -346,6 +349,21 @@ def _shells(entry, handle, radii, center=None, E_edges=None, mu_edges=None):
     check(entry(handle, S, ra.ctypes.data, ptr(ce), ptr(edges[0]), nb(edges[0]), ptr(edges[1]), nb(edges[1]), counts.ctypes.data,
                 ptr(hists[0]), ptr(hists[1])))
     return counts, hists[0], hists[1]
+
+
+def _detector(entry, handle, position, frame, radius, x_edges, y_edges, E_edges=None):
+    """One call of pcl_step_detector_image / pcl_group_step_detector_image: (counts int64[2] = [through, seen], image
+    int64[max(bands, 1), ny, nx]).  ``frame``: e1, e2, n as nine numbers ((3, 3), a row each); the edges go over as given."""
+    po = np.ascontiguousarray(position, dtype=np.float64).reshape(3)
+    fr = np.ascontiguousarray(frame, dtype=np.float64).reshape(9)
+    xe, ye = (np.ascontiguousarray(e, dtype=np.float64).reshape(-1) for e in (x_edges, y_edges))
+    ee = None if E_edges is None else np.ascontiguousarray(E_edges, dtype=np.float64).reshape(-1)
+    nx, ny, nE = len(xe) - 1, len(ye) - 1, 0 if ee is None else len(ee) - 1
+    counts = np.zeros(2, dtype=np.int64)
+    image = np.zeros((max(nE, 1), max(ny, 0), max(nx, 0)), dtype=np.int64)
+    check(entry(handle, po.ctypes.data, fr.ctypes.data, float(radius), xe.ctypes.data, nx, ye.ctypes.data, ny,
+                None if ee is None else ee.ctypes.data, nE, counts.ctypes.data, image.ctypes.data))
+    return counts, image
 
 
 def _surface(entry, handle, radius, center, albedo, mode, c, seed, n_pass):
@@ -1035,6 +1053,13 @@ class Device:
         ``mu_edges``: of the cosine between the move and the outward normal.  ShellCrossingMeasureStep."""
         return _shells(self.lib.pcl_step_shell_crossings, self.ctx, radii, center, E_edges, mu_edges)
 
+    def detector_image(self, position, frame, radius, x_edges, y_edges, E_edges=None):
+        """What went through the disc of ``radius`` about ``position`` from the front in the last move, every particle of the
+        store, in one sweep (pcl_step_detector_image): ``(counts int64[2] = [through, seen], image int64[max(bands, 1), ny,
+        nx])``.  ``frame``: the orthonormal e1, e2, n (n from the detector into the scene); ``x_edges``, ``y_edges``: pixel edges
+        in the tangent plane (the direction a photon came from, e1 and e2 over n); ``E_edges``: bands.  DetectorMeasureStep."""
+        return _detector(self.lib.pcl_step_detector_image, self.ctx, position, frame, radius, x_edges, y_edges, E_edges)
+
     def surface_reflect(self, radius, center=None, albedo=1.0, mode="lambertian", c=0.0, seed=0, n_pass=0):
         """The photons whose last move took them into the sphere of ``radius`` about ``center`` (None: the origin) are put
         back, in one sweep (pcl_step_surface_reflect): reflected at the hit point (``mode``: "lambertian" or "specular") with
@@ -1172,6 +1197,10 @@ class DeviceGroup:
     def shell_crossings(self, radii, center=None, E_edges=None, mu_edges=None):
         """``Device.shell_crossings`` summed over the group's contexts (pcl_group_step_shell_crossings)."""
         return _shells(self.lib.pcl_group_step_shell_crossings, self.g, radii, center, E_edges, mu_edges)
+
+    def detector_image(self, position, frame, radius, x_edges, y_edges, E_edges=None):
+        """``Device.detector_image`` summed over the group's contexts (pcl_group_step_detector_image)."""
+        return _detector(self.lib.pcl_group_step_detector_image, self.g, position, frame, radius, x_edges, y_edges, E_edges)
 
     def surface_reflect(self, radius, center=None, albedo=1.0, mode="lambertian", c=0.0, seed=0, n_pass=0):
         """``Device.surface_reflect`` on every context of the group, the counts summed (pcl_group_step_surface_reflect)."""

@@ -14,6 +14,17 @@
 //                          energy edges and W = s*|s| against w_b*D in the direction edges (LDS, binary searches, no square
 //                          root and no division) and add to workgroup-private uint32 histograms in LDS; a workgroup
 //                          flushes its non-zero cells with 64-bit atomics at the end.
+//
+// Beside it, the crossing tally of a finite instrument (DetectorMeasureStep): what went through a small oriented aperture in
+// the last move, sorted by the direction it came from into the pixels of a pinhole camera and -- when asked for -- by energy
+// into bands.
+//
+//   k_detector_image<T>    one grid-stride sweep of the tiled slab, the same 48 B per slot: a = r - p and b = a - dr against the
+//                          aperture's plane (front to back: s_prev > 0 >= s_now), the hit point times D against R*R*(D*D), the
+//                          direction the photon came from against the pixel edges times wn (LDS, binary searches; no division,
+//                          no square root); one ballot + popcount each for the two counts; the few lanes that are seen add to
+//                          their image cell with a 64-bit atomic straight on the device block -- an aperture is small, so there
+//                          is no histogram in LDS and no flush, and the image may be large.
 #include "pcl_sweep.h"
 
 namespace {
@@ -204,6 +215,169 @@ int group_shell_crossings(pcl_group *group, int n_shells, const double *radii_ho
     });
 }
 
+// ---------------------------------------------------------------------------------------------- the aperture's image
+template <typename T>
+struct detector_args {
+    const T *r[3], *dr[3];
+    const T *E;                  // NULL without bands
+    const unsigned char *kind;   // NULL: every particle is a photon
+    const double *tables;        // x edges (nx + 1) | y edges (ny + 1) | E edges (n_E + 1, if any), device
+    unsigned long long *out;     // through, seen | image [max(n_E, 1)][ny][nx], device, zeroed by the entry point
+    int64_t N, ts;               // particles, tile stride of the slab (elements)
+    int tile_log;                // log2 of the tile length
+    int nx, ny, n_E;
+    double p[3], e1[3], e2[3], n[3], R2;
+};
+
+template <typename T>
+__global__ void __launch_bounds__(kBlock) k_detector_image(detector_args<T> a) {
+    extern __shared__ double s_det[];                                  // the three edge tables, nothing else
+    const int nx = a.nx, ny = a.ny, nE = a.n_E;
+    const int n_tab = (nx + 1) + (ny + 1) + (nE ? nE + 1 : 0);
+    const double *s_x = s_det, *s_y = s_x + (nx + 1), *s_E = s_y + (ny + 1);
+    for (int k = threadIdx.x; k < n_tab; k += kBlock) s_det[k] = a.tables[k];
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    // whole waves run the same number of trips (the ballots below need every lane of the wave inside the loop)
+    const int64_t n_round = (a.N + 63) / 64 * 64;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n_round; i += stride) {
+        const bool in = i < a.N;
+        const int64_t ti = tile_index(i, a.tile_log, a.ts);
+        double d[3] = {0.0, 0.0, 0.0}, m[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            if (in) {
+                d[k] = (double)a.r[k][ti] - a.p[k];                    // fp32 widens exactly
+                m[k] = (double)a.dr[k][ti];
+            }
+        // unfused, in this order (the library is built with -ffp-contract=off)
+        const double b0 = d[0] - m[0], b1 = d[1] - m[1], b2 = d[2] - m[2];            // where the move began
+        const double s_now = (d[0] * a.n[0] + d[1] * a.n[1]) + d[2] * a.n[2];
+        const double s_prev = (b0 * a.n[0] + b1 * a.n[1]) + b2 * a.n[2];
+        const bool crossed = in && s_prev > 0.0 && s_now <= 0.0;       // front to back; ending on the plane: arrived (NaN: neither)
+        const double D = s_prev - s_now;
+        const double H0 = b0 * D + m[0] * s_prev, H1 = b1 * D + m[1] * s_prev, H2 = b2 * D + m[2] * s_prev;   // the hit point times D
+        const double hh = (H0 * H0 + H1 * H1) + H2 * H2, lim = a.R2 * (D * D);
+        const bool through = crossed && hh <= lim && lim < INFINITY;   // the rim is inside
+        const double wn = -((m[0] * a.n[0] + m[1] * a.n[1]) + m[2] * a.n[2]);
+        const double ax = -((m[0] * a.e1[0] + m[1] * a.e1[1]) + m[2] * a.e1[2]);
+        const double ay = -((m[0] * a.e2[0] + m[1] * a.e2[1]) + m[2] * a.e2[2]);
+        // the direction it came from, gnomonic: ax / wn, ay / wn inside the edges -- compared as ax against e * wn, wn > 0
+        const bool seen = through && wn > 0.0 && wn < INFINITY && s_x[0] * wn <= ax && ax <= s_x[nx] * wn && s_y[0] * wn <= ay &&
+                          ay <= s_y[ny] * wn;
+        const unsigned long long n_through = (unsigned long long)__popcll(__ballot(through));
+        const unsigned long long n_seen = (unsigned long long)__popcll(__ballot(seen));
+        if (lane == 0 && n_through) atomicAdd(&a.out[0], n_through);
+        if (lane == 0 && n_seen) atomicAdd(&a.out[1], n_seen);
+        if (!seen) continue;    // lanes that saw nothing wait at the loop's head: no ballot below this line
+        int band = 0;
+        if (nE) {
+            if (a.kind ? a.kind[i] == 0 : false) continue;             // plain Objects carry no energy: seen, in no cell
+            const double e = (double)a.E[ti];
+            if (!(e >= s_E[0] && e <= s_E[nE])) continue;              // NaN and under/overflow: seen, in no cell
+            band = bin_of(s_E, nE, e);
+        }
+        const int col = bin_of(s_x, nx, ax, wn), row = bin_of(s_y, ny, ay, wn);
+        // band, row and col come from bin_of alone, which answers [0, n - 1] for n bins (lo starts at 0 and only ever becomes a
+        // mid < n): the cell lies in [0, max(n_E, 1) * ny * nx), the block the entry point allocated behind the two counts
+        atomicAdd(&a.out[2 + ((size_t)band * ny + row) * nx + col], 1ull);
+    }
+}
+
+struct detector_spec { // a call's arguments, checked; what the kernel compares against
+    int nx = 0, ny = 0, n_E = 0;
+    double p[3], frame[9], R2 = 0.0;
+    std::vector<double> tables; // x edges | y edges | E edges
+    size_t image_cells() const { return (size_t)(n_E > 0 ? n_E : 1) * ny * nx; }
+    size_t cells() const { return 2 + image_cells(); }
+    spans out(int64_t *counts, int64_t *image) const { return {{counts, 2}, {image, image_cells()}}; }
+};
+
+// Everything PCL_ERR_ARG stands for except the NULL context; nothing is launched or written before this has passed.
+bool check_detector(const double *position, const double *frame, double radius, const double *x_edges, int nx, const double *y_edges,
+                    int ny, const double *E_edges, int n_E, const int64_t *counts_out, const int64_t *image_out, detector_spec &s) {
+    if (!position || !frame || !x_edges || !y_edges || !counts_out || !image_out) return false;
+    if (nx < 1 || nx > PCL_DETECTOR_MAX_PIXELS || ny < 1 || ny > PCL_DETECTOR_MAX_PIXELS) return false;
+    if (n_E < 0 || n_E > PCL_DETECTOR_MAX_BANDS || (n_E > 0 && !E_edges)) return false;
+    if ((int64_t)(n_E > 0 ? n_E : 1) * ny * nx > PCL_DETECTOR_MAX_CELLS) return false;
+    for (int k = 0; k < 3; ++k) {
+        if (!std::isfinite(position[k])) return false;
+        s.p[k] = position[k];
+    }
+    for (int k = 0; k < 9; ++k) {
+        if (!std::isfinite(frame[k])) return false;
+        s.frame[k] = frame[k];
+    }
+    if (frame[6] == 0.0 && frame[7] == 0.0 && frame[8] == 0.0) return false;      // a plane needs a normal
+    s.R2 = radius * radius;
+    if (!std::isfinite(radius) || !(radius > 0) || !std::isfinite(s.R2)) return false;
+    if (!check_edges(x_edges, nx, kEdgePlain, &s.tables) || !check_edges(y_edges, ny, kEdgePlain, &s.tables)) return false;
+    if (n_E > 0 && !check_edges(E_edges, n_E, kEdgePlain, &s.tables)) return false;
+    s.nx = nx; s.ny = ny; s.n_E = n_E;
+    return true;
+}
+
+template <typename T>
+int launch_detector(pcl_ctx *ctx, const store_view &v, const detector_spec &s, const void *E, const staged &st) {
+    detector_args<T> a{};
+    for (int k = 0; k < 3; ++k) {
+        void *r = nullptr, *dr = nullptr;
+        PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_R0 + k, &r));
+        PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_DR0 + k, &dr));
+        a.r[k] = static_cast<const T *>(r);
+        a.dr[k] = static_cast<const T *>(dr);
+        a.p[k] = s.p[k]; a.e1[k] = s.frame[k]; a.e2[k] = s.frame[3 + k]; a.n[k] = s.frame[6 + k];
+    }
+    a.E = static_cast<const T *>(E); a.kind = st.kind; a.tables = st.tables; a.out = st.out;
+    a.N = v.N; a.ts = v.ts; a.tile_log = v.tile_log;
+    a.nx = s.nx; a.ny = s.ny; a.n_E = s.n_E; a.R2 = s.R2;
+    const size_t lds = s.tables.size() * sizeof(double);               // at most 3 x 1025 doubles
+    const int64_t grid = balanced_grid(v.N, v.n_cu, resident_per_cu(lds));
+    hipLaunchKernelGGL(k_detector_image<T>, dim3((unsigned)grid), dim3(kBlock), lds, v.stream, a);
+    return hipGetLastError() == hipSuccess ? PCL_OK : PCL_ERR_HIP;
+}
+
+int detector_image(pcl_ctx *ctx, const double *position_host, const double *frame_host, double radius, const double *x_edges_host, int nx,
+                   const double *y_edges_host, int ny, const double *E_edges_host, int n_E_bins, int64_t *counts_out_host,
+                   int64_t *image_out_host) {
+    detector_spec s;
+    if (!ctx || !check_detector(position_host, frame_host, radius, x_edges_host, nx, y_edges_host, ny, E_edges_host, n_E_bins,
+                                counts_out_host, image_out_host, s))
+        return bad_argument(ctx);
+    // E is asked for only with bands: the pointer costs a wavelength-dependent scatter step its term cache.
+    const spans out = s.out(counts_out_host, image_out_host);
+    store_view v;
+    staged st(ctx);
+    void *E = nullptr;
+    PCL_SWEEP_TRY(open_store(ctx, PCL_R0, &v));
+    if (s.n_E) PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_E, &E));
+    if (v.N <= 0) {
+        zero_spans(out);
+        return PCL_OK;
+    }
+    // the kinds go along when energies are binned and the store holds a plain Object; nothing is drawn: no ids
+    PCL_SWEEP_TRY(stage(st, v, s.cells(), s.tables.data(), s.tables.size(), false, s.n_E > 0));
+    PCL_SWEEP_TRY(PCL_SWEEP_LAUNCH(v, launch_detector, ctx, v, s, E, st));
+    return fetch(st, out);
+}
+
+int group_detector_image(pcl_group *group, const double *position_host, const double *frame_host, double radius,
+                         const double *x_edges_host, int nx, const double *y_edges_host, int ny, const double *E_edges_host, int n_E_bins,
+                         int64_t *counts_out_host, int64_t *image_out_host) {
+    std::vector<pcl_ctx *> ctx;
+    PCL_SWEEP_TRY(shards_of(group, ctx));
+    const int n = (int)ctx.size();
+    detector_spec s;
+    if (n < 1 || !check_detector(position_host, frame_host, radius, x_edges_host, nx, y_edges_host, ny, E_edges_host, n_E_bins,
+                                 counts_out_host, image_out_host, s))
+        return bad_argument(n > 0 ? ctx[0] : nullptr);
+    return sum_shards(ctx, s.out(counts_out_host, image_out_host), [&](pcl_ctx *one, int64_t *p) {
+        return pcl_step_detector_image(one, position_host, frame_host, radius, x_edges_host, nx, y_edges_host, ny, E_edges_host, n_E_bins,
+                                       p, p + 2);
+    });
+}
+
 } // namespace
 
 extern "C" {
@@ -223,6 +397,24 @@ int pcl_group_step_shell_crossings(pcl_group *group, int n_shells, const double 
     return guarded([&] {
         return group_shell_crossings(group, n_shells, radii_host, center_host, E_edges_host, n_E_bins, mu_edges_host, n_mu_bins,
                                      counts_out_host, E_hist_out_host, mu_hist_out_host);
+    });
+}
+
+int pcl_step_detector_image(pcl_ctx *ctx, const double *position_host, const double *frame_host, double radius,
+                            const double *x_edges_host, int nx, const double *y_edges_host, int ny, const double *E_edges_host,
+                            int n_E_bins, int64_t *counts_out_host, int64_t *image_out_host) {
+    return guarded([&] {
+        return detector_image(ctx, position_host, frame_host, radius, x_edges_host, nx, y_edges_host, ny, E_edges_host, n_E_bins,
+                              counts_out_host, image_out_host);
+    });
+}
+
+int pcl_group_step_detector_image(pcl_group *group, const double *position_host, const double *frame_host, double radius,
+                                  const double *x_edges_host, int nx, const double *y_edges_host, int ny, const double *E_edges_host,
+                                  int n_E_bins, int64_t *counts_out_host, int64_t *image_out_host) {
+    return guarded([&] {
+        return group_detector_image(group, position_host, frame_host, radius, x_edges_host, nx, y_edges_host, ny, E_edges_host, n_E_bins,
+                                    counts_out_host, image_out_host);
     });
 }
 

@@ -685,6 +685,170 @@ class ShellCrossingMeasureStep(tally.TallyStep):
         return [np.array(side, dtype=np.int64) for x in parts if x is not None for side in (x[0], x[1])]
 
 
+# ---------------------------------------------------------------------------------------------- a detector
+def _check_detector(position, frame, radius, x_edges, y_edges, E_edges=None):
+    """(position, frame (3, 3): e1, e2, n, radius, x edges, y edges, band edges or None) of a detector as float64, or
+    ValueError for everything pcl_step_detector_image would refuse."""
+    from ._hip import DETECTOR_MAX_BANDS, DETECTOR_MAX_CELLS, DETECTOR_MAX_PIXELS     # (the header's limits: one place)
+    try:
+        position, frame = np.array(position, dtype=np.float64), np.array(frame, dtype=np.float64)
+        radius = float(radius)
+    except (TypeError, ValueError):
+        raise ValueError("position must be three numbers, frame nine (e1, e2, n) and radius one") from None
+    if position.shape != (3,) or not np.all(np.isfinite(position)):
+        raise ValueError("position must be three finite numbers, got %r" % (position,))
+    if frame.size != 9 or not np.all(np.isfinite(frame)):
+        raise ValueError("frame must be nine finite numbers (e1, e2, n), got %r" % (frame,))
+    frame = np.ascontiguousarray(frame.reshape(3, 3))
+    if not frame[2].any():
+        raise ValueError("frame: the normal n must not be zero")
+    with np.errstate(over="ignore"):
+        if not np.isfinite(radius) or not radius > 0 or not np.isfinite(radius * radius):
+            raise ValueError("radius must be finite and positive (its square finite, too), got %r" % radius)
+    x_edges = tally.check_edges("x_edges", x_edges, DETECTOR_MAX_PIXELS)
+    y_edges = tally.check_edges("y_edges", y_edges, DETECTOR_MAX_PIXELS)
+    E_edges = None if E_edges is None else tally.check_edges("E_bins", E_edges, DETECTOR_MAX_BANDS)
+    cells = (1 if E_edges is None else len(E_edges) - 1) * (len(y_edges) - 1) * (len(x_edges) - 1)
+    if cells > DETECTOR_MAX_CELLS:
+        raise ValueError("%d bands x %d x %d pixels are %d image cells, at most %d are supported"
+                         % (1 if E_edges is None else len(E_edges) - 1, len(y_edges) - 1, len(x_edges) - 1, cells, DETECTOR_MAX_CELLS))
+    return np.ascontiguousarray(position), frame, radius, x_edges, y_edges, E_edges
+
+
+def _along(a, u):
+    """(a0*u0 + a1*u1) + a2*u2 per row of ``a`` (n, 3) with the vector ``u``: the device's order, one rounding each."""
+    return (a[:, 0] * u[0] + a[:, 1] * u[1]) + a[:, 2] * u[2]
+
+
+def _detector_image(r, dr, E, photon, position, frame, radius, x_edges, y_edges, E_edges=None):
+    """What pcl_step_detector_image answers, from (n, 3) float64 positions and last moves, the energies and who is a photon,
+    with numpy -- every operation the device's operation, one rounding each (include/physicl_hip.h):
+    (counts int64[2] = [through, seen], image int64[max(bands, 1), ny, nx])."""
+    r, m = np.asarray(r, dtype=np.float64).reshape(-1, 3), np.asarray(dr, dtype=np.float64).reshape(-1, 3)
+    e1, e2, n = np.asarray(frame, dtype=np.float64).reshape(3, 3)
+    xe, ye = np.asarray(x_edges, dtype=np.float64), np.asarray(y_edges, dtype=np.float64)
+    R2 = np.float64(radius) * np.float64(radius)
+    with np.errstate(invalid="ignore", over="ignore"):
+        a = r - np.asarray(position, dtype=np.float64)
+        b = a - m                                                 # where the move began
+        s_now, s_prev = _along(a, n), _along(b, n)
+        crossed = (s_prev > 0) & (s_now <= 0)                     # front to back; on the plane at the end: arrived.  NaN: neither
+        D = s_prev - s_now
+        H = b * D[:, None] + m * s_prev[:, None]                  # the hit point times D
+        hh = (H[:, 0] * H[:, 0] + H[:, 1] * H[:, 1]) + H[:, 2] * H[:, 2]
+        lim = R2 * (D * D)
+        through = crossed & (hh <= lim) & (lim < np.inf)          # the rim is inside
+        wn, ax, ay = -_along(m, n), -_along(m, e1), -_along(m, e2)   # the direction it came from: ax / wn, ay / wn
+        seen = through & (wn > 0) & (wn < np.inf) & (xe[0] * wn <= ax) & (ax <= xe[-1] * wn) & (ye[0] * wn <= ay) & (ay <= ye[-1] * wn)
+    counts = np.array([np.count_nonzero(through), np.count_nonzero(seen)], dtype=np.int64)
+    hit = np.flatnonzero(seen)                                    # the image looks at these only: an aperture is small
+    nx, ny, nE = len(xe) - 1, len(ye) - 1, 0 if E_edges is None else len(E_edges) - 1
+    with np.errstate(over="ignore"):                              # e_b*wn <= ax < e_(b+1)*wn, the last bin closed; the rounded products are monotone in b
+        col = np.clip((xe[None, :-1] * wn[hit, None] <= ax[hit, None]).sum(axis=1) - 1, 0, nx - 1)
+        row = np.clip((ye[None, :-1] * wn[hit, None] <= ay[hit, None]).sum(axis=1) - 1, 0, ny - 1)
+    band = np.zeros(len(hit), dtype=np.int64)
+    if nE:                                                        # numpy.histogram's bins; what is no photon or outside the bands: in no cell
+        e, v = np.asarray(E_edges, dtype=np.float64), np.asarray(E, dtype=np.float64).reshape(-1)[hit]
+        with np.errstate(invalid="ignore"):
+            ok = (v >= e[0]) & (v <= e[-1]) & np.asarray(photon, dtype=bool).reshape(-1)[hit]
+        band = np.clip(np.searchsorted(e, v, side="right") - 1, 0, nE - 1)
+        col, row, band = col[ok], row[ok], band[ok]
+    cells = max(nE, 1) * ny * nx
+    image = np.bincount((band * ny + row) * nx + col, minlength=cells)[:cells].astype(np.int64).reshape(max(nE, 1), ny, nx)
+    return counts, image
+
+
+def _detector_frame(normal, up=None):
+    """The camera's orthonormal frame (3, 3): e1, e2, n -- ``n = normal / |normal|`` (from the detector into the scene), e1 the
+    part of ``up`` at a right angle to n, normalised (default: the coordinate axis least aligned with n), ``e2 = n x e1``."""
+    try:
+        n = np.array(normal, dtype=np.float64)
+        u = None if up is None else np.array(up, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("normal (and up) must be three numbers") from None
+    if n.shape != (3,) or not np.all(np.isfinite(n)) or not n.any() or not np.isfinite(np_lin.norm(n)) or np_lin.norm(n) == 0:
+        raise ValueError("normal must be three finite numbers, not all zero, got %r" % (n,))
+    n = n / np_lin.norm(n)
+    if u is None:
+        u = np.zeros(3)
+        u[int(np.argmin(np.abs(n)))] = 1.0
+    if u.shape != (3,) or not np.all(np.isfinite(u)):
+        raise ValueError("up must be three finite numbers, got %r" % (u,))
+    e1 = u - np.dot(u, n) * n
+    length = np_lin.norm(e1)
+    if not np.isfinite(length) or not length > 1e-8 * max(np_lin.norm(u), np.finfo(np.float64).tiny):
+        raise ValueError("up must not be parallel to normal (or zero), got up %r for normal %r" % (u, n))
+    e1 = e1 / length
+    return np.ascontiguousarray(np.stack([e1, np.cross(n, e1), n]))
+
+
+class DetectorMeasureStep(tally.TallyStep):
+    """What a radiometer at ``position`` looking along ``normal`` sees (not in the reference): a pinhole camera.  The
+    instrument is a disc of ``radius`` (code units) about ``position`` whose ``normal`` points from the detector into the scene.
+    Every run records the row ``[t, N, through, seen]`` (no ``N`` with ``measure_n=False``) -- ``through``: the particles whose
+    last move took them through the disc from the front, ``seen``: those of them that came from a direction inside the field of
+    view -- and, with ``frames=True``, the pass's own image behind it.  ``step.image``, int64 ``[max(bands, 1), ny, nx]``, is the
+    sum over all passes so far (an exposure); ``step.through`` and ``step.seen`` are the last pass's counts.
+
+    A pixel is a direction: a photon that moved by ``m`` came from ``-m``, in gnomonic (tangent-plane) coordinates ``(-m.e1) /
+    (-m.n)``, ``(-m.e2) / (-m.n)`` -- ``e1`` the part of ``up`` at a right angle to the normal (default: the coordinate axis least
+    aligned with it), ``e2 = n x e1``; ``step.frame`` holds ``e1, e2, n``.  ``pixels=(nx, ny)`` with ``fov=(half_x, half_y)`` --
+    half angles in radians inside (0, pi/2), one number for both, pi/4 without -- makes ``linspace(-tan h, tan h, n + 1)`` edges; ``x_edges`` /
+    ``y_edges`` given explicitly win.  With ``E_bins`` (band edges, in the unit E is stored in) only photons whose energy lies
+    inside the bands reach the image, one plane per band as ``numpy.histogram`` bins them; a plain ``Object`` or another energy
+    is ``seen`` and lands in no cell.  At most 1024 pixels per axis, 1024 bands and 2**20 cells.
+
+    A crossing is a change of side between the end points of the move (``s_prev > 0 >= s_now``, the signed distances from the
+    aperture's plane in float64), the hit point is where the straight move met the plane, and the rim belongs to the disc.  No
+    division and no square root is taken anywhere, so numpy restates every cell exactly (``light._detector_image``).
+
+    The tally is made on the device in one read-only sweep of the resident store (pcl_step_detector_image) and adds, so sharded
+    runs all-reduce ``[N, through, seen, image]`` in one collective per pass.  A flux needs every pass, which the
+    K-passes-per-launch kernels cannot carry: a loop with this step runs one launch per light step, as with
+    ``ShellCrossingMeasureStep``, and ``sim.launch_note`` says so.  E is asked for only with bands."""
+    _fuse_role = None
+    _NOTE = "one launch per light step: a DetectorMeasureStep tallies the last move of every pass, which the " \
+            "K-passes-per-launch kernels cannot carry"
+
+    def __init__(self, out_fn, position, normal, radius, pixels=(64, 64), fov=None, x_edges=None, y_edges=None, up=None, E_bins=None,
+                 frames=False, measure_n=True):
+        MeasureStep.__init__(self, out_fn)
+        frame = _detector_frame(normal, up)
+        if x_edges is None or y_edges is None:
+            try:
+                nx, ny = (int(k) for k in pixels)
+                half = np.broadcast_to(np.array(np.pi / 4 if fov is None else fov, dtype=np.float64), (2,))
+            except (TypeError, ValueError):
+                raise ValueError("pixels must be two integers (nx, ny) and fov one or two half angles in radians") from None
+            if nx < 1 or ny < 1 or not np.all((half > 0) & (half < np.pi / 2)):       # (False for NaN as well)
+                raise ValueError("pixels must be positive and fov half angles inside (0, pi/2), got %r and %r" % (pixels, fov))
+            x_edges = np.linspace(-np.tan(half[0]), np.tan(half[0]), nx + 1) if x_edges is None else x_edges
+            y_edges = np.linspace(-np.tan(half[1]), np.tan(half[1]), ny + 1) if y_edges is None else y_edges
+        self.position, self.frame, self.radius, self.x_edges, self.y_edges, self.E_bins = _check_detector(
+            position, frame, radius, x_edges, y_edges, E_bins)
+        self.frames, self.measure_n = bool(frames), measure_n
+        self.image = np.zeros((1 if self.E_bins is None else len(self.E_bins) - 1, len(self.y_edges) - 1, len(self.x_edges) - 1), dtype=np.int64)
+        self.through = self.seen = 0
+
+    def _device_run(self, sim):
+        if getattr(sim, "launch_note", self._NOTE) is None and sim._k_wanted() > 1:      # (a device run only: the host path says nothing)
+            sim.launch_note = self._NOTE
+        tally.TallyStep._device_run(self, sim)
+
+    def _sweep(self, dev):
+        return list(dev.detector_image(self.position, self.frame, self.radius, self.x_edges, self.y_edges, self.E_bins))
+
+    def _host_parts(self, objs):
+        return list(_detector_image(tally.vec3(objs, "r"), tally.vec3(objs, "dr"), *tally.photon_energies(objs, PhotonObject),
+                                    self.position, self.frame, self.radius, self.x_edges, self.y_edges, self.E_bins))
+
+    def _cells(self, parts):                           # (counts, image), global: the exposure goes on
+        counts, image = parts
+        self.through, self.seen = int(counts[0]), int(counts[1])
+        self.image = self.image + np.asarray(image, dtype=np.int64).reshape(self.image.shape)
+        return [self.through, self.seen] + ([np.array(image, dtype=np.int64).reshape(self.image.shape)] if self.frames else [])
+
+
 # ---------------------------------------------------------------------------------------------- surface reflection
 _U32 = np.uint64(0xFFFFFFFF)
 
