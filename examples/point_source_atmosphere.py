@@ -5,6 +5,7 @@ examples (n(r) = 2.5e25 m^-3 * exp(-(|r| - 6371 km) / 8.6 km)) with photons that
     python examples/point_source_atmosphere.py [n_photons] [passes] [--cone | --beam-down | --default] [--profile] [--shells]
                                                [--ground [ALBEDO]] [--phase rayleigh | hg:G | isotropic] [--omega0 W | W1,W2,...]
                                                [--cloud LO,HI[,G]] [--recycle [TOP]] [--gas LO,HI,K[,EMIN,EMAX]] [--blue-sky]
+                                               [--reemit [TG[,TA]]]
                                                [--camera X,Y,Z:NX,NY,NZ:RADIUS:FOV_DEG:PIXELS]
 
 default: a point source at (6371 km, 0, 0) emitting isotropically; ``--cone``: a 0.3 rad cone pointing up (+x) from a 1 km disc;
@@ -43,6 +44,15 @@ coefficient per metre --, whether it scattered or not, and leaves it at rest.  W
 in that band are absorbed: the escaping spectrum gets a band.  One launch per light step; ``absorbed_by_cell`` summed over the
 passes is printed beside the shell counts.  ``--blue-sky`` makes the scatter step wavelength dependent (lambda**-4, scaled so that
 550 nm scatters as the grey atmosphere does); with a band the gas then asks for E in every pass, which drops that step's term cache.
+``--reemit [TG[,TA]]`` (kelvin, default 288,220) lets what was absorbed radiate again from where it was absorbed: a ReemissionStep behind
+the ground and before the lamp of ``--recycle``.  The ground parks the photons it absorbs on its sphere up to rounding, so it gets a
+thin shell of its own, R (1 - 1e-6) .. R (1 + 1e-6) -- wide enough for an fp32 store --, which emits cosine-weighted about the local
+vertical (lambertian) from a Planck table of the temperature TG between 3 and 100 micrometres; the gas between it and 100 km (what
+``--gas`` or ``--omega0`` absorbed there) re-emits isotropically from a table of TA.  ``parked``, ``reemitted`` and ``by_layer`` summed
+over the passes are printed beside the shell counts, and a ShellCrossingMeasureStep with one energy bin over the two tables counts the
+infrared photons through the ground's sphere: outward the ground's own glow (of the photons it parked a rounding below the sphere),
+inward what the gas sends back down -- the greenhouse return flux, which no run without the option has: no photon of the source is
+that red.  Try ``--ground 0.3 --gas 0,50000,2e-5 --reemit``.  One launch per light step.
 ``--camera X,Y,Z:NX,NY,NZ:RADIUS:FOV_DEG:PIXELS`` puts an instrument into the scene: a DetectorMeasureStep, a disc of RADIUS metres about
 (X, Y, Z) (metres from the Earth's centre) whose normal (NX, NY, NZ) points from the detector into the scene, with a square field of
 view of FOV_DEG degrees to either side and PIXELS x PIXELS pixels, e.g. ``--camera 6471000,0,0:-1,0,0:20000:60:32`` looks straight down
@@ -101,6 +111,15 @@ if "--gas" in argv:
     gas = [float(x) for x in (argv.pop(at + 1) if at + 1 < len(argv) else "").split(",")]
     if len(gas) not in (3, 5) or not 0.0 <= gas[0] < gas[1] or not gas[2] >= 0.0 or (len(gas) == 5 and not gas[3] < gas[4]):
         sys.exit("--gas LO,HI,K[,EMIN,EMAX]: two altitudes in metres, 0 <= LO < HI, a coefficient per metre and optionally an energy band in joules")
+reemit = None
+if "--reemit" in argv:
+    at = argv.index("--reemit")
+    reemit = [288.0, 220.0]
+    if at + 1 < len(argv) and not argv[at + 1].startswith("--"):
+        given = [float(x) for x in argv.pop(at + 1).split(",")]
+        reemit[:len(given)] = given
+    if len(reemit) != 2 or not min(reemit) > 0.0:
+        sys.exit("--reemit [TG[,TA]]: the temperatures of the ground and of the gas in kelvin")
 camera = None
 if "--camera" in argv:
     at = argv.index("--camera")
@@ -176,9 +195,22 @@ def run(ground):
     if camera is not None:                                     # before the ground, as the shells: it sees the incoming move
         eye = light.DetectorMeasureStep(None, **camera)        # (a malformed camera is a ValueError here, before anything runs)
         sim.add_step("camera", eye)
+    glow = red = None
+    if reemit is not None:                                     # Planck tables between 3 and 100 micrometres: the ground's, the gas's
+        infrared = [light.generate_photons_bulk(1, min=light.E_from_wavelength(100e-6), max=light.E_from_wavelength(3e-6), T=T, bins=256)
+                    for T in reemit]
+        grid = np.concatenate([np.asarray(batch.table[1], dtype=np.float64) for batch in infrared])
+        # who crosses the ground's sphere with a re-emitted energy (no photon of the source is that red); before the ground, as the shells
+        red = light.ShellCrossingMeasureStep(None, [R], E_bins=[0.999 * grid.min(), 1.001 * grid.max()], measure_n=False)
+        sim.add_step("infrared", red)
     if ground is not None:                                     # last in the pass: the tally before it sees the incoming move
         floor = light.SurfaceReflectStep(R, albedo=ground)
         sim.add_step(8, floor)
+    if reemit is not None:                                     # behind everything that parks photons, before the lamp
+        # the ground parks photons on the sphere up to rounding: a thin shell of its own, wide enough for an fp32 store
+        glow = light.ReemissionStep(infrared, edges=[R * (1.0 - 1e-6), R * (1.0 + 1e-6), R + 100e3], angular=["lambertian", "isotropic"])
+        glow.tally = red
+        sim.add_step("reemit", glow)
     if recycle_top is not None:                                # the very last: behind the ground
         lamp = light.RecycleStep(source, top=R + recycle_top)
         sim.add_step(9, lamp)
@@ -188,7 +220,7 @@ def run(ground):
     sim.join()
     if sim.error is not None:
         raise sim.error
-    return sim, signs, shells, profile, image, tally, floor, angles, medium, lamp, vapour, eye
+    return sim, signs, shells, profile, image, tally, floor, angles, medium, lamp, vapour, eye, glow
 
 
 bare_top = None
@@ -198,7 +230,7 @@ if albedo is not None and "--shells" in sys.argv:              # the same run wi
     print("without the ground: %d photons x %d steps in %.2f s" % (n, len(bare[0].ts), bare[0].run_time))
     bare[0].close(download=False)
     del bare
-sim, signs, shells, profile, image, tally, floor, angles, medium, lamp, vapour, eye = run(albedo)
+sim, signs, shells, profile, image, tally, floor, angles, medium, lamp, vapour, eye, glow = run(albedo)
 steps = len(sim.ts)
 print("source:", source)
 print("%d photons x %d steps in %.2f s  ->  %.3g particle-steps/s" % (n, steps, sim.run_time, n * steps / sim.run_time))
@@ -252,6 +284,14 @@ if vapour is not None:
     if tally is not None:
         print("  beside it: %d left through the top of the atmosphere (100 km)%s" % (
             int(sum(row[2][3] for row in tally.data)), "" if floor is None else ", %d absorbed by the ground" % sum(int(row[2]) for row in floor.data)))
+if glow is not None:
+    by_layer = np.sum([row[3] for row in glow.data], axis=0)
+    print("re-emission in place (the ground at %g K, lambertian; the gas up to 100 km at %g K, isotropic): %d parked, %d re-emitted over %d passes; "
+          "by_layer [ground, gas] %s" % (reemit[0], reemit[1], sum(int(row[1]) for row in glow.data), sum(int(row[2]) for row in glow.data),
+                                         len(glow.data), by_layer.tolist()))
+    print("  infrared photons through the ground's sphere: %d outward (the ground's glow, where it parked a rounding below the sphere), %d inward (the return "
+          "flux of the gas)" % (
+        sum(int(row[3][0][0]) for row in glow.tally.data), sum(int(row[4][0][0]) for row in glow.tally.data)))
 if lamp is not None:
     rate = [int(row[1]) + int(row[2]) for row in lamp.data]
     print("a continuous source (photons at rest or above %g km go back to it): %d re-emitted over %d passes, the population stays at %d" % (

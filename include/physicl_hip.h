@@ -948,6 +948,62 @@ int pcl_step_absorb_path(pcl_ctx *ctx, int n_layers, int n_E_bins, const double 
                          const double *center_host, const double *E_edges_host, uint64_t seed, uint32_t pass,
                          int64_t *counts_out_host /* [2]: exposed, absorbed */, int64_t *cells_out_host /* [L' * B'] */);
 
+/* Re-emission in place (ReemissionStep): what the ground or the medium has absorbed is radiated again from where it was absorbed.
+ * Every sink of a pass (pcl_step_surface_reflect with an albedo, pcl_step_absorb_scattered, pcl_step_absorb_path) parks a photon
+ * at rest; called behind them and before pcl_step_recycle_spent (which then takes what this call left at rest), this call gives the
+ * parked photons a new direction -- and, with a table, a new energy -- from their own position, by a law, a spectrum and a yield
+ * that belong to the radial layer they are parked in, in ONE sweep of the resident store.  Nothing is removed; r, ids and kinds are
+ * never written.  All arithmetic is fp64, unfused, every operation rounded once, in the order written; an fp32 store's values are
+ * widened first (exact) and what is written is rounded once to the store's dtype.  L' = max(n_layers, 1).
+ *   rest    =  v0 == 0 and v1 == 0 and v2 == 0                  (-0.0 counts as 0; a NaN in v: moving).  A slot with v0 != 0 is
+ *              decided by v0 alone: it loads neither v1 nor v2, nor anything else.
+ *   n_layers == 0:  b = 0;  edges_host is ignored, and r is read only if that one layer is lambertian
+ *   n_layers = L >= 1:  d = r - center;  q = (d0*d0 + d1*d1) + d2*d2;  e2_k = e_k*e_k (made on the host);  inside iff e2_0 <= q and
+ *              q <= e2_L (NaN: not inside);  b = the layer with e2_b <= q < e2_(b+1), the last one closed (numpy.histogram);
+ *              no square root is taken -- the layer pcl_step_absorb_scattered finds
+ *   parked  =  rest and the particle is a photon (kind != 0) and it has a layer b
+ *   eta_b == 0:  nothing is drawn.
+ *   eta_b > 0:   u = u53(w0, w1) of the counter (id_lo, id_hi, pass, 18);  re-emitted iff u < eta_b           (eta_b == 1: every one)
+ *   direction:   (u_a, u_b) = (u53(w0, w1), u53(w2, w3)) of the counter (id_lo, id_hi, pass, 19)
+ *     isotropic:   w = (1, 0, 0);  mu = 1 - 2*u_a
+ *     lambertian:  d = r - center;  q as above;  s = sqrt(q);  w_k = d_k / s;  mu = sqrt(1 - u_a)       (about the local vertical)
+ *                  q == 0 or q not finite: the photon has no vertical; it is not re-emitted and is counted in parked only
+ *     e1, e2 = the frame about w, sc, ss of (mu, u_b) and the direction (sc*e1_k + ss*e2_k) + mu*w_k as written out for
+ *     pcl_step_surface_reflect (frame, polar, turned), the same sin / cos;  v_k = c * direction_k
+ *   energy (only if layer b has a table):  u = u53(w0, w1) of the counter (id_lo, id_hi, pass, 20);  E = grid_b[x] for the first x
+ *              with cdf_b[x] >= u -- pcl_step_recycle_spent's look-up, a binary search: compares only.  The new E does not look at
+ *              the old one.  Without a table a re-emitted photon keeps its E; if no layer has a table E is neither written nor
+ *              asked for (pcl_store_field_ptr): a wavelength-dependent scatter step keeps its lambda^-4 cache.
+ *   dr = 0;  dv = 0                    (later calls of the pass see a photon that has neither moved nor scattered)
+ * A particle that is not re-emitted is not written at all.  The Philox4x32-10 blocks have the key (seed_lo, seed_hi), u53 of
+ * pcl_store_apply_source; ``pass`` is the caller's own counter, so a photon that stays parked (eta_b < 1) draws again in the next
+ * call: a lifetime of dt / eta_b.  The words 18, 19 and 20 are used by nothing else (scatter kernels 0 and 1, fill and source 2..5,
+ * pcl_step_surface_reflect 8 and 9, pcl_step_phase_redirect 10 and 11, pcl_step_absorb_scattered 12, pcl_step_phase_layered 13,
+ * pcl_step_recycle_spent 14, 15 and 16, pcl_step_absorb_path 17: 0-5 and 8-17 are taken), so every other step draws what it drew, and
+ * a photon is re-emitted the same way however the run is sharded.
+ * edges_host: L + 1 radii as for pcl_step_absorb_scattered, 1 <= L <= PCL_REEMIT_MAX_LAYERS.  center_host: 3 finite doubles, NULL =
+ * the origin.  eta_host: L' doubles in [0, 1].  lambertian_host: L' ints, 0 (isotropic) or 1.  table_offsets_host: L' + 1 ints, the
+ * first 0, not decreasing: layer b's table is [offsets[b], offsets[b + 1]) of cdf_host and grid_host, equal neighbours: no table; a
+ * table has at most PCL_REEMIT_MAX_BINS entries, all together at most PCL_REEMIT_MAX_TOTAL_BINS (32 KiB of LDS); each table's cdf
+ * does not decrease and ends in exactly 1, the grid is finite.  ``c`` = the speed of light in code units.
+ * counts_out_host[0] = photons parked (at rest, with a layer), [1] = re-emitted, [2 + b] = re-emitted from layer b, by this call.
+ * A store that is not uniform costs the host traffic it costs pcl_step_surface_reflect; the ids go along only if some eta > 0.
+ * PCL_ERR_ARG (NULL eta, flags, offsets or counts, L outside 0 .. PCL_REEMIT_MAX_LAYERS, an eta outside [0, 1] or NaN, a flag that
+ * is neither 0 nor 1, offsets that do not start at 0, decrease or exceed a limit, NULL tables with entries, a cdf that decreases or
+ * does not end in 1, a grid that is not finite, NULL or bad edges with L > 0, a centre or c that is not finite) is returned before
+ * the store is looked at, and nothing is launched or written; PCL_ERR_STATE without a store; an empty store answers zeros without a
+ * launch.  Host pointers; one device allocation per call, handed back on every way out; synchronises once, with the copy of the
+ * counts.  pcl_last_error() is generic, as for pcl_step_surface_reflect, whose source file these two entry points share
+ * (physicl_amd/csrc/pcl_surface.hip). */
+#define PCL_REEMIT_MAX_LAYERS 64
+#define PCL_REEMIT_MAX_BINS 1024
+#define PCL_REEMIT_MAX_TOTAL_BINS 2048
+int pcl_step_reemit_parked(pcl_ctx *ctx, int n_layers, const double *edges_host, const double *center_host,
+                           const double *eta_host /* [L'] */, const int *lambertian_host /* [L'] */,
+                           const int *table_offsets_host /* [L' + 1], equal neighbours: no table */, const double *cdf_host,
+                           const double *grid_host, double c, uint64_t seed, uint32_t pass,
+                           int64_t *counts_out_host /* [2 + L']: parked, re-emitted, by layer */);
+
 /* ---- Device groups: several GPUs from ONE process ---------------------------------------------------------------
  * The reference is a single process with one simulation thread (physicl/__init__.py:400-432, 501-524); this is how
  * a host written against this ABI uses a node's GPUs the same way, without one process per GPU.  A group owns one
@@ -1042,6 +1098,12 @@ int pcl_group_step_recycle_spent(pcl_group *group, const pcl_source *src, double
 int pcl_group_step_absorb_path(pcl_group *group, int n_layers, int n_E_bins, const double *p_host, const double *edges_host,
                                const double *center_host, const double *E_edges_host, uint64_t seed, uint32_t pass,
                                int64_t *counts_out_host, int64_t *cells_out_host);
+/* pcl_step_reemit_parked on every shard (side by side), the 2 + L' counts summed over the group's devices; the arguments are
+ * checked once for the group, before any shard is written (ids are global: the same photons are re-emitted the same way) */
+int pcl_group_step_reemit_parked(pcl_group *group, int n_layers, const double *edges_host, const double *center_host,
+                                 const double *eta_host, const int *lambertian_host, const int *table_offsets_host,
+                                 const double *cdf_host, const double *grid_host, double c, uint64_t seed, uint32_t pass,
+                                 int64_t *counts_out_host);
 
 /* ---------------------------------------------------------------- the counters' collective (one process per GPU)
  * The path shards by global index with no data-path exchange; the only global quantities are the int64

@@ -35,6 +35,8 @@ PHASE_TABLE = 3                                                              # P
 LPHASE_MAX_LAWS, LPHASE_MAX_LAYERS, LPHASE_MAX_NODES, LPHASE_MAX_TOTAL_NODES = 8, 64, 1024, 2048       # PCL_LPHASE_MAX_LAWS ...
 RECYCLE_MAX_BINS = 1024                                                      # PCL_RECYCLE_MAX_BINS: bins of a RecycleStep's spectrum
 PATH_ABSORB_MAX_LAYERS, PATH_ABSORB_MAX_BANDS, PATH_ABSORB_MAX_CELLS = 64, 1024, 4096          # PCL_PATH_ABSORB_MAX_LAYERS ...
+REEMIT_MAX_LAYERS, REEMIT_MAX_BINS, REEMIT_MAX_TOTAL_BINS = 64, 1024, 2048                      # PCL_REEMIT_MAX_LAYERS ...
+REEMIT_LAWS = {"isotropic": 0, "lambertian": 1}                              # the flags of pcl_step_reemit_parked's lambertian_host
 PROF_NEWTON, PROF_SCATTER, PROF_DELETE_MASK, PROF_COMPACT, PROF_COUNTERS, PROF_FUSED, PROF_MULTI, PROF_ONEPASS, \
     PROF_DELETE_AHEAD = range(9)
 PROF_NAMES = {PROF_NEWTON: "k_newton", PROF_SCATTER: "k_scatter", PROF_DELETE_MASK: "k_delete_mask",
@@ -163,6 +165,7 @@ _PROTOTYPES = {
     "pcl_step_phase_layered": [_vp, c_int, _vp, _vp, _vp, _vp, _vp, c_int, _vp, _vp, _vp, c_double, c_uint64, c_uint32, _vp],
     "pcl_step_recycle_spent": [_vp, _vp, c_double, c_int, c_double, _vp, c_int, _vp, _vp, c_uint64, c_uint32, _vp],
     "pcl_step_absorb_path": [_vp, c_int, c_int, _vp, _vp, _vp, _vp, c_uint64, c_uint32, _vp, _vp],
+    "pcl_step_reemit_parked": [_vp, c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, c_double, c_uint64, c_uint32, _vp],
     # device groups: several GPUs from one process (the C-level counterpart of physicl_amd.multidev.MultiDevice)
     "pcl_group_create": [c_int, POINTER(c_int), POINTER(_vp)],
     "pcl_group_destroy": [_vp],
@@ -196,6 +199,7 @@ _PROTOTYPES = {
     "pcl_group_step_phase_layered": [_vp, c_int, _vp, _vp, _vp, _vp, _vp, c_int, _vp, _vp, _vp, c_double, c_uint64, c_uint32, _vp],
     "pcl_group_step_recycle_spent": [_vp, _vp, c_double, c_int, c_double, _vp, c_int, _vp, _vp, c_uint64, c_uint32, _vp],
     "pcl_group_step_absorb_path": [_vp, c_int, c_int, _vp, _vp, _vp, _vp, c_uint64, c_uint32, _vp, _vp],
+    "pcl_group_step_reemit_parked": [_vp, c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, c_double, c_uint64, c_uint32, _vp],
 }
 EXPORTS = sorted(list(_PROTOTYPES) + ["pcl_last_error"])
 
@@ -494,6 +498,35 @@ def _absorb_path(entry, handle, p, edges, center, E_edges, seed, n_pass):
     check(entry(handle, L, B, pr.ctypes.data, ptr(ed), ptr(ce), ptr(Ee), int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_pass) & 0xFFFFFFFF,
                 counts.ctypes.data, cells.ctypes.data))
     return int(counts[0]), int(counts[1]), cells
+
+
+def _reemit(entry, handle, eta, angular, tables, edges, center, c, seed, n_pass):
+    """One call of pcl_step_reemit_parked / pcl_group_step_reemit_parked: (parked, reemitted, by_layer int64[L']).  ``eta`` and
+    ``angular`` ("isotropic", "lambertian" or the header's flags): one value, or one per layer of ``edges``; ``tables``: None, or per
+    layer None or ``(grid, cdf)``; the edges go over as given (the library squares them); ``n_pass``: the caller's own pass counter (a
+    Philox counter word)."""
+    ed = None if edges is None else np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+    L = 0 if ed is None else len(ed) - 1
+    rows = max(L, 1)
+    et = np.asarray(eta, dtype=np.float64).reshape(-1)
+    et = np.ascontiguousarray(np.repeat(et, rows) if len(et) == 1 else et)
+    laws = [angular] * rows if isinstance(angular, (str, int, np.integer)) else list(angular)
+    tabs = [None] * rows if tables is None else list(tables)
+    if not len(et) == len(laws) == len(tabs) == rows:
+        raise ValueError("eta, angular and tables hold %d, %d and %d values for %d layers" % (len(et), len(laws), len(tabs), rows))
+    lam = np.array([int(REEMIT_LAWS.get(a, a)) for a in laws], dtype=np.int32)
+    tabs = [None if t is None else tuple(np.ascontiguousarray(a, dtype=np.float64).reshape(-1) for a in t) for t in tabs]
+    if any(t is not None and len(t[0]) != len(t[1]) for t in tabs):
+        raise ValueError("a table's grid and cdf must hold the same number of values")
+    off = np.concatenate([[0], np.cumsum([0 if t is None else len(t[1]) for t in tabs])]).astype(np.int32)
+    grid = np.concatenate([t[0] for t in tabs if t is not None]) if off[-1] else None
+    cdf = np.concatenate([t[1] for t in tabs if t is not None]) if off[-1] else None
+    ce = None if center is None else np.ascontiguousarray(center, dtype=np.float64).reshape(3)
+    counts = np.zeros(2 + rows, dtype=np.int64)
+    ptr = lambda a: None if a is None else a.ctypes.data                                                       # noqa: E731
+    check(entry(handle, L, ptr(ed), ptr(ce), et.ctypes.data, lam.ctypes.data, off.ctypes.data, ptr(cdf), ptr(grid), float(c),
+                int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_pass) & 0xFFFFFFFF, counts.ctypes.data))
+    return int(counts[0]), int(counts[1]), counts[2:].copy()
 
 
 def _scatter(sc, required=False, lazy=False, empty_expr=b""):
@@ -1098,6 +1131,14 @@ class Device:
         PathAbsorptionStep."""
         return _absorb_path(self.lib.pcl_step_absorb_path, self.ctx, p, edges, center, E_edges, seed, n_pass)
 
+    def reemit_parked(self, c, eta=1.0, angular="isotropic", tables=None, edges=None, center=None, seed=0, n_pass=0):
+        """The photons of the resident store that are parked at rest in a radial layer of ``edges`` about ``center`` (``None``: one
+        layer everywhere) re-emitted from where they are with speed ``c``, each with the probability ``eta`` of its layer: a new
+        direction -- isotropic, or "lambertian" about the local vertical --, dr = dv = 0 and, where the layer has a table ``(grid,
+        cdf)``, a new E, in one sweep (pcl_step_reemit_parked).  ``(parked, reemitted, by_layer int64[L'])``.  light._reemit_parked
+        restates the sweep with numpy."""
+        return _reemit(self.lib.pcl_step_reemit_parked, self.ctx, eta, angular, tables, edges, center, c, seed, n_pass)
+
 
 class DeviceGroup:
     """``pcl_group_*``: several contexts in one process, sharded by global index, behind the C ABI (the shim owns the
@@ -1225,6 +1266,10 @@ class DeviceGroup:
     def absorb_path(self, p, edges=None, center=None, E_edges=None, seed=0, n_pass=0):
         """``Device.absorb_path`` on every context of the group, the tallies summed (pcl_group_step_absorb_path)."""
         return _absorb_path(self.lib.pcl_group_step_absorb_path, self.g, p, edges, center, E_edges, seed, n_pass)
+
+    def reemit_parked(self, c, eta=1.0, angular="isotropic", tables=None, edges=None, center=None, seed=0, n_pass=0):
+        """``Device.reemit_parked`` on every context of the group, the counts summed (pcl_group_step_reemit_parked)."""
+        return _reemit(self.lib.pcl_group_step_reemit_parked, self.g, eta, angular, tables, edges, center, c, seed, n_pass)
 
     def download(self, field, n=None, offset=0, dtype=None):
         n = self.count - offset if n is None else n

@@ -56,6 +56,19 @@ UNITS = [CORE] + ADDONS
 EXTRA_SWEEPS = {
     "pcl_shell.hip": (_sweep("pcl_step_detector_image", "pcl_group_step_detector_image", "k_detector_image"),),
 }
+# A writer sweep that joined the unit of the six behind them, in the same form (tests/test_reemit_cpu.py holds the re-emission's
+# to it): what is parked by the sweeps above is re-emitted beside them.
+WRITER_SWEEPS = {
+    "pcl_surface.hip": (_sweep("pcl_step_reemit_parked", "pcl_group_step_reemit_parked", "k_reemit_parked"),),
+}
+
+
+def sweeps_of(unit):
+    """Every sweep a unit of ADDONS holds, in the file's order: its row's, then what EXTRA_SWEEPS and WRITER_SWEEPS add."""
+    name = os.path.basename(unit["src"])
+    return tuple(unit["sweeps"]) + EXTRA_SWEEPS.get(name, ()) + WRITER_SWEEPS.get(name, ())
+
+
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -ffp-contract=off: the reference's kernels must be evaluated unfused (bit-exact parity, DESIGN.md)
 # -disable-machine-licm: the pre-RA pass hoists every scalar constant out of the kernels' long loops, the scalar register file

@@ -116,6 +116,26 @@
 //   moving iff not (v0 == 0 and v1 == 0 and v2 == 0), a photon;  b: the absorber's layer of q (no layers: 0);  e: the bin of E in the
 //   energy edges, the last one closed (no bands: 0);  exposed iff both exist;  p = P[b][e];  p > 0: u = u53(w0, w1) of counter
 //   (id_lo, id_hi, pass, 17);  absorbed iff u < p:  v_k = 0;  dv_k = 0
+//
+// Re-emission in place (ReemissionStep): what the ground or the medium has absorbed is radiated again from where it was absorbed --
+// a ground that glows in the infrared, a gas layer that returns its band, fluorescence with a lifetime.  A law, a spectrum and a
+// yield per pass belong to the radial layer a photon is parked in.
+//
+//   k_reemit_parked<T>     one grid-stride sweep: per slot v0 (k_absorb_path's test the other way round: a moving lane is decided
+//                          by v0 alone and loads nothing more; a lane at rest loads v1 and v2); lanes at rest load, with layers or a
+//                          lambertian layer, r and look q up in the squared edges; a parked lane whose layer's eta is not zero loads
+//                          its id and draws; re-emitted lanes draw a direction -- about (1, 0, 0), or cosine-weighted about the local
+//                          vertical d / sqrt(q) --, write v, dr = 0 and dv = 0 and, if their layer has a table, look a third draw up
+//                          in it and write E.  Two ballots + popcounts per wave for the two counters.  The tables (eta, squared
+//                          edges, every layer's cdf and grid, 34 KiB at the most) sit in dynamic LDS in front of the
+//                          workgroup-private uint32 cells [parked, re-emitted | by layer].  r, ids and kinds are never written.
+//
+// Operation order (what light._reemit_parked restates with numpy):
+//   parked iff v0 == 0 and v1 == 0 and v2 == 0, a photon, with a layer b (the absorber's layer of q; no layers: 0)
+//   eta_b > 0: u = u53(w0, w1) of counter (id_lo, id_hi, pass, 18);  re-emitted iff u < eta_b (lambertian: and 0 < q < inf)
+//   (u_a, u_b) of counter (id_lo, id_hi, pass, 19);  isotropic: w = (1, 0, 0), mu = 1 - 2*u_a;  lambertian: w_k = d_k / sqrt(q),
+//   mu = sqrt(1 - u_a);  e1, e2 = frame(w);  sc, ss = polar(mu, u_b);  v_k = c*turned;  dr_k = 0;  dv_k = 0
+//   a table:  E = grid_b[x], the first x with cdf_b[x] >= u53(w0, w1) of counter (id_lo, id_hi, pass, 20)
 #include "pcl_sweep.h"
 
 #include "pcl_device.h" // (after the HIP runtime and the ABI's header, which pcl_sweep.h brings)
@@ -697,6 +717,113 @@ __global__ void __launch_bounds__(kBlock) k_absorb_path(pabsorb_args<T> a) {
         if (s_cnt[k]) atomicAdd(&a.out[k], (unsigned long long)s_cnt[k]);
 }
 
+// The counter words of a re-emission in place: who is re-emitted, where to, with which energy (the header lists who uses which
+// word: 18, 19 and 20 are this kernel's alone).
+constexpr uint32_t kReemitDraw = 18, kReemitDir = 19, kReemitEnergy = 20;
+
+template <typename T>
+struct reemit_args {
+    const T *r[3];               // read only with layers or a lambertian layer
+    T *v[3], *dr[3], *dv[3];
+    T *E;                        // NULL if no layer has a table: a re-emitted photon keeps its energy
+    const unsigned char *kind;   // NULL: every particle is a photon
+    const int64_t *ids;          // NULL: the id of slot i is id_base + i
+    const double *tables;        // eta (L') | e*e of the layer edges (L + 1, if L) | cdf (n_bins) | grid (n_bins) | the layers' ints
+    unsigned long long *out;     // parked, re-emitted | by layer [L']; device, zeroed by the entry point
+    int64_t N, ts, id_base;      // particles, tile stride of the slab (elements), id of slot 0
+    int tile_log;                // log2 of the tile length
+    int n_layers, n_bins;        // L (0: one layer everywhere, L' = 1), the bins of all tables together
+    int need_r;                  // layers, or a lambertian layer: somebody's position matters
+    double c[3], speed;
+    uint32_t k0, k1, pass;       // Philox key (seed_lo, seed_hi), the step's own pass counter
+};
+
+template <typename T>
+__global__ void __launch_bounds__(kBlock) k_reemit_parked(reemit_args<T> a) {
+    extern __shared__ double s_mem[];                                  // tables | parked, re-emitted | by layer
+    const int L = a.n_layers, Lp = L > 0 ? L : 1, nB = a.n_bins;
+    const int n_dbl = Lp + (L ? L + 1 : 0) + 2 * nB;
+    const int n_tab = n_dbl + (2 * Lp + 2) / 2;                         // 2 L' + 1 ints, packed behind the doubles
+    const int n_cells = 2 + Lp;
+    const double *s_eta = s_mem;
+    const double *s_e2 = s_eta + Lp;
+    const double *s_cdf = s_e2 + (L ? L + 1 : 0);
+    const double *s_grid = s_cdf + nB;
+    const int *s_lam = reinterpret_cast<const int *>(s_mem + n_dbl);   // 1: layer b emits cosine-weighted about the local vertical
+    const int *s_off = s_lam + Lp;                                     // layer b's table: [s_off[b], s_off[b + 1]) of cdf and grid
+    uint32_t *s_cnt = reinterpret_cast<uint32_t *>(s_mem + n_tab);
+    uint32_t *s_lay = s_cnt + 2;
+    for (int k = threadIdx.x; k < n_tab; k += kBlock) s_mem[k] = a.tables[k];
+    for (int k = threadIdx.x; k < n_cells; k += kBlock) s_cnt[k] = 0;  // (the layers follow the two counts)
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int64_t stride = grid_stride(), n_round = whole_waves(a.N);   // (the ballots below need whole waves inside the loop)
+    for (int64_t i = first_slot(); i < n_round; i += stride) {
+        const bool in = i < a.N;
+        const int64_t ti = tile_index(i, a.tile_log, a.ts);
+        // at_rest, written out as in k_absorb_path: -0.0 == 0, a NaN moves, v0 != 0 loads no more of v (fp32 widens exactly)
+        bool rest = in && (double)a.v[0][ti] == 0.0 && (double)a.v[1][ti] == 0.0 && (double)a.v[2][ti] == 0.0;
+        if (rest && a.kind) rest = a.kind[i] != 0;                      // plain Objects are never re-emitted
+        double d[3] = {0.0, 0.0, 0.0};
+        if (rest && a.need_r) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) d[k] = __dsub_rn((double)a.r[k][ti], a.c[k]);   // fp32 widens exactly
+        }
+        const double q = dot3(d, d);
+        int b = rest && L == 0 ? 0 : -1;                                // the layer; -1: in no layer, left parked
+        if (rest && L > 0 && q >= s_e2[0] && q <= s_e2[L]) b = bin_of(s_e2, L, q);      // (dist2, closed_bin: written out) NaN: in no layer
+        const bool parked = b >= 0;
+        bool go = false;
+        uint64_t id = 0;
+        if (parked) {
+            const double eta = s_eta[b];
+            if (eta > 0.0) {                                            // a layer that holds what it absorbed draws nothing
+                id = id_of(a.ids, a.id_base, i);
+                go = first_u53(pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, kReemitDraw, a.k0, a.k1)) < eta;   // u < 1: eta == 1 re-emits everybody
+                if (go && s_lam[b]) go = q > 0.0 && q < INFINITY;       // no vertical at the centre (or with a NaN): parked only
+            }
+        }
+        const uint32_t n_parked = (uint32_t)__popcll(__ballot(parked)), n_go = (uint32_t)__popcll(__ballot(go));
+        if (lane == 0 && n_parked) atomicAdd(&s_cnt[0], n_parked);
+        if (lane == 0 && n_go) {
+            atomicAdd(&s_cnt[1], n_go);
+            if (Lp == 1) atomicAdd(&s_lay[0], n_go);                    // one layer: the wave's count, not a lane's
+        }
+        if (!go) continue;      // lanes that are left alone wait at the loop's head: no ballot below this line
+        if (Lp > 1) atomicAdd(&s_lay[b], 1u);
+        double u_a, u_b, sc, ss, w[3] = {1.0, 0.0, 0.0}, e1[3], e2[3];
+        pair_u53(pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, kReemitDir, a.k0, a.k1), &u_a, &u_b);
+        double mu = __dsub_rn(1.0, __dmul_rn(2.0, u_a));                                             // uniform on the sphere
+        if (s_lam[b]) {
+            const double s = __dsqrt_rn(q);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) w[k] = __ddiv_rn(d[k], s);      // the local vertical
+            mu = __dsqrt_rn(__dsub_rn(1.0, u_a));                                                    // cosine-weighted hemisphere
+        }
+        polar(mu, u_b, &sc, &ss);
+        frame(w, e1, e2);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {                                   // it has neither moved nor scattered
+            a.v[k][ti] = (T)__dmul_rn(a.speed, turned(sc, ss, mu, e1[k], e2[k], w[k]));
+            a.dr[k][ti] = (T)0.0;
+            a.dv[k][ti] = (T)0.0;
+        }
+        int lo = s_off[b], hi = s_off[b + 1] - 1;
+        if (hi >= lo) {                                                 // the first x with cdf[x] >= u (the table ends in 1 > u): compares only
+            const double u = first_u53(pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, kReemitEnergy, a.k0, a.k1));
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (s_cdf[mid] >= u) hi = mid; else lo = mid + 1;
+            }
+            a.E[ti] = (T)s_grid[lo];
+        }
+    }
+    __syncthreads();
+    // pcl_sweep::flush_cells, written out, for the reason given in k_absorb_scattered: the count is not a literal
+    for (int k = threadIdx.x; k < n_cells; k += kBlock)
+        if (s_cnt[k]) atomicAdd(&a.out[k], (unsigned long long)s_cnt[k]);
+}
+
 struct surface_spec { // a call's arguments, checked
     double c[3] = {0.0, 0.0, 0.0};
     double R2 = 0.0, albedo = 1.0, speed = 0.0;
@@ -1226,6 +1353,124 @@ int group_absorb_path(pcl_group *group, int n_layers, int n_E_bins, const double
     });
 }
 
+struct reemit_spec { // a call's arguments, checked; what the kernel reads
+    int n_layers = 0, n_bins = 0;
+    double c[3] = {0.0, 0.0, 0.0};
+    double speed = 0.0;
+    bool draws = false;         // some layer has eta > 0: the ids are needed
+    bool need_r = false;        // layers, or a lambertian layer
+    std::vector<double> tables; // eta | e*e | cdf | grid | the layers' ints
+    size_t rows() const { return n_layers > 0 ? (size_t)n_layers : 1; }
+    size_t cells() const { return (size_t)2 + rows(); }                // parked, re-emitted | by layer
+    size_t lds() const { return tables.size() * sizeof(double) + cells() * sizeof(uint32_t); }
+};
+
+// Everything PCL_ERR_ARG stands for except the NULL context; nothing is launched or written before this has passed.
+bool check_reemit(int n_layers, const double *edges, const double *center, const double *eta, const int *lambertian, const int *offsets,
+                  const double *cdf, const double *grid, double c, const int64_t *counts_out, reemit_spec &s) {
+    if (!eta || !lambertian || !offsets || !counts_out || n_layers < 0 || n_layers > PCL_REEMIT_MAX_LAYERS || !std::isfinite(c)) return false;
+    s.n_layers = n_layers; s.speed = c; s.need_r = n_layers > 0;
+    const size_t Lp = s.rows();
+    for (size_t b = 0; b < Lp; ++b) {
+        if (!(eta[b] >= 0.0 && eta[b] <= 1.0)) return false;            // (NaN as well)
+        if (lambertian[b] != 0 && lambertian[b] != 1) return false;
+        s.draws = s.draws || eta[b] > 0.0;
+        s.need_r = s.need_r || lambertian[b] == 1;
+        s.tables.push_back(eta[b]);
+    }
+    if (n_layers > 0 && (!edges || !check_edges(edges, n_layers, kEdgeSquare, &s.tables))) return false;
+    if (offsets[0] != 0) return false;
+    for (size_t b = 0; b < Lp; ++b) {                                   // equal neighbours: the layer has no table
+        const int64_t bins = (int64_t)offsets[b + 1] - offsets[b];
+        if (bins < 0 || bins > PCL_REEMIT_MAX_BINS || offsets[b + 1] > PCL_REEMIT_MAX_TOTAL_BINS) return false;
+    }
+    s.n_bins = offsets[Lp];
+    if (s.n_bins > 0 && (!cdf || !grid)) return false;
+    for (size_t b = 0; b < Lp; ++b) {                                   // each table as pcl_step_recycle_spent checks its one
+        double prev = -INFINITY;
+        for (int k = offsets[b]; k < offsets[b + 1]; ++k) {
+            if (!(cdf[k] >= prev)) return false;                        // (NaN as well)
+            s.tables.push_back(prev = cdf[k]);
+        }
+        if (offsets[b + 1] > offsets[b] && prev != 1.0) return false;
+    }
+    for (int k = 0; k < s.n_bins; ++k) {
+        if (!std::isfinite(grid[k])) return false;
+        s.tables.push_back(grid[k]);
+    }
+    std::vector<int> ints;                                              // lambertian (L') | offsets (L' + 1)
+    ints.insert(ints.end(), lambertian, lambertian + Lp);
+    ints.insert(ints.end(), offsets, offsets + Lp + 1);
+    const size_t n_dbl = s.tables.size();
+    s.tables.resize(n_dbl + (2 * Lp + 2) / 2, 0.0);
+    memcpy(s.tables.data() + n_dbl, ints.data(), ints.size() * sizeof(int));
+    if (center) {
+        if (!finite3(center)) return false;
+        for (int k = 0; k < 3; ++k) s.c[k] = center[k];
+    }
+    return true;
+}
+
+template <typename T>
+int launch_reemit(pcl_ctx *ctx, const store_view &v, const reemit_spec &s, uint64_t seed, uint32_t pass, const staged &st) {
+    reemit_args<T> a{};
+    for (int k = 0; k < 3; ++k) {
+        void *r = nullptr, *vel = nullptr, *dr = nullptr, *dv = nullptr;
+        if (s.need_r) PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_R0 + k, &r));
+        PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_V0 + k, &vel));
+        PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_DR0 + k, &dr));     // (what makes an implicit dr and a lazy dv real: a re-emitted
+        PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_DV0 + k, &dv));     //  photon's are written)
+        a.r[k] = static_cast<const T *>(r); a.v[k] = static_cast<T *>(vel);
+        a.dr[k] = static_cast<T *>(dr); a.dv[k] = static_cast<T *>(dv);
+        a.c[k] = s.c[k];
+    }
+    // E is asked for only if a layer has a table: the pointer costs a wavelength-dependent scatter step its term cache (pcl_shell.hip).
+    void *E = nullptr;
+    if (s.n_bins > 0) PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_E, &E));
+    a.E = static_cast<T *>(E); a.kind = st.kind; a.ids = st.ids; a.tables = st.tables; a.out = st.out;
+    a.N = v.N; a.ts = v.ts; a.id_base = st.id_base; a.tile_log = v.tile_log;
+    a.n_layers = s.n_layers; a.n_bins = s.n_bins; a.need_r = s.need_r; a.speed = s.speed;
+    a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32); a.pass = pass;
+    const size_t lds = s.lds();                                         // 34 KiB with the largest tables: four workgroups a CU still
+    const int64_t grid = balanced_grid(v.N, v.n_cu, resident_per_cu(lds));
+    hipLaunchKernelGGL(k_reemit_parked<T>, dim3((unsigned)grid), dim3(kBlock), lds, v.stream, a);
+    return hipGetLastError() == hipSuccess ? PCL_OK : PCL_ERR_HIP;
+}
+
+int reemit_parked(pcl_ctx *ctx, int n_layers, const double *edges_host, const double *center_host, const double *eta_host,
+                  const int *lambertian_host, const int *table_offsets_host, const double *cdf_host, const double *grid_host, double c,
+                  uint64_t seed, uint32_t pass, int64_t *counts_out_host) {
+    reemit_spec s;
+    if (!ctx || !check_reemit(n_layers, edges_host, center_host, eta_host, lambertian_host, table_offsets_host, cdf_host, grid_host, c,
+                              counts_out_host, s))
+        return bad_argument(ctx);
+    const spans out = {{counts_out_host, s.cells()}};
+    store_view v;
+    staged st(ctx);
+    PCL_SWEEP_TRY(open_store(ctx, PCL_V0, &v));
+    zero_spans(out);
+    if (v.N <= 0) return PCL_OK;
+    PCL_SWEEP_TRY(stage(st, v, s.cells(), s.tables.data(), s.tables.size(), s.draws));   // the ids only if somebody may draw
+    PCL_SWEEP_TRY(PCL_SWEEP_LAUNCH(v, launch_reemit, ctx, v, s, seed, pass, st));
+    return fetch(st, out);
+}
+
+int group_reemit_parked(pcl_group *group, int n_layers, const double *edges_host, const double *center_host, const double *eta_host,
+                        const int *lambertian_host, const int *table_offsets_host, const double *cdf_host, const double *grid_host,
+                        double c, uint64_t seed, uint32_t pass, int64_t *counts_out_host) {
+    std::vector<pcl_ctx *> ctx;
+    PCL_SWEEP_TRY(shards_of(group, ctx));
+    const int n = (int)ctx.size();
+    reemit_spec s;
+    if (n < 1 || !check_reemit(n_layers, edges_host, center_host, eta_host, lambertian_host, table_offsets_host, cdf_host, grid_host, c,
+                               counts_out_host, s))
+        return bad_argument(n > 0 ? ctx[0] : nullptr);
+    return sum_shards(ctx, {{counts_out_host, s.cells()}}, [&](pcl_ctx *one, int64_t *p) {
+        return pcl_step_reemit_parked(one, n_layers, edges_host, center_host, eta_host, lambertian_host, table_offsets_host, cdf_host,
+                                      grid_host, c, seed, pass, p);
+    });
+}
+
 } // namespace
 
 extern "C" {
@@ -1316,6 +1561,25 @@ int pcl_group_step_absorb_path(pcl_group *group, int n_layers, int n_E_bins, con
     return guarded([&] {
         return group_absorb_path(group, n_layers, n_E_bins, p_host, edges_host, center_host, E_edges_host, seed, pass, counts_out_host,
                                  cells_out_host);
+    });
+}
+
+int pcl_step_reemit_parked(pcl_ctx *ctx, int n_layers, const double *edges_host, const double *center_host, const double *eta_host,
+                           const int *lambertian_host, const int *table_offsets_host, const double *cdf_host, const double *grid_host,
+                           double c, uint64_t seed, uint32_t pass, int64_t *counts_out_host) {
+    return guarded([&] {
+        return reemit_parked(ctx, n_layers, edges_host, center_host, eta_host, lambertian_host, table_offsets_host, cdf_host, grid_host, c,
+                             seed, pass, counts_out_host);
+    });
+}
+
+int pcl_group_step_reemit_parked(pcl_group *group, int n_layers, const double *edges_host, const double *center_host,
+                                 const double *eta_host, const int *lambertian_host, const int *table_offsets_host,
+                                 const double *cdf_host, const double *grid_host, double c, uint64_t seed, uint32_t pass,
+                                 int64_t *counts_out_host) {
+    return guarded([&] {
+        return group_reemit_parked(group, n_layers, edges_host, center_host, eta_host, lambertian_host, table_offsets_host, cdf_host,
+                                   grid_host, c, seed, pass, counts_out_host);
     });
 }
 

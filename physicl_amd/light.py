@@ -1580,29 +1580,35 @@ def _check_recycle(source, top, center, at_rest, spectrum):
     at_rest = bool(at_rest)
     if not at_rest and top is None:
         raise ValueError("at_rest and top: at least one of the two criteria must be on")
-    if spectrum is not None:
-        if isinstance(spectrum, PhotonBatch):
-            if spectrum.table is None:
-                raise ValueError("spectrum: this PhotonBatch has no table (make it with generate_photons_bulk(T=...))")
-            cdf, grid = spectrum.table                         # (a batch keeps the fill's order)
-        else:
-            try:
-                grid, cdf = spectrum
-            except (TypeError, ValueError):
-                raise ValueError("spectrum must be None, (grid, cdf) or a PhotonBatch with a table") from None
+    return source, top, center, at_rest, _check_spectrum(spectrum, RECYCLE_MAX_BINS)
+
+
+def _check_spectrum(spectrum, max_bins, name="spectrum"):
+    """A table to draw energies from as ``(grid, cdf)`` float64 arrays, or None: what RecycleStep(spectrum=) accepts -- None,
+    ``(grid, cdf)`` or a PhotonBatch with a table --, or ValueError."""
+    if spectrum is None:
+        return None
+    if isinstance(spectrum, PhotonBatch):
+        if spectrum.table is None:
+            raise ValueError("%s: this PhotonBatch has no table (make it with generate_photons_bulk(T=...))" % name)
+        cdf, grid = spectrum.table                             # (a batch keeps the fill's order)
+    else:
         try:
-            grid, cdf = np.array(grid, dtype=np.float64), np.array(cdf, dtype=np.float64)
+            grid, cdf = spectrum
         except (TypeError, ValueError):
-            raise ValueError("spectrum: grid and cdf must be sequences of numbers") from None
-        if grid.ndim != 1 or cdf.ndim != 1 or len(grid) != len(cdf) or not 1 <= len(cdf) <= RECYCLE_MAX_BINS:
-            raise ValueError("spectrum: grid and cdf must be two sequences of one length between 1 and %d, got shapes %r and %r"
-                             % (RECYCLE_MAX_BINS, grid.shape, cdf.shape))
-        if not np.all(np.isfinite(grid)):
-            raise ValueError("spectrum: grid must be finite")
-        if np.any(np.isnan(cdf)) or np.any(np.diff(cdf) < 0) or cdf[-1] != 1.0:
-            raise ValueError("spectrum: cdf must not decrease and must end in exactly 1")
-        spectrum = (np.ascontiguousarray(grid), np.ascontiguousarray(cdf))
-    return source, top, center, at_rest, spectrum
+            raise ValueError("%s must be None, (grid, cdf) or a PhotonBatch with a table" % name) from None
+    try:
+        grid, cdf = np.array(grid, dtype=np.float64), np.array(cdf, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("%s: grid and cdf must be sequences of numbers" % name) from None
+    if grid.ndim != 1 or cdf.ndim != 1 or len(grid) != len(cdf) or not 1 <= len(cdf) <= max_bins:
+        raise ValueError("%s: grid and cdf must be two sequences of one length between 1 and %d, got shapes %r and %r"
+                         % (name, max_bins, grid.shape, cdf.shape))
+    if not np.all(np.isfinite(grid)):
+        raise ValueError("%s: grid must be finite" % name)
+    if np.any(np.isnan(cdf)) or np.any(np.diff(cdf) < 0) or cdf[-1] != 1.0:
+        raise ValueError("%s: cdf must not decrease and must end in exactly 1" % name)
+    return np.ascontiguousarray(grid), np.ascontiguousarray(cdf)
 
 
 def _source_emit(ids, source, c, seed, word2, dir_word, pos_word):
@@ -1879,6 +1885,179 @@ class PathAbsorptionStep(tally.WriterStep):
         return new, new["absorbed"], (new["exposed"].sum(), new["absorbed"].sum(), new["absorbed_by_cell"])
 
     terminate = tally.TallyStep.terminate                # (a row holds arrays: written as the tally steps write theirs, as plain lists)
+
+
+# ---------------------------------------------------------------------------------------------- re-emission in place
+def _check_reemission(spectra, edges, center, eta, angular):
+    """(tables -- per layer None or (grid, cdf) float64 arrays --, edges or None, centre, eta as a float64 array [L'], angular as a
+    tuple of L' names) of a ReemissionStep, L' = max(layers, 1), or ValueError for everything pcl_step_reemit_parked would refuse."""
+    from ._hip import REEMIT_LAWS, REEMIT_MAX_BINS, REEMIT_MAX_LAYERS, REEMIT_MAX_TOTAL_BINS      # (the header's limits: one place)
+    if edges is not None:
+        edges = tally.check_edges("edges", edges, REEMIT_MAX_LAYERS, "square")               # (the device compares q with e*e)
+    rows = 1 if edges is None else len(edges) - 1
+    center = tally.check_center(center)
+    try:
+        et = np.array(eta, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("eta must be a number, or one number per layer") from None
+    if et.shape not in ((), (rows,)):
+        raise ValueError("eta must be one number or one per layer (%d), got shape %r" % (rows, et.shape))
+    if not np.all((et >= 0.0) & (et <= 1.0)):                  # (False for NaN as well)
+        raise ValueError("eta must lie in [0, 1], got %r" % (eta,))
+    et = np.ascontiguousarray(np.broadcast_to(et, (rows,)))
+    laws = (angular,) * rows if isinstance(angular, str) else angular
+    try:
+        laws = tuple(laws)
+    except TypeError:
+        raise ValueError("angular must be 'isotropic' or 'lambertian', or one of them per layer, got %r" % (angular,)) from None
+    if len(laws) != rows or not all(isinstance(a, str) and a in REEMIT_LAWS for a in laws):
+        raise ValueError("angular must be 'isotropic' or 'lambertian', or one of them per layer (%d), got %r" % (rows, angular))
+    one = spectra is None or isinstance(spectra, PhotonBatch)
+    if not one:                                                # (grid, cdf): two sequences of numbers, not two spectra
+        try:
+            one = len(spectra) == 2 and all(x is not None and not isinstance(x, PhotonBatch)
+                                            and np.array(x, dtype=np.float64).ndim == 1 for x in spectra)
+        except (TypeError, ValueError):
+            one = False
+    if one:
+        tables = [_check_spectrum(spectra, REEMIT_MAX_BINS, "spectra")] * rows
+    else:
+        try:
+            given = list(spectra)
+        except TypeError:
+            raise ValueError("spectra must be None, one spectrum or one per layer, got %r" % (spectra,)) from None
+        if len(given) != rows:
+            raise ValueError("spectra must hold one entry per layer (%d), got %d" % (rows, len(given)))
+        tables = [_check_spectrum(s, REEMIT_MAX_BINS, "spectra[%d]" % b) for b, s in enumerate(given)]
+    total = sum(len(t[1]) for t in tables if t is not None)
+    if total > REEMIT_MAX_TOTAL_BINS:
+        raise ValueError("spectra: the tables of all layers hold %d entries, at most %d are supported" % (total, REEMIT_MAX_TOTAL_BINS))
+    return tables, edges, center, et, laws
+
+
+_REEMIT_WORDS = (18, 19, 20)                                  # the draw, the direction, the energy (the header lists the words taken)
+
+
+def _reemit_parked(r, v, E, photon, ids, eta, angular, tables, edges, center, c, seed, n_pass, dtype=np.float64):
+    """What pcl_step_reemit_parked makes of (n, 3) float64 positions and velocities, the energies, who is a photon and the particles'
+    ids, with numpy -- every operation the device's operation in the device's order, one rounding each (include/physicl_hip.h), and
+    what is written rounded once to ``dtype``.  The rule, the draw and the table look-up are the device's bit for bit; sin / cos are
+    libm's here.  ``eta``, ``angular`` and ``tables`` (None, or per layer None or ``(grid, cdf)``): one value, or one per layer.  A
+    dict: ``r, v, dr, dv, E`` the new state (float64 arrays; ``r`` is the argument's, and so is every row of a particle that is not
+    re-emitted -- ``dr`` and ``dv`` hold NaN there: the sweep does not write them), the boolean masks ``parked`` and ``reemitted``,
+    ``layer`` (int64: of every photon at rest, -1 for none) and the tally ``by_layer`` (int64 [L'])."""
+    r, v = (np.array(a, dtype=np.float64).reshape(-1, 3) for a in (r, v))
+    n = len(v)
+    E = np.full(n, np.nan) if E is None else np.array(E, dtype=np.float64).reshape(-1)
+    ids = np.asarray(ids).reshape(-1)
+    rows = 1 if edges is None else len(edges) - 1
+    eta = np.broadcast_to(np.asarray(eta, dtype=np.float64).reshape(-1), (rows,))
+    lam = np.array([a == "lambertian" for a in ((angular,) * rows if isinstance(angular, str) else angular)], dtype=bool)
+    tables = [None] * rows if tables is None else list(tables)
+    center, c = np.asarray(center, dtype=np.float64), np.float64(c)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        at = np.flatnonzero(_at_rest(v) & np.asarray(photon, dtype=bool).reshape(-1))
+        layer = np.full(n, -1, dtype=np.int64)
+        layer[at] = _layer_of(r[at], edges, center)
+        parked = layer >= 0
+        draws = np.flatnonzero(parked)
+        draws = draws[eta[layer[draws]] > 0.0]                 # a layer that holds what it absorbed draws nothing
+        go = draws[_philox_block(ids[draws], seed, n_pass, _REEMIT_WORDS[0])[0] < eta[layer[draws]]]
+        d = r[go] - center
+        q = _dot3(d, d)
+        ok = ~lam[layer[go]] | ((q > 0.0) & (q < np.inf))      # no vertical at the centre (or with a NaN): parked only
+        go, d, q = go[ok], d[ok], q[ok]
+        up = lam[layer[go]]
+        u_a, u_b = _philox_block(ids[go], seed, n_pass, _REEMIT_WORDS[1])
+        w, mu = np.tile([1.0, 0.0, 0.0], (len(go), 1)), 1.0 - 2.0 * u_a
+        w[up] = d[up] / np.sqrt(q[up])[:, None]                # the local vertical
+        mu[up] = np.sqrt(1.0 - u_a[up])                        # cosine-weighted about it
+        v_new = c * _turn_about(w, mu, u_b)
+    reemitted = np.zeros(n, dtype=bool)
+    reemitted[go] = True
+    dr, dv = np.full((n, 3), np.nan), np.full((n, 3), np.nan)
+    v[go] = _stored(v_new.reshape(len(go), 3), dtype)
+    dr[go], dv[go] = 0.0, 0.0
+    for b, table in enumerate(tables):
+        if table is not None:
+            grid, cdf = (np.asarray(a, dtype=np.float64) for a in table)
+            sel = go[layer[go] == b]
+            u = _philox_block(ids[sel], seed, n_pass, _REEMIT_WORDS[2])[0]
+            E[sel] = _stored(grid[np.searchsorted(cdf, u, side="left")], dtype)               # the first x with cdf[x] >= u
+    return {"r": r, "v": v, "dr": dr, "dv": dv, "E": E, "parked": parked, "reemitted": reemitted, "layer": layer,
+            "by_layer": np.bincount(layer[go], minlength=rows).astype(np.int64)}
+
+
+class ReemissionStep(tally.WriterStep):
+    """Absorbed photons re-emitted in place (not in the reference).  Every sink of a pass -- ``AbsorptionStep``,
+    ``PathAbsorptionStep``, a ``SurfaceReflectStep`` with an albedo -- parks the photon at rest where it was absorbed; from there it
+    either stays for ever or a ``RecycleStep`` hands its slot back to the lamp.  This step puts the energy back WHERE it was absorbed:
+    a ground that absorbs sunlight and radiates in the infrared, a gas layer that absorbs a band and returns it isotropically (the
+    greenhouse return flux a ``ShellCrossingMeasureStep`` counts inward at the ground), fluorescence with a lifetime.  It stands
+    anywhere behind the steps of a pass that park photons, and before a ``RecycleStep`` if there is one: the lamp then takes what this
+    step left at rest.
+
+    * ``edges``: ``L + 1`` finite, non-negative, strictly increasing radii about ``center`` (at most 64 layers), ``AbsorptionStep``'s
+      rule exactly: layer ``b`` holds a photon iff ``e_b**2 <= q < e_(b+1)**2``, the last layer closed, ``q = (d0*d0 + d1*d1) + d2*d2``
+      in float64; no square root is taken; a NaN is in no layer.  Without ``edges`` one layer holds everything and ``r`` is not read,
+      unless that layer is lambertian.  A photon parked in no layer stays parked.  Below, ``L' = max(L, 1)``.
+    * ``eta``: one number in [0, 1] or ``L'`` of them: the chance per pass that a photon parked in the layer is re-emitted in this
+      pass.  1 re-emits at once; below 1 the photon stays parked and draws again next pass -- a lifetime of ``dt / eta``; 0 draws nothing.
+    * ``angular``: ``"isotropic"`` or ``"lambertian"``, one name or ``L'`` of them.  Lambertian is cosine-weighted about the local
+      vertical ``(r - center)/|r - center|``: a ground shell radiating upward.  The ground parks photons on its sphere up to rounding,
+      so give the ground a thin shell of its own, for example ``R*(1 - 1e-6) .. R*(1 + 1e-6)`` -- wide enough for an fp32 store.  A
+      photon exactly at ``center`` has no vertical: it is counted as parked and left alone.
+    * ``spectra``: None (a re-emitted photon keeps its ``E``), one spectrum for every layer, or a sequence of ``L'`` entries, each
+      None, ``(grid, cdf)`` or a ``PhotonBatch`` with a table -- what ``RecycleStep(spectrum=)`` accepts, by the same checks: a table has
+      at most 1024 entries, all tables of a step together at most 2048.  The new ``E`` does not look at the old one.  If no layer has
+      a table ``E`` is neither written nor asked for, so a wavelength-dependent scatter step keeps its term cache.
+
+    A re-emitted photon gets ``v`` at speed c along the drawn direction and ``dr = dv = 0``: later steps of the pass see a photon that
+    has neither moved nor scattered.  ``r``, ids and kinds are never written; a particle that is not re-emitted is not written at
+    all; plain ``Object``s are never touched.  The draws are Philox blocks keyed by ``sim.seed``, the photon's id and a pass counter of
+    the step's own, in counter words no other kernel uses (18, 19, 20): every other step draws what it draws without this one, and a
+    sharded run re-emits the same photons the same way.  The rule is written out in include/physicl_hip.h
+    (pcl_step_reemit_parked); ``_reemit_parked`` restates it with numpy.  The step reads no ``dv`` rule, so it works under
+    ``cl_on=False`` as well.
+
+    After each run ``self.parked`` (the photons at rest that have a layer), ``self.reemitted`` and ``self.by_layer`` (int64 ``[L']``:
+    the re-emitted per layer) hold the pass's tallies, global over shards and ranks; ``self.data`` gains the row ``[t, parked,
+    reemitted, by_layer]``; ``out_fn`` takes the rows at the end.
+
+    One launch per light step: the K-passes-per-launch kernels cannot re-emit a photon between two of their passes, and
+    ``sim.launch_note`` says so.  On host-resident objects (``step.run(sim)`` outside a device loop) the same state is made with
+    numpy, the ids being the places in the object list."""
+    _NOTE = "one launch per light step: a ReemissionStep re-emits the parked photons behind every pass, which the " \
+            "K-passes-per-launch kernels cannot carry"
+
+    def __init__(self, spectra=None, edges=None, center=(0, 0, 0), eta=1.0, angular="isotropic", out_fn=None):
+        MeasureStep.__init__(self, out_fn)
+        self.spectra, self.edges, self.center, self.eta, self.angular = _check_reemission(spectra, edges, center, eta, angular)
+        self.parked = self.reemitted = 0
+        self.by_layer = np.zeros(len(self.eta), dtype=np.int64)
+        self._pass = 0                                   # the step's own Philox counter word: one per run
+
+    def _record_pass(self, sim, parked, reemitted, *by_layer):
+        self.parked, self.reemitted = int(parked), int(reemitted)
+        self.by_layer = np.array(by_layer, dtype=np.int64).reshape(-1)
+        self.data.append(tally.object_row([tally._snap(sim.t), self.parked, self.reemitted, self.by_layer.copy()]))
+
+    @property
+    def _writes(self):                                   # r goes back as it came; without a table a re-emitted photon keeps its E
+        return ("r", "dr", "v", "dv") + (("E",) if any(t is not None for t in self.spectra) else ())
+
+    def _sweep(self, sim, prep):
+        parked, reemitted, by_layer = sim._dev.reemit_parked(_c_h_literals()[0], self.eta, self.angular, self.spectra, self.edges,
+                                                             self.center, sim.seed, self._pass)
+        return [np.concatenate([[parked, reemitted], by_layer]).astype(np.int64)]
+
+    def _host_sweep(self, objs, ids, seed, prep):
+        E, photon = tally.photon_energies(objs, PhotonObject)
+        new = _reemit_parked(tally.vec3(objs, "r"), tally.vec3(objs, "v"), E, photon, ids, self.eta, self.angular, self.spectra,
+                             self.edges, self.center, _c_h_literals()[0], seed, self._pass)
+        return new, new["reemitted"], (new["parked"].sum(), new["reemitted"].sum(), *new["by_layer"])
+
+    terminate = tally.TallyStep.terminate                # (a row holds an array: written as the tally steps write theirs, as plain lists)
 
 
 def _DEFAULT_ID_INFO(x):

@@ -1,5 +1,5 @@
 """What the cost tools of the writer sweeps (tools/bench_surface.py, bench_phase.py, bench_absorb.py, bench_layered_phase.py,
-bench_recycle.py, bench_path_absorb.py) share; not run by itself.
+bench_recycle.py, bench_path_absorb.py, bench_reemit.py) share; not run by itself.
 
 A tool keeps what is its own -- its docstring, ``CASES``, how a state is prepared, which call is timed and what a slot costs in
 bytes -- and takes from here the population, the two timed loops, the JSON lines and the command line:
