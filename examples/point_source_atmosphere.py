@@ -5,7 +5,7 @@ examples (n(r) = 2.5e25 m^-3 * exp(-(|r| - 6371 km) / 8.6 km)) with photons that
     python examples/point_source_atmosphere.py [n_photons] [passes] [--cone | --beam-down | --default] [--profile] [--shells]
                                                [--ground [ALBEDO]] [--phase rayleigh | hg:G | isotropic] [--omega0 W | W1,W2,...]
                                                [--cloud LO,HI[,G]] [--recycle [TOP]] [--gas LO,HI,K[,EMIN,EMAX]] [--blue-sky]
-                                               [--reemit [TG[,TA]]]
+                                               [--reemit [TG[,TA]]] [--ocean N]
                                                [--camera X,Y,Z:NX,NY,NZ:RADIUS:FOV_DEG:PIXELS]
 
 default: a point source at (6371 km, 0, 0) emitting isotropically; ``--cone``: a 0.3 rad cone pointing up (+x) from a 1 km disc;
@@ -53,6 +53,14 @@ over the passes are printed beside the shell counts, and a ShellCrossingMeasureS
 infrared photons through the ground's sphere: outward the ground's own glow (of the photons it parked a rounding below the sphere),
 inward what the gas sends back down -- the greenhouse return flux, which no run without the option has: no photon of the source is
 that red.  Try ``--ground 0.3 --gas 0,50000,2e-5 --reemit``.  One launch per light step.
+``--ocean N`` puts an ocean of refractive index N under the atmosphere: a RefractiveSurfaceStep at the ground's radius -- photons
+that reach the water are refracted into it by Snell's law or reflected off it with Fresnel's probability, and those that come back up
+from below are refracted out or, beyond the critical angle, reflected back down -- with the ground 6 km below it (two moves: a photon
+must not pass the sea floor within the move that took it into the water), black unless ``--ground`` gives it an albedo.  The step
+changes directions, not speeds.  The six counts summed over the passes are printed: ``in_refracted``, ``in_reflected``,
+``out_refracted``, ``out_reflected``, ``out_total``, and ``overshot`` (photons whose remaining move took them through the sphere once
+more: none, for a sphere this large).  Try ``--ocean 1.33 --shells``.  One launch per light step.  Not with ``--reemit``: its ground
+glows at the surface.
 ``--camera X,Y,Z:NX,NY,NZ:RADIUS:FOV_DEG:PIXELS`` puts an instrument into the scene: a DetectorMeasureStep, a disc of RADIUS metres about
 (X, Y, Z) (metres from the Earth's centre) whose normal (NX, NY, NZ) points from the detector into the scene, with a square field of
 view of FOV_DEG degrees to either side and PIXELS x PIXELS pixels, e.g. ``--camera 6471000,0,0:-1,0,0:20000:60:32`` looks straight down
@@ -120,6 +128,20 @@ if "--reemit" in argv:
         reemit[:len(given)] = given
     if len(reemit) != 2 or not min(reemit) > 0.0:
         sys.exit("--reemit [TG[,TA]]: the temperatures of the ground and of the gas in kelvin")
+ocean = None
+if "--ocean" in argv:
+    at = argv.index("--ocean")
+    try:
+        ocean = float(argv.pop(at + 1))
+    except (IndexError, ValueError):
+        ocean = None
+    if ocean is None or not ocean > 0.0:
+        sys.exit("--ocean N: the refractive index of the water, e.g. 1.33")
+    if reemit is not None:
+        sys.exit("--ocean and --reemit: the re-emitting ground stands at the surface")
+    if albedo is None:
+        albedo = 0.0                                           # a black sea floor
+OCEAN_DEPTH = 6000.0                                           # two moves: the floor is not passed within the move into the water
 camera = None
 if "--camera" in argv:
     at = argv.index("--camera")
@@ -204,8 +226,12 @@ def run(ground):
         red = light.ShellCrossingMeasureStep(None, [R], E_bins=[0.999 * grid.min(), 1.001 * grid.max()], measure_n=False)
         sim.add_step("infrared", red)
     if ground is not None:                                     # last in the pass: the tally before it sees the incoming move
-        floor = light.SurfaceReflectStep(R, albedo=ground)
+        floor = light.SurfaceReflectStep(R - (OCEAN_DEPTH if ocean is not None else 0.0), albedo=ground)
         sim.add_step(8, floor)
+    sea = None
+    if ocean is not None:                                      # behind the sea floor, before the lamp: where a ground would stand
+        sea = light.RefractiveSurfaceStep(R, ocean)
+        sim.add_step("ocean", sea)
     if reemit is not None:                                     # behind everything that parks photons, before the lamp
         # the ground parks photons on the sphere up to rounding: a thin shell of its own, wide enough for an fp32 store
         glow = light.ReemissionStep(infrared, edges=[R * (1.0 - 1e-6), R * (1.0 + 1e-6), R + 100e3], angular=["lambertian", "isotropic"])
@@ -220,7 +246,7 @@ def run(ground):
     sim.join()
     if sim.error is not None:
         raise sim.error
-    return sim, signs, shells, profile, image, tally, floor, angles, medium, lamp, vapour, eye, glow
+    return sim, signs, shells, profile, image, tally, floor, angles, medium, lamp, vapour, eye, glow, sea
 
 
 bare_top = None
@@ -230,7 +256,7 @@ if albedo is not None and "--shells" in sys.argv:              # the same run wi
     print("without the ground: %d photons x %d steps in %.2f s" % (n, len(bare[0].ts), bare[0].run_time))
     bare[0].close(download=False)
     del bare
-sim, signs, shells, profile, image, tally, floor, angles, medium, lamp, vapour, eye, glow = run(albedo)
+sim, signs, shells, profile, image, tally, floor, angles, medium, lamp, vapour, eye, glow, sea = run(albedo)
 steps = len(sim.ts)
 print("source:", source)
 print("%d photons x %d steps in %.2f s  ->  %.3g particle-steps/s" % (n, steps, sim.run_time, n * steps / sim.run_time))
@@ -264,6 +290,11 @@ if floor is not None:
     print("the ground (albedo %g, lambertian): %d reflected, %d absorbed over %d passes" % (albedo, sum(int(row[1]) for row in floor.data), sum(int(row[2]) for row in floor.data), len(floor.data)))
     if tally is not None:
         print("outward through the top of the atmosphere (100 km): %d with the ground, %d without" % (int(sum(row[2][3] for row in tally.data)), bare_top))
+if sea is not None:
+    names = ("in_refracted", "in_reflected", "out_refracted", "out_reflected", "out_total", "overshot")
+    sums = np.sum([[int(x) for x in list(row)[1:]] for row in sea.data], axis=0).tolist()
+    print("an ocean of n = %g, its floor %g km down, over %d passes: %s" % (ocean, OCEAN_DEPTH / 1e3, len(sea.data),
+                                                                            ", ".join("%s %d" % kv for kv in zip(names, sums))))
 if medium is not None:
     by_layer = np.sum([row[3] for row in medium.data], axis=0)
     print("the medium (omega0 %s): %d interactions, %d absorbed over %d passes" % (

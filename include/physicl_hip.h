@@ -1004,6 +1004,59 @@ int pcl_step_reemit_parked(pcl_ctx *ctx, int n_layers, const double *edges_host,
                            const double *grid_host, double c, uint64_t seed, uint32_t pass,
                            int64_t *counts_out_host /* [2 + L']: parked, re-emitted, by layer */);
 
+/* A refracting sphere (RefractiveSurfaceStep): a dielectric interface between a medium of refractive index n_inside within the
+ * sphere of ``radius`` about center_host and one of n_outside around it -- an ocean under an atmosphere, a drop, the top of an
+ * atmosphere.  Photons whose last move crossed the sphere, in either direction, are refracted by Snell's law or reflected -- with
+ * Fresnel's probability for unpolarised light, and always beyond the critical angle -- in ONE sweep of the resident store.  It
+ * stands where a ground would: the last call of a pass (before pcl_step_recycle_spent).  Nothing is removed; E, ids and kinds are
+ * not touched and E is not asked for.  The model's photons move c*dt per pass everywhere (pcl_step_absorb_path relies on it), so
+ * this call changes DIRECTIONS, NOT SPEEDS: |v| = c on both sides.  All arithmetic is fp64, unfused, every operation rounded
+ * once, in the order written (x.y of two vectors is (x0*y0 + x1*y1) + x2*y2); an fp32 store's values are widened first (exact) and
+ * what is written is rounded once to the store's dtype.
+ *   d = r - center;  m = dr;  p = d - m;  q_now = d.d;  q_prev = p.p;  R2 = radius*radius (made on the host)
+ *   inward   iff  q_now < R2 and R2 <= q_prev and q_prev < inf       (pcl_step_surface_reflect's test, character for character)
+ *   outward  iff  q_prev < R2 and R2 <= q_now and q_now < inf
+ * -- the two crossings of pcl_step_shell_crossings for one shell (a particle exactly on the sphere is outside), so that tally,
+ * made BEFORE this call, counts exactly the photons that cross here if every q_prev is finite.  Only photons (kind != 0) cross; a
+ * NaN anywhere in r or dr: no crossing.  A particle that does not cross is not written at all.
+ *   a = m.m;  b = p.m;  cq = q_prev - R2;  disc = max(b*b - a*cq, 0);  sq = sqrt(disc)
+ *   inward:   t = cq / (sq - b)                                                           (pcl_step_surface_reflect's lines)
+ *   outward:  the other root, in the form that does not cancel:  b > 0:  t = (0 - cq) / (sq + b);  otherwise  t = (sq - b) / a;
+ *             then t = min(max(t, 0), 1)  (min and max ignore a NaN: fmin, fmax)
+ *   x = p + t*m;  nrm = x / sqrt(x.x);  sa = sqrt(a);  w = (1 - t)*sa;  mh = m / sa       (as pcl_step_surface_reflect goes on)
+ *   inward:   N = nrm;   eta = n_outside / n_inside           (the two ratios are made on the host, one rounding each)
+ *   outward:  N = -nrm;  eta = n_inside / n_outside
+ *   ci = max(0 - mh.N, 0);  k = 1 - (eta*eta)*(1 - ci*ci)
+ *   k < 0:    total internal reflection:  dir = mh + (2*ci)*N;  nothing is drawn
+ *   k >= 0:   ct = sqrt(k) -- but eta == 1 (no interface): ct = ci, whatever 1 - (1 - ci*ci) rounds to, so that F = 0 and dir = mh --;
+ *             ec = eta*ci;  rs = (ec - ct) / (ec + ct);  ect = eta*ct;  rp = (ci - ect) / (ci + ect);  F = (rs*rs + rp*rp)*0.5
+ *             fresnel != 0 and F > 0 (a NaN is not):  u = u53(w0, w1) of the counter (id_lo, id_hi, pass, 21);  reflected iff u < F:
+ *             dir = mh + (2*ci)*N
+ *             otherwise refracted:  dir = eta*mh + (ec - ct)*N
+ *   fresnel == 0:  nothing is ever drawn; every crossing that is not total refracts.
+ *   v = c*dir;  dv = v - v_old;  dr = w*dir;  y = x + dr;  r = center + y         (the rest of the move, flown along dir)
+ * One interaction per photon per call.  overshot: after the write, y.y >= R2 for an outcome that ends inside (inward refracted,
+ * outward reflected or total), y.y < R2 for one that ends outside (inward reflected, outward refracted) -- the rest of the move has
+ * carried the photon through the sphere again (a NaN: not counted).  A counter only, it changes nothing: c*dt is too large for
+ * the radius.
+ * The Philox4x32-10 block has the key (seed_lo, seed_hi), u53 of pcl_store_apply_source; ``pass`` is the caller's own counter.
+ * The word 21 is used by nothing else (scatter kernels 0 and 1, fill and source 2..5, pcl_step_surface_reflect 8 and 9,
+ * pcl_step_phase_redirect 10 and 11, pcl_step_absorb_scattered 12, pcl_step_phase_layered 13, pcl_step_recycle_spent 14, 15 and 16,
+ * pcl_step_absorb_path 17, pcl_step_reemit_parked 18, 19 and 20: 0-5 and 8-20 are taken), so every other step draws what it drew,
+ * and a photon meets the same fate however the run is sharded.
+ * counts_out_host[0] = inward refracted, [1] = inward reflected (a total reflection on the way in, n_outside > n_inside, among
+ * them), [2] = outward refracted, [3] = outward reflected (drawn), [4] = outward total, [5] = overshot, by this call.
+ * A store that is not uniform costs the host traffic it costs pcl_step_surface_reflect; the ids go along only with fresnel != 0.
+ * PCL_ERR_ARG (NULL counts, radius not positive / not finite / its square not finite, n_inside or n_outside not positive or not
+ * finite, a centre or c that is not finite) is returned before the store is looked at -- by the group's entry point before the group
+ * is --, and nothing is launched or written; PCL_ERR_STATE without a store; an empty store answers zeros without a launch.  Host
+ * pointers; one device allocation per call, handed back on every way out; synchronises once, with the copy of the six counts.
+ * pcl_last_error() is generic, as for pcl_step_surface_reflect, whose source file these two entry points share
+ * (physicl_amd/csrc/pcl_surface.hip). */
+int pcl_step_refract_surface(pcl_ctx *ctx, double radius, const double *center_host, double n_inside, double n_outside, int fresnel,
+                             double c, uint64_t seed, uint32_t pass,
+                             int64_t *counts_out_host /* [6]: in refracted, in reflected, out refracted, out reflected, out total, overshot */);
+
 /* ---- Device groups: several GPUs from ONE process ---------------------------------------------------------------
  * The reference is a single process with one simulation thread (physicl/__init__.py:400-432, 501-524); this is how
  * a host written against this ABI uses a node's GPUs the same way, without one process per GPU.  A group owns one
@@ -1104,6 +1157,10 @@ int pcl_group_step_reemit_parked(pcl_group *group, int n_layers, const double *e
                                  const double *eta_host, const int *lambertian_host, const int *table_offsets_host,
                                  const double *cdf_host, const double *grid_host, double c, uint64_t seed, uint32_t pass,
                                  int64_t *counts_out_host);
+/* pcl_step_refract_surface on every shard (side by side), the six counts summed over the group's devices; the arguments are
+ * checked once for the group, before the group is looked at (ids are global: the same photons meet the same fate) */
+int pcl_group_step_refract_surface(pcl_group *group, double radius, const double *center_host, double n_inside, double n_outside,
+                                   int fresnel, double c, uint64_t seed, uint32_t pass, int64_t *counts_out_host);
 
 /* ---------------------------------------------------------------- the counters' collective (one process per GPU)
  * The path shards by global index with no data-path exchange; the only global quantities are the int64

@@ -166,6 +166,7 @@ _PROTOTYPES = {
     "pcl_step_recycle_spent": [_vp, _vp, c_double, c_int, c_double, _vp, c_int, _vp, _vp, c_uint64, c_uint32, _vp],
     "pcl_step_absorb_path": [_vp, c_int, c_int, _vp, _vp, _vp, _vp, c_uint64, c_uint32, _vp, _vp],
     "pcl_step_reemit_parked": [_vp, c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, c_double, c_uint64, c_uint32, _vp],
+    "pcl_step_refract_surface": [_vp, c_double, _vp, c_double, c_double, c_int, c_double, c_uint64, c_uint32, _vp],
     # device groups: several GPUs from one process (the C-level counterpart of physicl_amd.multidev.MultiDevice)
     "pcl_group_create": [c_int, POINTER(c_int), POINTER(_vp)],
     "pcl_group_destroy": [_vp],
@@ -200,6 +201,7 @@ _PROTOTYPES = {
     "pcl_group_step_recycle_spent": [_vp, _vp, c_double, c_int, c_double, _vp, c_int, _vp, _vp, c_uint64, c_uint32, _vp],
     "pcl_group_step_absorb_path": [_vp, c_int, c_int, _vp, _vp, _vp, _vp, c_uint64, c_uint32, _vp, _vp],
     "pcl_group_step_reemit_parked": [_vp, c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, c_double, c_uint64, c_uint32, _vp],
+    "pcl_group_step_refract_surface": [_vp, c_double, _vp, c_double, c_double, c_int, c_double, c_uint64, c_uint32, _vp],
 }
 EXPORTS = sorted(list(_PROTOTYPES) + ["pcl_last_error"])
 
@@ -527,6 +529,16 @@ def _reemit(entry, handle, eta, angular, tables, edges, center, c, seed, n_pass)
     check(entry(handle, L, ptr(ed), ptr(ce), et.ctypes.data, lam.ctypes.data, off.ctypes.data, ptr(cdf), ptr(grid), float(c),
                 int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_pass) & 0xFFFFFFFF, counts.ctypes.data))
     return int(counts[0]), int(counts[1]), counts[2:].copy()
+
+
+def _refract(entry, handle, radius, center, n_inside, n_outside, fresnel, c, seed, n_pass):
+    """One call of pcl_step_refract_surface / pcl_group_step_refract_surface: int64[6] -- in refracted, in reflected, out refracted,
+    out reflected, out total, overshot -- of this call.  ``n_pass``: the caller's own pass counter (a Philox counter word)."""
+    ce = None if center is None else np.ascontiguousarray(center, dtype=np.float64).reshape(3)
+    counts = np.zeros(6, dtype=np.int64)
+    check(entry(handle, float(radius), None if ce is None else ce.ctypes.data, float(n_inside), float(n_outside), int(bool(fresnel)),
+                float(c), int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_pass) & 0xFFFFFFFF, counts.ctypes.data))
+    return counts
 
 
 def _scatter(sc, required=False, lazy=False, empty_expr=b""):
@@ -1139,6 +1151,14 @@ class Device:
         restates the sweep with numpy."""
         return _reemit(self.lib.pcl_step_reemit_parked, self.ctx, eta, angular, tables, edges, center, c, seed, n_pass)
 
+    def refract_surface(self, radius, n_inside, n_outside=1.0, center=None, fresnel=True, c=0.0, seed=0, n_pass=0):
+        """The photons of the resident store whose last move crossed the sphere of ``radius`` about ``center``, in either direction,
+        refracted into the medium beyond (``n_inside`` within the sphere, ``n_outside`` around it) or reflected -- with Fresnel's
+        probability if ``fresnel``, and always beyond the critical angle -- at speed ``c``, with the rest of the move flown along the
+        new direction, in one sweep (pcl_step_refract_surface).  int64[6]: in refracted, in reflected, out refracted, out reflected,
+        out total, overshot.  light._refract_surface restates the sweep with numpy."""
+        return _refract(self.lib.pcl_step_refract_surface, self.ctx, radius, center, n_inside, n_outside, fresnel, c, seed, n_pass)
+
 
 class DeviceGroup:
     """``pcl_group_*``: several contexts in one process, sharded by global index, behind the C ABI (the shim owns the
@@ -1270,6 +1290,10 @@ class DeviceGroup:
     def reemit_parked(self, c, eta=1.0, angular="isotropic", tables=None, edges=None, center=None, seed=0, n_pass=0):
         """``Device.reemit_parked`` on every context of the group, the counts summed (pcl_group_step_reemit_parked)."""
         return _reemit(self.lib.pcl_group_step_reemit_parked, self.g, eta, angular, tables, edges, center, c, seed, n_pass)
+
+    def refract_surface(self, radius, n_inside, n_outside=1.0, center=None, fresnel=True, c=0.0, seed=0, n_pass=0):
+        """``Device.refract_surface`` on every context of the group, the counts summed (pcl_group_step_refract_surface)."""
+        return _refract(self.lib.pcl_group_step_refract_surface, self.g, radius, center, n_inside, n_outside, fresnel, c, seed, n_pass)
 
     def download(self, field, n=None, offset=0, dtype=None):
         n = self.count - offset if n is None else n

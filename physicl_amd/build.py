@@ -69,6 +69,19 @@ def sweeps_of(unit):
     return tuple(unit["sweeps"]) + EXTRA_SWEEPS.get(name, ()) + WRITER_SWEEPS.get(name, ())
 
 
+# A sweep that joined a unit behind the tables above, in the same form (tests/test_refract_cpu.py holds the refracting sphere's to
+# it): the dielectric interface stands beside the ground, whose hit-point arithmetic it shares.  sweeps_of() does not fold this
+# table in -- the tests of the sweeps above count what it returns --; described_sweeps_of() is every sweep a unit holds.
+INTERFACE_SWEEPS = {
+    "pcl_surface.hip": (_sweep("pcl_step_refract_surface", "pcl_group_step_refract_surface", "k_refract_surface"),),
+}
+
+
+def described_sweeps_of(unit):
+    """Every sweep a unit of ADDONS holds, in the file's order: sweeps_of(unit), then what INTERFACE_SWEEPS adds."""
+    return sweeps_of(unit) + INTERFACE_SWEEPS.get(os.path.basename(unit["src"]), ())
+
+
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -ffp-contract=off: the reference's kernels must be evaluated unfused (bit-exact parity, DESIGN.md)
 # -disable-machine-licm: the pre-RA pass hoists every scalar constant out of the kernels' long loops, the scalar register file

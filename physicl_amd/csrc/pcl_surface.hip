@@ -136,6 +136,29 @@
 //   (u_a, u_b) of counter (id_lo, id_hi, pass, 19);  isotropic: w = (1, 0, 0), mu = 1 - 2*u_a;  lambertian: w_k = d_k / sqrt(q),
 //   mu = sqrt(1 - u_a);  e1, e2 = frame(w);  sc, ss = polar(mu, u_b);  v_k = c*turned;  dr_k = 0;  dv_k = 0
 //   a table:  E = grid_b[x], the first x with cdf_b[x] >= u53(w0, w1) of counter (id_lo, id_hi, pass, 20)
+//
+// A refracting sphere (RefractiveSurfaceStep): a dielectric interface -- an ocean, a drop, the top of an atmosphere.  The ground's
+// geometry for both crossing directions; where the ground bounces or parks, this sweep refracts by Snell's law or reflects with
+// Fresnel's probability.  Directions change, speeds do not.
+//
+//   k_refract_surface<T>   k_surface_reflect's sweep of r and dr (48 B a slot in fp64); q_now and q_prev against R*R decide who
+//                          crosses, and which way.  Only crossing lanes go on: they work the hit point, the facing normal and the
+//                          outcome out in fp64, load their id and draw only where Fresnel's F > 0, load v and write r, v, dr, dv.
+//                          The lanes meet again behind that block: one ballot + popcount per wave and counter (six LDS cells,
+//                          flushed with 64-bit atomics), skipped by a wave nobody of which crosses.
+//
+// Operation order (what light._refract_surface restates with numpy):
+//   d, m, p, q_now, q_prev as the ground's;  inward iff q_now < R2 <= q_prev < inf;  outward iff q_prev < R2 <= q_now < inf;  a photon
+//   a = m.m;  b = p.m;  cq = q_prev - R2;  sq = sqrt(max(b*b - a*cq, 0));  inward: t = cq / (sq - b)
+//   outward: t = min(max(b > 0 ? (0 - cq) / (sq + b) : (sq - b) / a, 0), 1)
+//   x_k = p_k + t*m_k;  nrm_k = x_k / sqrt(x.x);  sa = sqrt(a);  mh_k = m_k / sa;  w = (1 - t)*sa
+//   inward: N = nrm, eta = n_outside / n_inside;  outward: N = -nrm, eta = n_inside / n_outside      (the ratios made on the host)
+//   ci = max(0 - mh.N, 0);  k = 1 - (eta*eta)*(1 - ci*ci);  k < 0: total, dir_k = mh_k + (2*ci)*N_k
+//   ct = sqrt(k) (eta == 1: ct = ci);  ec = eta*ci;  rs = (ec - ct) / (ec + ct);  ect = eta*ct;  rp = (ci - ect) / (ci + ect)
+//   F = (rs*rs + rp*rp)*0.5;  fresnel and F > 0: u = u53(w0, w1) of counter (id_lo, id_hi, pass, 21), reflected iff u < F: dir as above
+//   refracted: dir_k = eta*mh_k + (ec - ct)*N_k
+//   v_k = c*dir_k;  dv_k = v_k - v_old_k;  dr_k = w*dir_k;  y_k = x_k + dr_k;  r_k = center_k + y_k
+//   overshot iff y.y >= R2 where the outcome ends inside (in refracted, out reflected, out total), y.y < R2 where it ends outside
 #include "pcl_sweep.h"
 
 #include "pcl_device.h" // (after the HIP runtime and the ABI's header, which pcl_sweep.h brings)
@@ -824,6 +847,126 @@ __global__ void __launch_bounds__(kBlock) k_reemit_parked(reemit_args<T> a) {
         if (s_cnt[k]) atomicAdd(&a.out[k], (unsigned long long)s_cnt[k]);
 }
 
+// The counter word of the Fresnel draw (the header lists who uses which word: 21 is this kernel's alone).
+constexpr uint32_t kRefractDraw = 21;
+
+template <typename T>
+struct refract_args {
+    T *r[3], *v[3], *dr[3], *dv[3];
+    const unsigned char *kind;   // NULL: every particle is a photon
+    const int64_t *ids;          // NULL: the id of slot i is id_base + i
+    unsigned long long *out;     // [6]: in refracted, in reflected, out refracted, out reflected, out total, overshot; device, zeroed
+    int64_t N, ts, id_base;      // particles, tile stride of the slab (elements), id of slot 0
+    int tile_log;                // log2 of the tile length
+    int fresnel;                 // 0: nothing is drawn, every crossing that is not total refracts
+    double c[3], R2, speed;
+    double eta_in, eta_out;      // n_outside / n_inside, n_inside / n_outside (made on the host)
+    uint32_t k0, k1, pass;       // Philox key (seed_lo, seed_hi), the step's own pass counter
+};
+
+template <typename T>
+__global__ void __launch_bounds__(kBlock) k_refract_surface(refract_args<T> a) {
+    __shared__ uint32_t s_cnt[6];
+    if (threadIdx.x < 6) s_cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int64_t stride = grid_stride(), n_round = whole_waves(a.N);   // (the ballots below need whole waves inside the loop)
+    for (int64_t i = first_slot(); i < n_round; i += stride) {
+        const bool in = i < a.N;
+        const int64_t ti = tile_index(i, a.tile_log, a.ts);
+        double d[3] = {0.0, 0.0, 0.0}, m[3] = {0.0, 0.0, 0.0}, p[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            if (in) {
+                d[k] = __dsub_rn((double)a.r[k][ti], a.c[k]);           // fp32 widens exactly
+                m[k] = (double)a.dr[k][ti];
+            }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) p[k] = __dsub_rn(d[k], m[k]);
+        const double q_now = dot3(d, d), q_prev = dot3(p, p);
+        // the ground's inward crossing, and the same the other way round (on the sphere is outside; NaN: false)
+        const bool inward = in && q_now < a.R2 && q_prev >= a.R2 && q_prev < INFINITY;
+        const bool outward = in && q_prev < a.R2 && q_now >= a.R2 && q_now < INFINITY;
+        bool cross = inward || outward;
+        if (cross && a.kind) cross = a.kind[i] != 0;
+        int outcome = -1;       // the cell: 0 in refracted, 1 in reflected, 2 out refracted, 3 out reflected, 4 out total
+        bool over = false;
+        if (cross) {            // (no ballot inside: the lanes meet again behind this block)
+            const double aq = dot3(m, m), b = dot3(p, m), cq = __dsub_rn(q_prev, a.R2);
+            const double sq = __dsqrt_rn(fmax(__dsub_rn(__dmul_rn(b, b), __dmul_rn(aq, cq)), 0.0));
+            double t;
+            if (inward)                                                 // the ground's root
+                t = __ddiv_rn(cq, __dsub_rn(sq, b));
+            else                                                        // the other root, in the form that does not cancel
+                t = fmin(fmax(b > 0.0 ? __ddiv_rn(__dsub_rn(0.0, cq), __dadd_rn(sq, b)) : __ddiv_rn(__dsub_rn(sq, b), aq), 0.0), 1.0);
+            double x[3], nf[3], mh[3], dir[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) x[k] = __dadd_rn(p[k], __dmul_rn(t, m[k]));
+            const double xn = __dsqrt_rn(dot3(x, x)), sa = __dsqrt_rn(aq);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const double nrm = __ddiv_rn(x[k], xn);
+                nf[k] = inward ? nrm : -nrm;                            // the normal that faces the photon
+                mh[k] = __ddiv_rn(m[k], sa);
+            }
+            const double w = __dmul_rn(__dsub_rn(1.0, t), sa);          // the rest of the move, flown along the new direction
+            const double eta = inward ? a.eta_in : a.eta_out;
+            const double ci = fmax(__dsub_rn(0.0, dot3(mh, nf)), 0.0);
+            const double kk = __dsub_rn(1.0, __dmul_rn(__dmul_rn(eta, eta), __dsub_rn(1.0, __dmul_rn(ci, ci))));
+            bool refl = kk < 0.0;                                       // total internal reflection: no draw
+            double ec = 0.0, ct = 0.0;
+            if (refl) {
+                outcome = inward ? 1 : 4;                               // (inward, with n_outside > n_inside: counted as reflected)
+            } else {
+                ct = eta == 1.0 ? ci : __dsqrt_rn(kk);                  // no interface: the photon passes, whatever 1 - (1 - ci*ci) rounds to
+                ec = __dmul_rn(eta, ci);
+                const double ect = __dmul_rn(eta, ct);
+                const double rs = __ddiv_rn(__dsub_rn(ec, ct), __dadd_rn(ec, ct)), rp = __ddiv_rn(__dsub_rn(ci, ect), __dadd_rn(ci, ect));
+                const double F = __dmul_rn(__dadd_rn(__dmul_rn(rs, rs), __dmul_rn(rp, rp)), 0.5);
+                if (a.fresnel && F > 0.0) {                             // (NaN: refracted, no draw)
+                    const uint64_t id = id_of(a.ids, a.id_base, i);
+                    refl = first_u53(pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, kRefractDraw, a.k0, a.k1)) < F;
+                }
+                outcome = (inward ? 0 : 2) + (refl ? 1 : 0);
+            }
+            if (refl) {
+                const double c2 = __dmul_rn(2.0, ci);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) dir[k] = __dadd_rn(mh[k], __dmul_rn(c2, nf[k]));
+            } else {
+                const double g = __dsub_rn(ec, ct);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) dir[k] = __dadd_rn(__dmul_rn(eta, mh[k]), __dmul_rn(g, nf[k]));
+            }
+            double y[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const double vk = __dmul_rn(a.speed, dir[k]), drk = __dmul_rn(w, dir[k]), vo = (double)a.v[k][ti];
+                y[k] = __dadd_rn(x[k], drk);
+                a.r[k][ti] = (T)__dadd_rn(a.c[k], y[k]);
+                a.v[k][ti] = (T)vk;
+                a.dr[k][ti] = (T)drk;
+                a.dv[k][ti] = (T)__dsub_rn(vk, vo);
+            }
+            const double q_new = dot3(y, y);                            // where the rest of the move has carried it (NaN: not counted)
+            over = inward != refl ? q_new >= a.R2 : q_new < a.R2;       // in refracted and out reflected end inside, the others outside
+        }
+        if (__ballot(cross)) {  // (the same answer in every lane of the wave)
+#pragma unroll
+            for (int k = 0; k < 5; ++k) {
+                const uint32_t n_k = (uint32_t)__popcll(__ballot(outcome == k));
+                if (lane == 0 && n_k) atomicAdd(&s_cnt[k], n_k);
+            }
+            const uint32_t n_over = (uint32_t)__popcll(__ballot(over));
+            if (lane == 0 && n_over) atomicAdd(&s_cnt[5], n_over);
+        }
+    }
+    __syncthreads();
+    // pcl_sweep::flush_cells, written out, for the reason given in k_absorb_scattered: a further caller changes the older kernels
+    for (int k = threadIdx.x; k < 6; k += kBlock)
+        if (s_cnt[k]) atomicAdd(&a.out[k], (unsigned long long)s_cnt[k]);
+}
+
 struct surface_spec { // a call's arguments, checked
     double c[3] = {0.0, 0.0, 0.0};
     double R2 = 0.0, albedo = 1.0, speed = 0.0;
@@ -1471,6 +1614,77 @@ int group_reemit_parked(pcl_group *group, int n_layers, const double *edges_host
     });
 }
 
+struct refract_spec { // a call's arguments, checked; the two ratios are made here, once
+    double c[3] = {0.0, 0.0, 0.0};
+    double R2 = 0.0, eta_in = 1.0, eta_out = 1.0, speed = 0.0;
+    bool fresnel = true;
+};
+
+// Everything PCL_ERR_ARG stands for except the NULL context; nothing is launched or written before this has passed.
+bool check_refract(double radius, const double *center, double n_inside, double n_outside, int fresnel, double c, const int64_t *counts_out,
+                   refract_spec &s) {
+    if (!counts_out) return false;
+    s.R2 = radius * radius;
+    if (!std::isfinite(radius) || !(radius > 0) || !std::isfinite(s.R2)) return false;
+    if (!std::isfinite(n_inside) || !(n_inside > 0) || !std::isfinite(n_outside) || !(n_outside > 0) || !std::isfinite(c)) return false;
+    if (center) {
+        if (!finite3(center)) return false;
+        for (int k = 0; k < 3; ++k) s.c[k] = center[k];
+    }
+    s.eta_in = n_outside / n_inside; s.eta_out = n_inside / n_outside;   // one rounding each
+    s.fresnel = fresnel != 0; s.speed = c;
+    return true;
+}
+
+template <typename T>
+int launch_refract(pcl_ctx *ctx, const store_view &v, const refract_spec &s, uint64_t seed, uint32_t pass, const staged &st) {
+    refract_args<T> a{};
+    for (int k = 0; k < 3; ++k) {
+        void *r = nullptr, *vel = nullptr, *dr = nullptr, *dv = nullptr;
+        PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_R0 + k, &r));
+        PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_V0 + k, &vel));
+        PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_DR0 + k, &dr));
+        PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_DV0 + k, &dv));
+        a.r[k] = static_cast<T *>(r); a.v[k] = static_cast<T *>(vel);
+        a.dr[k] = static_cast<T *>(dr); a.dv[k] = static_cast<T *>(dv);
+        a.c[k] = s.c[k];
+    }
+    a.kind = st.kind; a.ids = st.ids; a.out = st.out;
+    a.N = v.N; a.ts = v.ts; a.id_base = st.id_base; a.tile_log = v.tile_log; a.fresnel = s.fresnel;
+    a.R2 = s.R2; a.eta_in = s.eta_in; a.eta_out = s.eta_out; a.speed = s.speed;
+    a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32); a.pass = pass;
+    const int64_t grid = balanced_grid(v.N, v.n_cu, resident_per_cu(6 * sizeof(uint32_t)));
+    hipLaunchKernelGGL(k_refract_surface<T>, dim3((unsigned)grid), dim3(kBlock), 0, v.stream, a);
+    return hipGetLastError() == hipSuccess ? PCL_OK : PCL_ERR_HIP;
+}
+
+int refract_surface(pcl_ctx *ctx, double radius, const double *center_host, double n_inside, double n_outside, int fresnel, double c,
+                    uint64_t seed, uint32_t pass, int64_t *counts_out_host) {
+    refract_spec s;
+    if (!ctx || !check_refract(radius, center_host, n_inside, n_outside, fresnel, c, counts_out_host, s)) return bad_argument(ctx);
+    const spans out = {{counts_out_host, 6}};
+    store_view v;                                                       // E is never asked for, as in surface_reflect
+    staged st(ctx);
+    PCL_SWEEP_TRY(open_store(ctx, PCL_R0, &v));
+    zero_spans(out);
+    if (v.N <= 0) return PCL_OK;
+    PCL_SWEEP_TRY(stage(st, v, 6, nullptr, 0, s.fresnel));              // the ids only if somebody may draw
+    PCL_SWEEP_TRY(PCL_SWEEP_LAUNCH(v, launch_refract, ctx, v, s, seed, pass, st));
+    return fetch(st, out);
+}
+
+int group_refract_surface(pcl_group *group, double radius, const double *center_host, double n_inside, double n_outside, int fresnel,
+                          double c, uint64_t seed, uint32_t pass, int64_t *counts_out_host) {
+    refract_spec s;                                                     // the arguments first: a refused call looks at no group
+    if (!check_refract(radius, center_host, n_inside, n_outside, fresnel, c, counts_out_host, s)) return bad_argument(nullptr);
+    std::vector<pcl_ctx *> ctx;
+    PCL_SWEEP_TRY(shards_of(group, ctx));
+    if (ctx.empty()) return bad_argument(nullptr);
+    return sum_shards(ctx, {{counts_out_host, 6}}, [&](pcl_ctx *one, int64_t *p) {
+        return pcl_step_refract_surface(one, radius, center_host, n_inside, n_outside, fresnel, c, seed, pass, p);
+    });
+}
+
 } // namespace
 
 extern "C" {
@@ -1580,6 +1794,18 @@ int pcl_group_step_reemit_parked(pcl_group *group, int n_layers, const double *e
     return guarded([&] {
         return group_reemit_parked(group, n_layers, edges_host, center_host, eta_host, lambertian_host, table_offsets_host, cdf_host,
                                    grid_host, c, seed, pass, counts_out_host);
+    });
+}
+
+int pcl_step_refract_surface(pcl_ctx *ctx, double radius, const double *center_host, double n_inside, double n_outside, int fresnel,
+                             double c, uint64_t seed, uint32_t pass, int64_t *counts_out_host) {
+    return guarded([&] { return refract_surface(ctx, radius, center_host, n_inside, n_outside, fresnel, c, seed, pass, counts_out_host); });
+}
+
+int pcl_group_step_refract_surface(pcl_group *group, double radius, const double *center_host, double n_inside, double n_outside,
+                                   int fresnel, double c, uint64_t seed, uint32_t pass, int64_t *counts_out_host) {
+    return guarded([&] {
+        return group_refract_surface(group, radius, center_host, n_inside, n_outside, fresnel, c, seed, pass, counts_out_host);
     });
 }
 

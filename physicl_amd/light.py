@@ -1130,6 +1130,166 @@ class SurfaceReflectStep(tally.WriterStep):
         return new, new["hit"], (new["reflected"].sum(), new["absorbed"].sum())
 
 
+# ---------------------------------------------------------------------------------------------- refraction
+_REFRACT_WORD = 21                                             # the Fresnel draw's counter word (the header lists the words taken)
+_REFRACT_COUNTS = ("in_refracted", "in_reflected", "out_refracted", "out_reflected", "out_total", "overshot")
+
+
+def _check_refractive(radius, n_inside, n_outside, center):
+    """(radius, n_inside, n_outside, centre as 3 float64) of a RefractiveSurfaceStep, or ValueError for everything
+    pcl_step_refract_surface would refuse."""
+    radius = _radius(radius, "radius", "radius must be a number")
+    index = []
+    for name, x in (("n_inside", n_inside), ("n_outside", n_outside)):
+        x = _scalar(x, name + " must be a number")
+        if not (np.isfinite(x) and x > 0):
+            raise ValueError("%s must be finite and positive, got %r" % (name, x))
+        index.append(x)
+    return radius, index[0], index[1], tally.check_center(center)
+
+
+def _refract_surface(r, dr, v, photon, ids, radius, center, n_inside, n_outside, fresnel, c, seed, n_pass, dtype=np.float64):
+    """What pcl_step_refract_surface makes of (n, 3) float64 positions, last moves and velocities, who is a photon and the particles'
+    ids, with numpy -- every operation the device's operation in the device's order, one rounding each (include/physicl_hip.h), and
+    what is written rounded once to ``dtype``: the device's bit for bit, everywhere (the sweep takes no sin / cos).  A dict: ``r, v,
+    dr, dv`` the new state (float64 arrays; rows of particles that do not cross are the arguments', NaN in ``dv``: the sweep does not
+    write them), the boolean masks ``inward, outward, crossed, refracted, reflected`` (drawn), ``total`` and ``overshot``, ``counts``
+    (int64 [6], the order of the header) and of the crossing particles (NaN elsewhere) ``t``, ``x`` (the hit point about the centre),
+    ``N`` (the normal facing the photon), ``mh``, ``dir``, ``eta``, ``ci``, ``ct``, ``rs``, ``rp`` and ``F`` (NaN where total)."""
+    r, dr, v = (np.array(a, dtype=np.float64).reshape(-1, 3) for a in (r, dr, v))
+    n = len(r)
+    center, c, R2 = np.asarray(center, dtype=np.float64), np.float64(c), np.float64(radius) * np.float64(radius)
+    eta_in, eta_out = np.float64(n_outside) / np.float64(n_inside), np.float64(n_inside) / np.float64(n_outside)
+    with np.errstate(invalid="ignore", over="ignore"):
+        d = r - center
+        p = d - dr
+        q_now, q_prev = _dot3(d, d), _dot3(p, p)
+        photon = np.asarray(photon, dtype=bool).reshape(-1)
+        inward = (q_now < R2) & (q_prev >= R2) & (q_prev < np.inf) & photon      # the ground's test
+        outward = (q_prev < R2) & (q_now >= R2) & (q_now < np.inf) & photon
+    at = np.flatnonzero(inward | outward)
+    ids = np.asarray(ids).reshape(-1)[at]
+    inw = inward[at]
+    m, p, vo = dr[at], p[at], v[at]
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        a, b, cq = _dot3(m, m), _dot3(p, m), q_prev[at] - R2
+        sq = np.sqrt(np.fmax(b * b - a * cq, 0.0))
+        t = np.where(inw, cq / (sq - b), np.fmin(np.fmax(np.where(b > 0.0, (0.0 - cq) / (sq + b), (sq - b) / a), 0.0), 1.0))
+        x = p + t[:, None] * m
+        nrm = x / np.sqrt(_dot3(x, x))[:, None]
+        sa = np.sqrt(a)
+        mh = m / sa[:, None]
+        w = (1.0 - t) * sa
+        N = np.where(inw[:, None], nrm, -nrm)
+        eta = np.where(inw, eta_in, eta_out)
+        ci = np.fmax(0.0 - _dot3(mh, N), 0.0)
+        k = 1.0 - (eta * eta) * (1.0 - ci * ci)
+        total = k < 0.0
+        ct = np.where(eta == 1.0, ci, np.sqrt(k))              # no interface: the photon passes
+        ec, ect = eta * ci, eta * ct
+        rs, rp = (ec - ct) / (ec + ct), (ci - ect) / (ci + ect)
+        F = (rs * rs + rp * rp) * 0.5
+        drawn = np.zeros(len(at), dtype=bool)
+        draws = np.flatnonzero(~total & (F > 0.0)) if fresnel else np.zeros(0, dtype=np.int64)
+        drawn[draws] = _philox_block(ids[draws], seed, n_pass, _REFRACT_WORD)[0] < F[draws]
+        back = total | drawn
+        direction = np.where(back[:, None], mh + (2.0 * ci)[:, None] * N, eta[:, None] * mh + (ec - ct)[:, None] * N)
+        v_new = c * direction
+        dr_new = w[:, None] * direction
+        y = x + dr_new
+        r_new = center + y
+        dv_new = v_new - vo
+        q_new = _dot3(y, y)
+        over = np.where(inw != back, q_new >= R2, q_new < R2)  # in refracted and out reflected end inside, the others outside
+    out = {"r": r, "v": v, "dr": dr, "dv": np.full((n, 3), np.nan)}
+    for name, new in (("r", r_new), ("v", v_new), ("dr", dr_new), ("dv", dv_new)):
+        out[name][at] = _stored(new, dtype)
+    masks = {"inward": inward, "outward": outward, "crossed": inward | outward, "refracted": ~back, "reflected": drawn, "total": total,
+             "overshot": over}
+    for name, mask in masks.items():
+        if name in ("inward", "outward", "crossed"):
+            out[name] = mask
+        else:
+            out[name] = np.zeros(n, dtype=bool)
+            out[name][at] = mask
+    F = np.where(total, np.nan, F)
+    for name, val in (("t", t), ("x", x), ("N", N), ("mh", mh), ("dir", direction), ("eta", eta), ("ci", ci), ("ct", ct), ("rs", rs),
+                      ("rp", rp), ("F", F)):
+        out[name] = np.full((n,) + val.shape[1:], np.nan)
+        out[name][at] = val
+    # an inward total reflection (n_outside > n_inside) is counted as reflected: the header's [1]
+    out["counts"] = np.array([(inw & ~back).sum(), (inw & back).sum(), (~inw & ~back).sum(), (~inw & drawn).sum(), (~inw & total).sum(),
+                              over.sum()], dtype=np.int64)
+    return out
+
+
+class RefractiveSurfaceStep(tally.WriterStep):
+    """A refracting sphere: a dielectric interface (not in the reference) -- an ocean under an atmosphere, a water drop or a glass
+    sphere, the top of an atmosphere that is a real change of refractive index.  The medium within the sphere of ``radius`` about
+    ``center`` (code units) has the refractive index ``n_inside``, the one around it ``n_outside``.  Every photon whose last move
+    crossed the sphere, in EITHER direction, is put onto its new path at the point where the move met the sphere: refracted by Snell's
+    law into the medium beyond, or reflected back into the one it came from -- always beyond the critical angle (total internal
+    reflection) and, with ``fresnel=True``, with Fresnel's probability ``F`` for unpolarised light below it; ``fresnel=False`` draws
+    nothing and refracts every crossing that is not total.  The rest of the move is flown along the new direction.  Equal indices
+    are no interface: ``F = 0`` and every photon passes on its way.
+
+    The step changes DIRECTIONS, NOT SPEEDS: the model's photons move ``c*dt`` per pass everywhere, and ``PathAbsorptionStep``
+    relies on that, so ``|v| = c`` on both sides of the sphere.  What an index does to the light's speed is not modelled; what it
+    does to its path is.
+
+    Put the step where a ground would stand: LAST in a pass, before a ``RecycleStep``, behind the Newton step, the scatter step
+    and any measures.  A ``ShellCrossingMeasureStep`` of the same radius and centre placed BEFORE it sees the incoming moves: its
+    ``in`` count is this step's ``in_refracted + in_reflected``, its ``out`` count ``out_refracted + out_reflected + out_total``
+    (the shell's own rule in float64: a particle exactly on the sphere is outside, every change of side is counted once; a move
+    from infinitely far is counted there and left alone here).  A ground (``SurfaceReflectStep``) a little below an ocean's surface
+    stands BEFORE this step.  Plain ``Object``s and particles with a NaN in ``r`` or ``dr`` never cross.
+
+    One interaction per photon per pass.  ``overshot`` counts the photons whose remaining move carried them through the sphere
+    again (a grazing path whose chord is shorter than the rest of the move): it changes nothing and says that ``c*dt`` is too large
+    for the radius.  A total reflection on the way IN (``n_outside > n_inside``: a bubble) is counted in ``in_reflected``.
+
+    After each run ``in_refracted``, ``in_reflected``, ``out_refracted``, ``out_reflected``, ``out_total`` and ``overshot`` hold
+    the pass's counts (global over shards and ranks, one collective) and ``self.data`` gains the row ``[t, ...the six...]``;
+    ``out_fn`` takes the rows at the end of the run.  The arithmetic is written out in include/physicl_hip.h
+    (pcl_step_refract_surface); ``_refract_surface`` restates it with numpy, bit for bit.
+
+    The draw is a Philox block keyed by ``sim.seed``, the photon's id and a pass counter of the step's own, in a counter word no
+    other kernel uses (21): every other step draws what it draws without this one, and a photon meets the same fate however the run
+    is sharded.  It is made on the device with EVERY ``rng=`` setting.  The step reads no ``dv`` rule, so it works under
+    ``cl_on=False`` as well.
+
+    One launch per light step: the K-passes-per-launch kernels cannot refract a photon between two of their passes, and
+    ``sim.launch_note`` says so.  On host-resident objects (``step.run(sim)`` outside a device loop) the same state is made with
+    numpy, the ids being the places in the object list."""
+    _NOTE = "one launch per light step: a RefractiveSurfaceStep refracts photons at its sphere behind every pass, which the " \
+            "K-passes-per-launch kernels cannot carry"
+    _writes = ("r", "dr", "v", "dv")
+
+    def __init__(self, radius, n_inside, n_outside=1.0, center=(0, 0, 0), fresnel=True, out_fn=None):
+        MeasureStep.__init__(self, out_fn)
+        self.radius, self.n_inside, self.n_outside, self.center = _check_refractive(radius, n_inside, n_outside, center)
+        self.fresnel = bool(fresnel)
+        self._record_counts(np.zeros(6, dtype=np.int64))
+        self._pass = 0                                   # the step's own Philox counter word: one per run
+
+    def _record_counts(self, counts):
+        for name, x in zip(_REFRACT_COUNTS, counts):
+            setattr(self, name, int(x))
+
+    def _record_pass(self, sim, *counts):
+        self._record_counts(counts)
+        self.data.append(tally.object_row([tally._snap(sim.t)] + [getattr(self, name) for name in _REFRACT_COUNTS]))
+
+    def _sweep(self, sim, prep):
+        return [np.asarray(sim._dev.refract_surface(self.radius, self.n_inside, self.n_outside, self.center, self.fresnel,
+                                                    _c_h_literals()[0], sim.seed, self._pass), dtype=np.int64)]
+
+    def _host_sweep(self, objs, ids, seed, prep):
+        new = _refract_surface(tally.vec3(objs, "r"), tally.vec3(objs, "dr"), tally.vec3(objs, "v"), _photons(objs), ids, self.radius,
+                               self.center, self.n_inside, self.n_outside, self.fresnel, _c_h_literals()[0], seed, self._pass)
+        return new, new["crossed"], tuple(new["counts"])
+
+
 # ---------------------------------------------------------------------------------------------- phase functions
 def _check_phase(phase, g):
     """(phase, g as a float) of a PhaseFunctionStep, or ValueError for everything pcl_step_phase_redirect would refuse

@@ -306,6 +306,9 @@ class MultiDevice:
     def reemit_parked(self, *a, **kw):
         return self._sum_parts("reemit_parked", *a, **kw)
 
+    def refract_surface(self, *a, **kw):
+        return self._sum_parts("refract_surface", *a, **kw)
+
     def plane_energies(self, plane, n_hint=None):
         return self._concat(self._each(lambda s: s.plane_energies(plane)))      # (a shard does not know its share of the hint)
 
