@@ -720,10 +720,9 @@ def _along(a, u):
     return (a[:, 0] * u[0] + a[:, 1] * u[1]) + a[:, 2] * u[2]
 
 
-def _detector_image(r, dr, E, photon, position, frame, radius, x_edges, y_edges, E_edges=None):
-    """What pcl_step_detector_image answers, from (n, 3) float64 positions and last moves, the energies and who is a photon,
-    with numpy -- every operation the device's operation, one rounding each (include/physicl_hip.h):
-    (counts int64[2] = [through, seen], image int64[max(bands, 1), ny, nx])."""
+def _detector_seen(r, dr, position, frame, radius, x_edges, y_edges):
+    """Who pcl_step_detector_image counts, particle by particle: (through, seen) as masks, and (wn, ax, ay), the direction each
+    came from in the camera's frame -- ax / wn and ay / wn are what the image bins.  _detector_image's first half."""
     r, m = np.asarray(r, dtype=np.float64).reshape(-1, 3), np.asarray(dr, dtype=np.float64).reshape(-1, 3)
     e1, e2, n = np.asarray(frame, dtype=np.float64).reshape(3, 3)
     xe, ye = np.asarray(x_edges, dtype=np.float64), np.asarray(y_edges, dtype=np.float64)
@@ -740,6 +739,15 @@ def _detector_image(r, dr, E, photon, position, frame, radius, x_edges, y_edges,
         through = crossed & (hh <= lim) & (lim < np.inf)          # the rim is inside
         wn, ax, ay = -_along(m, n), -_along(m, e1), -_along(m, e2)   # the direction it came from: ax / wn, ay / wn
         seen = through & (wn > 0) & (wn < np.inf) & (xe[0] * wn <= ax) & (ax <= xe[-1] * wn) & (ye[0] * wn <= ay) & (ay <= ye[-1] * wn)
+    return through, seen, wn, ax, ay
+
+
+def _detector_image(r, dr, E, photon, position, frame, radius, x_edges, y_edges, E_edges=None):
+    """What pcl_step_detector_image answers, from (n, 3) float64 positions and last moves, the energies and who is a photon,
+    with numpy -- every operation the device's operation, one rounding each (include/physicl_hip.h):
+    (counts int64[2] = [through, seen], image int64[max(bands, 1), ny, nx])."""
+    xe, ye = np.asarray(x_edges, dtype=np.float64), np.asarray(y_edges, dtype=np.float64)
+    through, seen, wn, ax, ay = _detector_seen(r, dr, position, frame, radius, xe, ye)
     counts = np.array([np.count_nonzero(through), np.count_nonzero(seen)], dtype=np.int64)
     hit = np.flatnonzero(seen)                                    # the image looks at these only: an aperture is small
     nx, ny, nE = len(xe) - 1, len(ye) - 1, 0 if E_edges is None else len(E_edges) - 1

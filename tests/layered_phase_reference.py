@@ -1,10 +1,13 @@
-"""Populations, laws and layers for the tests of LayeredPhaseStep (tests/test_layered_phase_cpu.py and the GPU tests).  Not a test
-file: a helper they import.  The velocities are tests/phase_reference.py's cloud, the layers tests/absorb_reference.py's; the
-restatement of the kernel itself is physicl_amd.light._layered_phase_redirect."""
+"""Populations, laws and layers for the tests of LayeredPhaseStep (tests/test_layered_phase_cpu.py and the GPU tests), and the
+comparison of a sweep on two downloaded states (``check_layered``: tests/test_gpu_writer_store_states.py and
+test_writer_trips_gpu.py).  Not a test file: a helper they import.  The velocities are tests/phase_reference.py's cloud, the layers
+tests/absorb_reference.py's; the restatement of the kernel itself is physicl_amd.light._layered_phase_redirect."""
 import numpy as np
 
+import writer_reference as W
 from absorb_reference import CENTER, EDGES
 from phase_reference import C, SEED, cloud as phase_cloud, unit
+from physicl_amd import light
 
 assert C == 299792458.0 and SEED == 0x5EED5A7F
 SINGLE = ["isotropic", ("hg", 0.85), ("hg", -0.5), "rayleigh"]      # the laws PhaseFunctionStep has
@@ -64,6 +67,36 @@ def all_scattered(n, seed=1):
     rng = np.random.RandomState(seed)
     old, new = C * unit(rng.normal(size=(n, 3))), C * unit(rng.normal(size=(n, 3)))
     return new, new - old, np.arange(n, dtype=np.int64) + 7_000_000_001
+
+
+# ------------------------------------------------------------------------------------------------ a sweep against its restatement
+def check_layered(before, after, answer, laws, weights, edges, center, c, seed, n_pass, what):
+    """A state downloaded before the sweep (tests/writer_reference.py: ``snapshot``), the state downloaded after it and the sweep's
+    answer ``(scattered, redirected, by_layer, by_law)`` against light._layered_phase_redirect: every tally exact; E, ids and kinds,
+    r and dr of everybody and every row of a particle that is not re-directed bit-identical; re-directed rows within the bounds
+    tests/writer_reference.py derives for the phase function's v and dv.  Returns the restatement's dict."""
+    bw, aw = W.wide(before), W.wide(after)
+    T = np.asarray(before["E"]).dtype.type
+    ref = light._layered_phase_redirect(bw["r"], bw["v"], bw["dv"], W.photons(before), before["id"], laws, weights, edges, center, c,
+                                        seed, n_pass, T)
+    scattered, redirected, by_layer, by_law = answer
+    by_layer, by_law = np.asarray(by_layer).tolist(), np.asarray(by_law).tolist()
+    print("%s: scattered %d, redirected %d, by layer %s, by law %s" % (what, scattered, redirected, by_layer, by_law))
+    assert (scattered, redirected) == (int(ref["scattered"].sum()), int(ref["redirected"].sum())), what
+    assert by_layer == ref["by_layer"].tolist() and by_law == ref["by_law"].tolist(), what
+    assert sum(by_layer) == sum(by_law) == redirected, what
+    go = ref["redirected"]
+    for f in set(before) - set(W.FIELDS) - {"count"}:                  # E, ids, kinds
+        assert W.same_bits(before[f], after[f]), (what, f)
+    for f in W.FIELDS:                                                 # not re-directed: bit-identical; r and dr: everybody
+        assert W.same_bits(aw[f][~go], bw[f][~go]), (what, f)
+    assert W.same_bits(aw["r"], bw["r"]) and W.same_bits(aw["dr"], bw["dr"]), what
+    v_unit, v_bound = (W.ulp(c), W.DIR_ULP) if T is np.float64 else (W.ulp(c, np.float32), W.DIR_ULP + 0.5)
+    v_err = np.max(np.abs(aw["v"][go] - ref["v"][go])) / v_unit        # (somebody is re-directed: the callers' populations see to it)
+    dv_err = np.max(np.abs(aw["dv"][go] - ref["dv"][go])) / v_unit
+    print("%s: v %.3g ulp(c) (bound %g), dv %.3g ulp(c) (bound %g)" % (what, v_err, v_bound, dv_err, v_bound + 1))
+    assert v_err <= v_bound and dv_err <= v_bound + 1.0, what
+    return ref
 
 
 # ------------------------------------------------------------------------------------------------ the ABI, by hand

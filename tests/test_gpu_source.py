@@ -259,18 +259,13 @@ def test_simulation_over_two_contexts_starts_from_the_same_photons():
 GEOMETRY = {"oblique_far": ((6371000.0, 0.0, 0.0), (1, -2, 0.5), 1e6), "axis_at_origin": ((0.0, 0.0, 0.0), (0, 0, -1), 2.5)}
 
 
-@pytest.mark.parametrize("dtype", ["f64", "f32"])
-@pytest.mark.parametrize("geometry", sorted(GEOMETRY))
-@pytest.mark.parametrize("spatial", sorted(SPATIAL))
-@pytest.mark.parametrize("angular", sorted(ANGULAR))
-def test_every_photon_against_the_numpy_restatement(make_store, hip, angular, spatial, geometry, dtype):
-    n, id_base = 100_003, 7_000_000_001
-    origin, direction, radius = GEOMETRY[geometry]
-    src = src_of(angular, spatial, origin, direction, radius)
-    d = make_store(n, dtype)
-    fill(d, hip, n, id_base)
-    d.apply_source(src, C, SEED)
+def check_source(d, src, id_base, angular, spatial, geometry, dtype):
+    """The store of ``d`` behind ``apply_source(src, C, SEED)`` on a fill with ids from ``id_base``, every photon against the numpy
+    restatement under the bounds of the module's docstring (tests/test_writer_trips_gpu.py runs it past a sweep's first trip).
+    (r, v) as downloaded, widened."""
+    radius = GEOMETRY[geometry][2]
     s = d.download_state()
+    n = len(s["E"])
     ref = source_state(src, np.arange(n, dtype=np.uint64) + np.uint64(id_base), SEED, C)
     v, r = np.stack(s["v"], 1).astype(np.float64), np.stack(s["r"], 1).astype(np.float64)
     if dtype == "f64":
@@ -294,6 +289,21 @@ def test_every_photon_against_the_numpy_restatement(make_store, hip, angular, sp
     if spatial != "point":                                   # in the plane through origin perpendicular to d
         off = (r - src.origin) @ src.d
         assert np.max(np.abs(off)) <= (1e-9 if dtype == "f64" else 2.0) * max(radius, 1.0)
+    return r, v
+
+
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+@pytest.mark.parametrize("geometry", sorted(GEOMETRY))
+@pytest.mark.parametrize("spatial", sorted(SPATIAL))
+@pytest.mark.parametrize("angular", sorted(ANGULAR))
+def test_every_photon_against_the_numpy_restatement(make_store, hip, angular, spatial, geometry, dtype):
+    n, id_base = 100_003, 7_000_000_001
+    origin, direction, radius = GEOMETRY[geometry]
+    src = src_of(angular, spatial, origin, direction, radius)
+    d = make_store(n, dtype)
+    fill(d, hip, n, id_base)
+    d.apply_source(src, C, SEED)
+    check_source(d, src, id_base, angular, spatial, geometry, dtype)
 
 
 # ------------------------------------------------------------------------------------------------ the distributions

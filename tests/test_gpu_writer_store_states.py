@@ -45,7 +45,7 @@ import numpy as np
 import pytest
 
 import writer_reference as W
-from layered_phase_reference import MIX_LAWS, MIX_WEIGHTS
+from layered_phase_reference import MIX_LAWS, MIX_WEIGHTS, check_layered
 from path_absorb_reference import check_path_absorb
 from physicl_amd import light
 from recycle_reference import CDF, GRID, check_recycle
@@ -158,26 +158,9 @@ class Layered:
         return scattered, redirected, by_layer.tolist(), by_law.tolist()
 
     def check(self, before, after, answer, state, what):
-        bw, aw = W.wide(before), W.wide(after)
-        T = np.asarray(before["E"]).dtype.type
-        ref = light._layered_phase_redirect(bw["r"], bw["v"], bw["dv"], W.photons(before), before["id"], MIX_LAWS, MIX_WEIGHTS,
-                                            W.layer_edges(state), W.Source.origin, W.C, W.SEED, W.N_PASS, T)
         scattered, redirected, by_layer, by_law = answer
-        print("%s: scattered %d, redirected %d, by layer %s, by law %s" % (what, scattered, redirected, by_layer, by_law))
-        assert (scattered, redirected) == (int(ref["scattered"].sum()), int(ref["redirected"].sum())), what
-        assert by_layer == ref["by_layer"].tolist() and by_law == ref["by_law"].tolist(), what
         assert min(by_layer) > 0 and min(by_law) > 0 and sum(by_layer) == sum(by_law) == redirected, what  # every layer and law has work
-        go = ref["redirected"]
-        for f in set(before) - set(W.FIELDS) - {"count"}:              # E, ids, kinds
-            assert W.same_bits(before[f], after[f]), (what, f)
-        for f in W.FIELDS:                                             # not re-directed: bit-identical; r and dr: everybody
-            assert W.same_bits(aw[f][~go], bw[f][~go]), (what, f)
-        assert W.same_bits(aw["r"], bw["r"]) and W.same_bits(aw["dr"], bw["dr"]), what
-        v_unit, v_bound = (W.ulp(W.C), W.DIR_ULP) if T is np.float64 else (W.ulp(W.C, np.float32), W.DIR_ULP + 0.5)
-        v_err = np.max(np.abs(aw["v"][go] - ref["v"][go])) / v_unit
-        dv_err = np.max(np.abs(aw["dv"][go] - ref["dv"][go])) / v_unit
-        print("%s: v %.3g ulp(c) (bound %g), dv %.3g ulp(c) (bound %g)" % (what, v_err, v_bound, dv_err, v_bound + 1))
-        assert v_err <= v_bound and dv_err <= v_bound + 1.0, what
+        check_layered(before, after, answer, MIX_LAWS, MIX_WEIGHTS, W.layer_edges(state), W.Source.origin, W.C, W.SEED, W.N_PASS, what)
 
 
 class Recycle:

@@ -30,11 +30,11 @@ def restated(st, cfg):
     return light._detector_image(*st, **cfg)
 
 
-def uploaded(hip, st, dtype):
+def uploaded(hip, st, dtype, capacity=None):
     r, dr, E, photon = st
     N = len(E)
     dev = hip.Device(0)
-    dev.store_alloc(max(N, 1), dtype)
+    dev.store_alloc(capacity or max(N, 1), dtype)
     dev.set_count(N)
     for k in range(3):
         dev.upload(hip.R0 + k, r[:, k])

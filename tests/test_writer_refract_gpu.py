@@ -21,9 +21,12 @@ from writer_reference import same_bits
 pytestmark = pytest.mark.gpu
 
 SIZES = [1, 63, 64, 65, 2047, 2048, 2049, 4097, 3 * 2048 + 77]       # wave and tile edges (tests/test_reemit_gpu.py's, and the issue's)
-# a sweep's grid is capped at 8 resident workgroups of 256 slots on each of the 256 CUs: this many slots take a second trip
-PAST_FIRST_STRIDE = 256 * 8 * 256 + 2049
 ROOM = 300                                                             # capacity beyond N
+
+
+def first_stride(dev):
+    """A sweep's grid is capped at 8 resident workgroups of 256 slots on each CU: slots from here on take a second trip."""
+    return dev.info()["compute_units"] * 8 * 256
 
 
 @pytest.fixture(scope="module")
@@ -80,10 +83,11 @@ def test_every_slot_against_the_numpy_restatement(dev, n, dtype):
 
 @pytest.mark.parametrize("dtype", ["f64", "f32"])
 def test_past_the_grid_s_first_stride(dev, dtype):
-    n = PAST_FIRST_STRIDE
+    cap = first_stride(dev)
+    n = cap + 2049
     before, _ = upload(dev, n, dtype)
     counts, after, ref = sweep_and_check(dev, before, GLASS, 3, "refract n=%d %s" % (n, dtype))
-    tail = ref["crossed"][256 * 8 * 256:]                               # the second trip had work
+    tail = ref["crossed"][cap:]                                        # the second trip had work
     assert tail.sum() > 500 and min(counts[:5]) > 0
 
 
