@@ -5,7 +5,7 @@ examples (n(r) = 2.5e25 m^-3 * exp(-(|r| - 6371 km) / 8.6 km)) with photons that
     python examples/point_source_atmosphere.py [n_photons] [passes] [--cone | --beam-down | --default] [--profile] [--shells]
                                                [--ground [ALBEDO]] [--phase rayleigh | hg:G | isotropic] [--omega0 W | W1,W2,...]
                                                [--cloud LO,HI[,G]] [--recycle [TOP]] [--gas LO,HI,K[,EMIN,EMAX]] [--blue-sky]
-                                               [--reemit [TG[,TA]]] [--ocean N]
+                                               [--reemit [TG[,TA]]] [--ocean N] [--ground-bands E1,E2,...:a1,a2,...[:s1,...]]
                                                [--camera X,Y,Z:NX,NY,NZ:RADIUS:FOV_DEG:PIXELS]
 
 default: a point source at (6371 km, 0, 0) emitting isotropically; ``--cone``: a 0.3 rad cone pointing up (+x) from a 1 km disc;
@@ -61,6 +61,14 @@ changes directions, not speeds.  The six counts summed over the passes are print
 ``out_refracted``, ``out_reflected``, ``out_total``, and ``overshot`` (photons whose remaining move took them through the sphere once
 more: none, for a sphere this large).  Try ``--ocean 1.33 --shells``.  One launch per light step.  Not with ``--reemit``: its ground
 glows at the surface.
+``--ground-bands E1,E2,...:a1,a2,...[:s1,...]`` makes the ground spectral: a SpectralSurfaceStep in the place of ``--ground``'s step, with
+the band edges E1 < E2 < ... (joules, one more than bands), an albedo per band and -- optionally -- per band (or once for all) the share
+of the reflected photons that is mirrored; the others leave cosine-weighted about the local vertical.  A photon that comes down with an
+energy in no band is absorbed (``out_of_band``): the ground stays opaque.  ``reflected``, ``absorbed``, ``mirrored`` and ``out_of_band``
+summed over the passes and the rows ``reflected_by_band`` / ``absorbed_by_band`` are printed beside the shell counts.  With ``--reemit``
+the ground glows between 2e-21 and 6.6e-20 J and the source shines between 2.8e-19 and 9.9e-19 J: try
+``--ground-bands 1e-21,1e-19,1e-18:0.02,0.3 --gas 0,50000,2e-5 --reemit --shells`` -- a ground that takes nearly all of the infrared that
+the gas sends back down and reflects a third of the sunlight.  One launch per light step.
 ``--camera X,Y,Z:NX,NY,NZ:RADIUS:FOV_DEG:PIXELS`` puts an instrument into the scene: a DetectorMeasureStep, a disc of RADIUS metres about
 (X, Y, Z) (metres from the Earth's centre) whose normal (NX, NY, NZ) points from the detector into the scene, with a square field of
 view of FOV_DEG degrees to either side and PIXELS x PIXELS pixels, e.g. ``--camera 6471000,0,0:-1,0,0:20000:60:32`` looks straight down
@@ -85,6 +93,16 @@ if "--ground" in argv:
     albedo = 0.3
     if at + 1 < len(argv) and not argv[at + 1].startswith("--"):
         albedo = float(argv.pop(at + 1))
+bands = None
+if "--ground-bands" in argv:
+    at = argv.index("--ground-bands")
+    try:
+        parts = [[float(x) for x in part.split(",")] for part in (argv.pop(at + 1) if at + 1 < len(argv) else "").split(":")]
+        bands = dict(E_edges=parts[0], albedo=parts[1], specular=0.0 if len(parts) < 3 else parts[2][0] if len(parts[2]) == 1 else parts[2])
+        if len(parts) > 3:
+            raise ValueError
+    except (ValueError, IndexError):
+        sys.exit("--ground-bands E1,E2,...:a1,a2,...[:s1,...]: the band edges in joules, an albedo per band and the mirrored share (one, or per band)")
 phase = None
 if "--phase" in argv:
     at = argv.index("--phase")
@@ -139,8 +157,9 @@ if "--ocean" in argv:
         sys.exit("--ocean N: the refractive index of the water, e.g. 1.33")
     if reemit is not None:
         sys.exit("--ocean and --reemit: the re-emitting ground stands at the surface")
-    if albedo is None:
+    if albedo is None and bands is None:
         albedo = 0.0                                           # a black sea floor
+ground = albedo if bands is None else bands                    # None: no ground; a number: a grey one; --ground-bands' tables: a spectral one
 OCEAN_DEPTH = 6000.0                                           # two moves: the floor is not passed within the move into the water
 camera = None
 if "--camera" in argv:
@@ -179,7 +198,7 @@ if omega0 is not None and len(omega0) > 1:                     # one value per a
 
 
 def run(ground):
-    """One run of the step list, with the reflecting ground (``ground``: its albedo) or without (None)."""
+    """One run of the step list, with the reflecting ground (``ground``: its albedo, or the tables of a spectral one) or without (None)."""
     sim = phys.Simulation(cl_on=True, seed=1234, exit=lambda cond: cond.t >= dt * (passes - 0.5))
     sim.add_step(0, phys.UpdateTimeStep(lambda c: dt))
     sim.add_step(1, newton.NewtonianKinematicsStep())
@@ -226,7 +245,8 @@ def run(ground):
         red = light.ShellCrossingMeasureStep(None, [R], E_bins=[0.999 * grid.min(), 1.001 * grid.max()], measure_n=False)
         sim.add_step("infrared", red)
     if ground is not None:                                     # last in the pass: the tally before it sees the incoming move
-        floor = light.SurfaceReflectStep(R - (OCEAN_DEPTH if ocean is not None else 0.0), albedo=ground)
+        depth = OCEAN_DEPTH if ocean is not None else 0.0
+        floor = light.SpectralSurfaceStep(R - depth, **ground) if isinstance(ground, dict) else light.SurfaceReflectStep(R - depth, albedo=ground)
         sim.add_step(8, floor)
     sea = None
     if ocean is not None:                                      # behind the sea floor, before the lamp: where a ground would stand
@@ -250,13 +270,13 @@ def run(ground):
 
 
 bare_top = None
-if albedo is not None and "--shells" in sys.argv:              # the same run without the ground, for the top-of-atmosphere count
+if ground is not None and "--shells" in sys.argv:              # the same run without the ground, for the top-of-atmosphere count
     bare = run(None)
     bare_top = int(sum(row[2][3] for row in bare[5].data))
     print("without the ground: %d photons x %d steps in %.2f s" % (n, len(bare[0].ts), bare[0].run_time))
     bare[0].close(download=False)
     del bare
-sim, signs, shells, profile, image, tally, floor, angles, medium, lamp, vapour, eye, glow, sea = run(albedo)
+sim, signs, shells, profile, image, tally, floor, angles, medium, lamp, vapour, eye, glow, sea = run(ground)
 steps = len(sim.ts)
 print("source:", source)
 print("%d photons x %d steps in %.2f s  ->  %.3g particle-steps/s" % (n, steps, sim.run_time, n * steps / sim.run_time))
@@ -286,10 +306,16 @@ if tally is not None:
     for row in tally.data[-3:]:
         print("[t, N, out, in]:", float(row[0]), row[1], row[2].tolist(), row[3].tolist())
     print("escapes through 100 km by direction cosine against the vertical, 10 bins over [-1, 1]:", np.sum([row[4][3] for row in tally.data], axis=0).tolist())
-if floor is not None:
+if floor is not None and bands is not None:
+    sums = [sum(int(row[k]) for row in floor.data) for k in range(1, 5)]
+    print("the spectral ground (%d bands): %d reflected, %d absorbed, %d mirrored, %d out of band over %d passes" % (len(floor.albedo), *sums, len(floor.data)))
+    for b, (lo, hi) in enumerate(zip(floor.E_edges[:-1], floor.E_edges[1:])):
+        print("  %.3g - %.3g J (albedo %g, specular %g): %d reflected, %d absorbed" % (
+            lo, hi, floor.albedo[b], floor.specular[b], sum(int(row[5][b]) for row in floor.data), sum(int(row[6][b]) for row in floor.data)))
+elif floor is not None:
     print("the ground (albedo %g, lambertian): %d reflected, %d absorbed over %d passes" % (albedo, sum(int(row[1]) for row in floor.data), sum(int(row[2]) for row in floor.data), len(floor.data)))
-    if tally is not None:
-        print("outward through the top of the atmosphere (100 km): %d with the ground, %d without" % (int(sum(row[2][3] for row in tally.data)), bare_top))
+if floor is not None and tally is not None:
+    print("outward through the top of the atmosphere (100 km): %d with the ground, %d without" % (int(sum(row[2][3] for row in tally.data)), bare_top))
 if sea is not None:
     names = ("in_refracted", "in_reflected", "out_refracted", "out_reflected", "out_total", "overshot")
     sums = np.sum([[int(x) for x in list(row)[1:]] for row in sea.data], axis=0).tolist()

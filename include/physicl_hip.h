@@ -1057,6 +1057,50 @@ int pcl_step_refract_surface(pcl_ctx *ctx, double radius, const double *center_h
                              double c, uint64_t seed, uint32_t pass,
                              int64_t *counts_out_host /* [6]: in refracted, in reflected, out refracted, out reflected, out total, overshot */);
 
+/* A spectral ground (SpectralSurfaceStep): pcl_step_surface_reflect's sphere with an albedo and a mirrored share that depend on the
+ * band the photon's energy falls in -- vegetation, snow, water, a ground that is black in the infrared -- in ONE sweep of the resident
+ * store.  It stands where the ground stands: the last call of a pass (before pcl_step_reemit_parked and pcl_step_recycle_spent), and a
+ * pass has ONE ground: this call shares the ground's counter words 8 and 9.  Nothing is removed; the ground stays opaque.  E is read
+ * and never written; ids and kinds are not touched.  All arithmetic is fp64, unfused, every operation rounded once, in the order
+ * written; an fp32 store's values are widened first (exact) and what is written is rounded once to the store's dtype.
+ *   E_edges_host: B + 1 finite, strictly increasing doubles in the unit E is stored in, 1 <= B <= PCL_SPECTRAL_MAX_BANDS;
+ *   albedo_host, specular_host: B doubles in [0, 1] each.  center_host: 3 finite doubles, NULL = the origin.
+ *   hit  iff  q_now < R2 and R2 <= q_prev and q_prev < inf, a photon             (pcl_step_surface_reflect's test, its d, m, p, q)
+ *   e = (double)E;  band b: pcl_step_absorb_path's rule for E_edges -- numpy.histogram's bins [E_b, E_(b+1)), the last one closed;
+ *   e < E_0, e > E_B or a NaN: NO BAND -- the photon is absorbed and counted in out_of_band, nothing is drawn
+ *   albedo_b < 1:  u = u53(w0, w1) of the counter (id_lo, id_hi, pass, 9);  reflected iff u < albedo_b   (albedo_b == 1: reflected, no draw)
+ *   reflected and 0 < specular_b < 1:  u = u53(w0, w1) of the counter (id_lo, id_hi, pass, 22);  mirrored iff u < specular_b
+ *   reflected and specular_b == 1: mirrored, no draw;  specular_b == 0: not mirrored, no draw
+ *   t, x, nrm, sa, w: pcl_step_surface_reflect's lines, operation for operation
+ *   absorbed:      r = center + x;  v = 0;  dr = x - p;  dv = 0 - v_old                                    (the ground's park)
+ *   mirrored:      mh = m / sa;  dn = mh.nrm;  dir = mh - (2*dn)*nrm                                       (the ground's specular line)
+ *   not mirrored:  (u_a, u_b) of the counter (id_lo, id_hi, pass, 8);  mu = sqrt(1 - u_a);  dir as the ground's lambertian lines
+ *   reflected:     v = c*dir;  dv = v - v_old;  dr = w*dir;  r = center + (x + dr)
+ * So with one band that holds every energy of the store and specular = 0 (1) the store is left bit for bit as
+ * pcl_step_surface_reflect leaves it in PCL_SURFACE_LAMBERTIAN (PCL_SURFACE_SPECULAR) with that albedo, seed and pass.
+ * The Philox4x32-10 block has the key (seed_lo, seed_hi), u53 of pcl_store_apply_source; ``pass`` is the caller's own counter.
+ * The word 22 is used by nothing else (scatter kernels 0 and 1, fill and source 2..5, pcl_step_surface_reflect and this call 8 and 9,
+ * pcl_step_phase_redirect 10 and 11, pcl_step_absorb_scattered 12, pcl_step_phase_layered 13, pcl_step_recycle_spent 14, 15 and 16,
+ * pcl_step_absorb_path 17, pcl_step_reemit_parked 18, 19 and 20, pcl_step_refract_surface 21: 0-5 and 8-21 are taken), so every
+ * other step draws what it drew, and a photon meets the same fate however the run is sharded.
+ * counts_out_host[0] = reflected, [1] = absorbed (those in no band among them), [2] = mirrored (of the reflected), [3] = out_of_band;
+ * bands_out_host[0 .. B) = reflected by band, [B .. 2B) = absorbed by band (a photon in no band is in neither), by this call.
+ * A store that is not uniform costs the host traffic it costs pcl_step_surface_reflect; the ids go along unless every albedo and
+ * every specular is 1.  Asking for E costs a wavelength-dependent scatter step its term cache, every pass (the library has no
+ * read-only access to E), as pcl_step_absorb_path's bands do.
+ * PCL_ERR_ARG (NULL edges, albedo, specular, counts or bands, B outside 1 .. PCL_SPECTRAL_MAX_BANDS, edges that are not finite and
+ * strictly increasing, an albedo or a specular outside [0, 1] or NaN, radius not positive / not finite / its square not finite, a
+ * centre or c that is not finite) is returned before the store is looked at -- by the group's entry point before the group is --,
+ * and nothing is launched or written; PCL_ERR_STATE without a store; an empty store answers zeros without a launch.  Host pointers;
+ * one device allocation per call, handed back on every way out; synchronises once, with the copy of the tallies.
+ * pcl_last_error() is generic, as for pcl_step_surface_reflect, whose source file these two entry points share
+ * (physicl_amd/csrc/pcl_surface.hip). */
+#define PCL_SPECTRAL_MAX_BANDS 1024
+int pcl_step_ground_spectral(pcl_ctx *ctx, double radius, const double *center_host, int n_bands, const double *E_edges_host,
+                             const double *albedo_host, const double *specular_host, double c, uint64_t seed, uint32_t pass,
+                             int64_t *counts_out_host /* [4]: reflected, absorbed, mirrored, out_of_band */,
+                             int64_t *bands_out_host /* [2][B]: reflected by band, absorbed by band */);
+
 /* ---- Device groups: several GPUs from ONE process ---------------------------------------------------------------
  * The reference is a single process with one simulation thread (physicl/__init__.py:400-432, 501-524); this is how
  * a host written against this ABI uses a node's GPUs the same way, without one process per GPU.  A group owns one
@@ -1161,6 +1205,11 @@ int pcl_group_step_reemit_parked(pcl_group *group, int n_layers, const double *e
  * checked once for the group, before the group is looked at (ids are global: the same photons meet the same fate) */
 int pcl_group_step_refract_surface(pcl_group *group, double radius, const double *center_host, double n_inside, double n_outside,
                                    int fresnel, double c, uint64_t seed, uint32_t pass, int64_t *counts_out_host);
+/* pcl_step_ground_spectral on every shard (side by side), the four counts and the two rows by band summed over the group's devices;
+ * the arguments are checked once for the group, before the group is looked at (ids are global: the same photons meet the same fate) */
+int pcl_group_step_ground_spectral(pcl_group *group, double radius, const double *center_host, int n_bands, const double *E_edges_host,
+                                   const double *albedo_host, const double *specular_host, double c, uint64_t seed, uint32_t pass,
+                                   int64_t *counts_out_host, int64_t *bands_out_host);
 
 /* ---------------------------------------------------------------- the counters' collective (one process per GPU)
  * The path shards by global index with no data-path exchange; the only global quantities are the int64

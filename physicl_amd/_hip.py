@@ -36,6 +36,7 @@ LPHASE_MAX_LAWS, LPHASE_MAX_LAYERS, LPHASE_MAX_NODES, LPHASE_MAX_TOTAL_NODES = 8
 RECYCLE_MAX_BINS = 1024                                                      # PCL_RECYCLE_MAX_BINS: bins of a RecycleStep's spectrum
 PATH_ABSORB_MAX_LAYERS, PATH_ABSORB_MAX_BANDS, PATH_ABSORB_MAX_CELLS = 64, 1024, 4096          # PCL_PATH_ABSORB_MAX_LAYERS ...
 REEMIT_MAX_LAYERS, REEMIT_MAX_BINS, REEMIT_MAX_TOTAL_BINS = 64, 1024, 2048                      # PCL_REEMIT_MAX_LAYERS ...
+SPECTRAL_MAX_BANDS = 1024                                                    # PCL_SPECTRAL_MAX_BANDS: bands of a SpectralSurfaceStep
 REEMIT_LAWS = {"isotropic": 0, "lambertian": 1}                              # the flags of pcl_step_reemit_parked's lambertian_host
 PROF_NEWTON, PROF_SCATTER, PROF_DELETE_MASK, PROF_COMPACT, PROF_COUNTERS, PROF_FUSED, PROF_MULTI, PROF_ONEPASS, \
     PROF_DELETE_AHEAD = range(9)
@@ -167,6 +168,7 @@ _PROTOTYPES = {
     "pcl_step_absorb_path": [_vp, c_int, c_int, _vp, _vp, _vp, _vp, c_uint64, c_uint32, _vp, _vp],
     "pcl_step_reemit_parked": [_vp, c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, c_double, c_uint64, c_uint32, _vp],
     "pcl_step_refract_surface": [_vp, c_double, _vp, c_double, c_double, c_int, c_double, c_uint64, c_uint32, _vp],
+    "pcl_step_ground_spectral": [_vp, c_double, _vp, c_int, _vp, _vp, _vp, c_double, c_uint64, c_uint32, _vp, _vp],
     # device groups: several GPUs from one process (the C-level counterpart of physicl_amd.multidev.MultiDevice)
     "pcl_group_create": [c_int, POINTER(c_int), POINTER(_vp)],
     "pcl_group_destroy": [_vp],
@@ -202,6 +204,7 @@ _PROTOTYPES = {
     "pcl_group_step_absorb_path": [_vp, c_int, c_int, _vp, _vp, _vp, _vp, c_uint64, c_uint32, _vp, _vp],
     "pcl_group_step_reemit_parked": [_vp, c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, c_double, c_uint64, c_uint32, _vp],
     "pcl_group_step_refract_surface": [_vp, c_double, _vp, c_double, c_double, c_int, c_double, c_uint64, c_uint32, _vp],
+    "pcl_group_step_ground_spectral": [_vp, c_double, _vp, c_int, _vp, _vp, _vp, c_double, c_uint64, c_uint32, _vp, _vp],
 }
 EXPORTS = sorted(list(_PROTOTYPES) + ["pcl_last_error"])
 
@@ -539,6 +542,25 @@ def _refract(entry, handle, radius, center, n_inside, n_outside, fresnel, c, see
     check(entry(handle, float(radius), None if ce is None else ce.ctypes.data, float(n_inside), float(n_outside), int(bool(fresnel)),
                 float(c), int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_pass) & 0xFFFFFFFF, counts.ctypes.data))
     return counts
+
+
+def _ground_spectral(entry, handle, radius, center, E_edges, albedo, specular, c, seed, n_pass):
+    """One call of pcl_step_ground_spectral / pcl_group_step_ground_spectral: (counts int64[4] -- reflected, absorbed, mirrored,
+    out_of_band --, reflected_by_band int64[B], absorbed_by_band int64[B]) of this call.  ``albedo``: one value per band of ``E_edges``;
+    ``specular``: one value for every band, or one per band; ``n_pass``: the caller's own pass counter (a Philox counter word)."""
+    Ee = np.ascontiguousarray(E_edges, dtype=np.float64).reshape(-1)
+    B = len(Ee) - 1
+    al = np.ascontiguousarray(albedo, dtype=np.float64).reshape(-1)
+    sp = np.asarray(specular, dtype=np.float64).reshape(-1)
+    sp = np.ascontiguousarray(np.repeat(sp, B) if len(sp) == 1 else sp)
+    if not len(al) == len(sp) == B:
+        raise ValueError("albedo and specular hold %d and %d values for %d bands" % (len(al), len(sp), B))
+    ce = None if center is None else np.ascontiguousarray(center, dtype=np.float64).reshape(3)
+    counts = np.zeros(4, dtype=np.int64)
+    bands = np.zeros((2, max(B, 1)), dtype=np.int64)
+    check(entry(handle, float(radius), None if ce is None else ce.ctypes.data, B, Ee.ctypes.data, al.ctypes.data, sp.ctypes.data, float(c),
+                int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_pass) & 0xFFFFFFFF, counts.ctypes.data, bands.ctypes.data))
+    return counts, bands[0].copy(), bands[1].copy()
 
 
 def _scatter(sc, required=False, lazy=False, empty_expr=b""):
@@ -1159,6 +1181,14 @@ class Device:
         out total, overshot.  light._refract_surface restates the sweep with numpy."""
         return _refract(self.lib.pcl_step_refract_surface, self.ctx, radius, center, n_inside, n_outside, fresnel, c, seed, n_pass)
 
+    def ground_spectral(self, radius, E_edges, albedo, specular=0.0, center=None, c=0.0, seed=0, n_pass=0):
+        """The photons of the resident store whose last move took them into the sphere of ``radius`` about ``center`` put back as
+        ``Device.surface_reflect`` puts them, with the albedo and the mirrored share of the band their energy falls in (``E_edges``:
+        B + 1 edges, ``albedo``: B values, ``specular``: one value or B), in one sweep (pcl_step_ground_spectral); a hit photon in no
+        band is absorbed.  ``(counts int64[4]: reflected, absorbed, mirrored, out_of_band; reflected_by_band int64[B];
+        absorbed_by_band int64[B])``.  light._spectral_bounce restates the sweep with numpy."""
+        return _ground_spectral(self.lib.pcl_step_ground_spectral, self.ctx, radius, center, E_edges, albedo, specular, c, seed, n_pass)
+
 
 class DeviceGroup:
     """``pcl_group_*``: several contexts in one process, sharded by global index, behind the C ABI (the shim owns the
@@ -1294,6 +1324,10 @@ class DeviceGroup:
     def refract_surface(self, radius, n_inside, n_outside=1.0, center=None, fresnel=True, c=0.0, seed=0, n_pass=0):
         """``Device.refract_surface`` on every context of the group, the counts summed (pcl_group_step_refract_surface)."""
         return _refract(self.lib.pcl_group_step_refract_surface, self.g, radius, center, n_inside, n_outside, fresnel, c, seed, n_pass)
+
+    def ground_spectral(self, radius, E_edges, albedo, specular=0.0, center=None, c=0.0, seed=0, n_pass=0):
+        """``Device.ground_spectral`` on every context of the group, the tallies summed (pcl_group_step_ground_spectral)."""
+        return _ground_spectral(self.lib.pcl_group_step_ground_spectral, self.g, radius, center, E_edges, albedo, specular, c, seed, n_pass)
 
     def download(self, field, n=None, offset=0, dtype=None):
         n = self.count - offset if n is None else n

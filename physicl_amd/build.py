@@ -82,6 +82,19 @@ def described_sweeps_of(unit):
     return sweeps_of(unit) + INTERFACE_SWEEPS.get(os.path.basename(unit["src"]), ())
 
 
+# The spectral ground's sweep, in the same form (tests/test_spectral_surface_cpu.py holds it to it): the ground by energy band stands
+# beside the grey one, whose arithmetic and counter words it shares.  Neither function above folds this table in -- the tests of the
+# older sweeps hold both to their contents --; every_sweep_of() is every sweep a unit holds.
+SPECTRAL_SWEEPS = {
+    "pcl_surface.hip": (_sweep("pcl_step_ground_spectral", "pcl_group_step_ground_spectral", "k_ground_spectral"),),
+}
+
+
+def every_sweep_of(unit):
+    """Every sweep a unit of ADDONS holds, in the file's order: described_sweeps_of(unit), then what SPECTRAL_SWEEPS adds."""
+    return described_sweeps_of(unit) + SPECTRAL_SWEEPS.get(os.path.basename(unit["src"]), ())
+
+
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -ffp-contract=off: the reference's kernels must be evaluated unfused (bit-exact parity, DESIGN.md)
 # -disable-machine-licm: the pre-RA pass hoists every scalar constant out of the kernels' long loops, the scalar register file

@@ -159,6 +159,25 @@
 //   refracted: dir_k = eta*mh_k + (ec - ct)*N_k
 //   v_k = c*dir_k;  dv_k = v_k - v_old_k;  dr_k = w*dir_k;  y_k = x_k + dr_k;  r_k = center_k + y_k
 //   overshot iff y.y >= R2 where the outcome ends inside (in refracted, out reflected, out total), y.y < R2 where it ends outside
+//
+// A spectral ground (SpectralSurfaceStep): the ground with an albedo and a mirrored share that depend on the band the photon's energy
+// falls in -- vegetation, snow, water, a ground that is black in the infrared.  The ground's geometry, parking and flight; the band is
+// k_absorb_path's lookup of E.  A hit photon in no band is absorbed: the ground stays opaque.
+//
+//   k_ground_spectral<T>   k_surface_reflect's sweep of r and dr (48 B a slot in fp64).  Only hit lanes go on: they load their kind, E
+//                          and id, look the band up, draw (word 9 iff albedo_b < 1, the word of its own iff 0 < specular_b < 1) and
+//                          meet the others at four ballots + popcounts per wave (reflected, absorbed, mirrored, out of band); then
+//                          they add to their band's cell (an LDS atomic per lane), load v and write r, v, dr, dv as the ground does.
+//                          The tables (albedo, specular, energy edges: 24 KiB at 1024 bands) sit in dynamic LDS in front of the
+//                          workgroup-private uint32 cells [reflected, absorbed, mirrored, out of band | reflected by band |
+//                          absorbed by band].  E, ids and kinds are never written.
+//
+// Operation order (what light._spectral_bounce restates with numpy):
+//   hit: the ground's test;  e: the bin of (double)E in the energy edges, the last one closed (NaN and outside: no band)
+//   no band: absorbed, out of band.  albedo_e < 1: u = u53(w0, w1) of counter (id_lo, id_hi, pass, 9); reflected iff u < albedo_e
+//   reflected and 0 < specular_e < 1: u = u53(w0, w1) of counter (id_lo, id_hi, pass, 22); mirrored iff u < specular_e
+//   (specular_e == 1: mirrored, == 0: not);  absorbed: the ground's park;  mirrored: the ground's specular line;  otherwise the
+//   ground's lambertian lines with counter (id_lo, id_hi, pass, 8);  reflected: the ground's flight of the rest of the move
 #include "pcl_sweep.h"
 
 #include "pcl_device.h" // (after the HIP runtime and the ABI's header, which pcl_sweep.h brings)
@@ -967,6 +986,135 @@ __global__ void __launch_bounds__(kBlock) k_refract_surface(refract_args<T> a) {
         if (s_cnt[k]) atomicAdd(&a.out[k], (unsigned long long)s_cnt[k]);
 }
 
+// The counter word of the draw that decides between the mirror and Lambert (the header lists who uses which word: 22 is this
+// kernel's alone; the ground's own draws keep the ground's words 8 and 9).
+constexpr uint32_t kSpectralMirrorDraw = 22;
+
+template <typename T>
+struct gspectral_args {
+    T *r[3], *v[3], *dr[3], *dv[3];
+    const T *E;
+    const unsigned char *kind;   // NULL: every particle is a photon
+    const int64_t *ids;          // NULL: the id of slot i is id_base + i
+    const double *tables;        // albedo (B) | specular (B) | E edges (B + 1), device
+    unsigned long long *out;     // reflected, absorbed, mirrored, out of band | reflected by band [B] | absorbed by band [B]; device, zeroed
+    int64_t N, ts, id_base;      // particles, tile stride of the slab (elements), id of slot 0
+    int tile_log;                // log2 of the tile length
+    int n_E;                     // B >= 1
+    double c[3], R2, speed;
+    uint32_t k0, k1, pass;       // Philox key (seed_lo, seed_hi), the step's own pass counter
+};
+
+template <typename T>
+__global__ void __launch_bounds__(kBlock) k_ground_spectral(gspectral_args<T> a) {
+    extern __shared__ double s_mem[];                                  // albedo | specular | E edges | the four counts | by band, twice
+    const int nE = a.n_E;
+    const int n_tab = 3 * nE + 1, n_cells = 4 + 2 * nE;
+    const double *s_alb = s_mem;
+    const double *s_spec = s_alb + nE;
+    const double *s_E = s_spec + nE;
+    uint32_t *s_cnt = reinterpret_cast<uint32_t *>(s_mem + n_tab);
+    uint32_t *s_refl = s_cnt + 4;
+    uint32_t *s_gone = s_refl + nE;
+    for (int k = threadIdx.x; k < n_tab; k += kBlock) s_mem[k] = a.tables[k];
+    for (int k = threadIdx.x; k < n_cells; k += kBlock) s_cnt[k] = 0;  // (the bands' cells follow the four counts)
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int64_t stride = grid_stride(), n_round = whole_waves(a.N);   // (the ballots below need whole waves inside the loop)
+    for (int64_t i = first_slot(); i < n_round; i += stride) {
+        const bool in = i < a.N;
+        const int64_t ti = tile_index(i, a.tile_log, a.ts);
+        double d[3] = {0.0, 0.0, 0.0}, m[3] = {0.0, 0.0, 0.0}, p[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            if (in) {
+                d[k] = __dsub_rn((double)a.r[k][ti], a.c[k]);           // fp32 widens exactly
+                m[k] = (double)a.dr[k][ti];
+            }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) p[k] = __dsub_rn(d[k], m[k]);
+        const double q_now = dot3(d, d), q_prev = dot3(p, p);
+        // the ground's hit (NaN: false)
+        bool hit = in && q_now < a.R2 && q_prev >= a.R2 && q_prev < INFINITY;
+        if (hit && a.kind) hit = a.kind[i] != 0;
+        uint64_t id = 0;
+        int band = -1;                                                  // -1: in no band, absorbed
+        bool refl = false, mirror = false;
+        if (hit) {
+            const double e = (double)a.E[ti];                           // fp32 widens exactly
+            if (e >= s_E[0] && e <= s_E[nE]) band = bin_of(s_E, nE, e); // (closed_bin: k_absorb_path's lookup) NaN and under/overflow: in no band
+        }
+        if (band >= 0) {
+            const double alb = s_alb[band], sp = s_spec[band];
+            id = id_of(a.ids, a.id_base, i);
+            refl = true;
+            if (alb < 1.0) refl = first_u53(pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, 9u, a.k0, a.k1)) < alb;   // the ground's draw
+            mirror = refl && sp >= 1.0;
+            if (refl && sp > 0.0 && sp < 1.0)
+                mirror = first_u53(pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, kSpectralMirrorDraw, a.k0, a.k1)) < sp;
+        }
+        const uint32_t n_hit = (uint32_t)__popcll(__ballot(hit)), n_refl = (uint32_t)__popcll(__ballot(refl));
+        const uint32_t n_mirror = (uint32_t)__popcll(__ballot(mirror)), n_none = (uint32_t)__popcll(__ballot(hit && band < 0));
+        if (lane == 0 && n_refl) atomicAdd(&s_cnt[0], n_refl);
+        if (lane == 0 && n_hit - n_refl) atomicAdd(&s_cnt[1], n_hit - n_refl);
+        if (lane == 0 && n_mirror) atomicAdd(&s_cnt[2], n_mirror);
+        if (lane == 0 && n_none) atomicAdd(&s_cnt[3], n_none);
+        if (!hit) continue;     // lanes that are not hit wait at the loop's head: no ballot below this line
+        if (band >= 0) atomicAdd(refl ? &s_refl[band] : &s_gone[band], 1u);
+        const double aq = dot3(m, m), b = dot3(p, m), cq = __dsub_rn(q_prev, a.R2);
+        const double disc = fmax(__dsub_rn(__dmul_rn(b, b), __dmul_rn(aq, cq)), 0.0);
+        const double t = __ddiv_rn(cq, __dsub_rn(__dsqrt_rn(disc), b));
+        double x[3], nrm[3], vo[3], dir[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            x[k] = __dadd_rn(p[k], __dmul_rn(t, m[k]));
+            vo[k] = (double)a.v[k][ti];
+        }
+        if (!refl) {            // absorbed: the ground's park, on the sphere, at rest
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                a.r[k][ti] = (T)__dadd_rn(a.c[k], x[k]);
+                a.v[k][ti] = (T)0.0;
+                a.dr[k][ti] = (T)__dsub_rn(x[k], p[k]);
+                a.dv[k][ti] = (T)__dsub_rn(0.0, vo[k]);
+            }
+            continue;
+        }
+        const double xn = __dsqrt_rn(dot3(x, x)), sa = __dsqrt_rn(aq);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) nrm[k] = __ddiv_rn(x[k], xn);
+        if (mirror) {
+            double mh[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) mh[k] = __ddiv_rn(m[k], sa);
+            const double dn2 = __dmul_rn(2.0, dot3(mh, nrm));
+#pragma unroll
+            for (int k = 0; k < 3; ++k) dir[k] = __dsub_rn(mh[k], __dmul_rn(dn2, nrm[k]));
+        } else {
+            double u_a, u_b, sc, ss, e1[3], e2[3];
+            pair_u53(pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, 8u, a.k0, a.k1), &u_a, &u_b);   // the ground's block
+            const double mu = __dsqrt_rn(__dsub_rn(1.0, u_a));                                       // cosine-weighted hemisphere
+            polar(mu, u_b, &sc, &ss);
+            frame(nrm, e1, e2);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) dir[k] = turned(sc, ss, mu, e1[k], e2[k], nrm[k]);
+        }
+        const double w = __dmul_rn(__dsub_rn(1.0, t), sa);              // the rest of the move, flown along the new direction
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double vk = __dmul_rn(a.speed, dir[k]), drk = __dmul_rn(w, dir[k]);
+            a.r[k][ti] = (T)__dadd_rn(a.c[k], __dadd_rn(x[k], drk));
+            a.v[k][ti] = (T)vk;
+            a.dr[k][ti] = (T)drk;
+            a.dv[k][ti] = (T)__dsub_rn(vk, vo[k]);
+        }
+    }
+    __syncthreads();
+    // pcl_sweep::flush_cells, written out, for the reason given in k_absorb_scattered: the count is not a literal
+    for (int k = threadIdx.x; k < n_cells; k += kBlock)
+        if (s_cnt[k]) atomicAdd(&a.out[k], (unsigned long long)s_cnt[k]);
+}
+
 struct surface_spec { // a call's arguments, checked
     double c[3] = {0.0, 0.0, 0.0};
     double R2 = 0.0, albedo = 1.0, speed = 0.0;
@@ -1685,6 +1833,95 @@ int group_refract_surface(pcl_group *group, double radius, const double *center_
     });
 }
 
+struct gspectral_spec { // a call's arguments, checked; what the kernel reads
+    int n_E = 0;
+    double c[3] = {0.0, 0.0, 0.0};
+    double R2 = 0.0, speed = 0.0;
+    bool draws = false;         // some band has albedo < 1 or specular < 1: the ids are needed
+    std::vector<double> tables; // albedo | specular | E edges
+    size_t cells() const { return (size_t)4 + 2 * (size_t)n_E; }      // reflected, absorbed, mirrored, out of band | by band, twice
+    size_t lds() const { return tables.size() * sizeof(double) + cells() * sizeof(uint32_t); }
+    spans out(int64_t *counts, int64_t *bands) const { return {{counts, 4}, {bands, cells() - 4}}; }
+};
+
+// Everything PCL_ERR_ARG stands for except the NULL context; nothing is launched or written before this has passed.
+bool check_gspectral(double radius, const double *center, int n_E, const double *E_edges, const double *albedo, const double *specular,
+                     double c, const int64_t *counts_out, const int64_t *bands_out, gspectral_spec &s) {
+    if (!counts_out || !bands_out || !E_edges || !albedo || !specular || n_E < 1 || n_E > PCL_SPECTRAL_MAX_BANDS) return false;
+    s.R2 = radius * radius;
+    if (!std::isfinite(radius) || !(radius > 0) || !std::isfinite(s.R2) || !std::isfinite(c)) return false;
+    if (center) {
+        if (!finite3(center)) return false;
+        for (int k = 0; k < 3; ++k) s.c[k] = center[k];
+    }
+    s.n_E = n_E; s.speed = c;
+    for (const double *tab : {albedo, specular})
+        for (int k = 0; k < n_E; ++k) {
+            if (!(tab[k] >= 0.0 && tab[k] <= 1.0)) return false;        // (NaN as well)
+            s.draws = s.draws || tab[k] < 1.0;                          // (specular < 1: somebody may leave by Lambert's block)
+            s.tables.push_back(tab[k]);
+        }
+    return check_edges(E_edges, n_E, kEdgePlain, &s.tables);
+}
+
+template <typename T>
+int launch_gspectral(pcl_ctx *ctx, const store_view &v, const gspectral_spec &s, uint64_t seed, uint32_t pass, const staged &st) {
+    gspectral_args<T> a{};
+    for (int k = 0; k < 3; ++k) {
+        void *r = nullptr, *vel = nullptr, *dr = nullptr, *dv = nullptr;
+        PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_R0 + k, &r));
+        PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_V0 + k, &vel));
+        PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_DR0 + k, &dr));
+        PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_DV0 + k, &dv));
+        a.r[k] = static_cast<T *>(r); a.v[k] = static_cast<T *>(vel);
+        a.dr[k] = static_cast<T *>(dr); a.dv[k] = static_cast<T *>(dv);
+        a.c[k] = s.c[k];
+    }
+    // E is always asked for (the band is the point of the call): the pointer costs a wavelength-dependent scatter step its term
+    // cache (pcl_shell.hip), every pass.
+    void *E = nullptr;
+    PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_E, &E));
+    a.E = static_cast<const T *>(E); a.kind = st.kind; a.ids = st.ids; a.tables = st.tables; a.out = st.out;
+    a.N = v.N; a.ts = v.ts; a.id_base = st.id_base; a.tile_log = v.tile_log; a.n_E = s.n_E;
+    a.R2 = s.R2; a.speed = s.speed;
+    a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32); a.pass = pass;
+    const size_t lds = s.lds();                                         // 56 B for one band, 32 KiB for 1024
+    const int64_t grid = balanced_grid(v.N, v.n_cu, resident_per_cu(lds));
+    hipLaunchKernelGGL(k_ground_spectral<T>, dim3((unsigned)grid), dim3(kBlock), lds, v.stream, a);
+    return hipGetLastError() == hipSuccess ? PCL_OK : PCL_ERR_HIP;
+}
+
+int ground_spectral(pcl_ctx *ctx, double radius, const double *center_host, int n_bands, const double *E_edges_host,
+                    const double *albedo_host, const double *specular_host, double c, uint64_t seed, uint32_t pass,
+                    int64_t *counts_out_host, int64_t *bands_out_host) {
+    gspectral_spec s;
+    if (!ctx || !check_gspectral(radius, center_host, n_bands, E_edges_host, albedo_host, specular_host, c, counts_out_host, bands_out_host, s))
+        return bad_argument(ctx);
+    const spans out = s.out(counts_out_host, bands_out_host);
+    store_view v;
+    staged st(ctx);
+    PCL_SWEEP_TRY(open_store(ctx, PCL_R0, &v));
+    zero_spans(out);
+    if (v.N <= 0) return PCL_OK;
+    PCL_SWEEP_TRY(stage(st, v, s.cells(), s.tables.data(), s.tables.size(), s.draws));   // the ids only if somebody may draw
+    PCL_SWEEP_TRY(PCL_SWEEP_LAUNCH(v, launch_gspectral, ctx, v, s, seed, pass, st));
+    return fetch(st, out);
+}
+
+int group_ground_spectral(pcl_group *group, double radius, const double *center_host, int n_bands, const double *E_edges_host,
+                          const double *albedo_host, const double *specular_host, double c, uint64_t seed, uint32_t pass,
+                          int64_t *counts_out_host, int64_t *bands_out_host) {
+    gspectral_spec s;                                                   // the arguments first: a refused call looks at no group
+    if (!check_gspectral(radius, center_host, n_bands, E_edges_host, albedo_host, specular_host, c, counts_out_host, bands_out_host, s))
+        return bad_argument(nullptr);
+    std::vector<pcl_ctx *> ctx;
+    PCL_SWEEP_TRY(shards_of(group, ctx));
+    if (ctx.empty()) return bad_argument(nullptr);
+    return sum_shards(ctx, s.out(counts_out_host, bands_out_host), [&](pcl_ctx *one, int64_t *p) {
+        return pcl_step_ground_spectral(one, radius, center_host, n_bands, E_edges_host, albedo_host, specular_host, c, seed, pass, p, p + 4);
+    });
+}
+
 } // namespace
 
 extern "C" {
@@ -1806,6 +2043,24 @@ int pcl_group_step_refract_surface(pcl_group *group, double radius, const double
                                    int fresnel, double c, uint64_t seed, uint32_t pass, int64_t *counts_out_host) {
     return guarded([&] {
         return group_refract_surface(group, radius, center_host, n_inside, n_outside, fresnel, c, seed, pass, counts_out_host);
+    });
+}
+
+int pcl_step_ground_spectral(pcl_ctx *ctx, double radius, const double *center_host, int n_bands, const double *E_edges_host,
+                             const double *albedo_host, const double *specular_host, double c, uint64_t seed, uint32_t pass,
+                             int64_t *counts_out_host, int64_t *bands_out_host) {
+    return guarded([&] {
+        return ground_spectral(ctx, radius, center_host, n_bands, E_edges_host, albedo_host, specular_host, c, seed, pass, counts_out_host,
+                               bands_out_host);
+    });
+}
+
+int pcl_group_step_ground_spectral(pcl_group *group, double radius, const double *center_host, int n_bands, const double *E_edges_host,
+                                   const double *albedo_host, const double *specular_host, double c, uint64_t seed, uint32_t pass,
+                                   int64_t *counts_out_host, int64_t *bands_out_host) {
+    return guarded([&] {
+        return group_ground_spectral(group, radius, center_host, n_bands, E_edges_host, albedo_host, specular_host, c, seed, pass,
+                                     counts_out_host, bands_out_host);
     });
 }
 

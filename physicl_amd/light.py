@@ -1031,18 +1031,32 @@ def _surface_bounce(r, dr, v, photon, ids, radius, center, albedo, mode, c, seed
     arrays; rows of particles that are not hit are the arguments', zeros in ``dv``), ``hit, reflected, absorbed`` boolean masks, and of the hit
     particles (NaN elsewhere) ``t``, ``x`` (the hit point about the centre), ``nrm`` and -- lambertian -- ``mu``."""
     r, dr, v = (np.array(a, dtype=np.float64).reshape(-1, 3) for a in (r, dr, v))
-    n = len(r)
     center, c, R2 = np.asarray(center, dtype=np.float64), np.float64(c), np.float64(radius) * np.float64(radius)
+    hit, p, q_prev = _ground_hits(r, dr, photon, R2, center)
+    ids = np.asarray(ids).reshape(-1)[hit]
+    refl = np.ones(len(ids), dtype=bool)
+    if albedo < 1.0:
+        refl = _philox_block(ids, seed, n_pass, 9)[0] < albedo
+    return _ground_bounce(r, dr, v, hit, p, q_prev, ids, refl, np.full(len(ids), mode == "specular"), R2, center, c, seed, n_pass, dtype)
+
+
+def _ground_hits(r, dr, photon, R2, center):
+    """The ground's hit test, once: (hit, p, q_prev) -- a photon with q_now < R2 <= q_prev < inf, d = r - center, p = d - dr."""
     with np.errstate(invalid="ignore", over="ignore"):
         d = r - center
         p = d - dr
         q_now, q_prev = _dot3(d, d), _dot3(p, p)
         hit = (q_now < R2) & (q_prev >= R2) & (q_prev < np.inf) & np.asarray(photon, dtype=bool).reshape(-1)
+    return hit, p, q_prev
+
+
+def _ground_bounce(r, dr, v, hit, p, q_prev, ids, refl, mirror, R2, center, c, seed, n_pass, dtype):
+    """The ground's hit point, parking and flight, once, for ``_surface_bounce`` and ``_spectral_bounce``: of the ``hit`` particles
+    (``ids``, ``refl``, ``mirror``: one value each) those with ``refl`` are reflected -- mirrored where ``mirror``, otherwise
+    cosine-weighted about the normal with the block of counter word 8 (drawn for every hit lane that is not ``mirror``: ``mu``) --
+    and the others parked on the sphere.  ``_surface_bounce``'s dict; ``r``, ``dr`` and ``v`` are written in place."""
+    n = len(r)
     at = np.flatnonzero(hit)
-    ids = np.asarray(ids).reshape(-1)[at]
-    refl = np.ones(len(at), dtype=bool)
-    if albedo < 1.0:
-        refl = _philox_block(ids, seed, n_pass, 9)[0] < albedo
     out = {"hit": hit, "reflected": np.zeros(n, dtype=bool), "absorbed": np.zeros(n, dtype=bool),
            "t": np.full(n, np.nan), "x": np.full((n, 3), np.nan), "nrm": np.full((n, 3), np.nan), "mu": np.full(n, np.nan)}
     out["reflected"][at[refl]], out["absorbed"][at[~refl]] = True, True
@@ -1054,14 +1068,13 @@ def _surface_bounce(r, dr, v, photon, ids, radius, center, albedo, mode, c, seed
         x = p + t[:, None] * m
         nrm = x / np.sqrt(_dot3(x, x))[:, None]
         sa = np.sqrt(a)
-        if mode == "specular":
-            mh = m / sa[:, None]
-            direction = mh - (2.0 * _dot3(mh, nrm))[:, None] * nrm
-        else:
-            u_a, u_b = _philox_block(ids, seed, n_pass, 8)
-            mu = np.sqrt(1.0 - u_a)                            # cosine-weighted hemisphere
-            direction = _turn_about(nrm, mu, u_b)
-            out["mu"][at] = mu
+        mh = m / sa[:, None]
+        direction = mh - (2.0 * _dot3(mh, nrm))[:, None] * nrm  # mirrored
+        lam = np.flatnonzero(~mirror)
+        u_a, u_b = _philox_block(ids[lam], seed, n_pass, 8)
+        mu = np.sqrt(1.0 - u_a)                                # cosine-weighted hemisphere
+        direction[lam] = _turn_about(nrm[lam], mu, u_b)
+        out["mu"][at[lam]] = mu
         w = (1.0 - t) * sa
         v_new = c * direction
         dr_new = w[:, None] * direction
@@ -1136,6 +1149,149 @@ class SurfaceReflectStep(tally.WriterStep):
         new = _surface_bounce(tally.vec3(objs, "r"), tally.vec3(objs, "dr"), tally.vec3(objs, "v"), _photons(objs), ids,
                               self.radius, self.center, self.albedo, self.mode, _c_h_literals()[0], seed, self._pass)
         return new, new["hit"], (new["reflected"].sum(), new["absorbed"].sum())
+
+
+# ---------------------------------------------------------------------------------------------- a spectral ground
+_SPECTRAL_MIRROR_WORD = 22                                     # mirror or Lambert: the counter word (the header lists the words taken)
+_SPECTRAL_COUNTS = ("reflected", "absorbed", "mirrored", "out_of_band")
+
+
+def _check_spectral_surface(radius, albedo, E_edges, center, specular):
+    """(radius, albedo [B], energy edges [B + 1], centre, specular [B]) of a SpectralSurfaceStep as float64, or ValueError for
+    everything pcl_step_ground_spectral would refuse."""
+    from ._hip import SPECTRAL_MAX_BANDS                       # (the header's limit: one place)
+    radius = _radius(radius, "radius", "radius must be a number")
+    E_edges = tally.check_edges("E_edges", E_edges, SPECTRAL_MAX_BANDS)        # PathAbsorptionStep(E_edges=)'s rule
+    B = len(E_edges) - 1
+    tables = []
+    for name, x, one in (("albedo", albedo, False), ("specular", specular, True)):
+        try:
+            x = np.array(x, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("%s must be numbers, one per band of E_edges" % name) from None
+        if one and x.shape == ():
+            x = np.repeat(x, B)
+        if x.shape != (B,):
+            raise ValueError("%s must hold one value per band of E_edges (%d)%s, got the shape %r" % (name, B, " or be one number" if one else "", x.shape))
+        if not np.all((x >= 0.0) & (x <= 1.0)):                # (False for NaN as well)
+            raise ValueError("%s must lie in [0, 1], got %r" % (name, x.tolist()))
+        tables.append(np.ascontiguousarray(x))
+    return radius, tables[0], E_edges, tally.check_center(center), tables[1]
+
+
+def _spectral_bounce(r, dr, v, E, photon, ids, radius, center, albedo, specular, E_edges, c, seed, n_pass, dtype=np.float64):
+    """What pcl_step_ground_spectral makes of (n, 3) float64 positions, last moves and velocities, the energies, who is a photon and
+    the particles' ids, with numpy -- ``_surface_bounce``'s arithmetic (``_ground_hits``, ``_ground_bounce``) behind the band lookup
+    of ``_absorb_path`` (``_bin_of``) and the draws of include/physicl_hip.h: word 9 iff ``albedo_b < 1``, word 22 by a reflected lane
+    iff ``0 < specular_b < 1``, word 8 for Lambert.  ``albedo``, ``specular``: B values each, ``E_edges``: B + 1.  ``_surface_bounce``'s
+    dict -- ``absorbed`` includes ``out_of_band`` -- plus ``band`` (int64: of every hit photon, -1 for none and elsewhere), the masks
+    ``mirrored`` and ``out_of_band``, and the tallies ``reflected_by_band``, ``absorbed_by_band`` (int64 [B])."""
+    r, dr, v = (np.array(a, dtype=np.float64).reshape(-1, 3) for a in (r, dr, v))
+    n = len(r)
+    center, c, R2 = np.asarray(center, dtype=np.float64), np.float64(c), np.float64(radius) * np.float64(radius)
+    albedo, specular, E_edges = (np.asarray(a, dtype=np.float64).reshape(-1) for a in (albedo, specular, E_edges))
+    B = len(E_edges) - 1
+    hit, p, q_prev = _ground_hits(r, dr, photon, R2, center)
+    ids = np.asarray(ids).reshape(-1)[hit]
+    b = _bin_of(np.asarray(E, dtype=np.float64).reshape(-1)[hit], E_edges)     # NaN and under/overflow: in no band
+    inside = b >= 0
+    alb, sp = np.where(inside, albedo[np.fmax(b, 0)], 0.0), np.where(inside, specular[np.fmax(b, 0)], 1.0)
+    refl = inside.copy()
+    draws = np.flatnonzero(inside & (alb < 1.0))
+    refl[draws] = _philox_block(ids[draws], seed, n_pass, 9)[0] < alb[draws]
+    mirror = sp >= 1.0                                         # (a lane that is not reflected: whether Lambert's block is looked at -- ``mu``)
+    draws = np.flatnonzero(refl & (sp > 0.0) & (sp < 1.0))
+    mirror[draws] = _philox_block(ids[draws], seed, n_pass, _SPECTRAL_MIRROR_WORD)[0] < sp[draws]
+    out = _ground_bounce(r, dr, v, hit, p, q_prev, ids, refl, mirror, R2, center, c, seed, n_pass, dtype)
+    at = np.flatnonzero(hit)
+    out["band"] = np.full(n, -1, dtype=np.int64)
+    out["band"][at] = b
+    out["mirrored"], out["out_of_band"] = np.zeros(n, dtype=bool), np.zeros(n, dtype=bool)
+    out["mirrored"][at[refl & mirror]], out["out_of_band"][at[~inside]] = True, True
+    out["reflected_by_band"] = np.bincount(b[refl], minlength=B).astype(np.int64)
+    out["absorbed_by_band"] = np.bincount(b[inside & ~refl], minlength=B).astype(np.int64)
+    return out
+
+
+class SpectralSurfaceStep(tally.WriterStep):
+    """A ground whose albedo depends on the photon's energy (not in the reference): ``SurfaceReflectStep``'s sphere of ``radius`` about
+    ``center`` with, per energy band, the chance that a photon is reflected and the share of the reflected ones that is mirrored --
+    vegetation that is dark in the visible and bright in the near infrared, snow the other way round, water, a ground under a
+    ``ReemissionStep`` that absorbs nearly all of the infrared coming back down while it reflects a third of the sunlight.
+
+    * ``E_edges``: ``B + 1`` finite, strictly increasing energies in the unit ``E`` is stored in, ``1 <= B <= 1024``:
+      ``numpy.histogram``'s bins, the last one closed -- ``PathAbsorptionStep(E_edges=)``'s rule and its lookup, on ``(double)E``.
+    * ``albedo``: ``B`` numbers in ``[0, 1]``; ``specular``: one number or ``B`` in ``[0, 1]``, the share of the reflected photons
+      that is mirrored; the others leave cosine-weighted about the local vertical.
+    * A hit photon whose ``E`` lies in no band (below, above, NaN) is absorbed and counted in ``out_of_band``: the ground stays opaque.
+
+    Who is hit, where, how an absorbed photon is parked (``r`` on the sphere, ``v = 0``, ``dr`` the move up to the hit point,
+    ``dv = -v_old``) and how a reflected one flies the rest of its move are ``SurfaceReflectStep``'s, operation for operation; so is the
+    placement: LAST in a pass, before a ``ReemissionStep`` or ``RecycleStep``, a ``ShellCrossingMeasureStep`` of the same radius in
+    front of it has ``in == reflected + absorbed``.  Plain ``Object``s and particles with a NaN in ``r`` or ``dr`` are never hit.
+
+    The draws a grey ground makes come from the grey ground's Philox blocks: reflect or absorb is word 9 (drawn iff
+    ``albedo_b < 1``), the lambertian direction word 8; only mirror-or-Lambert has a word of its own (22, drawn by a reflected photon
+    iff ``0 < specular_b < 1``).  With one band that holds every energy and ``specular=0`` the step leaves the store bit for bit as
+    ``SurfaceReflectStep(radius, center, albedo, "lambertian")`` does with the same seed, with ``specular=1`` as ``"specular"``.  Because
+    words 8 and 9 are shared a simulation holds ONE ground: the first run raises ValueError if the simulation also holds a
+    ``SurfaceReflectStep`` or a second ``SpectralSurfaceStep``.  The draws are made on the device with EVERY ``rng=`` setting, and the
+    step reads no ``dv`` rule, so it works under ``cl_on=False`` as well.
+
+    After each run ``reflected``, ``absorbed`` (``out_of_band`` among them), ``mirrored`` and ``out_of_band`` hold the pass's counts and
+    ``reflected_by_band`` / ``absorbed_by_band`` int64 arrays ``[B]``, global over shards and ranks; ``self.data`` gains the row ``[t,
+    reflected, absorbed, mirrored, out_of_band, reflected_by_band, absorbed_by_band]``; ``out_fn`` takes the rows at the end.  The
+    rule is written out in include/physicl_hip.h (pcl_step_ground_spectral); ``_spectral_bounce`` restates it with numpy.
+
+    The sweep reads ``E`` and never writes it.  Asking for ``E`` costs a wavelength-dependent scatter step its term cache, which is
+    dropped every pass (the library has no read-only access to E) -- what ``PathAbsorptionStep(E_edges=)`` costs it, and a grey
+    ``SurfaceReflectStep`` does not.
+
+    One launch per light step: the K-passes-per-launch kernels cannot bounce a photon between two of their passes, and
+    ``sim.launch_note`` says so.  On host-resident objects (``step.run(sim)`` outside a device loop) the same state is made with
+    numpy, the ids being the places in the object list."""
+    _NOTE = "one launch per light step: a SpectralSurfaceStep bounces photons off its sphere behind every pass, which the " \
+            "K-passes-per-launch kernels cannot carry"
+    _writes = ("r", "dr", "v", "dv")
+
+    def __init__(self, radius, albedo, E_edges, center=(0, 0, 0), specular=0.0, out_fn=None):
+        MeasureStep.__init__(self, out_fn)
+        self.radius, self.albedo, self.E_edges, self.center, self.specular = _check_spectral_surface(radius, albedo, E_edges, center, specular)
+        self._record_counts(np.zeros(4, dtype=np.int64), np.zeros((2, len(self.albedo)), dtype=np.int64))
+        self._pass = 0                                   # the step's own Philox counter word: one per run
+
+    def _record_counts(self, counts, bands):
+        for name, x in zip(_SPECTRAL_COUNTS, counts):
+            setattr(self, name, int(x))
+        bands = np.array(bands, dtype=np.int64).reshape(2, len(self.albedo))
+        self.reflected_by_band, self.absorbed_by_band = bands[0].copy(), bands[1].copy()
+
+    def _record_pass(self, sim, reflected, absorbed, mirrored, out_of_band, bands):
+        self._record_counts((reflected, absorbed, mirrored, out_of_band), bands)
+        self.data.append(tally.object_row([tally._snap(sim.t)] + [getattr(self, name) for name in _SPECTRAL_COUNTS] +
+                                          [self.reflected_by_band.copy(), self.absorbed_by_band.copy()]))
+
+    def _refuse(self, sim):                              # words 8 and 9 are the ground's: a simulation holds one ground
+        steps = getattr(sim, "steps", None) or {}
+        others = [s for s in (steps.values() if hasattr(steps, "values") else steps)
+                  if s is not self and isinstance(s, (SurfaceReflectStep, SpectralSurfaceStep))]
+        if others:
+            raise ValueError("a simulation holds one ground: this SpectralSurfaceStep shares the counter words 8 and 9 with the %s "
+                             "that is among the steps as well" % type(others[0]).__name__)
+
+    def _sweep(self, sim, prep):
+        counts, refl, gone = sim._dev.ground_spectral(self.radius, self.E_edges, self.albedo, self.specular, self.center,
+                                                      _c_h_literals()[0], sim.seed, self._pass)
+        return [np.asarray(counts, dtype=np.int64), np.stack([np.asarray(refl, dtype=np.int64), np.asarray(gone, dtype=np.int64)])]
+
+    def _host_sweep(self, objs, ids, seed, prep):
+        E, photon = tally.photon_energies(objs, PhotonObject)
+        new = _spectral_bounce(tally.vec3(objs, "r"), tally.vec3(objs, "dr"), tally.vec3(objs, "v"), E, photon, ids, self.radius,
+                               self.center, self.albedo, self.specular, self.E_edges, _c_h_literals()[0], seed, self._pass)
+        return new, new["hit"], (new["reflected"].sum(), new["absorbed"].sum(), new["mirrored"].sum(), new["out_of_band"].sum(),
+                                 np.stack([new["reflected_by_band"], new["absorbed_by_band"]]))
+
+    terminate = tally.TallyStep.terminate                # (a row holds arrays: written as the tally steps write theirs, as plain lists)
 
 
 # ---------------------------------------------------------------------------------------------- refraction
