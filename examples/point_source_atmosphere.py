@@ -4,7 +4,7 @@ examples (n(r) = 2.5e25 m^-3 * exp(-(|r| - 6371 km) / 8.6 km)) with photons that
 
     python examples/point_source_atmosphere.py [n_photons] [passes] [--cone | --beam-down | --default] [--profile] [--shells]
                                                [--ground [ALBEDO]] [--phase rayleigh | hg:G | isotropic] [--omega0 W | W1,W2,...]
-                                               [--cloud LO,HI[,G]] [--recycle [TOP]] [--gas LO,HI,K[,EMIN,EMAX]] [--blue-sky]
+                                               [--cloud LO,HI[,G]] [--cloud-tau TAU] [--recycle [TOP]] [--gas LO,HI,K[,EMIN,EMAX]] [--blue-sky]
                                                [--reemit [TG[,TA]]] [--ocean N] [--ground-bands E1,E2,...:a1,a2,...[:s1,...]]
                                                [--camera X,Y,Z:NX,NY,NZ:RADIUS:FOV_DEG:PIXELS]
 
@@ -34,6 +34,10 @@ printed beside the top-of-atmosphere and ground counts.
 function scatters by Rayleigh's law everywhere and, between the altitudes LO and HI, by a mixture of one part Rayleigh and nine
 parts Henyey-Greenstein with the mean cosine G (default 0.85).  One launch per light step; the photons re-directed per layer and
 per law are printed beside the shell counts.  Not together with ``--phase``: a pass holds one phase step.
+``--cloud-tau TAU`` (with ``--cloud``) gives that cloud its own optical thickness: a LayeredScatterStep with the scattering coefficient
+``TAU / (HI - LO)`` per metre between LO and HI, behind the clear air's scatter step and in front of the LayeredPhaseStep, which then
+turns the cloud's hits about the direction they came from.  ``exposed``, ``scattered`` and ``scattered_by_cell`` summed over the passes
+are printed beside the shell counts.  Without it the cloud changes the phase function only and the output is as it was.
 ``--recycle [TOP]`` (an altitude in metres, default 100 km) makes the source a continuous one: a RecycleStep at the end of every pass
 gives the slots of the photons at rest (absorbed by the ground or the medium) and of those above TOP back to the source.  The
 population stays constant; the emission rate (photons recycled per pass) and the counts at rest and through the top are printed as
@@ -121,6 +125,15 @@ if "--cloud" in argv:
     if phase is not None:
         sys.exit("--cloud and --phase: a pass holds one phase step")
     cloud = (cloud[0], cloud[1], cloud[2] if len(cloud) == 3 else 0.85)
+cloud_tau = None
+if "--cloud-tau" in argv:
+    at = argv.index("--cloud-tau")
+    try:
+        cloud_tau = float(argv.pop(at + 1))
+    except (IndexError, ValueError):
+        cloud_tau = -1.0
+    if cloud is None or not 0.0 <= cloud_tau < float("inf"):
+        sys.exit("--cloud-tau TAU: the cloud's optical thickness, not negative, together with --cloud LO,HI[,G]")
 recycle_top = None
 if "--recycle" in argv:
     at = argv.index("--recycle")
@@ -211,6 +224,10 @@ def run(ground):
         medium = light.AbsorptionStep(omega0[0] if layer_edges is None else omega0, edges=layer_edges)
         sim.add_step("absorb", medium)
     angles = light.PhaseFunctionStep(*phase) if phase is not None else None
+    droplets = None
+    if cloud_tau is not None:                                  # behind the clear air's scatter step, in front of the phase step: first=False
+        droplets = light.LayeredScatterStep([cloud_tau / (cloud[1] - cloud[0])], edges=[R + cloud[0], R + cloud[1]])
+        sim.add_step("cloud", droplets)
     if cloud is not None:                                      # from the Earth's centre to 1000 km up: Rayleigh, but for the cloud
         angles = light.LayeredPhaseStep(["rayleigh", ("hg", cloud[2])], CLOUD_WEIGHTS, edges=[0.0, R + cloud[0], R + cloud[1], R + 1000e3])
     if angles is not None:                                     # directly behind the scatter step (steps run in the order they were added)
@@ -266,7 +283,7 @@ def run(ground):
     sim.join()
     if sim.error is not None:
         raise sim.error
-    return sim, signs, shells, profile, image, tally, floor, angles, medium, lamp, vapour, eye, glow, sea
+    return sim, signs, shells, profile, image, tally, floor, angles, medium, lamp, vapour, eye, glow, sea, droplets
 
 
 bare_top = None
@@ -276,7 +293,7 @@ if ground is not None and "--shells" in sys.argv:              # the same run wi
     print("without the ground: %d photons x %d steps in %.2f s" % (n, len(bare[0].ts), bare[0].run_time))
     bare[0].close(download=False)
     del bare
-sim, signs, shells, profile, image, tally, floor, angles, medium, lamp, vapour, eye, glow, sea = run(ground)
+sim, signs, shells, profile, image, tally, floor, angles, medium, lamp, vapour, eye, glow, sea, droplets = run(ground)
 steps = len(sim.ts)
 print("source:", source)
 print("%d photons x %d steps in %.2f s  ->  %.3g particle-steps/s" % (n, steps, sim.run_time, n * steps / sim.run_time))
@@ -291,6 +308,10 @@ if cloud is not None:
     print("cloud between %g and %g km (0.1 rayleigh + 0.9 hg, g = %g) in a rayleigh atmosphere: %d photons scattered, %d re-directed over %d passes" % (
         cloud[0] / 1e3, cloud[1] / 1e3, cloud[2], sum(int(row[1]) for row in angles.data), sum(int(row[2]) for row in angles.data), len(angles.data)))
     print("  by_layer [below, cloud, above]: %s   by_law [rayleigh, hg]: %s" % (by_layer.tolist(), by_law.tolist()))
+    if droplets is not None:
+        print("  the cloud's own optical thickness %g (k = %g per m, first=%s): %d photons exposed, %d scattered over %d passes; scattered_by_cell %s" % (
+            cloud_tau, droplets.k[0, 0], droplets.first, sum(int(row[1]) for row in droplets.data), sum(int(row[2]) for row in droplets.data),
+            len(droplets.data), np.sum([row[3] for row in droplets.data], axis=0).tolist()))
 elif angles is not None:
     print("phase function %s (g = %g): %d photons re-directed over %d passes" % (angles.phase, angles.g, sum(int(row[1]) for row in angles.data), len(angles.data)))
 if profile is not None and profile.data:

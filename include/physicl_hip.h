@@ -1101,6 +1101,58 @@ int pcl_step_ground_spectral(pcl_ctx *ctx, double radius, const double *center_h
                              int64_t *counts_out_host /* [4]: reflected, absorbed, mirrored, out_of_band */,
                              int64_t *bands_out_host /* [2][B]: reflected by band, absorbed by band */);
 
+/* Scattering by layer and band (LayeredScatterStep): who scatters, with a scattering coefficient that depends on the radial layer a
+ * photon stands in and on the band its energy falls in -- a cloud's optical depth, an aerosol spectrum beside the Rayleigh one, a
+ * drop in vacuum.  The scattering twin of pcl_step_absorb_path: called behind pcl_step_newton (alone, or behind the scatter kernels
+ * with first = 0) and before the phase, absorption and ground calls of the pass, it scatters in ONE sweep of the resident store.  A
+ * photon moves c*dt in every pass, so the path length is not read from the store: the host makes the probability of scattering per
+ * pass, p = -expm1(-k * (c*dt)), and the device only ever sees p.  Nothing is removed; r, dr, E, ids and kinds are never written.
+ * All arithmetic is fp64, unfused, every operation rounded once, in the order written; an fp32 store's values are widened first
+ * (exact) and what is written is rounded once to the store's dtype.  L' = max(n_layers, 1), B' = max(n_E_bins, 1).
+ *   a particle that is not a photon (kind 0) is skipped and never written.
+ *   at rest   iff  v0 == 0 and v1 == 0 and v2 == 0            (-0.0 counts as 0; a NaN in v: moving).  A slot with v0 != 0 is decided
+ *                  by v0 alone and loads neither v1 nor v2; a slot at rest loads nothing more.
+ *   layer b, band e:  pcl_step_absorb_path's lines, character for character -- n_layers == 0: b = 0, r is not read;  otherwise
+ *                  d = r - center;  q = (d0*d0 + d1*d1) + d2*d2;  b = the layer with e2_b <= q < e2_(b+1), the last one closed, no
+ *                  square root is taken;  n_E_bins == 0: e = 0, E is neither read nor asked for;  otherwise e = the bin of E (widened
+ *                  to double) in E_edges_host: [E_e, E_(e+1)), the last one closed;  a NaN, a photon outside the edges: skipped
+ *   exposed   =    a moving photon with a layer and a band;  p = p_host[b * B' + e]
+ *   p == 0:        nothing is drawn.   p > 0:  u = u53(w0, w1) of the counter (id_lo, id_hi, pass, 23);  scattered iff u < p
+ *   scattered:     (u_a, u_b) = (u53(w0, w1), u53(w2, w3)) of the counter (id_lo, id_hi, pass, 24);  w = (1, 0, 0);  mu = 1 - 2*u_a;
+ *                  e1, e2 = the frame about w, sc, ss of (mu, u_b) and the direction (sc*e1_k + ss*e2_k) + mu*w_k as written out for
+ *                  pcl_step_surface_reflect (frame, polar, turned), the same sin / cos -- pcl_step_reemit_parked's isotropic lines,
+ *                  operation for operation: uniform on the sphere
+ *                  v_k = c * direction_k;  dv_k = v_k - v_old_k         (both from the widened old velocity, rounded once: the
+ *                  scatter kernels' mark, as pcl_step_phase_redirect writes it)
+ *   not scattered: first == 0:  the particle is not written at all -- a mark an earlier scatterer of the pass left in dv survives
+ *                  first == 1:  dv = 0 for every photon that is not scattered, exposed or not, at rest or not -- the scatter
+ *                  kernels' contract for the first scatterer of a pass: dv != 0 then reads "scattered in this pass"
+ * So a pcl_step_phase_redirect or pcl_step_phase_layered call behind this one turns its hits about v - dv, the direction before the
+ * scatter, and pcl_step_absorb_scattered gives them a single-scattering albedo; a photon two scatterers of a pass both hit has
+ * scattered twice, and a phase call turns it about the direction after the first.  A hit whose new velocity equals the old one bit
+ * for bit reads as a miss, as with the scatter kernels.  The Philox4x32-10 blocks have the key (seed_lo, seed_hi), u53 of
+ * pcl_store_apply_source; ``pass`` is the caller's own counter.  The words 23 and 24 are used by nothing else (scatter kernels 0 and
+ * 1, fill and source 2..5, pcl_step_surface_reflect and pcl_step_ground_spectral 8 and 9, pcl_step_phase_redirect 10 and 11,
+ * pcl_step_absorb_scattered 12, pcl_step_phase_layered 13, pcl_step_recycle_spent 14, 15 and 16, pcl_step_absorb_path 17,
+ * pcl_step_reemit_parked 18, 19 and 20, pcl_step_refract_surface 21, pcl_step_ground_spectral 22: 0-5 and 8-22 are taken), so every
+ * other step draws what it drew, and a photon scatters the same way however the run is sharded.
+ * p_host, edges_host, E_edges_host, center_host: as for pcl_step_absorb_path, with PCL_SCATTER_LAYERED_MAX_LAYERS, _BANDS and _CELLS
+ * equal to its limits for the same budget: a workgroup's uint32 cells (16 KiB), the probabilities (32 KiB) and the two edge tables
+ * stay below 64 KiB of LDS.  first: 0 or 1.  ``c`` = the speed of light in code units.
+ * counts_out_host[0] = photons exposed, [1] = scattered, by this call;  cells_out_host[b * B' + e] = scattered in layer b and band e.
+ * A store that is not uniform costs the host traffic it costs pcl_step_surface_reflect; the ids go along only if some p > 0.
+ * PCL_ERR_ARG (everything pcl_step_absorb_path refuses, a first that is neither 0 nor 1, a c that is not finite) is returned before
+ * the store is looked at -- by the group's entry point before the group is --, and nothing is launched or written; PCL_ERR_STATE
+ * without a store; an empty store answers zeros without a launch.  Host pointers; one device allocation per call, handed back on
+ * every way out; synchronises once, with the copy of the tallies.  pcl_last_error() is generic, as for pcl_step_surface_reflect,
+ * whose source file these two entry points share (physicl_amd/csrc/pcl_surface.hip). */
+#define PCL_SCATTER_LAYERED_MAX_LAYERS 64
+#define PCL_SCATTER_LAYERED_MAX_BANDS 1024
+#define PCL_SCATTER_LAYERED_MAX_CELLS 4096 /* L' * B' */
+int pcl_step_scatter_layered(pcl_ctx *ctx, int n_layers, int n_E_bins, const double *p_host, const double *edges_host,
+                             const double *center_host, const double *E_edges_host, int first, double c, uint64_t seed, uint32_t pass,
+                             int64_t *counts_out_host /* [2]: exposed, scattered */, int64_t *cells_out_host /* [L' * B'] */);
+
 /* ---- Device groups: several GPUs from ONE process ---------------------------------------------------------------
  * The reference is a single process with one simulation thread (physicl/__init__.py:400-432, 501-524); this is how
  * a host written against this ABI uses a node's GPUs the same way, without one process per GPU.  A group owns one
@@ -1210,6 +1262,11 @@ int pcl_group_step_refract_surface(pcl_group *group, double radius, const double
 int pcl_group_step_ground_spectral(pcl_group *group, double radius, const double *center_host, int n_bands, const double *E_edges_host,
                                    const double *albedo_host, const double *specular_host, double c, uint64_t seed, uint32_t pass,
                                    int64_t *counts_out_host, int64_t *bands_out_host);
+/* pcl_step_scatter_layered on every shard (side by side), the counts and the cells summed over the group's devices; the arguments
+ * are checked once for the group, before the group is looked at (ids are global: the same photons scatter the same way) */
+int pcl_group_step_scatter_layered(pcl_group *group, int n_layers, int n_E_bins, const double *p_host, const double *edges_host,
+                                   const double *center_host, const double *E_edges_host, int first, double c, uint64_t seed,
+                                   uint32_t pass, int64_t *counts_out_host, int64_t *cells_out_host);
 
 /* ---------------------------------------------------------------- the counters' collective (one process per GPU)
  * The path shards by global index with no data-path exchange; the only global quantities are the int64

@@ -37,6 +37,7 @@ RECYCLE_MAX_BINS = 1024                                                      # P
 PATH_ABSORB_MAX_LAYERS, PATH_ABSORB_MAX_BANDS, PATH_ABSORB_MAX_CELLS = 64, 1024, 4096          # PCL_PATH_ABSORB_MAX_LAYERS ...
 REEMIT_MAX_LAYERS, REEMIT_MAX_BINS, REEMIT_MAX_TOTAL_BINS = 64, 1024, 2048                      # PCL_REEMIT_MAX_LAYERS ...
 SPECTRAL_MAX_BANDS = 1024                                                    # PCL_SPECTRAL_MAX_BANDS: bands of a SpectralSurfaceStep
+SCATTER_LAYERED_MAX_LAYERS, SCATTER_LAYERED_MAX_BANDS, SCATTER_LAYERED_MAX_CELLS = 64, 1024, 4096       # PCL_SCATTER_LAYERED_MAX_LAYERS ...
 REEMIT_LAWS = {"isotropic": 0, "lambertian": 1}                              # the flags of pcl_step_reemit_parked's lambertian_host
 PROF_NEWTON, PROF_SCATTER, PROF_DELETE_MASK, PROF_COMPACT, PROF_COUNTERS, PROF_FUSED, PROF_MULTI, PROF_ONEPASS, \
     PROF_DELETE_AHEAD = range(9)
@@ -169,6 +170,7 @@ _PROTOTYPES = {
     "pcl_step_reemit_parked": [_vp, c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, c_double, c_uint64, c_uint32, _vp],
     "pcl_step_refract_surface": [_vp, c_double, _vp, c_double, c_double, c_int, c_double, c_uint64, c_uint32, _vp],
     "pcl_step_ground_spectral": [_vp, c_double, _vp, c_int, _vp, _vp, _vp, c_double, c_uint64, c_uint32, _vp, _vp],
+    "pcl_step_scatter_layered": [_vp, c_int, c_int, _vp, _vp, _vp, _vp, c_int, c_double, c_uint64, c_uint32, _vp, _vp],
     # device groups: several GPUs from one process (the C-level counterpart of physicl_amd.multidev.MultiDevice)
     "pcl_group_create": [c_int, POINTER(c_int), POINTER(_vp)],
     "pcl_group_destroy": [_vp],
@@ -205,6 +207,7 @@ _PROTOTYPES = {
     "pcl_group_step_reemit_parked": [_vp, c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, c_double, c_uint64, c_uint32, _vp],
     "pcl_group_step_refract_surface": [_vp, c_double, _vp, c_double, c_double, c_int, c_double, c_uint64, c_uint32, _vp],
     "pcl_group_step_ground_spectral": [_vp, c_double, _vp, c_int, _vp, _vp, _vp, c_double, c_uint64, c_uint32, _vp, _vp],
+    "pcl_group_step_scatter_layered": [_vp, c_int, c_int, _vp, _vp, _vp, _vp, c_int, c_double, c_uint64, c_uint32, _vp, _vp],
 }
 EXPORTS = sorted(list(_PROTOTYPES) + ["pcl_last_error"])
 
@@ -561,6 +564,27 @@ def _ground_spectral(entry, handle, radius, center, E_edges, albedo, specular, c
     check(entry(handle, float(radius), None if ce is None else ce.ctypes.data, B, Ee.ctypes.data, al.ctypes.data, sp.ctypes.data, float(c),
                 int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_pass) & 0xFFFFFFFF, counts.ctypes.data, bands.ctypes.data))
     return counts, bands[0].copy(), bands[1].copy()
+
+
+def _scatter_layered(entry, handle, p, edges, center, E_edges, first, c, seed, n_pass):
+    """One call of pcl_step_scatter_layered / pcl_group_step_scatter_layered: (exposed, scattered, scattered_by_cell int64[L', B']).
+    ``p``: the probability of scattering per pass, L' = max(layers, 1) rows of B' = max(bands, 1) values (any shape of that size); the
+    edges go over as given (the library squares the radii); ``first``: the pass's first scatterer (a miss gets dv = 0) or not (a miss
+    is not written); ``n_pass``: the caller's own pass counter (a Philox counter word)."""
+    pr = np.ascontiguousarray(p, dtype=np.float64).reshape(-1)
+    ed = None if edges is None else np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+    Ee = None if E_edges is None else np.ascontiguousarray(E_edges, dtype=np.float64).reshape(-1)
+    L, B = (0 if e is None else len(e) - 1 for e in (ed, Ee))
+    rows, cols = max(L, 1), max(B, 1)
+    if len(pr) != rows * cols:
+        raise ValueError("p holds %d values for %d layers of %d bands" % (len(pr), rows, cols))
+    ce = None if center is None else np.ascontiguousarray(center, dtype=np.float64).reshape(3)
+    counts = np.zeros(2, dtype=np.int64)
+    cells = np.zeros((rows, cols), dtype=np.int64)
+    ptr = lambda a: None if a is None else a.ctypes.data                                                       # noqa: E731
+    check(entry(handle, L, B, pr.ctypes.data, ptr(ed), ptr(ce), ptr(Ee), int(bool(first)), float(c), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                int(n_pass) & 0xFFFFFFFF, counts.ctypes.data, cells.ctypes.data))
+    return int(counts[0]), int(counts[1]), cells
 
 
 def _scatter(sc, required=False, lazy=False, empty_expr=b""):
@@ -1189,6 +1213,13 @@ class Device:
         absorbed_by_band int64[B])``.  light._spectral_bounce restates the sweep with numpy."""
         return _ground_spectral(self.lib.pcl_step_ground_spectral, self.ctx, radius, center, E_edges, albedo, specular, c, seed, n_pass)
 
+    def scatter_layered(self, p, edges=None, center=None, E_edges=None, first=True, c=0.0, seed=0, n_pass=0):
+        """Scattering by layer and band: every moving photon with a layer and a band scatters with the probability ``p[layer][band]``
+        into a direction uniform on the sphere, ``dv = v' - v_old``; with ``first`` every other photon gets ``dv = 0``, without it
+        nothing else is written -- one sweep (pcl_step_scatter_layered).  ``(exposed, scattered, scattered_by_cell int64[L', B'])``.
+        ``n_pass``: the caller's own pass counter (a Philox counter word)."""
+        return _scatter_layered(self.lib.pcl_step_scatter_layered, self.ctx, p, edges, center, E_edges, first, c, seed, n_pass)
+
 
 class DeviceGroup:
     """``pcl_group_*``: several contexts in one process, sharded by global index, behind the C ABI (the shim owns the
@@ -1328,6 +1359,10 @@ class DeviceGroup:
     def ground_spectral(self, radius, E_edges, albedo, specular=0.0, center=None, c=0.0, seed=0, n_pass=0):
         """``Device.ground_spectral`` on every context of the group, the tallies summed (pcl_group_step_ground_spectral)."""
         return _ground_spectral(self.lib.pcl_group_step_ground_spectral, self.g, radius, center, E_edges, albedo, specular, c, seed, n_pass)
+
+    def scatter_layered(self, p, edges=None, center=None, E_edges=None, first=True, c=0.0, seed=0, n_pass=0):
+        """``Device.scatter_layered`` on every context of the group, the tallies summed (pcl_group_step_scatter_layered)."""
+        return _scatter_layered(self.lib.pcl_group_step_scatter_layered, self.g, p, edges, center, E_edges, first, c, seed, n_pass)
 
     def download(self, field, n=None, offset=0, dtype=None):
         n = self.count - offset if n is None else n

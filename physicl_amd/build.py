@@ -95,6 +95,19 @@ def every_sweep_of(unit):
     return described_sweeps_of(unit) + SPECTRAL_SWEEPS.get(os.path.basename(unit["src"]), ())
 
 
+# The medium's scattering by layer and band, in the same form (tests/test_scatter_layered_cpu.py holds it to it): path absorption's
+# twin stands beside it, whose tables and checks it shares.  None of the functions above folds this table in -- the tests of the older
+# sweeps hold all three to their contents --; all_sweeps_of() is every sweep a unit holds.
+MEDIUM_SWEEPS = {
+    "pcl_surface.hip": (_sweep("pcl_step_scatter_layered", "pcl_group_step_scatter_layered", "k_scatter_layered"),),
+}
+
+
+def all_sweeps_of(unit):
+    """Every sweep a unit of ADDONS holds, in the file's order: every_sweep_of(unit), then what MEDIUM_SWEEPS adds."""
+    return every_sweep_of(unit) + MEDIUM_SWEEPS.get(os.path.basename(unit["src"]), ())
+
+
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -ffp-contract=off: the reference's kernels must be evaluated unfused (bit-exact parity, DESIGN.md)
 # -disable-machine-licm: the pre-RA pass hoists every scalar constant out of the kernels' long loops, the scalar register file

@@ -178,6 +178,25 @@
 //   reflected and 0 < specular_e < 1: u = u53(w0, w1) of counter (id_lo, id_hi, pass, 22); mirrored iff u < specular_e
 //   (specular_e == 1: mirrored, == 0: not);  absorbed: the ground's park;  mirrored: the ground's specular line;  otherwise the
 //   ground's lambertian lines with counter (id_lo, id_hi, pass, 8);  reflected: the ground's flight of the rest of the move
+//
+// Scattering by layer and band (LayeredScatterStep): who scatters, decided per radial layer and energy band -- a cloud's optical
+// depth, an aerosol spectrum, a drop in vacuum.  k_absorb_path's exposure and draw against a probability made on the host; where that
+// sweep parks, this one turns the photon into a direction uniform on the sphere (k_reemit_parked's isotropic lines) and leaves the
+// scatter step's mark, dv = v' - v_old, for the phase and absorption sweeps behind it.
+//
+//   k_scatter_layered<T>   one grid-stride sweep: per slot the kind (a mixed store only) and v0 (a lane at rest loads v1 and v2 as well
+//                          and nothing more; a moving lane is decided by v0 alone); moving photons load, with layers, r and, with
+//                          bands, E, and look both up (k_absorb_path's searches); an exposed lane whose cell's p is not zero loads its
+//                          id and draws.  Two ballots + popcounts per wave for the two counters.  With ``first`` every photon lane
+//                          that is not hit stores zeros to its three dv rows -- one branch for the three rows, the whole wave in a
+//                          uniform store.  Hit lanes add to their cell, load what they have not loaded of v, draw a direction and write
+//                          v and dv.  The tables (p, squared edges, energy edges) sit in dynamic LDS in front of the workgroup-private
+//                          uint32 cells [exposed, scattered | by cell].  r, dr and E are never written.
+//
+// Operation order (what light._scatter_layered restates with numpy):
+//   moving, b, e, exposed, p = P[b][e]: k_absorb_path's lines;  p > 0: u = u53(w0, w1) of counter (id_lo, id_hi, pass, 23);
+//   scattered iff u < p:  (u_a, u_b) of counter (id_lo, id_hi, pass, 24);  w = (1, 0, 0);  mu = 1 - 2*u_a;  e1, e2 = frame(w);
+//   sc, ss = polar(mu, u_b);  v_k = c*turned;  dv_k = v_k - v_old_k;   first and a photon that is not scattered:  dv_k = 0
 #include "pcl_sweep.h"
 
 #include "pcl_device.h" // (after the HIP runtime and the ABI's header, which pcl_sweep.h brings)
@@ -1922,6 +1941,176 @@ int group_ground_spectral(pcl_group *group, double radius, const double *center_
     });
 }
 
+// ---- scattering by layer and band: the kernel stands with its host side, behind the older sweeps (their tests read the file by its order)
+// The counter words of a scattering by layer and band: who scatters, where to (the header lists who uses which word: 23 and 24
+// are this kernel's alone).
+constexpr uint32_t kLayeredScatterDraw = 23, kLayeredScatterDir = 24;
+
+template <typename T>
+struct lscatter_args {
+    const T *r[3];               // read only with layers
+    T *v[3], *dv[3];
+    const T *E;                  // NULL without energy bands
+    const unsigned char *kind;   // NULL: every particle is a photon
+    const int64_t *ids;          // NULL: the id of slot i is id_base + i
+    const double *tables;        // p (L' x B') | e*e of the layer edges (L + 1, if L) | E edges (B + 1, if B), device
+    unsigned long long *out;     // exposed, scattered | scattered by cell [L' x B']; device, zeroed by the entry point
+    int64_t N, ts, id_base;      // particles, tile stride of the slab (elements), id of slot 0
+    int tile_log;                // log2 of the tile length
+    int n_layers, n_E;           // L (0: one row of p everywhere, L' = 1), B (0: one column for every energy, B' = 1)
+    int first;                   // 1: the pass's first scatterer -- a photon that is not scattered gets dv = 0
+    double c[3], speed;
+    uint32_t k0, k1, pass;       // Philox key (seed_lo, seed_hi), the step's own pass counter
+};
+
+template <typename T>
+__global__ void __launch_bounds__(kBlock) k_scatter_layered(lscatter_args<T> a) {
+    extern __shared__ double s_mem[];                                  // p | e*e | E edges | exposed, scattered | by cell
+    const int L = a.n_layers, Lp = L > 0 ? L : 1, nE = a.n_E, Bp = nE > 0 ? nE : 1;
+    const int n_tab = Lp * Bp + (L ? L + 1 : 0) + (nE ? nE + 1 : 0);
+    const int n_cells = 2 + Lp * Bp;
+    const double *s_p = s_mem;
+    const double *s_e2 = s_p + Lp * Bp;
+    const double *s_E = s_e2 + (L ? L + 1 : 0);
+    uint32_t *s_cnt = reinterpret_cast<uint32_t *>(s_mem + n_tab);
+    uint32_t *s_cell = s_cnt + 2;
+    for (int k = threadIdx.x; k < n_tab; k += kBlock) s_mem[k] = a.tables[k];
+    for (int k = threadIdx.x; k < n_cells; k += kBlock) s_cnt[k] = 0;  // (the cells follow the two counts)
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int64_t stride = grid_stride(), n_round = whole_waves(a.N);   // (the ballots below need whole waves inside the loop)
+    for (int64_t i = first_slot(); i < n_round; i += stride) {
+        const bool in = i < a.N;
+        const int64_t ti = tile_index(i, a.tile_log, a.ts);
+        bool photon = in;
+        if (photon && a.kind) photon = a.kind[i] != 0;                  // plain Objects are never touched
+        // moving: at_rest, written out as in k_absorb_path and negated -- -0.0 == 0, a NaN moves, v0 != 0 loads no more of v
+        const bool go = photon && !((double)a.v[0][ti] == 0.0 && (double)a.v[1][ti] == 0.0 && (double)a.v[2][ti] == 0.0);
+        int b = go && L == 0 ? 0 : -1;                                  // the layer; -1: in no layer
+        if (go && L > 0) {
+            double x[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) x[k] = __dsub_rn((double)a.r[k][ti], a.c[k]);   // fp32 widens exactly
+            const double q = dot3(x, x);
+            if (q >= s_e2[0] && q <= s_e2[L]) b = bin_of(s_e2, L, q);   // (dist2, closed_bin: written out) NaN: in no layer
+        }
+        int cell = b >= 0 && nE == 0 ? b : -1;                          // b * B' + e; -1: not exposed
+        if (b >= 0 && nE > 0) {
+            const double e = (double)a.E[ti];
+            if (e >= s_E[0] && e <= s_E[nE]) cell = b * nE + bin_of(s_E, nE, e);         // NaN and under/overflow: in no band
+        }
+        const bool exposed = cell >= 0;
+        bool hit = false;
+        uint64_t id = 0;
+        if (exposed) {
+            const double p = s_p[cell];
+            if (p > 0.0) {                                              // a clear cell draws nothing
+                id = id_of(a.ids, a.id_base, i);
+                hit = first_u53(pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, kLayeredScatterDraw, a.k0, a.k1)) < p;   // u < 1: p == 1 scatters everybody
+            }
+        }
+        const uint32_t n_exp = (uint32_t)__popcll(__ballot(exposed)), n_hit = (uint32_t)__popcll(__ballot(hit));
+        if (lane == 0 && n_exp) atomicAdd(&s_cnt[0], n_exp);
+        if (lane == 0 && n_hit) atomicAdd(&s_cnt[1], n_hit);
+        if (a.first && photon && !hit) {                                // the scatter step's miss: "did not scatter", the three rows together
+#pragma unroll
+            for (int k = 0; k < 3; ++k) a.dv[k][ti] = (T)0.0;
+        }
+        if (!hit) continue;     // lanes that are left alone wait at the loop's head: no ballot below this line
+        atomicAdd(&s_cell[cell], 1u);
+        double u_a, u_b, sc, ss, e1[3], e2[3];
+        const double w[3] = {1.0, 0.0, 0.0};
+        pair_u53(pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, kLayeredScatterDir, a.k0, a.k1), &u_a, &u_b);
+        const double mu = __dsub_rn(1.0, __dmul_rn(2.0, u_a));                                       // uniform on the sphere
+        polar(mu, u_b, &sc, &ss);
+        frame(w, e1, e2);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double vo = (double)a.v[k][ti];                       // the velocity before the scatter (fp32 widens exactly)
+            const double vk = __dmul_rn(a.speed, turned(sc, ss, mu, e1[k], e2[k], w[k]));
+            a.v[k][ti] = (T)vk;
+            a.dv[k][ti] = (T)__dsub_rn(vk, vo);
+        }
+    }
+    __syncthreads();
+    // pcl_sweep::flush_cells, written out, for the reason given in k_absorb_scattered: a further caller changes the older kernels
+    for (int k = threadIdx.x; k < n_cells; k += kBlock)
+        if (s_cnt[k]) atomicAdd(&a.out[k], (unsigned long long)s_cnt[k]);
+}
+
+// The scattering by layer and band takes pcl_step_absorb_path's tables by pcl_step_absorb_path's check: the limits are the same.
+static_assert(PCL_SCATTER_LAYERED_MAX_LAYERS == PCL_PATH_ABSORB_MAX_LAYERS && PCL_SCATTER_LAYERED_MAX_BANDS == PCL_PATH_ABSORB_MAX_BANDS &&
+              PCL_SCATTER_LAYERED_MAX_CELLS == PCL_PATH_ABSORB_MAX_CELLS, "one check serves both sweeps");
+
+struct lscatter_spec { // a call's arguments, checked; what the kernel compares against
+    pabsorb_spec tab;           // p | e*e | E edges, the centre, who draws: cells() = exposed, scattered | by cell
+    int first = 0;
+    double speed = 0.0;
+};
+
+// Everything PCL_ERR_ARG stands for except the NULL context; nothing is launched or written before this has passed.
+bool check_lscatter(int n_layers, int n_E, const double *p, const double *edges, const double *center, const double *E_edges, int first,
+                    double c, const int64_t *counts_out, const int64_t *cells_out, lscatter_spec &s) {
+    if ((first != 0 && first != 1) || !std::isfinite(c)) return false;
+    s.first = first; s.speed = c;
+    return check_pabsorb(n_layers, n_E, p, edges, center, E_edges, counts_out, cells_out, s.tab);
+}
+
+template <typename T>
+int launch_lscatter(pcl_ctx *ctx, const store_view &v, const lscatter_spec &s, uint64_t seed, uint32_t pass, const staged &st) {
+    lscatter_args<T> a{};
+    for (int k = 0; k < 3; ++k) {
+        void *r = nullptr, *vel = nullptr, *dv = nullptr;
+        if (s.tab.n_layers > 0) PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_R0 + k, &r));
+        PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_V0 + k, &vel));
+        PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_DV0 + k, &dv));     // (what makes a lazy dv real: a hit's and, with first, a miss's is written)
+        a.r[k] = static_cast<const T *>(r); a.v[k] = static_cast<T *>(vel); a.dv[k] = static_cast<T *>(dv);
+        a.c[k] = s.tab.c[k];
+    }
+    // E is asked for only with energy bands: the pointer costs a wavelength-dependent scatter step its term cache (pcl_shell.hip).
+    void *E = nullptr;
+    if (s.tab.n_E > 0) PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_E, &E));
+    a.E = static_cast<const T *>(E); a.kind = st.kind; a.ids = st.ids; a.tables = st.tables; a.out = st.out;
+    a.N = v.N; a.ts = v.ts; a.id_base = st.id_base; a.tile_log = v.tile_log;
+    a.n_layers = s.tab.n_layers; a.n_E = s.tab.n_E; a.first = s.first; a.speed = s.speed;
+    a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32); a.pass = pass;
+    const size_t lds = s.tab.lds();                                     // what this call uses: 24 B for one cell everywhere
+    const int64_t grid = balanced_grid(v.N, v.n_cu, resident_per_cu(lds));
+    hipLaunchKernelGGL(k_scatter_layered<T>, dim3((unsigned)grid), dim3(kBlock), lds, v.stream, a);
+    return hipGetLastError() == hipSuccess ? PCL_OK : PCL_ERR_HIP;
+}
+
+int scatter_layered(pcl_ctx *ctx, int n_layers, int n_E_bins, const double *p_host, const double *edges_host, const double *center_host,
+                    const double *E_edges_host, int first, double c, uint64_t seed, uint32_t pass, int64_t *counts_out_host,
+                    int64_t *cells_out_host) {
+    lscatter_spec s;
+    if (!ctx || !check_lscatter(n_layers, n_E_bins, p_host, edges_host, center_host, E_edges_host, first, c, counts_out_host, cells_out_host, s))
+        return bad_argument(ctx);
+    const spans out = s.tab.out(counts_out_host, cells_out_host);
+    store_view v;
+    staged st(ctx);
+    PCL_SWEEP_TRY(open_store(ctx, PCL_V0, &v));
+    zero_spans(out);
+    if (v.N <= 0) return PCL_OK;
+    PCL_SWEEP_TRY(stage(st, v, s.tab.cells(), s.tab.tables.data(), s.tab.tables.size(), s.tab.draws));   // the ids only if somebody may draw
+    PCL_SWEEP_TRY(PCL_SWEEP_LAUNCH(v, launch_lscatter, ctx, v, s, seed, pass, st));
+    return fetch(st, out);
+}
+
+int group_scatter_layered(pcl_group *group, int n_layers, int n_E_bins, const double *p_host, const double *edges_host,
+                          const double *center_host, const double *E_edges_host, int first, double c, uint64_t seed, uint32_t pass,
+                          int64_t *counts_out_host, int64_t *cells_out_host) {
+    lscatter_spec s;                                                    // the arguments first: a refused call looks at no group
+    if (!check_lscatter(n_layers, n_E_bins, p_host, edges_host, center_host, E_edges_host, first, c, counts_out_host, cells_out_host, s))
+        return bad_argument(nullptr);
+    std::vector<pcl_ctx *> ctx;
+    PCL_SWEEP_TRY(shards_of(group, ctx));
+    if (ctx.empty()) return bad_argument(nullptr);
+    return sum_shards(ctx, s.tab.out(counts_out_host, cells_out_host), [&](pcl_ctx *one, int64_t *p) {
+        return pcl_step_scatter_layered(one, n_layers, n_E_bins, p_host, edges_host, center_host, E_edges_host, first, c, seed, pass, p, p + 2);
+    });
+}
+
 } // namespace
 
 extern "C" {
@@ -2061,6 +2250,24 @@ int pcl_group_step_ground_spectral(pcl_group *group, double radius, const double
     return guarded([&] {
         return group_ground_spectral(group, radius, center_host, n_bands, E_edges_host, albedo_host, specular_host, c, seed, pass,
                                      counts_out_host, bands_out_host);
+    });
+}
+
+int pcl_step_scatter_layered(pcl_ctx *ctx, int n_layers, int n_E_bins, const double *p_host, const double *edges_host,
+                             const double *center_host, const double *E_edges_host, int first, double c, uint64_t seed, uint32_t pass,
+                             int64_t *counts_out_host, int64_t *cells_out_host) {
+    return guarded([&] {
+        return scatter_layered(ctx, n_layers, n_E_bins, p_host, edges_host, center_host, E_edges_host, first, c, seed, pass, counts_out_host,
+                               cells_out_host);
+    });
+}
+
+int pcl_group_step_scatter_layered(pcl_group *group, int n_layers, int n_E_bins, const double *p_host, const double *edges_host,
+                                   const double *center_host, const double *E_edges_host, int first, double c, uint64_t seed,
+                                   uint32_t pass, int64_t *counts_out_host, int64_t *cells_out_host) {
+    return guarded([&] {
+        return group_scatter_layered(group, n_layers, n_E_bins, p_host, edges_host, center_host, E_edges_host, first, c, seed, pass,
+                                     counts_out_host, cells_out_host);
     });
 }
 

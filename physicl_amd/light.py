@@ -2107,14 +2107,11 @@ def _path_probability(k, c, dt):
 _PATH_ABSORB_WORD = 17                                        # the draw's counter word (the header lists the words taken)
 
 
-def _absorb_path(r, v, dv, E, photon, ids, p, edges, center, E_edges, seed, n_pass, dtype=np.float64):
-    """What pcl_step_absorb_path makes of (n, 3) float64 positions, velocities and last velocity changes, the energies, who is a
-    photon and the particles' ids, with numpy -- every operation the device's operation in the device's order, one rounding each
-    (include/physicl_hip.h): no transcendental function, no division and no square root, so everything is the device's bit for bit.
-    ``p``: the probabilities, max(L, 1) rows of max(B, 1) values.  What is written is zero, in any ``dtype``.  A dict: ``v, dv`` the new
-    state (float64 arrays; rows that are not absorbed are the arguments'), the boolean masks ``exposed`` and ``absorbed``, ``layer``
-    and ``band`` (int64: of every moving photon, -1 for none) and the tally ``absorbed_by_cell`` (int64 [L', B'])."""
-    r, v, dv = (np.array(a, dtype=np.float64).reshape(-1, 3) for a in (r, v, dv))
+def _path_draw(r, v, E, photon, ids, p, edges, center, E_edges, seed, n_pass, word):
+    """Who is exposed over the move of a pass and whose draw falls below the cell's probability -- the lines pcl_step_absorb_path and
+    pcl_step_scatter_layered share, on (n, 3) float64 ``r`` and ``v``: ``(p as [L'][B'], layer, band, exposed, drawn)``.  ``layer`` and
+    ``band``: int64, of every moving photon, -1 for none; ``exposed``: a moving photon with both; ``drawn``: the places whose
+    ``u53(w0, w1)`` of the counter ``(id_lo, id_hi, n_pass, word)`` is below ``p[layer][band]`` (a cell with p == 0 draws nothing)."""
     n = len(v)
     rows, cols = (1 if e is None else len(e) - 1 for e in (edges, E_edges))
     p = np.asarray(p, dtype=np.float64).reshape(rows, cols)
@@ -2129,13 +2126,26 @@ def _absorb_path(r, v, dv, E, photon, ids, p, edges, center, E_edges, seed, n_pa
             band[at] = _bin_of(np.asarray(E, dtype=np.float64).reshape(-1)[at], np.asarray(E_edges, dtype=np.float64))
     exposed = band >= 0
     draws = np.flatnonzero(exposed)
-    draws = draws[p[layer[draws], band[draws]] > 0.0]          # a transparent cell draws nothing
-    u = _philox_block(np.asarray(ids).reshape(-1)[draws], seed, n_pass, _PATH_ABSORB_WORD)[0]
-    gone = draws[u < p[layer[draws], band[draws]]]
+    draws = draws[p[layer[draws], band[draws]] > 0.0]          # a cell with p == 0 draws nothing
+    u = _philox_block(np.asarray(ids).reshape(-1)[draws], seed, n_pass, word)[0]
+    return p, layer, band, exposed, draws[u < p[layer[draws], band[draws]]]
+
+
+def _absorb_path(r, v, dv, E, photon, ids, p, edges, center, E_edges, seed, n_pass, dtype=np.float64):
+    """What pcl_step_absorb_path makes of (n, 3) float64 positions, velocities and last velocity changes, the energies, who is a
+    photon and the particles' ids, with numpy -- every operation the device's operation in the device's order, one rounding each
+    (include/physicl_hip.h): no transcendental function, no division and no square root, so everything is the device's bit for bit.
+    ``p``: the probabilities, max(L, 1) rows of max(B, 1) values.  What is written is zero, in any ``dtype``.  A dict: ``v, dv`` the new
+    state (float64 arrays; rows that are not absorbed are the arguments'), the boolean masks ``exposed`` and ``absorbed``, ``layer``
+    and ``band`` (int64: of every moving photon, -1 for none) and the tally ``absorbed_by_cell`` (int64 [L', B'])."""
+    r, v, dv = (np.array(a, dtype=np.float64).reshape(-1, 3) for a in (r, v, dv))
+    n = len(v)
+    p, layer, band, exposed, gone = _path_draw(r, v, E, photon, ids, p, edges, center, E_edges, seed, n_pass, _PATH_ABSORB_WORD)
+    cols = p.shape[1]
     absorbed = np.zeros(n, dtype=bool)
     absorbed[gone] = True
     v[gone], dv[gone] = np.zeros(3, dtype=dtype), np.zeros(3, dtype=dtype)
-    cells = np.bincount(layer[gone] * cols + band[gone], minlength=rows * cols).astype(np.int64).reshape(rows, cols)
+    cells = np.bincount(layer[gone] * cols + band[gone], minlength=p.size).astype(np.int64).reshape(p.shape)
     return {"v": v, "dv": dv, "exposed": exposed, "absorbed": absorbed, "layer": layer, "band": band, "absorbed_by_cell": cells}
 
 
@@ -2207,6 +2217,143 @@ class PathAbsorptionStep(tally.WriterStep):
         new = _absorb_path(tally.vec3(objs, "r"), tally.vec3(objs, "v"), tally.vec3(objs, "dv"), E, photon, ids, p,
                            self.edges, self.center, self.E_edges, seed, self._pass)
         return new, new["absorbed"], (new["exposed"].sum(), new["absorbed"].sum(), new["absorbed_by_cell"])
+
+    terminate = tally.TallyStep.terminate                # (a row holds arrays: written as the tally steps write theirs, as plain lists)
+
+
+# ---------------------------------------------------------------------------------------------- scattering by layer and band
+_LAYERED_SCATTER_WORDS = (23, 24)                             # the draw, the direction (the header lists the words taken)
+
+
+def _scatter_layered(r, v, dv, E, photon, ids, p, edges, center, E_edges, first, c, seed, n_pass, dtype=np.float64):
+    """What pcl_step_scatter_layered makes of (n, 3) float64 positions, velocities and last velocity changes, the energies, who is a
+    photon and the particles' ids, with numpy -- every operation the device's operation in the device's order, one rounding each
+    (include/physicl_hip.h), and what is written rounded once to ``dtype``.  Who is exposed, who is hit and every tally are the
+    device's bit for bit; sin / cos are libm's here.  ``p``: the probabilities, max(L, 1) rows of max(B, 1) values; ``first``: the
+    pass's first scatterer (a photon that is not scattered gets dv = 0) or not (it is not written).  A dict: ``v, dv`` the new state
+    (float64 arrays; rows that are not written are the arguments'), the boolean masks ``exposed``, ``scattered`` and ``written``,
+    ``layer`` and ``band`` (int64: of every moving photon, -1 for none) and the tally ``scattered_by_cell`` (int64 [L', B'])."""
+    r, v, dv = (np.array(a, dtype=np.float64).reshape(-1, 3) for a in (r, v, dv))
+    n = len(v)
+    photon = np.asarray(photon, dtype=bool).reshape(-1)
+    p, layer, band, exposed, hit = _path_draw(r, v, E, photon, ids, p, edges, center, E_edges, seed, n_pass, _LAYERED_SCATTER_WORDS[0])
+    u_a, u_b = _philox_block(np.asarray(ids).reshape(-1)[hit], seed, n_pass, _LAYERED_SCATTER_WORDS[1])
+    with np.errstate(invalid="ignore", over="ignore"):
+        v_new = np.float64(c) * _turn_about(np.tile([1.0, 0.0, 0.0], (len(hit), 1)), 1.0 - 2.0 * u_a, u_b)     # uniform on the sphere
+        dv[hit] = _stored(v_new - v[hit], dtype)               # the scatter step's mark, from the old velocity
+    v[hit] = _stored(v_new, dtype)
+    scattered = np.zeros(n, dtype=bool)
+    scattered[hit] = True
+    written = scattered | (photon & bool(first))
+    dv[written & ~scattered] = 0.0                             # first: "did not scatter in this pass"
+    cells = np.bincount(layer[hit] * p.shape[1] + band[hit], minlength=p.size).astype(np.int64).reshape(p.shape)
+    return {"v": v, "dv": dv, "exposed": exposed, "scattered": scattered, "written": written, "layer": layer, "band": band,
+            "scattered_by_cell": cells}
+
+
+def _earlier_steps(sim, step):
+    """(the steps in front of ``step`` in the simulation's pass, those behind it), in the order the pass runs them."""
+    steps = getattr(sim, "steps", None) or {}
+    steps = list(steps.values() if isinstance(steps, dict) else steps)
+    at = next((k for k, s in enumerate(steps) if s is step), len(steps))
+    return steps[:at], steps[at + 1:]
+
+
+class LayeredScatterStep(tally.WriterStep):
+    """Who scatters, by radial layer and energy band (not in the reference): the scattering twin of ``PathAbsorptionStep``.
+    ``ScatterIsotropicStep`` decides with ``A * n * |dr|`` -- ``n`` a constant or a closed-form expression, the only colour a
+    ``lambda^-4`` --; this step takes a scattering coefficient from a table: a cloud with its own optical depth, an aerosol layer
+    with a ``lambda^-1`` spectrum beside the Rayleigh one, a drop or a fog bank in vacuum with no ``ScatterIsotropicStep`` at all.
+    It stands BEHIND the Newton step of a pass -- alone, or behind a ``ScatterIsotropicStep`` -- and in front of the phase,
+    absorption and ground steps.
+
+    * ``k``: the scattering coefficient per unit length (code units), finite and not negative: one number; ``[L]`` numbers with
+      ``edges`` only; ``[B]`` with ``E_edges`` only; ``[L][B]`` with both.
+    * ``edges``, ``center``, ``E_edges``: ``PathAbsorptionStep``'s arguments by ``PathAbsorptionStep``'s rules, limits (64 layers, 1024
+      bands, 4096 cells) and error messages: layer ``b`` holds a photon iff ``e_b**2 <= q < e_(b+1)**2``, the last layer closed, no
+      square root taken; the bands are ``numpy.histogram``'s bins; without ``E_edges`` E is neither read nor asked for, so a
+      wavelength-dependent scatter step keeps its term cache.
+    * ``first``: True -- this step is the pass's first scatterer and keeps ``ScatterIsotropicStep``'s contract: every photon it does
+      not scatter gets ``dv = 0``, exposed or not, at rest or not.  False -- it stands behind another scatterer: a photon that is not
+      scattered is not written at all, so the earlier step's mark survives.  None (the default) is decided at the step's first run
+      from the simulation's step order: False iff a ``ScatterIsotropicStep``, a ``ScatterSphericalStep`` or another
+      ``LayeredScatterStep`` stands earlier in the pass.  A ``ScatterIsotropicStep`` BEHIND this step would wipe its marks: the first
+      run raises ``ValueError``.
+
+    Per pass the host makes ``p = -numpy.expm1(-k * (c * dt))`` from the simulation's current ``dt`` (``_path_probability``), and the
+    device only ever sees ``p``.  Every moving photon with a layer and a band is EXPOSED (a photon at rest -- ``-0.0`` counts as 0, a
+    NaN moves --, a plain ``Object`` and a photon in no layer or no band are skipped); it scatters iff ``u < p`` (``p == 0`` draws
+    nothing), ``u`` from a Philox block keyed by ``sim.seed``, the photon's id and a pass counter of the step's own, in counter words
+    no other kernel uses (23, and 24 for the direction): every other step draws what it draws without this one, and a sharded run
+    scatters the same photons the same way.  The draws are made on the device with every ``rng=`` setting.  A hit gets a direction
+    uniform on the sphere at speed c -- ``ReemissionStep``'s isotropic arithmetic -- and the scatter step's mark: ``v = v'``,
+    ``dv = v' - v_old``.  ``r``, ``dr``, ``E``, ids and kinds are never written; plain ``Object``s are never touched.
+
+    What follows from the ``dv`` contract:
+
+    * a ``PhaseFunctionStep`` or ``LayeredPhaseStep`` behind this step re-directs its hits about ``v - dv``, the direction before the
+      scatter: that is how a cloud gets both its optical depth and its forward peak;
+    * an ``AbsorptionStep`` behind it gives the cloud its own ``omega0``;
+    * two scatterers that both hit one photon in one pass are two scatterings, and the phase step turns about the direction after
+      the first;
+    * a hit whose new direction equals the old one bit for bit reads as a miss -- the same negligible case as in the scatter step.
+
+    After each run ``self.exposed`` and ``self.scattered`` hold the pass's counts and ``self.scattered_by_cell`` an int64 array
+    ``[max(L, 1)][max(B, 1)]``, global over shards and ranks; ``self.data`` gains the row ``[t, exposed, scattered,
+    scattered_by_cell]``; ``out_fn`` takes the rows at the end.  The rule is written out in include/physicl_hip.h
+    (pcl_step_scatter_layered); ``_scatter_layered`` restates it with numpy.  The step writes its own ``dv`` rule and reads none, so it
+    works under ``cl_on=False`` -- but not with ``first=False`` there: the Python-semantics scatter step leaves ``dv = v_old``, and
+    nothing behind it can use the marks.
+
+    One launch per light step: the K-passes-per-launch kernels cannot scatter a photon by a table between two of their passes, and
+    ``sim.launch_note`` says so.  On host-resident objects (``step.run(sim)`` outside a device loop) the same state is made with
+    numpy, the ids being the places in the object list."""
+    _NOTE = "one launch per light step: a LayeredScatterStep scatters moving photons by layer and band behind every pass, which " \
+            "the K-passes-per-launch kernels cannot carry"
+
+    def __init__(self, k, edges=None, center=(0, 0, 0), E_edges=None, first=None, out_fn=None):
+        MeasureStep.__init__(self, out_fn)
+        self.k, self.edges, self.center, self.E_edges = _check_path_absorb(k, edges, center, E_edges)
+        if first is not None and not isinstance(first, (bool, np.bool_)):
+            raise ValueError("first must be None, True or False, got %r" % (first,))
+        self.first = None if first is None else bool(first)
+        self.exposed = self.scattered = 0
+        self.scattered_by_cell = np.zeros(self.k.shape, dtype=np.int64)
+        self._pass = 0                                   # the step's own Philox counter word: one per run
+
+    def _record_pass(self, sim, exposed, scattered, cells):
+        self.exposed, self.scattered = int(exposed), int(scattered)
+        self.scattered_by_cell = np.array(cells, dtype=np.int64).reshape(self.k.shape)
+        self.data.append(tally.object_row([tally._snap(sim.t), self.exposed, self.scattered, self.scattered_by_cell.copy()]))
+
+    def _refuse(self, sim):
+        first = self.first
+        if self._pass == 0:                              # the step order is looked at once, before anything moves
+            front, behind = _earlier_steps(sim, self)
+            for other in behind:
+                if isinstance(other, ScatterIsotropicStep):
+                    raise ValueError("a pass marks its scattered photons once: the simulation's steps hold a %s behind this "
+                                     "LayeredScatterStep, and it would overwrite the dv of every photon this step has scattered -- "
+                                     "put the LayeredScatterStep behind it" % type(other).__name__)
+            if first is None:
+                first = not any(isinstance(other, (ScatterIsotropicStep, LayeredScatterStep)) for other in front)
+        if first is False:
+            _dv_rule_refusal(sim, "LayeredScatterStep(first=False)", "the earlier scatter step's marks")
+        self.first = first
+
+    def _prepare(self, sim, on_host):                    # p of this pass's dt; a dt that is refused raises here
+        return _path_probability(self.k, _c_h_literals()[0], np.asarray(sim.dt) if on_host else sim._dt_code())
+
+    def _sweep(self, sim, p):
+        exposed, scattered, cells = sim._dev.scatter_layered(p, self.edges, self.center, self.E_edges, self.first, _c_h_literals()[0],
+                                                             sim.seed, self._pass)
+        return [np.array([exposed, scattered], dtype=np.int64), np.asarray(cells, dtype=np.int64)]
+
+    def _host_sweep(self, objs, ids, seed, p):
+        E, photon = tally.photon_energies(objs, PhotonObject)
+        new = _scatter_layered(tally.vec3(objs, "r"), tally.vec3(objs, "v"), tally.vec3(objs, "dv"), E, photon, ids, p, self.edges,
+                               self.center, self.E_edges, self.first, _c_h_literals()[0], seed, self._pass)
+        return new, new["written"], (new["exposed"].sum(), new["scattered"].sum(), new["scattered_by_cell"])
 
     terminate = tally.TallyStep.terminate                # (a row holds arrays: written as the tally steps write theirs, as plain lists)
 

@@ -312,6 +312,9 @@ class MultiDevice:
     def ground_spectral(self, *a, **kw):
         return self._sum_parts("ground_spectral", *a, **kw)
 
+    def scatter_layered(self, *a, **kw):
+        return self._sum_parts("scatter_layered", *a, **kw)
+
     def plane_energies(self, plane, n_hint=None):
         return self._concat(self._each(lambda s: s.plane_energies(plane)))      # (a shard does not know its share of the hint)
 
