@@ -704,7 +704,10 @@ int pcl_step_detector_image(pcl_ctx *ctx, const double *position_host,      /* 3
  *   reflected:   v = c*dir;  dv = v - v_old;  dr = w*dir;  r = center + (x + dr)    (the rest of the move, flown along dir)
  * ``c`` = the speed of light in code units (what the scatter step is handed).  The draws are Philox4x32-10 blocks with the key
  * (seed_lo, seed_hi) and u53 of pcl_store_apply_source: counter (id_lo, id_hi, pass, 8): u_a = u53(w0, w1), u_b = u53(w2, w3);
- * counter (id_lo, id_hi, pass, 9): u_0 = u53(w0, w1), drawn only with albedo < 1.  ``pass`` is the caller's own counter; the
+ * counter (id_lo, id_hi, pass, 9): u_0 = u53(w0, w1), drawn only with albedo < 1.  ``pass`` is the caller's own counter, here and in
+ * every entry point below that takes one: calls that share a counter word within one pass of the caller's loop (two calls of one
+ * entry point -- two gases, two clouds --, or of two that share words: the two grounds, the two phase functions) must be given
+ * distinct ``pass`` values, or a photon draws the same number in both (physicl_amd.tally.WriterStep interleaves them).  The
  * scatter kernels use the counter words (step >> 1, 0) and (step, 1), fill and source (0xFFFFFFFF, 2..5): no block is shared,
  * and a photon draws the same numbers however the run is sharded.
  * counts_out_host[0] = photons reflected, [1] = absorbed, by this call.

@@ -1115,7 +1115,7 @@ class SurfaceReflectStep(tally.WriterStep):
     re-directs the photon with speed c, a ScatterDeleteStep removes it: absorbed photons are recognised by ``v == 0`` only until
     then.  The scatter kernels are left as they are.
 
-    The draws are Philox blocks keyed by ``sim.seed``, the photon's id and a pass counter of the step's own, in counter words no
+    The draws are Philox blocks keyed by ``sim.seed``, the photon's id and the step's pass counter ``_n_pass``, in counter words no
     other kernel uses -- so the scatter steps of a simulation draw what they draw without this step, and a photon draws the same
     numbers however the run is sharded.  They are made on the device with EVERY ``rng=`` setting: the step is not in the
     reference, so there is no host stream to reproduce.
@@ -1130,7 +1130,7 @@ class SurfaceReflectStep(tally.WriterStep):
         MeasureStep.__init__(self, out_fn)
         self.radius, self.center, self.albedo, self.mode = _check_surface(radius, center, albedo, mode)
         self.reflected = self.absorbed = 0
-        self._pass = 0                                   # the step's own Philox counter word: one per run
+        self._pass = 0                                   # runs so far; the sweep is handed _n_pass (tally.WriterStep)
 
     def _record_pass(self, sim, reflected, absorbed):
         self.reflected, self.absorbed = int(reflected), int(absorbed)
@@ -1139,7 +1139,7 @@ class SurfaceReflectStep(tally.WriterStep):
     _writes = ("r", "dr", "v", "dv")
 
     def _sweep(self, sim, prep):
-        return [np.array(sim._dev.surface_reflect(self.radius, self.center, self.albedo, self.mode, _c_h_literals()[0], sim.seed, self._pass),
+        return [np.array(sim._dev.surface_reflect(self.radius, self.center, self.albedo, self.mode, _c_h_literals()[0], sim.seed, self._n_pass),
                          dtype=np.int64)]
 
     def _reduce(self, sim, parts):
@@ -1147,7 +1147,7 @@ class SurfaceReflectStep(tally.WriterStep):
 
     def _host_sweep(self, objs, ids, seed, prep):
         new = _surface_bounce(tally.vec3(objs, "r"), tally.vec3(objs, "dr"), tally.vec3(objs, "v"), _photons(objs), ids,
-                              self.radius, self.center, self.albedo, self.mode, _c_h_literals()[0], seed, self._pass)
+                              self.radius, self.center, self.albedo, self.mode, _c_h_literals()[0], seed, self._n_pass)
         return new, new["hit"], (new["reflected"].sum(), new["absorbed"].sum())
 
 
@@ -1258,7 +1258,7 @@ class SpectralSurfaceStep(tally.WriterStep):
         MeasureStep.__init__(self, out_fn)
         self.radius, self.albedo, self.E_edges, self.center, self.specular = _check_spectral_surface(radius, albedo, E_edges, center, specular)
         self._record_counts(np.zeros(4, dtype=np.int64), np.zeros((2, len(self.albedo)), dtype=np.int64))
-        self._pass = 0                                   # the step's own Philox counter word: one per run
+        self._pass = 0                                   # runs so far; the sweep is handed _n_pass (tally.WriterStep)
 
     def _record_counts(self, counts, bands):
         for name, x in zip(_SPECTRAL_COUNTS, counts):
@@ -1281,13 +1281,13 @@ class SpectralSurfaceStep(tally.WriterStep):
 
     def _sweep(self, sim, prep):
         counts, refl, gone = sim._dev.ground_spectral(self.radius, self.E_edges, self.albedo, self.specular, self.center,
-                                                      _c_h_literals()[0], sim.seed, self._pass)
+                                                      _c_h_literals()[0], sim.seed, self._n_pass)
         return [np.asarray(counts, dtype=np.int64), np.stack([np.asarray(refl, dtype=np.int64), np.asarray(gone, dtype=np.int64)])]
 
     def _host_sweep(self, objs, ids, seed, prep):
         E, photon = tally.photon_energies(objs, PhotonObject)
         new = _spectral_bounce(tally.vec3(objs, "r"), tally.vec3(objs, "dr"), tally.vec3(objs, "v"), E, photon, ids, self.radius,
-                               self.center, self.albedo, self.specular, self.E_edges, _c_h_literals()[0], seed, self._pass)
+                               self.center, self.albedo, self.specular, self.E_edges, _c_h_literals()[0], seed, self._n_pass)
         return new, new["hit"], (new["reflected"].sum(), new["absorbed"].sum(), new["mirrored"].sum(), new["out_of_band"].sum(),
                                  np.stack([new["reflected_by_band"], new["absorbed_by_band"]]))
 
@@ -1417,7 +1417,7 @@ class RefractiveSurfaceStep(tally.WriterStep):
     ``out_fn`` takes the rows at the end of the run.  The arithmetic is written out in include/physicl_hip.h
     (pcl_step_refract_surface); ``_refract_surface`` restates it with numpy, bit for bit.
 
-    The draw is a Philox block keyed by ``sim.seed``, the photon's id and a pass counter of the step's own, in a counter word no
+    The draw is a Philox block keyed by ``sim.seed``, the photon's id and the step's pass counter ``_n_pass``, in a counter word no
     other kernel uses (21): every other step draws what it draws without this one, and a photon meets the same fate however the run
     is sharded.  It is made on the device with EVERY ``rng=`` setting.  The step reads no ``dv`` rule, so it works under
     ``cl_on=False`` as well.
@@ -1434,7 +1434,7 @@ class RefractiveSurfaceStep(tally.WriterStep):
         self.radius, self.n_inside, self.n_outside, self.center = _check_refractive(radius, n_inside, n_outside, center)
         self.fresnel = bool(fresnel)
         self._record_counts(np.zeros(6, dtype=np.int64))
-        self._pass = 0                                   # the step's own Philox counter word: one per run
+        self._pass = 0                                   # runs so far; the sweep is handed _n_pass (tally.WriterStep)
 
     def _record_counts(self, counts):
         for name, x in zip(_REFRACT_COUNTS, counts):
@@ -1446,11 +1446,11 @@ class RefractiveSurfaceStep(tally.WriterStep):
 
     def _sweep(self, sim, prep):
         return [np.asarray(sim._dev.refract_surface(self.radius, self.n_inside, self.n_outside, self.center, self.fresnel,
-                                                    _c_h_literals()[0], sim.seed, self._pass), dtype=np.int64)]
+                                                    _c_h_literals()[0], sim.seed, self._n_pass), dtype=np.int64)]
 
     def _host_sweep(self, objs, ids, seed, prep):
         new = _refract_surface(tally.vec3(objs, "r"), tally.vec3(objs, "dr"), tally.vec3(objs, "v"), _photons(objs), ids, self.radius,
-                               self.center, self.n_inside, self.n_outside, self.fresnel, _c_h_literals()[0], seed, self._pass)
+                               self.center, self.n_inside, self.n_outside, self.fresnel, _c_h_literals()[0], seed, self._n_pass)
         return new, new["crossed"], tuple(new["counts"])
 
 
@@ -1515,7 +1515,7 @@ class PhaseFunctionStep(tally.WriterStep):
     the scatter step's hit count -- and ``self.data`` gains the row ``[t, redirected]``; ``out_fn`` takes the rows at the end.
     The arithmetic is written out in include/physicl_hip.h (pcl_step_phase_redirect); ``_phase_redirect`` restates it with numpy.
 
-    The draws are Philox blocks keyed by ``sim.seed``, the photon's id and a pass counter of the step's own, in counter words no
+    The draws are Philox blocks keyed by ``sim.seed``, the photon's id and the step's pass counter ``_n_pass``, in counter words no
     other kernel uses: the scatter step draws what it draws without this step, and a photon draws the same numbers however the
     run is sharded.  They are made on the device with every ``rng=`` setting.  Under the reference's Python semantics
     (``cl_on=False``) a hit leaves ``dv = v_old``, the rule above does not hold, and the step raises ``ValueError``.
@@ -1530,7 +1530,7 @@ class PhaseFunctionStep(tally.WriterStep):
         MeasureStep.__init__(self, out_fn)
         self.phase, self.g = _check_phase(phase, g)
         self.redirected = 0
-        self._pass = 0                                   # the step's own Philox counter word: one per run
+        self._pass = 0                                   # runs so far; the sweep is handed _n_pass (tally.WriterStep)
 
     def _record_pass(self, sim, redirected):
         self.redirected = int(redirected)
@@ -1540,14 +1540,14 @@ class PhaseFunctionStep(tally.WriterStep):
         _dv_rule_refusal(sim, "PhaseFunctionStep", "its direction before the scatter")
 
     def _sweep(self, sim, prep):
-        return [np.array([sim._dev.phase_redirect(self.phase, self.g, _c_h_literals()[0], sim.seed, self._pass)], dtype=np.int64)]
+        return [np.array([sim._dev.phase_redirect(self.phase, self.g, _c_h_literals()[0], sim.seed, self._n_pass)], dtype=np.int64)]
 
     def _reduce(self, sim, parts):
         return [sim._global(parts[0].tolist())]          # the count alone, as ever
 
     def _host_sweep(self, objs, ids, seed, prep):
         new = _phase_redirect(tally.vec3(objs, "v"), tally.vec3(objs, "dv"), _photons(objs), ids, self.phase, self.g,
-                              _c_h_literals()[0], seed, self._pass)
+                              _c_h_literals()[0], seed, self._n_pass)
         return new, new["redirected"], (new["redirected"].sum(),)
 
 
@@ -1643,9 +1643,10 @@ class AbsorptionStep(tally.WriterStep):
     absorbed_by_layer (, E_hist)]``; ``out_fn`` takes the rows at the end.  The arithmetic is written out in include/physicl_hip.h
     (pcl_step_absorb_scattered); ``_absorb_scattered`` restates every bit of it with numpy.
 
-    The draw is a Philox block keyed by ``sim.seed``, the photon's id and a pass counter of the step's own, in a counter word no
+    The draw is a Philox block keyed by ``sim.seed``, the photon's id and the step's pass counter ``_n_pass``, in a counter word no
     other kernel uses: every other step draws what it draws without this one, and a photon draws the same number however the run
-    is sharded.  A layer with ``omega0 == 1`` draws nothing.  The draws are made on the device with every ``rng=`` setting.  Under
+    is sharded.  Two ``AbsorptionStep``s of one pass count on through one another (``tally.WriterStep``), so their draws are
+    independent.  A layer with ``omega0 == 1`` draws nothing.  The draws are made on the device with every ``rng=`` setting.  Under
     the reference's Python semantics (``cl_on=False``) a hit leaves ``dv = v_old``, the rule above does not hold, and the step
     raises ``ValueError``.
 
@@ -1662,7 +1663,7 @@ class AbsorptionStep(tally.WriterStep):
         self.interacted = self.absorbed = 0
         self.absorbed_by_layer = np.zeros(rows, dtype=np.int64)
         self.E_hist = None if self.E_bins is None else np.zeros((rows, len(self.E_bins) - 1), dtype=np.int64)
-        self._pass = 0                                   # the step's own Philox counter word: one per run
+        self._pass = 0                                   # runs so far; the sweep is handed _n_pass (tally.WriterStep)
 
     def _record_pass(self, sim, interacted, absorbed, by_layer, E_hist):
         self.interacted, self.absorbed = int(interacted), int(absorbed)
@@ -1675,13 +1676,13 @@ class AbsorptionStep(tally.WriterStep):
         _dv_rule_refusal(sim, "AbsorptionStep", "who interacted in this pass")
 
     def _sweep(self, sim, prep):
-        interacted, absorbed, by_layer, E_hist = sim._dev.absorb_scattered(self.omega0, self.edges, self.center, self.E_bins, sim.seed, self._pass)
+        interacted, absorbed, by_layer, E_hist = sim._dev.absorb_scattered(self.omega0, self.edges, self.center, self.E_bins, sim.seed, self._n_pass)
         return [np.array([interacted, absorbed], dtype=np.int64), np.asarray(by_layer), E_hist]
 
     def _host_sweep(self, objs, ids, seed, prep):
         E, photon = tally.photon_energies(objs, PhotonObject)
         new = _absorb_scattered(tally.vec3(objs, "r"), tally.vec3(objs, "v"), tally.vec3(objs, "dv"), E, photon, ids,
-                                self.omega0, self.edges, self.center, self.E_bins, seed, self._pass)
+                                self.omega0, self.edges, self.center, self.E_bins, seed, self._n_pass)
         return new, new["absorbed"], (new["interacted"].sum(), new["absorbed"].sum(), new["absorbed_by_layer"], new["E_hist"])
 
     terminate = tally.TallyStep.terminate                # (a row holds arrays: written as the tally steps write theirs, as plain lists)
@@ -1843,7 +1844,7 @@ class LayeredPhaseStep(tally.WriterStep):
     (pcl_step_phase_layered); ``_layered_phase_redirect`` restates it with numpy.
 
     The angle is drawn from the Philox blocks ``PhaseFunctionStep`` draws from (counter words 10 and 11), the law from a block of
-    this step's own (word 13), keyed by ``sim.seed``, the photon's id and the step's own pass counter: with one law and no edges
+    this step's own (word 13), keyed by ``sim.seed``, the photon's id and the step's pass counter ``_n_pass``: with one law and no edges
     the step leaves the store bit for bit as ``PhaseFunctionStep`` with that law leaves it.  Sharing the words means A PASS HOLDS
     ONE PHASE STEP: at its first run the step raises ``ValueError`` if the simulation's steps hold another ``PhaseFunctionStep`` or
     ``LayeredPhaseStep``.  Under the reference's Python semantics (``cl_on=False``) a hit leaves ``dv = v_old``, the rule above does
@@ -1862,7 +1863,7 @@ class LayeredPhaseStep(tally.WriterStep):
         self.scattered = self.redirected = 0
         self.by_layer = np.zeros(len(self.cum), dtype=np.int64)
         self.by_law = np.zeros(len(self._laws), dtype=np.int64)
-        self._pass = 0                                   # the step's own Philox counter word: one per run
+        self._pass = 0                                   # runs so far; the sweep is handed _n_pass (tally.WriterStep)
 
     def _record_pass(self, sim, scattered, redirected, by_layer, by_law):
         self.scattered, self.redirected = int(scattered), int(redirected)
@@ -1880,12 +1881,12 @@ class LayeredPhaseStep(tally.WriterStep):
 
     def _sweep(self, sim, prep):
         scattered, redirected, by_layer, by_law = sim._dev.phase_layered(self._laws, self.cum, self.edges, self.center, _c_h_literals()[0],
-                                                                         sim.seed, self._pass)
+                                                                         sim.seed, self._n_pass)
         return [np.array([scattered, redirected], dtype=np.int64), np.asarray(by_layer), np.asarray(by_law)]
 
     def _host_sweep(self, objs, ids, seed, prep):
         new = _layered_phase_apply(tally.vec3(objs, "r"), tally.vec3(objs, "v"), tally.vec3(objs, "dv"), _photons(objs), ids,
-                                   self._laws, self.cum, self.edges, self.center, _c_h_literals()[0], seed, self._pass)
+                                   self._laws, self.cum, self.edges, self.center, _c_h_literals()[0], seed, self._n_pass)
         return new, new["redirected"], (new["scattered"].sum(), new["redirected"].sum(), new["by_layer"], new["by_law"])
 
     terminate = tally.TallyStep.terminate                # (a row holds arrays: written as the tally steps write theirs, as plain lists)
@@ -2024,7 +2025,7 @@ class RecycleStep(tally.WriterStep):
       device: read them with ``sim.download``.)
 
     A spent photon is re-emitted the way ``generate_photons_bulk(source=)`` created it (include/physicl_hip.h:
-    pcl_store_apply_source), from Philox blocks keyed by ``sim.seed``, its id and a pass counter of the step's own, in counter words
+    pcl_store_apply_source), from Philox blocks keyed by ``sim.seed``, its id and the step's pass counter ``_n_pass``, in counter words
     no other kernel uses (14, 15, 16): ``r`` and ``v`` from the source, ``dr = dv = 0`` -- a newborn has not moved and has not scattered.
     Ids and kinds are never written: a slot keeps its id, every re-emission draws new numbers because the pass counter moves, and a
     sharded run recycles the same photons the same way.  Plain ``Object``s are never spent; a particle that is not spent is not
@@ -2044,7 +2045,7 @@ class RecycleStep(tally.WriterStep):
         MeasureStep.__init__(self, out_fn)
         self.source, self.top, self.center, self.rest_on, self.spectrum = _check_recycle(source, top, center, at_rest, spectrum)
         self.at_rest = self.escaped = self.recycled = 0
-        self._pass = 0                                   # the step's own Philox counter word: one per run
+        self._pass = 0                                   # runs so far; the sweep is handed _n_pass (tally.WriterStep)
 
     def _record_pass(self, sim, at_rest, escaped):
         self.at_rest, self.escaped = int(at_rest), int(escaped)
@@ -2057,12 +2058,12 @@ class RecycleStep(tally.WriterStep):
 
     def _sweep(self, sim, prep):
         return [np.array(sim._dev.recycle_spent(self.source, _c_h_literals()[0], self.rest_on, self.top, self.center, self.spectrum, sim.seed,
-                                                self._pass), dtype=np.int64)]
+                                                self._n_pass), dtype=np.int64)]
 
     def _host_sweep(self, objs, ids, seed, prep):
         E, photon = tally.photon_energies(objs, PhotonObject)
         new = _recycle_spent(tally.vec3(objs, "r"), tally.vec3(objs, "v"), E, photon, ids, self.source, self.top,
-                             self.center, self.rest_on, self.spectrum, _c_h_literals()[0], seed, self._pass)
+                             self.center, self.rest_on, self.spectrum, _c_h_literals()[0], seed, self._n_pass)
         return new, new["spent"], (new["at_rest"].sum(), new["escaped"].sum())
 
 
@@ -2174,9 +2175,11 @@ class PathAbsorptionStep(tally.WriterStep):
 
     Every moving photon with a layer and a band is EXPOSED; a photon at rest (``v == (0, 0, 0)``; ``-0.0`` counts as 0, a NaN moves), a
     plain ``Object`` and a photon in no layer or no band are skipped.  An exposed photon is absorbed iff ``u < p`` (``p == 0`` draws
-    nothing, ``p == 1`` absorbs every one), ``u`` from a Philox block keyed by ``sim.seed``, the photon's id and a pass counter of the
-    step's own, in a counter word no other kernel uses (17): every other step draws what it draws without this one, and a photon
-    draws the same number however the run is sharded.  An absorbed photon is parked at rest where it is, ``v = 0`` and ``dv = 0`` --
+    nothing, ``p == 1`` absorbs every one), ``u`` from a Philox block keyed by ``sim.seed``, the photon's id and the step's pass counter
+    ``_n_pass``, in a counter word no other kernel uses (17): every other step draws what it draws without this one, and a photon
+    draws the same number however the run is sharded.  Several ``PathAbsorptionStep``s in one pass -- two gases whose layers and
+    bands overlap -- count on through one another (``tally.WriterStep``): their draws are independent, and a photon exposed to both
+    survives with ``(1 - p1)(1 - p2)``.  An absorbed photon is parked at rest where it is, ``v = 0`` and ``dv = 0`` --
     ``AbsorptionStep``'s convention and for its reason: a phase or absorption step later in the pass leaves it alone, and
     ``RecycleStep(at_rest=True)`` gives its slot back to the source.  A photon that is not absorbed is not written at all; ``r``,
     ``dr``, ``E``, ids and kinds are never written.  The analog treatment keeps E the photon's colour (it is no statistical weight).
@@ -2198,7 +2201,7 @@ class PathAbsorptionStep(tally.WriterStep):
         self.k, self.edges, self.center, self.E_edges = _check_path_absorb(k, edges, center, E_edges)
         self.exposed = self.absorbed = 0
         self.absorbed_by_cell = np.zeros(self.k.shape, dtype=np.int64)
-        self._pass = 0                                   # the step's own Philox counter word: one per run
+        self._pass = 0                                   # runs so far; the sweep is handed _n_pass (tally.WriterStep)
 
     def _record_pass(self, sim, exposed, absorbed, cells):
         self.exposed, self.absorbed = int(exposed), int(absorbed)
@@ -2209,13 +2212,13 @@ class PathAbsorptionStep(tally.WriterStep):
         return _path_probability(self.k, _c_h_literals()[0], np.asarray(sim.dt) if on_host else sim._dt_code())
 
     def _sweep(self, sim, p):
-        exposed, absorbed, cells = sim._dev.absorb_path(p, self.edges, self.center, self.E_edges, sim.seed, self._pass)
+        exposed, absorbed, cells = sim._dev.absorb_path(p, self.edges, self.center, self.E_edges, sim.seed, self._n_pass)
         return [np.array([exposed, absorbed], dtype=np.int64), np.asarray(cells, dtype=np.int64)]
 
     def _host_sweep(self, objs, ids, seed, p):
         E, photon = tally.photon_energies(objs, PhotonObject)
         new = _absorb_path(tally.vec3(objs, "r"), tally.vec3(objs, "v"), tally.vec3(objs, "dv"), E, photon, ids, p,
-                           self.edges, self.center, self.E_edges, seed, self._pass)
+                           self.edges, self.center, self.E_edges, seed, self._n_pass)
         return new, new["absorbed"], (new["exposed"].sum(), new["absorbed"].sum(), new["absorbed_by_cell"])
 
     terminate = tally.TallyStep.terminate                # (a row holds arrays: written as the tally steps write theirs, as plain lists)
@@ -2251,12 +2254,7 @@ def _scatter_layered(r, v, dv, E, photon, ids, p, edges, center, E_edges, first,
             "scattered_by_cell": cells}
 
 
-def _earlier_steps(sim, step):
-    """(the steps in front of ``step`` in the simulation's pass, those behind it), in the order the pass runs them."""
-    steps = getattr(sim, "steps", None) or {}
-    steps = list(steps.values() if isinstance(steps, dict) else steps)
-    at = next((k for k, s in enumerate(steps) if s is step), len(steps))
-    return steps[:at], steps[at + 1:]
+_earlier_steps = tally.earlier_steps                           # (stated once, beside the writer steps' counter rule)
 
 
 class LayeredScatterStep(tally.WriterStep):
@@ -2283,9 +2281,11 @@ class LayeredScatterStep(tally.WriterStep):
     Per pass the host makes ``p = -numpy.expm1(-k * (c * dt))`` from the simulation's current ``dt`` (``_path_probability``), and the
     device only ever sees ``p``.  Every moving photon with a layer and a band is EXPOSED (a photon at rest -- ``-0.0`` counts as 0, a
     NaN moves --, a plain ``Object`` and a photon in no layer or no band are skipped); it scatters iff ``u < p`` (``p == 0`` draws
-    nothing), ``u`` from a Philox block keyed by ``sim.seed``, the photon's id and a pass counter of the step's own, in counter words
+    nothing), ``u`` from a Philox block keyed by ``sim.seed``, the photon's id and the step's pass counter ``_n_pass``, in counter words
     no other kernel uses (23, and 24 for the direction): every other step draws what it draws without this one, and a sharded run
-    scatters the same photons the same way.  The draws are made on the device with every ``rng=`` setting.  A hit gets a direction
+    scatters the same photons the same way.  Several ``LayeredScatterStep``s in one pass count on through one another
+    (``tally.WriterStep``): each draws its own hits and its own directions.  The draws are made on the device with every ``rng=``
+    setting.  A hit gets a direction
     uniform on the sphere at speed c -- ``ReemissionStep``'s isotropic arithmetic -- and the scatter step's mark: ``v = v'``,
     ``dv = v' - v_old``.  ``r``, ``dr``, ``E``, ids and kinds are never written; plain ``Object``s are never touched.
 
@@ -2319,7 +2319,7 @@ class LayeredScatterStep(tally.WriterStep):
         self.first = None if first is None else bool(first)
         self.exposed = self.scattered = 0
         self.scattered_by_cell = np.zeros(self.k.shape, dtype=np.int64)
-        self._pass = 0                                   # the step's own Philox counter word: one per run
+        self._pass = 0                                   # runs so far; the sweep is handed _n_pass (tally.WriterStep)
 
     def _record_pass(self, sim, exposed, scattered, cells):
         self.exposed, self.scattered = int(exposed), int(scattered)
@@ -2346,13 +2346,13 @@ class LayeredScatterStep(tally.WriterStep):
 
     def _sweep(self, sim, p):
         exposed, scattered, cells = sim._dev.scatter_layered(p, self.edges, self.center, self.E_edges, self.first, _c_h_literals()[0],
-                                                             sim.seed, self._pass)
+                                                             sim.seed, self._n_pass)
         return [np.array([exposed, scattered], dtype=np.int64), np.asarray(cells, dtype=np.int64)]
 
     def _host_sweep(self, objs, ids, seed, p):
         E, photon = tally.photon_energies(objs, PhotonObject)
         new = _scatter_layered(tally.vec3(objs, "r"), tally.vec3(objs, "v"), tally.vec3(objs, "dv"), E, photon, ids, p, self.edges,
-                               self.center, self.E_edges, self.first, _c_h_literals()[0], seed, self._pass)
+                               self.center, self.E_edges, self.first, _c_h_literals()[0], seed, self._n_pass)
         return new, new["written"], (new["exposed"].sum(), new["scattered"].sum(), new["scattered_by_cell"])
 
     terminate = tally.TallyStep.terminate                # (a row holds arrays: written as the tally steps write theirs, as plain lists)
@@ -2485,9 +2485,10 @@ class ReemissionStep(tally.WriterStep):
 
     A re-emitted photon gets ``v`` at speed c along the drawn direction and ``dr = dv = 0``: later steps of the pass see a photon that
     has neither moved nor scattered.  ``r``, ids and kinds are never written; a particle that is not re-emitted is not written at
-    all; plain ``Object``s are never touched.  The draws are Philox blocks keyed by ``sim.seed``, the photon's id and a pass counter of
-    the step's own, in counter words no other kernel uses (18, 19, 20): every other step draws what it draws without this one, and a
-    sharded run re-emits the same photons the same way.  The rule is written out in include/physicl_hip.h
+    all; plain ``Object``s are never touched.  The draws are Philox blocks keyed by ``sim.seed``, the photon's id and the step's pass counter
+    ``_n_pass``, in counter words no other kernel uses (18, 19, 20): every other step draws what it draws without this one, and a
+    sharded run re-emits the same photons the same way; several ``ReemissionStep``s in one pass count on through one another
+    (``tally.WriterStep``), so each draws for itself.  The rule is written out in include/physicl_hip.h
     (pcl_step_reemit_parked); ``_reemit_parked`` restates it with numpy.  The step reads no ``dv`` rule, so it works under
     ``cl_on=False`` as well.
 
@@ -2506,7 +2507,7 @@ class ReemissionStep(tally.WriterStep):
         self.spectra, self.edges, self.center, self.eta, self.angular = _check_reemission(spectra, edges, center, eta, angular)
         self.parked = self.reemitted = 0
         self.by_layer = np.zeros(len(self.eta), dtype=np.int64)
-        self._pass = 0                                   # the step's own Philox counter word: one per run
+        self._pass = 0                                   # runs so far; the sweep is handed _n_pass (tally.WriterStep)
 
     def _record_pass(self, sim, parked, reemitted, *by_layer):
         self.parked, self.reemitted = int(parked), int(reemitted)
@@ -2519,13 +2520,13 @@ class ReemissionStep(tally.WriterStep):
 
     def _sweep(self, sim, prep):
         parked, reemitted, by_layer = sim._dev.reemit_parked(_c_h_literals()[0], self.eta, self.angular, self.spectra, self.edges,
-                                                             self.center, sim.seed, self._pass)
+                                                             self.center, sim.seed, self._n_pass)
         return [np.concatenate([[parked, reemitted], by_layer]).astype(np.int64)]
 
     def _host_sweep(self, objs, ids, seed, prep):
         E, photon = tally.photon_energies(objs, PhotonObject)
         new = _reemit_parked(tally.vec3(objs, "r"), tally.vec3(objs, "v"), E, photon, ids, self.eta, self.angular, self.spectra,
-                             self.edges, self.center, _c_h_literals()[0], seed, self._pass)
+                             self.edges, self.center, _c_h_literals()[0], seed, self._n_pass)
         return new, new["reemitted"], (new["parked"].sum(), new["reemitted"].sum(), *new["by_layer"])
 
     terminate = tally.TallyStep.terminate                # (a row holds an array: written as the tally steps write theirs, as plain lists)

@@ -92,6 +92,32 @@ def object_row(cells):
     return out
 
 
+# ---------------------------------------------------------------------------------------------- the writer steps' streams
+# The writer classes (light.py) whose draws share a Philox counter word: the two grounds draw the bounce from words 8 and 9, the two
+# phase steps the angles from 10 and 11.  Every other writer class has words of its own and is a family of one class.
+WRITER_FAMILIES = (("SurfaceReflectStep", "SpectralSurfaceStep"), ("PhaseFunctionStep", "LayeredPhaseStep"))
+N_PASS_MAX = 0xFFFFFFFF      # n_pass is one 32-bit counter word
+
+
+def writer_family(step):
+    """What the steps that share ``step``'s counter words have in common: a row of ``WRITER_FAMILIES``, or the writer class itself
+    (the class right below ``WriterStep``: a subclass of a step draws from its words)."""
+    line = [c for c in type(step).__mro__ if issubclass(c, WriterStep) and c is not WriterStep]
+    for c in line:
+        for family in WRITER_FAMILIES:
+            if c.__name__ in family:
+                return family
+    return line[-1]
+
+
+def earlier_steps(sim, step):
+    """(the steps in front of ``step`` in the simulation's pass, those behind it), in the order the pass runs them."""
+    steps = getattr(sim, "steps", None) or {}
+    steps = list(steps.values() if isinstance(steps, dict) else steps)
+    at = next((k for k, s in enumerate(steps) if s is step), len(steps))
+    return steps[:at], steps[at + 1:]
+
+
 class TallyStep(DeviceStep, MeasureStep):
     """A measure step whose row is ``[t, N, cells...]``, the cells made of integer tallies that add over shards.  A subclass
     sets ``measure_n`` and supplies three things:
@@ -150,9 +176,20 @@ class TallyStep(DeviceStep, MeasureStep):
 
 
 class WriterStep(DeviceStep, MeasureStep):
-    """A step that WRITES the store in one sweep behind a pass, draws from Philox blocks keyed by a pass counter of its own
-    (``_pass``: one per run) and records the sweep's tallies.  "refuse -> prepare -> move ``_pass`` -> one sweep -> one collective
-    -> ``_record_pass``", on the device and -- with numpy, float64 -- on host-resident objects, is here once.  A subclass sets
+    """A step that WRITES the store in one sweep behind a pass, draws from Philox blocks keyed by a pass counter of its own and
+    records the sweep's tallies.  "refuse -> prepare -> move ``_pass`` -> one sweep -> one collective -> ``_record_pass``", on the
+    device and -- with numpy, float64 -- on host-resident objects, is here once.
+
+    Two counters.  ``_pass`` is the number of runs so far.  ``_n_pass`` is the Philox counter word the run's sweep and its numpy
+    restatement are handed -- what a subclass passes on, readable after each run.  Steps whose draws share a counter word (a
+    FAMILY: ``WRITER_FAMILIES``, and every other writer class on its own) would draw the same number for the same photon if their
+    counters moved in lock-step -- two gases absorbing in one pass would absorb the same photons.  So at its first run a step takes
+    from the simulation's step list how many members ``m`` its family has in the pass and its place ``j`` among them in pass order,
+    and from then on ``_n_pass = (_pass - 1) * m + j + 1``: the members' counters interleave and never meet.  With one member (and
+    for a stand-in ``sim`` without ``steps``) that is ``_pass``.  Every rank of a sharded run holds the same step list, so nothing
+    is communicated.  A counter beyond 2**32 - 1 is refused (ValueError) before ``_pass`` moves: it would wrap.
+
+    A subclass sets
     ``_NOTE`` (what ``sim.launch_note`` says: the K-passes-per-launch kernels cannot carry the step) and ``_writes`` (which of
     ``r``, ``dr``, ``v``, ``dv``, ``E`` the host path writes back), keeps its own ``__init__`` and ``_record_pass``, and supplies:
 
@@ -167,6 +204,24 @@ class WriterStep(DeviceStep, MeasureStep):
     _fuse_role = None
     _NOTE = None
     _writes = ("v", "dv")
+    _pass = _n_pass = 0
+    _family = None                                       # (members in the pass, this step's place among them): the first run's
+
+    def _place(self, sim):
+        """(m, j): how many steps of this step's family the simulation's pass holds and this step's place among them."""
+        mine = writer_family(self)
+        front, behind = earlier_steps(sim, self)
+        same = lambda others: sum(1 for s in others if isinstance(s, WriterStep) and writer_family(s) == mine)   # noqa: E731
+        return same(front) + 1 + same(behind), same(front)
+
+    def _next_pass(self, sim):
+        """Move ``_pass`` and set ``_n_pass`` for the run that begins, or ValueError with the step as it was."""
+        place = self._family or self._place(sim)
+        n_pass = self._pass * place[0] + place[1] + 1
+        if n_pass > N_PASS_MAX:
+            raise ValueError("%s: the Philox pass counter would pass 2**32 - 1 (run %d of member %d of %d that share a counter "
+                             "word): it would wrap and repeat earlier draws" % (type(self).__name__, self._pass + 1, place[1] + 1, place[0]))
+        self._family, self._pass, self._n_pass = place, self._pass + 1, n_pass
 
     def _refuse(self, sim):
         pass
@@ -187,9 +242,9 @@ class WriterStep(DeviceStep, MeasureStep):
     def _device_run(self, sim):
         self._refuse(sim)
         prep = self._prepare(sim, False)
+        self._next_pass(sim)                             # (may refuse, too: before anything is said)
         if getattr(sim, "launch_note", self._NOTE) is None and sim._k_wanted() > 1:      # (a device run only: the host path says nothing)
             sim.launch_note = self._NOTE
-        self._pass += 1
         parts = self._sweep(sim, prep)
         sim._scattered = True                            # velocities were replaced on the device
         parts = self._reduce(sim, parts)
@@ -201,7 +256,7 @@ class WriterStep(DeviceStep, MeasureStep):
             return DeviceStep.run(self, sim)
         prep = self._prepare(sim, True)
         objs = list(sim.objects)
-        self._pass += 1
+        self._next_pass(sim)
         new, mask, record = self._host_sweep(objs, np.arange(len(objs)), getattr(sim, "seed", 0), prep)
         for k in np.flatnonzero(mask).tolist():
             o = objs[k]
