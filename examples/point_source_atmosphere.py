@@ -4,7 +4,7 @@ examples (n(r) = 2.5e25 m^-3 * exp(-(|r| - 6371 km) / 8.6 km)) with photons that
 
     python examples/point_source_atmosphere.py [n_photons] [passes] [--cone | --beam-down | --default] [--profile] [--shells]
                                                [--ground [ALBEDO]] [--phase rayleigh | hg:G | isotropic] [--omega0 W | W1,W2,...]
-                                               [--cloud LO,HI[,G]] [--cloud-tau TAU] [--recycle [TOP]] [--gas LO,HI,K[,EMIN,EMAX]] [--blue-sky]
+                                               [--cloud LO,HI[,G]] [--cloud-tau TAU] [--cloud-field NX,NY,NZ:EXTENT:TAU] [--recycle [TOP]] [--gas LO,HI,K[,EMIN,EMAX]] [--blue-sky]
                                                [--reemit [TG[,TA]]] [--ocean N] [--ground-bands E1,E2,...:a1,a2,...[:s1,...]]
                                                [--camera X,Y,Z:NX,NY,NZ:RADIUS:FOV_DEG:PIXELS]
 
@@ -38,6 +38,13 @@ per law are printed beside the shell counts.  Not together with ``--phase``: a p
 ``TAU / (HI - LO)`` per metre between LO and HI, behind the clear air's scatter step and in front of the LayeredPhaseStep, which then
 turns the cloud's hits about the direction they came from.  ``exposed``, ``scattered`` and ``scattered_by_cell`` summed over the passes
 are printed beside the shell counts.  Without it the cloud changes the phase function only and the output is as it was.
+``--cloud-field NX,NY,NZ:EXTENT:TAU`` puts a broken cloud field above the source: a GridScatterStep on a box of NX x NY x NZ cells,
+EXTENT metres wide in y and z about the source's vertical and reaching from EXTENT / 4 to 3 EXTENT / 4 above the ground (x is the
+vertical), whose scattering coefficient is a checkerboard of clear and cloudy columns: ``2 TAU / EXTENT`` per metre where NY- and
+NZ-index add up to an even number -- a vertical path through a cloudy column has the optical thickness TAU -- and 0 beside it.  It
+stands behind the clear air's scatter step (``first`` resolves to False) and in front of the phase step.  ``exposed``, ``scattered`` and
+the column sums of ``scattered_by_cell`` over the passes are printed; with ``--camera`` looking down from above the box, e.g.
+``--cloud-field 8,8,8:40000:4 --camera 6421000,0,0:-1,0,0:20000:60:32``, the image shows the gaps.  One launch per light step.
 ``--recycle [TOP]`` (an altitude in metres, default 100 km) makes the source a continuous one: a RecycleStep at the end of every pass
 gives the slots of the photons at rest (absorbed by the ground or the medium) and of those above TOP back to the source.  The
 population stays constant; the emission rate (photons recycled per pass) and the counts at rest and through the top are printed as
@@ -134,6 +141,16 @@ if "--cloud-tau" in argv:
         cloud_tau = -1.0
     if cloud is None or not 0.0 <= cloud_tau < float("inf"):
         sys.exit("--cloud-tau TAU: the cloud's optical thickness, not negative, together with --cloud LO,HI[,G]")
+cloud_field = None
+if "--cloud-field" in argv:
+    at = argv.index("--cloud-field")
+    try:
+        cells, extent, tau = (argv.pop(at + 1) if at + 1 < len(argv) else "").split(":")
+        cloud_field = (tuple(int(x) for x in cells.split(",")), float(extent), float(tau))
+        if len(cloud_field[0]) != 3 or min(cloud_field[0]) < 1 or not cloud_field[1] > 0.0 or not 0.0 <= cloud_field[2] < float("inf"):
+            raise ValueError
+    except ValueError:
+        sys.exit("--cloud-field NX,NY,NZ:EXTENT:TAU: the cells of the box, its width in metres and the optical thickness of a cloudy column")
 recycle_top = None
 if "--recycle" in argv:
     at = argv.index("--recycle")
@@ -228,6 +245,14 @@ def run(ground):
     if cloud_tau is not None:                                  # behind the clear air's scatter step, in front of the phase step: first=False
         droplets = light.LayeredScatterStep([cloud_tau / (cloud[1] - cloud[0])], edges=[R + cloud[0], R + cloud[1]])
         sim.add_step("cloud", droplets)
+    broken = None
+    if cloud_field is not None:                                # a box of cells above the source, cloudy and clear columns in a checkerboard
+        (nx, ny, nz), extent, tau = cloud_field
+        _, iy, iz = np.indices((nx, ny, nz))
+        broken = light.GridScatterStep(np.where((iy + iz) % 2 == 0, 2.0 * tau / extent, 0.0), ("x", "y", "z"),
+                                       [R + np.linspace(0.25, 0.75, nx + 1) * extent, np.linspace(-0.5, 0.5, ny + 1) * extent,
+                                        np.linspace(-0.5, 0.5, nz + 1) * extent])
+        sim.add_step("cloud_field", broken)
     if cloud is not None:                                      # from the Earth's centre to 1000 km up: Rayleigh, but for the cloud
         angles = light.LayeredPhaseStep(["rayleigh", ("hg", cloud[2])], CLOUD_WEIGHTS, edges=[0.0, R + cloud[0], R + cloud[1], R + 1000e3])
     if angles is not None:                                     # directly behind the scatter step (steps run in the order they were added)
@@ -283,7 +308,7 @@ def run(ground):
     sim.join()
     if sim.error is not None:
         raise sim.error
-    return sim, signs, shells, profile, image, tally, floor, angles, medium, lamp, vapour, eye, glow, sea, droplets
+    return sim, signs, shells, profile, image, tally, floor, angles, medium, lamp, vapour, eye, glow, sea, droplets, broken
 
 
 bare_top = None
@@ -293,7 +318,7 @@ if ground is not None and "--shells" in sys.argv:              # the same run wi
     print("without the ground: %d photons x %d steps in %.2f s" % (n, len(bare[0].ts), bare[0].run_time))
     bare[0].close(download=False)
     del bare
-sim, signs, shells, profile, image, tally, floor, angles, medium, lamp, vapour, eye, glow, sea, droplets = run(ground)
+sim, signs, shells, profile, image, tally, floor, angles, medium, lamp, vapour, eye, glow, sea, droplets, broken = run(ground)
 steps = len(sim.ts)
 print("source:", source)
 print("%d photons x %d steps in %.2f s  ->  %.3g particle-steps/s" % (n, steps, sim.run_time, n * steps / sim.run_time))
@@ -314,6 +339,14 @@ if cloud is not None:
             len(droplets.data), np.sum([row[3] for row in droplets.data], axis=0).tolist()))
 elif angles is not None:
     print("phase function %s (g = %g): %d photons re-directed over %d passes" % (angles.phase, angles.g, sum(int(row[1]) for row in angles.data), len(angles.data)))
+if broken is not None:
+    by_cell = np.sum([row[3] for row in broken.data], axis=0)
+    print("cloud field of %d x %d x %d cells, %g km wide, tau = %g in the cloudy columns (k = %g per m, first=%s): %d photons exposed, %d scattered over %d passes" % (
+        *by_cell.shape, cloud_field[1] / 1e3, cloud_field[2], broken.k.max(), broken.first, sum(int(row[1]) for row in broken.data),
+        sum(int(row[2]) for row in broken.data), len(broken.data)))
+    print("  scattered by column (summed over x, rows: y, columns: z):")
+    for line in by_cell.sum(axis=0):
+        print("   " + " ".join("%8d" % x for x in line))
 if profile is not None and profile.data:
     t, N, shells_now = profile.data[-1]
     print("altitude profile at t = %g s (%d records, one every 32 passes): %d of %d photons between 0 and 200 km" % (float(t), len(profile.data), shells_now.sum(), N))

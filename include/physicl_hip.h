@@ -1156,6 +1156,58 @@ int pcl_step_scatter_layered(pcl_ctx *ctx, int n_layers, int n_E_bins, const dou
                              const double *center_host, const double *E_edges_host, int first, double c, uint64_t seed, uint32_t pass,
                              int64_t *counts_out_host /* [2]: exposed, scattered */, int64_t *cells_out_host /* [L' * B'] */);
 
+/* Scattering on a grid of cells (GridScatterStep): who scatters, with a scattering coefficient given per cell of a grid over one to
+ * three of x, y, z and the distance from a centre, and per band of the photon's energy -- a cloud of finite width, a broken cloud
+ * field, a plume or a fog bank over half of the scene.  pcl_step_scatter_layered with pcl_step_position_grid's cells in place of the
+ * radial layers: called where that sweep is called, it scatters in ONE sweep of the resident store, the host makes
+ * p = -expm1(-k * (c*dt)) and the device only ever sees p.  Nothing is removed; r, dr, E, ids and kinds are never written.  All
+ * arithmetic is fp64, unfused, every operation rounded once, in the order written; an fp32 store's values are widened first (exact)
+ * and what is written is rounded once to the store's dtype.  B' = max(n_E_bins, 1), G = the product of n_bins_host.
+ *   a particle that is not a photon (kind 0) is skipped and never written.
+ *   at rest   iff  v0 == 0 and v1 == 0 and v2 == 0            (-0.0 counts as 0; a NaN in v: moving), as pcl_step_scatter_layered
+ *   cell g:        pcl_step_position_grid's lines, character for character -- per axis the bin with e_b <= x < e_(b+1), the last one
+ *                  closed;  a PCL_GRID_RADIUS axis bins q = ((x-cx)*(x-cx) + (y-cy)*(y-cy)) + (z-cz)*(z-cz) against the squared
+ *                  edges, no square root is taken;  a NaN, a position outside any axis's range: in no cell, skipped;  cells are
+ *                  row-major in the order of the axes.  Only the rows of r some axis needs are read.
+ *   band e:        n_E_bins == 0: e = 0, E is neither read nor asked for;  otherwise e = the bin of E (widened to double) in
+ *                  E_edges_host: [E_e, E_(e+1)), the last one closed;  a NaN, a photon outside the edges: skipped
+ *   exposed   =    a moving photon with a cell and a band;  p = p_host[g * B' + e]
+ *   p == 0:        nothing is drawn.   p > 0:  u = u53(w0, w1) of the counter (id_lo, id_hi, pass, 25);  scattered iff u < p
+ *   scattered:     (u_a, u_b) = (u53(w0, w1), u53(w2, w3)) of the counter (id_lo, id_hi, pass, 26);  w = (1, 0, 0);  mu = 1 - 2*u_a;
+ *                  the direction, v_k = c * direction_k and dv_k = v_k - v_old_k: pcl_step_scatter_layered's lines, operation for
+ *                  operation (frame, polar, turned; the same sin / cos): uniform on the sphere, the scatter kernels' mark
+ *   not scattered: first == 0:  the particle is not written at all -- a mark an earlier scatterer of the pass left in dv survives
+ *                  first == 1:  dv = 0 for every photon that is not scattered, exposed or not, at rest or not
+ * What follows from the mark is what follows from pcl_step_scatter_layered's.  The Philox4x32-10 blocks have the key (seed_lo,
+ * seed_hi), u53 of pcl_store_apply_source; ``pass`` is the caller's own counter.  The words 25 and 26 are used by nothing else (scatter
+ * kernels 0 and 1, fill and source 2..5, pcl_step_surface_reflect and pcl_step_ground_spectral 8 and 9, pcl_step_phase_redirect 10 and
+ * 11, pcl_step_absorb_scattered 12, pcl_step_phase_layered 13, pcl_step_recycle_spent 14, 15 and 16, pcl_step_absorb_path 17,
+ * pcl_step_reemit_parked 18, 19 and 20, pcl_step_refract_surface 21, pcl_step_ground_spectral 22, pcl_step_scatter_layered 23 and 24,
+ * this call 25 and 26: 0-5 and 8-26 are taken), so every other step draws what it drew, and a photon scatters the same way however
+ * the run is sharded.
+ * n_axes, coords_host, n_bins_host, edges_host, center_host: as for pcl_step_position_grid (1..PCL_GRID_MAX_AXES distinct axes,
+ * 1..PCL_GRID_MAX_BINS bins each).  n_E_bins: 0..PCL_SCATTER_GRID_MAX_BANDS; E_edges_host: n_E_bins + 1 finite, strictly increasing
+ * edges (NULL with 0).  p_host: G * B' values, every one finite and in [0, 1]; G * B' <= PCL_SCATTER_GRID_MAX_CELLS.  first: 0 or 1.
+ * ``c`` = the speed of light in code units.
+ * counts_out_host[0] = photons exposed, [1] = scattered, by this call;  cells_out_host[g * B' + e] = scattered in cell g and band e.
+ * The edges are always staged in LDS (at most 4 x 1025 doubles).  Up to 4096 cells, and while edges, probabilities (8 B a cell) and a
+ * workgroup's uint32 tallies (4 B a cell) stay within 64 KiB, the probabilities and tallies are in LDS too; above that the kernel
+ * reads p from device memory and adds its hits to the device tallies with 64-bit atomics, one add per wave and cell where the hit
+ * lanes of a wave share a cell.  Cost: the table goes up over the host link once per call and the tallies come back -- at 2^20 cells
+ * 8 MB up and 8 MB down per call, whatever the store holds; nothing is cached between calls.  A store that is not uniform costs the
+ * host traffic it costs pcl_step_surface_reflect; the ids go along only if some p > 0.
+ * PCL_ERR_ARG (everything pcl_step_position_grid refuses of the geometry, everything pcl_step_scatter_layered refuses of p, E_edges,
+ * first and c, too many cells, a NULL output) is returned before the store is looked at -- by the group's entry point before the
+ * group is --, and nothing is launched or written; PCL_ERR_STATE without a store; an empty store answers zeros without a launch.
+ * Host pointers; one device allocation per call, handed back on every way out; synchronises once, with the copy of the tallies.
+ * pcl_last_error() is generic, as for pcl_step_surface_reflect, whose source file these two entry points share. */
+#define PCL_SCATTER_GRID_MAX_BANDS 1024
+#define PCL_SCATTER_GRID_MAX_CELLS (1 << 20) /* G * B': PCL_GRID_MAX_CELLS */
+int pcl_step_scatter_grid(pcl_ctx *ctx, int n_axes, const int *coords_host, const int *n_bins_host, const double *edges_host,
+                          const double *center_host, int n_E_bins, const double *E_edges_host, const double *p_host, int first, double c,
+                          uint64_t seed, uint32_t pass, int64_t *counts_out_host /* [2]: exposed, scattered */,
+                          int64_t *cells_out_host /* [G * B'] */);
+
 /* ---- Device groups: several GPUs from ONE process ---------------------------------------------------------------
  * The reference is a single process with one simulation thread (physicl/__init__.py:400-432, 501-524); this is how
  * a host written against this ABI uses a node's GPUs the same way, without one process per GPU.  A group owns one
@@ -1270,6 +1322,12 @@ int pcl_group_step_ground_spectral(pcl_group *group, double radius, const double
 int pcl_group_step_scatter_layered(pcl_group *group, int n_layers, int n_E_bins, const double *p_host, const double *edges_host,
                                    const double *center_host, const double *E_edges_host, int first, double c, uint64_t seed,
                                    uint32_t pass, int64_t *counts_out_host, int64_t *cells_out_host);
+/* pcl_step_scatter_grid on every shard (side by side), the counts and the cells summed over the group's devices; the arguments are
+ * checked once for the group, before the group is looked at (ids are global: the same photons scatter the same way).  Every shard
+ * stages the table and brings its tallies back: at 2^20 cells 8 MB up and 8 MB down per device */
+int pcl_group_step_scatter_grid(pcl_group *group, int n_axes, const int *coords_host, const int *n_bins_host, const double *edges_host,
+                                const double *center_host, int n_E_bins, const double *E_edges_host, const double *p_host, int first,
+                                double c, uint64_t seed, uint32_t pass, int64_t *counts_out_host, int64_t *cells_out_host);
 
 /* ---------------------------------------------------------------- the counters' collective (one process per GPU)
  * The path shards by global index with no data-path exchange; the only global quantities are the int64

@@ -38,6 +38,7 @@ PATH_ABSORB_MAX_LAYERS, PATH_ABSORB_MAX_BANDS, PATH_ABSORB_MAX_CELLS = 64, 1024,
 REEMIT_MAX_LAYERS, REEMIT_MAX_BINS, REEMIT_MAX_TOTAL_BINS = 64, 1024, 2048                      # PCL_REEMIT_MAX_LAYERS ...
 SPECTRAL_MAX_BANDS = 1024                                                    # PCL_SPECTRAL_MAX_BANDS: bands of a SpectralSurfaceStep
 SCATTER_LAYERED_MAX_LAYERS, SCATTER_LAYERED_MAX_BANDS, SCATTER_LAYERED_MAX_CELLS = 64, 1024, 4096       # PCL_SCATTER_LAYERED_MAX_LAYERS ...
+SCATTER_GRID_MAX_BANDS, SCATTER_GRID_MAX_CELLS = 1024, 1 << 20                # PCL_SCATTER_GRID_MAX_BANDS, PCL_SCATTER_GRID_MAX_CELLS
 REEMIT_LAWS = {"isotropic": 0, "lambertian": 1}                              # the flags of pcl_step_reemit_parked's lambertian_host
 PROF_NEWTON, PROF_SCATTER, PROF_DELETE_MASK, PROF_COMPACT, PROF_COUNTERS, PROF_FUSED, PROF_MULTI, PROF_ONEPASS, \
     PROF_DELETE_AHEAD = range(9)
@@ -171,6 +172,7 @@ _PROTOTYPES = {
     "pcl_step_refract_surface": [_vp, c_double, _vp, c_double, c_double, c_int, c_double, c_uint64, c_uint32, _vp],
     "pcl_step_ground_spectral": [_vp, c_double, _vp, c_int, _vp, _vp, _vp, c_double, c_uint64, c_uint32, _vp, _vp],
     "pcl_step_scatter_layered": [_vp, c_int, c_int, _vp, _vp, _vp, _vp, c_int, c_double, c_uint64, c_uint32, _vp, _vp],
+    "pcl_step_scatter_grid": [_vp, c_int, _vp, _vp, _vp, _vp, c_int, _vp, _vp, c_int, c_double, c_uint64, c_uint32, _vp, _vp],
     # device groups: several GPUs from one process (the C-level counterpart of physicl_amd.multidev.MultiDevice)
     "pcl_group_create": [c_int, POINTER(c_int), POINTER(_vp)],
     "pcl_group_destroy": [_vp],
@@ -208,6 +210,7 @@ _PROTOTYPES = {
     "pcl_group_step_refract_surface": [_vp, c_double, _vp, c_double, c_double, c_int, c_double, c_uint64, c_uint32, _vp],
     "pcl_group_step_ground_spectral": [_vp, c_double, _vp, c_int, _vp, _vp, _vp, c_double, c_uint64, c_uint32, _vp, _vp],
     "pcl_group_step_scatter_layered": [_vp, c_int, c_int, _vp, _vp, _vp, _vp, c_int, c_double, c_uint64, c_uint32, _vp, _vp],
+    "pcl_group_step_scatter_grid": [_vp, c_int, _vp, _vp, _vp, _vp, c_int, _vp, _vp, c_int, c_double, c_uint64, c_uint32, _vp, _vp],
 }
 EXPORTS = sorted(list(_PROTOTYPES) + ["pcl_last_error"])
 
@@ -584,6 +587,33 @@ def _scatter_layered(entry, handle, p, edges, center, E_edges, first, c, seed, n
     ptr = lambda a: None if a is None else a.ctypes.data                                                       # noqa: E731
     check(entry(handle, L, B, pr.ctypes.data, ptr(ed), ptr(ce), ptr(Ee), int(bool(first)), float(c), int(seed) & 0xFFFFFFFFFFFFFFFF,
                 int(n_pass) & 0xFFFFFFFF, counts.ctypes.data, cells.ctypes.data))
+    return int(counts[0]), int(counts[1]), cells
+
+
+def _scatter_grid(entry, handle, p, axes, edges, center, E_edges, first, c, seed, n_pass):
+    """One call of pcl_step_scatter_grid / pcl_group_step_scatter_grid: (exposed, scattered, scattered_by_cell int64 of the grid's shape,
+    with a last dimension of B bands if ``E_edges`` is given).  ``p``: the probability of scattering per pass, one value per cell (and
+    band), row-major in the order of ``axes`` (any shape of that size); ``axes``, ``edges``, ``center``: as for ``_grid`` (the library
+    squares the edges of a radius axis); ``first``: the pass's first scatterer (a miss gets dv = 0) or not (a miss is not written);
+    ``n_pass``: the caller's own pass counter (a Philox counter word).  The table goes up and the tallies come back with every call."""
+    coords = np.array([GRID_COORDS.get(a, a) for a in axes], dtype=np.int32)
+    per_axis = [np.ascontiguousarray(e, dtype=np.float64).reshape(-1) for e in edges]
+    if len(per_axis) != len(coords):
+        raise ValueError("one sequence of edges per axis: %d axes, %d sequences" % (len(coords), len(per_axis)))
+    n_bins = np.array([len(e) - 1 for e in per_axis], dtype=np.int32)
+    ed = np.ascontiguousarray(np.concatenate(per_axis)) if per_axis else np.zeros(0)
+    Ee = None if E_edges is None else np.ascontiguousarray(E_edges, dtype=np.float64).reshape(-1)
+    B = 0 if Ee is None else len(Ee) - 1
+    shape = [max(int(b), 0) for b in n_bins] + ([B] if Ee is not None else [])
+    pr = np.ascontiguousarray(p, dtype=np.float64).reshape(-1)
+    if len(pr) != int(np.prod(shape)):
+        raise ValueError("p holds %d values for a grid of shape %r" % (len(pr), tuple(shape)))
+    ce = None if center is None else np.ascontiguousarray(center, dtype=np.float64).reshape(3)
+    counts = np.zeros(2, dtype=np.int64)
+    cells = np.zeros(shape, dtype=np.int64)
+    ptr = lambda a: None if a is None else a.ctypes.data                                                       # noqa: E731
+    check(entry(handle, len(coords), coords.ctypes.data, n_bins.ctypes.data, ed.ctypes.data, ptr(ce), B, ptr(Ee), pr.ctypes.data,
+                int(bool(first)), float(c), int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_pass) & 0xFFFFFFFF, counts.ctypes.data, cells.ctypes.data))
     return int(counts[0]), int(counts[1]), cells
 
 
@@ -1220,6 +1250,13 @@ class Device:
         ``n_pass``: the caller's own pass counter (a Philox counter word)."""
         return _scatter_layered(self.lib.pcl_step_scatter_layered, self.ctx, p, edges, center, E_edges, first, c, seed, n_pass)
 
+    def scatter_grid(self, p, axes, edges, center=None, E_edges=None, first=True, c=0.0, seed=0, n_pass=0):
+        """Scattering on a grid of cells: every moving photon with a cell of the grid over ``axes`` (``position_grid``'s cells) and a
+        band of ``E_edges`` scatters with the probability ``p[cell][band]`` into a direction uniform on the sphere, ``dv = v' - v_old``;
+        with ``first`` every other photon gets ``dv = 0``, without it nothing else is written -- one sweep (pcl_step_scatter_grid).
+        ``(exposed, scattered, scattered_by_cell int64 of the grid's shape (+ bands))``.  ``n_pass``: the caller's own pass counter."""
+        return _scatter_grid(self.lib.pcl_step_scatter_grid, self.ctx, p, axes, edges, center, E_edges, first, c, seed, n_pass)
+
 
 class DeviceGroup:
     """``pcl_group_*``: several contexts in one process, sharded by global index, behind the C ABI (the shim owns the
@@ -1363,6 +1400,10 @@ class DeviceGroup:
     def scatter_layered(self, p, edges=None, center=None, E_edges=None, first=True, c=0.0, seed=0, n_pass=0):
         """``Device.scatter_layered`` on every context of the group, the tallies summed (pcl_group_step_scatter_layered)."""
         return _scatter_layered(self.lib.pcl_group_step_scatter_layered, self.g, p, edges, center, E_edges, first, c, seed, n_pass)
+
+    def scatter_grid(self, p, axes, edges, center=None, E_edges=None, first=True, c=0.0, seed=0, n_pass=0):
+        """``Device.scatter_grid`` on every context of the group, the tallies summed (pcl_group_step_scatter_grid)."""
+        return _scatter_grid(self.lib.pcl_group_step_scatter_grid, self.g, p, axes, edges, center, E_edges, first, c, seed, n_pass)
 
     def download(self, field, n=None, offset=0, dtype=None):
         n = self.count - offset if n is None else n

@@ -108,6 +108,20 @@ def all_sweeps_of(unit):
     return every_sweep_of(unit) + MEDIUM_SWEEPS.get(os.path.basename(unit["src"]), ())
 
 
+# The medium's scattering on a grid of cells, in the same form (tests/test_scatter_grid_cpu.py holds it to it): the scattering by
+# layer stands beside it, whose draw and direction it shares; four instantiations, an LDS and a global form per dtype, as the position
+# grid's.  None of the functions above folds this table in -- the tests of the older sweeps hold all four to their contents --;
+# volume_sweeps_of() is every sweep a unit holds.
+VOLUME_SWEEPS = {
+    "pcl_surface.hip": (_sweep("pcl_step_scatter_grid", "pcl_group_step_scatter_grid", "k_scatter_grid", count=4),),
+}
+
+
+def volume_sweeps_of(unit):
+    """Every sweep a unit of ADDONS holds, in the file's order: all_sweeps_of(unit), then what VOLUME_SWEEPS adds."""
+    return all_sweeps_of(unit) + VOLUME_SWEEPS.get(os.path.basename(unit["src"]), ())
+
+
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -ffp-contract=off: the reference's kernels must be evaluated unfused (bit-exact parity, DESIGN.md)
 # -disable-machine-licm: the pre-RA pass hoists every scalar constant out of the kernels' long loops, the scalar register file

@@ -197,6 +197,24 @@
 //   moving, b, e, exposed, p = P[b][e]: k_absorb_path's lines;  p > 0: u = u53(w0, w1) of counter (id_lo, id_hi, pass, 23);
 //   scattered iff u < p:  (u_a, u_b) of counter (id_lo, id_hi, pass, 24);  w = (1, 0, 0);  mu = 1 - 2*u_a;  e1, e2 = frame(w);
 //   sc, ss = polar(mu, u_b);  v_k = c*turned;  dv_k = v_k - v_old_k;   first and a photon that is not scattered:  dv_k = 0
+//
+// Scattering on a grid of cells (GridScatterStep): who scatters, decided per cell of a one- to three-dimensional grid over x, y, z and
+// the distance from a centre, and per energy band -- a cloud of finite width, a broken cloud field, a plume.  k_position_grid's cell,
+// k_scatter_layered's exposure, draw, direction and mark.  The table may hold 2^20 probabilities: it does not always fit in LDS.
+//
+//   k_scatter_grid<T, lds>   one grid-stride sweep in k_scatter_layered's shape; a moving photon loads the r rows some axis needs and,
+//                            with bands, E, and is looked up axis by axis in the edges (always in LDS).  lds = true: the
+//                            probabilities and the workgroup's uint32 tallies by cell sit in LDS too (up to 4096 cells, the whole within
+//                            64 KiB);  lds = false: p is a read-only load from the device table (8 MB at most, L2-resident over a
+//                            sweep) and a hit adds to its cell in device memory with a 64-bit atomic.  In both forms the hit lanes of
+//                            a wave that share one cell issue ONE add of their count, and one add for a whole run of such trips in
+//                            the same cell (k_position_grid's ballot and compare): a bulk run starts with every photon in one cell.
+//                            exposed and scattered are LDS counts fed from wave ballots in both forms.
+//
+// Operation order (what light._scatter_grid restates with numpy):
+//   moving: k_scatter_layered's line;  cell: k_position_grid's lines, then the band as in k_absorb_path;  p = P[cell][e];
+//   p > 0: u = u53(w0, w1) of counter (id_lo, id_hi, pass, 25);  scattered iff u < p:  (u_a, u_b) of counter (id_lo, id_hi, pass, 26);
+//   the direction, v and dv: k_scatter_layered's lines;   first and a photon that is not scattered:  dv_k = 0
 #include "pcl_sweep.h"
 
 #include "pcl_device.h" // (after the HIP runtime and the ABI's header, which pcl_sweep.h brings)
@@ -2111,6 +2129,278 @@ int group_scatter_layered(pcl_group *group, int n_layers, int n_E_bins, const do
     });
 }
 
+// ---- scattering on a grid of cells: the kernel stands with its host side, behind the older sweeps (their tests read the file by its order)
+// The counter words of a scattering on a grid: who scatters, where to (the header lists who uses which word: 25 and 26 are this
+// kernel's alone).
+constexpr uint32_t kGridScatterDraw = 25, kGridScatterDir = 26;
+// The LDS form's switch-over: up to this many cells the probabilities and a workgroup's tallies sit in LDS beside the edges, if
+// the whole stays within what a launch may ask for; above it both stay in device memory.
+constexpr int kGridScatterLdsCells = 4096;
+constexpr size_t kGridScatterLdsBytes = 64 * 1024;
+static_assert(PCL_SCATTER_GRID_MAX_CELLS == PCL_GRID_MAX_CELLS, "the medium's grid is the position grid's");
+
+template <typename T>
+struct gscatter_args {
+    const T *r[3];               // rows some axis needs (NULL otherwise)
+    T *v[3], *dv[3];
+    const T *E;                  // NULL without energy bands
+    const unsigned char *kind;   // NULL: every particle is a photon
+    const int64_t *ids;          // NULL: the id of slot i is id_base + i
+    const double *tables;        // p [n_cells] | the axes' edges one after another (a radius axis: squared) | E edges (B + 1, if B), device
+    unsigned long long *out;     // exposed, scattered | scattered by cell [n_cells]; device, zeroed by the entry point
+    int64_t N, ts, id_base;      // particles, tile stride of the slab (elements), id of slot 0
+    int tile_log;                // log2 of the tile length
+    int n_axes, n_E;             // axes of the grid, B (0: one column for every energy, B' = 1)
+    int n_edges, n_cells;        // every edge of the axes and of E; cells of the grid x B'
+    int coord[PCL_GRID_MAX_AXES], n_bins[PCL_GRID_MAX_AXES], edge_at[PCL_GRID_MAX_AXES], E_at;
+    int rows;                    // bit k: row k of r is read
+    int first;                   // 1: the pass's first scatterer -- a photon that is not scattered gets dv = 0
+    double c[3], speed;
+    uint32_t k0, k1, pass;       // Philox key (seed_lo, seed_hi), the step's own pass counter
+};
+
+template <typename T, bool kLds>
+__global__ void __launch_bounds__(kBlock) k_scatter_grid(gscatter_args<T> a) {
+    extern __shared__ double s_mem[];                                  // edges | p (LDS form) | exposed, scattered | by cell (LDS form)
+    const int nE = a.n_E, n_lds_p = kLds ? a.n_cells : 0;
+    double *s_edges = s_mem;
+    double *s_p = s_mem + a.n_edges;
+    uint32_t *s_cnt = reinterpret_cast<uint32_t *>(s_p + n_lds_p);
+    uint32_t *s_cell = s_cnt + 2;
+    const int n_cnt = 2 + n_lds_p;
+    for (int k = threadIdx.x; k < a.n_edges; k += kBlock) s_edges[k] = a.tables[a.n_cells + k];
+    for (int k = threadIdx.x; k < n_lds_p; k += kBlock) s_p[k] = a.tables[k];
+    for (int k = threadIdx.x; k < n_cnt; k += kBlock) s_cnt[k] = 0;    // (the cells follow the two counts)
+    __syncthreads();
+    const double *s_E = s_edges + a.E_at;
+    const int lane = threadIdx.x & 63;
+    const int64_t stride = grid_stride(), n_round = whole_waves(a.N);   // (the ballots below need whole waves inside the loop)
+    // wave-uniform, as in k_position_grid: the cell and the count of consecutive trips whose hit lanes all sat in that one cell,
+    // not added yet (fewer than 2^32: kMaxSlotsPerWorkgroup).  Every bulk run starts with all photons in ONE cell, and adds to one
+    // address serialise where they are carried out; so a run is added once.
+    int run_cell = 0;
+    uint32_t run_n = 0;
+    auto flush_run = [&]() {
+        if (lane == 0 && run_n) {
+            if (kLds) atomicAdd(&s_cell[run_cell], run_n);
+            else atomicAdd(&a.out[2 + run_cell], (unsigned long long)run_n);
+        }
+        run_n = 0;
+    };
+    for (int64_t i = first_slot(); i < n_round; i += stride) {
+        const bool in = i < a.N;
+        const int64_t ti = tile_index(i, a.tile_log, a.ts);
+        bool photon = in;
+        if (photon && a.kind) photon = a.kind[i] != 0;                  // plain Objects are never touched
+        // moving: at_rest, written out as in k_scatter_layered and negated -- -0.0 == 0, a NaN moves, v0 != 0 loads no more of v
+        const bool go = photon && !((double)a.v[0][ti] == 0.0 && (double)a.v[1][ti] == 0.0 && (double)a.v[2][ti] == 0.0);
+        int cell = -1;                                                  // (cell of the grid) * B' + e; -1: not exposed
+        if (go) {
+            double x[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                if ((a.rows >> k) & 1) x[k] = (double)a.r[k][ti];       // fp32 widens exactly
+            bool ok = true;
+            int at = 0;
+            for (int ax = 0; ax < a.n_axes; ++ax) {                     // k_position_grid's lines
+                const int co = a.coord[ax], nb = a.n_bins[ax];
+                const double *e = s_edges + a.edge_at[ax];
+                double q;
+                if (co == PCL_GRID_RADIUS) {   // q, unfused, in this order (the library is built with -ffp-contract=off)
+                    const double dx = x[0] - a.c[0], dy = x[1] - a.c[1], dz = x[2] - a.c[2];
+                    q = (dx * dx + dy * dy) + dz * dz;
+                } else {
+                    q = co == 0 ? x[0] : (co == 1 ? x[1] : x[2]);
+                }
+                ok = ok && q >= e[0] && q <= e[nb];                     // NaN and anything outside the axis's range are in no cell
+                at = at * nb + bin_of(e, nb, q);
+            }
+            if (ok && nE > 0) {
+                const double e = (double)a.E[ti];
+                ok = e >= s_E[0] && e <= s_E[nE];                       // NaN and under/overflow: in no band
+                at = at * nE + bin_of(s_E, nE, e);
+            }
+            if (ok) cell = at;
+        }
+        const bool exposed = cell >= 0;
+        bool hit = false;
+        uint64_t id = 0;
+        if (exposed) {
+            const double p = kLds ? s_p[cell] : a.tables[cell];         // (global form: a read-only load, the table stays in L2)
+            if (p > 0.0) {                                              // a clear cell draws nothing
+                id = id_of(a.ids, a.id_base, i);
+                hit = first_u53(pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, kGridScatterDraw, a.k0, a.k1)) < p;   // u < 1: p == 1 scatters everybody
+            }
+        }
+        const unsigned long long m_hit = __ballot(hit);
+        const uint32_t n_exp = (uint32_t)__popcll(__ballot(exposed)), n_hit = (uint32_t)__popcll(m_hit);
+        if (lane == 0 && n_exp) atomicAdd(&s_cnt[0], n_exp);
+        if (lane == 0 && n_hit) atomicAdd(&s_cnt[1], n_hit);
+        bool counted = false;                                           // this lane's hit is in the wave's run
+        if (m_hit) {                                                    // (wave-uniform)
+            const int c0 = __shfl(cell, __ffsll((long long)m_hit) - 1);
+            if (__ballot(hit && cell == c0) == m_hit) {                 // every hit lane of the wave in one cell: one add of their count,
+                if (c0 != run_cell) {                                   // put off while the next trips hit in the same cell
+                    flush_run();
+                    run_cell = c0;
+                }
+                run_n += n_hit;
+                counted = true;
+            }
+        }
+        if (a.first && photon && !hit) {                                // the scatter step's miss: "did not scatter", the three rows together
+#pragma unroll
+            for (int k = 0; k < 3; ++k) a.dv[k][ti] = (T)0.0;
+        }
+        if (!hit) continue;     // lanes that are left alone wait at the loop's head: no ballot below this line
+        if (!counted) {
+            if (kLds) atomicAdd(&s_cell[cell], 1u);
+            else atomicAdd(&a.out[2 + cell], 1ull);
+        }
+        double u_a, u_b, sc, ss, e1[3], e2[3];
+        const double w[3] = {1.0, 0.0, 0.0};
+        pair_u53(pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, kGridScatterDir, a.k0, a.k1), &u_a, &u_b);
+        const double mu = __dsub_rn(1.0, __dmul_rn(2.0, u_a));                                       // uniform on the sphere
+        polar(mu, u_b, &sc, &ss);
+        frame(w, e1, e2);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double vo = (double)a.v[k][ti];                       // the velocity before the scatter (fp32 widens exactly)
+            const double vk = __dmul_rn(a.speed, turned(sc, ss, mu, e1[k], e2[k], w[k]));
+            a.v[k][ti] = (T)vk;
+            a.dv[k][ti] = (T)__dsub_rn(vk, vo);
+        }
+    }
+    flush_run();
+    __syncthreads();
+    // pcl_sweep::flush_cells, written out, for the reason given in k_absorb_scattered: a further caller changes the older kernels
+    for (int k = threadIdx.x; k < n_cnt; k += kBlock)
+        if (s_cnt[k]) atomicAdd(&a.out[k], (unsigned long long)s_cnt[k]);
+}
+
+struct gscatter_spec { // a call's arguments, checked; what the kernel compares against
+    int n_axes = 0, n_E = 0, n_edges = 0, rows = 0, E_at = 0;
+    int64_t n_p = 1;            // cells of the grid x B'
+    int coord[PCL_GRID_MAX_AXES], n_bins[PCL_GRID_MAX_AXES], edge_at[PCL_GRID_MAX_AXES];
+    double c[3] = {0.0, 0.0, 0.0}, speed = 0.0;
+    int first = 0;
+    bool draws = false;         // some cell has p > 0: the ids are needed
+    std::vector<double> tables; // p | the axes' edges (a radius axis: squared) | E edges
+    size_t cells() const { return (size_t)2 + (size_t)n_p; }            // exposed, scattered | by cell
+    size_t lds_small() const { return (size_t)n_edges * sizeof(double) + 2 * sizeof(uint32_t); }               // the global form's
+    size_t lds_whole() const { return lds_small() + (size_t)n_p * (sizeof(double) + sizeof(uint32_t)); }       // the LDS form's
+    bool lds_form() const { return n_p <= kGridScatterLdsCells && lds_whole() <= kGridScatterLdsBytes; }
+    spans out(int64_t *counts, int64_t *by_cell) const { return {{counts, 2}, {by_cell, (size_t)n_p}}; }
+};
+
+// Everything PCL_ERR_ARG stands for except the NULL context; nothing is launched or written before this has passed.  The geometry
+// by pcl_grid.hip's check_spec, p by check_pabsorb, first and c by check_lscatter.
+bool check_gscatter(int n_axes, const int *coords, const int *n_bins, const double *edges, const double *center, int n_E,
+                    const double *E_edges, const double *p, int first, double c, const int64_t *counts_out, const int64_t *cells_out,
+                    gscatter_spec &s) {
+    if ((first != 0 && first != 1) || !std::isfinite(c)) return false;
+    if (!coords || !n_bins || !edges || !p || !counts_out || !cells_out) return false;
+    if (n_axes < 1 || n_axes > PCL_GRID_MAX_AXES || n_E < 0 || n_E > PCL_SCATTER_GRID_MAX_BANDS || (n_E > 0 && !E_edges)) return false;
+    s.first = first; s.speed = c; s.n_axes = n_axes; s.n_E = n_E;
+    int seen = 0;
+    for (int a = 0; a < n_axes; ++a) {
+        if (coords[a] < PCL_GRID_X || coords[a] > PCL_GRID_RADIUS || ((seen >> coords[a]) & 1)) return false;
+        seen |= 1 << coords[a];
+        if (n_bins[a] < 1 || n_bins[a] > PCL_GRID_MAX_BINS) return false;
+        s.n_p *= n_bins[a];
+    }
+    s.n_p *= n_E > 0 ? n_E : 1;                                          // (below 2^41: no overflow)
+    if (s.n_p > PCL_SCATTER_GRID_MAX_CELLS) return false;
+    if (center)
+        for (int k = 0; k < 3; ++k) {
+            if (!std::isfinite(center[k])) return false;
+            s.c[k] = center[k];
+        }
+    s.tables.reserve((size_t)s.n_p + 4 * (PCL_GRID_MAX_BINS + 1));
+    for (int64_t k = 0; k < s.n_p; ++k) {
+        if (!(p[k] >= 0.0 && p[k] <= 1.0)) return false;                // (NaN as well)
+        s.draws = s.draws || p[k] > 0.0;
+        s.tables.push_back(p[k]);
+    }
+    for (int a = 0; a < n_axes; ++a) {
+        s.coord[a] = coords[a];
+        s.n_bins[a] = n_bins[a];
+        s.edge_at[a] = s.n_edges;
+        s.rows |= coords[a] == PCL_GRID_RADIUS ? 7 : 1 << coords[a];
+        // q of a radius axis is compared against e*e: no square root anywhere
+        if (!check_edges(edges + s.n_edges, n_bins[a], coords[a] == PCL_GRID_RADIUS ? kEdgeSquare : kEdgePlain, &s.tables)) return false;
+        s.n_edges += n_bins[a] + 1;
+    }
+    s.E_at = s.n_edges;
+    if (n_E > 0) {
+        if (!check_edges(E_edges, n_E, kEdgePlain, &s.tables)) return false;
+        s.n_edges += n_E + 1;
+    }
+    return true;
+}
+
+template <typename T>
+int launch_gscatter(pcl_ctx *ctx, const store_view &v, const gscatter_spec &s, uint64_t seed, uint32_t pass, const staged &st) {
+    gscatter_args<T> a{};
+    for (int k = 0; k < 3; ++k) {
+        void *r = nullptr, *vel = nullptr, *dv = nullptr;
+        if ((s.rows >> k) & 1) PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_R0 + k, &r));
+        PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_V0 + k, &vel));
+        PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_DV0 + k, &dv));     // (what makes a lazy dv real: a hit's and, with first, a miss's is written)
+        a.r[k] = static_cast<const T *>(r); a.v[k] = static_cast<T *>(vel); a.dv[k] = static_cast<T *>(dv);
+        a.c[k] = s.c[k];
+    }
+    // E is asked for only with energy bands: the pointer costs a wavelength-dependent scatter step its term cache (pcl_shell.hip).
+    void *E = nullptr;
+    if (s.n_E > 0) PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_E, &E));
+    a.E = static_cast<const T *>(E); a.kind = st.kind; a.ids = st.ids; a.tables = st.tables; a.out = st.out;
+    a.N = v.N; a.ts = v.ts; a.id_base = st.id_base; a.tile_log = v.tile_log;
+    a.n_axes = s.n_axes; a.n_E = s.n_E; a.n_edges = s.n_edges; a.n_cells = (int)s.n_p; a.E_at = s.E_at; a.rows = s.rows;
+    for (int k = 0; k < s.n_axes; ++k) { a.coord[k] = s.coord[k]; a.n_bins[k] = s.n_bins[k]; a.edge_at[k] = s.edge_at[k]; }
+    a.first = s.first; a.speed = s.speed;
+    a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32); a.pass = pass;
+    const bool lds_form = s.lds_form();
+    const size_t lds = lds_form ? s.lds_whole() : s.lds_small();
+    const int64_t grid = balanced_grid(v.N, v.n_cu, resident_per_cu(lds));
+    if (lds_form) hipLaunchKernelGGL((k_scatter_grid<T, true>), dim3((unsigned)grid), dim3(kBlock), lds, v.stream, a);
+    else hipLaunchKernelGGL((k_scatter_grid<T, false>), dim3((unsigned)grid), dim3(kBlock), lds, v.stream, a);
+    return hipGetLastError() == hipSuccess ? PCL_OK : PCL_ERR_HIP;
+}
+
+int scatter_grid(pcl_ctx *ctx, int n_axes, const int *coords_host, const int *n_bins_host, const double *edges_host,
+                 const double *center_host, int n_E_bins, const double *E_edges_host, const double *p_host, int first, double c,
+                 uint64_t seed, uint32_t pass, int64_t *counts_out_host, int64_t *cells_out_host) {
+    gscatter_spec s;
+    if (!ctx || !check_gscatter(n_axes, coords_host, n_bins_host, edges_host, center_host, n_E_bins, E_edges_host, p_host, first, c,
+                                counts_out_host, cells_out_host, s))
+        return bad_argument(ctx);
+    const spans out = s.out(counts_out_host, cells_out_host);
+    store_view v;
+    staged st(ctx);
+    PCL_SWEEP_TRY(open_store(ctx, PCL_V0, &v));
+    zero_spans(out);
+    if (v.N <= 0) return PCL_OK;
+    PCL_SWEEP_TRY(stage(st, v, s.cells(), s.tables.data(), s.tables.size(), s.draws));   // the ids only if somebody may draw
+    PCL_SWEEP_TRY(PCL_SWEEP_LAUNCH(v, launch_gscatter, ctx, v, s, seed, pass, st));
+    return fetch(st, out);
+}
+
+int group_scatter_grid(pcl_group *group, int n_axes, const int *coords_host, const int *n_bins_host, const double *edges_host,
+                       const double *center_host, int n_E_bins, const double *E_edges_host, const double *p_host, int first, double c,
+                       uint64_t seed, uint32_t pass, int64_t *counts_out_host, int64_t *cells_out_host) {
+    gscatter_spec s;                                                    // the arguments first: a refused call looks at no group
+    if (!check_gscatter(n_axes, coords_host, n_bins_host, edges_host, center_host, n_E_bins, E_edges_host, p_host, first, c,
+                        counts_out_host, cells_out_host, s))
+        return bad_argument(nullptr);
+    std::vector<pcl_ctx *> ctx;
+    PCL_SWEEP_TRY(shards_of(group, ctx));
+    if (ctx.empty()) return bad_argument(nullptr);
+    return sum_shards(ctx, s.out(counts_out_host, cells_out_host), [&](pcl_ctx *one, int64_t *p) {
+        return pcl_step_scatter_grid(one, n_axes, coords_host, n_bins_host, edges_host, center_host, n_E_bins, E_edges_host, p_host, first,
+                                     c, seed, pass, p, p + 2);
+    });
+}
+
 } // namespace
 
 extern "C" {
@@ -2268,6 +2558,24 @@ int pcl_group_step_scatter_layered(pcl_group *group, int n_layers, int n_E_bins,
     return guarded([&] {
         return group_scatter_layered(group, n_layers, n_E_bins, p_host, edges_host, center_host, E_edges_host, first, c, seed, pass,
                                      counts_out_host, cells_out_host);
+    });
+}
+
+int pcl_step_scatter_grid(pcl_ctx *ctx, int n_axes, const int *coords_host, const int *n_bins_host, const double *edges_host,
+                          const double *center_host, int n_E_bins, const double *E_edges_host, const double *p_host, int first, double c,
+                          uint64_t seed, uint32_t pass, int64_t *counts_out_host, int64_t *cells_out_host) {
+    return guarded([&] {
+        return scatter_grid(ctx, n_axes, coords_host, n_bins_host, edges_host, center_host, n_E_bins, E_edges_host, p_host, first, c, seed,
+                            pass, counts_out_host, cells_out_host);
+    });
+}
+
+int pcl_group_step_scatter_grid(pcl_group *group, int n_axes, const int *coords_host, const int *n_bins_host, const double *edges_host,
+                                const double *center_host, int n_E_bins, const double *E_edges_host, const double *p_host, int first,
+                                double c, uint64_t seed, uint32_t pass, int64_t *counts_out_host, int64_t *cells_out_host) {
+    return guarded([&] {
+        return group_scatter_grid(group, n_axes, coords_host, n_bins_host, edges_host, center_host, n_E_bins, E_edges_host, p_host, first,
+                                  c, seed, pass, counts_out_host, cells_out_host);
     });
 }
 

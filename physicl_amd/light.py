@@ -503,12 +503,12 @@ def _check_grid(axes, edges, center):
     return axes, edges, tally.check_center(center)
 
 
-def _grid_of_positions(r, axes, edges, center):
-    """The grid of pcl_step_position_grid from an (n, 3) float64 array of positions, with numpy: per axis the bin with
-    e_b <= v < e_(b+1), the last bin closed (numpy.histogramdd); a radius axis bins the squared distance
-    ((x-cx)**2 + (y-cy)**2) + (z-cz)**2 against the squared edges."""
+def _cell_of_positions(r, axes, edges, center):
+    """(who has a cell, the cell -- row-major in the order of ``axes``; arbitrary where there is none) of an (n, 3) float64 array of
+    positions, as pcl_step_position_grid and pcl_step_scatter_grid find it, with numpy: per axis the bin with e_b <= v < e_(b+1), the
+    last bin closed (numpy.histogramdd); a radius axis bins the squared distance ((x-cx)**2 + (y-cy)**2) + (z-cz)**2 against the
+    squared edges; a NaN and a position outside any axis's range are in no cell."""
     from ._hip import GRID_COORDS
-    r = np.asarray(r, dtype=np.float64).reshape(-1, 3)
     ok, cell = np.ones(len(r), dtype=bool), np.zeros(len(r), dtype=np.int64)
     for a, e in zip(axes, edges):
         if a == "r":
@@ -520,6 +520,13 @@ def _grid_of_positions(r, axes, edges, center):
         with np.errstate(invalid="ignore"):
             ok &= (v >= e[0]) & (v <= e[-1])
         cell = cell * nb + np.clip(np.searchsorted(e, v, side="right") - 1, 0, nb - 1)
+    return ok, cell
+
+
+def _grid_of_positions(r, axes, edges, center):
+    """The grid of pcl_step_position_grid from an (n, 3) float64 array of positions, with numpy (``_cell_of_positions``)."""
+    r = np.asarray(r, dtype=np.float64).reshape(-1, 3)
+    ok, cell = _cell_of_positions(r, axes, edges, center)
     shape = [len(e) - 1 for e in edges]
     return np.bincount(cell[ok], minlength=int(np.prod(shape))).astype(np.int64).reshape(shape)
 
@@ -2274,8 +2281,8 @@ class LayeredScatterStep(tally.WriterStep):
     * ``first``: True -- this step is the pass's first scatterer and keeps ``ScatterIsotropicStep``'s contract: every photon it does
       not scatter gets ``dv = 0``, exposed or not, at rest or not.  False -- it stands behind another scatterer: a photon that is not
       scattered is not written at all, so the earlier step's mark survives.  None (the default) is decided at the step's first run
-      from the simulation's step order: False iff a ``ScatterIsotropicStep``, a ``ScatterSphericalStep`` or another
-      ``LayeredScatterStep`` stands earlier in the pass.  A ``ScatterIsotropicStep`` BEHIND this step would wipe its marks: the first
+      from the simulation's step order: False iff a ``ScatterIsotropicStep``, a ``ScatterSphericalStep``, another
+      ``LayeredScatterStep`` or a ``GridScatterStep`` stands earlier in the pass.  A ``ScatterIsotropicStep`` BEHIND this step would wipe its marks: the first
       run raises ``ValueError``.
 
     Per pass the host makes ``p = -numpy.expm1(-k * (c * dt))`` from the simulation's current ``dt`` (``_path_probability``), and the
@@ -2333,12 +2340,12 @@ class LayeredScatterStep(tally.WriterStep):
             for other in behind:
                 if isinstance(other, ScatterIsotropicStep):
                     raise ValueError("a pass marks its scattered photons once: the simulation's steps hold a %s behind this "
-                                     "LayeredScatterStep, and it would overwrite the dv of every photon this step has scattered -- "
-                                     "put the LayeredScatterStep behind it" % type(other).__name__)
+                                     "%s, and it would overwrite the dv of every photon this step has scattered -- "
+                                     "put the %s behind it" % (type(other).__name__, type(self).__name__, type(self).__name__))
             if first is None:
-                first = not any(isinstance(other, (ScatterIsotropicStep, LayeredScatterStep)) for other in front)
+                first = not any(isinstance(other, (ScatterIsotropicStep, LayeredScatterStep, GridScatterStep)) for other in front)
         if first is False:
-            _dv_rule_refusal(sim, "LayeredScatterStep(first=False)", "the earlier scatter step's marks")
+            _dv_rule_refusal(sim, "%s(first=False)" % type(self).__name__, "the earlier scatter step's marks")
         self.first = first
 
     def _prepare(self, sim, on_host):                    # p of this pass's dt; a dt that is refused raises here
@@ -2356,6 +2363,148 @@ class LayeredScatterStep(tally.WriterStep):
         return new, new["written"], (new["exposed"].sum(), new["scattered"].sum(), new["scattered_by_cell"])
 
     terminate = tally.TallyStep.terminate                # (a row holds arrays: written as the tally steps write theirs, as plain lists)
+
+
+# ---------------------------------------------------------------------------------------------- scattering on a grid of cells
+_GRID_SCATTER_WORDS = (25, 26)                                # the draw, the direction (the header lists the words taken)
+
+
+def _check_grid_scatter(k, axes, edges, center, E_edges):
+    """(k as a float64 array of the grid's shape (+ (B,) with E_edges), axes, edges, centre, energy edges or None) of a
+    GridScatterStep, or ValueError for everything pcl_step_scatter_grid would refuse.  A single number is broadcast."""
+    from ._hip import SCATTER_GRID_MAX_BANDS, SCATTER_GRID_MAX_CELLS      # (the header's limits: one place)
+    axes, edges, center = _check_grid(axes, edges, center)
+    if E_edges is not None:
+        E_edges = tally.check_edges("E_edges", E_edges, SCATTER_GRID_MAX_BANDS)
+    try:
+        ka = np.array(k, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("k must be a number, or numbers per cell of the grid (and energy band)") from None
+    want = tuple(len(e) - 1 for e in edges) + (() if E_edges is None else (len(E_edges) - 1,))
+    if ka.shape not in ((), want):
+        raise ValueError("k must be one number or have the shape %r -- %s -- got %r" % (
+            want, "the grid's cells" + ("" if E_edges is None else " by bands of E_edges"), ka.shape))
+    if not np.all(np.isfinite(ka) & (ka >= 0.0)):             # (False for NaN as well)
+        raise ValueError("k must be finite and not negative, got %r" % (k,))
+    cells = int(np.prod(want))
+    if cells > SCATTER_GRID_MAX_CELLS:
+        raise ValueError("k: %s are %d cells, at most %d are supported" % (" x ".join(str(n) for n in want), cells, SCATTER_GRID_MAX_CELLS))
+    return np.ascontiguousarray(np.broadcast_to(ka, want)), axes, edges, center, E_edges
+
+
+def _scatter_grid(r, v, dv, E, photon, ids, p, axes, edges, center, E_edges, first, c, seed, n_pass, dtype=np.float64):
+    """What pcl_step_scatter_grid makes of (n, 3) float64 positions, velocities and last velocity changes, the energies, who is a
+    photon and the particles' ids, with numpy -- every operation the device's operation in the device's order, one rounding each
+    (include/physicl_hip.h), and what is written rounded once to ``dtype``.  Who is exposed, who is hit and every tally are the
+    device's bit for bit; sin / cos are libm's here.  ``p``: the probabilities, one per cell of the grid (row-major in the order of
+    ``axes``) and band; ``first``: the pass's first scatterer (a photon that is not scattered gets dv = 0) or not (it is not written).
+    A dict: ``v, dv`` the new state (float64 arrays; rows that are not written are the arguments'), the boolean masks ``exposed``,
+    ``scattered`` and ``written``, ``cell`` (int64: cell of the grid times B' plus the band, of every exposed photon, -1 for none)
+    and the tally ``scattered_by_cell`` (int64, the grid's shape, with a last dimension of B bands if ``E_edges`` is given)."""
+    r, v, dv = (np.array(a, dtype=np.float64).reshape(-1, 3) for a in (r, v, dv))
+    n = len(v)
+    photon = np.asarray(photon, dtype=bool).reshape(-1)
+    edges = [np.asarray(e, dtype=np.float64) for e in edges]
+    shape = tuple(len(e) - 1 for e in edges) + (() if E_edges is None else (len(E_edges) - 1,))
+    p = np.asarray(p, dtype=np.float64).reshape(-1)
+    cell = np.full(n, -1, dtype=np.int64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        at = np.flatnonzero(~_at_rest(v) & photon)
+        ok, g = _cell_of_positions(r[at], axes, edges, np.asarray(center, dtype=np.float64))
+        at, g = at[ok], g[ok]
+        if E_edges is not None:                                # NaN and under/overflow: in no band
+            Ee = np.asarray(E_edges, dtype=np.float64)
+            band = _bin_of(np.asarray(E, dtype=np.float64).reshape(-1)[at], Ee)
+            at, g = at[band >= 0], g[band >= 0] * (len(Ee) - 1) + band[band >= 0]
+    cell[at] = g
+    exposed = cell >= 0
+    draws = at[p[g] > 0.0]                                     # a cell with p == 0 draws nothing
+    u = _philox_block(np.asarray(ids).reshape(-1)[draws], seed, n_pass, _GRID_SCATTER_WORDS[0])[0]
+    hit = draws[u < p[cell[draws]]]
+    u_a, u_b = _philox_block(np.asarray(ids).reshape(-1)[hit], seed, n_pass, _GRID_SCATTER_WORDS[1])
+    with np.errstate(invalid="ignore", over="ignore"):
+        v_new = np.float64(c) * _turn_about(np.tile([1.0, 0.0, 0.0], (len(hit), 1)), 1.0 - 2.0 * u_a, u_b)     # uniform on the sphere
+        dv[hit] = _stored(v_new - v[hit], dtype)               # the scatter step's mark, from the old velocity
+    v[hit] = _stored(v_new, dtype)
+    scattered = np.zeros(n, dtype=bool)
+    scattered[hit] = True
+    written = scattered | (photon & bool(first))
+    dv[written & ~scattered] = 0.0                             # first: "did not scatter in this pass"
+    cells = np.bincount(cell[hit], minlength=p.size).astype(np.int64).reshape(shape)
+    return {"v": v, "dv": dv, "exposed": exposed, "scattered": scattered, "written": written, "cell": cell, "scattered_by_cell": cells}
+
+
+class GridScatterStep(LayeredScatterStep):
+    """Who scatters, by cell of a 3-D grid and energy band (not in the reference): ``LayeredScatterStep`` with
+    ``PositionGridMeasureStep``'s cells in place of the concentric layers -- a cloud of finite width, a broken cloud field, a plume
+    or a fog bank over half of the scene, a cloud that shades the ground beside it.  It stands where a ``LayeredScatterStep`` stands:
+    BEHIND the Newton step of a pass -- alone, or behind other scatterers -- and in front of the phase, absorption and ground steps.
+
+    * ``axes``, ``edges``, ``center``: ``PositionGridMeasureStep``'s arguments by its rules, limits and error messages: one to three
+      distinct names out of ``"x"``, ``"y"``, ``"z"``, ``"r"``, one sequence of bin edges per axis (at most 1024 bins per axis).  The
+      cell of a photon is the cell that step would count it in: bins ``[e_b, e_b+1)``, the last one closed; an ``"r"`` axis compares
+      ``q = ((x-cx)*(x-cx) + (y-cy)*(y-cy)) + (z-cz)*(z-cz)`` in float64 with the squared edges, no square root is taken; a NaN or a
+      position outside any axis's range is in no cell; cells are row-major in the order of ``axes``.
+    * ``E_edges``: ``LayeredScatterStep``'s argument by its rule: ``B + 1`` energy edges, ``numpy.histogram``'s bins, at most 1024
+      bands.  Without it E is neither read nor asked for, so a wavelength-dependent scatter step keeps its term cache.
+    * ``k``: the scattering coefficient per unit length (code units), finite and not negative: one number, or an array of the grid's
+      shape (without ``E_edges``) or the grid's shape ``+ (B,)`` (with them).  At most ``2**20`` cells (grid cells times bands).
+    * ``first``: ``LayeredScatterStep``'s argument with the same meaning: True -- every photon this step does not scatter gets
+      ``dv = 0``; False -- a photon that is not scattered is not written at all, so an earlier scatterer's mark survives (refused
+      under ``cl_on=False``); None (the default) is decided at the step's first run: False iff a ``ScatterIsotropicStep``, a
+      ``ScatterSphericalStep``, a ``LayeredScatterStep`` or another ``GridScatterStep`` stands earlier in the pass.  A
+      ``ScatterIsotropicStep`` BEHIND this step would wipe its marks: the first run raises ``ValueError``.
+
+    Per pass the host makes ``p = -numpy.expm1(-k * (c * dt))`` from the simulation's current ``dt`` (``_path_probability``), and the
+    device only ever sees ``p``.  Every moving photon with a cell (and a band, with ``E_edges``) is EXPOSED (a photon at rest --
+    ``-0.0`` counts as 0, a NaN moves --, a plain ``Object`` and a photon in no cell or no band are skipped); it scatters iff
+    ``u < p`` (``p == 0`` draws nothing), ``u`` from a Philox block keyed by ``sim.seed``, the photon's id and the step's pass counter
+    ``_n_pass``, in counter words no other kernel uses (25, and 26 for the direction).  Several ``GridScatterStep``s in one pass count
+    on through one another (``tally.WriterStep``).  A hit gets a direction uniform on the sphere at speed c and the scatter step's
+    mark, ``v = v'``, ``dv = v' - v_old`` -- ``LayeredScatterStep``'s arithmetic line for line, so a ``PhaseFunctionStep`` or
+    ``LayeredPhaseStep`` behind this step re-directs its hits about ``v - dv`` and an ``AbsorptionStep`` gives them an ``omega0``; those
+    steps still act by radial layer, not by cell.  ``r``, ``dr``, ``E``, ids and kinds are never written.
+
+    After each run ``self.exposed`` and ``self.scattered`` hold the pass's counts and ``self.scattered_by_cell`` an int64 array of
+    ``k``'s broadcast shape, global over shards and ranks; ``self.data`` gains the row ``[t, exposed, scattered,
+    scattered_by_cell]``; ``out_fn`` takes the rows at the end.  The rule is written out in include/physicl_hip.h
+    (pcl_step_scatter_grid); ``_scatter_grid`` restates it with numpy.
+
+    Cost: up to 4096 cells the table and the tallies live in LDS; above that the kernel reads ``p`` from device memory and adds its
+    hits there.  Either way the table goes up over the host link and the tallies come back every pass -- 8 MB each way at ``2**20``
+    cells -- and a sharded run all-reduces the tallies in pieces of ``tally.ALLREDUCE_CHUNK``; nothing is cached between passes.
+
+    One launch per light step: the K-passes-per-launch kernels cannot scatter a photon by a table between two of their passes, and
+    ``sim.launch_note`` says so.  On host-resident objects (``step.run(sim)`` outside a device loop) the same state is made with
+    numpy, the ids being the places in the object list.
+
+    The class derives from ``LayeredScatterStep`` for what is the same -- the ``first`` rule and its refusals, ``p`` per pass, the row --
+    and is a writer family of its own (``tally.writer_family``): its draws have words of their own, so its pass counter does not
+    interleave with a ``LayeredScatterStep``'s."""
+    _OWN_WORDS = True                                    # (tally.writer_family: not the parent's counter words)
+    _NOTE = "one launch per light step: a GridScatterStep scatters moving photons by grid cell and band behind every pass, which " \
+            "the K-passes-per-launch kernels cannot carry"
+
+    def __init__(self, k, axes, edges, center=(0, 0, 0), E_edges=None, first=None, out_fn=None):
+        MeasureStep.__init__(self, out_fn)
+        self.k, self.axes, self.edges, self.center, self.E_edges = _check_grid_scatter(k, axes, edges, center, E_edges)
+        if first is not None and not isinstance(first, (bool, np.bool_)):
+            raise ValueError("first must be None, True or False, got %r" % (first,))
+        self.first = None if first is None else bool(first)
+        self.exposed = self.scattered = 0
+        self.scattered_by_cell = np.zeros(self.k.shape, dtype=np.int64)
+        self._pass = 0                                   # runs so far; the sweep is handed _n_pass (tally.WriterStep)
+
+    def _sweep(self, sim, p):
+        exposed, scattered, cells = sim._dev.scatter_grid(p, self.axes, self.edges, self.center, self.E_edges, self.first,
+                                                          _c_h_literals()[0], sim.seed, self._n_pass)
+        return [np.array([exposed, scattered], dtype=np.int64), np.asarray(cells, dtype=np.int64)]
+
+    def _host_sweep(self, objs, ids, seed, p):
+        E, photon = tally.photon_energies(objs, PhotonObject)
+        new = _scatter_grid(tally.vec3(objs, "r"), tally.vec3(objs, "v"), tally.vec3(objs, "dv"), E, photon, ids, p, self.axes, self.edges,
+                            self.center, self.E_edges, self.first, _c_h_literals()[0], seed, self._n_pass)
+        return new, new["written"], (new["exposed"].sum(), new["scattered"].sum(), new["scattered_by_cell"])
 
 
 # ---------------------------------------------------------------------------------------------- re-emission in place

@@ -315,6 +315,9 @@ class MultiDevice:
     def scatter_layered(self, *a, **kw):
         return self._sum_parts("scatter_layered", *a, **kw)
 
+    def scatter_grid(self, *a, **kw):
+        return self._sum_parts("scatter_grid", *a, **kw)
+
     def plane_energies(self, plane, n_hint=None):
         return self._concat(self._each(lambda s: s.plane_energies(plane)))      # (a shard does not know its share of the hint)
 

@@ -101,12 +101,15 @@ N_PASS_MAX = 0xFFFFFFFF      # n_pass is one 32-bit counter word
 
 def writer_family(step):
     """What the steps that share ``step``'s counter words have in common: a row of ``WRITER_FAMILIES``, or the writer class itself
-    (the class right below ``WriterStep``: a subclass of a step draws from its words)."""
+    (the class right below ``WriterStep``: a subclass of a step draws from its words -- unless it says that it has words of its own,
+    ``_OWN_WORDS = True`` in the class's own body: then it, and what derives from it, is a family of its own)."""
     line = [c for c in type(step).__mro__ if issubclass(c, WriterStep) and c is not WriterStep]
     for c in line:
         for family in WRITER_FAMILIES:
             if c.__name__ in family:
                 return family
+        if vars(c).get("_OWN_WORDS"):
+            return c
     return line[-1]
 
 
