@@ -4,7 +4,7 @@ examples (n(r) = 2.5e25 m^-3 * exp(-(|r| - 6371 km) / 8.6 km)) with photons that
 
     python examples/point_source_atmosphere.py [n_photons] [passes] [--cone | --beam-down | --default] [--profile] [--shells]
                                                [--ground [ALBEDO]] [--phase rayleigh | hg:G | isotropic] [--omega0 W | W1,W2,...]
-                                               [--cloud LO,HI[,G]] [--cloud-tau TAU] [--cloud-field NX,NY,NZ:EXTENT:TAU] [--recycle [TOP]] [--gas LO,HI,K[,EMIN,EMAX]] [--blue-sky]
+                                               [--cloud LO,HI[,G]] [--cloud-tau TAU] [--cloud-field NX,NY,NZ:EXTENT:TAU] [--box periodic | mirror | open] [--recycle [TOP]] [--gas LO,HI,K[,EMIN,EMAX]] [--blue-sky]
                                                [--reemit [TG[,TA]]] [--ocean N] [--ground-bands E1,E2,...:a1,a2,...[:s1,...]]
                                                [--camera X,Y,Z:NX,NY,NZ:RADIUS:FOV_DEG:PIXELS]
 
@@ -45,6 +45,12 @@ NZ-index add up to an even number -- a vertical path through a cloudy column has
 stands behind the clear air's scatter step (``first`` resolves to False) and in front of the phase step.  ``exposed``, ``scattered`` and
 the column sums of ``scattered_by_cell`` over the passes are printed; with ``--camera`` looking down from above the box, e.g.
 ``--cloud-field 8,8,8:40000:4 --camera 6421000,0,0:-1,0,0:20000:60:32``, the image shows the gaps.  One launch per light step.
+``--box periodic | mirror | open`` (with ``--cloud-field``) gives the scene sides: a BoxBoundaryStep around the cloud field's box on its
+two horizontal axes y and z (x, the vertical, has no wall), last in the pass, behind the ground and in front of a re-emission or the
+recycling lamp.  ``periodic`` hands a photon that leaves the field sideways back in on the other side -- the boundary condition
+domain-averaged fluxes of a cloud field need --, ``mirror`` folds it back at the wall, ``open`` parks it at rest (``--recycle`` then gives
+its slot back to the source).  ``moving`` and ``crossed`` of the first and the last pass and their sums are printed, and the number of
+photons inside the box's horizontal extent pass by pass: constant with ``periodic`` and ``mirror``.  One launch per light step.
 ``--recycle [TOP]`` (an altitude in metres, default 100 km) makes the source a continuous one: a RecycleStep at the end of every pass
 gives the slots of the photons at rest (absorbed by the ground or the medium) and of those above TOP back to the source.  The
 population stays constant; the emission rate (photons recycled per pass) and the counts at rest and through the top are printed as
@@ -151,6 +157,12 @@ if "--cloud-field" in argv:
             raise ValueError
     except ValueError:
         sys.exit("--cloud-field NX,NY,NZ:EXTENT:TAU: the cells of the box, its width in metres and the optical thickness of a cloudy column")
+box = None
+if "--box" in argv:
+    at = argv.index("--box")
+    box = argv.pop(at + 1) if at + 1 < len(argv) else ""
+    if box not in ("periodic", "mirror", "open") or cloud_field is None:
+        sys.exit("--box periodic | mirror | open: the walls around the box of --cloud-field NX,NY,NZ:EXTENT:TAU")
 recycle_top = None
 if "--recycle" in argv:
     at = argv.index("--recycle")
@@ -294,6 +306,13 @@ def run(ground):
     if ocean is not None:                                      # behind the sea floor, before the lamp: where a ground would stand
         sea = light.RefractiveSurfaceStep(R, ocean)
         sim.add_step("ocean", sea)
+    walls = inside = None
+    if box is not None:                                        # last in the pass: behind the ground and the interface, before re-emission and the lamp
+        half = 0.5 * cloud_field[1]
+        walls = light.BoxBoundaryStep((0.0, -half, -half), (0.0, half, half), walls=(None, box, box))
+        sim.add_step("box", walls)
+        inside = light.PositionGridMeasureStep(None, ("y", "z"), [[-half, half], [-half, half]])       # behind it: who stands between the walls
+        sim.add_step("inside", inside)
     if reemit is not None:                                     # behind everything that parks photons, before the lamp
         # the ground parks photons on the sphere up to rounding: a thin shell of its own, wide enough for an fp32 store
         glow = light.ReemissionStep(infrared, edges=[R * (1.0 - 1e-6), R * (1.0 + 1e-6), R + 100e3], angular=["lambertian", "isotropic"])
@@ -308,7 +327,7 @@ def run(ground):
     sim.join()
     if sim.error is not None:
         raise sim.error
-    return sim, signs, shells, profile, image, tally, floor, angles, medium, lamp, vapour, eye, glow, sea, droplets, broken
+    return sim, signs, shells, profile, image, tally, floor, angles, medium, lamp, vapour, eye, glow, sea, droplets, broken, walls, inside
 
 
 bare_top = None
@@ -318,7 +337,7 @@ if ground is not None and "--shells" in sys.argv:              # the same run wi
     print("without the ground: %d photons x %d steps in %.2f s" % (n, len(bare[0].ts), bare[0].run_time))
     bare[0].close(download=False)
     del bare
-sim, signs, shells, profile, image, tally, floor, angles, medium, lamp, vapour, eye, glow, sea, droplets, broken = run(ground)
+sim, signs, shells, profile, image, tally, floor, angles, medium, lamp, vapour, eye, glow, sea, droplets, broken, walls, inside = run(ground)
 steps = len(sim.ts)
 print("source:", source)
 print("%d photons x %d steps in %.2f s  ->  %.3g particle-steps/s" % (n, steps, sim.run_time, n * steps / sim.run_time))
@@ -347,6 +366,15 @@ if broken is not None:
     print("  scattered by column (summed over x, rows: y, columns: z):")
     for line in by_cell.sum(axis=0):
         print("   " + " ".join("%8d" % x for x in line))
+if walls is not None:
+    crossed = np.sum([row[3] for row in walls.data], axis=0)
+    print("box walls (%s in y and z, %g km apart): moving %d in the first pass and %d in the last; crossed [[x], [y below, above], [z below, above]] %s "
+          "in the last pass, %s over %d passes; multi %d" % (box, cloud_field[1] / 1e3, int(walls.data[0][1]), int(walls.data[-1][1]),
+                                                           np.asarray(walls.data[-1][3]).tolist(), crossed.tolist(), len(walls.data),
+                                                           sum(int(row[2]) for row in walls.data)))
+    count = [int(np.asarray(row[2]).sum()) for row in inside.data]
+    print("  photons between the walls behind the step: %d in the first pass, %d at the least, %d in the last (of %d)" % (
+        count[0], min(count), count[-1], int(inside.data[-1][1])))
 if profile is not None and profile.data:
     t, N, shells_now = profile.data[-1]
     print("altitude profile at t = %g s (%d records, one every 32 passes): %d of %d photons between 0 and 200 km" % (float(t), len(profile.data), shells_now.sum(), N))

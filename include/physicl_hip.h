@@ -1208,6 +1208,54 @@ int pcl_step_scatter_grid(pcl_ctx *ctx, int n_axes, const int *coords_host, cons
                           uint64_t seed, uint32_t pass, int64_t *counts_out_host /* [2]: exposed, scattered */,
                           int64_t *cells_out_host /* [G * B'] */);
 
+/* Box walls (BoxBoundaryStep): the sides of the scene.  Per axis x, y, z the box [lo, hi] has a wall of one kind or none: a
+ * PERIODIC wall hands a photon that has left through one side back in through the other (the horizontal boundary condition of a
+ * cloud field), a MIRROR wall folds its whole move back at the wall, an OPEN wall ends its life: it is parked at rest as
+ * pcl_step_absorb_path parks, for pcl_step_recycle_spent (at_rest) to hand its slot back to a source.  Called last in a pass, behind a
+ * ground or an interface.  ONE deterministic sweep of the resident store: nothing is drawn, no id is read, nothing is removed; E, ids
+ * and kinds are never written and E and ids never read.  All arithmetic is fp64, unfused, every operation rounded once, in the order
+ * written; an fp32 store's values are widened first (exact) and what is written is rounded once to the store's dtype (a negation is
+ * exact).  The operations are add, subtract, multiply, divide, floor, min, max and compares, so numpy restates every bit; min and max
+ * are C's fmin and fmax (of a NaN and a number: the number).  L_a = hi_a - lo_a, made once on the host.
+ *   a particle that is not a photon (kind 0) is skipped and never written.
+ *   moving    iff  not (v0 == 0 and v1 == 0 and v2 == 0)         (-0.0 counts as 0; a NaN in v: moving), the siblings' test;
+ *                  a photon at rest is not read further and not written.  moving is counted in counts_out_host[0].
+ *   per axis a with a wall, x = r_a:   x not finite (NaN, +-inf): the axis is skipped.   below = x < lo.
+ *                  above = x >= hi (PCL_WALL_PERIODIC: the box is [lo, hi)),  above = x > hi (PCL_WALL_MIRROR, PCL_WALL_OPEN: on the
+ *                  wall is inside).   outside on a = below or above;  side = 0 if below, 1 if above.
+ *   open first:    outside on some PCL_WALL_OPEN axis:  v_k = 0 and dv_k = 0 for k = 0, 1, 2;  r and dr are left alone;
+ *                  crossed[a][side] += 1 for the FIRST such axis a in the order x, y, z, and for no other axis, whatever its kind;
+ *                  nothing else is done to the photon and it is not counted in multi.  It is at rest: no later call counts it.
+ *   otherwise, per PCL_WALL_PERIODIC or PCL_WALL_MIRROR axis a the photon is outside on, each by itself:
+ *                  s = x - lo;   n = floor(s / L);   f = min(max(s - n*L, 0), L);   crossed[a][side] += 1, whatever n is
+ *     periodic:    y = lo + f;   if not (y < hi): y = lo;   r_a = y.   dr, v and dv are not touched: r - dr is the image of where
+ *                  the photon came from.  y is in [lo, hi).
+ *     mirror:      h = n * 0.5;   odd = floor(h) != h;   y = odd ? hi - f : lo + f;   y = min(max(y, lo), hi);   r_a = y;
+ *                  if odd:  v_a = -v_a,  dv_a = -dv_a,  dr_a = -dr_a.   The image of the whole move under the reflections, exact for
+ *                  any number of bounces; |v| does not change.  y is in [lo, hi].
+ *   multi:         a photon that is not parked with n < -1 or n > 1 on some axis it is outside on is counted once in
+ *                  counts_out_host[1]: c*dt is too large for the box (pcl_step_refract_surface's overshot).  It changes nothing.
+ *   a photon that is outside on no axis is not written at all.
+ * modes_host: three of PCL_WALL_NONE, PCL_WALL_PERIODIC, PCL_WALL_MIRROR, PCL_WALL_OPEN, for x, y, z; lo_host, hi_host: three
+ * doubles each, read for the axes with a wall only.  counts_out_host: moving, multi, crossed[3][2] (axis-major: [2 + 2*a + side]), by
+ * this call.  Rows the call asks the store for (pcl_store_field_ptr, which is the whole store protocol): the three v rows; the r row
+ * of every axis with a wall; dr of a mirror axis; dv of a mirror axis, and all three dv rows if some axis is open.  With three
+ * periodic walls and nobody outside the sweep reads 48 B a slot in fp64.  A store that is not uniform costs the kinds' host traffic,
+ * as for pcl_step_surface_reflect; ids never travel.
+ * The call takes no seed, no pass and no c: it draws nothing, so the Philox counter words stay as they are (0-5 and 8-26 are taken,
+ * see pcl_step_scatter_grid).
+ * PCL_ERR_ARG (a NULL pointer, an unknown mode, all three modes PCL_WALL_NONE, and on an axis with a wall: lo, hi or hi - lo not
+ * finite, or hi - lo <= 0) is returned before the store is looked at -- by the group's entry point before the group is --, and nothing
+ * is launched or written; PCL_ERR_STATE without a store; an empty store answers zeros without a launch.  Host pointers; one device
+ * allocation per call, handed back on every way out; synchronises once, with the copy of the counts.  pcl_last_error() is generic,
+ * as for pcl_step_surface_reflect, whose source file these two entry points share. */
+#define PCL_WALL_NONE 0
+#define PCL_WALL_PERIODIC 1
+#define PCL_WALL_MIRROR 2
+#define PCL_WALL_OPEN 3
+int pcl_step_box_walls(pcl_ctx *ctx, const int *modes_host /* [3] */, const double *lo_host /* [3] */, const double *hi_host /* [3] */,
+                       int64_t *counts_out_host /* [8]: moving, multi, crossed[3][2] */);
+
 /* ---- Device groups: several GPUs from ONE process ---------------------------------------------------------------
  * The reference is a single process with one simulation thread (physicl/__init__.py:400-432, 501-524); this is how
  * a host written against this ABI uses a node's GPUs the same way, without one process per GPU.  A group owns one
@@ -1328,6 +1376,10 @@ int pcl_group_step_scatter_layered(pcl_group *group, int n_layers, int n_E_bins,
 int pcl_group_step_scatter_grid(pcl_group *group, int n_axes, const int *coords_host, const int *n_bins_host, const double *edges_host,
                                 const double *center_host, int n_E_bins, const double *E_edges_host, const double *p_host, int first,
                                 double c, uint64_t seed, uint32_t pass, int64_t *counts_out_host, int64_t *cells_out_host);
+/* pcl_step_box_walls on every shard (side by side), the eight counts summed over the group's devices; the arguments are checked once
+ * for the group, before the group is looked at (the rule reads no id: a photon meets the same wall however the run is sharded) */
+int pcl_group_step_box_walls(pcl_group *group, const int *modes_host, const double *lo_host, const double *hi_host,
+                             int64_t *counts_out_host);
 
 /* ---------------------------------------------------------------- the counters' collective (one process per GPU)
  * The path shards by global index with no data-path exchange; the only global quantities are the int64

@@ -39,6 +39,7 @@ REEMIT_MAX_LAYERS, REEMIT_MAX_BINS, REEMIT_MAX_TOTAL_BINS = 64, 1024, 2048      
 SPECTRAL_MAX_BANDS = 1024                                                    # PCL_SPECTRAL_MAX_BANDS: bands of a SpectralSurfaceStep
 SCATTER_LAYERED_MAX_LAYERS, SCATTER_LAYERED_MAX_BANDS, SCATTER_LAYERED_MAX_CELLS = 64, 1024, 4096       # PCL_SCATTER_LAYERED_MAX_LAYERS ...
 SCATTER_GRID_MAX_BANDS, SCATTER_GRID_MAX_CELLS = 1024, 1 << 20                # PCL_SCATTER_GRID_MAX_BANDS, PCL_SCATTER_GRID_MAX_CELLS
+WALL_MODES = {None: 0, "periodic": 1, "mirror": 2, "open": 3}               # PCL_WALL_NONE, PCL_WALL_PERIODIC, PCL_WALL_MIRROR, PCL_WALL_OPEN
 REEMIT_LAWS = {"isotropic": 0, "lambertian": 1}                              # the flags of pcl_step_reemit_parked's lambertian_host
 PROF_NEWTON, PROF_SCATTER, PROF_DELETE_MASK, PROF_COMPACT, PROF_COUNTERS, PROF_FUSED, PROF_MULTI, PROF_ONEPASS, \
     PROF_DELETE_AHEAD = range(9)
@@ -173,6 +174,7 @@ _PROTOTYPES = {
     "pcl_step_ground_spectral": [_vp, c_double, _vp, c_int, _vp, _vp, _vp, c_double, c_uint64, c_uint32, _vp, _vp],
     "pcl_step_scatter_layered": [_vp, c_int, c_int, _vp, _vp, _vp, _vp, c_int, c_double, c_uint64, c_uint32, _vp, _vp],
     "pcl_step_scatter_grid": [_vp, c_int, _vp, _vp, _vp, _vp, c_int, _vp, _vp, c_int, c_double, c_uint64, c_uint32, _vp, _vp],
+    "pcl_step_box_walls": [_vp, _vp, _vp, _vp, _vp],
     # device groups: several GPUs from one process (the C-level counterpart of physicl_amd.multidev.MultiDevice)
     "pcl_group_create": [c_int, POINTER(c_int), POINTER(_vp)],
     "pcl_group_destroy": [_vp],
@@ -211,6 +213,7 @@ _PROTOTYPES = {
     "pcl_group_step_ground_spectral": [_vp, c_double, _vp, c_int, _vp, _vp, _vp, c_double, c_uint64, c_uint32, _vp, _vp],
     "pcl_group_step_scatter_layered": [_vp, c_int, c_int, _vp, _vp, _vp, _vp, c_int, c_double, c_uint64, c_uint32, _vp, _vp],
     "pcl_group_step_scatter_grid": [_vp, c_int, _vp, _vp, _vp, _vp, c_int, _vp, _vp, c_int, c_double, c_uint64, c_uint32, _vp, _vp],
+    "pcl_group_step_box_walls": [_vp, _vp, _vp, _vp, _vp],
 }
 EXPORTS = sorted(list(_PROTOTYPES) + ["pcl_last_error"])
 
@@ -615,6 +618,18 @@ def _scatter_grid(entry, handle, p, axes, edges, center, E_edges, first, c, seed
     check(entry(handle, len(coords), coords.ctypes.data, n_bins.ctypes.data, ed.ctypes.data, ptr(ce), B, ptr(Ee), pr.ctypes.data,
                 int(bool(first)), float(c), int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_pass) & 0xFFFFFFFF, counts.ctypes.data, cells.ctypes.data))
     return int(counts[0]), int(counts[1]), cells
+
+
+def _box_walls(entry, handle, modes, lo, hi):
+    """One call of pcl_step_box_walls / pcl_group_step_box_walls: int64[8] -- moving, multi, crossed[3][2] (axis-major: below, above) --
+    of this call.  ``modes``: three of ``WALL_MODES``' keys or values, for x, y, z; ``lo``, ``hi``: three numbers each (those of an axis
+    without a wall are not read)."""
+    md = np.array([WALL_MODES.get(m, m) if m is None or isinstance(m, str) else m for m in modes], dtype=np.int32).reshape(3)
+    lo = np.ascontiguousarray(lo, dtype=np.float64).reshape(3)
+    hi = np.ascontiguousarray(hi, dtype=np.float64).reshape(3)
+    counts = np.zeros(8, dtype=np.int64)
+    check(entry(handle, md.ctypes.data, lo.ctypes.data, hi.ctypes.data, counts.ctypes.data))
+    return counts
 
 
 def _scatter(sc, required=False, lazy=False, empty_expr=b""):
@@ -1257,6 +1272,13 @@ class Device:
         ``(exposed, scattered, scattered_by_cell int64 of the grid's shape (+ bands))``.  ``n_pass``: the caller's own pass counter."""
         return _scatter_grid(self.lib.pcl_step_scatter_grid, self.ctx, p, axes, edges, center, E_edges, first, c, seed, n_pass)
 
+    def box_walls(self, modes, lo, hi):
+        """The walls of the box ``[lo, hi]``, per axis ``"periodic"``, ``"mirror"``, ``"open"`` or None: every moving photon outside on
+        an axis with a wall is handed back in through the other side, folded back at the wall (an odd number of bounces turns ``v``,
+        ``dv`` and ``dr`` of the axis round) or, through an open wall, parked at rest -- one deterministic sweep (pcl_step_box_walls).
+        int64[8]: moving, multi, crossed[3][2].  light._box_walls restates the sweep with numpy, bit for bit."""
+        return _box_walls(self.lib.pcl_step_box_walls, self.ctx, modes, lo, hi)
+
 
 class DeviceGroup:
     """``pcl_group_*``: several contexts in one process, sharded by global index, behind the C ABI (the shim owns the
@@ -1404,6 +1426,10 @@ class DeviceGroup:
     def scatter_grid(self, p, axes, edges, center=None, E_edges=None, first=True, c=0.0, seed=0, n_pass=0):
         """``Device.scatter_grid`` on every context of the group, the tallies summed (pcl_group_step_scatter_grid)."""
         return _scatter_grid(self.lib.pcl_group_step_scatter_grid, self.g, p, axes, edges, center, E_edges, first, c, seed, n_pass)
+
+    def box_walls(self, modes, lo, hi):
+        """``Device.box_walls`` on every context of the group, the counts summed (pcl_group_step_box_walls)."""
+        return _box_walls(self.lib.pcl_group_step_box_walls, self.g, modes, lo, hi)
 
     def download(self, field, n=None, offset=0, dtype=None):
         n = self.count - offset if n is None else n

@@ -122,6 +122,20 @@ def volume_sweeps_of(unit):
     return all_sweeps_of(unit) + VOLUME_SWEEPS.get(os.path.basename(unit["src"]), ())
 
 
+# The walls of a box, in the same form (tests/test_writer_walls_cpu.py holds it to it): the sides of the scene stand beside the ground and
+# the interface, whose rows (r, dr, v, dv) the sweep writes; it parks what leaves through an open wall as path absorption parks.  None of
+# the functions above folds this table in -- the tests of the older sweeps hold all five to their contents --; boundary_sweeps_of() is
+# every sweep a unit holds.
+BOUNDARY_SWEEPS = {
+    "pcl_surface.hip": (_sweep("pcl_step_box_walls", "pcl_group_step_box_walls", "k_box_walls"),),
+}
+
+
+def boundary_sweeps_of(unit):
+    """Every sweep a unit of ADDONS holds, in the file's order: volume_sweeps_of(unit), then what BOUNDARY_SWEEPS adds."""
+    return volume_sweeps_of(unit) + BOUNDARY_SWEEPS.get(os.path.basename(unit["src"]), ())
+
+
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -ffp-contract=off: the reference's kernels must be evaluated unfused (bit-exact parity, DESIGN.md)
 # -disable-machine-licm: the pre-RA pass hoists every scalar constant out of the kernels' long loops, the scalar register file

@@ -215,6 +215,21 @@
 //   moving: k_scatter_layered's line;  cell: k_position_grid's lines, then the band as in k_absorb_path;  p = P[cell][e];
 //   p > 0: u = u53(w0, w1) of counter (id_lo, id_hi, pass, 25);  scattered iff u < p:  (u_a, u_b) of counter (id_lo, id_hi, pass, 26);
 //   the direction, v and dv: k_scatter_layered's lines;   first and a photon that is not scattered:  dv_k = 0
+//
+// Box walls (BoxBoundaryStep): the sides of the scene -- per axis a periodic, a mirror or an open wall, or none.  Deterministic: no
+// draw, no id, no table.
+//
+//   k_box_walls<T>         one grid-stride sweep in k_absorb_path's shape: v decides a moving lane, which loads the r rows of the axes
+//                          with a wall and is classified per axis (below / above / inside; a NaN or an infinity: skipped).  A lane
+//                          outside on an open axis is parked (v = dv = 0); any other lane that is outside folds each such axis with one
+//                          division and one floor.  The eight counts -- moving, multi, crossed[3][2] -- are wave ballots and popcounts
+//                          into LDS above the continue of the lanes without work (the six of crossed and multi only in a wave that has
+//                          such a lane), flushed once per workgroup.  A lane that crosses nothing writes nothing.
+//
+// Operation order (what light._box_walls restates with numpy):
+//   moving: k_absorb_path's line;  below = x < lo;  above = x >= hi (periodic), x > hi (mirror, open);  open: park, first open axis counted;
+//   s = x - lo;  n = floor(s / L);  f = min(max(s - n*L, 0), L);  periodic: y = lo + f, not (y < hi): y = lo;
+//   mirror: h = n*0.5;  odd = floor(h) != h;  y = min(max(odd ? hi - f : lo + f, lo), hi);  odd: v_a, dv_a, dr_a negated
 #include "pcl_sweep.h"
 
 #include "pcl_device.h" // (after the HIP runtime and the ABI's header, which pcl_sweep.h brings)
@@ -2401,6 +2416,188 @@ int group_scatter_grid(pcl_group *group, int n_axes, const int *coords_host, con
     });
 }
 
+// ---- box walls: the kernel stands with its host side, at the end of the unit, as the scattering on a grid does
+template <typename T>
+struct walls_args {
+    T *r[3];                     // the axes with a wall (NULL otherwise)
+    T *v[3];                     // always: who moves
+    T *dr[3];                    // the mirror axes (NULL otherwise)
+    T *dv[3];                    // the mirror axes, and all three with an open wall (NULL otherwise)
+    const unsigned char *kind;   // NULL: every particle is a photon
+    unsigned long long *out;     // [8]: moving, multi, crossed[3][2]; device, zeroed by the entry point
+    int64_t N, ts;               // particles, tile stride of the slab (elements)
+    int tile_log;                // log2 of the tile length
+    int mode[3];                 // PCL_WALL_* per axis
+    double lo[3], hi[3], L[3];   // L = hi - lo, made on the host, once
+};
+
+template <typename T>
+__global__ void __launch_bounds__(kBlock) k_box_walls(walls_args<T> a) {
+    __shared__ uint32_t s_cnt[8];                                       // moving, multi, crossed[3][2]
+    if (threadIdx.x < 8) s_cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int64_t stride = grid_stride(), n_round = whole_waves(a.N);   // (the ballots below need whole waves inside the loop)
+    for (int64_t i = first_slot(); i < n_round; i += stride) {
+        const bool in = i < a.N;
+        const int64_t ti = tile_index(i, a.tile_log, a.ts);
+        // moving: at_rest, written out as in k_absorb_path and negated -- -0.0 == 0, a NaN moves, v0 != 0 loads no more of v
+        bool go = in && !((double)a.v[0][ti] == 0.0 && (double)a.v[1][ti] == 0.0 && (double)a.v[2][ti] == 0.0);
+        if (go && a.kind) go = a.kind[i] != 0;                          // plain Objects are never touched
+        int side[3] = {-1, -1, -1};                                     // 0 below, 1 above; -1: inside, no wall, or not finite
+        double x[3] = {0.0, 0.0, 0.0};
+        bool park = false;
+        if (go) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                if (a.mode[k] != PCL_WALL_NONE) {
+                    x[k] = (double)a.r[k][ti];                          // fp32 widens exactly
+                    const bool below = x[k] < a.lo[k];
+                    const bool above = a.mode[k] == PCL_WALL_PERIODIC ? x[k] >= a.hi[k] : x[k] > a.hi[k];   // (mirror, open: on the wall is inside)
+                    if ((below || above) && x[k] > -INFINITY && x[k] < INFINITY) side[k] = below ? 0 : 1;   // NaN, +-inf: skipped
+                    park = park || (side[k] >= 0 && a.mode[k] == PCL_WALL_OPEN);
+                }
+        }
+        // the cell each axis counts in: with an open wall crossed only the first such axis, otherwise every axis that is outside
+        int cell[3];
+        bool seen = false;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const bool open_k = side[k] >= 0 && a.mode[k] == PCL_WALL_OPEN;
+            cell[k] = park ? (open_k && !seen ? side[k] : -1) : side[k];
+            seen = seen || open_k;
+        }
+        const bool fold = !park && (side[0] >= 0 || side[1] >= 0 || side[2] >= 0);
+        double n[3] = {0.0, 0.0, 0.0}, f[3] = {0.0, 0.0, 0.0};
+        bool multi = false;
+        if (fold) {             // (no ballot inside: the lanes meet again behind this block)
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                if (side[k] >= 0) {
+                    const double s = __dsub_rn(x[k], a.lo[k]);
+                    n[k] = floor(__ddiv_rn(s, a.L[k]));
+                    f[k] = fmin(fmax(__dsub_rn(s, __dmul_rn(n[k], a.L[k])), 0.0), a.L[k]);
+                    multi = multi || n[k] < -1.0 || n[k] > 1.0;
+                }
+        }
+        const bool work = park || fold;
+        const uint32_t n_go = (uint32_t)__popcll(__ballot(go));
+        if (lane == 0 && n_go) atomicAdd(&s_cnt[0], n_go);
+        if (__ballot(work)) {   // (the same answer in every lane of the wave)
+            const uint32_t n_multi = (uint32_t)__popcll(__ballot(multi));
+            if (lane == 0 && n_multi) atomicAdd(&s_cnt[1], n_multi);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const uint32_t n_lo = (uint32_t)__popcll(__ballot(cell[k] == 0)), n_hi = (uint32_t)__popcll(__ballot(cell[k] == 1));
+                if (lane == 0 && n_lo) atomicAdd(&s_cnt[2 + 2 * k], n_lo);
+                if (lane == 0 && n_hi) atomicAdd(&s_cnt[3 + 2 * k], n_hi);
+            }
+        }
+        if (!work) continue;    // lanes that are left alone wait at the loop's head: no ballot below this line
+        if (park) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {                               // park, written out: at rest where it is; r and dr stay
+                a.v[k][ti] = (T)0.0;
+                a.dv[k][ti] = (T)0.0;
+            }
+            continue;
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            if (side[k] < 0) continue;
+            if (a.mode[k] == PCL_WALL_PERIODIC) {
+                double y = __dadd_rn(a.lo[k], f[k]);
+                if (!(y < a.hi[k])) y = a.lo[k];
+                a.r[k][ti] = (T)y;                                      // dr, v and dv stay: r - dr is the image of where it came from
+            } else {
+                const double h = __dmul_rn(n[k], 0.5);
+                const bool odd = floor(h) != h;
+                const double y = odd ? __dsub_rn(a.hi[k], f[k]) : __dadd_rn(a.lo[k], f[k]);
+                a.r[k][ti] = (T)fmin(fmax(y, a.lo[k]), a.hi[k]);
+                if (odd) {                                              // an odd number of bounces: the axis is turned round (a negation is exact)
+                    a.v[k][ti] = -a.v[k][ti];
+                    a.dv[k][ti] = -a.dv[k][ti];
+                    a.dr[k][ti] = -a.dr[k][ti];
+                }
+            }
+        }
+    }
+    __syncthreads();
+    // pcl_sweep::flush_cells, written out, for the reason given in k_absorb_scattered: a further caller changes the older kernels
+    for (int k = threadIdx.x; k < 8; k += kBlock)
+        if (s_cnt[k]) atomicAdd(&a.out[k], (unsigned long long)s_cnt[k]);
+}
+
+struct walls_spec { // a call's arguments, checked; L is made here, once
+    int mode[3] = {PCL_WALL_NONE, PCL_WALL_NONE, PCL_WALL_NONE};
+    double lo[3] = {0.0, 0.0, 0.0}, hi[3] = {0.0, 0.0, 0.0}, L[3] = {1.0, 1.0, 1.0};
+    bool open = false;          // some axis has an open wall: the three dv rows are written
+};
+
+// Everything PCL_ERR_ARG stands for except the NULL context; nothing is launched or written before this has passed.
+bool check_walls(const int *modes, const double *lo, const double *hi, const int64_t *counts_out, walls_spec &s) {
+    if (!modes || !lo || !hi || !counts_out) return false;
+    bool any = false;
+    for (int k = 0; k < 3; ++k)
+        if (modes[k] < PCL_WALL_NONE || modes[k] > PCL_WALL_OPEN) return false;
+    for (int k = 0; k < 3; ++k) {
+        s.mode[k] = modes[k];
+        if (modes[k] == PCL_WALL_NONE) continue;                        // the bounds of an axis without a wall are not read
+        const double L = hi[k] - lo[k];                                 // one rounding
+        if (!std::isfinite(lo[k]) || !std::isfinite(hi[k]) || !std::isfinite(L) || !(L > 0)) return false;
+        s.lo[k] = lo[k]; s.hi[k] = hi[k]; s.L[k] = L;
+        s.open = s.open || modes[k] == PCL_WALL_OPEN;
+        any = true;
+    }
+    return any;
+}
+
+template <typename T>
+int launch_walls(pcl_ctx *ctx, const store_view &v, const walls_spec &s, const staged &st) {
+    walls_args<T> a{};
+    for (int k = 0; k < 3; ++k) {
+        void *r = nullptr, *vel = nullptr, *dr = nullptr, *dv = nullptr;
+        const bool mirror = s.mode[k] == PCL_WALL_MIRROR;
+        PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_V0 + k, &vel));
+        if (s.mode[k] != PCL_WALL_NONE) PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_R0 + k, &r));
+        if (mirror) PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_DR0 + k, &dr));
+        if (mirror || s.open) PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_DV0 + k, &dv));
+        a.r[k] = static_cast<T *>(r); a.v[k] = static_cast<T *>(vel);
+        a.dr[k] = static_cast<T *>(dr); a.dv[k] = static_cast<T *>(dv);
+        a.mode[k] = s.mode[k]; a.lo[k] = s.lo[k]; a.hi[k] = s.hi[k]; a.L[k] = s.L[k];
+    }
+    a.kind = st.kind; a.out = st.out;
+    a.N = v.N; a.ts = v.ts; a.tile_log = v.tile_log;
+    const int64_t grid = balanced_grid(v.N, v.n_cu, resident_per_cu(8 * sizeof(uint32_t)));
+    hipLaunchKernelGGL(k_box_walls<T>, dim3((unsigned)grid), dim3(kBlock), 0, v.stream, a);
+    return hipGetLastError() == hipSuccess ? PCL_OK : PCL_ERR_HIP;
+}
+
+int box_walls(pcl_ctx *ctx, const int *modes_host, const double *lo_host, const double *hi_host, int64_t *counts_out_host) {
+    walls_spec s;
+    if (!ctx || !check_walls(modes_host, lo_host, hi_host, counts_out_host, s)) return bad_argument(ctx);
+    const spans out = {{counts_out_host, 8}};
+    store_view v;                                                       // E is never asked for, ids never travel
+    staged st(ctx);
+    PCL_SWEEP_TRY(open_store(ctx, PCL_V0, &v));
+    zero_spans(out);
+    if (v.N <= 0) return PCL_OK;
+    PCL_SWEEP_TRY(stage(st, v, 8, nullptr, 0, false));
+    PCL_SWEEP_TRY(PCL_SWEEP_LAUNCH(v, launch_walls, ctx, v, s, st));
+    return fetch(st, out);
+}
+
+int group_box_walls(pcl_group *group, const int *modes_host, const double *lo_host, const double *hi_host, int64_t *counts_out_host) {
+    walls_spec s;                                                       // the arguments first: a refused call looks at no group
+    if (!check_walls(modes_host, lo_host, hi_host, counts_out_host, s)) return bad_argument(nullptr);
+    std::vector<pcl_ctx *> ctx;
+    PCL_SWEEP_TRY(shards_of(group, ctx));
+    if (ctx.empty()) return bad_argument(nullptr);
+    return sum_shards(ctx, {{counts_out_host, 8}}, [&](pcl_ctx *one, int64_t *p) {
+        return pcl_step_box_walls(one, modes_host, lo_host, hi_host, p);
+    });
+}
+
 } // namespace
 
 extern "C" {
@@ -2577,6 +2774,15 @@ int pcl_group_step_scatter_grid(pcl_group *group, int n_axes, const int *coords_
         return group_scatter_grid(group, n_axes, coords_host, n_bins_host, edges_host, center_host, n_E_bins, E_edges_host, p_host, first,
                                   c, seed, pass, counts_out_host, cells_out_host);
     });
+}
+
+int pcl_step_box_walls(pcl_ctx *ctx, const int *modes_host, const double *lo_host, const double *hi_host, int64_t *counts_out_host) {
+    return guarded([&] { return box_walls(ctx, modes_host, lo_host, hi_host, counts_out_host); });
+}
+
+int pcl_group_step_box_walls(pcl_group *group, const int *modes_host, const double *lo_host, const double *hi_host,
+                             int64_t *counts_out_host) {
+    return guarded([&] { return group_box_walls(group, modes_host, lo_host, hi_host, counts_out_host); });
 }
 
 } // extern "C"

@@ -2507,6 +2507,178 @@ class GridScatterStep(LayeredScatterStep):
         return new, new["written"], (new["exposed"].sum(), new["scattered"].sum(), new["scattered_by_cell"])
 
 
+# ---------------------------------------------------------------------------------------------- the walls of a box
+_BOX_WALLS = ("periodic", "mirror", "open")
+
+
+def _check_box(lo, hi, walls):
+    """(lo, hi as 3 float64 each, the three walls -- ``"periodic"``, ``"mirror"``, ``"open"`` or None per axis) of a BoxBoundaryStep, or
+    ValueError for everything pcl_step_box_walls would refuse.  One wall stands for all three axes."""
+    if walls is None or isinstance(walls, str):
+        walls = (walls,) * 3
+    try:
+        walls = tuple(walls)
+    except TypeError:
+        raise ValueError("walls must be one of %s or None, or three of them (x, y, z)" % ", ".join(repr(w) for w in _BOX_WALLS)) from None
+    if len(walls) != 3 or any(w is not None and (not isinstance(w, str) or w not in _BOX_WALLS) for w in walls):
+        raise ValueError("walls must be one of %s or None, or three of them (x, y, z), got %r" % (", ".join(repr(w) for w in _BOX_WALLS), walls))
+    if all(w is None for w in walls):
+        raise ValueError("walls: a box needs a wall on one axis at least, got None for all three")
+    bounds = []
+    for name, x in (("lo", lo), ("hi", hi)):
+        try:
+            x = np.array(x, dtype=np.float64)                   # a Measurement is taken by its stored value, as center is
+        except (TypeError, ValueError):
+            raise ValueError("%s must be three numbers" % name) from None
+        if x.shape != (3,):
+            raise ValueError("%s must be three numbers, got %r" % (name, x))
+        bounds.append(np.ascontiguousarray(x))
+    lo, hi = bounds
+    for k, w in enumerate(walls):
+        if w is None:                                           # the bounds of an axis without a wall are ignored
+            continue
+        with np.errstate(over="ignore", invalid="ignore"):
+            L = hi[k] - lo[k]
+        if not (np.isfinite(lo[k]) and np.isfinite(hi[k]) and np.isfinite(L) and L > 0):
+            raise ValueError("axis %s: lo, hi and hi - lo must be finite and hi - lo > 0 on an axis with a wall, got lo = %r, hi = %r" % (
+                "xyz"[k], lo[k], hi[k]))
+    return lo, hi, walls
+
+
+def _box_walls(r, v, dr, dv, photon, modes, lo, hi, dtype=np.float64):
+    """What pcl_step_box_walls makes of (n, 3) float64 positions, velocities, last moves and last velocity changes and who is a photon,
+    with numpy -- every operation the device's operation in the device's order, one rounding each (include/physicl_hip.h), and what is
+    written rounded once to ``dtype``: the device's bit for bit, everywhere (add, subtract, multiply, divide, floor, fmin / fmax and
+    compares only).  ``modes``: per axis ``"periodic"``, ``"mirror"``, ``"open"`` or None.  A dict: ``r, v, dr, dv`` the new state
+    (float64 arrays; what is not written is the arguments'), the boolean masks ``moving``, ``parked``, ``folded`` (outside on an axis
+    and not parked), ``multi``, ``written`` (``parked | folded``) and ``outside`` ((n, 3): outside on the axis, whatever becomes of
+    it), ``side`` ((n, 3) int: 0 below, 1 above, -1 not outside), ``n`` ((n, 3): the floor of the folded axes, NaN elsewhere),
+    ``crossed`` (int64 [3][2]) and ``counts`` (int64 [8]: moving, multi, crossed -- the header's order)."""
+    r, v, dr, dv = (np.array(a, dtype=np.float64).reshape(-1, 3) for a in (r, v, dr, dv))
+    cnt = len(r)
+    lo, hi = np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64)
+    photon = np.asarray(photon, dtype=bool).reshape(-1)
+    moving = ~_at_rest(v) & photon
+    side = np.full((cnt, 3), -1, dtype=np.int64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for a, mode in enumerate(modes):
+            if mode is None:
+                continue
+            x = r[:, a]
+            below = x < lo[a]
+            above = x >= hi[a] if mode == "periodic" else x > hi[a]
+            out = (below | above) & np.isfinite(x) & moving
+            side[out, a] = np.where(below[out], 0, 1)
+    outside = side >= 0
+    is_open = np.array([m == "open" for m in modes], dtype=bool)
+    parked = (outside & is_open).any(axis=1)
+    folded = outside.any(axis=1) & ~parked
+    crossed = np.zeros((3, 2), dtype=np.int64)
+    first_open = np.argmax(outside & is_open, axis=1)           # the first open axis a parked photon is outside on
+    for a in range(3):
+        for sd in range(2):
+            crossed[a, sd] = (parked & (first_open == a) & (side[:, a] == sd)).sum() + (folded & (side[:, a] == sd)).sum()
+    v[parked] = 0.0
+    dv[parked] = 0.0
+    n_all = np.full((cnt, 3), np.nan)
+    multi = np.zeros(cnt, dtype=bool)
+    for a, mode in enumerate(modes):
+        at = np.flatnonzero(folded & outside[:, a])
+        if mode is None or not len(at):
+            continue
+        with np.errstate(invalid="ignore", over="ignore"):
+            L = hi[a] - lo[a]
+            s = r[at, a] - lo[a]
+            n = np.floor(s / L)
+            f = np.fmin(np.fmax(s - n * L, 0.0), L)
+            n_all[at, a] = n
+            multi[at] |= (n < -1.0) | (n > 1.0)
+            if mode == "periodic":
+                y = lo[a] + f
+                y = np.where(y < hi[a], y, lo[a])
+            else:
+                h = n * 0.5
+                odd = np.floor(h) != h
+                y = np.fmin(np.fmax(np.where(odd, hi[a] - f, lo[a] + f), lo[a]), hi[a])
+                for field in (v, dv, dr):                       # an odd number of bounces turns the axis round
+                    field[at[odd], a] = -field[at[odd], a]
+        r[at, a] = _stored(y, dtype)
+    counts = np.concatenate([[moving.sum(), multi.sum()], crossed.reshape(-1)]).astype(np.int64)
+    return {"r": r, "v": v, "dr": dr, "dv": dv, "moving": moving, "parked": parked, "folded": folded, "multi": multi,
+            "written": parked | folded, "outside": outside, "side": side, "n": n_all, "crossed": crossed, "counts": counts}
+
+
+class BoxBoundaryStep(RefractiveSurfaceStep):
+    """The sides of the scene (not in the reference): a box ``[lo, hi]`` with a wall of one kind, or none, per axis.  ``lo`` and ``hi``
+    are three numbers each (code units, taken by stored value as ``center`` is); ``walls`` is one of ``"periodic"``, ``"mirror"``,
+    ``"open"`` and None, or three of them for x, y, z.  On an axis with a wall ``lo``, ``hi`` and ``L = hi - lo`` (float64, rounded
+    once) must be finite and ``L > 0``; on an axis with None the bounds are ignored; None on all three raises ``ValueError``.
+
+    * ``"periodic"``: a photon that has left through one side comes back in through the other -- the horizontal boundary condition of
+      a cloud field, without which domain-averaged fluxes mean nothing.  The box is ``[lo, hi)``; only ``r`` of the axis is written, so
+      ``r - dr`` is the image of where the photon came from.
+    * ``"mirror"``: the whole move is folded back at the walls, exact for any number of bounces: ``r`` of the axis is the image, and an
+      odd number of bounces turns ``v``, ``dv`` and ``dr`` of the axis round.  ``|v|`` does not change.  On the wall is inside.
+    * ``"open"``: a photon outside is parked as ``PathAbsorptionStep`` parks -- ``v = 0``, ``dv = 0``, ``r`` and ``dr`` left alone -- and
+      counted once, for the first open axis it is outside on (x, y, z order).  It is at rest from then on, no later pass counts it, and a
+      ``RecycleStep(at_rest=True)`` behind the step hands its slot back to the source.  Open walls come first: a photon parked through
+      one is not folded on any other axis.
+
+    Only moving photons are looked at (the sibling sweeps' test: some ``v_k != 0``; ``-0.0`` counts as 0, a NaN moves); plain
+    ``Object``s, photons at rest and a position that is not finite on an axis are left alone.  A photon that crosses nothing is not
+    written at all; ``E``, ids and kinds are never written.
+
+    Put the step LAST in a pass: behind the ground or the interface, if there is one, and in front of a ``ReemissionStep`` or a
+    ``RecycleStep``.  A tally placed BEHIND it in the same pass sees image positions -- a plane or shell crossing read off ``r - dr``
+    there is the image's, not the move's; nothing refuses that placement.  The step changes nothing in any other step.
+
+    After each run ``moving`` and ``multi`` hold the pass's counts, ``crossed`` an int64 ``[3][2]`` array (axis; below, above) and
+    ``parked`` the sum of ``crossed`` over the open axes, global over shards and ranks (one collective); ``self.data`` gains the row
+    ``[t, moving, multi, crossed]``; ``out_fn`` takes the rows at the end.  ``multi`` counts the photons folded more than once on
+    some axis (``n < -1`` or ``n > 1``): it changes nothing and says that ``c*dt`` is too large for the box, as
+    ``RefractiveSurfaceStep.overshot`` does for a sphere.  The rule is written out in include/physicl_hip.h (pcl_step_box_walls);
+    ``_box_walls`` restates it with numpy, bit for bit.
+
+    The sweep is deterministic: no draw, no id, no seed.  It works with every ``rng=`` setting and, reading no ``dv`` rule, under
+    ``cl_on=False`` as well.  One launch per light step: the K-passes-per-launch kernels cannot fold a photon between two of their
+    passes, and ``sim.launch_note`` says so.  On host-resident objects (``step.run(sim)`` outside a device loop) the same state is
+    made with numpy.
+
+    The class derives from ``RefractiveSurfaceStep``, which writes the same four fields, for ``tally.WriterStep``'s scaffold alone --
+    nothing of the sphere is kept -- and is a writer family of its own (``_OWN_WORDS``; it draws nothing, so its pass counter is handed
+    to nobody)."""
+    _OWN_WORDS = True                                    # (tally.writer_family: not the parent's counter word)
+    _NOTE = "one launch per light step: a BoxBoundaryStep folds or parks the photons that have left its box behind every pass, " \
+            "which the K-passes-per-launch kernels cannot carry"
+    _writes = ("r", "dr", "v", "dv")
+
+    def __init__(self, lo, hi, walls="periodic", out_fn=None):
+        MeasureStep.__init__(self, out_fn)
+        self.lo, self.hi, self.walls = _check_box(lo, hi, walls)
+        self._record_counts(np.zeros(8, dtype=np.int64))
+        self._pass = 0                                   # runs so far (tally.WriterStep)
+
+    def _record_counts(self, counts):
+        counts = np.asarray(counts, dtype=np.int64).reshape(8)
+        self.moving, self.multi = int(counts[0]), int(counts[1])
+        self.crossed = counts[2:].reshape(3, 2).copy()
+        self.parked = int(sum(self.crossed[a].sum() for a, w in enumerate(self.walls) if w == "open"))
+
+    def _record_pass(self, sim, *counts):
+        self._record_counts(counts)
+        self.data.append(tally.object_row([tally._snap(sim.t), self.moving, self.multi, self.crossed]))
+
+    def _sweep(self, sim, prep):
+        return [np.asarray(sim._dev.box_walls(self.walls, self.lo, self.hi), dtype=np.int64)]
+
+    def _host_sweep(self, objs, ids, seed, prep):
+        new = _box_walls(tally.vec3(objs, "r"), tally.vec3(objs, "v"), tally.vec3(objs, "dr"), tally.vec3(objs, "dv"), _photons(objs),
+                         self.walls, self.lo, self.hi)
+        return new, new["written"], tuple(new["counts"])
+
+    terminate = tally.TallyStep.terminate                # (a row holds an array: written as the tally steps write theirs, as a plain list)
+
+
 # ---------------------------------------------------------------------------------------------- re-emission in place
 def _check_reemission(spectra, edges, center, eta, angular):
     """(tables -- per layer None or (grid, cdf) float64 arrays --, edges or None, centre, eta as a float64 array [L'], angular as a

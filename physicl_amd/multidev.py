@@ -318,6 +318,9 @@ class MultiDevice:
     def scatter_grid(self, *a, **kw):
         return self._sum_parts("scatter_grid", *a, **kw)
 
+    def box_walls(self, *a, **kw):
+        return self._sum_parts("box_walls", *a, **kw)
+
     def plane_energies(self, plane, n_hint=None):
         return self._concat(self._each(lambda s: s.plane_energies(plane)))      # (a shard does not know its share of the hint)
 
