@@ -27,7 +27,11 @@ HASHED = [_c("physicl_hip.hip"), _c("pcl_device.h"), _c("pcl_sincos.h")]
 CORE = dict(src=_c("physicl_hip.hip"), deps=[_c("pcl_device.h"), _c("pcl_sincos.h"), ABI_HEADER, _c("pcl_rtc_source.inc")])
 # The units on the public ABI beside it, one row per translation unit.  ``sweeps``: one element per sweep the unit holds, in
 # the file's order -- ``entries``: the context's and the group's entry point; ``kernel``, ``count``: the kernel template and how
-# many instantiations of it the unit's assembly holds.  A new unit is one more row, a new sweep in a unit one more element.
+# many instantiations of it the unit's assembly holds.  A new unit is one more row, a new sweep in a unit one more element
+# (tests/test_build_cpu.py checks every element alike).  Why a unit's sweeps stand together:
+#   pcl_shell.hip    the crossing tallies: the aperture's image stands behind the shells'.
+#   pcl_grid.hip     four instantiations, an LDS and a global form per dtype (as k_scatter_grid's).
+#   pcl_surface.hip  the sweeps that write photons: they share their rules (pcl_rules.h), hit-point arithmetic and tables.
 SWEEP = [_c("pcl_sweep.h"), ABI_HEADER]
 DEVICE = SWEEP + [_c("pcl_device.h"), _c("pcl_sincos.h")]
 RULES = DEVICE + [_c("pcl_rules.h")]          # the units that write photons share their rules
@@ -40,7 +44,9 @@ def _sweep(ctx_entry, group_entry, kernel, count=2):
 ADDONS = [
     dict(src=_c("pcl_spectrum.hip"), deps=SWEEP, sweeps=(_sweep("pcl_step_plane_spectra", "pcl_group_step_plane_spectra", "k_plane_spectra"),)),
     dict(src=_c("pcl_source.hip"), deps=RULES, sweeps=(_sweep("pcl_store_apply_source", "pcl_group_apply_source", "k_apply_source"),)),
-    dict(src=_c("pcl_shell.hip"), deps=SWEEP, sweeps=(_sweep("pcl_step_shell_crossings", "pcl_group_step_shell_crossings", "k_shell_crossings"),)),
+    dict(src=_c("pcl_shell.hip"), deps=SWEEP, sweeps=(
+        _sweep("pcl_step_shell_crossings", "pcl_group_step_shell_crossings", "k_shell_crossings"),
+        _sweep("pcl_step_detector_image", "pcl_group_step_detector_image", "k_detector_image"))),
     dict(src=_c("pcl_grid.hip"), deps=SWEEP, sweeps=(_sweep("pcl_step_position_grid", "pcl_group_step_position_grid", "k_position_grid", count=4),)),
     dict(src=_c("pcl_surface.hip"), deps=RULES, sweeps=(
         _sweep("pcl_step_surface_reflect", "pcl_group_step_surface_reflect", "k_surface_reflect"),
@@ -48,93 +54,15 @@ ADDONS = [
         _sweep("pcl_step_absorb_scattered", "pcl_group_step_absorb_scattered", "k_absorb_scattered"),
         _sweep("pcl_step_phase_layered", "pcl_group_step_phase_layered", "k_phase_layered"),
         _sweep("pcl_step_recycle_spent", "pcl_group_step_recycle_spent", "k_recycle_spent"),
-        _sweep("pcl_step_absorb_path", "pcl_group_step_absorb_path", "k_absorb_path"))),
+        _sweep("pcl_step_absorb_path", "pcl_group_step_absorb_path", "k_absorb_path"),
+        _sweep("pcl_step_reemit_parked", "pcl_group_step_reemit_parked", "k_reemit_parked"),
+        _sweep("pcl_step_refract_surface", "pcl_group_step_refract_surface", "k_refract_surface"),
+        _sweep("pcl_step_ground_spectral", "pcl_group_step_ground_spectral", "k_ground_spectral"),
+        _sweep("pcl_step_scatter_layered", "pcl_group_step_scatter_layered", "k_scatter_layered"),
+        _sweep("pcl_step_scatter_grid", "pcl_group_step_scatter_grid", "k_scatter_grid", count=4),
+        _sweep("pcl_step_box_walls", "pcl_group_step_box_walls", "k_box_walls"))),
 ]
 UNITS = [CORE] + ADDONS
-# Sweeps a unit holds beside the one of its row, by the unit's file name: the same description (tests/test_detector_cpu.py holds
-# the detector's to it).  The crossing tallies share a unit: the aperture's image stands beside the shells'.
-EXTRA_SWEEPS = {
-    "pcl_shell.hip": (_sweep("pcl_step_detector_image", "pcl_group_step_detector_image", "k_detector_image"),),
-}
-# A writer sweep that joined the unit of the six behind them, in the same form (tests/test_reemit_cpu.py holds the re-emission's
-# to it): what is parked by the sweeps above is re-emitted beside them.
-WRITER_SWEEPS = {
-    "pcl_surface.hip": (_sweep("pcl_step_reemit_parked", "pcl_group_step_reemit_parked", "k_reemit_parked"),),
-}
-
-
-def sweeps_of(unit):
-    """Every sweep a unit of ADDONS holds, in the file's order: its row's, then what EXTRA_SWEEPS and WRITER_SWEEPS add."""
-    name = os.path.basename(unit["src"])
-    return tuple(unit["sweeps"]) + EXTRA_SWEEPS.get(name, ()) + WRITER_SWEEPS.get(name, ())
-
-
-# A sweep that joined a unit behind the tables above, in the same form (tests/test_refract_cpu.py holds the refracting sphere's to
-# it): the dielectric interface stands beside the ground, whose hit-point arithmetic it shares.  sweeps_of() does not fold this
-# table in -- the tests of the sweeps above count what it returns --; described_sweeps_of() is every sweep a unit holds.
-INTERFACE_SWEEPS = {
-    "pcl_surface.hip": (_sweep("pcl_step_refract_surface", "pcl_group_step_refract_surface", "k_refract_surface"),),
-}
-
-
-def described_sweeps_of(unit):
-    """Every sweep a unit of ADDONS holds, in the file's order: sweeps_of(unit), then what INTERFACE_SWEEPS adds."""
-    return sweeps_of(unit) + INTERFACE_SWEEPS.get(os.path.basename(unit["src"]), ())
-
-
-# The spectral ground's sweep, in the same form (tests/test_spectral_surface_cpu.py holds it to it): the ground by energy band stands
-# beside the grey one, whose arithmetic and counter words it shares.  Neither function above folds this table in -- the tests of the
-# older sweeps hold both to their contents --; every_sweep_of() is every sweep a unit holds.
-SPECTRAL_SWEEPS = {
-    "pcl_surface.hip": (_sweep("pcl_step_ground_spectral", "pcl_group_step_ground_spectral", "k_ground_spectral"),),
-}
-
-
-def every_sweep_of(unit):
-    """Every sweep a unit of ADDONS holds, in the file's order: described_sweeps_of(unit), then what SPECTRAL_SWEEPS adds."""
-    return described_sweeps_of(unit) + SPECTRAL_SWEEPS.get(os.path.basename(unit["src"]), ())
-
-
-# The medium's scattering by layer and band, in the same form (tests/test_scatter_layered_cpu.py holds it to it): path absorption's
-# twin stands beside it, whose tables and checks it shares.  None of the functions above folds this table in -- the tests of the older
-# sweeps hold all three to their contents --; all_sweeps_of() is every sweep a unit holds.
-MEDIUM_SWEEPS = {
-    "pcl_surface.hip": (_sweep("pcl_step_scatter_layered", "pcl_group_step_scatter_layered", "k_scatter_layered"),),
-}
-
-
-def all_sweeps_of(unit):
-    """Every sweep a unit of ADDONS holds, in the file's order: every_sweep_of(unit), then what MEDIUM_SWEEPS adds."""
-    return every_sweep_of(unit) + MEDIUM_SWEEPS.get(os.path.basename(unit["src"]), ())
-
-
-# The medium's scattering on a grid of cells, in the same form (tests/test_scatter_grid_cpu.py holds it to it): the scattering by
-# layer stands beside it, whose draw and direction it shares; four instantiations, an LDS and a global form per dtype, as the position
-# grid's.  None of the functions above folds this table in -- the tests of the older sweeps hold all four to their contents --;
-# volume_sweeps_of() is every sweep a unit holds.
-VOLUME_SWEEPS = {
-    "pcl_surface.hip": (_sweep("pcl_step_scatter_grid", "pcl_group_step_scatter_grid", "k_scatter_grid", count=4),),
-}
-
-
-def volume_sweeps_of(unit):
-    """Every sweep a unit of ADDONS holds, in the file's order: all_sweeps_of(unit), then what VOLUME_SWEEPS adds."""
-    return all_sweeps_of(unit) + VOLUME_SWEEPS.get(os.path.basename(unit["src"]), ())
-
-
-# The walls of a box, in the same form (tests/test_writer_walls_cpu.py holds it to it): the sides of the scene stand beside the ground and
-# the interface, whose rows (r, dr, v, dv) the sweep writes; it parks what leaves through an open wall as path absorption parks.  None of
-# the functions above folds this table in -- the tests of the older sweeps hold all five to their contents --; boundary_sweeps_of() is
-# every sweep a unit holds.
-BOUNDARY_SWEEPS = {
-    "pcl_surface.hip": (_sweep("pcl_step_box_walls", "pcl_group_step_box_walls", "k_box_walls"),),
-}
-
-
-def boundary_sweeps_of(unit):
-    """Every sweep a unit of ADDONS holds, in the file's order: volume_sweeps_of(unit), then what BOUNDARY_SWEEPS adds."""
-    return volume_sweeps_of(unit) + BOUNDARY_SWEEPS.get(os.path.basename(unit["src"]), ())
-
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -ffp-contract=off: the reference's kernels must be evaluated unfused (bit-exact parity, DESIGN.md)

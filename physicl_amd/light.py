@@ -1130,6 +1130,7 @@ class SurfaceReflectStep(tally.WriterStep):
     One launch per light step: the K-passes-per-launch kernels cannot bounce a photon between two of their passes, and
     ``sim.launch_note`` says so.  On host-resident objects (``step.run(sim)`` outside a device loop) the same state is made with
     numpy, the ids being the places in the object list -- what an upload would give them."""
+    _STREAM = "ground"                                   # (words 8 and 9, as the spectral ground's)
     _NOTE = "one launch per light step: a SurfaceReflectStep bounces photons off its sphere behind every pass, which the " \
             "K-passes-per-launch kernels cannot carry"
 
@@ -1257,6 +1258,7 @@ class SpectralSurfaceStep(tally.WriterStep):
     One launch per light step: the K-passes-per-launch kernels cannot bounce a photon between two of their passes, and
     ``sim.launch_note`` says so.  On host-resident objects (``step.run(sim)`` outside a device loop) the same state is made with
     numpy, the ids being the places in the object list."""
+    _STREAM = "ground"                                   # (the grey ground's words 8 and 9 (22 is its own))
     _NOTE = "one launch per light step: a SpectralSurfaceStep bounces photons off its sphere behind every pass, which the " \
             "K-passes-per-launch kernels cannot carry"
     _writes = ("r", "dr", "v", "dv")
@@ -1432,6 +1434,7 @@ class RefractiveSurfaceStep(tally.WriterStep):
     One launch per light step: the K-passes-per-launch kernels cannot refract a photon between two of their passes, and
     ``sim.launch_note`` says so.  On host-resident objects (``step.run(sim)`` outside a device loop) the same state is made with
     numpy, the ids being the places in the object list."""
+    _STREAM = "refract"
     _NOTE = "one launch per light step: a RefractiveSurfaceStep refracts photons at its sphere behind every pass, which the " \
             "K-passes-per-launch kernels cannot carry"
     _writes = ("r", "dr", "v", "dv")
@@ -1530,6 +1533,7 @@ class PhaseFunctionStep(tally.WriterStep):
     One launch per light step: the K-passes-per-launch kernels cannot re-direct a photon between two of their passes, and
     ``sim.launch_note`` says so.  On host-resident objects (``step.run(sim)`` outside a device loop) the same state is made with
     numpy, the ids being the places in the object list."""
+    _STREAM = "phase"                                    # (words 10 and 11, as the layered phase step's)
     _NOTE = "one launch per light step: a PhaseFunctionStep re-directs the scattered photons behind every pass, which the " \
             "K-passes-per-launch kernels cannot carry"
 
@@ -1660,6 +1664,7 @@ class AbsorptionStep(tally.WriterStep):
     One launch per light step: the K-passes-per-launch kernels cannot absorb a photon between two of their passes, and
     ``sim.launch_note`` says so.  On host-resident objects (``step.run(sim)`` outside a device loop) the same state is made with
     numpy, the ids being the places in the object list."""
+    _STREAM = "absorb"
     _NOTE = "one launch per light step: an AbsorptionStep absorbs interacting photons behind every pass, which the " \
             "K-passes-per-launch kernels cannot carry"
 
@@ -1860,6 +1865,7 @@ class LayeredPhaseStep(tally.WriterStep):
     One launch per light step: the K-passes-per-launch kernels cannot re-direct a photon between two of their passes, and
     ``sim.launch_note`` says so.  On host-resident objects (``step.run(sim)`` outside a device loop) the same state is made with
     numpy, the ids being the places in the object list."""
+    _STREAM = "phase"                                    # (the phase step's words 10 and 11 (13 is its own))
     _NOTE = "one launch per light step: a LayeredPhaseStep re-directs the scattered photons behind every pass, which the " \
             "K-passes-per-launch kernels cannot carry"
 
@@ -2045,6 +2051,7 @@ class RecycleStep(tally.WriterStep):
     One launch per light step: the K-passes-per-launch kernels cannot re-emit a photon between two of their passes, and
     ``sim.launch_note`` says so.  On host-resident objects (``step.run(sim)`` outside a device loop) the same state is made with
     numpy, the ids being the places in the object list."""
+    _STREAM = "recycle"
     _NOTE = "one launch per light step: a RecycleStep re-emits the spent photons behind every pass, which the " \
             "K-passes-per-launch kernels cannot carry"
 
@@ -2200,6 +2207,7 @@ class PathAbsorptionStep(tally.WriterStep):
     One launch per light step: the K-passes-per-launch kernels cannot absorb a photon between two of their passes, and
     ``sim.launch_note`` says so.  On host-resident objects (``step.run(sim)`` outside a device loop) the same state is made with
     numpy, the ids being the places in the object list."""
+    _STREAM = "path_absorb"
     _NOTE = "one launch per light step: a PathAbsorptionStep absorbs moving photons behind every pass, which the " \
             "K-passes-per-launch kernels cannot carry"
 
@@ -2261,9 +2269,6 @@ def _scatter_layered(r, v, dv, E, photon, ids, p, edges, center, E_edges, first,
             "scattered_by_cell": cells}
 
 
-_earlier_steps = tally.earlier_steps                           # (stated once, beside the writer steps' counter rule)
-
-
 class LayeredScatterStep(tally.WriterStep):
     """Who scatters, by radial layer and energy band (not in the reference): the scattering twin of ``PathAbsorptionStep``.
     ``ScatterIsotropicStep`` decides with ``A * n * |dr|`` -- ``n`` a constant or a closed-form expression, the only colour a
@@ -2315,6 +2320,7 @@ class LayeredScatterStep(tally.WriterStep):
     One launch per light step: the K-passes-per-launch kernels cannot scatter a photon by a table between two of their passes, and
     ``sim.launch_note`` says so.  On host-resident objects (``step.run(sim)`` outside a device loop) the same state is made with
     numpy, the ids being the places in the object list."""
+    _STREAM = "scatter_layered"
     _NOTE = "one launch per light step: a LayeredScatterStep scatters moving photons by layer and band behind every pass, which " \
             "the K-passes-per-launch kernels cannot carry"
 
@@ -2336,7 +2342,7 @@ class LayeredScatterStep(tally.WriterStep):
     def _refuse(self, sim):
         first = self.first
         if self._pass == 0:                              # the step order is looked at once, before anything moves
-            front, behind = _earlier_steps(sim, self)
+            front, behind = tally.earlier_steps(sim, self)   # (stated once, beside the writer steps' counter rule)
             for other in behind:
                 if isinstance(other, ScatterIsotropicStep):
                     raise ValueError("a pass marks its scattered photons once: the simulation's steps hold a %s behind this "
@@ -2476,12 +2482,8 @@ class GridScatterStep(LayeredScatterStep):
 
     One launch per light step: the K-passes-per-launch kernels cannot scatter a photon by a table between two of their passes, and
     ``sim.launch_note`` says so.  On host-resident objects (``step.run(sim)`` outside a device loop) the same state is made with
-    numpy, the ids being the places in the object list.
-
-    The class derives from ``LayeredScatterStep`` for what is the same -- the ``first`` rule and its refusals, ``p`` per pass, the row --
-    and is a writer family of its own (``tally.writer_family``): its draws have words of their own, so its pass counter does not
-    interleave with a ``LayeredScatterStep``'s."""
-    _OWN_WORDS = True                                    # (tally.writer_family: not the parent's counter words)
+    numpy, the ids being the places in the object list."""
+    _STREAM = "scatter_grid"                             # (words 25 and 26: not the parent's)
     _NOTE = "one launch per light step: a GridScatterStep scatters moving photons by grid cell and band behind every pass, which " \
             "the K-passes-per-launch kernels cannot carry"
 
@@ -2608,7 +2610,7 @@ def _box_walls(r, v, dr, dv, photon, modes, lo, hi, dtype=np.float64):
             "written": parked | folded, "outside": outside, "side": side, "n": n_all, "crossed": crossed, "counts": counts}
 
 
-class BoxBoundaryStep(RefractiveSurfaceStep):
+class BoxBoundaryStep(tally.WriterStep):
     """The sides of the scene (not in the reference): a box ``[lo, hi]`` with a wall of one kind, or none, per axis.  ``lo`` and ``hi``
     are three numbers each (code units, taken by stored value as ``center`` is); ``walls`` is one of ``"periodic"``, ``"mirror"``,
     ``"open"`` and None, or three of them for x, y, z.  On an axis with a wall ``lo``, ``hi`` and ``L = hi - lo`` (float64, rounded
@@ -2642,12 +2644,8 @@ class BoxBoundaryStep(RefractiveSurfaceStep):
     The sweep is deterministic: no draw, no id, no seed.  It works with every ``rng=`` setting and, reading no ``dv`` rule, under
     ``cl_on=False`` as well.  One launch per light step: the K-passes-per-launch kernels cannot fold a photon between two of their
     passes, and ``sim.launch_note`` says so.  On host-resident objects (``step.run(sim)`` outside a device loop) the same state is
-    made with numpy.
-
-    The class derives from ``RefractiveSurfaceStep``, which writes the same four fields, for ``tally.WriterStep``'s scaffold alone --
-    nothing of the sphere is kept -- and is a writer family of its own (``_OWN_WORDS``; it draws nothing, so its pass counter is handed
-    to nobody)."""
-    _OWN_WORDS = True                                    # (tally.writer_family: not the parent's counter word)
+    made with numpy."""
+    _STREAM = "box_walls"                                # (it draws nothing: its pass counter is handed to nobody)
     _NOTE = "one launch per light step: a BoxBoundaryStep folds or parks the photons that have left its box behind every pass, " \
             "which the K-passes-per-launch kernels cannot carry"
     _writes = ("r", "dr", "v", "dv")
@@ -2820,6 +2818,7 @@ class ReemissionStep(tally.WriterStep):
     One launch per light step: the K-passes-per-launch kernels cannot re-emit a photon between two of their passes, and
     ``sim.launch_note`` says so.  On host-resident objects (``step.run(sim)`` outside a device loop) the same state is made with
     numpy, the ids being the places in the object list."""
+    _STREAM = "reemit"
     _NOTE = "one launch per light step: a ReemissionStep re-emits the parked photons behind every pass, which the " \
             "K-passes-per-launch kernels cannot carry"
 

@@ -93,24 +93,16 @@ def object_row(cells):
 
 
 # ---------------------------------------------------------------------------------------------- the writer steps' streams
-# The writer classes (light.py) whose draws share a Philox counter word: the two grounds draw the bounce from words 8 and 9, the two
-# phase steps the angles from 10 and 11.  Every other writer class has words of its own and is a family of one class.
-WRITER_FAMILIES = (("SurfaceReflectStep", "SpectralSurfaceStep"), ("PhaseFunctionStep", "LayeredPhaseStep"))
 N_PASS_MAX = 0xFFFFFFFF      # n_pass is one 32-bit counter word
 
 
 def writer_family(step):
-    """What the steps that share ``step``'s counter words have in common: a row of ``WRITER_FAMILIES``, or the writer class itself
-    (the class right below ``WriterStep``: a subclass of a step draws from its words -- unless it says that it has words of its own,
-    ``_OWN_WORDS = True`` in the class's own body: then it, and what derives from it, is a family of its own)."""
-    line = [c for c in type(step).__mro__ if issubclass(c, WriterStep) and c is not WriterStep]
-    for c in line:
-        for family in WRITER_FAMILIES:
-            if c.__name__ in family:
-                return family
-        if vars(c).get("_OWN_WORDS"):
-            return c
-    return line[-1]
+    """The name of the Philox stream ``step`` draws from, which its class states (``_STREAM``, ``WriterStep``): steps of one name
+    share counter words and are a family."""
+    stream = type(step)._STREAM
+    if stream is None:
+        raise TypeError("%s states no _STREAM: a class below WriterStep names the Philox stream it draws from" % type(step).__name__)
+    return stream
 
 
 def earlier_steps(sim, step):
@@ -185,7 +177,7 @@ class WriterStep(DeviceStep, MeasureStep):
 
     Two counters.  ``_pass`` is the number of runs so far.  ``_n_pass`` is the Philox counter word the run's sweep and its numpy
     restatement are handed -- what a subclass passes on, readable after each run.  Steps whose draws share a counter word (a
-    FAMILY: ``WRITER_FAMILIES``, and every other writer class on its own) would draw the same number for the same photon if their
+    FAMILY: the classes that state the same ``_STREAM``) would draw the same number for the same photon if their
     counters moved in lock-step -- two gases absorbing in one pass would absorb the same photons.  So at its first run a step takes
     from the simulation's step list how many members ``m`` its family has in the pass and its place ``j`` among them in pass order,
     and from then on ``_n_pass = (_pass - 1) * m + j + 1``: the members' counters interleave and never meet.  With one member (and
@@ -193,6 +185,9 @@ class WriterStep(DeviceStep, MeasureStep):
     is communicated.  A counter beyond 2**32 - 1 is refused (ValueError) before ``_pass`` moves: it would wrap.
 
     A subclass sets
+    ``_STREAM`` (every class directly below this one states it in its body: the name of the Philox stream it draws from -- the name of
+    another class's where the two share counter words, as the two grounds do; what derives from the class inherits it, or states a
+    name of its own where its draws have words of their own; a class that states none is refused at its first run, TypeError),
     ``_NOTE`` (what ``sim.launch_note`` says: the K-passes-per-launch kernels cannot carry the step) and ``_writes`` (which of
     ``r``, ``dr``, ``v``, ``dv``, ``E`` the host path writes back), keeps its own ``__init__`` and ``_record_pass``, and supplies:
 
@@ -205,6 +200,7 @@ class WriterStep(DeviceStep, MeasureStep):
 
     ``_reduce(sim, parts)`` is the pass's ONE collective (every rank issues it, also with an empty shard)."""
     _fuse_role = None
+    _STREAM = None
     _NOTE = None
     _writes = ("v", "dv")
     _pass = _n_pass = 0

@@ -19,6 +19,7 @@ from physicl_amd import _hip, build
 
 CORE_FILES = ["physicl_hip.hip", "pcl_device.h", "pcl_sincos.h"]
 ORDER = ["physicl_hip.hip", "pcl_spectrum.hip", "pcl_source.hip", "pcl_shell.hip", "pcl_grid.hip", "pcl_surface.hip"]
+PER_UNIT = {"pcl_spectrum.hip": 1, "pcl_source.hip": 1, "pcl_shell.hip": 2, "pcl_grid.hip": 1, "pcl_surface.hip": 12}     # sweeps
 SWEEP_H = os.path.join(build.CSRC, "pcl_sweep.h")
 name = os.path.basename
 names = lambda paths: [name(p) for p in paths]                                                              # noqa: E731
@@ -26,12 +27,13 @@ by_name = lambda rows: pytest.mark.parametrize("unit", rows, ids=[name(u["src"])
 SWEEPS = [(u, s) for u in build.ADDONS for s in u["sweeps"]]
 by_sweep = pytest.mark.parametrize("unit,sweep", SWEEPS, ids=["%s-%s" % (name(u["src"]), s["kernel"]) for u, s in SWEEPS])
 # What a sweep's kernels must show beyond the instantiations without scratch or VGPR spills: no SGPR spills, a VGPR count
-# (shell: eight waves per SIMD, occupancy is left to LDS; the surface unit's: six waves per SIMD or more), and instructions in
-# the unit's assembly.
+# (64: eight waves per SIMD -- the shell unit's, where occupancy is left to LDS, and the surface unit's later sweeps; 80: six waves
+# per SIMD or more), and instructions in the unit's assembly.  One row per sweep of the table, in the table's order.
 ASM = {
     "k_plane_spectra": {},
     "k_apply_source": dict(no_sgpr_spills=True, has=["v_fma_f64"]),          # (the sincos' explicit FMAs; everything else is unfused)
     "k_shell_crossings": dict(no_sgpr_spills=True, vgprs=64),
+    "k_detector_image": dict(no_sgpr_spills=True, vgprs=64),
     # 64-bit adds on the device grid, 32-bit ones in LDS; q is unfused, and no square root anywhere
     "k_position_grid": dict(no_sgpr_spills=True, has=["global_atomic_add_x2", "ds_add_u32"], lacks=["v_fma_f64", "v_sqrt"]),
     "k_surface_reflect": dict(vgprs=80),
@@ -40,7 +42,16 @@ ASM = {
     "k_phase_layered": dict(vgprs=80),
     "k_recycle_spent": dict(vgprs=80),
     "k_absorb_path": dict(vgprs=80),
+    "k_reemit_parked": dict(vgprs=80),
+    "k_refract_surface": dict(vgprs=80),
+    "k_ground_spectral": dict(vgprs=80),
+    "k_scatter_layered": dict(vgprs=64),
+    "k_scatter_grid": dict(vgprs=64),
+    "k_box_walls": dict(vgprs=64),
 }
+# The forms a kernel template is instantiated in, by their number: what follows the kernel's name in the mangled one, and the sorted
+# matches -- a float and a double form; an LDS and a global form of each, as the position grid's and the grid scatter's.
+FORMS = {2: (r"I([df])E", [("d",), ("f",)]), 4: (r"I([df])Lb([01])E", [("d", "0"), ("d", "1"), ("f", "0"), ("f", "1")])}
 
 
 # ------------------------------------------------------------------------------------------------ the table
@@ -58,11 +69,13 @@ def test_units_and_their_link_order():
     assert SWEEP_H not in build.CORE["deps"] and SWEEP_H not in [u["src"] for u in build.UNITS]
     for u in build.ADDONS:
         assert SWEEP_H in u["deps"] and build.ABI_HEADER in u["deps"], u["src"]
-        assert set(u) == {"src", "deps", "sweeps"} and len(u["sweeps"]) == (6 if name(u["src"]) == "pcl_surface.hip" else 1)
+        assert set(u) == {"src", "deps", "sweeps"} and len(u["sweeps"]) == PER_UNIT[name(u["src"])]
         for s in u["sweeps"]:
             assert len(s["entries"]) == 2 and s["entries"][1].startswith("pcl_group_") and s["kernel"].startswith("k_"), s
     entries = [e for _, s in SWEEPS for e in s["entries"]]
-    assert len(set(entries)) == len(entries) == 20                     # no entry point belongs to two sweeps
+    assert len(SWEEPS) == 17 and len(set(entries)) == len(entries) == 34          # no entry point belongs to two sweeps
+    # (a sweep's instantiations are found by the kernel's name inside the mangled one: no name holds another)
+    assert not any(a is not b and a["kernel"] in b["kernel"] for _, a in SWEEPS for _, b in SWEEPS)
     assert [s["kernel"] for _, s in SWEEPS] == list(ASM) and all(os.path.isfile(p) for p in table_files())
 
 
@@ -186,13 +199,15 @@ def assembly(tmp_path_factory):
 
 @by_sweep
 def test_kernels_use_no_scratch(unit, sweep, assembly):
-    """From the unit's assembly: every instantiation of the sweep's kernel, nothing in scratch, no spills, its budget."""
+    """From the unit's assembly: every instantiation of the sweep's kernel in its forms, nothing in scratch, no spills, its budget."""
     text, want = assembly(unit), ASM[sweep["kernel"]]
     kernels = re.findall(r"\.name:\s+(_Z\w*%s\w*)\n(.*?)\.wavefront_size" % sweep["kernel"], text, re.S)
     assert len(kernels) == sweep["count"], [k for k, _ in kernels]
+    form, forms = FORMS[sweep["count"]]
+    assert sorted(re.search(sweep["kernel"] + form, k).groups() for k, _ in kernels) == forms
     for kernel, blk in kernels:
         get = lambda k: int(re.search(r"\.%s:\s+(\d+)" % k, blk).group(1))                                  # noqa: E731
-        print(kernel, "vgprs", get("vgpr_count"), "sgprs", get("sgpr_count"))
+        print(kernel, "vgprs", get("vgpr_count"), "sgprs", get("sgpr_count"), "sgpr spills", get("sgpr_spill_count"))
         assert get("private_segment_fixed_size") == 0 and get("vgpr_spill_count") == 0, kernel
         assert get("sgpr_spill_count") == 0 or not want.get("no_sgpr_spills"), kernel
         assert "vgprs" not in want or get("vgpr_count") <= want["vgprs"], kernel

@@ -7,13 +7,12 @@
   header's limits against ``_hip``;
 * the TallyStep wiring on a stand-in device (rows, ``frames``, the exposure, ``out_fn``), the MultiDevice sum on stand-in shards, the
   binding on a stand-in library, the host-plugin path on Python objects;
-* from one cross-compile of the unit with the library's options: the kernel's two instantiations, no scratch, no spills, its
-  register budget; both entry points exported and declared; the extra row of the build table.
+* both entry points declared; the sweep's element of the build table (tests/test_build_cpu.py holds the kernel's assembly to its
+  budget, as every sweep's).
 """
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -291,14 +290,9 @@ def test_header_limits_prototypes_and_the_build_table():
     assert 3 * 1025 * 8 < 64 * 1024                         # the largest call's three edge tables fit the LDS a launch may ask for
     assert "wavelength-dependent scatter" in " ".join(text[text.index("What a radiometer sees"):text.index("#define PCL_DETECTOR_MAX_PIXELS")].split())
     assert hasattr(_hip.Device, "detector_image") and hasattr(_hip.DeviceGroup, "detector_image")
-    # the extra row: the unit for crossing tallies holds the sweep beside its own, described as every sweep is
-    assert list(build.EXTRA_SWEEPS) == ["pcl_shell.hip"] and [os.path.basename(u["src"]) for u in build.ADDONS].count("pcl_shell.hip") == 1
-    (sweep,) = build.EXTRA_SWEEPS["pcl_shell.hip"]
-    assert sweep == dict(entries=ENTRIES, kernel="k_detector_image", count=2)
-    listed = [e for u in build.ADDONS for s in u["sweeps"] for e in s["entries"]]
-    assert not set(ENTRIES) & set(listed)
-    # (tests/test_build_cpu.py finds a sweep's instantiations by the kernel's name inside the mangled one: no name holds another)
-    assert not any(s["kernel"] in sweep["kernel"] or sweep["kernel"] in s["kernel"] for u in build.ADDONS for s in u["sweeps"])
+    # the table: the unit for crossing tallies holds the sweep behind the shells', described as every sweep is (tests/test_build_cpu.py)
+    (unit,) = [u for u in build.ADDONS if os.path.basename(u["src"]) == "pcl_shell.hip"]
+    assert unit["sweeps"][1] == dict(entries=ENTRIES, kernel="k_detector_image", count=2)
 
 
 # ------------------------------------------------------------------------------------------------ the library
@@ -379,36 +373,3 @@ def test_host_path_gives_the_restatement_s_rows(tmp_path):
     assert list(b.data[0]) == [0.25, wide[0][0], wide[0][1]] and np.array_equal(b.image, 2 * wide[1]) and np.count_nonzero(b.image) >= 2
     a.terminate(sim)
     assert out.read_text() == ("0.25, %d, %d, %d, %s\n" % (n, counts[0], counts[1], image.tolist())) * 2
-
-
-# ------------------------------------------------------------------------------------------------ the kernel
-@pytest.fixture(scope="module")
-def unit_assembly(tmp_path_factory):
-    """The device assembly of the unit that holds the sweep, compiled once with the library's own options."""
-    (src,) = [u["src"] for u in build.ADDONS if os.path.basename(u["src"]) in build.EXTRA_SWEEPS]
-    out = str(tmp_path_factory.mktemp("asm") / "unit.s")
-    subprocess.check_call([build.HIPCC] + [f for f in build.FLAGS if f not in ("-shared", "-fPIC")] + ["--cuda-device-only", "-S", "-o", out, src],
-                          stderr=subprocess.DEVNULL)
-    return open(out).read()
-
-
-def test_the_kernel_uses_no_scratch_and_keeps_eight_waves(unit_assembly):
-    (sweep,) = build.EXTRA_SWEEPS["pcl_shell.hip"]
-    kernels = re.findall(r"\.name:\s+(_Z\w*%s\w*)\n(.*?)\.wavefront_size" % sweep["kernel"], unit_assembly, re.S)
-    assert len(kernels) == sweep["count"] == 2, [k for k, _ in kernels]
-    assert sorted(re.search(r"k_detector_imageI([df])E", k).group(1) for k, _ in kernels) == ["d", "f"]
-    for kernel, blk in kernels:
-        get = lambda k: int(re.search(r"\.%s:\s+(\d+)" % k, blk).group(1))                                  # noqa: E731
-        print(kernel, "vgprs", get("vgpr_count"), "sgprs", get("sgpr_count"))
-        assert get("private_segment_fixed_size") == 0 and get("vgpr_spill_count") == 0 and get("sgpr_spill_count") == 0, kernel
-        assert get("vgpr_count") <= 64, kernel              # eight waves per SIMD, as the shells' kernel
-    # the shells' kernel beside it keeps its own budget (tests/test_build_cpu.py holds it, too)
-    shells = re.findall(r"\.name:\s+(_Z\w*k_shell_crossings\w*)\n(.*?)\.wavefront_size", unit_assembly, re.S)
-    assert len(shells) == 2 and all(int(re.search(r"\.vgpr_count:\s+(\d+)", blk).group(1)) <= 64 for _, blk in shells)
-
-
-def test_library_exports_both_entry_points():
-    build.build_lib()
-    lib = ctypes.CDLL(_hip.LIB_PATH)
-    assert lib.pcl_abi_version() == 1 and all(hasattr(lib, e) for e in ENTRIES)
-    assert build.csrc_sha() == "b54e0443ee3f400f"

@@ -1,10 +1,9 @@
 """CPU: ReemissionStep (light.ReemissionStep, light._reemit_parked, pcl_step_reemit_parked) -- the constructor, the numpy
 restatement against a plain loop on a scene that holds every case, the directions, the host-resident path, the header, the
-bindings, the build table, the unit's assembly and the refusals that need no device."""
+bindings, the build table and the refusals that need no device."""
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -332,17 +331,9 @@ def test_header_limits_prototypes_and_the_build_table():
     flat = " ".join(text.split()).replace("* ", "")
     assert "words 18, 19 and 20 are used by nothing else" in flat and "0-5 and 8-17 are taken" in flat
     assert hasattr(_hip.Device, "reemit_parked") and hasattr(_hip.DeviceGroup, "reemit_parked")
-    # the table: the unit of the writer sweeps holds this one beside its six, described as every sweep is
-    assert list(build.WRITER_SWEEPS) == ["pcl_surface.hip"] and [os.path.basename(u["src"]) for u in build.ADDONS].count("pcl_surface.hip") == 1
-    (sweep,) = build.WRITER_SWEEPS["pcl_surface.hip"]
-    assert sweep == dict(entries=ENTRIES, kernel="k_reemit_parked", count=2)
+    # the table: the unit of the writer sweeps holds this one, described as every sweep is (tests/test_build_cpu.py checks it as one)
     (unit,) = [u for u in build.ADDONS if os.path.basename(u["src"]) == "pcl_surface.hip"]
-    assert build.sweeps_of(unit) == tuple(unit["sweeps"]) + (sweep,) and len(build.sweeps_of(unit)) == 7
-    every = [s for u in build.ADDONS for s in build.sweeps_of(u)]
-    entries = [e for s in every for e in s["entries"]]
-    assert len(set(entries)) == len(entries) == 24                     # no entry point belongs to two sweeps
-    # (a sweep's instantiations are found by the kernel's name inside the mangled one: no name holds another)
-    assert not any(a is not b and a["kernel"] in b["kernel"] for a in every for b in every)
+    assert dict(entries=ENTRIES, kernel="k_reemit_parked", count=2) in unit["sweeps"]
 
 
 def test_the_counter_words_are_named_constants_used_nowhere_else():
@@ -371,33 +362,3 @@ def test_refused_calls_need_no_device():
         assert lib.pcl_step_reemit_parked(None, *args) == -2, kw
         assert lib.pcl_group_step_reemit_parked(None, *args) != 0, kw
         assert counts is None or (counts == -7).all(), kw
-
-
-def test_library_exports_both_entry_points():
-    build.build_lib()
-    lib = ctypes.CDLL(_hip.LIB_PATH)
-    assert lib.pcl_abi_version() == 1 and all(hasattr(lib, e) for e in ENTRIES)
-    assert build.csrc_sha() == "b54e0443ee3f400f"
-
-
-# ------------------------------------------------------------------------------------------------ the kernel
-@pytest.fixture(scope="module")
-def unit_assembly(tmp_path_factory):
-    """The device assembly of the unit that holds the sweep, compiled once with the library's own options."""
-    out = str(tmp_path_factory.mktemp("asm") / "unit.s")
-    subprocess.check_call([build.HIPCC] + [f for f in build.FLAGS if f not in ("-shared", "-fPIC")] +
-                          ["--cuda-device-only", "-S", "-o", out, os.path.join(build.CSRC, "pcl_surface.hip")], stderr=subprocess.DEVNULL)
-    return open(out).read()
-
-
-def test_the_kernel_uses_no_scratch_and_the_unit_keeps_its_budgets(unit_assembly):
-    (unit,) = [u for u in build.ADDONS if os.path.basename(u["src"]) == "pcl_surface.hip"]
-    for sweep in build.sweeps_of(unit):                                # the new kernel and the six beside it: six waves per SIMD
-        kernels = re.findall(r"\.name:\s+(_Z\w*%s\w*)\n(.*?)\.wavefront_size" % sweep["kernel"], unit_assembly, re.S)
-        assert len(kernels) == sweep["count"] == 2, (sweep["kernel"], [k for k, _ in kernels])
-        assert sorted(re.search(r"%sI([df])E" % sweep["kernel"], k).group(1) for k, _ in kernels) == ["d", "f"]
-        for kernel, blk in kernels:
-            get = lambda k: int(re.search(r"\.%s:\s+(\d+)" % k, blk).group(1))                              # noqa: E731
-            print(kernel, "vgprs", get("vgpr_count"), "sgprs", get("sgpr_count"))
-            assert get("private_segment_fixed_size") == 0 and get("vgpr_spill_count") == 0, kernel
-            assert get("vgpr_count") <= 80, kernel

@@ -1,11 +1,10 @@
 """CPU: RefractiveSurfaceStep (light.RefractiveSurfaceStep, light._refract_surface, pcl_step_refract_surface) -- the constructor, the
 numpy restatement against a plain loop on a scene that holds every case, the closed forms of Snell and Fresnel, the statistics of
-the draw, the agreement with a shell tally of the same radius, the host-resident path, the header, the bindings, the build table,
-the unit's assembly and the refusals that need no device."""
+the draw, the agreement with a shell tally of the same radius, the host-resident path, the header, the bindings, the build table
+and the refusals that need no device."""
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -412,33 +411,8 @@ def test_header_prototypes_and_the_build_table():
     assert hasattr(_hip.Device, "refract_surface") and hasattr(_hip.DeviceGroup, "refract_surface")
     from physicl_amd.multidev import MultiDevice
     assert hasattr(MultiDevice, "refract_surface")
-    # the table: the unit of the writer sweeps holds this one beside its seven, described as every sweep is -- in a table of its own
-    assert list(build.INTERFACE_SWEEPS) == ["pcl_surface.hip"]
-    (sweep,) = build.INTERFACE_SWEEPS["pcl_surface.hip"]
-    assert sweep == dict(entries=ENTRIES, kernel="k_refract_surface", count=2)
-    unit = surface_unit()
-    assert build.described_sweeps_of(unit) == build.sweeps_of(unit) + (sweep,) and len(build.described_sweeps_of(unit)) == 8
-    every = [s for u in build.ADDONS for s in build.described_sweeps_of(u)]
-    entries = [e for s in every for e in s["entries"]]
-    assert len(set(entries)) == len(entries) == 26                     # no entry point belongs to two sweeps
-    assert not any(a is not b and a["kernel"] in b["kernel"] for a in every for b in every)
-    tool = open(os.path.join(os.path.dirname(build.HERE), "tools", "compare_unit_asm.py")).read()
-    assert "described_sweeps_of" in tool                               # the new kernel counts as described
-
-
-def test_sweeps_of_and_the_source_hash_have_not_moved():
-    assert build.csrc_sha() == "b54e0443ee3f400f"
-    assert len(build.ADDONS) == 5 and len(build.UNITS) == 6
-    want = {"pcl_spectrum.hip": ["k_plane_spectra"], "pcl_source.hip": ["k_apply_source"], "pcl_shell.hip": ["k_shell_crossings", "k_detector_image"],
-            "pcl_grid.hip": ["k_position_grid"],
-            "pcl_surface.hip": ["k_surface_reflect", "k_phase_redirect", "k_absorb_scattered", "k_phase_layered", "k_recycle_spent", "k_absorb_path",
-                                "k_reemit_parked"]}
-    for unit in build.ADDONS:
-        name = os.path.basename(unit["src"])
-        assert [s["kernel"] for s in build.sweeps_of(unit)] == want[name], name
-        if name != "pcl_surface.hip":
-            assert build.described_sweeps_of(unit) == build.sweeps_of(unit), name
-    assert not any(os.path.basename(p) == "pcl_surface.hip" for p in build.HASHED)
+    # the table: the unit of the writer sweeps holds this one, described as every sweep is (tests/test_build_cpu.py checks it as one)
+    assert dict(entries=ENTRIES, kernel="k_refract_surface", count=2) in surface_unit()["sweeps"]
 
 
 def test_the_counter_word_is_a_named_constant_used_nowhere_else():
@@ -470,31 +444,3 @@ def test_refused_calls_need_no_device():
     keep, args, counts = abi_args()                                    # a good call without a context is refused, too
     assert lib.pcl_step_refract_surface(None, *args) == -2 and lib.pcl_group_step_refract_surface(None, *args) != 0
     assert (counts == -7).all()
-
-
-def test_library_exports_both_entry_points():
-    build.build_lib()
-    lib = ctypes.CDLL(_hip.LIB_PATH)
-    assert lib.pcl_abi_version() == 1 and all(hasattr(lib, e) for e in ENTRIES)
-
-
-# ------------------------------------------------------------------------------------------------ the kernel
-@pytest.fixture(scope="module")
-def unit_assembly(tmp_path_factory):
-    """The device assembly of the unit that holds the sweep, compiled once with the library's own options."""
-    out = str(tmp_path_factory.mktemp("asm") / "unit.s")
-    subprocess.check_call([build.HIPCC] + [f for f in build.FLAGS if f not in ("-shared", "-fPIC")] +
-                          ["--cuda-device-only", "-S", "-o", out, os.path.join(build.CSRC, "pcl_surface.hip")], stderr=subprocess.DEVNULL)
-    return open(out).read()
-
-
-def test_the_kernel_uses_no_scratch_and_keeps_the_unit_s_budget(unit_assembly):
-    (sweep,) = build.INTERFACE_SWEEPS["pcl_surface.hip"]
-    kernels = re.findall(r"\.name:\s+(_Z\w*%s\w*)\n(.*?)\.wavefront_size" % sweep["kernel"], unit_assembly, re.S)
-    assert len(kernels) == sweep["count"] == 2, [k for k, _ in kernels]
-    assert sorted(re.search(r"%sI([df])E" % sweep["kernel"], k).group(1) for k, _ in kernels) == ["d", "f"]
-    for kernel, blk in kernels:
-        get = lambda k: int(re.search(r"\.%s:\s+(\d+)" % k, blk).group(1))                              # noqa: E731
-        print(kernel, "vgprs", get("vgpr_count"), "sgprs", get("sgpr_count"))
-        assert get("private_segment_fixed_size") == 0 and get("vgpr_spill_count") == 0, kernel
-        assert get("vgpr_count") <= 80, kernel

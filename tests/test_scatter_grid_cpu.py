@@ -1,12 +1,11 @@
 """CPU: GridScatterStep (light.GridScatterStep, light._scatter_grid, pcl_step_scatter_grid) -- the refusals, the numpy restatement
 against a plain loop on Python integers and floats on the edge scene, the radius grid against the scattering by layer, the position
 grid behind its refactoring, the step on host-resident objects, the statistics of the draw, the counter words, the bindings, the
-collective of a large row, the header, the build table, the unit's assembly and the refusals of the library that need no device."""
+collective of a large row, the header, the build table and the refusals of the library that need no device."""
 import ast
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -218,12 +217,12 @@ def test_constructor_keeps_what_it_was_given():
     cls = light.GridScatterStep
     assert issubclass(cls, tally.WriterStep) and not set(vars(cls)) & {"run", "_device_run", "_reduce"}
     # a writer family of its own, though the class derives from the sibling for the rules they share
-    assert tally.writer_family(step) is cls and not any("GridScatterStep" in f for f in tally.WRITER_FAMILIES)
-    assert tally.writer_family(layered()) is light.LayeredScatterStep and cls not in tally.WriterStep.__subclasses__()
+    assert tally.writer_family(step) == cls._STREAM != tally.writer_family(layered()) and "_STREAM" in vars(cls)
+    assert tally.writer_family(layered()) == light.LayeredScatterStep._STREAM and issubclass(cls, light.LayeredScatterStep)
 
     class Plume(cls):                                                   # a subclass draws from the grid step's words
         pass
-    assert tally.writer_family(Plume(0.5, AXES, EDGES)) is cls
+    assert tally.writer_family(Plume(0.5, AXES, EDGES)) == cls._STREAM
     assert "one launch per light step" in cls._NOTE and "GridScatterStep" in cls._NOTE and cls._NOTE != light.LayeredScatterStep._NOTE
     assert cls.terminate is tally.TallyStep.terminate
     assert (_hip.SCATTER_GRID_MAX_BANDS, _hip.SCATTER_GRID_MAX_CELLS) == (1024, 2 ** 20) and _hip.SCATTER_GRID_MAX_CELLS == _hip.GRID_MAX_CELLS
@@ -523,24 +522,8 @@ def test_header_prototypes_and_the_build_table():
     assert hasattr(_hip.Device, "scatter_grid") and hasattr(_hip.DeviceGroup, "scatter_grid")
     from physicl_amd.multidev import MultiDevice
     assert hasattr(MultiDevice, "scatter_grid")
-    # the table: described as every sweep is, in a table of its own that the older functions do not fold in
-    assert list(build.VOLUME_SWEEPS) == ["pcl_surface.hip"]
-    (sweep,) = build.VOLUME_SWEEPS["pcl_surface.hip"]
-    assert sweep == dict(entries=ENTRIES, kernel="k_scatter_grid", count=4)
-    unit = surface_unit()
-    assert build.volume_sweeps_of(unit) == build.all_sweeps_of(unit) + (sweep,) and len(build.volume_sweeps_of(unit)) == 11
-    assert len(build.all_sweeps_of(unit)) == 10 and len(build.every_sweep_of(unit)) == 9 and len(build.described_sweeps_of(unit)) == 8
-    assert len(build.sweeps_of(unit)) == 7 and sweep not in build.all_sweeps_of(unit) and len(build.ADDONS) == 5
-    assert len(build.MEDIUM_SWEEPS["pcl_surface.hip"]) == 1
-    for other in build.ADDONS:
-        if other is not unit:
-            assert build.volume_sweeps_of(other) == build.all_sweeps_of(other)
-    every = [s for u in build.ADDONS for s in build.volume_sweeps_of(u)]
-    entries = [e for s in every for e in s["entries"]]
-    assert len(set(entries)) == len(entries) == 32                     # no entry point belongs to two sweeps
-    assert not any(a is not b and a["kernel"] in b["kernel"] for a in every for b in every)
-    tool = open(os.path.join(os.path.dirname(build.HERE), "tools", "compare_unit_asm.py")).read()
-    assert "volume_sweeps_of" in tool and "all_sweeps_of" in tool and "every_sweep_of" in tool
+    # the table: the unit of the writer sweeps holds this one, described as every sweep is (tests/test_build_cpu.py checks it as one)
+    assert dict(entries=ENTRIES, kernel="k_scatter_grid", count=4) in surface_unit()["sweeps"]
     assert build.csrc_sha() == "b54e0443ee3f400f"                       # the tuned core has not moved
 
 
@@ -560,43 +543,7 @@ def test_refused_calls_need_no_device():
     assert (counts == -7).all() and (cells == -7).all()
 
 
-# ------------------------------------------------------------------------------------------------ the kernel
-@pytest.fixture(scope="module")
-def unit_assembly(tmp_path_factory):
-    """The device assembly of the unit that holds the sweep, compiled once with the library's own options."""
-    out = str(tmp_path_factory.mktemp("asm") / "unit.s")
-    subprocess.check_call([build.HIPCC] + [f for f in build.FLAGS if f not in ("-shared", "-fPIC")] +
-                          ["--cuda-device-only", "-S", "-o", out, os.path.join(build.CSRC, "pcl_surface.hip")], stderr=subprocess.DEVNULL)
-    return open(out).read()
-
-
-def test_the_four_kernels_use_no_scratch_and_keep_the_unit_s_budget(unit_assembly):
-    (sweep,) = build.VOLUME_SWEEPS["pcl_surface.hip"]
-    kernels = re.findall(r"\.name:\s+(_Z\w*%s\w*)\n(.*?)\.wavefront_size" % sweep["kernel"], unit_assembly, re.S)
-    assert len(kernels) == sweep["count"] == 4, [k for k, _ in kernels]
-    assert sorted(re.search(r"%sI([df])Lb([01])E" % sweep["kernel"], k).groups() for k, _ in kernels) == \
-        [("d", "0"), ("d", "1"), ("f", "0"), ("f", "1")]
-    for kernel, blk in kernels:
-        get = lambda k: int(re.search(r"\.%s:\s+(\d+)" % k, blk).group(1))                              # noqa: E731
-        print(kernel, "vgprs", get("vgpr_count"), "sgprs", get("sgpr_count"), "sgpr spills", get("sgpr_spill_count"))
-        assert get("private_segment_fixed_size") == 0 and get("vgpr_spill_count") == 0, kernel
-        assert get("vgpr_count") <= 64, kernel                         # eight waves per SIMD
-
-
 # ------------------------------------------------------------------------------------------------ past the first trip
-def test_the_sweep_has_a_case_past_its_first_trip():
-    """tests/test_writer_trips_cpu.py's check for the table of its own: the kernel's case exists in the file it names."""
-    from test_scatter_grid_trips_gpu import TRIP_CASES
-    assert sorted(TRIP_CASES) == [s["kernel"] for s in build.VOLUME_SWEEPS["pcl_surface.hip"]]
-    tests = os.path.dirname(os.path.abspath(__file__))
-    for kernel, (name, test) in TRIP_CASES.items():
-        path = os.path.join(tests, name)
-        assert name.startswith("test_") and os.path.isfile(path), (kernel, name)
-        with open(path) as f:
-            defined = {node.name for node in ast.parse(f.read()).body if isinstance(node, ast.FunctionDef)}
-        assert test.startswith("test_") and test in defined, (kernel, name, test)
-
-
 @pytest.mark.parametrize("size", ["N2", "N3"])
 def test_the_run_cases_send_waves_from_cell_to_cell_between_trips(size):
     """tests/test_scatter_grid_trips_gpu.py's patterns, by their own arithmetic and without a device (256 CUs): a wave stands in one

@@ -36,9 +36,6 @@ from test_writer_trips_gpu import has_work, slots
 
 pytestmark = pytest.mark.gpu
 
-# kernel -> (file, test) of the case that takes it past one trip and compares every slot (tests/test_scatter_grid_cpu.py)
-TRIP_CASES = {"k_scatter_grid": ("test_scatter_grid_trips_gpu.py", "test_both_forms_past_one_trip")}
-
 AXES = ("x", "y", "z")
 FORMS = {"lds": (4, 4, 4), "global": (17, 16, 16)}                     # 64 cells; 4352 cells, above the 4096 of the switch
 

@@ -1,12 +1,10 @@
 """CPU: LayeredScatterStep (light.LayeredScatterStep, light._scatter_layered, pcl_step_scatter_layered) -- the numpy restatement
 against a plain loop on states that hold every case, the contracts of the two miss modes, the independence of the draws, Beer-Lambert
 and isotropy on the restatement, the composition with the phase and absorption steps on host-resident objects, the refusals, the
-bindings, the header, the build table, the unit's assembly and the refusals of the library that need no device."""
-import ast
+bindings, the header, the build table and the refusals of the library that need no device."""
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -477,23 +475,8 @@ def test_header_prototypes_and_the_build_table():
     assert hasattr(_hip.Device, "scatter_layered") and hasattr(_hip.DeviceGroup, "scatter_layered")
     from physicl_amd.multidev import MultiDevice
     assert hasattr(MultiDevice, "scatter_layered")
-    # the table: described as every sweep is, in a table of its own that the older functions do not fold in
-    assert list(build.MEDIUM_SWEEPS) == ["pcl_surface.hip"]
-    (sweep,) = build.MEDIUM_SWEEPS["pcl_surface.hip"]
-    assert sweep == dict(entries=ENTRIES, kernel="k_scatter_layered", count=2)
-    unit = surface_unit()
-    assert build.all_sweeps_of(unit) == build.every_sweep_of(unit) + (sweep,) and len(build.all_sweeps_of(unit)) == 10
-    assert len(build.every_sweep_of(unit)) == 9 and len(build.described_sweeps_of(unit)) == 8 and len(build.sweeps_of(unit)) == 7
-    assert sweep not in build.every_sweep_of(unit) and len(build.ADDONS) == 5
-    for other in build.ADDONS:
-        if other is not unit:
-            assert build.all_sweeps_of(other) == build.every_sweep_of(other)
-    every = [s for u in build.ADDONS for s in build.all_sweeps_of(u)]
-    entries = [e for s in every for e in s["entries"]]
-    assert len(set(entries)) == len(entries) == 30                     # no entry point belongs to two sweeps
-    assert not any(a is not b and a["kernel"] in b["kernel"] for a in every for b in every)
-    tool = open(os.path.join(os.path.dirname(build.HERE), "tools", "compare_unit_asm.py")).read()
-    assert "all_sweeps_of" in tool                                     # the new kernel counts as described
+    # the table: the unit of the writer sweeps holds this one, described as every sweep is (tests/test_build_cpu.py checks it as one)
+    assert dict(entries=ENTRIES, kernel="k_scatter_layered", count=2) in surface_unit()["sweeps"]
 
 
 def test_refused_calls_need_no_device():
@@ -510,45 +493,3 @@ def test_refused_calls_need_no_device():
     keep, args, (counts, cells) = abi_args()                           # a good call without a context is refused, too
     assert lib.pcl_step_scatter_layered(None, *args) == -2 and lib.pcl_group_step_scatter_layered(None, *args) != 0
     assert (counts == -7).all() and (cells == -7).all()
-
-
-def test_library_exports_both_entry_points():
-    build.build_lib()
-    lib = ctypes.CDLL(_hip.LIB_PATH)
-    assert lib.pcl_abi_version() == 1 and all(hasattr(lib, e) for e in ENTRIES)
-
-
-# ------------------------------------------------------------------------------------------------ the kernel
-@pytest.fixture(scope="module")
-def unit_assembly(tmp_path_factory):
-    """The device assembly of the unit that holds the sweep, compiled once with the library's own options."""
-    out = str(tmp_path_factory.mktemp("asm") / "unit.s")
-    subprocess.check_call([build.HIPCC] + [f for f in build.FLAGS if f not in ("-shared", "-fPIC")] +
-                          ["--cuda-device-only", "-S", "-o", out, os.path.join(build.CSRC, "pcl_surface.hip")], stderr=subprocess.DEVNULL)
-    return open(out).read()
-
-
-def test_the_kernel_uses_no_scratch_and_keeps_the_unit_s_budget(unit_assembly):
-    (sweep,) = build.MEDIUM_SWEEPS["pcl_surface.hip"]
-    kernels = re.findall(r"\.name:\s+(_Z\w*%s\w*)\n(.*?)\.wavefront_size" % sweep["kernel"], unit_assembly, re.S)
-    assert len(kernels) == sweep["count"] == 2, [k for k, _ in kernels]
-    assert sorted(re.search(r"%sI([df])E" % sweep["kernel"], k).group(1) for k, _ in kernels) == ["d", "f"]
-    for kernel, blk in kernels:
-        get = lambda k: int(re.search(r"\.%s:\s+(\d+)" % k, blk).group(1))                              # noqa: E731
-        print(kernel, "vgprs", get("vgpr_count"), "sgprs", get("sgpr_count"), "sgpr spills", get("sgpr_spill_count"))
-        assert get("private_segment_fixed_size") == 0 and get("vgpr_spill_count") == 0, kernel
-        assert get("vgpr_count") <= 64, kernel                         # eight waves per SIMD
-
-
-# ------------------------------------------------------------------------------------------------ past the first trip
-def test_the_sweep_has_a_case_past_its_first_trip():
-    """tests/test_writer_trips_cpu.py's check for the table of its own: the kernel's case exists in the file it names."""
-    from test_scatter_layered_gpu import TRIP_CASES
-    assert sorted(TRIP_CASES) == [s["kernel"] for s in build.MEDIUM_SWEEPS["pcl_surface.hip"]]
-    tests = os.path.dirname(os.path.abspath(__file__))
-    for kernel, (name, test) in TRIP_CASES.items():
-        path = os.path.join(tests, name)
-        assert name.startswith("test_") and os.path.isfile(path), (kernel, name)
-        with open(path) as f:
-            defined = {node.name for node in ast.parse(f.read()).body if isinstance(node, ast.FunctionDef)}
-        assert test.startswith("test_") and test in defined, (kernel, name, test)

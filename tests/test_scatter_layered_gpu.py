@@ -27,9 +27,6 @@ from writer_reference import same_bits
 
 pytestmark = pytest.mark.gpu
 
-# kernel -> (file, test) of the case that takes it past one trip and compares every slot (tests/test_scatter_layered_cpu.py)
-TRIP_CASES = {"k_scatter_layered": ("test_scatter_layered_gpu.py", "test_just_past_the_first_trip_of_the_balanced_grid")}
-
 SIZES = [1, 63, 64, 65, 255, 256, 257, 2047, 2048, 2049]
 SHAPES = [(L, B) for L in (0, 3) for B in (0, 3, 1024)]
 FIELDS = ("r", "v", "dr", "dv")

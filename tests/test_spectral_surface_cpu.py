@@ -1,12 +1,10 @@
 """CPU: SpectralSurfaceStep (light.SpectralSurfaceStep, light._spectral_bounce, pcl_step_ground_spectral) -- the constructor, the numpy
 restatement against a plain loop on a scene that holds every case, the grey ground as the one-band case, the statistics of the
-draws, the host-resident path, the header, the bindings, the build table, the unit's assembly, the trip case and the refusals that
+draws, the host-resident path, the header, the bindings, the build table and the refusals that
 need no device."""
-import ast
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -378,22 +376,8 @@ def test_header_prototypes_and_the_build_table():
     assert hasattr(_hip.Device, "ground_spectral") and hasattr(_hip.DeviceGroup, "ground_spectral")
     from physicl_amd.multidev import MultiDevice
     assert hasattr(MultiDevice, "ground_spectral")
-    # the table: described as every sweep is, in a table of its own that the older functions do not fold in
-    assert list(build.SPECTRAL_SWEEPS) == ["pcl_surface.hip"]
-    (sweep,) = build.SPECTRAL_SWEEPS["pcl_surface.hip"]
-    assert sweep == dict(entries=ENTRIES, kernel="k_ground_spectral", count=2)
-    unit = surface_unit()
-    assert build.every_sweep_of(unit) == build.described_sweeps_of(unit) + (sweep,) and len(build.every_sweep_of(unit)) == 9
-    assert sweep not in build.described_sweeps_of(unit) and sweep not in build.sweeps_of(unit)
-    for other in build.ADDONS:
-        if other is not unit:
-            assert build.every_sweep_of(other) == build.described_sweeps_of(other)
-    every = [s for u in build.ADDONS for s in build.every_sweep_of(u)]
-    entries = [e for s in every for e in s["entries"]]
-    assert len(set(entries)) == len(entries) == 28                     # no entry point belongs to two sweeps
-    assert not any(a is not b and a["kernel"] in b["kernel"] for a in every for b in every)
-    tool = open(os.path.join(os.path.dirname(build.HERE), "tools", "compare_unit_asm.py")).read()
-    assert "every_sweep_of" in tool                                    # the new kernel counts as described
+    # the table: the unit of the writer sweeps holds this one, described as every sweep is (tests/test_build_cpu.py checks it as one)
+    assert dict(entries=ENTRIES, kernel="k_ground_spectral", count=2) in surface_unit()["sweeps"]
 
 
 def test_the_counter_word_is_a_named_constant_used_once():
@@ -436,45 +420,3 @@ def test_refused_calls_need_no_device():
                 keep, args, counts, bands = abi_args(n_bands=B, E_edges=edges, albedo=tabs[0], specular=tabs[1],
                                                      bands=np.full(2 * B + 2, -7, dtype=np.int64))
                 assert lib.pcl_step_ground_spectral(None, *args) == -2, kw
-
-
-def test_library_exports_both_entry_points():
-    build.build_lib()
-    lib = ctypes.CDLL(_hip.LIB_PATH)
-    assert lib.pcl_abi_version() == 1 and all(hasattr(lib, e) for e in ENTRIES)
-
-
-# ------------------------------------------------------------------------------------------------ the kernel
-@pytest.fixture(scope="module")
-def unit_assembly(tmp_path_factory):
-    """The device assembly of the unit that holds the sweep, compiled once with the library's own options."""
-    out = str(tmp_path_factory.mktemp("asm") / "unit.s")
-    subprocess.check_call([build.HIPCC] + [f for f in build.FLAGS if f not in ("-shared", "-fPIC")] +
-                          ["--cuda-device-only", "-S", "-o", out, os.path.join(build.CSRC, "pcl_surface.hip")], stderr=subprocess.DEVNULL)
-    return open(out).read()
-
-
-def test_the_kernel_uses_no_scratch_and_keeps_the_unit_s_budget(unit_assembly):
-    (sweep,) = build.SPECTRAL_SWEEPS["pcl_surface.hip"]
-    kernels = re.findall(r"\.name:\s+(_Z\w*%s\w*)\n(.*?)\.wavefront_size" % sweep["kernel"], unit_assembly, re.S)
-    assert len(kernels) == sweep["count"] == 2, [k for k, _ in kernels]
-    assert sorted(re.search(r"%sI([df])E" % sweep["kernel"], k).group(1) for k, _ in kernels) == ["d", "f"]
-    for kernel, blk in kernels:
-        get = lambda k: int(re.search(r"\.%s:\s+(\d+)" % k, blk).group(1))                              # noqa: E731
-        print(kernel, "vgprs", get("vgpr_count"), "sgprs", get("sgpr_count"))
-        assert get("private_segment_fixed_size") == 0 and get("vgpr_spill_count") == 0, kernel
-        assert get("vgpr_count") <= 80, kernel                         # six waves per SIMD
-
-
-# ------------------------------------------------------------------------------------------------ past the first trip
-def test_the_sweep_has_a_case_past_its_first_trip():
-    """tests/test_writer_trips_cpu.py's check for the table of its own: the kernel's case exists in the file it names."""
-    from test_spectral_surface_gpu import TRIP_CASES
-    assert sorted(TRIP_CASES) == [s["kernel"] for s in build.SPECTRAL_SWEEPS["pcl_surface.hip"]]
-    tests = os.path.dirname(os.path.abspath(__file__))
-    for kernel, (name, test) in TRIP_CASES.items():
-        path = os.path.join(tests, name)
-        assert name.startswith("test_") and os.path.isfile(path), (kernel, name)
-        with open(path) as f:
-            defined = {node.name for node in ast.parse(f.read()).body if isinstance(node, ast.FunctionDef)}
-        assert test.startswith("test_") and test in defined, (kernel, name, test)

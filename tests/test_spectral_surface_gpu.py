@@ -49,8 +49,6 @@ pytestmark = pytest.mark.gpu
 SIZES = [1, 63, 64, 65, 2047, 2048, 2049, 4097]                        # wave and tile edges
 BANDS = [1, 3, 1024]
 ROOM = 300                                                             # capacity beyond N
-# kernel -> (file, test) of the case that takes it past one trip and compares every slot (tests/test_spectral_surface_cpu.py)
-TRIP_CASES = {"k_ground_spectral": ("test_spectral_surface_gpu.py", "test_past_the_first_trip")}
 
 
 @pytest.fixture(scope="module")

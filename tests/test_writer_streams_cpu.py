@@ -1,4 +1,4 @@
-"""CPU: the Philox streams of the writer steps (tally.WriterStep and its ten steps in light.py).
+"""CPU: the Philox streams of the writer steps (tally.WriterStep and its twelve steps in light.py).
 
 Every writer sweep draws from the Philox4x32-10 block with the counter ``(id_lo, id_hi, n_pass, word)`` and the key ``(seed_lo,
 seed_hi)``; ``word`` is a constant per kind of draw.  Three things are held here:
@@ -160,23 +160,79 @@ def test_a_step_without_a_step_list_counts_its_runs():
     assert (loose._pass, loose._n_pass) == (1, 3) and loose._family == (3, 2)            # counted behind those it holds: no counter is shared
 
 
+def twelve():
+    """One step of every writer class of light.py, by a short name, in one order."""
+    L = phys.light
+    return {"ground": L.SurfaceReflectStep(2.0), "spectral": L.SpectralSurfaceStep(2.0, [0.5, 0.5], [1.0, 2.0, 3.0]),
+            "phase": L.PhaseFunctionStep("hg", 0.5), "layered": L.LayeredPhaseStep(["rayleigh"]), "absorb": L.AbsorptionStep(0.5),
+            "glass": L.RefractiveSurfaceStep(2.0, 1.5), "lamp": L.RecycleStep(L.PhotonSource()), "gas": gas(), "cloud": L.LayeredScatterStep(1.0),
+            "grid": L.GridScatterStep(1.0, ("x",), [[-4.0, 0.0, 4.0]]), "box": L.BoxBoundaryStep((-4, -4, -4), (4, 4, 4)),
+            "glow": L.ReemissionStep()}
+
+
+def below(cls):
+    return [c for sub in cls.__subclasses__() for c in [sub] + below(sub)]
+
+
 def test_families_are_the_steps_that_share_a_counter_word():
     L = phys.light
-    src = L.PhotonSource()
-    made = {"ground": L.SurfaceReflectStep(2.0), "spectral": L.SpectralSurfaceStep(2.0, [0.5, 0.5], [1.0, 2.0, 3.0]),
-            "phase": L.PhaseFunctionStep("hg", 0.5), "layered": L.LayeredPhaseStep(["rayleigh"]), "absorb": L.AbsorptionStep(0.5),
-            "glass": L.RefractiveSurfaceStep(2.0, 1.5), "lamp": L.RecycleStep(src), "gas": gas(), "cloud": L.LayeredScatterStep(1.0),
-            "glow": L.ReemissionStep()}
+    made = twelve()
     fam = {k: tally.writer_family(s) for k, s in made.items()}
-    assert fam["ground"] == fam["spectral"] == ("SurfaceReflectStep", "SpectralSurfaceStep")
-    assert fam["phase"] == fam["layered"] == ("PhaseFunctionStep", "LayeredPhaseStep")
-    rest = [k for k in made if k not in ("ground", "spectral", "phase", "layered")]
-    assert all(fam[k] is type(made[k]) for k in rest) and len({fam[k] for k in made}) == 2 + len(rest)
-    assert sorted(type(s).__name__ for s in made.values()) == sorted(c.__name__ for c in tally.WriterStep.__subclasses__())   # all ten
+    assert fam["ground"] == fam["spectral"] and fam["phase"] == fam["layered"]
+    rest = [k for k in made if k not in ("spectral", "layered")]
+    assert len(made) == 12 and len({fam[k] for k in rest}) == len(rest) == 10       # the others pairwise distinct: ten families
+    assert fam["grid"] != fam["cloud"] and fam["box"] != fam["glass"]
+    assert sorted(type(s).__name__ for s in made.values()) == sorted(c.__name__ for c in below(tally.WriterStep) if c.__module__ == light.__name__)
+    assert all("_STREAM" in vars(c) for c in tally.WriterStep.__subclasses__() if c.__module__ == light.__name__)    # stated, not inherited
 
-    class Haze(L.PathAbsorptionStep):                                  # a subclass draws from its parent's words
+    class Haze(L.PathAbsorptionStep):                                  # a subclass draws from its parent's stream
         pass
-    assert tally.writer_family(Haze(0.5)) is L.PathAbsorptionStep
+
+    class Plume(L.GridScatterStep):
+        pass
+    assert tally.writer_family(Haze(0.5)) == fam["gas"] and tally.writer_family(Plume(1.0, ("x",), [[-4.0, 0.0, 4.0]])) == fam["grid"]
+
+
+def test_a_writer_class_that_states_no_stream_is_refused_at_its_first_run():
+    class Nameless(tally.WriterStep):
+        def __init__(self):
+            phys.MeasureStep.__init__(self, None)
+
+        def _host_sweep(self, objs, ids, seed, prep):
+            raise AssertionError("nothing is swept")
+    step = Nameless()
+    assert tally.WriterStep._STREAM is None
+    with pytest.raises(TypeError, match="_STREAM"):
+        step.run(HostSim(a_few(), [step]))
+    assert (step._pass, step._n_pass, step._family) == (0, 0, None)
+
+    class Named(Nameless):
+        _STREAM = "named"
+    assert tally.writer_family(Named()) == "named"
+
+
+# (members of the family in the pass, the step's place among them) behind the first run of two steps of every class in one pass, in
+# the order of twelve() twice: the two grounds share a stream and so do the two phase steps, every other class has its own
+FAMILY_OF = {"ground": [(4, 0), (4, 2)], "spectral": [(4, 1), (4, 3)], "phase": [(4, 0), (4, 2)], "layered": [(4, 1), (4, 3)]}
+# a second ground refuses a spectral one its run, a second phase step a layered one: their place is what the counter rule alone gives
+REFUSED = {"spectral": "a simulation holds one ground", "layered": "a pass holds one phase step"}
+
+
+def test_two_steps_of_every_class_in_one_pass_take_their_places():
+    first, second = twelve(), twelve()
+    order = [(k, j, s) for j, made in enumerate((first, second)) for k, s in made.items()]
+    sim = HostSim(a_few(), [phys.newton.NewtonianKinematicsStep()] + [s for _, _, s in order])
+    for k, j, s in order:
+        if k in REFUSED:
+            with pytest.raises(ValueError, match=REFUSED[k]):
+                s.run(sim)
+            assert (s._pass, s._family) == (0, None)
+            s._next_pass(sim)                                          # what run() does behind the refusal
+        else:
+            s.run(sim)
+    for k, j, s in order:
+        assert s._family == FAMILY_OF.get(k, [(2, 0), (2, 1)])[j], (k, j)
+        assert (s._pass, s._n_pass) == (1, s._family[1] + 1), (k, j)
 
 
 @pytest.mark.parametrize("kind", ["ground", "glass"])

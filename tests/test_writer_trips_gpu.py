@@ -5,7 +5,7 @@ large LDS tables --, so a store of more than ``CAP = compute_units * 8 * 256`` s
 again.  The second trip is the first in which the wave-wide ballots at the head of the body run behind a divergent ``continue``, in
 which a value computed once outside the loop is used a second time, in which a tile index passes ``gridDim * 256``, and -- with a
 third -- in which neighbouring workgroups take different numbers of trips.  ``TRIP_CASES`` names, for every kernel of
-``build.described_sweeps_of``, the test that compares it slot by slot at such a size (tests/test_writer_trips_cpu.py holds the
+``build.ADDONS``, the test that compares it slot by slot at such a size (tests/test_writer_trips_cpu.py holds the
 table against the build's); the seven that had none are in this file.
 
 * the five writers (the ground, the phase function, absorption, the layered phase function, re-emission) through the ``Device`` call,
@@ -56,6 +56,10 @@ TRIP_CASES = {
     "k_absorb_path": ("test_path_absorb_gpu.py", "test_a_workgroup_takes_more_than_one_trip"),
     "k_reemit_parked": (HERE, "test_a_writer_past_one_trip"),
     "k_refract_surface": ("test_writer_refract_gpu.py", "test_past_the_grid_s_first_stride"),
+    "k_ground_spectral": ("test_spectral_surface_gpu.py", "test_past_the_first_trip"),
+    "k_scatter_layered": ("test_scatter_layered_gpu.py", "test_just_past_the_first_trip_of_the_balanced_grid"),
+    "k_scatter_grid": ("test_scatter_grid_trips_gpu.py", "test_both_forms_past_one_trip"),
+    "k_box_walls": ("test_writer_walls_trips_gpu.py", "test_the_walls_past_one_trip"),
 }
 
 ID_BASE = W.ID_BASE                                                    # above 2^32

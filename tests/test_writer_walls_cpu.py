@@ -4,13 +4,10 @@
   for fp64 and for fp32 stored values, every kind of wall alone and mixed, both boxes; what the rule promises of its images
   (periodic in [lo, hi), mirror in [lo, hi] with |v| kept, a single bounce equal to 2w - x to an ulp of L, open parks).
 * every ValueError of the constructor; the host-resident path on Python objects; a second run parks nothing new.
-* the build table, the header's text and the tool; the refusals of the library without a device; the kernels' registers;
-  ``TRIP_CASES`` of tests/test_writer_walls_trips_gpu.py held to the build table.
+* the sweep's element of the build table, the header's text; the refusals of the library without a device.
 """
-import ast
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -160,9 +157,8 @@ def test_constructor_keeps_what_it_was_given():
     import phys.light as short
     cls = light.BoxBoundaryStep
     assert short.BoxBoundaryStep is cls is phys.light.BoxBoundaryStep
-    assert issubclass(cls, tally.WriterStep) and issubclass(cls, light.RefractiveSurfaceStep) and cls not in tally.WriterStep.__subclasses__()
-    assert not set(vars(cls)) & {"run", "_device_run", "_reduce"} and len(tally.WriterStep.__subclasses__()) == 10
-    assert tally.writer_family(step) is cls and tally.writer_family(light.RefractiveSurfaceStep(1.0, 1.33)) is light.RefractiveSurfaceStep
+    assert cls.__mro__[1] is tally.WriterStep and not set(vars(cls)) & {"run", "_device_run", "_reduce"}
+    assert tally.writer_family(step) == cls._STREAM != tally.writer_family(light.RefractiveSurfaceStep(1.0, 1.33)) and "_STREAM" in vars(cls)
     assert "one launch per light step" in cls._NOTE and "BoxBoundaryStep" in cls._NOTE and cls._NOTE != light.RefractiveSurfaceStep._NOTE
     assert cls.terminate is tally.TallyStep.terminate and "image positions" in " ".join(cls.__doc__.split())
     assert _hip.WALL_MODES == MODE_CODES
@@ -339,23 +335,8 @@ def test_header_prototypes_and_the_build_table():
     assert hasattr(_hip.Device, "box_walls") and hasattr(_hip.DeviceGroup, "box_walls")
     from physicl_amd.multidev import MultiDevice
     assert hasattr(MultiDevice, "box_walls")
-    # the table: described as every sweep is, in a table of its own that the older functions do not fold in
-    assert list(build.BOUNDARY_SWEEPS) == ["pcl_surface.hip"]
-    (sweep,) = build.BOUNDARY_SWEEPS["pcl_surface.hip"]
-    assert sweep == dict(entries=ENTRIES, kernel="k_box_walls", count=2)
-    unit = surface_unit()
-    assert build.boundary_sweeps_of(unit) == build.volume_sweeps_of(unit) + (sweep,) and len(build.boundary_sweeps_of(unit)) == 12
-    assert len(build.volume_sweeps_of(unit)) == 11 and len(build.all_sweeps_of(unit)) == 10 and sweep not in build.volume_sweeps_of(unit)
-    assert len(build.ADDONS) == 5 and [os.path.basename(u["src"]) for u in build.ADDONS][-1] == "pcl_surface.hip"
-    for other in build.ADDONS:
-        if other is not unit:
-            assert build.boundary_sweeps_of(other) == build.volume_sweeps_of(other)
-    every = [s for u in build.ADDONS for s in build.boundary_sweeps_of(u)]
-    entries = [e for s in every for e in s["entries"]]
-    assert len(set(entries)) == len(entries) == 34                     # no entry point belongs to two sweeps
-    assert not any(a is not b and a["kernel"] in b["kernel"] for a in every for b in every)
-    tool = open(os.path.join(os.path.dirname(build.HERE), "tools", "compare_unit_asm.py")).read()
-    assert "boundary_sweeps_of(u)" in tool and "volume_sweeps_of" in tool and "all_sweeps_of" in tool and "every_sweep_of" in tool
+    # the table: the unit of the writer sweeps holds this one last, described as every sweep is (tests/test_build_cpu.py checks it as one)
+    assert surface_unit()["sweeps"][-1] == dict(entries=ENTRIES, kernel="k_box_walls", count=2)
     assert build.csrc_sha() == "b54e0443ee3f400f"                       # the tuned core has not moved
     src = open(os.path.join(build.CSRC, "pcl_surface.hip")).read()
     body = src[src.index("void __launch_bounds__(kBlock) k_box_walls"):src.index("struct walls_spec")]
@@ -376,38 +357,3 @@ def test_refused_calls_need_no_device():
         assert (lib.pcl_group_step_box_walls(None, *args) == -2) or kw in GOOD_CALLS, kw
         assert lib.pcl_group_step_box_walls(None, *args) != 0, kw
         assert counts is None or (counts == -7).all(), kw
-
-
-@pytest.fixture(scope="module")
-def unit_assembly(tmp_path_factory):
-    """The device assembly of the unit that holds the sweep, compiled once with the library's own options."""
-    out = str(tmp_path_factory.mktemp("asm") / "unit.s")
-    subprocess.check_call([build.HIPCC] + [f for f in build.FLAGS if f not in ("-shared", "-fPIC")] +
-                          ["--cuda-device-only", "-S", "-o", out, os.path.join(build.CSRC, "pcl_surface.hip")], stderr=subprocess.DEVNULL)
-    return open(out).read()
-
-
-def test_the_two_kernels_use_no_scratch_and_keep_the_unit_s_budget(unit_assembly):
-    (sweep,) = build.BOUNDARY_SWEEPS["pcl_surface.hip"]
-    kernels = re.findall(r"\.name:\s+(_Z\w*%s\w*)\n(.*?)\.wavefront_size" % sweep["kernel"], unit_assembly, re.S)
-    assert len(kernels) == sweep["count"] == 2, [k for k, _ in kernels]
-    assert sorted(re.search(r"%sI([df])E" % sweep["kernel"], k).group(1) for k, _ in kernels) == ["d", "f"]
-    for kernel, blk in kernels:
-        get = lambda k: int(re.search(r"\.%s:\s+(\d+)" % k, blk).group(1))                              # noqa: E731
-        print(kernel, "vgprs", get("vgpr_count"), "sgprs", get("sgpr_count"), "sgpr spills", get("sgpr_spill_count"))
-        assert get("private_segment_fixed_size") == 0 and get("vgpr_spill_count") == 0, kernel
-        assert get("vgpr_count") <= 64, kernel                         # eight waves per SIMD
-
-
-# ------------------------------------------------------------------------------------------------ past the first trip
-def test_the_sweep_has_a_case_past_its_first_trip():
-    """tests/test_writer_trips_cpu.py's check for the table of its own: the kernel's case exists in the file it names."""
-    from test_writer_walls_trips_gpu import TRIP_CASES
-    assert sorted(TRIP_CASES) == [s["kernel"] for s in build.BOUNDARY_SWEEPS["pcl_surface.hip"]]
-    tests = os.path.dirname(os.path.abspath(__file__))
-    for kernel, (name, test) in TRIP_CASES.items():
-        path = os.path.join(tests, name)
-        assert name.startswith("test_") and os.path.isfile(path), (kernel, name)
-        with open(path) as f:
-            defined = {node.name for node in ast.parse(f.read()).body if isinstance(node, ast.FunctionDef)}
-        assert test.startswith("test_") and test in defined, (kernel, name, test)

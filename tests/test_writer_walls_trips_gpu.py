@@ -25,9 +25,6 @@ from test_writer_trips_gpu import has_work, slots
 
 pytestmark = pytest.mark.gpu
 
-# kernel -> (file, test) of the case that takes it past one trip and compares every slot (tests/test_writer_walls_cpu.py)
-TRIP_CASES = {"k_box_walls": ("test_writer_walls_trips_gpu.py", "test_the_walls_past_one_trip")}
-
 
 @pytest.fixture(scope="module")
 def hip():
