@@ -738,8 +738,15 @@ int pcl_step_surface_reflect(pcl_ctx *ctx, double radius, const double *center_h
  *   block A: u_a = u53(w0, w1), u_b = u53(w2, w3);  mu, the cosine of the scattering angle:
  *   PCL_PHASE_ISOTROPIC:  mu = 1 - 2*u_a                        (uniform on the sphere: the law of PCL_SRC_ISOTROPIC)
  *   PCL_PHASE_HG:         Henyey-Greenstein, |g| < 1 its mean cosine;  g == 0: the isotropic line, bit for bit;  otherwise
- *                         q = (1 - g*g) / ((1 - g) + (2*g)*u_a);  mu = min(max(((1 + g*g) - q*q) / (2*g), -1), 1)
- *                         (for tiny |g| the numerator is a difference of the order g: mu is good to about ulp(1)/|g|; harmless)
+ *                         |g| >= 1/2, the closed inverse of the cumulative distribution:
+ *                           q = (1 - g*g) / ((1 - g) + (2*g)*u_a);  m = ((1 + g*g) - q*q) / (2*g)
+ *                         |g| < 1/2, the same inverse as a polynomial in g (the closed form subtracts two numbers near 1 and
+ *                         divides by 2g: it loses ulp(1)/|g|, and below |g| = 1e-16 every digit):
+ *                           s = 1 - 2*u_a;  gs = g*s;  d = 1 - gs;  s2 = s*s
+ *                           p = (0.5*(s2 + 3) - gs) + (g*g)*(0.5*(s2 - 1));  m = (g*p - s) / (d*d)
+ *                         mu = min(max(m, -1), 1).  Against exact arithmetic mu is good to 8 ulp(1) for |g| < 1/2, down to the
+ *                         smallest g, and to 32 ulp(1)/(1 - |g|) above (q's denominator).  As g -> 0 the law tends to
+ *                         mu = -(1 - 2*u_a), while g == 0 gives +(1 - 2*u_a): both are uniform on the sphere.
  *   PCL_PHASE_RAYLEIGH:   3/8 (1 + mu*mu) as the mixture of 3/4 uniform and 1/4 of the density 3/2 mu*mu:
  *                         s4 = u_a*4;  j = floor(s4);  f = s4 - j (both exact);  gq = 2*f - 1;   j < 3: mu = gq;
  *                         j == 3: block B: u_c = u53(w0, w1), u_d = u53(w2, w3);  mu = copysign(max(max(|gq|, u_c), u_d), gq)

@@ -45,8 +45,8 @@
 // Operation order (what light._phase_redirect restates with numpy):
 //   scattered iff a photon and (dv0 != 0 or dv1 != 0 or dv2 != 0);  o_k = v_k - dv_k;  oo = o.o;  go on iff 0 < oo < inf
 //   on = sqrt(oo);  w_k = o_k / on;  block A = counter (id_lo, id_hi, pass, 10): u_a, u_b
-//   mu by the law (law_mu; include/physicl_hip.h writes the lines out): isotropic 1 - 2*u_a;  hg by the closed inverse, g == 0 the
-//   isotropic line (for tiny |g| mu is good to about ulp(1)/|g| -- harmless, the law is flat to first order in g there);  rayleigh
+//   mu by the law (law_mu; include/physicl_hip.h writes the lines out): isotropic 1 - 2*u_a;  hg by the closed inverse for |g| >= 1/2
+//   and by the same inverse written as a polynomial in g below it (good to 8 ulp(1) down to the smallest g), g == 0 the isotropic line;  rayleigh
 //   3/4 uniform + 1/4 (3/2 mu^2): one lane in four takes the largest of three uniforms, block B = counter (id_lo, id_hi, pass, 11)
 //   sc, ss = polar(mu, u_b);  e1, e2 = frame(w);  dir_k = (sc*e1_k + ss*e2_k) + mu*w_k;  v_k = c*dir_k;  dv_k = v_k - o_k
 //
@@ -386,9 +386,17 @@ __global__ void __launch_bounds__(kBlock) k_phase_redirect(phase_args<T> a) {
         pair_u53(pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, 10u, a.k0, a.k1), &u_a, &u_b);
         double mu = __dsub_rn(1.0, __dmul_rn(2.0, u_a));                                             // uniform on the sphere
         if (a.phase == PCL_PHASE_HG && a.g != 0.0) {
-            const double gg = __dmul_rn(a.g, a.g), g2 = __dmul_rn(2.0, a.g);
-            const double q = __ddiv_rn(__dsub_rn(1.0, gg), __dadd_rn(__dsub_rn(1.0, a.g), __dmul_rn(g2, u_a)));
-            mu = fmin(fmax(__ddiv_rn(__dsub_rn(__dadd_rn(1.0, gg), __dmul_rn(q, q)), g2), -1.0), 1.0);
+            const double gg = __dmul_rn(a.g, a.g);
+            if (fabs(a.g) < 0.5) {                                      // the inverse as a polynomial in g: no difference of ones
+                const double s = mu, gs = __dmul_rn(a.g, s), d = __dsub_rn(1.0, gs), s2 = __dmul_rn(s, s);
+                const double p = __dadd_rn(__dsub_rn(__dmul_rn(0.5, __dadd_rn(s2, 3.0)), gs), __dmul_rn(gg, __dmul_rn(0.5, __dsub_rn(s2, 1.0))));
+                mu = __ddiv_rn(__dsub_rn(__dmul_rn(a.g, p), s), __dmul_rn(d, d));
+            } else {                                                    // the closed inverse
+                const double g2 = __dmul_rn(2.0, a.g);
+                const double q = __ddiv_rn(__dsub_rn(1.0, gg), __dadd_rn(__dsub_rn(1.0, a.g), __dmul_rn(g2, u_a)));
+                mu = __ddiv_rn(__dsub_rn(__dadd_rn(1.0, gg), __dmul_rn(q, q)), g2);
+            }
+            mu = fmin(fmax(mu, -1.0), 1.0);
         } else if (a.phase == PCL_PHASE_RAYLEIGH) {
             const double s4 = __dmul_rn(u_a, 4.0), j = floor(s4);
             const double gq = __dsub_rn(__dmul_rn(2.0, __dsub_rn(s4, j)), 1.0);
@@ -591,9 +599,17 @@ __global__ void __launch_bounds__(kBlock) k_phase_layered(lphase_args<T> a) {
         const double g = s_g[j];
         double mu = __dsub_rn(1.0, __dmul_rn(2.0, u_a));                                             // uniform on the sphere
         if (law == PCL_PHASE_HG && g != 0.0) {                                 // law_mu, written out in both phase kernels
-            const double gg = __dmul_rn(g, g), g2 = __dmul_rn(2.0, g);
-            const double q = __ddiv_rn(__dsub_rn(1.0, gg), __dadd_rn(__dsub_rn(1.0, g), __dmul_rn(g2, u_a)));
-            mu = fmin(fmax(__ddiv_rn(__dsub_rn(__dadd_rn(1.0, gg), __dmul_rn(q, q)), g2), -1.0), 1.0);
+            const double gg = __dmul_rn(g, g);
+            if (fabs(g) < 0.5) {                                        // the inverse as a polynomial in g: no difference of ones
+                const double s = mu, gs = __dmul_rn(g, s), d = __dsub_rn(1.0, gs), s2 = __dmul_rn(s, s);
+                const double p = __dadd_rn(__dsub_rn(__dmul_rn(0.5, __dadd_rn(s2, 3.0)), gs), __dmul_rn(gg, __dmul_rn(0.5, __dsub_rn(s2, 1.0))));
+                mu = __ddiv_rn(__dsub_rn(__dmul_rn(g, p), s), __dmul_rn(d, d));
+            } else {                                                    // the closed inverse
+                const double g2 = __dmul_rn(2.0, g);
+                const double q = __ddiv_rn(__dsub_rn(1.0, gg), __dadd_rn(__dsub_rn(1.0, g), __dmul_rn(g2, u_a)));
+                mu = __ddiv_rn(__dsub_rn(__dadd_rn(1.0, gg), __dmul_rn(q, q)), g2);
+            }
+            mu = fmin(fmax(mu, -1.0), 1.0);
         } else if (law == PCL_PHASE_RAYLEIGH) {
             const double s4 = __dmul_rn(u_a, 4.0), jq = floor(s4);
             const double gq = __dsub_rn(__dmul_rn(2.0, __dsub_rn(s4, jq)), 1.0);

@@ -10,7 +10,7 @@ from phase_reference import C, SEED, cloud as phase_cloud, unit
 from physicl_amd import light
 
 assert C == 299792458.0 and SEED == 0x5EED5A7F
-SINGLE = ["isotropic", ("hg", 0.85), ("hg", -0.5), "rayleigh"]      # the laws PhaseFunctionStep has
+SINGLE = ["isotropic", ("hg", 0.85), ("hg", -0.5), "rayleigh", ("hg", 1e-12), ("hg", -1e-300)]      # the laws PhaseFunctionStep has
 AS_PHASE = {"isotropic": ("isotropic", 0.0), "rayleigh": ("rayleigh", 0.0)}
 MIX_LAWS = ("rayleigh", ("hg", 0.85))
 MIX_WEIGHTS = [[1, 0], [0.3, 0.7], [0, 1]]                          # three layers: molecular, a mixture, a cloud

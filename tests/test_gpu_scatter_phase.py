@@ -30,7 +30,7 @@ pytestmark = pytest.mark.gpu
 
 assert (DIR_OPS, DIR_ULP) == (8, 8.0)
 SIZES = [1, 63, 64, 65, 255, 256, 257, 2047, 2048, 2049, 4097]
-LAWS = [("isotropic", 0.0), ("hg", 0.85), ("hg", -0.5), ("rayleigh", 0.0)]
+LAWS = [("isotropic", 0.0), ("hg", 0.85), ("hg", -0.5), ("rayleigh", 0.0), ("hg", 1e-12), ("hg", -1e-300)]
 FIELDS = ("r", "v", "dr", "dv")
 ID_BASE = 7_000_000_001
 

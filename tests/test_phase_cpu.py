@@ -89,7 +89,7 @@ def test_isotropic_is_uniform_on_the_sphere():
     assert near((mu > 0.5).mean(), 0.25, 0.25 * 0.75, n)
 
 
-@pytest.mark.parametrize("g", [-0.5, 0.3, 0.85])
+@pytest.mark.parametrize("g", [-0.5, 0.3, 0.85, -1e-17])
 def test_henyey_greenstein_has_the_mean_cosine_g(g):
     (v, dv), o = redirect("hg", g)
     mu, n = check_geometry(v, dv, o)
@@ -97,7 +97,9 @@ def test_henyey_greenstein_has_the_mean_cosine_g(g):
     assert np.all(np.abs(mu) <= 1) and near(mu.mean(), g, second - g * g, n), mu.mean()
     assert near((mu * mu).mean(), second, 1.0, n)                      # (a variance bound: mu^2 lies in [0, 1])
     # the cumulative distribution at mu = 0:  P(mu <= 0) = (1 - g*g)/(2g) * (1/sqrt(1 + g*g) - 1/(1 + g))
-    below = (1 - g * g) / (2 * g) * (1 / np.sqrt(1 + g * g) - 1 / (1 + g))
+    # (with the difference worked out, (1 + g) - sqrt(1 + g*g) = 2g / ((1 + g) + sqrt(1 + g*g)): the line above is 0/0 at a tiny g)
+    root = np.sqrt(1 + g * g)
+    below = (1 - g) / (root * ((1 + g) + root))
     assert near((mu <= 0).mean(), below, below * (1 - below), n)
 
 
@@ -150,7 +152,7 @@ def test_degenerate_rows_are_left_alone_and_not_counted():
 
 def test_fp32_rows_are_the_fp64_results_rounded_once():
     state = cloud(N, dtype=np.float32)
-    for phase, g in (("hg", 0.85), ("rayleigh", 0.0)):
+    for phase, g in (("hg", 0.85), ("rayleigh", 0.0), ("hg", 1e-12), ("hg", -1e-300)):
         _, o64 = redirect(phase, g, state=state)
         _, o32 = redirect(phase, g, state=state, dtype=np.float32)
         assert o64["redirected"].sum() == len(range(0, N, 3))
