@@ -4,7 +4,7 @@ examples (n(r) = 2.5e25 m^-3 * exp(-(|r| - 6371 km) / 8.6 km)) with photons that
 
     python examples/point_source_atmosphere.py [n_photons] [passes] [--cone | --beam-down | --default] [--profile] [--shells]
                                                [--ground [ALBEDO]] [--phase rayleigh | hg:G | isotropic] [--omega0 W | W1,W2,...]
-                                               [--cloud LO,HI[,G]] [--cloud-tau TAU] [--cloud-field NX,NY,NZ:EXTENT:TAU] [--box periodic | mirror | open] [--recycle [TOP]] [--gas LO,HI,K[,EMIN,EMAX]] [--blue-sky]
+                                               [--cloud LO,HI[,G]] [--cloud-tau TAU] [--cloud-field NX,NY,NZ:EXTENT:TAU] [--cloud-phase G] [--box periodic | mirror | open] [--recycle [TOP]] [--gas LO,HI,K[,EMIN,EMAX]] [--blue-sky]
                                                [--reemit [TG[,TA]]] [--ocean N] [--ground-bands E1,E2,...:a1,a2,...[:s1,...]]
                                                [--camera X,Y,Z:NX,NY,NZ:RADIUS:FOV_DEG:PIXELS]
 
@@ -45,6 +45,11 @@ NZ-index add up to an even number -- a vertical path through a cloudy column has
 stands behind the clear air's scatter step (``first`` resolves to False) and in front of the phase step.  ``exposed``, ``scattered`` and
 the column sums of ``scattered_by_cell`` over the passes are printed; with ``--camera`` looking down from above the box, e.g.
 ``--cloud-field 8,8,8:40000:4 --camera 6421000,0,0:-1,0,0:20000:60:32``, the image shows the gaps.  One launch per light step.
+``--cloud-phase G`` (with ``--cloud-field``) gives the field's droplets their phase function: a GridPhaseStep on the field's cells in
+the place of the phase function turns a photon scattered in a cloudy cell by a mixture of one part Rayleigh and nine parts
+Henyey-Greenstein with the mean cosine G, and one scattered in a clear cell or anywhere outside the box (``outside``) by Rayleigh's law.
+``by_mixture`` [clear, cloudy] and ``by_law`` [rayleigh, hg] summed over the passes are printed.  Not together with ``--phase`` or
+``--cloud``: a pass holds one phase step.
 ``--box periodic | mirror | open`` (with ``--cloud-field``) gives the scene sides: a BoxBoundaryStep around the cloud field's box on its
 two horizontal axes y and z (x, the vertical, has no wall), last in the pass, behind the ground and in front of a re-emission or the
 recycling lamp.  ``periodic`` hands a photon that leaves the field sideways back in on the other side -- the boundary condition
@@ -157,6 +162,15 @@ if "--cloud-field" in argv:
             raise ValueError
     except ValueError:
         sys.exit("--cloud-field NX,NY,NZ:EXTENT:TAU: the cells of the box, its width in metres and the optical thickness of a cloudy column")
+cloud_phase = None
+if "--cloud-phase" in argv:
+    at = argv.index("--cloud-phase")
+    try:
+        cloud_phase = float(argv.pop(at + 1))
+    except (IndexError, ValueError):
+        cloud_phase = 2.0
+    if cloud_field is None or cloud is not None or phase is not None or not abs(cloud_phase) < 1.0:
+        sys.exit("--cloud-phase G: the droplets' mean cosine, |G| < 1, together with --cloud-field NX,NY,NZ:EXTENT:TAU and without --phase or --cloud")
 box = None
 if "--box" in argv:
     at = argv.index("--box")
@@ -265,6 +279,9 @@ def run(ground):
                                        [R + np.linspace(0.25, 0.75, nx + 1) * extent, np.linspace(-0.5, 0.5, ny + 1) * extent,
                                         np.linspace(-0.5, 0.5, nz + 1) * extent])
         sim.add_step("cloud_field", broken)
+        if cloud_phase is not None:                            # the field's cells again: the droplets' forward peak where it is cloudy
+            angles = light.GridPhaseStep(["rayleigh", ("hg", cloud_phase)], [[1.0, 0.0], CLOUD_WEIGHTS[1]], broken.axes, broken.edges,
+                                         mixture=(broken.k > 0).astype(np.int64), outside=0)
     if cloud is not None:                                      # from the Earth's centre to 1000 km up: Rayleigh, but for the cloud
         angles = light.LayeredPhaseStep(["rayleigh", ("hg", cloud[2])], CLOUD_WEIGHTS, edges=[0.0, R + cloud[0], R + cloud[1], R + 1000e3])
     if angles is not None:                                     # directly behind the scatter step (steps run in the order they were added)
@@ -356,6 +373,11 @@ if cloud is not None:
         print("  the cloud's own optical thickness %g (k = %g per m, first=%s): %d photons exposed, %d scattered over %d passes; scattered_by_cell %s" % (
             cloud_tau, droplets.k[0, 0], droplets.first, sum(int(row[1]) for row in droplets.data), sum(int(row[2]) for row in droplets.data),
             len(droplets.data), np.sum([row[3] for row in droplets.data], axis=0).tolist()))
+elif cloud_phase is not None:
+    by_mixture, by_law = (np.sum([row[k] for row in angles.data], axis=0) for k in (3, 4))
+    print("cloud field's phase functions (cloudy cells: 0.1 rayleigh + 0.9 hg, g = %g; clear cells and outside: rayleigh): %d photons scattered, "
+          "%d re-directed over %d passes" % (cloud_phase, sum(int(row[1]) for row in angles.data), sum(int(row[2]) for row in angles.data), len(angles.data)))
+    print("  by_mixture [clear, cloudy]: %s   by_law [rayleigh, hg]: %s" % (by_mixture.tolist(), by_law.tolist()))
 elif angles is not None:
     print("phase function %s (g = %g): %d photons re-directed over %d passes" % (angles.phase, angles.g, sum(int(row[1]) for row in angles.data), len(angles.data)))
 if broken is not None:

@@ -1263,6 +1263,77 @@ int pcl_step_scatter_grid(pcl_ctx *ctx, int n_axes, const int *coords_host, cons
 int pcl_step_box_walls(pcl_ctx *ctx, const int *modes_host /* [3] */, const double *lo_host /* [3] */, const double *hi_host /* [3] */,
                        int64_t *counts_out_host /* [8]: moving, multi, crossed[3][2] */);
 
+/* Phase functions by grid cell (GridPhaseStep): pcl_step_phase_layered with pcl_step_position_grid's cells in place of the radial
+ * layers -- droplets' forward peak in the cloudy cells of a broken cloud field, Rayleigh in the clear air between and around them.
+ * Called where pcl_step_phase_layered would be called (directly behind the scatter step of a pass, before or behind
+ * pcl_step_absorb_scattered), it re-directs the photons that step scattered in ONE sweep of the resident store.  The n_laws = M laws
+ * are mixed in n_mixtures = K rows of cumulative weights, the MIXTURES; every cell of the grid names one of them, or none.  A pass
+ * holds ONE phase step: this entry point shares the blocks 10, 11 and 13 with pcl_step_phase_redirect and pcl_step_phase_layered and
+ * must not be called in a pass in which one of the three has already been called with the same ``pass``.  Nothing is removed; r, dr,
+ * E, ids and kinds are not written, E is not asked for and of r only the rows some axis needs.  All arithmetic is fp64, unfused, every
+ * operation rounded once, in the order written; an fp32 store's values are widened first (exact) and what is written is rounded once
+ * to the store's dtype.  G = the product of n_bins_host.
+ *   scattered  iff  the particle is a photon, (dv0 != 0 or dv1 != 0 or dv2 != 0), and o = v - dv has 0 < o.o < inf, o.o = (o0*o0 +
+ *                   o1*o1) + o2*o2                                                    (pcl_step_phase_layered's "scattered")
+ *   cell g:         pcl_step_position_grid's lines, character for character -- per axis the bin with e_b <= x < e_(b+1), the last one
+ *                   closed;  a PCL_GRID_RADIUS axis bins q = ((x-cx)*(x-cx) + (y-cy)*(y-cy)) + (z-cz)*(z-cz) against the squared
+ *                   edges, no square root is taken;  a NaN, a position outside any axis's range: in no cell;  cells are row-major in
+ *                   the order of the axes.  Only the rows of r some axis needs are read, and only of scattered photons.
+ *   mixture m:      in a cell:  mixture_host[g], a row of cum_host, or PCL_PHASE_GRID_ALONE: none.   in no cell:  ``outside``, a row of
+ *                   cum_host, or -1: none.
+ *   m = none:       counted as scattered, not written: the photon keeps the direction the scatter step gave it
+ *   otherwise:      re-directed.  The law: M == 1: j = 0;  otherwise j = the first law with u_s < cum_host[m*M + j], u_s = u53(w0, w1)
+ *                   of the block (id_lo, id_hi, pass, 13).  (Whether that block is computed for a row that is one-hot is the
+ *                   kernel's business: the first positive entry of such a row is 1 and 0 <= u_s < 1.)
+ *   block A (id_lo, id_hi, pass, 10): u_a = u53(w0, w1), u_b = u53(w2, w3);  mu by the law's kind:
+ *     PCL_PHASE_ISOTROPIC:  mu = 1 - 2*u_a
+ *     PCL_PHASE_HG with g = g_host[j]:  g == 0: the isotropic line.   |g| >= 1/2:  gg = g*g;  g2 = 2*g;
+ *       q = (1 - gg) / ((1 - g) + g2*u_a);  mu = ((1 + gg) - q*q) / g2.   0 < |g| < 1/2:  s = 1 - 2*u_a;  gs = g*s;  d = 1 - gs;
+ *       s2 = s*s;  p = (0.5*(s2 + 3) - gs) + gg*(0.5*(s2 - 1));  mu = (g*p - s) / (d*d).   Both:  mu = min(max(mu, -1), 1)
+ *     PCL_PHASE_RAYLEIGH:  s4 = u_a*4;  jq = floor(s4);  gq = 2*(s4 - jq) - 1;  jq != 3: mu = gq;  jq == 3: block B (id_lo, id_hi,
+ *       pass, 11): mu = copysign(max(max(|gq|, u53(w0, w1)), u53(w2, w3)), gq)
+ *     PCL_PHASE_TABLE:  k = the bin of u_a in F ([F_k, F_(k+1)), always inside);  s_k = (mu_(k+1) - mu_k) / (F_(k+1) - F_k), made by the
+ *       library on the host;  mu = min(max(mu_k + (u_a - F_k)*s_k, mu_k), mu_(k+1))
+ *     -- pcl_step_phase_redirect's and pcl_step_phase_layered's lines, bit for bit
+ *   then  on = sqrt(o.o);  w = o / on;  s = sqrt((1 - mu)*(1 + mu));  psi = (u_b*2)*pi;  sc = s*cos psi;  ss = s*sin psi;  e1, e2 = the
+ *   frame of Duff et al. about w (pcl_step_surface_reflect writes it out);  dir = (sc*e1 + ss*e2) + mu*w;  v = c*dir;  dv = v - o.
+ * So two calls are bit for bit, store and tallies, what an older entry point leaves:  one PCL_GRID_RADIUS axis with the edges e,
+ * mixture_host[b] = b and outside = -1 is pcl_step_phase_layered with n_layers = L, cum_host and edges_host = e;  one cell, one law and
+ * outside = 0 is pcl_step_phase_redirect with that law.  No new counter word is taken: the words in use are the scatter kernels' 0 and
+ * 1, fill and source 2..5, pcl_step_surface_reflect and pcl_step_ground_spectral 8 and 9, pcl_step_phase_redirect 10 and 11,
+ * pcl_step_absorb_scattered 12, pcl_step_phase_layered 10, 11 and 13, pcl_step_phase_grid (this call) 10, 11 and 13,
+ * pcl_step_recycle_spent 14, 15 and 16, pcl_step_absorb_path 17, pcl_step_reemit_parked 18, 19 and 20, pcl_step_refract_surface 21,
+ * pcl_step_ground_spectral 22, pcl_step_scatter_layered 23 and 24, pcl_step_scatter_grid 25 and 26: 0-5 and 8-26 are taken.
+ * n_laws, kinds_host, g_host, law_bins_host (pcl_step_phase_layered's n_bins_host), mu_host, F_host: as for pcl_step_phase_layered.
+ * cum_host: K rows of M cumulative weights, 1 <= K <= PCL_PHASE_GRID_MAX_MIXTURES, each row as pcl_step_phase_layered's.  n_axes,
+ * coords_host, n_bins_host, edges_host, center_host: as for pcl_step_position_grid, G <= PCL_PHASE_GRID_MAX_CELLS.  mixture_host: G
+ * bytes, row-major in the order of the axes, each below K or PCL_PHASE_GRID_ALONE.  outside: -1 .. K - 1.  ``c``: the speed of light
+ * in code units.
+ * The mixture map goes up with every call (G bytes, at most 1 MiB) and stays in device memory: a scattered photon reads one byte of
+ * it.  Everything else sits in LDS, and with E = the sum of n_bins_host[a] + 1 over the axes and T = the nodes of all tables (the sum
+ * of law_bins_host[j] + 1 over the PCL_PHASE_TABLE laws) a call is accepted only if
+ *     8 * (K*M + E + M + 3*T + (3*M + 1)/2)  +  4 * (2 + K + M)  <=  PCL_PHASE_GRID_LDS_BYTES           ((3*M + 1)/2 rounded down)
+ * -- the 64 KiB a launch may ask for.  The largest law tables (T = 2056: 49 344 B) and the largest edge tables (E = 2052: 16 416 B)
+ * together do not fit; either fits with a small other.  A call is sized by what it uses.
+ * counts_out_host[0] = photons scattered, [1] = re-directed, [2 + m] = re-directed by mixture m, [2 + K + j] = re-directed by law j.
+ * A store that is not uniform costs the host traffic it costs pcl_step_surface_reflect.
+ * PCL_ERR_ARG (everything pcl_step_phase_layered refuses of the laws, the rows of weights, the centre and c, everything
+ * pcl_step_position_grid refuses of the geometry, K or outside beyond their limits, a byte of the map that is neither a row nor
+ * PCL_PHASE_GRID_ALONE, tables beyond the LDS bound, a NULL kinds, cum, coords, n_bins, edges, mixture or counts pointer) is
+ * returned before the store is looked at -- by the group's entry point before the group is --, and nothing is launched or written;
+ * PCL_ERR_STATE without a store; an empty store answers zeros without a launch.  Host pointers; one device allocation per call,
+ * handed back on every way out; synchronises once, with the copy of the tallies.  pcl_last_error() is generic, as for
+ * pcl_step_surface_reflect, whose source file these two entry points share. */
+#define PCL_PHASE_GRID_MAX_MIXTURES 64
+#define PCL_PHASE_GRID_MAX_CELLS (1 << 20) /* G: PCL_GRID_MAX_CELLS */
+#define PCL_PHASE_GRID_ALONE 255           /* a byte of mixture_host: a scattered photon in this cell is left alone */
+#define PCL_PHASE_GRID_LDS_BYTES 65536
+int pcl_step_phase_grid(pcl_ctx *ctx, int n_laws, const int *kinds_host, const double *g_host, const int *law_bins_host,
+                        const double *mu_host, const double *F_host, int n_mixtures, const double *cum_host, int n_axes,
+                        const int *coords_host, const int *n_bins_host, const double *edges_host, const double *center_host,
+                        const unsigned char *mixture_host /* [G] */, int outside, double c, uint64_t seed, uint32_t pass,
+                        int64_t *counts_out_host /* [2 + K + M] */);
+
 /* ---- Device groups: several GPUs from ONE process ---------------------------------------------------------------
  * The reference is a single process with one simulation thread (physicl/__init__.py:400-432, 501-524); this is how
  * a host written against this ABI uses a node's GPUs the same way, without one process per GPU.  A group owns one
@@ -1387,6 +1458,13 @@ int pcl_group_step_scatter_grid(pcl_group *group, int n_axes, const int *coords_
  * for the group, before the group is looked at (the rule reads no id: a photon meets the same wall however the run is sharded) */
 int pcl_group_step_box_walls(pcl_group *group, const int *modes_host, const double *lo_host, const double *hi_host,
                              int64_t *counts_out_host);
+/* pcl_step_phase_grid on every shard (side by side), the tallies summed over the group's devices; the arguments are checked once for
+ * the group, before the group is looked at (ids are global: the same photons are turned the same way).  Every shard stages the map */
+int pcl_group_step_phase_grid(pcl_group *group, int n_laws, const int *kinds_host, const double *g_host, const int *law_bins_host,
+                              const double *mu_host, const double *F_host, int n_mixtures, const double *cum_host, int n_axes,
+                              const int *coords_host, const int *n_bins_host, const double *edges_host, const double *center_host,
+                              const unsigned char *mixture_host, int outside, double c, uint64_t seed, uint32_t pass,
+                              int64_t *counts_out_host);
 
 /* ---------------------------------------------------------------- the counters' collective (one process per GPU)
  * The path shards by global index with no data-path exchange; the only global quantities are the int64

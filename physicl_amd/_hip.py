@@ -39,6 +39,7 @@ REEMIT_MAX_LAYERS, REEMIT_MAX_BINS, REEMIT_MAX_TOTAL_BINS = 64, 1024, 2048      
 SPECTRAL_MAX_BANDS = 1024                                                    # PCL_SPECTRAL_MAX_BANDS: bands of a SpectralSurfaceStep
 SCATTER_LAYERED_MAX_LAYERS, SCATTER_LAYERED_MAX_BANDS, SCATTER_LAYERED_MAX_CELLS = 64, 1024, 4096       # PCL_SCATTER_LAYERED_MAX_LAYERS ...
 SCATTER_GRID_MAX_BANDS, SCATTER_GRID_MAX_CELLS = 1024, 1 << 20                # PCL_SCATTER_GRID_MAX_BANDS, PCL_SCATTER_GRID_MAX_CELLS
+PHASE_GRID_MAX_MIXTURES, PHASE_GRID_MAX_CELLS, PHASE_GRID_ALONE, PHASE_GRID_LDS_BYTES = 64, 1 << 20, 255, 65536   # PCL_PHASE_GRID_MAX_MIXTURES ...
 WALL_MODES = {None: 0, "periodic": 1, "mirror": 2, "open": 3}               # PCL_WALL_NONE, PCL_WALL_PERIODIC, PCL_WALL_MIRROR, PCL_WALL_OPEN
 REEMIT_LAWS = {"isotropic": 0, "lambertian": 1}                              # the flags of pcl_step_reemit_parked's lambertian_host
 PROF_NEWTON, PROF_SCATTER, PROF_DELETE_MASK, PROF_COMPACT, PROF_COUNTERS, PROF_FUSED, PROF_MULTI, PROF_ONEPASS, \
@@ -175,6 +176,7 @@ _PROTOTYPES = {
     "pcl_step_scatter_layered": [_vp, c_int, c_int, _vp, _vp, _vp, _vp, c_int, c_double, c_uint64, c_uint32, _vp, _vp],
     "pcl_step_scatter_grid": [_vp, c_int, _vp, _vp, _vp, _vp, c_int, _vp, _vp, c_int, c_double, c_uint64, c_uint32, _vp, _vp],
     "pcl_step_box_walls": [_vp, _vp, _vp, _vp, _vp],
+    "pcl_step_phase_grid": [_vp, c_int, _vp, _vp, _vp, _vp, _vp, c_int, _vp, c_int, _vp, _vp, _vp, _vp, _vp, c_int, c_double, c_uint64, c_uint32, _vp],
     # device groups: several GPUs from one process (the C-level counterpart of physicl_amd.multidev.MultiDevice)
     "pcl_group_create": [c_int, POINTER(c_int), POINTER(_vp)],
     "pcl_group_destroy": [_vp],
@@ -214,6 +216,8 @@ _PROTOTYPES = {
     "pcl_group_step_scatter_layered": [_vp, c_int, c_int, _vp, _vp, _vp, _vp, c_int, c_double, c_uint64, c_uint32, _vp, _vp],
     "pcl_group_step_scatter_grid": [_vp, c_int, _vp, _vp, _vp, _vp, c_int, _vp, _vp, c_int, c_double, c_uint64, c_uint32, _vp, _vp],
     "pcl_group_step_box_walls": [_vp, _vp, _vp, _vp, _vp],
+    "pcl_group_step_phase_grid": [_vp, c_int, _vp, _vp, _vp, _vp, _vp, c_int, _vp, c_int, _vp, _vp, _vp, _vp, _vp, c_int, c_double, c_uint64,
+                                  c_uint32, _vp],
 }
 EXPORTS = sorted(list(_PROTOTYPES) + ["pcl_last_error"])
 
@@ -424,6 +428,22 @@ def _absorb(entry, handle, omega0, edges, center, E_edges, seed, n_pass):
     return int(counts[0]), int(counts[1]), counts[2:].copy(), hist
 
 
+def _law_arrays(laws):
+    """(kinds int32[M], g float64[M], n_bins int32[M], mu, F) of a sequence of ``(kind, g, mu, F)`` laws as pcl_step_phase_layered and
+    pcl_step_phase_grid take them: the tables' nodes and cumulative values one behind the other (None without a table)."""
+    kinds = np.array([int(PHASE_TABLE if k == "table" else PHASE_FUNCTIONS.get(k, k)) for k, _, _, _ in laws], dtype=np.int32)
+    g = np.array([float(x) for _, x, _, _ in laws], dtype=np.float64)
+    tabs = [(np.ascontiguousarray(m, dtype=np.float64).reshape(-1), np.ascontiguousarray(f, dtype=np.float64).reshape(-1))
+            for _, _, m, f in laws if m is not None]
+    if any(len(m) != len(f) for m, f in tabs):
+        raise ValueError("a table's mu and F must hold the same number of nodes")
+    n_bins = np.zeros(len(laws), dtype=np.int32)
+    n_bins[[j for j, law in enumerate(laws) if law[2] is not None]] = [len(m) - 1 for m, _ in tabs]
+    mu = np.concatenate([m for m, _ in tabs]) if tabs else None
+    F = np.concatenate([f for _, f in tabs]) if tabs else None
+    return kinds, g, n_bins, mu, F
+
+
 def _phase_layered(entry, handle, laws, cum, edges, center, c, seed, n_pass):
     """One call of pcl_step_phase_layered / pcl_group_step_phase_layered: (scattered, redirected, by_layer int64[L'], by_law
     int64[M]).  ``laws``: a sequence of ``(kind, g, mu, F)`` -- kind "isotropic", "hg", "rayleigh", "table" or the header's numbers,
@@ -431,16 +451,7 @@ def _phase_layered(entry, handle, laws, cum, edges, center, c, seed, n_pass):
     of M per layer; the edges go over as given (the library squares them, and makes the tables' slopes); ``n_pass``: the caller's
     own pass counter (a Philox counter word)."""
     M = len(laws)
-    kinds = np.array([int(PHASE_TABLE if k == "table" else PHASE_FUNCTIONS.get(k, k)) for k, _, _, _ in laws], dtype=np.int32)
-    g = np.array([float(x) for _, x, _, _ in laws], dtype=np.float64)
-    tabs = [(np.ascontiguousarray(m, dtype=np.float64).reshape(-1), np.ascontiguousarray(f, dtype=np.float64).reshape(-1))
-            for _, _, m, f in laws if m is not None]
-    if any(len(m) != len(f) for m, f in tabs):
-        raise ValueError("a table's mu and F must hold the same number of nodes")
-    n_bins = np.zeros(M, dtype=np.int32)
-    n_bins[[j for j, law in enumerate(laws) if law[2] is not None]] = [len(m) - 1 for m, _ in tabs]
-    mu = np.concatenate([m for m, _ in tabs]) if tabs else None
-    F = np.concatenate([f for _, f in tabs]) if tabs else None
+    kinds, g, n_bins, mu, F = _law_arrays(laws)
     ed = None if edges is None else np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
     L = 0 if ed is None else len(ed) - 1
     rows = max(L, 1)
@@ -630,6 +641,47 @@ def _box_walls(entry, handle, modes, lo, hi):
     counts = np.zeros(8, dtype=np.int64)
     check(entry(handle, md.ctypes.data, lo.ctypes.data, hi.ctypes.data, counts.ctypes.data))
     return counts
+
+
+def phase_grid_lds_bytes(n_mixtures, n_laws, n_edges, n_nodes):
+    """The LDS a pcl_step_phase_grid call asks for, by the header's formula: K mixtures of M laws, E edges over all axes, T nodes over
+    all tables.  At most ``PHASE_GRID_LDS_BYTES``."""
+    K, M = int(n_mixtures), int(n_laws)
+    return 8 * (K * M + int(n_edges) + M + 3 * int(n_nodes) + (3 * M + 1) // 2) + 4 * (2 + K + M)
+
+
+def _phase_grid(entry, handle, laws, cum, axes, edges, center, mixture, outside, c, seed, n_pass):
+    """One call of pcl_step_phase_grid / pcl_group_step_phase_grid: (scattered, redirected, by_mixture int64[K], by_law int64[M]).
+    ``laws``: as for ``_phase_layered``; ``cum``: the cumulative weights, one row of M per mixture; ``axes``, ``edges``, ``center``: as
+    for ``_grid`` (the library squares the edges of a radius axis); ``mixture``: one integer per cell, row-major in the order of
+    ``axes`` (any shape of that size) -- a row of ``cum``, or -1 (``PHASE_GRID_ALONE`` as the byte that goes over) for a cell whose
+    photons are left alone; ``outside``: the row of a scattered photon in no cell, None for none; ``n_pass``: the caller's own pass
+    counter (a Philox counter word).  The map goes up with every call, one byte a cell."""
+    M = len(laws)
+    kinds, g, n_tab, mu, F = _law_arrays(laws)
+    cu = np.ascontiguousarray(cum, dtype=np.float64).reshape(-1)
+    if M < 1 or len(cu) % M or not len(cu):
+        raise ValueError("cum holds %d values for mixtures of %d laws" % (len(cu), M))
+    K = len(cu) // M
+    coords = np.array([GRID_COORDS.get(a, a) for a in axes], dtype=np.int32)
+    per_axis = [np.ascontiguousarray(e, dtype=np.float64).reshape(-1) for e in edges]
+    if len(per_axis) != len(coords):
+        raise ValueError("one sequence of edges per axis: %d axes, %d sequences" % (len(coords), len(per_axis)))
+    n_bins = np.array([len(e) - 1 for e in per_axis], dtype=np.int32)
+    ed = np.ascontiguousarray(np.concatenate(per_axis)) if per_axis else np.zeros(0)
+    mx = np.asarray(mixture).reshape(-1)
+    if len(mx) != int(np.prod([max(int(b), 0) for b in n_bins])):
+        raise ValueError("mixture holds %d values for a grid of shape %r" % (len(mx), tuple(int(b) for b in n_bins)))
+    if not np.all((mx >= -1) & (mx < PHASE_GRID_ALONE)):
+        raise ValueError("mixture must hold rows of cum or -1")
+    mp = np.ascontiguousarray(np.where(mx < 0, PHASE_GRID_ALONE, mx), dtype=np.uint8)
+    ce = None if center is None else np.ascontiguousarray(center, dtype=np.float64).reshape(3)
+    counts = np.zeros(2 + K + M, dtype=np.int64)
+    ptr = lambda a: None if a is None else a.ctypes.data                                                       # noqa: E731
+    check(entry(handle, M, kinds.ctypes.data, g.ctypes.data, n_tab.ctypes.data, ptr(mu), ptr(F), K, cu.ctypes.data, len(coords),
+                coords.ctypes.data, n_bins.ctypes.data, ed.ctypes.data, ptr(ce), mp.ctypes.data, -1 if outside is None else int(outside),
+                float(c), int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_pass) & 0xFFFFFFFF, counts.ctypes.data))
+    return int(counts[0]), int(counts[1]), counts[2:2 + K].copy(), counts[2 + K:].copy()
 
 
 def _scatter(sc, required=False, lazy=False, empty_expr=b""):
@@ -1272,6 +1324,15 @@ class Device:
         ``(exposed, scattered, scattered_by_cell int64 of the grid's shape (+ bands))``.  ``n_pass``: the caller's own pass counter."""
         return _scatter_grid(self.lib.pcl_step_scatter_grid, self.ctx, p, axes, edges, center, E_edges, first, c, seed, n_pass)
 
+    def phase_grid(self, laws, cum, axes, edges, center=None, mixture=None, outside=None, c=0.0, seed=0, n_pass=0):
+        """The phase functions by grid cell: the photons the scatter step of this pass has hit get a direction drawn about their old
+        one from a law chosen by the mixture of their cell -- ``mixture[cell]``, a row of the cumulative weights ``cum``, -1: left
+        alone; ``outside``: the row of a photon in no cell, None: left alone; ``mixture=None``: row 0 everywhere
+        (pcl_step_phase_grid).  ``(scattered, redirected, by_mixture int64[K], by_law int64[M])`` of this call."""
+        if mixture is None:
+            mixture = np.zeros([len(np.reshape(e, -1)) - 1 for e in edges], dtype=np.int64)
+        return _phase_grid(self.lib.pcl_step_phase_grid, self.ctx, laws, cum, axes, edges, center, mixture, outside, c, seed, n_pass)
+
     def box_walls(self, modes, lo, hi):
         """The walls of the box ``[lo, hi]``, per axis ``"periodic"``, ``"mirror"``, ``"open"`` or None: every moving photon outside on
         an axis with a wall is handed back in through the other side, folded back at the wall (an odd number of bounces turns ``v``,
@@ -1426,6 +1487,12 @@ class DeviceGroup:
     def scatter_grid(self, p, axes, edges, center=None, E_edges=None, first=True, c=0.0, seed=0, n_pass=0):
         """``Device.scatter_grid`` on every context of the group, the tallies summed (pcl_group_step_scatter_grid)."""
         return _scatter_grid(self.lib.pcl_group_step_scatter_grid, self.g, p, axes, edges, center, E_edges, first, c, seed, n_pass)
+
+    def phase_grid(self, laws, cum, axes, edges, center=None, mixture=None, outside=None, c=0.0, seed=0, n_pass=0):
+        """``Device.phase_grid`` on every context of the group, the tallies summed (pcl_group_step_phase_grid)."""
+        if mixture is None:
+            mixture = np.zeros([len(np.reshape(e, -1)) - 1 for e in edges], dtype=np.int64)
+        return _phase_grid(self.lib.pcl_group_step_phase_grid, self.g, laws, cum, axes, edges, center, mixture, outside, c, seed, n_pass)
 
     def box_walls(self, modes, lo, hi):
         """``Device.box_walls`` on every context of the group, the counts summed (pcl_group_step_box_walls)."""

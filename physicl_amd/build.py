@@ -63,6 +63,11 @@ ADDONS = [
         _sweep("pcl_step_box_walls", "pcl_group_step_box_walls", "k_box_walls"))),
 ]
 UNITS = [CORE] + ADDONS
+# Sweeps added to a unit since: a row has a sweep's shape plus ``src``, the unit that holds it (no new translation unit: the unit's row
+# above compiles and links it).  tests/test_build_later_cpu.py checks every row as tests/test_build_cpu.py checks a sweep of ADDONS.
+LATER = [
+    dict(_sweep("pcl_step_phase_grid", "pcl_group_step_phase_grid", "k_phase_grid"), src=_c("pcl_surface.hip")),
+]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -ffp-contract=off: the reference's kernels must be evaluated unfused (bit-exact parity)

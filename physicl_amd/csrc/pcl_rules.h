@@ -57,6 +57,38 @@ __device__ __forceinline__ double turned(double sc, double ss, double mu, double
     return __dadd_rn(__dadd_rn(__dmul_rn(sc, e1), __dmul_rn(ss, e2)), __dmul_rn(mu, axis));
 }
 
+// law_mu for the closed-form laws: the cosine of the scattering angle of PCL_PHASE_ISOTROPIC, PCL_PHASE_HG (g) and PCL_PHASE_RAYLEIGH
+// from u_a, in the lines include/physicl_hip.h writes out for pcl_step_phase_redirect -- Henyey-Greenstein by the closed inverse for
+// |g| >= 1/2 and by the same inverse as a polynomial in g below it (no difference of ones), g == 0 the isotropic line; Rayleigh's
+// 3/2 mu^2 part (one lane in four) draws the block (id_lo, id_hi, pass, 11).  A tabulated law, and any other kind, gets the isotropic
+// line: its caller overwrites it.  k_phase_grid calls it; k_phase_redirect and k_phase_layered keep these lines written out (the call
+// changes them).
+__device__ __forceinline__ double law_mu(int law, double g, double u_a, uint64_t id, uint32_t pass, uint32_t k0, uint32_t k1) {
+    double mu = __dsub_rn(1.0, __dmul_rn(2.0, u_a));                    // uniform on the sphere
+    if (law == PCL_PHASE_HG && g != 0.0) {
+        const double gg = __dmul_rn(g, g);
+        if (fabs(g) < 0.5) {
+            const double s = mu, gs = __dmul_rn(g, s), d = __dsub_rn(1.0, gs), s2 = __dmul_rn(s, s);
+            const double p = __dadd_rn(__dsub_rn(__dmul_rn(0.5, __dadd_rn(s2, 3.0)), gs), __dmul_rn(gg, __dmul_rn(0.5, __dsub_rn(s2, 1.0))));
+            mu = __ddiv_rn(__dsub_rn(__dmul_rn(g, p), s), __dmul_rn(d, d));
+        } else {
+            const double g2 = __dmul_rn(2.0, g);
+            const double q = __ddiv_rn(__dsub_rn(1.0, gg), __dadd_rn(__dsub_rn(1.0, g), __dmul_rn(g2, u_a)));
+            mu = __ddiv_rn(__dsub_rn(__dadd_rn(1.0, gg), __dmul_rn(q, q)), g2);
+        }
+        mu = fmin(fmax(mu, -1.0), 1.0);
+    } else if (law == PCL_PHASE_RAYLEIGH) {
+        const double s4 = __dmul_rn(u_a, 4.0), jq = floor(s4);
+        const double gq = __dsub_rn(__dmul_rn(2.0, __dsub_rn(s4, jq)), 1.0);
+        mu = gq;
+        if (jq == 3.0) {
+            const pcl_u32x4 wb = pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), pass, 11u, k0, k1);
+            mu = copysign(fmax(fmax(fabs(gq), pcl_u53(wb.x, wb.y)), pcl_u53(wb.z, wb.w)), gq);
+        }
+    }
+    return mu;
+}
+
 } // namespace pcl_rules
 
 #endif // PCL_RULES_H

@@ -230,6 +230,24 @@
 //   moving: k_absorb_path's line;  below = x < lo;  above = x >= hi (periodic), x > hi (mirror, open);  open: park, first open axis counted;
 //   s = x - lo;  n = floor(s / L);  f = min(max(s - n*L, 0), L);  periodic: y = lo + f, not (y < hi): y = lo;
 //   mirror: h = n*0.5;  odd = floor(h) != h;  y = min(max(odd ? hi - f : lo + f, lo), hi);  odd: v_a, dv_a, dr_a negated
+//
+// Phase functions by grid cell (GridPhaseStep): how a scattered photon is turned, decided by the cell of k_position_grid's grid it
+// stands in -- cloud droplets' forward peak in the cloudy columns, Rayleigh in the clear air beside them.  k_phase_layered's rule with
+// the grid's cell in place of the radial layer: a cell names a MIXTURE, one of up to 64 rows of cumulative weights over the laws.
+//
+//   k_phase_grid<T>        k_phase_layered's grid-stride sweep of the three dv rows; a scattered lane loads v and the r rows some axis
+//                          needs and is looked up axis by axis in the edges (LDS; k_position_grid's lines).  A lane with a cell reads
+//                          ONE byte of the mixture map -- device memory, at most 1 MiB, L2-resident over a sweep; 255: left alone --,
+//                          a lane in no cell takes the call's ``outside`` row (-1: left alone).  Then k_phase_layered's law draw, cosine
+//                          (law_mu of pcl_rules.h for the closed-form laws, the table written out) and turn.  The tables (cumulative
+//                          weights, edges, g, and mu, F and the slopes of the tabulated laws) sit in dynamic LDS in front of the
+//                          workgroup-private uint32 cells [scattered, re-directed | by mixture | by law]; the whole stays within 64 KiB
+//                          (the header states the bound; the largest law tables and the largest edge tables together do not fit).
+//
+// Operation order (what light_grid._grid_phase_redirect restates with numpy):
+//   scattered: k_phase_layered's line;  cell: k_position_grid's lines;  m = map[cell], or ``outside`` in no cell;  m = none: counted as
+//   scattered, not written;  otherwise law j = the first with u_s < C[m][j] (counter word 13), mu by the law (words 10 and 11) and the
+//   turn about o/|o|: k_phase_layered's lines
 #include "pcl_sweep.h"
 
 #include "pcl_device.h" // (after the HIP runtime and the ABI's header, which pcl_sweep.h brings)
@@ -501,7 +519,7 @@ __global__ void __launch_bounds__(kBlock) k_absorb_scattered(absorb_args<T> a) {
         if (s_cnt[k]) atomicAdd(&a.out[k], (unsigned long long)s_cnt[k]);
 }
 
-// The counter word of the draw that chooses a law (the header lists who uses which word: 13 is this kernel's alone).
+// The counter word of the draw that chooses a law (the header lists who uses which word: 13 is this kernel's and k_phase_grid's).
 constexpr uint32_t kLawWord = 13;
 
 template <typename T>
@@ -2614,6 +2632,266 @@ int group_box_walls(pcl_group *group, const int *modes_host, const double *lo_ho
     });
 }
 
+// ---- phase functions by grid cell: the kernel stands with its host side, at the end of the unit, as the scattering on a grid does
+// What a launch may ask for of LDS: the tables, the edges and the cells of a call stay within it (the header states the bound).
+constexpr size_t kGridPhaseLdsBytes = PCL_PHASE_GRID_LDS_BYTES;
+constexpr unsigned kGridPhaseAlone = PCL_PHASE_GRID_ALONE;              // a cell's byte of the map: left alone
+static_assert(PCL_PHASE_GRID_MAX_MIXTURES < PCL_PHASE_GRID_ALONE && PCL_PHASE_GRID_ALONE <= 255, "a mixture and the mark fit one byte of the map");
+static_assert(PCL_PHASE_GRID_MAX_CELLS == PCL_GRID_MAX_CELLS, "the mixtures' grid is the position grid's");
+
+template <typename T>
+struct gphase_args {
+    const T *r[3];               // rows some axis needs (NULL otherwise)
+    T *v[3], *dv[3];
+    const unsigned char *kind;   // NULL: every particle is a photon
+    const int64_t *ids;          // NULL: the id of slot i is id_base + i
+    const double *tables;        // C (K x M) | the axes' edges one after another (a radius axis: squared) | g (M) | mu, F, s (n_nodes each) | the laws' ints
+    const unsigned char *map;    // one byte per cell of the grid: its row of C, kGridPhaseAlone: left alone; device, read by scattered lanes only
+    unsigned long long *out;     // scattered, re-directed | by mixture [K] | by law [M]; device, zeroed by the entry point
+    int64_t N, ts, id_base;      // particles, tile stride of the slab (elements), id of slot 0
+    int tile_log;                // log2 of the tile length
+    int n_mix, n_laws;           // K, M
+    int n_nodes;                 // the nodes of all tables, bins + 1 each (0 without a table)
+    int n_axes, n_edges;         // axes of the grid, every edge of the axes
+    int coord[PCL_GRID_MAX_AXES], n_bins[PCL_GRID_MAX_AXES], edge_at[PCL_GRID_MAX_AXES];
+    int rows;                    // bit k: row k of r is read
+    int outside;                 // the row of C of a scattered photon in no cell; -1: left alone
+    double c[3], speed;
+    uint32_t k0, k1, pass;       // Philox key (seed_lo, seed_hi), the step's own pass counter
+};
+
+template <typename T>
+__global__ void __launch_bounds__(kBlock) k_phase_grid(gphase_args<T> a) {
+    extern __shared__ double s_mem[];                                  // tables | scattered, re-directed | by mixture | by law
+    const int K = a.n_mix, M = a.n_laws, Tn = a.n_nodes;
+    const int n_dbl = K * M + a.n_edges + M + 3 * Tn;
+    const int n_tab = n_dbl + (3 * M + 1) / 2;                         // three ints per law, packed behind the doubles
+    const int n_cells = 2 + K + M;
+    const double *s_C = s_mem;
+    const double *s_edges = s_C + K * M;
+    const double *s_g = s_edges + a.n_edges;
+    const double *s_mu = s_g + M;
+    const double *s_F = s_mu + Tn;
+    const double *s_s = s_F + Tn;
+    const int *s_kind = reinterpret_cast<const int *>(s_mem + n_dbl);  // PCL_PHASE_* of law j
+    const int *s_off = s_kind + M;                                     // a table's first node in mu, F and s
+    const int *s_K = s_off + M;                                        // a table's bins
+    uint32_t *s_cnt = reinterpret_cast<uint32_t *>(s_mem + n_tab);
+    uint32_t *s_mix = s_cnt + 2;
+    uint32_t *s_law = s_mix + K;
+    for (int k = threadIdx.x; k < n_tab; k += kBlock) s_mem[k] = a.tables[k];
+    for (int k = threadIdx.x; k < n_cells; k += kBlock) s_cnt[k] = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int64_t stride = grid_stride(), n_round = whole_waves(a.N);   // (the ballots below need whole waves inside the loop)
+    for (int64_t i = first_slot(); i < n_round; i += stride) {
+        const bool in = i < a.N;
+        const int64_t ti = tile_index(i, a.tile_log, a.ts);
+        double d[3] = {0.0, 0.0, 0.0}, o[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            if (in) d[k] = (double)a.dv[k][ti];                         // fp32 widens exactly
+        // scattered in this pass: k_phase_layered's lines (scattered and workable)
+        bool go = in && (d[0] != 0.0 || d[1] != 0.0 || d[2] != 0.0);
+        if (go && a.kind) go = a.kind[i] != 0;
+        if (go) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) o[k] = __dsub_rn((double)a.v[k][ti], d[k]);      // the velocity before the scatter
+        }
+        const double oo = dot3(o, o);
+        go = go && oo > 0.0 && oo < INFINITY;
+        int b = -1;                                                     // the row of C; -1: left as the scatter step left it
+        if (go) {
+            double x[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                if ((a.rows >> k) & 1) x[k] = (double)a.r[k][ti];       // fp32 widens exactly
+            bool ok = true;
+            int at = 0;
+            for (int ax = 0; ax < a.n_axes; ++ax) {                     // k_position_grid's lines
+                const int co = a.coord[ax], nb = a.n_bins[ax];
+                const double *e = s_edges + a.edge_at[ax];
+                double q;
+                if (co == PCL_GRID_RADIUS) {   // q, unfused, in this order (the library is built with -ffp-contract=off)
+                    const double dx = x[0] - a.c[0], dy = x[1] - a.c[1], dz = x[2] - a.c[2];
+                    q = (dx * dx + dy * dy) + dz * dz;
+                } else {
+                    q = co == 0 ? x[0] : (co == 1 ? x[1] : x[2]);
+                }
+                ok = ok && q >= e[0] && q <= e[nb];                     // NaN and anything outside the axis's range are in no cell
+                at = at * nb + bin_of(e, nb, q);
+            }
+            if (ok) {                                                   // (at is below the grid's cells: every bin is inside its axis)
+                const unsigned m = a.map[at];                           // one byte, L2-resident over a sweep
+                b = m == kGridPhaseAlone ? -1 : (int)m;
+            } else {
+                b = a.outside;
+            }
+        }
+        const bool turn = b >= 0;
+        const uint32_t n_go = (uint32_t)__popcll(__ballot(go)), n_turn = (uint32_t)__popcll(__ballot(turn));
+        if (lane == 0 && n_go) atomicAdd(&s_cnt[0], n_go);
+        if (lane == 0 && n_turn) {
+            atomicAdd(&s_cnt[1], n_turn);
+            if (K == 1) atomicAdd(&s_mix[0], n_turn);                   // one mixture, one law: the wave's count, not a lane's
+            if (M == 1) atomicAdd(&s_law[0], n_turn);
+        }
+        if (!turn) continue;    // lanes that are left alone wait at the loop's head: no ballot below this line
+        const uint64_t id = id_of(a.ids, a.id_base, i);
+        int j = 0;
+        if (M > 1) {
+            const double *row = s_C + b * M;                            // cumulative, ends in 1: the first j with u_s < row[j]
+            while (j < M - 1 && !(row[j] > 0.0)) ++j;                   // (u_s >= 0: a law without weight is never the first)
+            if (row[j] < 1.0) {                                         // a one-hot row draws nothing
+                const double u_s = first_u53(pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, kLawWord, a.k0, a.k1));
+                while (j < M - 1 && !(u_s < row[j])) ++j;
+            }
+            atomicAdd(&s_law[j], 1u);
+        }
+        if (K > 1) atomicAdd(&s_mix[b], 1u);
+        const double on = __dsqrt_rn(oo);
+        double w[3], sc, ss, e1[3], e2[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) w[k] = __ddiv_rn(o[k], on);
+        double u_a, u_b;
+        pair_u53(pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, 10u, a.k0, a.k1), &u_a, &u_b);
+        const int law = s_kind[j];
+        double mu = law_mu(law, s_g[j], u_a, id, a.pass, a.k0, a.k1);
+        if (law == PCL_PHASE_TABLE) {                                   // the inverse of a piecewise linear F: 0 <= u_a < 1 is inside
+            const int off = s_off[j];
+            const int kb = off + bin_of(s_F + off, s_K[j], u_a);
+            const double lo = s_mu[kb], hi = s_mu[kb + 1];
+            mu = fmin(fmax(__dadd_rn(lo, __dmul_rn(__dsub_rn(u_a, s_F[kb]), s_s[kb])), lo), hi);
+        }
+        polar(mu, u_b, &sc, &ss);
+        frame(w, e1, e2);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double vk = __dmul_rn(a.speed, turned(sc, ss, mu, e1[k], e2[k], w[k]));
+            a.v[k][ti] = (T)vk;
+            a.dv[k][ti] = (T)__dsub_rn(vk, o[k]);
+        }
+    }
+    __syncthreads();
+    // pcl_sweep::flush_cells, written out, for the reason given in k_absorb_scattered: a further caller changes the older kernels
+    for (int k = threadIdx.x; k < n_cells; k += kBlock)
+        if (s_cnt[k]) atomicAdd(&a.out[k], (unsigned long long)s_cnt[k]);
+}
+
+struct gphase_spec { // a call's arguments, checked; what the kernel reads
+    lphase_spec laws;           // the laws and the rows of C by check_lphase (n_layers = 0: no edges of its own); its tables are taken over
+    int n_mix = 0, n_axes = 0, n_edges = 0, rows = 0, outside = -1;
+    int64_t n_grid = 1;         // cells of the grid
+    int coord[PCL_GRID_MAX_AXES], n_bins[PCL_GRID_MAX_AXES], edge_at[PCL_GRID_MAX_AXES];
+    std::vector<double> tables; // C | the axes' edges (a radius axis: squared) | g | mu | F | s | the laws' ints || the map, eight cells a double
+    size_t n_lds = 0;           // the doubles in front of the map: what a workgroup copies into LDS
+    size_t cells() const { return (size_t)2 + (size_t)n_mix + (size_t)laws.n_laws; }
+    size_t lds() const { return n_lds * sizeof(double) + cells() * sizeof(uint32_t); }
+};
+
+// Everything PCL_ERR_ARG stands for except the NULL context; nothing is launched or written before this has passed.  The laws by
+// check_lphase (one row of C at a time), the geometry by check_gscatter's lines.
+bool check_gphase(int n_laws, const int *kinds, const double *g, const int *law_bins, const double *mu, const double *F, int n_mix,
+                  const double *cum, int n_axes, const int *coords, const int *n_bins, const double *edges, const double *center,
+                  const unsigned char *map, int outside, double c, const int64_t *counts_out, gphase_spec &s) {
+    if (!kinds || !cum || !coords || !n_bins || !edges || !map || !counts_out) return false;
+    if (n_laws < 1 || n_laws > PCL_LPHASE_MAX_LAWS || n_mix < 1 || n_mix > PCL_PHASE_GRID_MAX_MIXTURES) return false;
+    if (n_axes < 1 || n_axes > PCL_GRID_MAX_AXES || outside < -1 || outside >= n_mix) return false;
+    const int M = n_laws;
+    std::vector<double> rows_of_C;
+    for (int m = 0; m < n_mix; ++m) {                                   // check_lphase takes one row without layers: K calls' rows, the last call's laws
+        s.laws = lphase_spec();
+        if (!check_lphase(n_laws, kinds, g, law_bins, mu, F, 0, cum + (size_t)m * M, nullptr, center, c, counts_out, s.laws)) return false;
+        rows_of_C.insert(rows_of_C.end(), s.laws.tables.begin(), s.laws.tables.begin() + M);
+    }
+    s.n_mix = n_mix; s.n_axes = n_axes; s.outside = outside;
+    int seen = 0;
+    for (int a = 0; a < n_axes; ++a) {
+        if (coords[a] < PCL_GRID_X || coords[a] > PCL_GRID_RADIUS || ((seen >> coords[a]) & 1)) return false;
+        seen |= 1 << coords[a];
+        if (n_bins[a] < 1 || n_bins[a] > PCL_GRID_MAX_BINS) return false;
+        s.n_grid *= n_bins[a];
+    }
+    if (s.n_grid > PCL_PHASE_GRID_MAX_CELLS) return false;
+    s.tables = rows_of_C;
+    for (int a = 0; a < n_axes; ++a) {
+        s.coord[a] = coords[a];
+        s.n_bins[a] = n_bins[a];
+        s.edge_at[a] = s.n_edges;
+        s.rows |= coords[a] == PCL_GRID_RADIUS ? 7 : 1 << coords[a];
+        // q of a radius axis is compared against e*e: no square root anywhere
+        if (!check_edges(edges + s.n_edges, n_bins[a], coords[a] == PCL_GRID_RADIUS ? kEdgeSquare : kEdgePlain, &s.tables)) return false;
+        s.n_edges += n_bins[a] + 1;
+    }
+    s.tables.insert(s.tables.end(), s.laws.tables.begin() + M, s.laws.tables.end());     // g | mu | F | s | the laws' ints
+    s.n_lds = s.tables.size();
+    if (s.lds() > kGridPhaseLdsBytes) return false;                     // the header's bound
+    for (int64_t k = 0; k < s.n_grid; ++k)
+        if (map[k] >= n_mix && map[k] != kGridPhaseAlone) return false;
+    s.tables.resize(s.n_lds + ((size_t)s.n_grid + 7) / 8, 0.0);
+    memcpy(s.tables.data() + s.n_lds, map, (size_t)s.n_grid);
+    return true;
+}
+
+template <typename T>
+int launch_gphase(pcl_ctx *ctx, const store_view &v, const gphase_spec &s, uint64_t seed, uint32_t pass, const staged &st) {
+    gphase_args<T> a{};
+    for (int k = 0; k < 3; ++k) {
+        void *r = nullptr, *vel = nullptr, *dv = nullptr;
+        if ((s.rows >> k) & 1) PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_R0 + k, &r));
+        PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_V0 + k, &vel));
+        PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_DV0 + k, &dv));
+        a.r[k] = static_cast<const T *>(r); a.v[k] = static_cast<T *>(vel); a.dv[k] = static_cast<T *>(dv);
+        a.c[k] = s.laws.c[k];
+    }
+    a.kind = st.kind; a.ids = st.ids; a.tables = st.tables; a.out = st.out;
+    a.map = reinterpret_cast<const unsigned char *>(st.tables + s.n_lds);
+    a.N = v.N; a.ts = v.ts; a.id_base = st.id_base; a.tile_log = v.tile_log;
+    a.n_mix = s.n_mix; a.n_laws = s.laws.n_laws; a.n_nodes = s.laws.n_nodes; a.n_axes = s.n_axes; a.n_edges = s.n_edges;
+    for (int k = 0; k < s.n_axes; ++k) { a.coord[k] = s.coord[k]; a.n_bins[k] = s.n_bins[k]; a.edge_at[k] = s.edge_at[k]; }
+    a.rows = s.rows; a.outside = s.outside; a.speed = s.laws.speed;
+    a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32); a.pass = pass;
+    const size_t lds = s.lds();                                         // what this call uses
+    const int64_t grid = balanced_grid(v.N, v.n_cu, resident_per_cu(lds));
+    hipLaunchKernelGGL(k_phase_grid<T>, dim3((unsigned)grid), dim3(kBlock), lds, v.stream, a);
+    return hipGetLastError() == hipSuccess ? PCL_OK : PCL_ERR_HIP;
+}
+
+int phase_grid(pcl_ctx *ctx, int n_laws, const int *kinds, const double *g, const int *law_bins, const double *mu, const double *F,
+               int n_mix, const double *cum, int n_axes, const int *coords, const int *n_bins, const double *edges, const double *center,
+               const unsigned char *map, int outside, double c, uint64_t seed, uint32_t pass, int64_t *counts_out_host) {
+    gphase_spec s;
+    if (!ctx || !check_gphase(n_laws, kinds, g, law_bins, mu, F, n_mix, cum, n_axes, coords, n_bins, edges, center, map, outside, c,
+                              counts_out_host, s))
+        return bad_argument(ctx);
+    const spans out = {{counts_out_host, s.cells()}};
+    store_view v;                                                       // E is never asked for, as in phase_layered
+    staged st(ctx);
+    PCL_SWEEP_TRY(open_store(ctx, PCL_DV0, &v));
+    zero_spans(out);
+    if (v.N <= 0) return PCL_OK;
+    PCL_SWEEP_TRY(stage(st, v, s.cells(), s.tables.data(), s.tables.size(), true));
+    PCL_SWEEP_TRY(PCL_SWEEP_LAUNCH(v, launch_gphase, ctx, v, s, seed, pass, st));
+    return fetch(st, out);
+}
+
+int group_phase_grid(pcl_group *group, int n_laws, const int *kinds, const double *g, const int *law_bins, const double *mu,
+                     const double *F, int n_mix, const double *cum, int n_axes, const int *coords, const int *n_bins, const double *edges,
+                     const double *center, const unsigned char *map, int outside, double c, uint64_t seed, uint32_t pass,
+                     int64_t *counts_out_host) {
+    gphase_spec s;                                                      // the arguments first: a refused call looks at no group
+    if (!check_gphase(n_laws, kinds, g, law_bins, mu, F, n_mix, cum, n_axes, coords, n_bins, edges, center, map, outside, c,
+                      counts_out_host, s))
+        return bad_argument(nullptr);
+    std::vector<pcl_ctx *> ctx;
+    PCL_SWEEP_TRY(shards_of(group, ctx));
+    if (ctx.empty()) return bad_argument(nullptr);
+    return sum_shards(ctx, {{counts_out_host, s.cells()}}, [&](pcl_ctx *one, int64_t *p) {
+        return pcl_step_phase_grid(one, n_laws, kinds, g, law_bins, mu, F, n_mix, cum, n_axes, coords, n_bins, edges, center, map, outside,
+                                   c, seed, pass, p);
+    });
+}
+
 } // namespace
 
 extern "C" {
@@ -2799,6 +3077,28 @@ int pcl_step_box_walls(pcl_ctx *ctx, const int *modes_host, const double *lo_hos
 int pcl_group_step_box_walls(pcl_group *group, const int *modes_host, const double *lo_host, const double *hi_host,
                              int64_t *counts_out_host) {
     return guarded([&] { return group_box_walls(group, modes_host, lo_host, hi_host, counts_out_host); });
+}
+
+int pcl_step_phase_grid(pcl_ctx *ctx, int n_laws, const int *kinds_host, const double *g_host, const int *law_bins_host,
+                        const double *mu_host, const double *F_host, int n_mixtures, const double *cum_host, int n_axes,
+                        const int *coords_host, const int *n_bins_host, const double *edges_host, const double *center_host,
+                        const unsigned char *mixture_host, int outside, double c, uint64_t seed, uint32_t pass,
+                        int64_t *counts_out_host) {
+    return guarded([&] {
+        return phase_grid(ctx, n_laws, kinds_host, g_host, law_bins_host, mu_host, F_host, n_mixtures, cum_host, n_axes, coords_host,
+                          n_bins_host, edges_host, center_host, mixture_host, outside, c, seed, pass, counts_out_host);
+    });
+}
+
+int pcl_group_step_phase_grid(pcl_group *group, int n_laws, const int *kinds_host, const double *g_host, const int *law_bins_host,
+                              const double *mu_host, const double *F_host, int n_mixtures, const double *cum_host, int n_axes,
+                              const int *coords_host, const int *n_bins_host, const double *edges_host, const double *center_host,
+                              const unsigned char *mixture_host, int outside, double c, uint64_t seed, uint32_t pass,
+                              int64_t *counts_out_host) {
+    return guarded([&] {
+        return group_phase_grid(group, n_laws, kinds_host, g_host, law_bins_host, mu_host, F_host, n_mixtures, cum_host, n_axes,
+                                coords_host, n_bins_host, edges_host, center_host, mixture_host, outside, c, seed, pass, counts_out_host);
+    });
 }
 
 } // extern "C"

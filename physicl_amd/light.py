@@ -1737,10 +1737,11 @@ def _check_table_law(j, mu_edges, p, max_bins):
     return np.ascontiguousarray(mu), np.ascontiguousarray(F)
 
 
-def _check_layered_phase(laws, weights, edges, center):
+def _check_layered_phase(laws, weights, edges, center, rows=None):
     """(laws as ``(kind, g, mu, F)`` tuples -- mu and F the nodes and cumulative values of a table, None otherwise --, weights as a
     float64 array [L'][M], their cumulative rows C, edges or None, centre) of a LayeredPhaseStep, or ValueError for everything
-    pcl_step_phase_layered would refuse."""
+    pcl_step_phase_layered would refuse.  ``rows``: how many rows ``weights`` has where they are not one per layer (light_grid: one
+    per mixture, without ``edges``)."""
     from ._hip import LPHASE_MAX_LAWS, LPHASE_MAX_LAYERS, LPHASE_MAX_NODES, LPHASE_MAX_TOTAL_NODES      # (the header's limits: one place)
     if isinstance(laws, str) or not isinstance(laws, collections.abc.Sequence):
         raise ValueError("laws must be a sequence of laws: 'isotropic', 'rayleigh', ('hg', g) or ('table', mu_edges, p)")
@@ -1763,7 +1764,8 @@ def _check_layered_phase(laws, weights, edges, center):
         raise ValueError("the tables of laws have %d bins in total, at most %d are supported" % (total, LPHASE_MAX_TOTAL_NODES))
     if edges is not None:
         edges = tally.check_edges("edges", edges, LPHASE_MAX_LAYERS, "square")      # (the device compares q with e*e)
-    rows = 1 if edges is None else len(edges) - 1
+    if rows is None:
+        rows = 1 if edges is None else len(edges) - 1
     if weights is None:
         if M > 1:
             raise ValueError("weights may be omitted only with one law, laws holds %d" % M)
@@ -1798,8 +1800,10 @@ def _layered_phase_redirect(r, v, dv, photon, ids, laws, weights, edges, center,
     return _layered_phase_apply(r, v, dv, photon, ids, laws, cum, edges, center, c, seed, n_pass, dtype)
 
 
-def _layered_phase_apply(r, v, dv, photon, ids, laws, cum, edges, center, c, seed, n_pass, dtype=np.float64):
-    """``_layered_phase_redirect`` behind its checks: ``laws`` and ``cum`` as ``_check_layered_phase`` returns them."""
+def _layered_phase_apply(r, v, dv, photon, ids, laws, cum, edges, center, c, seed, n_pass, dtype=np.float64, row_of=None):
+    """``_layered_phase_redirect`` behind its checks: ``laws`` and ``cum`` as ``_check_layered_phase`` returns them.  ``row_of``: None
+    -- a photon's row of ``cum`` is its radial layer -- or what gives the rows of the scattered photons from their (k, 3) positions,
+    -1 for one that is left alone (light_grid: the mixture of the photon's grid cell); ``layer`` and ``by_layer`` then hold those."""
     r, v, dv = (np.array(a, dtype=np.float64).reshape(-1, 3) for a in (r, v, dv))
     n = len(v)
     M, rows = len(laws), len(cum)
@@ -1810,7 +1814,7 @@ def _layered_phase_apply(r, v, dv, photon, ids, laws, cum, edges, center, c, see
         scattered = _scattered(dv, photon) & _workable(oo)
         at = np.flatnonzero(scattered)
         layer = np.full(n, -1, dtype=np.int64)
-        layer[at] = _layer_of(r[at], edges, center)
+        layer[at] = _layer_of(r[at], edges, center) if row_of is None else row_of(r[at])
     go = layer >= 0
     at = np.flatnonzero(go)
     ids = np.asarray(ids).reshape(-1)[at]
@@ -1894,13 +1898,14 @@ class LayeredPhaseStep(tally.WriterStep):
         self.data.append(tally.object_row([tally._snap(sim.t), self.scattered, self.redirected, self.by_layer.copy(), self.by_law.copy()]))
 
     def _refuse(self, sim):
-        _dv_rule_refusal(sim, "LayeredPhaseStep", "its direction before the scatter")
+        name = type(self).__name__                       # (GridPhaseStep derives from this class)
+        _dv_rule_refusal(sim, name, "its direction before the scatter")
         if self._pass == 0:                              # the words 10 and 11 are drawn from once per photon and pass
             steps = getattr(sim, "steps", None) or {}
             for other in (steps.values() if isinstance(steps, dict) else steps):
                 if other is not self and isinstance(other, (PhaseFunctionStep, LayeredPhaseStep)):
-                    raise ValueError("a pass holds one phase step: the simulation's steps hold a %s beside this LayeredPhaseStep, and "
-                                     "both would draw from the same Philox blocks" % type(other).__name__)
+                    raise ValueError("a pass holds one phase step: the simulation's steps hold a %s beside this %s, and "
+                                     "both would draw from the same Philox blocks" % (type(other).__name__, name))
 
     def _sweep(self, sim, prep):
         scattered, redirected, by_layer, by_law = sim._dev.phase_layered(self._laws, self.cum, self.edges, self.center, _c_h_literals()[0],
@@ -2479,7 +2484,7 @@ class GridScatterStep(LayeredScatterStep):
     on through one another (``tally.WriterStep``).  A hit gets a direction uniform on the sphere at speed c and the scatter step's
     mark, ``v = v'``, ``dv = v' - v_old`` -- ``LayeredScatterStep``'s arithmetic line for line, so a ``PhaseFunctionStep`` or
     ``LayeredPhaseStep`` behind this step re-directs its hits about ``v - dv`` and an ``AbsorptionStep`` gives them an ``omega0``; those
-    steps still act by radial layer, not by cell.  ``r``, ``dr``, ``E``, ids and kinds are never written.
+    steps act by radial layer, not by cell -- ``GridPhaseStep`` (light_grid.py) is the phase step that acts by cell.  ``r``, ``dr``, ``E``, ids and kinds are never written.
 
     After each run ``self.exposed`` and ``self.scattered`` hold the pass's counts and ``self.scattered_by_cell`` an int64 array of
     ``k``'s broadcast shape, global over shards and ranks; ``self.data`` gains the row ``[t, exposed, scattered,
@@ -3196,3 +3201,8 @@ def _merge_shards(comm, rows):
     owners = tot[bits.size:].reshape(mine.shape)
     got[owners != 1] = np.nan
     return got
+
+
+# GridPhaseStep stands in light_grid.py, which builds on this module and hands the class to this module's names at its end
+# (``from physicl_amd.light import *`` and ``phys.light.GridPhaseStep`` find it, whichever of the two modules is imported first).
+from . import light_grid  # noqa: E402,F401
