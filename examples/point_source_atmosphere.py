@@ -4,7 +4,7 @@ examples (n(r) = 2.5e25 m^-3 * exp(-(|r| - 6371 km) / 8.6 km)) with photons that
 
     python examples/point_source_atmosphere.py [n_photons] [passes] [--cone | --beam-down | --default] [--profile] [--shells]
                                                [--ground [ALBEDO]] [--phase rayleigh | hg:G | isotropic] [--omega0 W | W1,W2,...]
-                                               [--cloud LO,HI[,G]] [--cloud-tau TAU] [--cloud-field NX,NY,NZ:EXTENT:TAU] [--cloud-phase G] [--box periodic | mirror | open] [--recycle [TOP]] [--gas LO,HI,K[,EMIN,EMAX]] [--blue-sky]
+                                               [--cloud LO,HI[,G]] [--cloud-tau TAU] [--cloud-field NX,NY,NZ:EXTENT:TAU] [--cloud-phase G] [--cloud-absorb OMEGA0[,K]] [--box periodic | mirror | open] [--recycle [TOP]] [--gas LO,HI,K[,EMIN,EMAX]] [--blue-sky]
                                                [--reemit [TG[,TA]]] [--ocean N] [--ground-bands E1,E2,...:a1,a2,...[:s1,...]]
                                                [--camera X,Y,Z:NX,NY,NZ:RADIUS:FOV_DEG:PIXELS]
 
@@ -50,6 +50,10 @@ the place of the phase function turns a photon scattered in a cloudy cell by a m
 Henyey-Greenstein with the mean cosine G, and one scattered in a clear cell or anywhere outside the box (``outside``) by Rayleigh's law.
 ``by_mixture`` [clear, cloudy] and ``by_law`` [rayleigh, hg] summed over the passes are printed.  Not together with ``--phase`` or
 ``--cloud``: a pass holds one phase step.
+``--cloud-absorb OMEGA0[,K]`` (with ``--cloud-field``) lets the field absorb: a GridAbsorptionStep on the field's cells behind the phase
+step gives the cloudy cells the single-scattering albedo OMEGA0 (the clear ones 1) and, with K, the column of cells at y index 0 and z
+index 1 -- a clear one -- the absorption coefficient K per metre: a column of water vapour.  ``exposed``, ``interacted``,
+``absorbed_path`` and ``absorbed_hit`` summed over the passes and the column sums of ``absorbed_by_cell`` are printed.
 ``--box periodic | mirror | open`` (with ``--cloud-field``) gives the scene sides: a BoxBoundaryStep around the cloud field's box on its
 two horizontal axes y and z (x, the vertical, has no wall), last in the pass, behind the ground and in front of a re-emission or the
 recycling lamp.  ``periodic`` hands a photon that leaves the field sideways back in on the other side -- the boundary condition
@@ -171,6 +175,16 @@ if "--cloud-phase" in argv:
         cloud_phase = 2.0
     if cloud_field is None or cloud is not None or phase is not None or not abs(cloud_phase) < 1.0:
         sys.exit("--cloud-phase G: the droplets' mean cosine, |G| < 1, together with --cloud-field NX,NY,NZ:EXTENT:TAU and without --phase or --cloud")
+cloud_absorb = None
+if "--cloud-absorb" in argv:
+    at = argv.index("--cloud-absorb")
+    try:
+        cloud_absorb = [float(x) for x in argv.pop(at + 1).split(",")]
+    except (IndexError, ValueError):
+        cloud_absorb = []
+    if cloud_field is None or len(cloud_absorb) not in (1, 2) or not 0.0 <= cloud_absorb[0] <= 1.0 or not 0.0 <= cloud_absorb[-1] < float("inf"):
+        sys.exit("--cloud-absorb OMEGA0[,K]: the droplets' single-scattering albedo in [0, 1] and optionally the absorption coefficient per "
+                 "metre of one column of cells, together with --cloud-field NX,NY,NZ:EXTENT:TAU")
 box = None
 if "--box" in argv:
     at = argv.index("--box")
@@ -286,6 +300,13 @@ def run(ground):
         angles = light.LayeredPhaseStep(["rayleigh", ("hg", cloud[2])], CLOUD_WEIGHTS, edges=[0.0, R + cloud[0], R + cloud[1], R + 1000e3])
     if angles is not None:                                     # directly behind the scatter step (steps run in the order they were added)
         sim.add_step("phase", angles)
+    heat = None
+    if cloud_absorb is not None:                               # the field's cells once more: droplets that absorb, and a column of vapour
+        column = np.zeros(broken.k.shape)
+        column[:, 0, 1 % column.shape[2]] = cloud_absorb[1] if len(cloud_absorb) == 2 else 0.0       # (a clear column, where there is one)
+        heat = light.GridAbsorptionStep(broken.axes, broken.edges, k=column if len(cloud_absorb) == 2 else None,
+                                        omega0=np.where(broken.k > 0, cloud_absorb[0], 1.0))
+        sim.add_step("cloud_absorb", heat)
     vapour = None
     if gas is not None:                                        # behind the scatter, absorption and phase steps, before the ground
         vapour = light.PathAbsorptionStep([gas[2]] if len(gas) == 3 else [[gas[2]]], edges=[R + gas[0], R + gas[1]],
@@ -344,7 +365,7 @@ def run(ground):
     sim.join()
     if sim.error is not None:
         raise sim.error
-    return sim, signs, shells, profile, image, tally, floor, angles, medium, lamp, vapour, eye, glow, sea, droplets, broken, walls, inside
+    return sim, signs, shells, profile, image, tally, floor, angles, medium, lamp, vapour, eye, glow, sea, droplets, broken, walls, inside, heat
 
 
 bare_top = None
@@ -354,7 +375,7 @@ if ground is not None and "--shells" in sys.argv:              # the same run wi
     print("without the ground: %d photons x %d steps in %.2f s" % (n, len(bare[0].ts), bare[0].run_time))
     bare[0].close(download=False)
     del bare
-sim, signs, shells, profile, image, tally, floor, angles, medium, lamp, vapour, eye, glow, sea, droplets, broken, walls, inside = run(ground)
+sim, signs, shells, profile, image, tally, floor, angles, medium, lamp, vapour, eye, glow, sea, droplets, broken, walls, inside, heat = run(ground)
 steps = len(sim.ts)
 print("source:", source)
 print("%d photons x %d steps in %.2f s  ->  %.3g particle-steps/s" % (n, steps, sim.run_time, n * steps / sim.run_time))
@@ -387,6 +408,14 @@ if broken is not None:
         sum(int(row[2]) for row in broken.data), len(broken.data)))
     print("  scattered by column (summed over x, rows: y, columns: z):")
     for line in by_cell.sum(axis=0):
+        print("   " + " ".join("%8d" % x for x in line))
+if heat is not None:
+    heating = np.sum([row[5] for row in heat.data], axis=0)
+    print("absorption on the field's cells (omega0 = %g in the cloudy cells%s): %d photons exposed, %d interacted, %d absorbed along the path, "
+          "%d at the interaction over %d passes" % (cloud_absorb[0], "" if len(cloud_absorb) == 1 else ", k = %g per m in the column y 0, z 1" % cloud_absorb[1],
+                                                   *(sum(int(row[k]) for row in heat.data) for k in (1, 2, 3, 4)), len(heat.data)))
+    print("  absorbed by column, the heating field (summed over x, rows: y, columns: z):")
+    for line in heating.sum(axis=0):
         print("   " + " ".join("%8d" % x for x in line))
 if walls is not None:
     crossed = np.sum([row[3] for row in walls.data], axis=0)

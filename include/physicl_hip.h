@@ -1334,6 +1334,64 @@ int pcl_step_phase_grid(pcl_ctx *ctx, int n_laws, const int *kinds_host, const d
                         const unsigned char *mixture_host /* [G] */, int outside, double c, uint64_t seed, uint32_t pass,
                         int64_t *counts_out_host /* [2 + K + M] */);
 
+/* Absorption on a grid of cells (GridAbsorptionStep): both kinds of absorption -- along the path (pcl_step_absorb_path's) and at an
+ * interaction (pcl_step_absorb_scattered's) -- per cell of pcl_step_position_grid's grid and per band of the photon's energy, in ONE
+ * sweep of the resident store, and the tally of what was absorbed per cell: the heating field of a smoke plume, a water-vapour column
+ * of finite width, the droplets of a broken cloud field.  Called where those two sweeps are called: behind the scatter and phase steps
+ * of a pass, in front of the ground.  Either table may be left out (NULL), not both.  The host makes p = -expm1(-k * (c*dt)) and the
+ * device only ever sees p.  Nothing is removed; r, dr, E, ids and kinds are never written.  The rule holds compares and stores only --
+ * no transcendental function, no division, no square root; q of a radius axis is fp64, unfused, every operation rounded once, in the
+ * order written, an fp32 store's values widened first (exact) -- so numpy restates every bit.  B' = max(n_E_bins, 1), G = the
+ * product of n_bins_host.
+ *   a particle that is not a photon (kind 0) is skipped and never written.
+ *   at rest    iff  v0 == 0 and v1 == 0 and v2 == 0           (-0.0 counts as 0; a NaN in v: moving), as pcl_step_scatter_grid;
+ *                   a photon at rest is skipped.
+ *   cell g, band e: pcl_step_scatter_grid's lines exactly -- per axis the bin with e_b <= x < e_(b+1), the last one closed;  a
+ *                   PCL_GRID_RADIUS axis bins q = ((x-cx)*(x-cx) + (y-cy)*(y-cy)) + (z-cz)*(z-cz) against the squared edges;  cells are
+ *                   row-major in the order of the axes;  n_E_bins == 0: e = 0, E is neither read nor asked for;  otherwise e = the bin
+ *                   of E in E_edges_host;  a NaN, a position outside any axis's range and an energy outside the bands are in no cell.
+ *                   Only the rows of r some axis needs are read.
+ *   exposed    =    a moving photon with a cell and a band;  c = g * B' + e
+ *   interacted =    exposed and (dv0 != 0 or dv1 != 0 or dv2 != 0), the scatter kernels' mark (a NaN in dv: interacted).  Evaluated
+ *                   only with omega0_host: without it dv is not read and the count is 0.
+ *   along the path  (p_host given and p_host[c] > 0; p == 0 draws nothing):  u = u53(w0, w1) of the counter (id_lo, id_hi, pass, 27);
+ *                   absorbed iff u < p_host[c]
+ *   at the interaction  (not absorbed along the path, omega0_host given, interacted, and omega0_host[c] < 1; a conservative cell
+ *                   draws nothing):  u = u53(w0, w1) of the counter (id_lo, id_hi, pass, 28);  absorbed iff not (u < omega0_host[c]),
+ *                   pcl_step_absorb_scattered's sense of the draw
+ *   absorbed:       parked as those two sweeps park:  v_k = 0 and dv_k = 0 for k = 0, 1, 2;  cells_out_host[c] += 1, whichever kind
+ *   not absorbed:   the particle is not written at all.
+ * The Philox4x32-10 blocks have the key (seed_lo, seed_hi), u53 of pcl_store_apply_source; ``pass`` is the caller's own counter.  The
+ * words 27 and 28 are used by nothing else: with this call's 27 and 28 the taken words are 0-5 and 8-28 (pcl_step_phase_grid lists the
+ * users of the others), so every other step draws what it drew, and a photon meets the same fate however the run is sharded.
+ * n_axes, coords_host, n_bins_host, edges_host, center_host, n_E_bins, E_edges_host: as for pcl_step_scatter_grid, n_E_bins at most
+ * PCL_ABSORB_GRID_MAX_BANDS.  p_host, omega0_host: NULL, or G * B' values, every one in [0, 1] (not NaN);
+ * G * B' <= PCL_ABSORB_GRID_MAX_CELLS.
+ * counts_out_host[0] = photons exposed, [1] = interacted, [2] = absorbed along the path, [3] = absorbed at the interaction, by this
+ * call;  cells_out_host[g * B' + e] = absorbed in cell g and band e, both kinds together.
+ * The edges are always staged in LDS.  With E = every edge of the axes and of E_edges_host, C = G * B' and t = the tables given (1 or
+ * 2), the tables and a workgroup's uint32 tallies are in LDS too while
+ *     C <= PCL_ABSORB_GRID_LDS_CELLS   and   8 * E  +  8 * t * C  +  4 * (4 + C)  <=  PCL_ABSORB_GRID_LDS_BYTES
+ * -- a 16 x 16 x 16 grid with one table, not with two; above that the kernel reads the tables from device memory and adds what it
+ * absorbed to the device tallies with 64-bit atomics, one add per wave and cell where the absorbed lanes of a wave share a cell.
+ * Cost: the tables go up over the host link once per call and the tallies come back, as for pcl_step_scatter_grid; nothing is cached
+ * between calls.  A store that is not uniform costs the host traffic it costs pcl_step_surface_reflect; the ids go along only if some
+ * p > 0 or some omega0 < 1.
+ * PCL_ERR_ARG (everything pcl_step_scatter_grid refuses of the geometry and of E_edges, both tables NULL, a table value outside
+ * [0, 1] or NaN, too many cells, a NULL output) is returned before the store is looked at -- by the group's entry point before the
+ * group is --, and nothing is launched or written; PCL_ERR_STATE without a store; an empty store answers zeros without a launch.
+ * Host pointers; one device allocation per call, handed back on every way out; synchronises once, with the copy of the tallies.
+ * pcl_last_error() is generic, as for pcl_step_surface_reflect, whose source file these two entry points share. */
+#define PCL_ABSORB_GRID_MAX_BANDS 1024
+#define PCL_ABSORB_GRID_MAX_CELLS (1 << 20) /* G * B': PCL_GRID_MAX_CELLS */
+#define PCL_ABSORB_GRID_LDS_CELLS 4096
+#define PCL_ABSORB_GRID_LDS_BYTES 65536
+int pcl_step_absorb_grid(pcl_ctx *ctx, int n_axes, const int *coords_host, const int *n_bins_host, const double *edges_host,
+                         const double *center_host, int n_E_bins, const double *E_edges_host, const double *p_host /* or NULL */,
+                         const double *omega0_host /* or NULL */, uint64_t seed, uint32_t pass,
+                         int64_t *counts_out_host /* [4]: exposed, interacted, absorbed along the path, at the interaction */,
+                         int64_t *cells_out_host /* [G * B'] */);
+
 /* ---- Device groups: several GPUs from ONE process ---------------------------------------------------------------
  * The reference is a single process with one simulation thread (physicl/__init__.py:400-432, 501-524); this is how
  * a host written against this ABI uses a node's GPUs the same way, without one process per GPU.  A group owns one
@@ -1465,6 +1523,13 @@ int pcl_group_step_phase_grid(pcl_group *group, int n_laws, const int *kinds_hos
                               const int *coords_host, const int *n_bins_host, const double *edges_host, const double *center_host,
                               const unsigned char *mixture_host, int outside, double c, uint64_t seed, uint32_t pass,
                               int64_t *counts_out_host);
+/* pcl_step_absorb_grid on every shard (side by side), the four counts and the cells summed over the group's devices; the arguments
+ * are checked once for the group, before the group is looked at (ids are global: the same photons meet the same fate).  Every shard
+ * stages the tables and brings its tallies back */
+int pcl_group_step_absorb_grid(pcl_group *group, int n_axes, const int *coords_host, const int *n_bins_host, const double *edges_host,
+                               const double *center_host, int n_E_bins, const double *E_edges_host, const double *p_host,
+                               const double *omega0_host, uint64_t seed, uint32_t pass, int64_t *counts_out_host,
+                               int64_t *cells_out_host);
 
 /* ---------------------------------------------------------------- the counters' collective (one process per GPU)
  * The path shards by global index with no data-path exchange; the only global quantities are the int64

@@ -40,6 +40,7 @@ SPECTRAL_MAX_BANDS = 1024                                                    # P
 SCATTER_LAYERED_MAX_LAYERS, SCATTER_LAYERED_MAX_BANDS, SCATTER_LAYERED_MAX_CELLS = 64, 1024, 4096       # PCL_SCATTER_LAYERED_MAX_LAYERS ...
 SCATTER_GRID_MAX_BANDS, SCATTER_GRID_MAX_CELLS = 1024, 1 << 20                # PCL_SCATTER_GRID_MAX_BANDS, PCL_SCATTER_GRID_MAX_CELLS
 PHASE_GRID_MAX_MIXTURES, PHASE_GRID_MAX_CELLS, PHASE_GRID_ALONE, PHASE_GRID_LDS_BYTES = 64, 1 << 20, 255, 65536   # PCL_PHASE_GRID_MAX_MIXTURES ...
+ABSORB_GRID_MAX_BANDS, ABSORB_GRID_MAX_CELLS, ABSORB_GRID_LDS_CELLS, ABSORB_GRID_LDS_BYTES = 1024, 1 << 20, 4096, 65536   # PCL_ABSORB_GRID_MAX_BANDS ...
 WALL_MODES = {None: 0, "periodic": 1, "mirror": 2, "open": 3}               # PCL_WALL_NONE, PCL_WALL_PERIODIC, PCL_WALL_MIRROR, PCL_WALL_OPEN
 REEMIT_LAWS = {"isotropic": 0, "lambertian": 1}                              # the flags of pcl_step_reemit_parked's lambertian_host
 PROF_NEWTON, PROF_SCATTER, PROF_DELETE_MASK, PROF_COMPACT, PROF_COUNTERS, PROF_FUSED, PROF_MULTI, PROF_ONEPASS, \
@@ -177,6 +178,7 @@ _PROTOTYPES = {
     "pcl_step_scatter_grid": [_vp, c_int, _vp, _vp, _vp, _vp, c_int, _vp, _vp, c_int, c_double, c_uint64, c_uint32, _vp, _vp],
     "pcl_step_box_walls": [_vp, _vp, _vp, _vp, _vp],
     "pcl_step_phase_grid": [_vp, c_int, _vp, _vp, _vp, _vp, _vp, c_int, _vp, c_int, _vp, _vp, _vp, _vp, _vp, c_int, c_double, c_uint64, c_uint32, _vp],
+    "pcl_step_absorb_grid": [_vp, c_int, _vp, _vp, _vp, _vp, c_int, _vp, _vp, _vp, c_uint64, c_uint32, _vp, _vp],
     # device groups: several GPUs from one process (the C-level counterpart of physicl_amd.multidev.MultiDevice)
     "pcl_group_create": [c_int, POINTER(c_int), POINTER(_vp)],
     "pcl_group_destroy": [_vp],
@@ -218,6 +220,7 @@ _PROTOTYPES = {
     "pcl_group_step_box_walls": [_vp, _vp, _vp, _vp, _vp],
     "pcl_group_step_phase_grid": [_vp, c_int, _vp, _vp, _vp, _vp, _vp, c_int, _vp, c_int, _vp, _vp, _vp, _vp, _vp, c_int, c_double, c_uint64,
                                   c_uint32, _vp],
+    "pcl_group_step_absorb_grid": [_vp, c_int, _vp, _vp, _vp, _vp, c_int, _vp, _vp, _vp, c_uint64, c_uint32, _vp, _vp],
 }
 EXPORTS = sorted(list(_PROTOTYPES) + ["pcl_last_error"])
 
@@ -682,6 +685,48 @@ def _phase_grid(entry, handle, laws, cum, axes, edges, center, mixture, outside,
                 coords.ctypes.data, n_bins.ctypes.data, ed.ctypes.data, ptr(ce), mp.ctypes.data, -1 if outside is None else int(outside),
                 float(c), int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_pass) & 0xFFFFFFFF, counts.ctypes.data))
     return int(counts[0]), int(counts[1]), counts[2:2 + K].copy(), counts[2 + K:].copy()
+
+
+def absorb_grid_lds_bytes(n_tables, n_edges, n_cells):
+    """The LDS the LDS form of a pcl_step_absorb_grid call asks for, by the header's formula: t tables (1 or 2), E edges over all axes
+    and the bands, C cells of the grid times bands."""
+    return 8 * int(n_edges) + 8 * int(n_tables) * int(n_cells) + 4 * (4 + int(n_cells))
+
+
+def absorb_grid_lds_form(n_tables, n_edges, n_cells):
+    """Whether a pcl_step_absorb_grid call keeps its tables and tallies in LDS (the header's bound) or in device memory."""
+    return n_cells <= ABSORB_GRID_LDS_CELLS and absorb_grid_lds_bytes(n_tables, n_edges, n_cells) <= ABSORB_GRID_LDS_BYTES
+
+
+def _absorb_grid(entry, handle, p, omega0, axes, edges, center, E_edges, seed, n_pass):
+    """One call of pcl_step_absorb_grid / pcl_group_step_absorb_grid: (counts int64[4] -- exposed, interacted, absorbed along the path,
+    absorbed at the interaction --, absorbed_by_cell int64 of the grid's shape, with a last dimension of B bands if ``E_edges`` is
+    given).  ``p``: the probability of absorption along the path per pass, ``omega0``: the single-scattering albedo, each None or one
+    value per cell (and band), row-major in the order of ``axes`` (any shape of that size), not both None; ``axes``, ``edges``,
+    ``center``: as for ``_grid`` (the library squares the edges of a radius axis); ``n_pass``: the caller's own pass counter (a Philox
+    counter word).  The tables go up and the tallies come back with every call."""
+    coords = np.array([GRID_COORDS.get(a, a) for a in axes], dtype=np.int32)
+    per_axis = [np.ascontiguousarray(e, dtype=np.float64).reshape(-1) for e in edges]
+    if len(per_axis) != len(coords):
+        raise ValueError("one sequence of edges per axis: %d axes, %d sequences" % (len(coords), len(per_axis)))
+    n_bins = np.array([len(e) - 1 for e in per_axis], dtype=np.int32)
+    ed = np.ascontiguousarray(np.concatenate(per_axis)) if per_axis else np.zeros(0)
+    Ee = None if E_edges is None else np.ascontiguousarray(E_edges, dtype=np.float64).reshape(-1)
+    B = 0 if Ee is None else len(Ee) - 1
+    shape = [max(int(b), 0) for b in n_bins] + ([B] if Ee is not None else [])
+    tabs = [None if t is None else np.ascontiguousarray(t, dtype=np.float64).reshape(-1) for t in (p, omega0)]
+    if tabs[0] is None and tabs[1] is None:
+        raise ValueError("p and omega0 are both None: an absorption needs one of them")
+    for name, t in zip(("p", "omega0"), tabs):
+        if t is not None and len(t) != int(np.prod(shape)):
+            raise ValueError("%s holds %d values for a grid of shape %r" % (name, len(t), tuple(shape)))
+    ce = None if center is None else np.ascontiguousarray(center, dtype=np.float64).reshape(3)
+    counts = np.zeros(4, dtype=np.int64)
+    cells = np.zeros(shape, dtype=np.int64)
+    ptr = lambda a: None if a is None else a.ctypes.data                                                       # noqa: E731
+    check(entry(handle, len(coords), coords.ctypes.data, n_bins.ctypes.data, ed.ctypes.data, ptr(ce), B, ptr(Ee), ptr(tabs[0]), ptr(tabs[1]),
+                int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_pass) & 0xFFFFFFFF, counts.ctypes.data, cells.ctypes.data))
+    return counts, cells
 
 
 def _scatter(sc, required=False, lazy=False, empty_expr=b""):
@@ -1333,6 +1378,15 @@ class Device:
             mixture = np.zeros([len(np.reshape(e, -1)) - 1 for e in edges], dtype=np.int64)
         return _phase_grid(self.lib.pcl_step_phase_grid, self.ctx, laws, cum, axes, edges, center, mixture, outside, c, seed, n_pass)
 
+    def absorb_grid(self, p, omega0, axes, edges, center=None, E_edges=None, seed=0, n_pass=0):
+        """Absorption on a grid of cells, both kinds in one sweep: every moving photon with a cell of the grid over ``axes``
+        (``position_grid``'s cells) and a band of ``E_edges`` is absorbed along the path with the probability ``p[cell][band]``, and,
+        if it was scattered in this pass (``dv != 0``) and is still under way, at the interaction with ``1 - omega0[cell][band]``; an
+        absorbed photon is parked (``v = dv = 0``), nobody else is written (pcl_step_absorb_grid).  Either table may be None, not both.
+        ``(counts int64[4]: exposed, interacted, absorbed along the path, absorbed at the interaction; absorbed_by_cell int64 of the
+        grid's shape (+ bands))``.  ``n_pass``: the caller's own pass counter."""
+        return _absorb_grid(self.lib.pcl_step_absorb_grid, self.ctx, p, omega0, axes, edges, center, E_edges, seed, n_pass)
+
     def box_walls(self, modes, lo, hi):
         """The walls of the box ``[lo, hi]``, per axis ``"periodic"``, ``"mirror"``, ``"open"`` or None: every moving photon outside on
         an axis with a wall is handed back in through the other side, folded back at the wall (an odd number of bounces turns ``v``,
@@ -1493,6 +1547,10 @@ class DeviceGroup:
         if mixture is None:
             mixture = np.zeros([len(np.reshape(e, -1)) - 1 for e in edges], dtype=np.int64)
         return _phase_grid(self.lib.pcl_group_step_phase_grid, self.g, laws, cum, axes, edges, center, mixture, outside, c, seed, n_pass)
+
+    def absorb_grid(self, p, omega0, axes, edges, center=None, E_edges=None, seed=0, n_pass=0):
+        """``Device.absorb_grid`` on every context of the group, the tallies summed (pcl_group_step_absorb_grid)."""
+        return _absorb_grid(self.lib.pcl_group_step_absorb_grid, self.g, p, omega0, axes, edges, center, E_edges, seed, n_pass)
 
     def box_walls(self, modes, lo, hi):
         """``Device.box_walls`` on every context of the group, the counts summed (pcl_group_step_box_walls)."""

@@ -68,6 +68,12 @@ UNITS = [CORE] + ADDONS
 LATER = [
     dict(_sweep("pcl_step_phase_grid", "pcl_group_step_phase_grid", "k_phase_grid"), src=_c("pcl_surface.hip")),
 ]
+# Sweeps added since, a row each, shaped as LATER's plus ``vgprs``, the row's own register budget: tests/test_grid_absorb_build_cpu.py
+# reads every expectation from the row, so the next sweep is one more row here and no further table.
+MORE = [
+    # k_scatter_grid's budget (eight waves per SIMD): this kernel does less arithmetic than that one
+    dict(_sweep("pcl_step_absorb_grid", "pcl_group_step_absorb_grid", "k_absorb_grid", count=4), src=_c("pcl_surface.hip"), vgprs=64),
+]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -ffp-contract=off: the reference's kernels must be evaluated unfused (bit-exact parity)

@@ -248,6 +248,23 @@
 //   scattered: k_phase_layered's line;  cell: k_position_grid's lines;  m = map[cell], or ``outside`` in no cell;  m = none: counted as
 //   scattered, not written;  otherwise law j = the first with u_s < C[m][j] (counter word 13), mu by the law (words 10 and 11) and the
 //   turn about o/|o|: k_phase_layered's lines
+//
+// Absorption on a grid of cells (GridAbsorptionStep): who is absorbed -- along the path, by a probability p per cell and band, and at an
+// interaction, by a single-scattering albedo per cell and band -- and the tally of the absorbed per cell, the heating field.  Both kinds
+// in one sweep: these sweeps are bound by the store's traffic, and the cell lookup is the expensive part.
+//
+//   k_absorb_grid<T, lds>  the grid scatter's sweep without its direction: a moving photon loads the r rows some axis needs and, with
+//                          bands, E, and is looked up in the edges (always in LDS); with an albedo table an exposed lane loads the
+//                          three dv rows.  Which tables a call gives is uniform over the launch.  lds = true: the tables given and the
+//                          workgroup's uint32 tallies by cell sit in LDS too (up to 4096 cells, the whole within 64 KiB: 4096 cells
+//                          with one table, not with two);  lds = false: read-only loads from the device tables and 64-bit atomics on
+//                          the device tallies.  The four counts are wave ballots and popcounts into LDS at the head of the body; the
+//                          absorbed lanes of a wave that share a cell issue ONE add, and one add for a run of such trips in one cell.
+//
+// Operation order (what light_grid._grid_absorb restates with numpy):
+//   moving, cell, band: the grid scatter's lines;  c = cell * B' + e;  interacted = dv != 0 (only with an albedo table);
+//   p[c] > 0: u = u53(w0, w1) of counter (id_lo, id_hi, pass, 27), absorbed iff u < p[c];  otherwise, interacted and omega0[c] < 1:
+//   u of counter (id_lo, id_hi, pass, 28), absorbed iff not (u < omega0[c]);  absorbed: v_k = 0, dv_k = 0;  anybody else is not written
 #include "pcl_sweep.h"
 
 #include "pcl_device.h" // (after the HIP runtime and the ABI's header, which pcl_sweep.h brings)
@@ -2892,6 +2909,251 @@ int group_phase_grid(pcl_group *group, int n_laws, const int *kinds, const doubl
     });
 }
 
+// ---- absorption on a grid of cells: the kernel stands with its host side, at the end of the unit, as the scattering on a grid does
+// The counter words of an absorption on a grid: along the path, at the interaction (the header lists who uses which word: 27 and 28
+// are this kernel's alone).
+constexpr uint32_t kGridAbsorbPath = 27, kGridAbsorbHit = 28;
+// The LDS form's switch-over (the header states the formula): up to this many cells the tables given and a workgroup's tallies sit in
+// LDS beside the edges, if the whole stays within what a launch may ask for; above it both stay in device memory.
+constexpr int kGridAbsorbLdsCells = PCL_ABSORB_GRID_LDS_CELLS;
+constexpr size_t kGridAbsorbLdsBytes = PCL_ABSORB_GRID_LDS_BYTES;
+static_assert(PCL_ABSORB_GRID_MAX_CELLS == PCL_GRID_MAX_CELLS && PCL_ABSORB_GRID_MAX_BANDS == PCL_SCATTER_GRID_MAX_BANDS,
+              "the absorber's grid and bands are the scattering medium's");
+
+template <typename T>
+struct gabsorb_args {
+    const T *r[3];               // rows some axis needs (NULL otherwise)
+    T *v[3], *dv[3];
+    const T *E;                  // NULL without energy bands
+    const unsigned char *kind;   // NULL: every particle is a photon
+    const int64_t *ids;          // NULL: the id of slot i is id_base + i
+    const double *tables;        // p [n_cells] (if has_p) | omega0 [n_cells] (if has_om) | the axes' edges (a radius axis: squared) | E edges; device
+    unsigned long long *out;     // exposed, interacted, absorbed along the path, at the interaction | absorbed by cell [n_cells]; device, zeroed
+    int64_t N, ts, id_base;      // particles, tile stride of the slab (elements), id of slot 0
+    int tile_log;                // log2 of the tile length
+    int n_axes, n_E;             // axes of the grid, B (0: one column for every energy, B' = 1)
+    int n_edges, n_cells;        // every edge of the axes and of E; cells of the grid x B'
+    int coord[PCL_GRID_MAX_AXES], n_bins[PCL_GRID_MAX_AXES], edge_at[PCL_GRID_MAX_AXES], E_at;
+    int rows;                    // bit k: row k of r is read
+    int has_p, has_om;           // which tables the call gave: uniform over the launch
+    double c[3];
+    uint32_t k0, k1, pass;       // Philox key (seed_lo, seed_hi), the step's own pass counter
+};
+
+template <typename T, bool kLds>
+__global__ void __launch_bounds__(kBlock) k_absorb_grid(gabsorb_args<T> a) {
+    extern __shared__ double s_mem[];                                  // edges | p, omega0 (LDS form, those given) | four counts | by cell (LDS form)
+    const int nE = a.n_E, n_tab = (a.has_p ? 1 : 0) + (a.has_om ? 1 : 0), n_lds_c = kLds ? a.n_cells : 0;
+    const int om_at = a.has_p ? a.n_cells : 0;                          // where omega0 starts behind p, in device memory and in LDS alike
+    double *s_edges = s_mem;
+    double *s_tab = s_mem + a.n_edges;
+    uint32_t *s_cnt = reinterpret_cast<uint32_t *>(s_tab + n_tab * n_lds_c);
+    uint32_t *s_cell = s_cnt + 4;
+    const int n_cnt = 4 + n_lds_c;
+    for (int k = threadIdx.x; k < a.n_edges; k += kBlock) s_edges[k] = a.tables[n_tab * a.n_cells + k];
+    for (int k = threadIdx.x; k < n_tab * n_lds_c; k += kBlock) s_tab[k] = a.tables[k];
+    for (int k = threadIdx.x; k < n_cnt; k += kBlock) s_cnt[k] = 0;    // (the cells follow the four counts)
+    __syncthreads();
+    const double *tab = kLds ? s_tab : a.tables;                        // (global form: read-only loads, the tables stay in L2)
+    const double *s_E = s_edges + a.E_at;
+    const int lane = threadIdx.x & 63;
+    const int64_t stride = grid_stride(), n_round = whole_waves(a.N);   // (the ballots below need whole waves inside the loop)
+    // wave-uniform, as in the scattering on a grid: the cell and the count of consecutive trips whose absorbed lanes all sat in that
+    // one cell, not added yet (fewer than 2^32: kMaxSlotsPerWorkgroup).  Every bulk run starts with all photons in ONE cell, and adds
+    // to one address serialise where they are carried out; so a run is added once.
+    int run_cell = 0;
+    uint32_t run_n = 0;
+    auto flush_run = [&]() {
+        if (lane == 0 && run_n) {
+            if (kLds) atomicAdd(&s_cell[run_cell], run_n);
+            else atomicAdd(&a.out[4 + run_cell], (unsigned long long)run_n);
+        }
+        run_n = 0;
+    };
+    for (int64_t i = first_slot(); i < n_round; i += stride) {
+        const bool in = i < a.N;
+        const int64_t ti = tile_index(i, a.tile_log, a.ts);
+        bool photon = in;
+        if (photon && a.kind) photon = a.kind[i] != 0;                  // plain Objects are never touched
+        // moving: at_rest, written out as in the scattering on a grid and negated -- -0.0 == 0, a NaN moves, v0 != 0 loads no more of v
+        const bool go = photon && !((double)a.v[0][ti] == 0.0 && (double)a.v[1][ti] == 0.0 && (double)a.v[2][ti] == 0.0);
+        int cell = -1;                                                  // (cell of the grid) * B' + e; -1: not exposed
+        if (go) {
+            double x[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                if ((a.rows >> k) & 1) x[k] = (double)a.r[k][ti];       // fp32 widens exactly
+            bool ok = true;
+            int at = 0;
+            for (int ax = 0; ax < a.n_axes; ++ax) {                     // k_position_grid's lines
+                const int co = a.coord[ax], nb = a.n_bins[ax];
+                const double *e = s_edges + a.edge_at[ax];
+                double q;
+                if (co == PCL_GRID_RADIUS) {   // q, unfused, in this order (the library is built with -ffp-contract=off)
+                    const double dx = x[0] - a.c[0], dy = x[1] - a.c[1], dz = x[2] - a.c[2];
+                    q = (dx * dx + dy * dy) + dz * dz;
+                } else {
+                    q = co == 0 ? x[0] : (co == 1 ? x[1] : x[2]);
+                }
+                ok = ok && q >= e[0] && q <= e[nb];                     // NaN and anything outside the axis's range are in no cell
+                at = at * nb + bin_of(e, nb, q);
+            }
+            if (ok && nE > 0) {
+                const double e = (double)a.E[ti];
+                ok = e >= s_E[0] && e <= s_E[nE];                       // NaN and under/overflow: in no band
+                at = at * nE + bin_of(s_E, nE, e);
+            }
+            if (ok) cell = at;
+        }
+        const bool exposed = cell >= 0;
+        bool inter = false, gone_path = false, gone_hit = false;
+        if (exposed) {
+            if (a.has_om)                                               // interacted in this pass: the scatter kernels' mark (NaN != 0 is true)
+                inter = (double)a.dv[0][ti] != 0.0 || (double)a.dv[1][ti] != 0.0 || (double)a.dv[2][ti] != 0.0;
+            const uint64_t id = id_of(a.ids, a.id_base, i);
+            if (a.has_p) {
+                const double p = tab[cell];
+                if (p > 0.0)                                            // a transparent cell draws nothing; u < 1: p == 1 absorbs everybody
+                    gone_path = first_u53(pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, kGridAbsorbPath, a.k0, a.k1)) < p;
+            }
+            if (inter && !gone_path) {
+                const double om = tab[om_at + cell];
+                if (om < 1.0)                                           // a conservative cell draws nothing; the sense of the ground's albedo draw
+                    gone_hit = !(first_u53(pcl_philox4x32_10((pcl_u32)id, (pcl_u32)(id >> 32), a.pass, kGridAbsorbHit, a.k0, a.k1)) < om);
+            }
+        }
+        const bool gone = gone_path || gone_hit;
+        const unsigned long long m_gone = __ballot(gone);
+        const uint32_t n_exp = (uint32_t)__popcll(__ballot(exposed)), n_int = (uint32_t)__popcll(__ballot(inter));
+        const uint32_t n_path = (uint32_t)__popcll(__ballot(gone_path)), n_hit = (uint32_t)__popcll(__ballot(gone_hit));
+        if (lane == 0 && n_exp) atomicAdd(&s_cnt[0], n_exp);
+        if (lane == 0 && n_int) atomicAdd(&s_cnt[1], n_int);
+        if (lane == 0 && n_path) atomicAdd(&s_cnt[2], n_path);
+        if (lane == 0 && n_hit) atomicAdd(&s_cnt[3], n_hit);
+        bool counted = false;                                           // this lane's absorption is in the wave's run
+        if (m_gone) {                                                   // (wave-uniform)
+            const int c0 = __shfl(cell, __ffsll((long long)m_gone) - 1);
+            if (__ballot(gone && cell == c0) == m_gone) {               // every absorbed lane of the wave in one cell: one add of their count,
+                if (c0 != run_cell) {                                   // put off while the next trips absorb in the same cell
+                    flush_run();
+                    run_cell = c0;
+                }
+                run_n += n_path + n_hit;
+                counted = true;
+            }
+        }
+        if (!gone) continue;    // lanes that are left alone wait at the loop's head: no ballot below this line
+        if (!counted) {
+            if (kLds) atomicAdd(&s_cell[cell], 1u);
+            else atomicAdd(&a.out[4 + cell], 1ull);
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {                                   // park, written out: at rest where it is; "did not scatter"
+            a.v[k][ti] = (T)0.0;
+            a.dv[k][ti] = (T)0.0;
+        }
+    }
+    flush_run();
+    __syncthreads();
+    // pcl_sweep::flush_cells, written out, for the reason given in k_absorb_scattered: a further caller changes the older kernels
+    for (int k = threadIdx.x; k < n_cnt; k += kBlock)
+        if (s_cnt[k]) atomicAdd(&a.out[k], (unsigned long long)s_cnt[k]);
+}
+
+struct gabsorb_spec { // a call's arguments, checked; what the kernel compares against
+    gscatter_spec g;            // the geometry, the bands and the first table given, by check_gscatter
+    bool has_p = false, has_om = false;
+    bool draws = false;         // some cell has p > 0 or omega0 < 1: the ids are needed
+    std::vector<double> tables; // p (if given) | omega0 (if given) | the axes' edges (a radius axis: squared) | E edges
+    size_t n_tab() const { return (size_t)has_p + (size_t)has_om; }
+    size_t cells() const { return (size_t)4 + (size_t)g.n_p; }          // the four counts | by cell
+    size_t lds_small() const { return (size_t)g.n_edges * sizeof(double) + 4 * sizeof(uint32_t); }             // the global form's
+    size_t lds_whole() const { return lds_small() + (size_t)g.n_p * (n_tab() * sizeof(double) + sizeof(uint32_t)); }   // the LDS form's
+    bool lds_form() const { return g.n_p <= kGridAbsorbLdsCells && lds_whole() <= kGridAbsorbLdsBytes; }
+    spans out(int64_t *counts, int64_t *by_cell) const { return {{counts, 4}, {by_cell, (size_t)g.n_p}}; }
+};
+
+// Everything PCL_ERR_ARG stands for except the NULL context; nothing is launched or written before this has passed.  The geometry,
+// the bands and the values of a table by check_gscatter itself, handed the first table given: what that call refuses, this one does.
+bool check_gabsorb(int n_axes, const int *coords, const int *n_bins, const double *edges, const double *center, int n_E,
+                   const double *E_edges, const double *p, const double *omega0, const int64_t *counts_out, const int64_t *cells_out,
+                   gabsorb_spec &s) {
+    if (!p && !omega0) return false;
+    if (!check_gscatter(n_axes, coords, n_bins, edges, center, n_E, E_edges, p ? p : omega0, 0, 0.0, counts_out, cells_out, s.g)) return false;
+    s.has_p = p != nullptr; s.has_om = omega0 != nullptr;
+    const size_t n_p = (size_t)s.g.n_p;
+    s.tables.assign(s.g.tables.begin(), s.g.tables.begin() + n_p);      // the first table given
+    for (size_t k = 0; k < n_p; ++k) {
+        if (!(omega0 == nullptr || (omega0[k] >= 0.0 && omega0[k] <= 1.0))) return false;   // (NaN as well)
+        s.draws = s.draws || (p && p[k] > 0.0) || (omega0 && omega0[k] < 1.0);
+    }
+    if (p && omega0) s.tables.insert(s.tables.end(), omega0, omega0 + n_p);
+    s.tables.insert(s.tables.end(), s.g.tables.begin() + n_p, s.g.tables.end());            // the edges
+    return true;
+}
+
+template <typename T>
+int launch_gabsorb(pcl_ctx *ctx, const store_view &v, const gabsorb_spec &s, uint64_t seed, uint32_t pass, const staged &st) {
+    gabsorb_args<T> a{};
+    for (int k = 0; k < 3; ++k) {
+        void *r = nullptr, *vel = nullptr, *dv = nullptr;
+        if ((s.g.rows >> k) & 1) PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_R0 + k, &r));
+        PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_V0 + k, &vel));
+        PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_DV0 + k, &dv));     // (what makes a lazy dv real: an absorbed photon's is written)
+        a.r[k] = static_cast<const T *>(r); a.v[k] = static_cast<T *>(vel); a.dv[k] = static_cast<T *>(dv);
+        a.c[k] = s.g.c[k];
+    }
+    // E is asked for only with energy bands: the pointer costs a wavelength-dependent scatter step its term cache (pcl_shell.hip).
+    void *E = nullptr;
+    if (s.g.n_E > 0) PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_E, &E));
+    a.E = static_cast<const T *>(E); a.kind = st.kind; a.ids = st.ids; a.tables = st.tables; a.out = st.out;
+    a.N = v.N; a.ts = v.ts; a.id_base = st.id_base; a.tile_log = v.tile_log;
+    a.n_axes = s.g.n_axes; a.n_E = s.g.n_E; a.n_edges = s.g.n_edges; a.n_cells = (int)s.g.n_p; a.E_at = s.g.E_at; a.rows = s.g.rows;
+    for (int k = 0; k < s.g.n_axes; ++k) { a.coord[k] = s.g.coord[k]; a.n_bins[k] = s.g.n_bins[k]; a.edge_at[k] = s.g.edge_at[k]; }
+    a.has_p = s.has_p; a.has_om = s.has_om;
+    a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32); a.pass = pass;
+    const bool lds_form = s.lds_form();
+    const size_t lds = lds_form ? s.lds_whole() : s.lds_small();
+    const int64_t grid = balanced_grid(v.N, v.n_cu, resident_per_cu(lds));
+    if (lds_form) hipLaunchKernelGGL((k_absorb_grid<T, true>), dim3((unsigned)grid), dim3(kBlock), lds, v.stream, a);
+    else hipLaunchKernelGGL((k_absorb_grid<T, false>), dim3((unsigned)grid), dim3(kBlock), lds, v.stream, a);
+    return hipGetLastError() == hipSuccess ? PCL_OK : PCL_ERR_HIP;
+}
+
+int absorb_grid(pcl_ctx *ctx, int n_axes, const int *coords_host, const int *n_bins_host, const double *edges_host,
+                const double *center_host, int n_E_bins, const double *E_edges_host, const double *p_host, const double *omega0_host,
+                uint64_t seed, uint32_t pass, int64_t *counts_out_host, int64_t *cells_out_host) {
+    gabsorb_spec s;
+    if (!ctx || !check_gabsorb(n_axes, coords_host, n_bins_host, edges_host, center_host, n_E_bins, E_edges_host, p_host, omega0_host,
+                               counts_out_host, cells_out_host, s))
+        return bad_argument(ctx);
+    const spans out = s.out(counts_out_host, cells_out_host);
+    store_view v;
+    staged st(ctx);
+    PCL_SWEEP_TRY(open_store(ctx, PCL_V0, &v));
+    zero_spans(out);
+    if (v.N <= 0) return PCL_OK;
+    PCL_SWEEP_TRY(stage(st, v, s.cells(), s.tables.data(), s.tables.size(), s.draws));   // the ids only if somebody may draw
+    PCL_SWEEP_TRY(PCL_SWEEP_LAUNCH(v, launch_gabsorb, ctx, v, s, seed, pass, st));
+    return fetch(st, out);
+}
+
+int group_absorb_grid(pcl_group *group, int n_axes, const int *coords_host, const int *n_bins_host, const double *edges_host,
+                      const double *center_host, int n_E_bins, const double *E_edges_host, const double *p_host, const double *omega0_host,
+                      uint64_t seed, uint32_t pass, int64_t *counts_out_host, int64_t *cells_out_host) {
+    gabsorb_spec s;                                                     // the arguments first: a refused call looks at no group
+    if (!check_gabsorb(n_axes, coords_host, n_bins_host, edges_host, center_host, n_E_bins, E_edges_host, p_host, omega0_host,
+                       counts_out_host, cells_out_host, s))
+        return bad_argument(nullptr);
+    std::vector<pcl_ctx *> ctx;
+    PCL_SWEEP_TRY(shards_of(group, ctx));
+    if (ctx.empty()) return bad_argument(nullptr);
+    return sum_shards(ctx, s.out(counts_out_host, cells_out_host), [&](pcl_ctx *one, int64_t *p) {
+        return pcl_step_absorb_grid(one, n_axes, coords_host, n_bins_host, edges_host, center_host, n_E_bins, E_edges_host, p_host,
+                                    omega0_host, seed, pass, p, p + 4);
+    });
+}
+
 } // namespace
 
 extern "C" {
@@ -3098,6 +3360,25 @@ int pcl_group_step_phase_grid(pcl_group *group, int n_laws, const int *kinds_hos
     return guarded([&] {
         return group_phase_grid(group, n_laws, kinds_host, g_host, law_bins_host, mu_host, F_host, n_mixtures, cum_host, n_axes,
                                 coords_host, n_bins_host, edges_host, center_host, mixture_host, outside, c, seed, pass, counts_out_host);
+    });
+}
+
+int pcl_step_absorb_grid(pcl_ctx *ctx, int n_axes, const int *coords_host, const int *n_bins_host, const double *edges_host,
+                         const double *center_host, int n_E_bins, const double *E_edges_host, const double *p_host,
+                         const double *omega0_host, uint64_t seed, uint32_t pass, int64_t *counts_out_host, int64_t *cells_out_host) {
+    return guarded([&] {
+        return absorb_grid(ctx, n_axes, coords_host, n_bins_host, edges_host, center_host, n_E_bins, E_edges_host, p_host, omega0_host, seed,
+                           pass, counts_out_host, cells_out_host);
+    });
+}
+
+int pcl_group_step_absorb_grid(pcl_group *group, int n_axes, const int *coords_host, const int *n_bins_host, const double *edges_host,
+                               const double *center_host, int n_E_bins, const double *E_edges_host, const double *p_host,
+                               const double *omega0_host, uint64_t seed, uint32_t pass, int64_t *counts_out_host,
+                               int64_t *cells_out_host) {
+    return guarded([&] {
+        return group_absorb_grid(group, n_axes, coords_host, n_bins_host, edges_host, center_host, n_E_bins, E_edges_host, p_host,
+                                 omega0_host, seed, pass, counts_out_host, cells_out_host);
     });
 }
 

@@ -2484,7 +2484,8 @@ class GridScatterStep(LayeredScatterStep):
     on through one another (``tally.WriterStep``).  A hit gets a direction uniform on the sphere at speed c and the scatter step's
     mark, ``v = v'``, ``dv = v' - v_old`` -- ``LayeredScatterStep``'s arithmetic line for line, so a ``PhaseFunctionStep`` or
     ``LayeredPhaseStep`` behind this step re-directs its hits about ``v - dv`` and an ``AbsorptionStep`` gives them an ``omega0``; those
-    steps act by radial layer, not by cell -- ``GridPhaseStep`` (light_grid.py) is the phase step that acts by cell.  ``r``, ``dr``, ``E``, ids and kinds are never written.
+    steps act by radial layer, not by cell -- ``GridPhaseStep`` (light_grid.py) is the phase step that acts by cell, ``GridAbsorptionStep``
+    (there, too) the absorption.  ``r``, ``dr``, ``E``, ids and kinds are never written.
 
     After each run ``self.exposed`` and ``self.scattered`` hold the pass's counts and ``self.scattered_by_cell`` an int64 array of
     ``k``'s broadcast shape, global over shards and ranks; ``self.data`` gains the row ``[t, exposed, scattered,
@@ -3203,6 +3204,6 @@ def _merge_shards(comm, rows):
     return got
 
 
-# GridPhaseStep stands in light_grid.py, which builds on this module and hands the class to this module's names at its end
-# (``from physicl_amd.light import *`` and ``phys.light.GridPhaseStep`` find it, whichever of the two modules is imported first).
+# GridPhaseStep and GridAbsorptionStep stand in light_grid.py, which builds on this module and hands the classes to this module's names
+# at its end (``from physicl_amd.light import *`` and ``phys.light.GridPhaseStep`` find them, whichever of the two modules is imported first).
 from . import light_grid  # noqa: E402,F401

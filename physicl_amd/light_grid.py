@@ -1,6 +1,7 @@
-"""The light steps that act by cell of a grid behind the scatter: ``GridPhaseStep``, the phase law by grid cell, and the numpy
+"""The light steps that act by cell of a grid behind the scatter: ``GridPhaseStep``, the phase law by grid cell, and
+``GridAbsorptionStep``, absorption along the path and at the interaction by grid cell with the heating field, each with the numpy
 restatement of its sweep.  Built on light.py -- ``LayeredPhaseStep``'s laws, draws and turn, ``PositionGridMeasureStep``'s cells --
-and re-exported there: ``phys.light.GridPhaseStep``."""
+and re-exported there: ``phys.light.GridPhaseStep``, ``phys.light.GridAbsorptionStep``."""
 import numpy as np
 
 from . import light, tally
@@ -151,3 +152,171 @@ class GridPhaseStep(light.LayeredPhaseStep):
 
 
 light.GridPhaseStep = GridPhaseStep                      # phys.light.GridPhaseStep, and ``from physicl_amd.light import *``
+
+
+# ---------------------------------------------------------------------------------------------- absorption on a grid of cells
+_GRID_ABSORB_WORDS = (27, 28)                                 # along the path, at the interaction (the header lists the words taken)
+
+
+def _check_grid_absorb(k, omega0, axes, edges, center, E_edges):
+    """(k and omega0, each None or a float64 array of the grid's shape (+ (B,) with E_edges), axes, edges, centre, energy edges or
+    None) of a GridAbsorptionStep, or ValueError for everything pcl_step_absorb_grid would refuse.  A single number is broadcast."""
+    from ._hip import ABSORB_GRID_MAX_BANDS, ABSORB_GRID_MAX_CELLS      # (the header's limits: one place)
+    axes, edges, center = light._check_grid(axes, edges, center)
+    if E_edges is not None:
+        E_edges = tally.check_edges("E_edges", E_edges, ABSORB_GRID_MAX_BANDS)
+    if k is None and omega0 is None:
+        raise ValueError("k and omega0 are both None: give an absorption coefficient, a single-scattering albedo, or both")
+    want = tuple(len(e) - 1 for e in edges) + (() if E_edges is None else (len(E_edges) - 1,))
+    cells = int(np.prod(want))
+    out = []
+    for name, x in (("k", k), ("omega0", omega0)):
+        if x is None:
+            out.append(None)
+            continue
+        try:
+            xa = np.array(x, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("%s must be a number, or numbers per cell of the grid (and energy band)" % name) from None
+        if xa.shape not in ((), want):
+            raise ValueError("%s must be one number or have the shape %r -- %s -- got %r" % (
+                name, want, "the grid's cells" + ("" if E_edges is None else " by bands of E_edges"), xa.shape))
+        if name == "k" and not np.all(np.isfinite(xa) & (xa >= 0.0)):             # (False for NaN as well)
+            raise ValueError("k must be finite and not negative, got %r" % (x,))
+        if name == "omega0" and not np.all((xa >= 0.0) & (xa <= 1.0)):
+            raise ValueError("omega0 must lie in [0, 1], got %r" % (x,))
+        if cells > ABSORB_GRID_MAX_CELLS:
+            raise ValueError("%s: %s are %d cells, at most %d are supported" % (name, " x ".join(str(n) for n in want), cells,
+                                                                                ABSORB_GRID_MAX_CELLS))
+        out.append(np.ascontiguousarray(np.broadcast_to(xa, want)))
+    return out[0], out[1], axes, edges, center, E_edges
+
+
+def _grid_absorb(r, v, dv, E, photon, ids, p, omega0, axes, edges, center, E_edges, seed, n_pass, dtype=np.float64):
+    """What pcl_step_absorb_grid makes of (n, 3) float64 positions, velocities and last velocity changes, the energies, who is a
+    photon and the particles' ids, with numpy -- the rule of include/physicl_hip.h: no transcendental function, no division and no
+    square root, so everything is the device's bit for bit.  ``p`` and ``omega0``: None, or one value per cell of the grid (row-major
+    in the order of ``axes``) and band, not both None.  What is written is zero, in any ``dtype``.  A dict: ``v, dv`` the new state
+    (float64 arrays; rows that are not absorbed are the arguments'), the boolean masks ``exposed``, ``interacted``, ``absorbed_path``,
+    ``absorbed_hit`` and ``absorbed`` (either), ``cell`` (int64: cell of the grid times B' plus the band, of every exposed photon, -1
+    for none) and the tally ``absorbed_by_cell`` (int64, the grid's shape, with a last dimension of B bands if ``E_edges`` is given)."""
+    r, v, dv = (np.array(a, dtype=np.float64).reshape(-1, 3) for a in (r, v, dv))
+    n = len(v)
+    photon = np.asarray(photon, dtype=bool).reshape(-1)
+    ids = np.asarray(ids).reshape(-1)
+    edges = [np.asarray(e, dtype=np.float64) for e in edges]
+    shape = tuple(len(e) - 1 for e in edges) + (() if E_edges is None else (len(E_edges) - 1,))
+    p, omega0 = (None if t is None else np.asarray(t, dtype=np.float64).reshape(-1) for t in (p, omega0))
+    cell = np.full(n, -1, dtype=np.int64)
+    with np.errstate(invalid="ignore", over="ignore"):        # the cell and the band: light._scatter_grid's lines
+        at = np.flatnonzero(~light._at_rest(v) & photon)
+        ok, g = light._cell_of_positions(r[at], axes, edges, np.asarray(center, dtype=np.float64))
+        at, g = at[ok], g[ok]
+        if E_edges is not None:                                # NaN and under/overflow: in no band
+            Ee = np.asarray(E_edges, dtype=np.float64)
+            band = light._bin_of(np.asarray(E, dtype=np.float64).reshape(-1)[at], Ee)
+            at, g = at[band >= 0], g[band >= 0] * (len(Ee) - 1) + band[band >= 0]
+    cell[at] = g
+    exposed = cell >= 0
+    gone_path, gone_hit = np.zeros(n, dtype=bool), np.zeros(n, dtype=bool)
+    interacted = exposed & light._scattered(dv, photon) if omega0 is not None else np.zeros(n, dtype=bool)
+    if p is not None:
+        draws = at[p[g] > 0.0]                                 # a transparent cell draws nothing
+        u = light._philox_block(ids[draws], seed, n_pass, _GRID_ABSORB_WORDS[0])[0]
+        gone_path[draws[u < p[cell[draws]]]] = True
+    if omega0 is not None:
+        draws = np.flatnonzero(interacted & ~gone_path)
+        draws = draws[omega0[cell[draws]] < 1.0]               # a conservative cell draws nothing
+        u = light._philox_block(ids[draws], seed, n_pass, _GRID_ABSORB_WORDS[1])[0]
+        gone_hit[draws[~(u < omega0[cell[draws]])]] = True     # AbsorptionStep's sense of the draw
+    absorbed = gone_path | gone_hit
+    v[absorbed], dv[absorbed] = np.zeros(3, dtype=dtype), np.zeros(3, dtype=dtype)        # parked
+    cells = np.bincount(cell[absorbed], minlength=int(np.prod(shape))).astype(np.int64).reshape(shape)
+    return {"v": v, "dv": dv, "exposed": exposed, "interacted": interacted, "absorbed_path": gone_path, "absorbed_hit": gone_hit,
+            "absorbed": absorbed, "cell": cell, "absorbed_by_cell": cells}
+
+
+class GridAbsorptionStep(tally.WriterStep):
+    """Absorption and heating rates by cell of a grid (not in the reference): ``PathAbsorptionStep`` (Beer-Lambert along the move) and
+    ``AbsorptionStep`` (the single-scattering albedo at an interaction) with ``PositionGridMeasureStep``'s cells in place of the
+    concentric layers, both in ONE sweep -- a smoke plume or a water-vapour column of finite width, droplets that absorb only where the
+    clouds of a broken cloud field are -- and the product a 3-D radiative-transfer run exists for: the absorbed photons by cell and
+    colour, the heating field.  It stands where those two steps stand: BEHIND the scatter and phase steps of a pass
+    (``GridScatterStep``, ``GridPhaseStep``), in front of the ground, the walls and a ``RecycleStep``.
+
+    * ``axes``, ``edges``, ``center``: ``PositionGridMeasureStep``'s arguments by its rules, limits and error messages (at most 1024
+      bins per axis).  A photon's cell is the cell that step would count it in; cells are row-major in the order of ``axes``.
+    * ``E_edges``: ``GridScatterStep``'s argument by its rule: ``B + 1`` energy edges, ``numpy.histogram``'s bins, at most 1024 bands.
+      Without it E is neither read nor asked for.
+    * ``k``: the absorption coefficient per unit length (code units), finite and not negative: one number, or an array of the grid's
+      shape (``+ (B,)`` with ``E_edges``).  Per pass the host makes ``p = -numpy.expm1(-k * (c * dt))`` (``light._path_probability``)
+      and the device only ever sees ``p``.
+    * ``omega0``: the single-scattering albedo, every value in ``[0, 1]``, with the same shapes as ``k``.
+    * At least one of ``k`` and ``omega0`` must be given; cells times bands may be at most ``2**20``.
+
+    Every moving photon with a cell (and a band) is EXPOSED -- a photon at rest (``-0.0`` counts as 0, a NaN moves), a plain ``Object``
+    and a photon in no cell or no band are skipped -- and, with ``omega0``, INTERACTED iff its ``dv`` is not zero (the scatter steps'
+    mark).  With ``k`` and ``p > 0`` in its cell it is absorbed along the path iff ``u < p``; otherwise, if it interacted and ``omega0
+    < 1`` there, it is absorbed at the interaction iff ``not (u < omega0)`` (``AbsorptionStep``'s sense of the draw).  The two ``u`` come
+    from Philox blocks keyed by ``sim.seed``, the photon's id and the step's pass counter ``_n_pass``, in counter words no other kernel
+    uses (27 and 28); several ``GridAbsorptionStep``s in one pass count on through one another (``tally.WriterStep``), so their draws
+    are independent.  An absorbed photon is parked as the older steps park it, ``v = 0`` and ``dv = 0``; a photon that is not absorbed
+    is not written at all; ``r``, ``dr``, ``E``, ids and kinds are never written.  With ``omega0`` the step reads the ``dv`` rule and
+    raises ``ValueError`` under ``cl_on=False``, as ``AbsorptionStep`` does; with ``k`` alone it works there too.
+
+    After each run ``self.exposed``, ``self.interacted`` (0 without ``omega0``), ``self.absorbed_path``, ``self.absorbed_hit`` and
+    ``self.absorbed`` (their sum) hold the pass's counts and ``self.absorbed_by_cell`` an int64 array of the tables' shape, both kinds
+    together: the heating field.  All are global over shards and ranks; ``self.data`` gains the row ``[t, exposed, interacted,
+    absorbed_path, absorbed_hit, absorbed_by_cell]``; ``out_fn`` takes the rows at the end.  The rule is written out in
+    include/physicl_hip.h (pcl_step_absorb_grid); ``_grid_absorb`` restates every bit of it with numpy.
+
+    Cost: up to 4096 cells, and while the edges, the tables given (8 B a cell each) and the tallies (4 B a cell) stay within 64 KiB,
+    tables and tallies live in LDS -- 16 x 16 x 16 cells with one table, not with two; above that the kernel reads the tables from
+    device memory and adds what it absorbed there.  Either way the tables go up and the tallies come back every pass.
+
+    One launch per light step: the K-passes-per-launch kernels cannot absorb a photon between two of their passes, and
+    ``sim.launch_note`` says so.  On host-resident objects (``step.run(sim)`` outside a device loop) the same state is made with
+    numpy, the ids being the places in the object list."""
+    _STREAM = "absorb_grid"                              # (words 27 and 28: nobody else's)
+    _NOTE = "one launch per light step: a GridAbsorptionStep absorbs photons by grid cell and band behind every pass, which the " \
+            "K-passes-per-launch kernels cannot carry"
+
+    def __init__(self, axes, edges, k=None, omega0=None, center=(0, 0, 0), E_edges=None, out_fn=None):
+        MeasureStep.__init__(self, out_fn)
+        self.k, self.omega0, self.axes, self.edges, self.center, self.E_edges = _check_grid_absorb(k, omega0, axes, edges, center, E_edges)
+        self.exposed = self.interacted = self.absorbed_path = self.absorbed_hit = self.absorbed = 0
+        self.absorbed_by_cell = np.zeros((self.k if self.k is not None else self.omega0).shape, dtype=np.int64)
+        self._pass = 0                                   # runs so far; the sweep is handed _n_pass (tally.WriterStep)
+
+    def _record_pass(self, sim, exposed, interacted, absorbed_path, absorbed_hit, cells):
+        self.exposed, self.interacted = int(exposed), int(interacted)
+        self.absorbed_path, self.absorbed_hit = int(absorbed_path), int(absorbed_hit)
+        self.absorbed = self.absorbed_path + self.absorbed_hit
+        self.absorbed_by_cell = np.array(cells, dtype=np.int64).reshape(self.absorbed_by_cell.shape)
+        self.data.append(tally.object_row([tally._snap(sim.t), self.exposed, self.interacted, self.absorbed_path, self.absorbed_hit,
+                                           self.absorbed_by_cell.copy()]))
+
+    def _refuse(self, sim):
+        if self.omega0 is not None:
+            light._dv_rule_refusal(sim, "GridAbsorptionStep with omega0", "who interacted in this pass")
+
+    def _prepare(self, sim, on_host):                    # p of this pass's dt; a dt that is refused raises here
+        if self.k is None:
+            return None
+        return light._path_probability(self.k, light._c_h_literals()[0], np.asarray(sim.dt) if on_host else sim._dt_code())
+
+    def _sweep(self, sim, p):
+        counts, cells = sim._dev.absorb_grid(p, self.omega0, self.axes, self.edges, self.center, self.E_edges, sim.seed, self._n_pass)
+        return [np.asarray(counts, dtype=np.int64), np.asarray(cells, dtype=np.int64)]
+
+    def _host_sweep(self, objs, ids, seed, p):
+        E, photon = tally.photon_energies(objs, light.PhotonObject)
+        new = _grid_absorb(tally.vec3(objs, "r"), tally.vec3(objs, "v"), tally.vec3(objs, "dv"), E, photon, ids, p, self.omega0, self.axes,
+                           self.edges, self.center, self.E_edges, seed, self._n_pass)
+        return new, new["absorbed"], (new["exposed"].sum(), new["interacted"].sum(), new["absorbed_path"].sum(),
+                                      new["absorbed_hit"].sum(), new["absorbed_by_cell"])
+
+    terminate = tally.TallyStep.terminate                # (a row holds arrays: written as the tally steps write theirs, as plain lists)
+
+
+light.GridAbsorptionStep = GridAbsorptionStep            # phys.light.GridAbsorptionStep, and ``from physicl_amd.light import *``

@@ -324,6 +324,9 @@ class MultiDevice:
     def phase_grid(self, *a, **kw):
         return self._sum_parts("phase_grid", *a, **kw)
 
+    def absorb_grid(self, *a, **kw):
+        return self._sum_parts("absorb_grid", *a, **kw)
+
     def plane_energies(self, plane, n_hint=None):
         return self._concat(self._each(lambda s: s.plane_energies(plane)))      # (a shard does not know its share of the hint)
 
