@@ -6,7 +6,7 @@ examples (n(r) = 2.5e25 m^-3 * exp(-(|r| - 6371 km) / 8.6 km)) with photons that
                                                [--ground [ALBEDO]] [--phase rayleigh | hg:G | isotropic] [--omega0 W | W1,W2,...]
                                                [--cloud LO,HI[,G]] [--cloud-tau TAU] [--cloud-field NX,NY,NZ:EXTENT:TAU] [--cloud-phase G] [--cloud-absorb OMEGA0[,K]] [--box periodic | mirror | open] [--recycle [TOP]] [--gas LO,HI,K[,EMIN,EMAX]] [--blue-sky]
                                                [--reemit [TG[,TA]]] [--ocean N] [--ground-bands E1,E2,...:a1,a2,...[:s1,...]]
-                                               [--camera X,Y,Z:NX,NY,NZ:RADIUS:FOV_DEG:PIXELS]
+                                               [--camera X,Y,Z:NX,NY,NZ:RADIUS:FOV_DEG:PIXELS] [--flux-map LEVEL[,LEVEL...]:HALF:N]
 
 default: a point source at (6371 km, 0, 0) emitting isotropically; ``--cone``: a 0.3 rad cone pointing up (+x) from a 1 km disc;
 ``--beam-down``: a 10 km gaussian beam entering from 100 km above the surface along -x; ``--default``: the same step list from
@@ -101,6 +101,11 @@ view of FOV_DEG degrees to either side and PIXELS x PIXELS pixels, e.g. ``--came
 from 100 km above the source.  Every pass tallies the photons that went through the disc from the front, by the direction they came
 from; ``through`` and ``seen`` summed over the passes and a coarse text rendering of the exposure ``step.image`` are printed.  One launch
 per light step, as with ``--shells``.
+``--flux-map LEVEL[,LEVEL...]:HALF:N`` records the irradiance field: a PlaneFluxMapStep with the horizontal planes LEVEL metres above the
+ground (x is the vertical; increasing) and N x N columns over HALF metres to either side of the source's vertical in y and z, in front of
+the ground and the walls.  The up and down counts per level summed over the passes are printed, and beside ``--cloud-field`` the downward
+map at the lowest level, so the shadow of the cloudy columns is visible: try ``--cloud-field 8,8,8:40000:4 --box periodic --beam-down
+--flux-map 5000,35000:20000:8``.  One launch per light step.
 """
 import os
 import sys
@@ -242,6 +247,16 @@ if "--camera" in argv:
     except ValueError:
         sys.exit("--camera X,Y,Z:NX,NY,NZ:RADIUS:FOV_DEG:PIXELS: a position and a normal (metres, any length), a radius in metres, the half "
                  "angle of the field of view in degrees and the pixels per side")
+flux_map = None
+if "--flux-map" in argv:
+    at = argv.index("--flux-map")
+    try:
+        lv, half_width, n_col = (argv.pop(at + 1) if at + 1 < len(argv) else "").split(":")
+        flux_map = ([float(x) for x in lv.split(",")], float(half_width), int(n_col))
+        if not flux_map[1] > 0.0 or flux_map[2] < 1:
+            raise ValueError
+    except ValueError:
+        sys.exit("--flux-map LEVEL[,LEVEL...]:HALF:N: altitudes in metres above the ground (increasing), the map's half width in metres and the columns per side")
 CLOUD_WEIGHTS = [[1, 0], [0.1, 0.9], [1, 0]]                  # below the cloud, in it, above it: (Rayleigh, Henyey-Greenstein)
 args = [a for a in argv if not a.startswith("--")]
 n = int(float(args[0])) if len(args) > 0 else 100_000_000
@@ -328,6 +343,11 @@ def run(ground):
     if camera is not None:                                     # before the ground, as the shells: it sees the incoming move
         eye = light.DetectorMeasureStep(None, **camera)        # (a malformed camera is a ValueError here, before anything runs)
         sim.add_step("camera", eye)
+    irradiance = None
+    if flux_map is not None:                                   # before the ground and the walls, as the shells: it sees the incoming move
+        sides = np.linspace(-flux_map[1], flux_map[1], flux_map[2] + 1)
+        irradiance = light.PlaneFluxMapStep(None, "x", R + np.array(flux_map[0]), [sides, sides])
+        sim.add_step("flux_map", irradiance)
     glow = red = None
     if reemit is not None:                                     # Planck tables between 3 and 100 micrometres: the ground's, the gas's
         infrared = [light.generate_photons_bulk(1, min=light.E_from_wavelength(100e-6), max=light.E_from_wavelength(3e-6), T=T, bins=256)
@@ -365,7 +385,7 @@ def run(ground):
     sim.join()
     if sim.error is not None:
         raise sim.error
-    return sim, signs, shells, profile, image, tally, floor, angles, medium, lamp, vapour, eye, glow, sea, droplets, broken, walls, inside, heat
+    return sim, signs, shells, profile, image, tally, floor, angles, medium, lamp, vapour, eye, glow, sea, droplets, broken, walls, inside, heat, irradiance
 
 
 bare_top = None
@@ -375,7 +395,7 @@ if ground is not None and "--shells" in sys.argv:              # the same run wi
     print("without the ground: %d photons x %d steps in %.2f s" % (n, len(bare[0].ts), bare[0].run_time))
     bare[0].close(download=False)
     del bare
-sim, signs, shells, profile, image, tally, floor, angles, medium, lamp, vapour, eye, glow, sea, droplets, broken, walls, inside, heat = run(ground)
+sim, signs, shells, profile, image, tally, floor, angles, medium, lamp, vapour, eye, glow, sea, droplets, broken, walls, inside, heat, irradiance = run(ground)
 steps = len(sim.ts)
 print("source:", source)
 print("%d photons x %d steps in %.2f s  ->  %.3g particle-steps/s" % (n, steps, sim.run_time, n * steps / sim.run_time))
@@ -417,6 +437,15 @@ if heat is not None:
     print("  absorbed by column, the heating field (summed over x, rows: y, columns: z):")
     for line in heating.sum(axis=0):
         print("   " + " ".join("%8d" % x for x in line))
+if irradiance is not None:
+    up, down = (np.sum([row[k] for row in irradiance.data], axis=0) for k in (2, 3))
+    print("flux through the planes %s m above the ground over %d passes: up %s, down %s; %d of the crossings inside the map of %d x %d columns, %g km wide" % (
+        flux_map[0], len(irradiance.data), up.tolist(), down.tolist(), int(irradiance.up_map.sum() + irradiance.down_map.sum()), flux_map[2], flux_map[2],
+        2e-3 * flux_map[1]))
+    if broken is not None:
+        print("  downward through the lowest level by column (rows: y, columns: z): the cloudy columns' shadow")
+        for line in irradiance.down_map[0, 0]:
+            print("   " + " ".join("%8d" % x for x in line))
 if walls is not None:
     crossed = np.sum([row[3] for row in walls.data], axis=0)
     print("box walls (%s in y and z, %g km apart): moving %d in the first pass and %d in the last; crossed [[x], [y below, above], [z below, above]] %s "

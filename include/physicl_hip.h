@@ -1392,6 +1392,57 @@ int pcl_step_absorb_grid(pcl_ctx *ctx, int n_axes, const int *coords_host, const
                          int64_t *counts_out_host /* [4]: exposed, interacted, absorbed along the path, at the interaction */,
                          int64_t *cells_out_host /* [G * B'] */);
 
+/* The irradiance field: up and down fluxes through the planes normal to one axis, as maps (PlaneFluxMapStep).  ``axis`` a = 0, 1, 2
+ * (x, y, z) is the normal; the transverse axes (u, v) are the remaining two in x, y, z order: 0 gives (y, z), 1 gives (x, z), 2 gives
+ * (x, y).  In ONE read-only sweep of the resident store every particle whose last move changed its side of a level is counted, by
+ * level and direction, and sorted by where its straight move met the plane into n_u x n_v columns and -- with bands -- by energy, as
+ * int64 cells that add across devices and ranks like every other counter row.  Called where pcl_step_shell_crossings of the ground's
+ * radius is called: in front of the sweeps that rewrite r and dr of the move (the ground, the refracting interface, the walls).
+ * All arithmetic is fp64, every operation rounded once, unfused, in the order written; an fp32 store's values are widened first
+ * (exact).  No division and no square root is taken anywhere, so numpy restates every cell exactly.  Per slot, plain Objects included,
+ * S = n_levels, B' = max(n_E_bins, 1):
+ *   now = r_a;  m = dr_a;  prev = now - m;
+ *   for each level X:   up  iff  prev < X and now >= X;   down  iff  prev >= X and now < X
+ *                       -- on the plane is above; a NaN crosses nothing.  Every change of side is counted exactly once, so
+ *                       cumsum(up - down) per level is the change of the population at or above it.  As for the shells, only the end
+ *                       points of the move are looked at.
+ *   counts_out_host[0][s] += 1 for up, counts_out_host[1][s] += 1 for down: every particle that crossed, photon or not.
+ *   for each level the particle crossed (a move may cross several: it is tallied at each of them, with that level's G):
+ *     G = |X - prev|;  D = |m|;
+ *     for t in (u, v):  p_t = r_t - dr_t;  H_t = p_t*D + dr_t*G     (the crossing point times D)
+ *     bin b of t  iff  e_b*D <= H_t < e_(b+1)*D, the last bin closed.  Rounded products are monotone in b: a binary search with one
+ *     multiply per probe.
+ *     in no cell  iff  D or an H_t is not finite, or H_t lies outside [e_0*D, e_n*D] on either axis.
+ *   Without bands (n_E_bins == 0, E_edges_host is not looked at, E is neither read nor asked for) the band is 0.  With bands only a
+ *   PHOTON (plain Objects carry no energy) with E_0 <= E <= E_nE has a band, as numpy.histogram(E, bins=E_edges) finds it; a plain
+ *   Object, an energy outside the bands or NaN is counted and lands in no cell.
+ *   maps_out_host[dir][s][band][iu][iv] += 1, dir 0 = up, 1 = down; C order.
+ * levels_host: n_levels in 1..PCL_PLANE_FLUX_MAX_LEVELS finite, strictly increasing doubles.  u_edges_host / v_edges_host /
+ * E_edges_host: n + 1 finite, strictly increasing doubles; n_u, n_v in 1..PCL_PLANE_FLUX_MAX_BINS, n_E_bins in
+ * 0..PCL_PLANE_FLUX_MAX_BANDS, C = 2 * S * B' * n_u * n_v at most PCL_PLANE_FLUX_MAX_CELLS.
+ * The levels and the three edge tables are always staged in LDS, and so are a workgroup's 2 S uint32 counts.  A workgroup's maps are
+ * uint32 cells in LDS too, flushed once at the end, while
+ *     C <= PCL_PLANE_FLUX_LDS_CELLS   and   8 * (S + n_u + 1 + n_v + 1 + (B ? B + 1 : 0))  +  4 * (2 S + C)  <=  PCL_PLANE_FLUX_LDS_BYTES
+ * (B = n_E_bins); above that the crossing lanes add to the device block with 64-bit atomics.  PCL_PLANE_FLUX_LDS_CELLS is the
+ * switch-over of pcl_step_scatter_grid and pcl_step_absorb_grid; it was not tuned for this sweep.  Per slot r_a and dr_a are read
+ * first; only a lane that crossed reads r and dr of the transverse axes, and E with bands.
+ * PCL_ERR_ARG (a NULL pointer, an axis outside 0..2, levels or edges that are not finite or not strictly increasing, a level, bin,
+ * band or cell count outside its limits) is returned before the store is looked at -- by the group's entry point before the group is
+ * --, with the outputs untouched; PCL_ERR_STATE without a store; an empty store answers zeros without a launch.  Host pointers; one
+ * device allocation per call, handed back on every way out; synchronises once, with the one copy of the results.  The store is seen
+ * dense with dr real (pcl_store_field_ptr); E is looked at only with bands, at pcl_step_detector_image's price.  pcl_last_error() is
+ * generic, as for pcl_step_shell_crossings, whose source file these two entry points share. */
+#define PCL_PLANE_FLUX_MAX_LEVELS 16
+#define PCL_PLANE_FLUX_MAX_BINS 1024       /* per transverse axis */
+#define PCL_PLANE_FLUX_MAX_BANDS 1024
+#define PCL_PLANE_FLUX_MAX_CELLS (1 << 20) /* 2 * S * B' * n_u * n_v */
+#define PCL_PLANE_FLUX_LDS_CELLS 4096
+#define PCL_PLANE_FLUX_LDS_BYTES 65536
+int pcl_step_plane_flux(pcl_ctx *ctx, int axis, int n_levels, const double *levels_host, const double *u_edges_host, int n_u,
+                        const double *v_edges_host, int n_v, const double *E_edges_host, int n_E_bins /* NULL, 0: no bands */,
+                        int64_t *counts_out_host /* [2][S]: up, down */,
+                        int64_t *maps_out_host /* [2][S][B'][n_u][n_v] */);
+
 /* ---- Device groups: several GPUs from ONE process ---------------------------------------------------------------
  * The reference is a single process with one simulation thread (physicl/__init__.py:400-432, 501-524); this is how
  * a host written against this ABI uses a node's GPUs the same way, without one process per GPU.  A group owns one
@@ -1530,6 +1581,11 @@ int pcl_group_step_absorb_grid(pcl_group *group, int n_axes, const int *coords_h
                                const double *center_host, int n_E_bins, const double *E_edges_host, const double *p_host,
                                const double *omega0_host, uint64_t seed, uint32_t pass, int64_t *counts_out_host,
                                int64_t *cells_out_host);
+/* pcl_step_plane_flux on every shard (side by side), the counts and the maps summed over the group's devices; the arguments are
+ * checked once for the group, before the group is looked at.  Every shard brings its maps back: 8 B a cell per shard and call */
+int pcl_group_step_plane_flux(pcl_group *group, int axis, int n_levels, const double *levels_host, const double *u_edges_host, int n_u,
+                              const double *v_edges_host, int n_v, const double *E_edges_host, int n_E_bins, int64_t *counts_out_host,
+                              int64_t *maps_out_host);
 
 /* ---------------------------------------------------------------- the counters' collective (one process per GPU)
  * The path shards by global index with no data-path exchange; the only global quantities are the int64

@@ -41,6 +41,9 @@ SCATTER_LAYERED_MAX_LAYERS, SCATTER_LAYERED_MAX_BANDS, SCATTER_LAYERED_MAX_CELLS
 SCATTER_GRID_MAX_BANDS, SCATTER_GRID_MAX_CELLS = 1024, 1 << 20                # PCL_SCATTER_GRID_MAX_BANDS, PCL_SCATTER_GRID_MAX_CELLS
 PHASE_GRID_MAX_MIXTURES, PHASE_GRID_MAX_CELLS, PHASE_GRID_ALONE, PHASE_GRID_LDS_BYTES = 64, 1 << 20, 255, 65536   # PCL_PHASE_GRID_MAX_MIXTURES ...
 ABSORB_GRID_MAX_BANDS, ABSORB_GRID_MAX_CELLS, ABSORB_GRID_LDS_CELLS, ABSORB_GRID_LDS_BYTES = 1024, 1 << 20, 4096, 65536   # PCL_ABSORB_GRID_MAX_BANDS ...
+PLANE_FLUX_AXES = {"x": 0, "y": 1, "z": 2}                                   # the normal; (u, v) are the remaining two in x, y, z order
+PLANE_FLUX_MAX_LEVELS, PLANE_FLUX_MAX_BINS, PLANE_FLUX_MAX_BANDS, PLANE_FLUX_MAX_CELLS = 16, 1024, 1024, 1 << 20   # PCL_PLANE_FLUX_MAX_LEVELS ...
+PLANE_FLUX_LDS_CELLS, PLANE_FLUX_LDS_BYTES = 4096, 65536                     # PCL_PLANE_FLUX_LDS_CELLS, PCL_PLANE_FLUX_LDS_BYTES
 WALL_MODES = {None: 0, "periodic": 1, "mirror": 2, "open": 3}               # PCL_WALL_NONE, PCL_WALL_PERIODIC, PCL_WALL_MIRROR, PCL_WALL_OPEN
 REEMIT_LAWS = {"isotropic": 0, "lambertian": 1}                              # the flags of pcl_step_reemit_parked's lambertian_host
 PROF_NEWTON, PROF_SCATTER, PROF_DELETE_MASK, PROF_COMPACT, PROF_COUNTERS, PROF_FUSED, PROF_MULTI, PROF_ONEPASS, \
@@ -221,6 +224,8 @@ _PROTOTYPES = {
     "pcl_group_step_phase_grid": [_vp, c_int, _vp, _vp, _vp, _vp, _vp, c_int, _vp, c_int, _vp, _vp, _vp, _vp, _vp, c_int, c_double, c_uint64,
                                   c_uint32, _vp],
     "pcl_group_step_absorb_grid": [_vp, c_int, _vp, _vp, _vp, _vp, c_int, _vp, _vp, _vp, c_uint64, c_uint32, _vp, _vp],
+    "pcl_step_plane_flux": [_vp, c_int, c_int, _vp, _vp, c_int, _vp, c_int, _vp, c_int, _vp, _vp],
+    "pcl_group_step_plane_flux": [_vp, c_int, c_int, _vp, _vp, c_int, _vp, c_int, _vp, c_int, _vp, _vp],
 }
 EXPORTS = sorted(list(_PROTOTYPES) + ["pcl_last_error"])
 
@@ -727,6 +732,37 @@ def _absorb_grid(entry, handle, p, omega0, axes, edges, center, E_edges, seed, n
     check(entry(handle, len(coords), coords.ctypes.data, n_bins.ctypes.data, ed.ctypes.data, ptr(ce), B, ptr(Ee), ptr(tabs[0]), ptr(tabs[1]),
                 int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_pass) & 0xFFFFFFFF, counts.ctypes.data, cells.ctypes.data))
     return counts, cells
+
+
+def plane_flux_lds_bytes(n_levels, n_u, n_v, n_bands, n_cells):
+    """The LDS the LDS form of a pcl_step_plane_flux call asks for, by the header's formula: S levels, n_u x n_v columns, B bands (0:
+    none) and C = 2 S max(B, 1) n_u n_v cells."""
+    S, B = int(n_levels), int(n_bands)
+    return 8 * (S + int(n_u) + 1 + int(n_v) + 1 + (B + 1 if B else 0)) + 4 * (2 * S + int(n_cells))
+
+
+def plane_flux_lds_form(n_levels, n_u, n_v, n_bands):
+    """Whether a pcl_step_plane_flux call keeps its maps in LDS (the header's bound) or adds to them in device memory."""
+    cells = 2 * int(n_levels) * max(int(n_bands), 1) * int(n_u) * int(n_v)
+    return cells <= PLANE_FLUX_LDS_CELLS and plane_flux_lds_bytes(n_levels, n_u, n_v, n_bands, cells) <= PLANE_FLUX_LDS_BYTES
+
+
+def _plane_flux(entry, handle, axis, levels, edges, E_edges=None):
+    """One call of pcl_step_plane_flux / pcl_group_step_plane_flux: (counts int64[2, S] -- [0]: up, [1]: down --, maps int64[2, S,
+    max(bands, 1), n_u, n_v]).  ``axis``: "x", "y", "z" (or the header's numbers), the normal; ``edges``: the bin edges of the two
+    transverse axes, (u, v); the levels and the edges go over as given."""
+    lv = np.ascontiguousarray(levels, dtype=np.float64).reshape(-1)
+    per_axis = [np.ascontiguousarray(e, dtype=np.float64).reshape(-1) for e in edges]
+    if len(per_axis) != 2:
+        raise ValueError("two sequences of edges, for u and for v: got %d" % len(per_axis))
+    ue, ve = per_axis
+    ee = None if E_edges is None else np.ascontiguousarray(E_edges, dtype=np.float64).reshape(-1)
+    S, nu, nv, nE = len(lv), len(ue) - 1, len(ve) - 1, 0 if ee is None else len(ee) - 1
+    counts = np.zeros((2, S), dtype=np.int64)
+    maps = np.zeros((2, S, max(nE, 1), max(nu, 0), max(nv, 0)), dtype=np.int64)
+    check(entry(handle, int(PLANE_FLUX_AXES.get(axis, axis)), S, lv.ctypes.data, ue.ctypes.data, nu, ve.ctypes.data, nv,
+                None if ee is None else ee.ctypes.data, nE, counts.ctypes.data, maps.ctypes.data))
+    return counts, maps
 
 
 def _scatter(sc, required=False, lazy=False, empty_expr=b""):
@@ -1387,6 +1423,12 @@ class Device:
         grid's shape (+ bands))``.  ``n_pass``: the caller's own pass counter."""
         return _absorb_grid(self.lib.pcl_step_absorb_grid, self.ctx, p, omega0, axes, edges, center, E_edges, seed, n_pass)
 
+    def plane_flux(self, axis, levels, edges, E_edges=None):
+        """What passed through the planes ``axis = levels[s]`` in the last move, by direction and by the column of ``edges`` (the
+        two transverse axes' bin edges) in which the straight move met the plane -- and by band of ``E_edges`` --, in one read-only
+        sweep (pcl_step_plane_flux): ``(counts int64[2, S] = [up, down], maps int64[2, S, max(bands, 1), n_u, n_v])``."""
+        return _plane_flux(self.lib.pcl_step_plane_flux, self.ctx, axis, levels, edges, E_edges)
+
     def box_walls(self, modes, lo, hi):
         """The walls of the box ``[lo, hi]``, per axis ``"periodic"``, ``"mirror"``, ``"open"`` or None: every moving photon outside on
         an axis with a wall is handed back in through the other side, folded back at the wall (an odd number of bounces turns ``v``,
@@ -1547,6 +1589,10 @@ class DeviceGroup:
         if mixture is None:
             mixture = np.zeros([len(np.reshape(e, -1)) - 1 for e in edges], dtype=np.int64)
         return _phase_grid(self.lib.pcl_group_step_phase_grid, self.g, laws, cum, axes, edges, center, mixture, outside, c, seed, n_pass)
+
+    def plane_flux(self, axis, levels, edges, E_edges=None):
+        """``Device.plane_flux`` summed over the group's contexts (pcl_group_step_plane_flux)."""
+        return _plane_flux(self.lib.pcl_group_step_plane_flux, self.g, axis, levels, edges, E_edges)
 
     def absorb_grid(self, p, omega0, axes, edges, center=None, E_edges=None, seed=0, n_pass=0):
         """``Device.absorb_grid`` on every context of the group, the tallies summed (pcl_group_step_absorb_grid)."""

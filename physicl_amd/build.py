@@ -74,6 +74,14 @@ MORE = [
     # k_scatter_grid's budget (eight waves per SIMD): this kernel does less arithmetic than that one
     dict(_sweep("pcl_step_absorb_grid", "pcl_group_step_absorb_grid", "k_absorb_grid", count=4), src=_c("pcl_surface.hip"), vgprs=64),
 ]
+# Sweeps added since, a row each, shaped as MORE's plus ``trip``: (test file, test name) of the case that takes the sweep past one trip
+# of its grid and compares every tally, so the row names its own.  tests/test_plane_flux_build_cpu.py reads every expectation, the trip
+# case included, from the row: the next sweep is one more row here, no further table and no further file to hold against.
+ROWS = [
+    # the shell unit's budget (eight waves per SIMD)
+    dict(_sweep("pcl_step_plane_flux", "pcl_group_step_plane_flux", "k_plane_flux", count=4), src=_c("pcl_shell.hip"), vgprs=64,
+         trip=("test_plane_flux_trips_gpu.py", "test_the_sweep_past_one_trip")),
+]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -ffp-contract=off: the reference's kernels must be evaluated unfused (bit-exact parity)

@@ -25,6 +25,9 @@
 //                          no square root); one ballot + popcount each for the two counts; the few lanes that are seen add to
 //                          their image cell with a 64-bit atomic straight on the device block -- an aperture is small, so there
 //                          is no histogram in LDS and no flush, and the image may be large.
+//
+// And at the end of the unit the crossing tally of horizontal levels by column (PlaneFluxMapStep), k_plane_flux<T, lds>, described
+// where it stands.
 #include "pcl_sweep.h"
 
 namespace {
@@ -378,6 +381,196 @@ int group_detector_image(pcl_group *group, const double *position_host, const do
     });
 }
 
+// ---------------------------------------------------------------------------------------------- the flux maps of planes
+// Up and down fluxes through the planes normal to one axis, resolved by column (PlaneFluxMapStep): the shells' change of side,
+// counted exactly once, and the detector's hit point without a division, sorted into the cells of a map.
+//
+//   k_plane_flux<T, lds>   one grid-stride sweep of the tiled slab for ALL levels of a call: per slot r and dr of the normal axis
+//                          (16 B in fp64) against every level (LDS), one ballot + popcount per level and direction for the counts;
+//                          only the lanes that crossed load r and dr of the two transverse axes (and E with bands), make the hit
+//                          point times D per level and look it up in the edges times D (LDS, binary searches, no division);
+//                          lds: the maps are workgroup-private uint32 cells in LDS, flushed at the end; otherwise the lanes add to
+//                          the device block with 64-bit atomics and only the 2S counts stay in LDS.
+// The LDS form's switch-over is the siblings' (k_scatter_grid, k_absorb_grid): it was not tuned for this kernel.
+constexpr int kPlaneFluxLdsCells = PCL_PLANE_FLUX_LDS_CELLS;
+constexpr size_t kPlaneFluxLdsBytes = PCL_PLANE_FLUX_LDS_BYTES;
+
+template <typename T>
+struct pflux_args {
+    const T *ra, *dra;           // r and dr along the normal
+    const T *rt[2], *drt[2];     // r and dr along u and v
+    const T *E;                  // NULL without bands
+    const unsigned char *kind;   // NULL: every particle is a photon
+    const double *tables;        // levels (S) | u edges (n_u + 1) | v edges (n_v + 1) | E edges (n_E + 1, if any), device
+    unsigned long long *out;     // counts [2][S] | maps [2][S][max(n_E, 1)][n_u][n_v], device, zeroed by the entry point
+    int64_t N, ts;               // particles, tile stride of the slab (elements)
+    int tile_log;                // log2 of the tile length
+    int S, n_u, n_v, n_E;
+};
+
+template <typename T, bool kLds>
+__global__ void __launch_bounds__(kBlock) k_plane_flux(pflux_args<T> a) {
+    extern __shared__ double s_flux[];                                 // tables | counts | maps (LDS form)
+    const int S = a.S, nu = a.n_u, nv = a.n_v, nE = a.n_E, nB = nE ? nE : 1;
+    const int n_tab = S + (nu + 1) + (nv + 1) + (nE ? nE + 1 : 0);
+    const int n_map = 2 * S * nB * nu * nv;                            // at most PCL_PLANE_FLUX_MAX_CELLS
+    const int n_cnt = 2 * S + (kLds ? n_map : 0);
+    const double *s_lev = s_flux, *s_u = s_lev + S, *s_v = s_u + (nu + 1), *s_E = s_v + (nv + 1);
+    uint32_t *s_cnt = reinterpret_cast<uint32_t *>(s_flux + n_tab);
+    uint32_t *s_map = s_cnt + 2 * S;
+    for (int k = threadIdx.x; k < n_tab; k += kBlock) s_flux[k] = a.tables[k];
+    for (int k = threadIdx.x; k < n_cnt; k += kBlock) s_cnt[k] = 0;    // (the maps follow the counts)
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    // whole waves run the same number of trips (the ballots below need every lane of the wave inside the loop)
+    const int64_t n_round = (a.N + 63) / 64 * 64;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n_round; i += stride) {
+        const bool in = i < a.N;
+        const int64_t ti = tile_index(i, a.tile_log, a.ts);
+        double now = 0.0, m = 0.0;
+        if (in) {
+            now = (double)a.ra[ti];                                    // fp32 widens exactly
+            m = (double)a.dra[ti];
+        }
+        const double prev = now - m;
+        uint32_t crossed = 0;   // bit s: up through level s in the last move, bit 16 + s: down (NaN: neither)
+        for (int s = 0; s < S; ++s) {
+            const double X = s_lev[s];
+            const bool up = in && prev < X && now >= X, dn = in && prev >= X && now < X;      // on the plane is above
+            const uint32_t n_up = (uint32_t)__popcll(__ballot(up)), n_dn = (uint32_t)__popcll(__ballot(dn));
+            if (lane == 0 && n_up) atomicAdd(&s_cnt[s], n_up);
+            if (lane == 0 && n_dn) atomicAdd(&s_cnt[S + s], n_dn);
+            crossed |= (up ? 1u << s : 0u) | (dn ? 0x10000u << s : 0u);
+        }
+        if (!crossed) continue; // lanes that crossed nothing wait at the loop's head: no ballot below this line
+        int band = 0;
+        if (nE) {
+            if (a.kind ? a.kind[i] == 0 : false) continue;             // plain Objects carry no energy: counted, in no cell
+            const double e = (double)a.E[ti];
+            if (!(e >= s_E[0] && e <= s_E[nE])) continue;              // NaN and under/overflow: counted, in no cell
+            band = bin_of(s_E, nE, e);
+        }
+        const double D = fabs(m);
+        if (!(D < INFINITY)) continue;                                 // an infinite move: counted, in no cell
+        const double du = (double)a.drt[0][ti], dv = (double)a.drt[1][ti];
+        const double pu = (double)a.rt[0][ti] - du, pv = (double)a.rt[1][ti] - dv;            // where the move began
+        // unfused, in this order (the library is built with -ffp-contract=off)
+        for (uint32_t x = crossed; x; x &= x - 1) {
+            const int bit = __ffs(x) - 1, s = bit & 15;
+            const double G = fabs(s_lev[s] - prev);
+            const double Hu = pu * D + du * G, Hv = pv * D + dv * G;   // the crossing point times D
+            // p_t + dr_t*G/D in bin b iff e_b*D <= H_t < e_(b+1)*D: one multiply per probe, rounded products are monotone in b
+            if (!(fabs(Hu) < INFINITY && fabs(Hv) < INFINITY)) continue;
+            if (!(Hu >= s_u[0] * D && Hu <= s_u[nu] * D && Hv >= s_v[0] * D && Hv <= s_v[nv] * D)) continue;
+            const int iu = bin_of(s_u, nu, Hu, D), iv = bin_of(s_v, nv, Hv, D);
+            // band, iu and iv come from bin_of alone, which answers [0, n - 1] for n bins; s < S and bit >> 4 is 0 or 1: the cell
+            // lies in [0, n_map), the block behind the 2S counts -- in LDS (the launch asked for it) or on the device
+            const int cell = ((((bit >> 4) * S + s) * nB + band) * nu + iu) * nv + iv;
+            if (kLds) atomicAdd(&s_map[cell], 1u);
+            else atomicAdd(&a.out[2 * S + cell], 1ull);
+        }
+    }
+    __syncthreads();
+    flush_cells(s_cnt, a.out, n_cnt);
+}
+
+struct pflux_spec { // a call's arguments, checked; what the kernel compares against
+    int axis = 0, S = 0, n_u = 0, n_v = 0, n_E = 0;
+    std::vector<double> tables; // levels | u edges | v edges | E edges
+    size_t n_cnt() const { return (size_t)2 * S; }
+    size_t n_map() const { return (size_t)2 * S * (n_E > 0 ? n_E : 1) * n_u * n_v; }
+    size_t cells() const { return n_cnt() + n_map(); }
+    size_t lds_small() const { return tables.size() * sizeof(double) + n_cnt() * sizeof(uint32_t); }          // the global form's
+    size_t lds_whole() const { return lds_small() + n_map() * sizeof(uint32_t); }                               // the LDS form's
+    bool lds_form() const { return n_map() <= (size_t)kPlaneFluxLdsCells && lds_whole() <= kPlaneFluxLdsBytes; }
+    spans out(int64_t *counts, int64_t *maps) const { return {{counts, n_cnt()}, {maps, n_map()}}; }
+};
+
+// Everything PCL_ERR_ARG stands for except the NULL context; nothing is launched or written before this has passed.
+bool check_pflux(int axis, int n_levels, const double *levels, const double *u_edges, int n_u, const double *v_edges, int n_v,
+                 const double *E_edges, int n_E, const int64_t *counts_out, const int64_t *maps_out, pflux_spec &s) {
+    if (!levels || !u_edges || !v_edges || !counts_out || !maps_out) return false;
+    if (axis < 0 || axis > 2 || n_levels < 1 || n_levels > PCL_PLANE_FLUX_MAX_LEVELS) return false;
+    if (n_u < 1 || n_u > PCL_PLANE_FLUX_MAX_BINS || n_v < 1 || n_v > PCL_PLANE_FLUX_MAX_BINS) return false;
+    if (n_E < 0 || n_E > PCL_PLANE_FLUX_MAX_BANDS || (n_E > 0 && !E_edges)) return false;
+    if ((int64_t)2 * n_levels * (n_E > 0 ? n_E : 1) * n_u * n_v > PCL_PLANE_FLUX_MAX_CELLS) return false;
+    for (int k = 0; k < n_levels; ++k) {
+        if (!std::isfinite(levels[k]) || (k > 0 && !(levels[k] > levels[k - 1]))) return false;
+        s.tables.push_back(levels[k]);
+    }
+    if (!check_edges(u_edges, n_u, kEdgePlain, &s.tables) || !check_edges(v_edges, n_v, kEdgePlain, &s.tables)) return false;
+    if (n_E > 0 && !check_edges(E_edges, n_E, kEdgePlain, &s.tables)) return false;
+    s.axis = axis; s.S = n_levels; s.n_u = n_u; s.n_v = n_v; s.n_E = n_E;
+    return true;
+}
+
+template <typename T>
+int launch_pflux(pcl_ctx *ctx, const store_view &v, const pflux_spec &s, const void *E, const staged &st) {
+    pflux_args<T> a{};
+    const int tu = s.axis == 0 ? 1 : 0, tv = s.axis == 2 ? 1 : 2;      // the remaining two axes, in x, y, z order
+    const int axes[3] = {s.axis, tu, tv};
+    for (int k = 0; k < 3; ++k) {
+        void *r = nullptr, *dr = nullptr;
+        PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_R0 + axes[k], &r));
+        PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_DR0 + axes[k], &dr));
+        if (k == 0) {
+            a.ra = static_cast<const T *>(r); a.dra = static_cast<const T *>(dr);
+        } else {
+            a.rt[k - 1] = static_cast<const T *>(r); a.drt[k - 1] = static_cast<const T *>(dr);
+        }
+    }
+    a.E = static_cast<const T *>(E); a.kind = st.kind; a.tables = st.tables; a.out = st.out;
+    a.N = v.N; a.ts = v.ts; a.tile_log = v.tile_log;
+    a.S = s.S; a.n_u = s.n_u; a.n_v = s.n_v; a.n_E = s.n_E;
+    const bool lds_form = s.lds_form();
+    const size_t lds = lds_form ? s.lds_whole() : s.lds_small();       // at most 64 KiB either way
+    const int64_t grid = balanced_grid(v.N, v.n_cu, resident_per_cu(lds));
+    if (lds_form) hipLaunchKernelGGL((k_plane_flux<T, true>), dim3((unsigned)grid), dim3(kBlock), lds, v.stream, a);
+    else hipLaunchKernelGGL((k_plane_flux<T, false>), dim3((unsigned)grid), dim3(kBlock), lds, v.stream, a);
+    return hipGetLastError() == hipSuccess ? PCL_OK : PCL_ERR_HIP;
+}
+
+int plane_flux(pcl_ctx *ctx, int axis, int n_levels, const double *levels_host, const double *u_edges_host, int n_u,
+               const double *v_edges_host, int n_v, const double *E_edges_host, int n_E_bins, int64_t *counts_out_host,
+               int64_t *maps_out_host) {
+    pflux_spec s;
+    if (!ctx || !check_pflux(axis, n_levels, levels_host, u_edges_host, n_u, v_edges_host, n_v, E_edges_host, n_E_bins, counts_out_host,
+                             maps_out_host, s))
+        return bad_argument(ctx);
+    // E is asked for only with bands: the pointer costs a wavelength-dependent scatter step its term cache.
+    const spans out = s.out(counts_out_host, maps_out_host);
+    store_view v;
+    staged st(ctx);
+    void *E = nullptr;
+    PCL_SWEEP_TRY(open_store(ctx, PCL_R0, &v));
+    if (s.n_E) PCL_SWEEP_TRY(pcl_store_field_ptr(ctx, PCL_E, &E));
+    if (v.N <= 0) {
+        zero_spans(out);
+        return PCL_OK;
+    }
+    // the kinds go along when energies are binned and the store holds a plain Object; nothing is drawn: no ids
+    PCL_SWEEP_TRY(stage(st, v, s.cells(), s.tables.data(), s.tables.size(), false, s.n_E > 0));
+    PCL_SWEEP_TRY(PCL_SWEEP_LAUNCH(v, launch_pflux, ctx, v, s, E, st));
+    return fetch(st, out);
+}
+
+int group_plane_flux(pcl_group *group, int axis, int n_levels, const double *levels_host, const double *u_edges_host, int n_u,
+                     const double *v_edges_host, int n_v, const double *E_edges_host, int n_E_bins, int64_t *counts_out_host,
+                     int64_t *maps_out_host) {
+    pflux_spec s;                                                       // the arguments first: a refused call looks at no group
+    if (!check_pflux(axis, n_levels, levels_host, u_edges_host, n_u, v_edges_host, n_v, E_edges_host, n_E_bins, counts_out_host,
+                     maps_out_host, s))
+        return bad_argument(nullptr);
+    std::vector<pcl_ctx *> ctx;
+    PCL_SWEEP_TRY(shards_of(group, ctx));
+    if (ctx.empty()) return bad_argument(nullptr);
+    return sum_shards(ctx, s.out(counts_out_host, maps_out_host), [&](pcl_ctx *one, int64_t *p) {
+        return pcl_step_plane_flux(one, axis, n_levels, levels_host, u_edges_host, n_u, v_edges_host, n_v, E_edges_host, n_E_bins, p,
+                                   p + s.n_cnt());
+    });
+}
+
 } // namespace
 
 extern "C" {
@@ -415,6 +608,24 @@ int pcl_group_step_detector_image(pcl_group *group, const double *position_host,
     return guarded([&] {
         return group_detector_image(group, position_host, frame_host, radius, x_edges_host, nx, y_edges_host, ny, E_edges_host, n_E_bins,
                                     counts_out_host, image_out_host);
+    });
+}
+
+int pcl_step_plane_flux(pcl_ctx *ctx, int axis, int n_levels, const double *levels_host, const double *u_edges_host, int n_u,
+                        const double *v_edges_host, int n_v, const double *E_edges_host, int n_E_bins, int64_t *counts_out_host,
+                        int64_t *maps_out_host) {
+    return guarded([&] {
+        return plane_flux(ctx, axis, n_levels, levels_host, u_edges_host, n_u, v_edges_host, n_v, E_edges_host, n_E_bins, counts_out_host,
+                          maps_out_host);
+    });
+}
+
+int pcl_group_step_plane_flux(pcl_group *group, int axis, int n_levels, const double *levels_host, const double *u_edges_host, int n_u,
+                              const double *v_edges_host, int n_v, const double *E_edges_host, int n_E_bins, int64_t *counts_out_host,
+                              int64_t *maps_out_host) {
+    return guarded([&] {
+        return group_plane_flux(group, axis, n_levels, levels_host, u_edges_host, n_u, v_edges_host, n_v, E_edges_host, n_E_bins,
+                                counts_out_host, maps_out_host);
     });
 }
 

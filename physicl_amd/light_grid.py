@@ -1,7 +1,8 @@
 """The light steps that act by cell of a grid behind the scatter: ``GridPhaseStep``, the phase law by grid cell, and
-``GridAbsorptionStep``, absorption along the path and at the interaction by grid cell with the heating field, each with the numpy
-restatement of its sweep.  Built on light.py -- ``LayeredPhaseStep``'s laws, draws and turn, ``PositionGridMeasureStep``'s cells --
-and re-exported there: ``phys.light.GridPhaseStep``, ``phys.light.GridAbsorptionStep``."""
+``GridAbsorptionStep``, absorption along the path and at the interaction by grid cell with the heating field -- and the tally that goes
+with them, ``PlaneFluxMapStep``, the up and down fluxes through planes as maps --, each with the numpy restatement of its sweep.  Built on
+light.py -- ``LayeredPhaseStep``'s laws, draws and turn, ``PositionGridMeasureStep``'s cells -- and re-exported there:
+``phys.light.GridPhaseStep``, ``phys.light.GridAbsorptionStep``, ``phys.light.PlaneFluxMapStep``."""
 import numpy as np
 
 from . import light, tally
@@ -320,3 +321,167 @@ class GridAbsorptionStep(tally.WriterStep):
 
 
 light.GridAbsorptionStep = GridAbsorptionStep            # phys.light.GridAbsorptionStep, and ``from physicl_amd.light import *``
+
+
+# ---------------------------------------------------------------------------------------------- flux maps of planes
+_PLANE_AXES = {"x": (0, 1, 2), "y": (1, 0, 2), "z": (2, 0, 1)}  # the normal, then (u, v): the remaining two in x, y, z order
+
+
+def _check_plane_flux(axis, levels, edges, E_bins=None):
+    """(axis, levels, [u edges, v edges], band edges or None) of a PlaneFluxMapStep as float64 arrays, or ValueError for everything
+    pcl_step_plane_flux would refuse."""
+    from ._hip import PLANE_FLUX_MAX_BANDS, PLANE_FLUX_MAX_BINS, PLANE_FLUX_MAX_CELLS, PLANE_FLUX_MAX_LEVELS      # (the header's limits: one place)
+    if not isinstance(axis, str) or axis not in _PLANE_AXES:
+        raise ValueError('axis must be one of "x", "y", "z" (the normal of the planes), got %r' % (axis,))
+    try:
+        levels = np.array(levels, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("levels must be a 1-D sequence of numbers (coordinates along %s)" % axis) from None
+    if levels.ndim != 1 or not 1 <= len(levels) <= PLANE_FLUX_MAX_LEVELS:
+        raise ValueError("levels must be a 1-D sequence of 1 to %d coordinates, got shape %r" % (PLANE_FLUX_MAX_LEVELS, levels.shape))
+    if not np.all(np.isfinite(levels)) or not np.all(np.diff(levels) > 0):
+        raise ValueError("levels must be finite and strictly increasing, got %r" % (levels,))
+    try:
+        n_seq = len(edges)
+    except TypeError:
+        n_seq = -1
+    if n_seq != 2:
+        raise ValueError("edges must be two sequences of bin edges, for u and for v (the axes other than %s, in x, y, z order)" % axis)
+    names = ["xyz"[k] for k in _PLANE_AXES[axis][1:]]
+    edges = [tally.check_edges("edges[%d] (%s)" % (k, names[k]), edges[k], PLANE_FLUX_MAX_BINS) for k in range(2)]
+    E_bins = None if E_bins is None else tally.check_edges("E_bins", E_bins, PLANE_FLUX_MAX_BANDS)
+    S, B, n_u, n_v = len(levels), 0 if E_bins is None else len(E_bins) - 1, len(edges[0]) - 1, len(edges[1]) - 1
+    cells = 2 * S * max(B, 1) * n_u * n_v
+    if cells > PLANE_FLUX_MAX_CELLS:
+        raise ValueError("2 directions x %d levels x %d bands x %d x %d bins are %d map cells, at most %d are supported"
+                         % (S, max(B, 1), n_u, n_v, cells, PLANE_FLUX_MAX_CELLS))
+    return axis, np.ascontiguousarray(levels), edges, E_bins
+
+
+def _bin_scaled(e, H, D):
+    """pcl_sweep::bin_of(e, n, H, D) for arrays: the bin b with ``e_b * D <= H < e_(b+1) * D``, the last one closed -- the device's
+    binary search, probe by probe (the caller has checked that H is inside)."""
+    lo, hi = np.zeros(len(H), dtype=np.int64), np.full(len(H), len(e) - 1, dtype=np.int64)
+    while True:
+        open_ = hi - lo > 1
+        if not open_.any():
+            return lo
+        mid = (lo + hi) >> 1
+        with np.errstate(invalid="ignore", over="ignore"):
+            below = e[mid] * D <= H
+        lo, hi = np.where(open_ & below, mid, lo), np.where(open_ & ~below, mid, hi)
+
+
+def _plane_flux_maps(r, dr, E, photon, axis, levels, edges, E_edges=None):
+    """What pcl_step_plane_flux answers, from (n, 3) float64 positions and last moves, the energies and who is a photon, with numpy --
+    every operation the device's operation, one rounding each (include/physicl_hip.h): (counts int64[2, S], maps int64[2, S, max(bands,
+    1), n_u, n_v]), [0] up, [1] down."""
+    r, dr = np.asarray(r, dtype=np.float64).reshape(-1, 3), np.asarray(dr, dtype=np.float64).reshape(-1, 3)
+    a, tu, tv = _PLANE_AXES[axis]
+    levels = np.asarray(levels, dtype=np.float64).reshape(-1)
+    ue, ve = (np.asarray(e, dtype=np.float64).reshape(-1) for e in edges)
+    S, n_u, n_v, nE = len(levels), len(ue) - 1, len(ve) - 1, 0 if E_edges is None else len(E_edges) - 1
+    nB = max(nE, 1)
+    with np.errstate(invalid="ignore", over="ignore"):
+        now, m = r[:, a], dr[:, a]
+        prev = now - m
+        cross = np.stack([(prev < levels[:, None]) & (now >= levels[:, None]),          # up: on the plane is above
+                          (prev >= levels[:, None]) & (now < levels[:, None])])         # down; NaN: neither
+    counts = cross.sum(axis=2).astype(np.int64)
+    hit = np.flatnonzero(cross.any(axis=(0, 1)))                                        # the maps look at these only
+    n_map = 2 * S * nB * n_u * n_v
+    maps = np.zeros(n_map, dtype=np.int64)
+    band = np.zeros(len(hit), dtype=np.int64)
+    if nE:                                                        # numpy.histogram's bins; what is no photon or outside the bands: in no cell
+        e, v = np.asarray(E_edges, dtype=np.float64), np.asarray(E, dtype=np.float64).reshape(-1)[hit]
+        with np.errstate(invalid="ignore"):
+            ok = (v >= e[0]) & (v <= e[-1]) & np.asarray(photon, dtype=bool).reshape(-1)[hit]
+        hit, band = hit[ok], np.clip(np.searchsorted(e, v, side="right") - 1, 0, nE - 1)[ok]
+    with np.errstate(invalid="ignore", over="ignore"):
+        D = np.abs(m[hit])
+        ok = D < np.inf
+        hit, band, D = hit[ok], band[ok], D[ok]
+        du, dv = dr[hit, tu], dr[hit, tv]
+        pu, pv = r[hit, tu] - du, r[hit, tv] - dv                                       # where the move began
+        for s in range(S):
+            for d in range(2):
+                w = np.flatnonzero(cross[d, s, hit])
+                G = np.abs(levels[s] - prev[hit[w]])
+                Hu, Hv = pu[w] * D[w] + du[w] * G, pv[w] * D[w] + dv[w] * G             # the crossing point times D
+                ok = (np.abs(Hu) < np.inf) & (np.abs(Hv) < np.inf) & (Hu >= ue[0] * D[w]) & (Hu <= ue[-1] * D[w]) \
+                    & (Hv >= ve[0] * D[w]) & (Hv <= ve[-1] * D[w])
+                w, Hu, Hv = w[ok], Hu[ok], Hv[ok]
+                iu, iv = _bin_scaled(ue, Hu, D[w]), _bin_scaled(ve, Hv, D[w])
+                maps += np.bincount((((d * S + s) * nB + band[w]) * n_u + iu) * n_v + iv, minlength=n_map)
+    return counts, maps.reshape(2, S, nB, n_u, n_v)
+
+
+class PlaneFluxMapStep(tally.TallyStep):
+    """The irradiance field (not in the reference): what passed up and down through horizontal levels in the last move, resolved by
+    column -- the shadow a cloud field throws on the ground beside it, the reflected flux above a broken deck.  ``axis`` (``"x"``,
+    ``"y"`` or ``"z"``) is the normal of the planes, ``levels`` 1 to 16 finite, strictly increasing coordinates along it (code units),
+    and ``edges`` the bin edges of the two transverse axes ``(u, v)`` -- the remaining two in x, y, z order: ``"x"`` gives (y, z), ``"y"``
+    gives (x, z), ``"z"`` gives (x, y) --, at most 1024 bins each.  With ``E_bins`` (band edges in the unit E is stored in, at most 1024
+    bands) only photons whose energy lies inside the bands reach the maps, one plane per band as ``numpy.histogram`` bins them; a plain
+    ``Object`` or another energy is counted and lands in no cell.  ``2 * S * max(B, 1) * n_u * n_v`` may be at most ``2**20``.
+
+    Every run records the row ``[t, N, up, down]`` (no ``N`` with ``measure_n=False``), ``up[s]`` / ``down[s]`` the particles whose last
+    move took them up / down through ``levels[s]``, int64 arrays of ``len(levels)``; with ``frames=True`` the row goes on with the pass's
+    ``up_map`` and ``down_map``, each int64 ``[S][max(B, 1)][n_u][n_v]``.  ``step.up`` and ``step.down`` are the last pass's counts;
+    ``step.up_map`` and ``step.down_map`` are exposures, the sum over all passes so far, as ``DetectorMeasureStep.image`` is.
+
+    A crossing is a change of side between the end points of the move, a particle exactly on the plane being above: up iff ``prev < X
+    <= now``, down iff ``now < X <= prev``, with ``prev = r_a - dr_a`` in float64; a NaN crosses nothing.  Every change of side is
+    counted exactly once, so ``cumsum(up - down)`` per level is the change of the population at or above it.  The column is where the
+    straight move met the plane, compared without a division as ``e_b * D <= H < e_(b+1) * D`` with ``D = |dr_a|``, ``G = |X - prev|``
+    and ``H_t = (r_t - dr_t) * D + dr_t * G``, the last bin closed; a photon that crosses several levels in one move is tallied at each
+    of them.  A crossing whose ``D`` or ``H`` is not finite, or whose point lies outside the edges, is counted and lands in no cell.  No
+    division and no square root is taken anywhere, so numpy restates every cell exactly (``light_grid._plane_flux_maps``); the rule is
+    written out in include/physicl_hip.h (pcl_step_plane_flux).
+
+    The step reads ``r`` and ``dr`` of the last move, so it stands IN FRONT of the steps that rewrite them -- the ground and the
+    refracting interface, which fly the rest of the move along the new direction, and the walls --, where a
+    ``ShellCrossingMeasureStep`` of the ground's radius stands.
+
+    The tally is made on the device in one read-only sweep of the resident store and adds, so sharded runs all-reduce ``[N, counts,
+    maps]`` in one collective per pass.  Cost: up to 4096 cells the maps are tallied in the workgroups' local memory and the sweep costs
+    what a one-shell ``ShellCrossingMeasureStep`` costs; above that the crossing photons add to device memory with 64-bit atomics, which
+    serialise where many photons cross into few cells in one pass (CHANGELOG.md has the times).  The maps come back from the device every pass (8 B a cell), and on the library's own
+    communicator, which carries 2048 values a call, a ``2**20``-cell map is 513 calls per pass -- keep the map small where ranks are
+    many, or hand the simulation a communicator that takes the payload whole.  A flux needs every pass, which the K-passes-per-launch
+    kernels cannot carry: a loop with this step runs one launch per light step, as with ``ShellCrossingMeasureStep``, and
+    ``sim.launch_note`` says so.  E is asked for only with bands.  On host-resident objects (hence under ``cl_on=False``) the same row
+    is made with numpy; the step draws nothing and works with every ``rng=`` setting."""
+    _fuse_role = None
+    _NOTE = "one launch per light step: a PlaneFluxMapStep tallies the last move of every pass, which the " \
+            "K-passes-per-launch kernels cannot carry"
+
+    def __init__(self, out_fn, axis, levels, edges, E_bins=None, frames=False, measure_n=True):
+        MeasureStep.__init__(self, out_fn)
+        self.axis, self.levels, self.edges, self.E_bins = _check_plane_flux(axis, levels, edges, E_bins)
+        self.frames, self.measure_n = bool(frames), measure_n
+        shape = (len(self.levels), 1 if self.E_bins is None else len(self.E_bins) - 1, len(self.edges[0]) - 1, len(self.edges[1]) - 1)
+        self.up_map, self.down_map = np.zeros(shape, dtype=np.int64), np.zeros(shape, dtype=np.int64)
+        self.up, self.down = np.zeros(shape[0], dtype=np.int64), np.zeros(shape[0], dtype=np.int64)
+
+    def _device_run(self, sim):
+        if getattr(sim, "launch_note", self._NOTE) is None and sim._k_wanted() > 1:      # (a device run only: the host path says nothing)
+            sim.launch_note = self._NOTE
+        tally.TallyStep._device_run(self, sim)
+
+    def _sweep(self, dev):
+        return list(dev.plane_flux(self.axis, self.levels, self.edges, self.E_bins))
+
+    def _host_parts(self, objs):
+        return list(_plane_flux_maps(tally.vec3(objs, "r"), tally.vec3(objs, "dr"), *tally.photon_energies(objs, light.PhotonObject),
+                                     self.axis, self.levels, self.edges, self.E_bins))
+
+    def _cells(self, parts):                           # (counts, maps), global: the exposures go on
+        counts, maps = (np.asarray(x, dtype=np.int64) for x in parts)
+        maps = maps.reshape((2,) + self.up_map.shape)
+        self.up, self.down = counts.reshape(2, -1)[0].copy(), counts.reshape(2, -1)[1].copy()
+        self.up_map, self.down_map = self.up_map + maps[0], self.down_map + maps[1]
+        return [self.up.copy(), self.down.copy()] + ([maps[0].copy(), maps[1].copy()] if self.frames else [])
+
+
+light.PlaneFluxMapStep = PlaneFluxMapStep                # phys.light.PlaneFluxMapStep, and ``from physicl_amd.light import *``

@@ -279,6 +279,10 @@ class MultiDevice:
         parts = self._each(lambda s: s.detector_image(position, frame, radius, x_edges, y_edges, E_edges))
         return tuple(self._sum(list(part)) for part in zip(*parts))                 # (counts, image), each summed over the shards
 
+    def plane_flux(self, axis, levels, edges, E_edges=None):
+        parts = self._each(lambda s: s.plane_flux(axis, levels, edges, E_edges))
+        return tuple(self._sum(list(part)) for part in zip(*parts))                 # (counts, maps), each summed over the shards
+
     def _sum_parts(self, name, *a, **kw):
         """``name`` on every shard, the answers -- a count, or a tuple of counts and tallies -- added up position by position
         (a tally that was not asked for stays None; ids are global, so every shard writes its own photons)."""

@@ -11,7 +11,7 @@ name, so one that moved between units is compared with itself.  Per kernel the r
 the instruction lines must be the same multiset (the scheduler may swap neighbours when a helper moves into a header, so not
 the same sequence).  A kernel that only the new tree has is listed as new with its metadata (a unit that gained a sweep: the
 kernels it had must still be the code they were) and must be a sweep this tree's build describes (``build.ADDONS``, ``build.LATER``,
-``build.MORE``); one
+``build.MORE``, ``build.ROWS``); one
 that only the old tree has counts as a difference.  Exit status 1 if any kernel differs or a new one is not described.
 """
 import argparse
@@ -28,7 +28,7 @@ sys.path.insert(0, ROOT)
 from physicl_amd import build  # noqa: E402
 
 CORE = os.path.basename(build.CORE["src"])
-DESCRIBED = [s["kernel"] for u in build.ADDONS for s in u["sweeps"]] + [s["kernel"] for s in build.LATER + build.MORE]  # every sweep this tree's build describes
+DESCRIBED = [s["kernel"] for u in build.ADDONS for s in u["sweeps"]] + [s["kernel"] for s in build.LATER + build.MORE + build.ROWS]  # every sweep this tree's build describes
 META = ["vgpr_count", "sgpr_count", "group_segment_fixed_size", "private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count"]
 
 
@@ -97,7 +97,7 @@ def main():
             print("%-18s %-44s %5d instructions  new: %s" % (u, dem_short(name), sum(i1.values()), m1))
         if not any(re.match(r"%s\b" % k, dem_short(name)) for k in DESCRIBED):
             bad += 1
-            print("    not described in physicl_amd/build.py (ADDONS, LATER, MORE)")
+            print("    not described in physicl_amd/build.py (ADDONS, LATER, MORE, ROWS)")
     for name in sorted(set(old) & set(new), key=lambda k: (new[k][0], k)):
         (u0, m0, i0), (u, m1, i1) = old[name], new[name]
         same_m, same_i = m0 == m1, i0 == i1
